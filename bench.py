@@ -2,7 +2,11 @@
 """bench.py — images/sec of Pipeline.recognize() on synthetic 768x768 RGB batches (BASELINE.json
 metric; workload = configs[3]: full pipeline, batch 32 x 768x768, scale=2, one MI355X per rank).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the headline loop's last timed step returned (rank 0's boxes, words per page and texts) as
+DIR/<name>.npy; pages and weights are seeded, so the same arguments give the same inputs on every run and two builds can
+be compared output for output.
 
 N > 1 without a torchrun environment: bench.py re-launches itself as
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` (and
@@ -295,6 +299,32 @@ def fast_mode_leg(ctx, pipe, step, timed, args, world, out_default, pages, oracl
         ctx.set_split_mode(args.split)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs DIR: what the headline path returned in its last timed step (Pipeline.recognize_device: per page a list
+    of (text, box)) as .npy arrays, so that two builds can be compared output for output on identical seeded inputs.
+      boxes.npy            (words, 4, 2) every box in page order, in input-image pixels (the dtype the pipeline returned)
+      words_per_page.npy   (pages,) float64: how many of those boxes belong to each page
+      text_codepoints.npy  (words, longest) float64: the Unicode code points of each word's text, -1 after its end"""
+    words = [(t, np.asarray(b)) for g in out for t, b in g]
+    dtype = np.float64 if any(b.dtype == np.float64 for _, b in words) else np.float32
+    width = max((len(t) for t, _ in words), default=0)
+    codes = np.full((len(words), width), -1, np.float64)
+    for i, (t, _) in enumerate(words):
+        codes[i, :len(t)] = [ord(c) for c in t]
+    arrays = {"boxes": np.array([b for _, b in words], dtype).reshape(-1, 4, 2),
+              "words_per_page": np.array([len(g) for g in out], np.float64),
+              "text_codepoints": codes}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def compact_line(res):
     """The ONE stdout line: the contract's keys, `config`, a trimmed `roofline`, `cpu_baseline`, and one number per extra leg --
     short enough that the driver's record holds it whole.  Everything else goes to stderr / gpurun_out/bench_full.json."""
@@ -426,7 +456,11 @@ def main(argv=None, env=None):
                     help="keep the HIP-event profiler on for the WHOLE process (headline loop included) and report the "
                          "per-launch averages over every launch: the numbers a rocprofv3 --stats / --pmc run of the "
                          "same command must agree with (scripts/profile_final.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the headline path computed in its last timed step to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         respawn_under_torchrun(args, env)
@@ -530,6 +564,8 @@ def main(argv=None, env=None):
     # ---- headline: profiler off ----------------------------------------------------------------------
     dt, out = timed(step, args.steps)
     n_words = sum(len(g) for g in out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # ---- the same K steps with the HIP-event profiler on: stage times + roofline of the dominant kernel --
     fold_process_profile()
     ctx.profile_reset()

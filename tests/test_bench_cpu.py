@@ -328,3 +328,39 @@ def test_bench_main_at_world_8_the_cfg5_job_shape(pages, blocks, capfd):
     line = json.loads(lines[0])
     assert line["n_gpus"] == 8 and line["ranks_seen"] == 8 and "crnn_ms_per_crop" in line["config"]
     assert line["legs_images_per_s"]["cfg5_sharded"] > 0 and len(lines[0]) < 6000   # the driver's record holds it whole
+
+
+def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the headline path's result of its last timed step as .npy arrays (float32 / float64), here from
+    the mocked library at world size 1: one box per page, then two, alternately; every word's text as code points."""
+    import socket
+    import torch.multiprocessing as mp
+
+    with socket.socket() as s_:
+        s_.bind(("127.0.0.1", 0))
+        port = s_.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_bench_worker, args=(0, 1, port, q, ("--no-extra", "--dump-outputs", str(tmp_path / "out"))))
+    p.start()
+    _, _, res = q.get(timeout=300)
+    p.join(timeout=60)
+    assert p.exitcode == 0 and res["steps"] == 2
+    got = {f.stem: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["boxes", "text_codepoints", "words_per_page"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["words_per_page"].tolist() == [1, 2, 1, 2]
+    boxes, codes = got["boxes"], got["text_codepoints"]
+    assert boxes.shape == (6, 4, 2) and len(codes) == 6
+    # the mock's box spans the detector input; back in input pixels it spans the 768 x 768 page
+    assert np.array_equal(boxes[0], np.array([[0, 0], [768, 0], [768, 768], [0, 768]], boxes.dtype))
+    texts = ["".join(chr(int(c)) for c in row if c >= 0) for row in codes]
+    assert all(1 <= len(t) <= 2 for t in texts)
+
+
+def test_bench_refuses_zero_steps():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    with pytest.raises(SystemExit):
+        bench.main(["--steps", "0"], env=_HostEnv())
