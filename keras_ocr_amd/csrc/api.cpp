@@ -169,11 +169,23 @@ int kocr_create(kocr_ctx** out, int hip_device) {
     c->sw.k5 = on("KOCR_K5", true);
     c->sw.up2x = on("KOCR_UP2X", true);
     c->sw.w43h = on("KOCR_W43H", true);
+    c->sw.w43 = on("KOCR_W43", true);
+    c->sw.w43r = on("KOCR_W43R", true);
+    c->sw.w43v = on("KOCR_W43V", true);
+    c->sw.w43rag = on("KOCR_W43RAG", true);
+    c->sw.w43dilh = on("KOCR_W43DILH", true);
+    c->sw.cells = on("KOCR_CELLS", true);
+    c->sw.wsplit = on("KOCR_WSPLIT", true);
+    c->sw.dsplit = on("KOCR_DSPLIT", true);
+    c->sw.hsplit = on("KOCR_HSPLIT", true);
+    c->sw.first = on("KOCR_FIRST", true);
   }
+  c->prof_layers = getenv("KOCR_PROF_LAYERS") != nullptr;
   if (const char* e = getenv("KOCR_LINFOLD")) c->opt_linfold = atoi(e) != 0;
   if (const char* e = getenv("KOCR_UPFOLD")) c->opt_upfold = atoi(e) != 0;
   c->device = hip_device;
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess ||
+      hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
     delete c;
     return KOCR_EHIP;
   }

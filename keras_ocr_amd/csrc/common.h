@@ -140,7 +140,7 @@ struct kocr_ctx {
   bool opt_linfold = true, opt_upfold = true;
   // kernel selection switches, read ONCE per context in kocr_create from the environment variable of the same name in
   // upper case with the KOCR_ prefix (KOCR_LSTM16=0 ...): the fallback kernels can be exercised per context, inside
-  // one process (the older switches of the convolution dispatch are still process-wide)
+  // one process
   struct Switches {
     bool dense_splitk = true;  // stn_dense_1 on the split-K kernel
     bool lstm16 = true;        // round-3 LSTM kernel (16 crops per workgroup, U resident in registers)
@@ -148,7 +148,19 @@ struct kocr_ctx {
     bool k5 = true;            // 5x5 / 16-cout kernel (stn_conv_1)
     bool up2x = true;          // shared-tap epilogue for exact 2x up-sampling in the decoder 1x1s
     bool w43h = true;          // fp16 F(4,3) kernels in the fp16 arithmetic modes
+    bool w43 = true;           // F(4,3) kernels altogether (wide 3x3 layers then on conv_ws / conv_ds)
+    bool w43r = true;          // row-reuse arrangement of the 64-cout layers (then conv_w43n)
+    bool w43v = true;          // vertical-reuse arrangement of the wider layers (then conv_w43_kernel)
+    bool w43rag = true;        // ragged tile grids (images that do not tile exactly: flattened / F(2,3) / fp32 kernels)
+    bool w43dilh = true;       // fp16 F(4,3) comb tiles of dilated layers (then bf16x3)
+    bool cells = true;         // cell grids of the recogniser's crop batch (then round 4's dense crop batch)
+    bool wsplit = true;        // conv_ws_kernel, Winograd F(2,3) on bf16x3
+    bool dsplit = true;        // conv_ds_kernel, direct convolution on bf16x3
+    bool hsplit = true;        // <= 32-cout 3x3 split kernels (then the fp32 MFMA kernel)
+    bool first = true;         // split first-layer kernel on raw uint8 (then the fp32 MFMA kernel)
   } sw;
+  bool prof_layers = false;  // KOCR_PROF_LAYERS (developer): one profiler row per layer (prof_name)
+  int n_cu = 0;              // compute units of the device (the grid of the persistent kernels)
 
   // max-|x| slots of the tensors of the current forward (see Tensor::amax): zeroed by amax_begin()
   unsigned* d_amax = nullptr;
@@ -227,6 +239,31 @@ struct ProfScope {
   }
 };
 
+// the profiler row of one launch: `row`, or with KOCR_PROF_LAYERS (developer) one row per layer, `layer_row` + ":" + layer
+inline std::string prof_name(const kocr_ctx* ctx, const ConvLayer& L, const std::string& row, const std::string& layer_row) {
+  return ctx->prof_layers ? layer_row + ":" + L.name : row;
+}
+
+// Launch of a persistent kernel K: min(total_tiles, n_cu * occ) blocks of `block` threads with `lds` bytes of dynamic LDS.
+// The kernel's LDS limit is raised to `attr_lds` (>= lds: a launch whose coefficient area depends on the layer may use less
+// than the maximum) once per device -- one process may hold contexts on several GPUs; a race only repeats the call.
+template <auto K, typename P>
+int launch_persistent(kocr_ctx* ctx, const P& p, int total_tiles, int block, int lds, int attr_lds, int occ = 1,
+                      int* grid_out = nullptr) {
+  static std::atomic<bool> attr_done[64];
+  const int dev = ctx->device & 63;
+  if (!attr_done[dev]) {
+    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, attr_lds));
+    attr_done[dev] = true;
+  }
+  const int slots = ctx->n_cu * occ;
+  const int grid = total_tiles < slots ? total_tiles : slots;
+  if (grid_out) *grid_out = grid;
+  hipLaunchKernelGGL(K, dim3(grid), dim3(block), lds, ctx->stream, p);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
 // wave-level max |x| into a Tensor::amax slot (device code; values are non-negative, so uint order = float order)
 #if defined(__HIPCC__)
 // max over the wave of a value that is >= 0 (not NaN) in every lane, as its bits, wave-uniform.  Non-negative floats order
@@ -289,7 +326,7 @@ int launch_conv_pool(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const 
 // kocr_ctx::split_mode; KOCR_SPLIT=bf16|f16 sets the initial value, kocr_set_split_mode changes it.
 // conv_wsplit.hip
 int prepare_wsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw);
-bool wsplit_applicable(const ConvLayer& L, const Tensor& in);
+bool wsplit_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);
 int launch_conv_wsplit(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const Tensor& out, const Tensor* pool,
                        bool need_full);
 // conv_w43.hip: Winograd F(4,3) on the bf16 cores (bf16x3 mode; 3.0 issued FLOPs per algorithmic FLOP instead of 4.0)
@@ -310,8 +347,8 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
                     bool need_full);
 // conv_dsplit.hip
 int prepare_dsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw);
-bool dsplit_applicable(const ConvLayer& L, const Tensor& in);
-bool dsplit_usable(const ConvLayer& L, const Tensor& in);
+bool dsplit_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);
+bool dsplit_usable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);
 // conv_hsplit.hip
 int prepare_hsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw);
 bool hsplit_applicable(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);

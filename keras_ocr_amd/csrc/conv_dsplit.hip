@@ -598,41 +598,28 @@ int prepare_dsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw) 
 }
 
 // the kernel can run this layer on this input (any size)
-bool dsplit_usable(const ConvLayer& L, const Tensor& in) {
-  static const bool off = getenv("KOCR_DSPLIT") && atoi(getenv("KOCR_DSPLIT")) == 0;
-  return !off && L.d_ds && in.cs % 4 == 0 && in.co % 4 == 0 && ((uintptr_t)in.p & 15) == 0 &&
+bool dsplit_usable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
+  return ctx->sw.dsplit && L.d_ds && in.cs % 4 == 0 && in.co % 4 == 0 && ((uintptr_t)in.p & 15) == 0 &&
          (size_t)in.pixels() * in.cs < ((size_t)1 << 40);
 }
 
 // ... and launch_conv's dispatch prefers it: small GEMMs (the CRNN's dense layers) stay on the fp32 kernel, nothing to
 // gain below a few tiles
-bool dsplit_applicable(const ConvLayer& L, const Tensor& in) { return dsplit_usable(L, in) && in.pixels() >= 4096; }
+bool dsplit_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
+  return dsplit_usable(ctx, L, in) && in.pixels() >= 4096;
+}
 
 template <int WM, int WN, int HALF, int UP = 0, int PAIR = 0>
 static int ds_launch(kocr_ctx* ctx, DsParams& p, size_t M) {
   // 48 / 96 KB (bf16x3), 32 / 64 KB (fp16x2); UP: + one 8 KB tap table per consumer wave
   constexpr int NCW = WM * WN;
   constexpr int LDS_BYTES = 2 * (HALF ? 2 : 3) * (8 * WM) * 2 * 256 * 2 + (UP ? NCW * 256 * 32 : 0);
-  static std::atomic<bool> attr_done[64];  // per device (one process may hold contexts on several GPUs); a race only repeats the call
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_ds_kernel<WM, WN, HALF, UP, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
   const size_t mtiles = (M + 256 * WM - 1) / (256 * WM);
   p.total_tiles = (int)(mtiles * (p.Cout_pad / (32 * WN)));
-  const int slots = n_cu * (NCW == 2 ? 2 : 1);  // (1, 2): two blocks per CU
-  const int grid = p.total_tiles < slots ? p.total_tiles : slots;
+  int grid;
   PROBE_RESET(ctx);
-  hipLaunchKernelGGL((conv_ds_kernel<WM, WN, HALF, UP, PAIR>), dim3(grid), dim3(128 * NCW), LDS_BYTES, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
+  KOCR_TRY((launch_persistent<conv_ds_kernel<WM, WN, HALF, UP, PAIR>>(ctx, p, p.total_tiles, 128 * NCW, LDS_BYTES, LDS_BYTES,
+                                                                       NCW == 2 ? 2 : 1, &grid)));  // (1, 2): two blocks per CU
   {
     char what[64];
     snprintf(what, sizeof what, "conv_ds<%d,%d,%d,pair%d> tiles %d steps %d", WM, WN, UP, PAIR, p.total_tiles, p.nsteps);
@@ -692,15 +679,12 @@ int launch_conv_dsplit(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, cons
   p.w_exp = 0;
   w4_div_magic((unsigned)(in.H * in.W), p.dv_hw);
   const int wcls = L.Cout > 64 ? 128 : 64;
-  static const bool per_layer = getenv("KOCR_PROF_LAYERS") != nullptr;
-  char nm[64];
-  if (per_layer)
-    snprintf(nm, sizeof nm, "conv_d%s_%dx%d%s:%s", half ? "h" : "s", wcls == 128 ? 256 : 512, wcls, up ? "_up" : "", L.name.c_str());
-  else
-    snprintf(nm, sizeof nm, "conv_d%s_%dx%d%s", half ? "h" : "s", wcls == 128 ? 256 : 512, wcls, up ? "_up" : "");
+  const std::string row = std::string("conv_d") + (half ? "h" : "s") + "_" + std::to_string(wcls == 128 ? 256 : 512) + "x" +
+                          std::to_string(wcls) + (up ? "_up" : "");
+  const std::string nm = prof_name(ctx, L, row, row);
   const double flops = 2.0 * (double)M * L.Kreal * L.Cout;
   const double bytes = 4.0 * ((double)M * L.Cin + (double)M * L.Cout + (double)L.Kreal * L.Cout + (up ? (double)up->pixels() * L.Cout : 0.0));
-  ProfScope ps(ctx, nm, flops, bytes);
+  ProfScope ps(ctx, nm.c_str(), flops, bytes);
   // whole 128-byte lines per fetch (PAIR): 1x1 convolutions over an even number of channel groups (A/B against round 5's one
   // K-step per fetch: profiles/r06_ab_notes.txt item 3)
   const bool line_pairs = L.KH == 1 && L.KW == 1 && (L.Cin / 16) % 2 == 0 && in.cs % 32 == 0 && in.co % 32 == 0;

@@ -732,8 +732,7 @@ int prepare_hsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw) 
 }
 
 bool hsplit_applicable(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
-  static const bool off = getenv("KOCR_HSPLIT") && atoi(getenv("KOCR_HSPLIT")) == 0;
-  return !off && L.d_hs && in.cs % 4 == 0 && in.co % 4 == 0 &&
+  return ctx->sw.hsplit && L.d_hs && in.cs % 4 == 0 && in.co % 4 == 0 &&
          ((uintptr_t)in.p & 15) == 0 && (size_t)in.H * in.W * in.cs * 4 < ((size_t)1 << 31) &&
          (size_t)in.H * in.W * 32 * 4 < ((size_t)1 << 31);
 }
@@ -762,7 +761,6 @@ int launch_conv_hsplit(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, cons
   p.amax_out = out.amax;
   p.amax_in = nullptr;
   const size_t M = in.pixels();
-  static const bool per_layer = getenv("KOCR_PROF_LAYERS") != nullptr;
   const bool no16 = !ctx->sw.hs16;
   const bool use16 = L.d_hs16 && !no16;  // <= 16 couts: the 16-wide product tile
   // fp16 arithmetic (conv_hsh_kernel) in the fp16 modes, for the 32-wide product tile
@@ -780,14 +778,11 @@ int launch_conv_hsplit(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, cons
     p.wgt = L.d_hsh;
     p.pre_a = L.d_pre_a_h;
   }
-  char nm[64];
-  if (per_layer)
-    snprintf(nm, sizeof nm, "conv_h%s_256x%d:%s", half ? "h" : "s", use16 ? 16 : 32, L.name.c_str());
-  else
-    snprintf(nm, sizeof nm, "conv_h%s_256x%d", half ? "h" : "s", use16 ? 16 : 32);
+  const std::string row = std::string("conv_h") + (half ? "h" : "s") + "_256x" + (use16 ? "16" : "32");
+  const std::string nm = prof_name(ctx, L, row, row);
   const double flops = 2.0 * (double)M * L.Kreal * L.Cout;
   const double bytes = 4.0 * ((double)M * L.Cin + (double)M * L.Cout + (double)L.Kreal * L.Cout);
-  ProfScope ps(ctx, nm, flops, bytes);
+  ProfScope ps(ctx, nm.c_str(), flops, bytes);
   const size_t grid = (size_t)in.N * p.tiles_y * p.tiles_x;
   if (use16) {
     p.wgt = L.d_hs16;
@@ -823,8 +818,7 @@ int prepare_first(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw) {
 }
 
 bool first_applicable(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
-  static const bool off = getenv("KOCR_FIRST") && atoi(getenv("KOCR_FIRST")) == 0;
-  return !off && L.d_first && (size_t)in.H * in.W * 64 * 4 < ((size_t)1 << 31);
+  return ctx->sw.first && L.d_first && (size_t)in.H * in.W * 64 * 4 < ((size_t)1 << 31);
 }
 
 int launch_conv_first(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const uint8_t* in_u8, const float* lut, const Tensor& out) {

@@ -222,15 +222,10 @@ int launch_conv_k5(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const Te
   p.relu = L.relu;
   p.amax_out = out.amax;
   const size_t M = in.pixels();
-  static const bool per_layer = getenv("KOCR_PROF_LAYERS") != nullptr;
-  char nm[64];
-  if (per_layer)
-    snprintf(nm, sizeof nm, "conv_k5_352x16:%s", L.name.c_str());
-  else
-    snprintf(nm, sizeof nm, "conv_k5_352x16");
+  const std::string nm = prof_name(ctx, L, "conv_k5_352x16", "conv_k5_352x16");
   const double flops = 2.0 * (double)M * L.Kreal * L.Cout;
   const double bytes = 4.0 * ((double)M * L.Cin + (double)M * L.Cout + (double)L.Kreal * L.Cout);
-  ProfScope ps(ctx, nm, flops, bytes);
+  ProfScope ps(ctx, nm.c_str(), flops, bytes);
   hipLaunchKernelGGL(conv_k5_kernel, dim3((unsigned)in.N), dim3(256), 0, ctx->stream, p);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;

@@ -650,15 +650,12 @@ int launch_conv_pool(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const 
     mode = 1;
   const bool fuse_pool = pool && mode == 0 && L.BN >= 64 && (in.H % 2 == 0) && (in.W % 64 == 0);
   // Layouts with zero padding that belongs to the tensor (cell grids, Tensor::cellW; width-padded rows, Tensor::Wv) are
-  // read and WRITTEN correctly by the fp16 F(4,3) kernels only: anything else fails here instead of silently writing
-  // convolution values into the padding
-  if (in.cellW || out.cellW || (pool && pool->cellW)) {
-    if (in_u8 || !w43_applicable(ctx, L, in))
-      KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": a cell-grid tensor needs the fp16 vertical-reuse F(4,3) kernel (disabled by a switch or the arithmetic mode)");
+  // read and WRITTEN correctly by the fp16 F(4,3) kernels only: anything else fails (in launch_conv_w43's plan) instead of
+  // silently writing convolution values into the padding
+  if (in.cellW || out.cellW || (pool && pool->cellW) || (out.Wv && out.Wv < out.W)) {
+    if (in_u8) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": a cell-grid or width-padded tensor needs an fp16 F(4,3) kernel");
     return launch_conv_w43(ctx, L, in, out, pool, need_full);
   }
-  if (out.Wv && out.Wv < out.W && (in_u8 || !w43_applicable(ctx, L, in) || !w43_flat_h_ok(ctx, L)))
-    KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": a width-padded output (Tensor::Wv) needs the flattened fp16 F(4,3) kernel (disabled by a switch or the arithmetic mode)");
   if (!out.p) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": no output buffer");
   if (in_u8 && lut && first_applicable(ctx, L, in)) {  // first layer from raw uint8 on the split path
     kocr_note_dispatch("first", L, in);
@@ -673,11 +670,11 @@ int launch_conv_pool(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const 
   if (!in_u8 && w43_applicable(ctx, L, in)) {
     return launch_conv_w43(ctx, L, in, out, pool, need_full);
   }
-  if (!in_u8 && wsplit_applicable(L, in)) {
+  if (!in_u8 && wsplit_applicable(ctx, L, in)) {
     kocr_note_dispatch("wsplit", L, in);
     return launch_conv_wsplit(ctx, L, in, out, pool, need_full);
   }
-  if (!in_u8 && dsplit_applicable(L, in)) {
+  if (!in_u8 && dsplit_applicable(ctx, L, in)) {
     kocr_note_dispatch("dsplit", L, in);
     KOCR_TRY(launch_conv_dsplit(ctx, L, in, out));
     return pool ? launch_maxpool2x2(ctx, out, *pool) : KOCR_OK;
@@ -706,15 +703,11 @@ int launch_conv_pool(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const 
   kocr_note_dispatch("mfma", L, in);
   const double flops = 2.0 * (double)M * L.Kreal * L.Cout;
   const double bytes = 4.0 * ((double)M * L.Cin + (double)M * L.Cout + (double)L.Kreal * L.Cout);
-  char nm[64];
   const int BM = 128;
-  static const bool per_layer = getenv("KOCR_PROF_LAYERS") != nullptr;  // developer: one row per layer
-  if (per_layer)
-    snprintf(nm, sizeof nm, "conv_%dx%d_m%d%s:%s", BM, L.BN, mode, fuse_pool ? "p" : "", L.name.c_str());
-  else
-    snprintf(nm, sizeof nm, "conv_mfma_%dx%d_m%d%s", BM, L.BN, mode, fuse_pool ? "_pool" : "");
+  const std::string tile = std::to_string(BM) + "x" + std::to_string(L.BN) + "_m" + std::to_string(mode);
+  const std::string nm = prof_name(ctx, L, "conv_mfma_" + tile + (fuse_pool ? "_pool" : ""), "conv_" + tile + (fuse_pool ? "p" : ""));
   {
-  ProfScope ps(ctx, nm, flops, bytes);
+  ProfScope ps(ctx, nm.c_str(), flops, bytes);
   const int mtiles = (int)((M + BM - 1) / BM);
   dim3 grid(mtiles * (L.Cout_pad / L.BN));
   if (fuse_pool) {  // BM == 128: tile = 2 rows x 64 columns; M is an exact multiple of 128

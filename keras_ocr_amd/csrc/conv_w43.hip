@@ -1661,22 +1661,23 @@ int prepare_w43(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw) {
   return KOCR_OK;
 }
 
+// the layer's fp16 F(4,3) weights are used in the context's arithmetic
+static bool w43_fp16(const kocr_ctx* ctx, const ConvLayer& L) {
+  return ctx->split_mode != KOCR_SPLIT_BF16X3 && ctx->sw.w43h && L.d_w4h;
+}
+// the reuse arrangements address the input with 32-bit byte offsets
+static bool w43_small(const Tensor& in) { return (size_t)in.H * in.W * in.cs * 4 < ((size_t)1 << 31); }
+
 // Round 5: the fp16 vertical- / row-reuse kernels take any H, W (their MODE 1, "ragged": masked gather and stores) and the
 // recogniser's cell grids (MODE 2).  Which geometry a ragged image gets, or -1: `narrow` = the 64-cout row-reuse kernel
 // (4 x 64 tiles only), else the vertical-reuse kernel on 4 x 64 or 8 x 32 tiles, whichever covers the image with fewer
 // padding pixels (8 x 32 has no fused pooling).  A ragged grid is used when the image's width is not a multiple of 4 (the
 // flattened-pixel arrangements then do not apply at all) or when the padding costs less than the flattened arrangement
 // loses against vertical reuse (measured 20-30 %, plus the unfused pooling).
-static bool w43_env_off(const char* name) {
-  const char* e = getenv(name);
-  return e && atoi(e) == 0;
-}
 static int w43_ragged_geo(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, bool pool) {
-  static const bool no_v = w43_env_off("KOCR_W43V"), no_rr = w43_env_off("KOCR_W43R"), no_rag = w43_env_off("KOCR_W43RAG");
-  if (no_rag || ctx->split_mode == KOCR_SPLIT_BF16X3 || !ctx->sw.w43h || !L.d_w4h || L.dil != 1) return -1;
-  if ((size_t)in.H * in.W * in.cs * 4 >= ((size_t)1 << 31)) return -1;
+  if (!ctx->sw.w43rag || !w43_fp16(ctx, L) || L.dil != 1 || !w43_small(in)) return -1;
   const bool narrow = L.w4_cout_pad == 64;
-  if (narrow ? no_rr : no_v) return -1;
+  if (narrow ? !ctx->sw.w43r : !ctx->sw.w43v) return -1;
   auto cover = [&](int rb, int tc) { return (double)((in.H + rb - 1) / rb * rb) * ((in.W + tc - 1) / tc * tc) / ((double)in.H * in.W); };
   const double c1 = cover(4, 64), c2 = cover(8, 32);
   const int geo = (narrow || pool || c1 <= c2 * 1.02) ? 1 : 2;
@@ -1686,132 +1687,142 @@ static int w43_ragged_geo(const kocr_ctx* ctx, const ConvLayer& L, const Tensor&
   return c <= 1.25 ? geo : -1;
 }
 
-// can layer L run on a cell grid (conv_w43vh_kernel MODE 2) in the context's current arithmetic?  KOCR_CELLS=0: never (the
-// recogniser then keeps round 4's dense crop batch on the flattened-pixel kernel)
-bool w43_cells_ok(const kocr_ctx* ctx, const ConvLayer& L) {
-  static const bool off = w43_env_off("KOCR_W43"), no_v = w43_env_off("KOCR_W43V"), no_cells = w43_env_off("KOCR_CELLS");
-  return !off && !no_v && !no_cells && ctx->split_mode != KOCR_SPLIT_BF16X3 && ctx->sw.w43h && L.d_w4h && L.w4_cout_pad > 64 &&
-         L.dil == 1 && L.Cin % 32 == 0;
-}
-// ... and the width-padded layout (Tensor::Wv) on the flattened fp16 kernel?
+// can a width-padded tensor (Tensor::Wv) run through layer L on the flattened fp16 kernel?
 bool w43_flat_h_ok(const kocr_ctx* ctx, const ConvLayer& L) {
-  static const bool off = w43_env_off("KOCR_W43");
-  return !off && ctx->split_mode != KOCR_SPLIT_BF16X3 && ctx->sw.w43h && L.d_w4h && L.w4_cout_pad > 64 && L.dil == 1 && L.Cin % 32 == 0;
+  return ctx->sw.w43 && w43_fp16(ctx, L) && L.w4_cout_pad > 64 && L.dil == 1 && L.Cin % 32 == 0;
+}
+// ... and a cell grid (conv_w43vh_kernel MODE 2)?  KOCR_CELLS=0: never (the recogniser then keeps round 4's dense crop batch
+// on the flattened-pixel kernel)
+bool w43_cells_ok(const kocr_ctx* ctx, const ConvLayer& L) { return ctx->sw.w43v && ctx->sw.cells && w43_flat_h_ok(ctx, L); }
+
+// How the F(4,3) family runs layer L on `in`, decided in one place: w43_applicable asks it without output and pooling,
+// launch_conv_w43 fills W4Params from it.
+struct W43Plan {
+  const char* fail = nullptr;  // not applicable: why (the text after "conv <layer>: ")
+  char arr = 's';  // 's' flattened pixels (conv_w43_kernel), 'n' the 64-cout flattened tiles (conv_w43n_kernel), 'r' row
+                   // reuse (conv_w43r_kernel / conv_w43rh_kernel), 'v' vertical reuse (conv_w43v_kernel / conv_w43vh_kernel),
+                   // 'f' flattened pixels in fp16 (conv_w43fh_kernel)
+  int geo = 0;     // 'r': 1 = 4 x 64 tiles, 0 = 2 x 128; 'v': 1 = 4 x 64, 2 = 8 x 32 (no fused pooling)
+  int mode = 0;    // 0 = the image tiles exactly, 1 = ragged (masked gather / stores), 2 = cell grid
+  bool fuse = false;  // the fused 2x2 pooling
+  int pieces = 0;  // fp16 pieces (2 in modes 1 and 2: their kernels exist with two pieces only); 0 = the exact bf16x3 kernels
+  // the kernel maintains the per-image max-|x| slots (Tensor::amax) in its epilogue; the flattened bf16x3 arrangements
+  // leave them to a reduction pass after the launch
+  bool tracks() const { return arr != 's' && arr != 'n'; }
+};
+
+static W43Plan plan_w43(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const Tensor* out, const Tensor* pool) {
+  const bool cells = in.cellW > 0;
+  const bool Wv = out && out->Wv && out->Wv < out->W;
+  const char* wv_fail = "a width-padded output (Tensor::Wv) needs the flattened fp16 F(4,3) kernel";
+  const char* cells_fail = "a cell-grid tensor (Tensor::cellW) needs the fp16 vertical-reuse F(4,3) kernel";
+  if (cells ? !w43_cells_ok(ctx, L)
+            : !ctx->sw.w43 || !L.d_w4 || in.cs % 4 != 0 || in.co % 4 != 0 || ((uintptr_t)in.p & 15) != 0 || L.Cin % 32 != 0 ||
+                  (size_t)in.pixels() >= ((size_t)1 << 29) ||
+                  (in.W % (4 * L.dil) != 0 && w43_ragged_geo(ctx, L, in, false) <= 0))  // a width the flattened arrangements do not take
+    return W43Plan{cells ? cells_fail : Wv ? wv_fail : "no F(4,3) arrangement takes this layer and input"};
+  if (cells || (out && out->cellW) || (pool && pool->cellW)) {
+    // tiles of 4 x 64 where a cell is at least 64 columns wide, else 8 x 32 (a tile may touch two cells, not three)
+    const bool cgeo_ok = in.cellW >= 64 ? (in.H % 4 == 0 && in.W % 64 == 0) : (in.cellW >= 32 && in.H % 8 == 0 && in.W % 32 == 0 && !pool);
+    const bool ok = cells && (!out || (out->cellW == in.cellW && out->cellWv == in.cellWv)) && cgeo_ok && in.cellW % 4 == 0 &&
+                    in.W % in.cellW == 0 && in.amax && w43_small(in) &&
+                    (!pool || (pool->cellW * 2 == in.cellW && pool->cellWv * 2 == in.cellWv && in.cellWv % 2 == 0 && pool->H * 2 == in.H &&
+                               pool->W * 2 == in.W));
+    if (!ok) return W43Plan{cells_fail};
+  }
+  W43Plan q;
+  const int rag_geo = cells ? -1 : w43_ragged_geo(ctx, L, in, pool != nullptr);
+  const bool exact_fuse = pool && L.dil == 1 && in.H % 2 == 0 && in.W % 64 == 0;
+  const bool narrow = L.w4_cout_pad == 64;  // 64-cout arrangement: 4 M-tiles x 64 couts per tile
+  const bool reuse_ok = L.dil == 1 && (!pool || exact_fuse) && w43_small(in);
+  if (narrow) {
+    // ... or, when the image tiles as 4 rows x 64 or 2 rows x 128 columns, the row-reuse arrangement (2 M-tiles of 2 rows x
+    // 64 columns); images that tile neither way on a ragged 4 x 64 grid
+    const bool r_ok = reuse_ok && ctx->sw.w43r;
+    q.arr = 'r';
+    if (r_ok && in.H % 4 == 0 && in.W % 64 == 0)
+      q.geo = 1;
+    else if (r_ok && in.H % 2 == 0 && in.W % 128 == 0)
+      q.geo = 0;
+    else if (rag_geo == 1)
+      q.geo = 1, q.mode = 1;
+    else
+      q.arr = 'n';
+  } else {
+    // Cout > 64: the vertical-reuse arrangement on 4 x 64 tiles where the image tiles that way, else 8 x 32 (the 96-wide
+    // layers); cell grids by their cell width; else a ragged grid; anything else (e.g. H % 4 != 0) stays flattened
+    const bool v_ok = reuse_ok && ctx->sw.w43v;
+    q.arr = 'v';
+    if (cells)
+      q.geo = in.cellW >= 64 ? 1 : 2, q.mode = 2;
+    else if (v_ok && in.H % 4 == 0 && in.W % 64 == 0)
+      q.geo = 1;
+    else if (v_ok && !pool && in.H % 8 == 0 && in.W % 32 == 0)
+      q.geo = 2;
+    else if (rag_geo > 0)
+      q.geo = rag_geo, q.mode = 1;
+    else
+      q.arr = 's';
+  }
+  // the fused 2x2 pooling: images that tile exactly as 2 rows x 64 columns (any arrangement), or the 4 x 64 ragged / cell grids
+  q.fuse = exact_fuse || (pool && q.mode != 0 && q.geo == 1);
+  // fp16 arithmetic (conv_w43h.hip) where an fp16 kernel exists for the arrangement: vertical reuse, row reuse on 4 x 64
+  // tiles, the flattened pixels without fused pooling on images of >= 256 pixels (a 256-pixel tile must not span three
+  // images; round 5: dilated layers too -- the comb tiles of conv_w43fh_kernel<.., DIL = 1>; KOCR_W43DILH=0: bf16x3 as
+  // before); else the exact bf16x3 kernels
+  if (w43_fp16(ctx, L)) {
+    if (q.arr == 's' && (L.dil == 1 || ctx->sw.w43dilh) && !q.fuse && (size_t)in.H * in.W >= 256) q.arr = 'f';
+    if (q.arr == 'v' || q.arr == 'f' || (q.arr == 'r' && q.geo == 1))
+      q.pieces = (ctx->split_mode == KOCR_SPLIT_F16X2 || q.mode != 0) ? 2 : 1;
+  }
+  if (q.mode != 0 && !q.pieces) return W43Plan{"ragged / cell grids exist in the fp16 kernels only"};
+  // only the flattened fp16 kernel writes the zero columns of a width-padded output
+  if (Wv && (q.arr != 'f' || L.dil != 1)) return W43Plan{wv_fail};
+  return q;
 }
 
-bool w43_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
-  static const bool off = getenv("KOCR_W43") && atoi(getenv("KOCR_W43")) == 0;
-  if (in.cellW) return w43_cells_ok(ctx, L);
-  if (off || !L.d_w4 || in.cs % 4 != 0 || in.co % 4 != 0 || ((uintptr_t)in.p & 15) != 0 || L.Cin % 32 != 0 ||
-      (size_t)in.pixels() >= ((size_t)1 << 29))
-    return false;
-  if (in.W % (4 * L.dil) == 0) return true;
-  return w43_ragged_geo(ctx, L, in, false) > 0;  // a width the flattened arrangements do not take
+bool w43_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) { return !plan_w43(ctx, L, in, nullptr, nullptr).fail; }
+
+// the profiler row and the dispatch-log family of a plan, e.g. conv_w4hv_256x128_pool and w4hv_pool
+static void w43_names(const kocr_ctx* ctx, const ConvLayer& L, const W43Plan& q, std::string& row, std::string& family) {
+  const char arr = q.arr == 'v' ? (q.geo == 2 ? 't' : 'v') : (q.arr == 'f' || (q.arr == 'r' && q.pieces)) ? q.arr : 's';
+  const std::string w4 = std::string("w4") + (q.pieces == 2 ? "h" : q.pieces == 1 ? "q" : "") + arr;
+  const char* tile = q.arr == 'r' ? "_256x64" : q.arr == 'n' ? "_512x64" : "_256x128";
+  const char* mode_sfx = q.mode == 1 ? "_rag" : q.mode == 2 ? "_cells" : "";
+  family = w4 + (q.fuse ? "_pool" : L.dil != 1 ? "_dil" : "") + mode_sfx;
+  row = prof_name(ctx, L, "conv_" + w4 + tile + family.substr(w4.size()),
+                  "conv_" + w4 + tile + (q.fuse ? "p" : L.dil != 1 ? "d" : "") + (q.mode == 1 ? "g" : q.mode == 2 ? "c" : ""));
 }
 
 template <int POOL, int DBG = 0, int DIL = 0>
 static int w4_launch(kocr_ctx* ctx, W4Params& p) {
-  static std::atomic<bool> attr_done[64];  // per device (one process may hold contexts on several GPUs); a race only repeats the call
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43_kernel<POOL, DBG, DIL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;  // persistent: one block per CU
-  hipLaunchKernelGGL((conv_w43_kernel<POOL, DBG, DIL>), dim3(grid), dim3(256), LDS_BYTES, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
-  return KOCR_OK;
+  return launch_persistent<conv_w43_kernel<POOL, DBG, DIL>>(ctx, p, p.total_tiles, 256, LDS_BYTES, LDS_BYTES);
 }
 
 template <int POOL>
 static int w4n_launch(kocr_ctx* ctx, W4Params& p) {
   constexpr int LDSN = 2 * LDS_BYTES;  // 2 x 72 KB
-  static std::atomic<bool> attr_done[64];
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43n_kernel<POOL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSN));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;
-  hipLaunchKernelGGL((conv_w43n_kernel<POOL>), dim3(grid), dim3(256), LDSN, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
-  return KOCR_OK;
+  return launch_persistent<conv_w43n_kernel<POOL>>(ctx, p, p.total_tiles, 256, LDSN, LDSN);
 }
 
 template <int POOL, int GEO>
 static int w4r_launch(kocr_ctx* ctx, W4Params& p) {
   // 2 x 72 KB, or 54 KB + the epilogue's 64 KB exchange area (which starts at the second 54 KB buffer)
   constexpr int LDSR = GEO ? 6 * 3 * 6 * 256 * 2 + 4 * 16 * 64 * 16 : 2 * LDS_BYTES;
-  static std::atomic<bool> attr_done[64];
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43r_kernel<POOL, GEO>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSR));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;
-  hipLaunchKernelGGL((conv_w43r_kernel<POOL, GEO>), dim3(grid), dim3(256), LDSR, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
-  return KOCR_OK;
+  return launch_persistent<conv_w43r_kernel<POOL, GEO>>(ctx, p, p.total_tiles, 256, LDSR, LDSR);
 }
 
 template <int POOL, int GEO>
 static int w4v_launch(kocr_ctx* ctx, W4Params& p) {
   constexpr int LDSV = GEO == 2 ? 2 * 6 * 3 * 10 * 128 * 2 : 2 * 6 * 3 * 6 * 256 * 2;  // 2 x 45 / 54 KB
-  static std::atomic<bool> attr_done[64];
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43v_kernel<POOL, GEO>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSV));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;
-  hipLaunchKernelGGL((conv_w43v_kernel<POOL, GEO>), dim3(grid), dim3(256), LDSV, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
-  return KOCR_OK;
+  return launch_persistent<conv_w43v_kernel<POOL, GEO>>(ctx, p, p.total_tiles, 256, LDSV, LDSV);
 }
 
 int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const Tensor& out, const Tensor* pool, bool need_full) {
-  // round 5: cell grids (the recogniser's crop batch) and ragged images on the fp16 vertical- / row-reuse kernels
-  const bool cells = in.cellW > 0;
-  if (cells || out.cellW || (pool && pool->cellW)) {
-    // tiles of 4 x 64 where a cell is at least 64 columns wide, else 8 x 32 (a tile may touch two cells, not three)
-    const bool cgeo_ok = in.cellW >= 64 ? (in.H % 4 == 0 && in.W % 64 == 0) : (in.cellW >= 32 && in.H % 8 == 0 && in.W % 32 == 0 && !pool);
-    const bool ok = cells && out.cellW == in.cellW && out.cellWv == in.cellWv && cgeo_ok && in.cellW % 4 == 0 &&
-                    in.W % in.cellW == 0 && in.amax && L.dil == 1 && L.w4_cout_pad > 64 && L.d_w4h && ctx->sw.w43h &&
-                    ctx->split_mode != KOCR_SPLIT_BF16X3 && (size_t)in.H * in.W * in.cs * 4 < ((size_t)1 << 31) &&
-                    (!pool || (pool->cellW * 2 == in.cellW && pool->cellWv * 2 == in.cellWv && in.cellWv % 2 == 0 && pool->H * 2 == in.H &&
-                               pool->W * 2 == in.W));
-    if (!ok) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": a cell-grid tensor (Tensor::cellW) needs the fp16 vertical-reuse F(4,3) kernel");
-  }
-  const int rag_geo = cells ? -1 : w43_ragged_geo(ctx, L, in, pool != nullptr);
-  const bool exact_fuse = pool && L.dil == 1 && in.H % 2 == 0 && in.W % 64 == 0;
+  const W43Plan q = plan_w43(ctx, L, in, &out, pool);
+  if (q.fail) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": " + q.fail);
+  const bool cells = q.mode == 2, narrow = L.w4_cout_pad == 64, fuse = q.fuse;
+  const bool reuse = q.arr == 'r' || q.arr == 'v', geo2 = q.arr == 'v' && q.geo == 2;
   const size_t M = in.pixels();
   W4Params p;
   p.in = in.p;
@@ -1842,37 +1853,6 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
   p.amax_in = nullptr;
   p.Wv = (out.Wv && out.Wv < out.W) ? out.Wv : 0;
   w4_div_magic((unsigned)in.W, p.dv_w);
-  const bool narrow = L.w4_cout_pad == 64;  // 64-cout arrangement: 4 M-tiles x 64 couts per tile
-  // ... or, when the image tiles as 2 rows x 128 columns, the row-reuse arrangement (2 M-tiles of 2 rows x 64 columns)
-  static const bool no_rr = getenv("KOCR_W43R") && atoi(getenv("KOCR_W43R")) == 0;
-  const bool r_ok = narrow && !no_rr && L.dil == 1 && (!pool || exact_fuse) && (size_t)in.H * in.W * in.cs * 4 < ((size_t)1 << 31);
-  const bool rgeo1_ok = r_ok && in.H % 4 == 0 && in.W % 64 == 0, rgeo0_ok = r_ok && in.H % 2 == 0 && in.W % 128 == 0;
-  int rgeo = rgeo1_ok ? 1 : rgeo0_ok ? 0 : -1;  // 4 x 64 tiles where the image tiles that way, else 2 x 128
-  // mode of the fp16 kernels: 0 = the image tiles exactly, 1 = ragged (masked gather / stores), 2 = cell grid
-  int mode = cells ? 2 : 0;
-  if (rgeo < 0 && narrow && rag_geo == 1) {
-    rgeo = 1;
-    mode = 1;
-  }
-  const bool rowreuse = rgeo >= 0;
-  // Cout > 64 on the same image geometry: the vertical-reuse arrangement (conv_w43v_kernel)
-  static const bool no_v = getenv("KOCR_W43V") && atoi(getenv("KOCR_W43V")) == 0;
-  // geometries of conv_w43v_kernel: GEO 1 = 4 rows x 64 columns (H % 4 == 0, W % 64 == 0), GEO 2 = 8 rows x 32 columns
-  // (H % 8 == 0, W % 32 == 0, no fused pooling)
-  const bool v_ok = !narrow && !no_v && L.dil == 1 && (!pool || exact_fuse) && (size_t)in.H * in.W * in.cs * 4 < ((size_t)1 << 31);
-  // 4 rows x 64 columns where the image tiles that way, else 8 rows x 32 columns (the 96-wide layers); anything else (e.g.
-  // H % 4 != 0) stays on conv_w43_kernel
-  const bool geo1_ok = v_ok && in.H % 4 == 0 && in.W % 64 == 0;
-  const bool geo2_ok = v_ok && !pool && in.H % 8 == 0 && in.W % 32 == 0;
-  int vgeo = geo1_ok ? 1 : geo2_ok ? 2 : -1;
-  if (cells) vgeo = in.cellW >= 64 ? 1 : 2;
-  if (vgeo < 0 && !narrow && rag_geo > 0) {
-    vgeo = rag_geo;
-    mode = 1;
-  }
-  const bool vreuse = vgeo >= 0;
-  // the fused 2x2 pooling: images that tile exactly as 2 rows x 64 columns (any arrangement), or the 4 x 64 ragged / cell grids
-  const bool fuse = exact_fuse || (pool && mode != 0 && (vreuse ? vgeo == 1 : rgeo == 1));
   if (fuse) {
     if (pool->H != in.H / 2 || pool->W != in.W / 2 || pool->N != in.N) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": bad pooled shape");
     p.pool_out = pool->p;
@@ -1882,13 +1862,13 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
     p.tiles_per_row = in.W / 64;
   }
   if (!out.p && !(fuse && !need_full)) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": no output buffer");
-  if ((rowreuse || vreuse) && !fuse) p.tiles_per_row = in.W / 64;  // the 2-row x 64-column M-tile geometry without the pooling
-  p.n_mpairs = (rowreuse || vreuse) ? p.total_mtiles / 2 : narrow ? (p.total_mtiles + 3) / 4 : (p.total_mtiles + 1) / 2;
-  if (vgeo == 2) p.tiles_per_row = in.W / 32;
+  if (reuse && !fuse) p.tiles_per_row = in.W / 64;  // the 2-row x 64-column M-tile geometry without the pooling
+  p.n_mpairs = reuse ? p.total_mtiles / 2 : narrow ? (p.total_mtiles + 3) / 4 : (p.total_mtiles + 1) / 2;
+  if (geo2) p.tiles_per_row = in.W / 32;
   p.rq_per_img = 0;
   p.cellW = p.cellWv = p.cells_per_row = 0;
-  if (mode != 0) {  // the ragged / cell tile grid: ceil(H / 4) x ceil(W / 64) (ceil(H / 8) x ceil(W / 32)) tiles per image
-    const int rb = (vreuse && vgeo == 2) ? 8 : 4, tc = (vreuse && vgeo == 2) ? 32 : 64;
+  if (q.mode != 0) {  // the ragged / cell tile grid: ceil(H / 4) x ceil(W / 64) (ceil(H / 8) x ceil(W / 32)) tiles per image
+    const int rb = geo2 ? 8 : 4, tc = geo2 ? 32 : 64;
     p.tiles_per_row = (in.W + tc - 1) / tc;
     p.rq_per_img = (in.H + rb - 1) / rb;
     p.n_mpairs = in.N * p.rq_per_img * p.tiles_per_row;
@@ -1906,29 +1886,14 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
   w4_div_magic((unsigned)(p.cellW ? p.cellW : 1), p.dv_wc);
   p.total_tiles = p.n_mpairs * (p.Cout_pad / (narrow ? 64 : 128));
   w4_div_magic((unsigned)p.tiles_per_row, p.dv_tpr);
-  w4_div_magic((unsigned)(vgeo == 2 ? in.H / 8 : in.H / 2), p.dv_hh);
+  w4_div_magic((unsigned)(geo2 ? in.H / 8 : in.H / 2), p.dv_hh);
   w4_div_magic((unsigned)p.n_mpairs, p.dv_mp);
   w4_div_magic((unsigned)(in.H * in.W), p.dv_hw);
-  // Per-image max-|x| slots (Tensor::amax): the one-image tiles of the row-reuse / vertical-reuse arrangements maintain
-  // them in their epilogue; the flattened-pixel arrangements leave them to a reduction pass after the launch.
-  // fp16 arithmetic (conv_w43h.hip) where an fp16 kernel exists for the arrangement; else the exact bf16x3 kernels
-  const int pieces = ctx->split_mode == KOCR_SPLIT_F16X2 ? 2 : ctx->split_mode == KOCR_SPLIT_F16X1 ? 1 : 0;
-  const bool no_h = !ctx->sw.w43h;
-  // ... the flattened-pixel arrangement too (no fused pooling, dilation 1; a 256-pixel tile must not span three images)
-  // (round 5: dilated layers too -- the comb tiles of conv_w43fh_kernel<.., DIL = 1>; KOCR_W43DILH=0: bf16x3 as before)
-  static const bool no_dilh = w43_env_off("KOCR_W43DILH");
-  const bool flat_h = pieces && !no_h && L.d_w4h && !narrow && !vreuse && !rowreuse && (L.dil == 1 || !no_dilh) && !fuse &&
-                      (size_t)in.H * in.W >= 256;
-  const bool use_h = (pieces && !no_h && L.d_w4h && (vreuse || (rowreuse && rgeo == 1))) || flat_h;
-  if (mode != 0 && !use_h) KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": ragged / cell grids exist in the fp16 kernels only");
-  if (p.Wv && !flat_h)  // only the flattened fp16 kernel writes the zero columns of a width-padded output
-    KOCR_FAIL(ctx, KOCR_EINVAL, "conv " + L.name + ": a width-padded output (Tensor::Wv) needs the flattened fp16 F(4,3) kernel");
-  const bool tracks = rowreuse || vreuse || flat_h;
-  if (tracks) {
+  if (q.tracks()) {
     p.amax_out = (!fuse || need_full) ? out.amax : nullptr;
     p.amax_pool = fuse ? pool->amax : nullptr;
   }
-  if (use_h) {
+  if (q.pieces) {
     const unsigned* slots = in.amax;
     if (!slots) {  // the producer did not track: reduce the input once, per image
       unsigned* tmp = ctx->amax_slots(in.N);
@@ -1946,24 +1911,15 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
   // flight on an XCD they overflow its 4 MB L2 and are re-streamed from the Infinity Cache by every round of tiles.
   // Pixel-tile-fastest order keeps ONE cout block per XCD at a time (measured +4 % on 512 -> 512, neutral below).
   p.m_fastest = (size_t)L.Cin * L.w4_cout_pad * 3 * 36 > ((size_t)6 << 20) ? 1 : 0;
-  static const bool per_layer = getenv("KOCR_PROF_LAYERS") != nullptr;
-  char nm[64];
-  if (per_layer)
-    snprintf(nm, sizeof nm, "conv_w4%s%s_%s%s%s:%s", use_h ? ((pieces == 2 || mode) ? "h" : "q") : "", vreuse ? (vgeo == 2 ? "t" : "v") : (flat_h ? "f" : use_h ? "r" : "s"), rowreuse ? "256x64" : narrow ? "512x64" : "256x128", fuse ? "p" : (L.dil != 1 ? "d" : ""), mode == 1 ? "g" : mode == 2 ? "c" : "", L.name.c_str());
-  else
-    snprintf(nm, sizeof nm, "conv_w4%s%s_%s%s%s", use_h ? ((pieces == 2 || mode) ? "h" : "q") : "", vreuse ? (vgeo == 2 ? "t" : "v") : (flat_h ? "f" : use_h ? "r" : "s"), rowreuse ? "256x64" : narrow ? "512x64" : "256x128", fuse ? "_pool" : (L.dil != 1 ? "_dil" : ""), mode == 1 ? "_rag" : mode == 2 ? "_cells" : "");
-  {
-    char fam[48];
-    snprintf(fam, sizeof fam, "w4%s%s%s%s", use_h ? ((pieces == 2 || mode) ? "h" : "q") : "", vreuse ? (vgeo == 2 ? "t" : "v") : (flat_h ? "f" : use_h ? "r" : "s"),
-             fuse ? "_pool" : (L.dil != 1 ? "_dil" : ""), mode == 1 ? "_rag" : mode == 2 ? "_cells" : "");
-    kocr_note_dispatch(fam, L, in);
-  }
+  std::string nm, fam;
+  w43_names(ctx, L, q, nm, fam);
+  kocr_note_dispatch(fam.c_str(), L, in);
   // algorithmic (direct-convolution) FLOPs and bytes: of the crops' own pixels in a cell grid, not of the gutters
   const double Malg = cells ? (double)in.N * in.cells() * (in.H - 1) * in.cellWv : (double)M;
   const double flops = 2.0 * Malg * L.Kreal * L.Cout;
   const double bytes = 4.0 * (Malg * L.Cin + Malg * L.Cout * ((fuse && !need_full) ? 0.25 : 1.0) + (double)L.Kreal * L.Cout);
   {
-    ProfScope ps(ctx, nm, flops, bytes);
+    ProfScope ps(ctx, nm.c_str(), flops, bytes);
 #ifdef KOCR_DEV_SWITCHES
     static const int dbg = getenv("KOCR_W43_DBG") ? atoi(getenv("KOCR_W43_DBG")) : 0;
     if (dbg && !fuse) {
@@ -1987,46 +1943,33 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
       }
     }
 #endif
-    if (use_h && vreuse) {
-      KOCR_TRY(launch_w43vh(ctx, p, fuse, vgeo, pieces, mode));
-    } else if (flat_h) {
-      KOCR_TRY(launch_w43fh(ctx, p, pieces));
-    } else if (use_h) {
-      KOCR_TRY(launch_w43rh(ctx, p, fuse, pieces, mode));
-    } else if (vreuse) {
-      if (vgeo == 2) {
-        KOCR_TRY((w4v_launch<0, 2>(ctx, p)));
-      } else {
-        if (fuse)
-          KOCR_TRY((w4v_launch<1, 1>(ctx, p)));
+    switch (q.arr) {
+      case 'v':
+        if (q.pieces)
+          KOCR_TRY(launch_w43vh(ctx, p, fuse, q.geo, q.pieces, q.mode));
+        else if (q.geo == 2)
+          KOCR_TRY((w4v_launch<0, 2>(ctx, p)));
         else
-          KOCR_TRY((w4v_launch<0, 1>(ctx, p)));
-      }
-    } else if (rowreuse) {
-      if (rgeo == 1) {
-        if (fuse)
-          KOCR_TRY((w4r_launch<1, 1>(ctx, p)));
+          KOCR_TRY((fuse ? w4v_launch<1, 1>(ctx, p) : w4v_launch<0, 1>(ctx, p)));
+        break;
+      case 'r':
+        if (q.pieces)
+          KOCR_TRY(launch_w43rh(ctx, p, fuse, q.pieces, q.mode));
+        else if (q.geo == 1)
+          KOCR_TRY((fuse ? w4r_launch<1, 1>(ctx, p) : w4r_launch<0, 1>(ctx, p)));
         else
-          KOCR_TRY((w4r_launch<0, 1>(ctx, p)));
-      } else {
-        if (fuse)
-          KOCR_TRY((w4r_launch<1, 0>(ctx, p)));
+          KOCR_TRY((fuse ? w4r_launch<1, 0>(ctx, p) : w4r_launch<0, 0>(ctx, p)));
+        break;
+      case 'f': KOCR_TRY(launch_w43fh(ctx, p, q.pieces)); break;
+      case 'n': KOCR_TRY(fuse ? w4n_launch<1>(ctx, p) : w4n_launch<0>(ctx, p)); break;
+      default:
+        if (L.dil != 1)
+          KOCR_TRY((w4_launch<0, 0, 1>(ctx, p)));
         else
-          KOCR_TRY((w4r_launch<0, 0>(ctx, p)));
-      }
-    } else if (narrow) {
-      if (fuse)
-        KOCR_TRY(w4n_launch<1>(ctx, p));
-      else
-        KOCR_TRY(w4n_launch<0>(ctx, p));
-    } else if (L.dil != 1)
-      KOCR_TRY((w4_launch<0, 0, 1>(ctx, p)));
-    else if (fuse)
-      KOCR_TRY(w4_launch<1>(ctx, p));
-    else
-      KOCR_TRY(w4_launch<0>(ctx, p));
+          KOCR_TRY(fuse ? w4_launch<1>(ctx, p) : w4_launch<0>(ctx, p));
+    }
   }
-  if (!tracks) {  // flattened-pixel arrangements: per-image max |x| of what was written, for an fp16 consumer
+  if (!q.tracks()) {  // flattened-pixel arrangements: per-image max |x| of what was written, for an fp16 consumer
     if (out.amax && (!fuse || need_full)) KOCR_TRY(launch_absmax(ctx, out, out.amax));
     if (fuse && pool->amax) KOCR_TRY(launch_absmax(ctx, *pool, pool->amax));
   }

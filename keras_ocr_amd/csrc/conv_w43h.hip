@@ -1637,23 +1637,10 @@ template <int POOL, int GEO, int NP, int DBG = 0, int MODE = 0>
 static int w4vh_launch(kocr_ctx* ctx, W4Params& p) {
   constexpr int LDSV0 = (GEO == 2 ? 2 * 6 * 10 * 128 * 2 : 2 * 6 * 6 * 256 * 2) * NP;  // 2 x 30 / 36 KB (NP = 2)
   const int LDSV = LDSV0 + 4 * p.Cout_pad * 4;                                         // + the epilogue's coefficients
-  static std::atomic<bool> attr_done[64];
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43vh_kernel<POOL, GEO, NP, DBG, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSV0 + W4_COEF_BYTES_MAX));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;  // persistent: one block per CU
+  int grid;
   PROBE_RESET(ctx);
-  hipLaunchKernelGGL((conv_w43vh_kernel<POOL, GEO, NP, DBG, MODE>), dim3(grid), dim3(256), LDSV, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
+  KOCR_TRY((launch_persistent<conv_w43vh_kernel<POOL, GEO, NP, DBG, MODE>>(ctx, p, p.total_tiles, 256, LDSV, LDSV0 + W4_COEF_BYTES_MAX,
+                                                                           1, &grid)));
   {
     char what[80];
     snprintf(what, sizeof what, "conv_w43vh<%d,%d,%d,%d> tiles %d steps %d cout %d", POOL, GEO, NP, MODE, p.total_tiles, p.nsteps, p.Cout);
@@ -1712,24 +1699,10 @@ static int w4rh_launch(kocr_ctx* ctx, W4Params& p) {
   // one 36 KB buffer + the epilogue's 64 KB exchange area (its head is the second buffer); OCC = 2: the two buffers only
   constexpr int LDSR0 = OCC == 2 ? 2 * 6 * NP * 6 * 256 * 2 : 6 * NP * 6 * 256 * 2 + 4 * 16 * 64 * 16;
   const int LDSR = LDSR0 + 4 * p.Cout_pad * 4;                    // + the epilogue's coefficients
-  static std::atomic<bool> attr_done[64];
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43rh_kernel<POOL, NP, MODE, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSR0 + W4_COEF_BYTES_MAX));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int slots = n_cu * OCC;
-  const int grid = p.total_tiles < slots ? p.total_tiles : slots;
+  int grid;
   PROBE_RESET(ctx);
-  hipLaunchKernelGGL((conv_w43rh_kernel<POOL, NP, MODE, OCC>), dim3(grid), dim3(256), LDSR, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
+  KOCR_TRY((launch_persistent<conv_w43rh_kernel<POOL, NP, MODE, OCC>>(ctx, p, p.total_tiles, 256, LDSR, LDSR0 + W4_COEF_BYTES_MAX, OCC,
+                                                                       &grid)));
   {
     char what[80];
     snprintf(what, sizeof what, "conv_w43rh<%d,%d,%d,occ%d> tiles %d steps %d", POOL, NP, MODE, OCC, p.total_tiles, p.nsteps);
@@ -1751,25 +1724,11 @@ int launch_w43rh(kocr_ctx* ctx, W4Params& p, bool fuse, int pieces, int mode) {
 
 template <int NP, int DIL = 0>
 static int w4fh_launch(kocr_ctx* ctx, W4Params& p) {
-  const int LDSF = 2 * 6 * NP * 2 * 2 * 256 * 2 + 4 * p.Cout_pad * 4;  // 2 x 24 KB (NP = 2) + the epilogue's coefficients
-  static std::atomic<bool> attr_done[64];
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_w43fh_kernel<NP, DIL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      2 * 6 * NP * 2 * 2 * 256 * 2 + W4_COEF_BYTES_MAX));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;
+  constexpr int LDSF0 = 2 * 6 * NP * 2 * 2 * 256 * 2;  // 2 x 24 KB (NP = 2) + the epilogue's coefficients
+  int grid;
   PROBE_RESET(ctx);
-  hipLaunchKernelGGL((conv_w43fh_kernel<NP, DIL>), dim3(grid), dim3(256), LDSF, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
+  KOCR_TRY((launch_persistent<conv_w43fh_kernel<NP, DIL>>(ctx, p, p.total_tiles, 256, LDSF0 + 4 * p.Cout_pad * 4, LDSF0 + W4_COEF_BYTES_MAX,
+                                                           1, &grid)));
   {
     char what[64];
     snprintf(what, sizeof what, "conv_w43fh<%d> tiles %d steps %d", NP, p.total_tiles, p.nsteps);

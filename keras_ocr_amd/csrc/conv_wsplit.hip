@@ -537,35 +537,17 @@ int prepare_wsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw) 
   return KOCR_OK;
 }
 
-bool wsplit_applicable(const ConvLayer& L, const Tensor& in) {
-  static const bool off = getenv("KOCR_WSPLIT") && atoi(getenv("KOCR_WSPLIT")) == 0;
-  return !off && L.d_ws && in.W % 2 == 0 && in.cs % 4 == 0 && in.co % 4 == 0 && ((uintptr_t)in.p & 15) == 0 &&
+bool wsplit_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
+  return ctx->sw.wsplit && L.d_ws && in.W % 2 == 0 && in.cs % 4 == 0 && in.co % 4 == 0 && ((uintptr_t)in.p & 15) == 0 &&
          L.Cin % 16 == 0;
 }
 
 template <int POOL, int WM, int WN, int HALF, int KB>
 static int ws_launch(kocr_ctx* ctx, WsParams& p, size_t M) {
   constexpr int LDS_BYTES = 2 * 4 * (HALF ? 2 : 3) * KB * (2 * WM) * 2 * 256 * 2;  // 48 / 96 KB (bf16x3), 32 / 64 KB * KB (fp16x2)
-  static std::atomic<bool> attr_done[64];  // per device (one process may hold contexts on several GPUs); a race only repeats the call
-  const int dev = ctx->device & 63;
-  if (!attr_done[dev]) {
-    KOCR_HIP(ctx, hipFuncSetAttribute((const void*)conv_ws_kernel<POOL, WM, WN, HALF, KB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      LDS_BYTES));
-    attr_done[dev] = true;
-  }
-  static std::atomic<int> n_cus[64];
-  if (!n_cus[dev]) {
-    hipDeviceProp_t prop;
-    KOCR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    n_cus[dev] = prop.multiProcessorCount;
-  }
-  const int n_cu = n_cus[dev];
   const size_t mtiles = POOL ? M / (size_t)(128 * WM) : (M + 128 * WM - 1) / (128 * WM);
   p.total_tiles = (int)(mtiles * (p.Cout_pad / (32 * WN)));
-  const int grid = p.total_tiles < n_cu ? p.total_tiles : n_cu;  // persistent: one block per CU
-  hipLaunchKernelGGL((conv_ws_kernel<POOL, WM, WN, HALF, KB>), dim3(grid), dim3(512), LDS_BYTES, ctx->stream, p);
-  KOCR_HIP(ctx, hipGetLastError());
-  return KOCR_OK;
+  return launch_persistent<conv_ws_kernel<POOL, WM, WN, HALF, KB>>(ctx, p, p.total_tiles, 512, LDS_BYTES, LDS_BYTES);
 }
 
 int launch_conv_wsplit(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const Tensor& out, const Tensor* pool,
@@ -613,16 +595,13 @@ int launch_conv_wsplit(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, cons
     p.write_full = need_full ? 1 : 0;
     p.tiles_per_row = in.W / tile_w;
   }
-  static const bool per_layer = getenv("KOCR_PROF_LAYERS") != nullptr;
-  char nm[64];
-  if (per_layer)
-    snprintf(nm, sizeof nm, "conv_w%s_%dx%d%s:%s", half ? "h" : "s", wcls == 128 ? 128 : 256, wcls, fuse ? "p" : "", L.name.c_str());
-  else
-    snprintf(nm, sizeof nm, "conv_w%s_%dx%d%s", half ? "h" : "s", wcls == 128 ? 128 : 256, wcls, fuse ? "_pool" : "");
+  const std::string base = std::string("conv_w") + (half ? "h" : "s") + "_" + std::to_string(wcls == 128 ? 128 : 256) + "x" +
+                           std::to_string(wcls);
+  const std::string nm = prof_name(ctx, L, base + (fuse ? "_pool" : ""), base + (fuse ? "p" : ""));
   const double flops = 2.0 * (double)M * L.Kreal * L.Cout;  // algorithmic (direct-convolution) FLOPs
   const double bytes = 4.0 * ((double)M * L.Cin + (double)M * L.Cout + (double)L.Kreal * L.Cout);
   {
-    ProfScope ps(ctx, nm, flops, bytes);
+    ProfScope ps(ctx, nm.c_str(), flops, bytes);
     if (wcls == 128) {
       if (fuse)
         KOCR_TRY((ws_launch<1, 1, 4, 0, 1>(ctx, p, M)));

@@ -413,7 +413,7 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
   KOCR_TRY(mk(d.H16, d.W16, 512, &u1a, true));
   bool lin_fold = false;
   if constexpr (!DRY) {
-    lin_fold = ctx->opt_linfold && dsplit_usable(L("upconv1.conv.0#skip"), s4) &&
+    lin_fold = ctx->opt_linfold && dsplit_usable(ctx, L("upconv1.conv.0#skip"), s4) &&
                2 * (size_t)h0.H * h0.W * 512 * 4 < ((size_t)1 << 31);
     if (lin_fold) {  // see craft_load: slice5.1 -> slice5.2 -> upconv1.conv.0 as one dilated 3x3 plus a 1x1 over s4
       Tensor t = h1;  // the first half of h1's buffer, as a contiguous 512-channel tensor
@@ -444,7 +444,7 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
     if constexpr (!DRY) {
       const ConvLayer& Ls = L((std::string(name) + "#skip").c_str());
       const Tensor skip = cat.slice(c_y, cat.C - c_y);
-      const bool fold = ctx->opt_upfold && dsplit_usable(Ls, skip) &&
+      const bool fold = ctx->opt_upfold && dsplit_usable(ctx, Ls, skip) &&
                         2 * (size_t)t.H * t.W * t.C * 4 < ((size_t)1 << 31);  // two images of t within 32-bit offsets
       if (fold) {
         KOCR_TRY(launch_conv(ctx, L((std::string(name) + "#y").c_str()), y, nullptr, nullptr, t));

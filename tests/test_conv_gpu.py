@@ -192,6 +192,32 @@ def test_split_kernel_is_fp32_class_against_fp64(ctx, case):
     assert rms <= 1.5e-7, f"rms = {rms:.3e}"
 
 
+def test_switches_act_per_context(monkeypatch):
+    """The kernel selection switches are read when a context is created (kocr_create), not once per process: KOCR_W43R=0
+    moves a 64-cout layer that tiles 4 x 64 off the row-reuse arrangement (onto conv_w43n_kernel's 512 x 64 tiles), and a
+    context created after the switch is unset in the same process is back on it."""
+    import keras_ocr_amd
+
+    if any(k.startswith("KOCR_") and k != "KOCR_DISPATCH_LOG" for k in os.environ):
+        pytest.skip("a KOCR_* switch is set for the whole process")
+    rng = np.random.default_rng(_seed("switches_per_context"))
+    x = np.maximum(rng.standard_normal((2, 64, 128, 64)), 0).astype(np.float32)
+    wt = (rng.standard_normal((3, 3, 64, 64)) * np.sqrt(2.0 / (64 * 9))).astype(np.float32)
+
+    def conv_rows():
+        c = keras_ocr_amd.Context(0)
+        try:
+            c.profile_enable(True)
+            c.conv2d_nhwc(x, wt)
+            return sorted(k for k in c.profile_report() if k.startswith("conv"))
+        finally:
+            c.close()
+
+    monkeypatch.setenv("KOCR_W43R", "0")
+    assert conv_rows() == ["conv_w4s_512x64"]
+    monkeypatch.delenv("KOCR_W43R")
+    assert conv_rows() == ["conv_w4hr_256x64"]
+
 # conv_k5.hip: 5x5, 16 couts, images of <= 384 pixels (the recogniser's stn_conv_1, recognition.py:259-262): one image
 # per block, two taps per MFMA K-step
 K5_CASES = [

@@ -1,5 +1,5 @@
 """The fallback kernels behind the library's environment switches, verified in FRESH processes (the switches are read
-once per process): the fp64-bounded convolution tests and the CRAFT heat-map-vs-oracle tests must also hold with
+when a context is created): the fp64-bounded convolution tests and the CRAFT heat-map-vs-oracle tests must also hold with
 
   KOCR_W43=0     no F(4,3) kernels          -> wide 3x3 layers on conv_ws (F(2,3)) / conv_ds
   KOCR_W43R=0    no row-reuse arrangement   -> 64-cout layers on conv_w43n
@@ -59,7 +59,7 @@ def _run_config(switches):
 
 
 def test_parity_suites_hold_on_the_fallback_paths():
-    """Every configuration is its own pytest child process (the switches are read once per process), one after the other:
+    """Every configuration is its own pytest child process (every context of a child reads its switches), one after the other:
     three at a time was tried in round 5 and took FIVE times longer -- processes sharing one GPU pay a full wave-state
     save / restore of these 512-register, 160-KB-LDS kernels at every switch.  The children run the dispatch-sensitive
     cases only (every fp64-bounded convolution case, two CRAFT heat-maps incl. the ragged page, the recogniser at 1 / 5 / 40
