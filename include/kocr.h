@@ -89,6 +89,28 @@ int kocr_load_crnn(kocr_ctx* ctx, int n, const char* const* names,
 int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W,
                        float* heat, int micro_batch, int on_device);
 
+/* ---- taps of the detector forward (test seam: one layer at a time against a float64 reference) --------------
+ * kocr_craft_set_taps selects launches of kocr_craft_forward by name: the layer names (basenet.slice1.3,
+ * basenet.slice5#fold, upconv2.conv.0#y, upconv2.conv.0#skip, conv_cls.4, ...) and maxpool3x3s1, resize:upconv2
+ * .. resize:upconv4 (the unfolded decoder's bilinear resize) and head_tail (conv_cls.6 + conv_cls.8); "*" selects
+ * every launch, n = 0 turns taps off.  Which launches run depends on the shapes, the arithmetic mode and the
+ * schedule.  Every kocr_craft_forward call with taps on restarts the record; for each selected launch it copies to
+ * context-owned host memory, ordered on the ctx stream, three parts, each accumulated over all micro-batches:
+ *   which = 0  the input view as the launch read it (absent for a uint8 image),
+ *   which = 1  the full output after the launch (absent where only the pooled tensor is written; for
+ *              resize:upconvN the whole concat buffer, for head_tail the heat-map),
+ *   which = 2  the pooled output,
+ * each as the logical N x H x W x C float32 tensor (channel slices gathered) with the tensor's per-image max-|x|
+ * slots as they stood at that moment (-1: the tensor has no slots).  Taps change no kernel and no result.
+ * kocr_craft_tap_count: launches recorded by the last call.  kocr_craft_tap_info: the i-th in launch order --
+ * name (64 bytes), kernel (256 bytes: the profiler rows of what the launch ran, '+'-joined, e.g.
+ * "conv_w4hr_256x64_pool"), dims[3][4] = N, H, W, C per part (all 0 = absent).  kocr_craft_get_tap synchronises the
+ * ctx stream and copies one part: dst N*H*W*C floats, amax_dst N floats (either may be NULL). */
+int kocr_craft_set_taps(kocr_ctx* ctx, int n, const char* const* names);
+int kocr_craft_tap_count(kocr_ctx* ctx);
+int kocr_craft_tap_info(kocr_ctx* ctx, int i, char* name, char* kernel, int32_t* dims);
+int kocr_craft_get_tap(kocr_ctx* ctx, const char* name, int which, float* dst, float* amax_dst);
+
 /* ---- detection.getBoxes (detection.py:207-287) ---------------------------------------- */
 /* heat: N x h x w x 2 float32.  Thresholds as Detector.detect's keyword arguments
  * (detection.py:748-751).  boxes: N x cap x 4 x 2 float32, corner order and x2 scaling as the
@@ -249,6 +271,8 @@ int kocr_get_split_mode(const kocr_ctx* ctx);
  * as resize(conv1x1_y(y)) + conv1x1_skip(skip).  Both default to on (KOCR_LINFOLD=0 / KOCR_UPFOLD=0 in the
  * environment of kocr_create turn them off for new contexts); results differ by fp32 round-off only. */
 int kocr_set_schedule(kocr_ctx* ctx, int fold_linear_chain, int fold_upsample);
+/* The switches as they stand (1 = on): the environment's choice until kocr_set_schedule changes it. */
+int kocr_get_schedule(kocr_ctx* ctx, int* fold_linear_chain, int* fold_upsample);
 
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx

@@ -59,6 +59,10 @@ def load_library():
         "kocr_load_craft": (ci, [vp, ci, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp), _c_i64_p, _c_int_p]),
         "kocr_load_crnn": (ci, [vp, ci, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp), _c_i64_p, _c_int_p]),
         "kocr_craft_forward": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, ci]),
+        "kocr_craft_set_taps": (ci, [vp, ci, ctypes.POINTER(ctypes.c_char_p)]),
+        "kocr_craft_tap_count": (ci, [vp]),
+        "kocr_craft_tap_info": (ci, [vp, ci, ctypes.c_char_p, ctypes.c_char_p, vp]),
+        "kocr_craft_get_tap": (ci, [vp, ctypes.c_char_p, ci, vp, vp]),
         "kocr_crnn_forward": (ci, [vp, vp, ci, vp, vp, ci]),
         "kocr_crnn_classes": (ci, [vp]),
         "kocr_crnn_label_width": (ci, [vp]),
@@ -80,6 +84,7 @@ def load_library():
         "kocr_set_split_mode": (ci, [vp, ci]),
         "kocr_get_split_mode": (ci, [vp]),
         "kocr_set_schedule": (ci, [vp, ci, ci]),
+        "kocr_get_schedule": (ci, [vp, _c_int_p, _c_int_p]),
         "kocr_profile_enable": (ci, [vp, ci]),
         "kocr_profile_reset": (ci, [vp]),
         "kocr_profile_report": (ci, [vp, ci, ctypes.c_char_p, _c_i64_p, _c_dbl_p, _c_dbl_p, _c_dbl_p]),
@@ -186,6 +191,34 @@ class Context:
         """Device-pointer variant (asynchronous on the ctx stream)."""
         self._check(self._lib.kocr_craft_forward(self._h, _ptr(d_img), int(dtype), n, h, w, _ptr(d_heat),
                                                  int(micro_batch), 1))
+
+    def craft_set_taps(self, names=("*",)):
+        """Record the named launches of every following craft_forward (include/kocr.h: kocr_craft_set_taps); "*" = all,
+        an empty list turns taps off."""
+        names = [n.encode() for n in names]
+        arr = (ctypes.c_char_p * max(1, len(names)))(*names)
+        self._check(self._lib.kocr_craft_set_taps(self._h, len(names), arr))
+
+    def craft_taps(self):
+        """What the last craft_forward recorded, in launch order: {name: {"kernel": profiler rows '+'-joined,
+        "in" / "out" / "pool": (N x H x W x C float32 array, per-image max-|x| slots or None) or None}}."""
+        out = {}
+        for i in range(self._check(self._lib.kocr_craft_tap_count(self._h))):
+            name = ctypes.create_string_buffer(64)
+            kernel = ctypes.create_string_buffer(256)
+            dims = np.zeros((3, 4), dtype=np.int32)
+            self._check(self._lib.kocr_craft_tap_info(self._h, i, name, kernel, _ptr(dims)))
+            rec = {"kernel": kernel.value.decode()}
+            for which, key in enumerate(("in", "out", "pool")):
+                if not dims[which, 0]:
+                    rec[key] = None
+                    continue
+                data = np.empty(tuple(int(v) for v in dims[which]), dtype=np.float32)
+                amax = np.empty(int(dims[which, 0]), dtype=np.float32)
+                self._check(self._lib.kocr_craft_get_tap(self._h, name.value, which, _ptr(data), _ptr(amax)))
+                rec[key] = (data, None if (amax < 0).any() else amax)
+            out[name.value.decode()] = rec
+        return out
 
     # -- inner seam #2 ---------------------------------------------------------------
     def crnn_classes(self):
@@ -467,6 +500,12 @@ class Context:
     def set_schedule(self, fold_linear_chain=True, fold_upsample=True):
         """CRAFT schedule switches (include/kocr.h kocr_set_schedule); both on by default."""
         self._check(self._lib.kocr_set_schedule(self._h, int(bool(fold_linear_chain)), int(bool(fold_upsample))))
+
+    def get_schedule(self):
+        """(fold_linear_chain, fold_upsample) in force on this context (include/kocr.h kocr_get_schedule)."""
+        lin, up = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.kocr_get_schedule(self._h, ctypes.byref(lin), ctypes.byref(up)))
+        return bool(lin.value), bool(up.value)
 
     # -- measurement -------------------------------------------------------------------
     def profile_enable(self, on=True):

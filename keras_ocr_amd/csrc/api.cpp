@@ -279,9 +279,15 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
   size_t need = craft_workspace_bytes(mb, H, W);
   if (!on_device) need += (in_img + out_img) * mb + 1024;
   KOCR_TRY(ctx->ws_reserve(need));
+  KOCR_TRY(craft_taps_begin(ctx, N));
+  struct TapsEnd {  // also on an error return: no later launch records into this call's taps
+    kocr_ctx* c;
+    ~TapsEnd() { craft_taps_batch(c, -1); }
+  } taps_end{ctx};
   for (int s = 0; s < N; s += mb) {
     const int nb = std::min(mb, N - s);
     ctx->ws_reset();
+    craft_taps_batch(ctx, s);
     const void* d_in;
     float* d_out;
     if (on_device) {
@@ -671,6 +677,13 @@ int kocr_set_schedule(kocr_ctx* ctx, int fold_linear_chain, int fold_upsample) {
   if (!ctx) return KOCR_EINVAL;
   ctx->opt_linfold = fold_linear_chain != 0;
   ctx->opt_upfold = fold_upsample != 0;
+  return KOCR_OK;
+}
+
+int kocr_get_schedule(kocr_ctx* ctx, int* fold_linear_chain, int* fold_upsample) {
+  if (!ctx || !fold_linear_chain || !fold_upsample) return KOCR_EINVAL;
+  *fold_linear_chain = ctx->opt_linfold ? 1 : 0;
+  *fold_upsample = ctx->opt_upfold ? 1 : 0;
   return KOCR_OK;
 }
 

@@ -126,6 +126,7 @@ struct Arena {
 
 struct CraftNet;
 struct CrnnNet;
+struct CraftTaps;
 
 struct kocr_ctx {
   int device = 0;
@@ -187,6 +188,10 @@ struct kocr_ctx {
 
   CraftNet* craft = nullptr;
   CrnnNet* crnn = nullptr;
+  // kocr_craft_set_taps (craft.cpp): the detector tensors recorded during kocr_craft_forward; nullptr = no taps.  While a
+  // tapped launch runs, tap_rows collects the profiler row names of what it launched (ProfScope), i.e. its kernel family.
+  CraftTaps* taps = nullptr;
+  std::vector<std::string>* tap_rows = nullptr;
 
   // the device-resident results of the last successful kocr_pipeline call (kocr_pipeline_device_results): boxes in the pl
   // arena, counts in the post-processing scratch, label rows in the io arena -- all valid until the next call that uses
@@ -232,6 +237,7 @@ inline void* kocr_ctx::ws_alloc(size_t bytes) { return arena_alloc(ws, bytes); }
 struct ProfScope {
   kocr_ctx* c;
   ProfScope(kocr_ctx* ctx, const char* name, double flops, double bytes) : c(ctx) {
+    if (c->tap_rows) c->tap_rows->push_back(name);
     if (c->prof_on) c->prof_begin(name, flops, bytes);
   }
   ~ProfScope() {
@@ -381,6 +387,8 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
 int craft_forward(kocr_ctx* ctx, const void* d_img, int dtype, int N, int H, int W, float* d_heat);
 size_t craft_workspace_bytes(int N, int H, int W);
 void craft_free(kocr_ctx* ctx);
+int craft_taps_begin(kocr_ctx* ctx, int N);  // kocr_craft_forward with taps on: restart the record for N images
+void craft_taps_batch(kocr_ctx* ctx, int n0); // ... the next micro-batch starts at image n0 (-1: the call is over)
 
 // crnn.cpp
 void crnn_free(kocr_ctx* ctx);

@@ -227,9 +227,176 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
   return KOCR_OK;
 }
 
+// ---- taps (kocr_craft_set_taps): named detector tensors copied to host memory during the forward -----------------
+// A tapped launch enqueues, on ctx->stream, a device-to-host copy of the input view it reads and of its slots just
+// before it, and of what it wrote (full and / or pooled output, with their slots) just after it -- LivePool reuses every
+// buffer, so nothing can be read back later.  Nothing else changes: no kernel, no launch order, no buffer.
+struct CraftTaps {
+  struct Part {
+    int N = 0, H = 0, W = 0, C = 0;  // N = 0: not recorded
+    std::vector<float> data;          // [N][H][W][C] of the whole call (every micro-batch)
+    std::vector<float> amax;          // [N] slot values as floats, -1 = the tensor had no slots
+  };
+  struct Tap {
+    std::string name;
+    std::vector<std::string> rows;  // profiler rows of the launch (ProfScope)
+    Part part[3];                   // input, full output, pooled output
+  };
+  bool all = false;
+  std::vector<std::string> sel;
+  std::vector<Tap> rec;  // launch order; reserved up front so that pointers into it stay valid during the call
+  int N = 0, n0 = -1;    // images of the kocr_craft_forward call, first image of its current micro-batch (-1: none running)
+  Tap* find(const std::string& nm) {
+    for (Tap& t : rec)
+      if (t.name == nm) return &t;
+    return nullptr;
+  }
+};
+
+namespace {
+
+int tap_copy(kocr_ctx* ctx, CraftTaps::Part& pt, const Tensor& t) {
+  CraftTaps* tp = ctx->taps;
+  if (!pt.N) {
+    pt.N = tp->N;
+    pt.H = t.H;
+    pt.W = t.W;
+    pt.C = t.C;
+    pt.data.assign((size_t)pt.N * t.H * t.W * t.C, 0.f);
+    pt.amax.assign(pt.N, -1.f);
+  }
+  if (pt.H != t.H || pt.W != t.W || pt.C != t.C || tp->n0 + t.N > pt.N)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_forward: tap shape changed between micro-batches");
+  float* dst = pt.data.data() + (size_t)tp->n0 * t.H * t.W * t.C;
+  const size_t rows = t.pixels(), row = (size_t)t.C * sizeof(float);
+  if (t.cs == t.C && t.co == 0)
+    KOCR_HIP(ctx, hipMemcpyAsync(dst, t.p, rows * row, hipMemcpyDeviceToHost, ctx->stream));
+  else  // a channel slice of a wider buffer: the logical N x H x W x C tensor
+    KOCR_HIP(ctx, hipMemcpy2DAsync(dst, row, t.p + t.co, (size_t)t.cs * sizeof(float), row, rows, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+  if (t.amax)  // non-negative floats as their bits
+    KOCR_HIP(ctx, hipMemcpyAsync(pt.amax.data() + tp->n0, t.amax, (size_t)t.N * sizeof(unsigned), hipMemcpyDeviceToHost,
+                                 ctx->stream));
+  return KOCR_OK;
+}
+
+// before the launch of `name`: nullptr if it is not tapped, else its record, the input copy enqueued
+int tap_begin(kocr_ctx* ctx, const std::string& name, const Tensor* in, CraftTaps::Tap** out) {
+  *out = nullptr;
+  CraftTaps* tp = ctx->taps;
+  if (!tp || tp->n0 < 0 || !(tp->all || std::find(tp->sel.begin(), tp->sel.end(), name) != tp->sel.end())) return KOCR_OK;
+  CraftTaps::Tap* t = tp->find(name);
+  if (!t) {
+    if (tp->rec.size() == tp->rec.capacity()) KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_craft_forward: too many taps");
+    tp->rec.emplace_back();
+    t = &tp->rec.back();
+    t->name = name;
+  }
+  if (in && in->p) KOCR_TRY(tap_copy(ctx, t->part[0], *in));
+  t->rows.clear();
+  ctx->tap_rows = &t->rows;
+  *out = t;
+  return KOCR_OK;
+}
+
+// after it: what it wrote
+int tap_end(kocr_ctx* ctx, CraftTaps::Tap* t, const Tensor* full, const Tensor* pool) {
+  if (!t) return KOCR_OK;
+  ctx->tap_rows = nullptr;
+  if (full) KOCR_TRY(tap_copy(ctx, t->part[1], *full));
+  if (pool) KOCR_TRY(tap_copy(ctx, t->part[2], *pool));
+  return KOCR_OK;
+}
+
+}  // namespace
+
+int craft_taps_begin(kocr_ctx* ctx, int N) {
+  ctx->tap_rows = nullptr;
+  if (!ctx->taps) return KOCR_OK;
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // no copy of the previous call is still in flight
+  ctx->taps->rec.clear();
+  ctx->taps->rec.reserve(64);
+  ctx->taps->N = N;
+  ctx->taps->n0 = -1;
+  return KOCR_OK;
+}
+
+void craft_taps_batch(kocr_ctx* ctx, int n0) {
+  ctx->tap_rows = nullptr;
+  if (ctx->taps) ctx->taps->n0 = n0;
+}
+
+extern "C" {
+
+int kocr_craft_set_taps(kocr_ctx* ctx, int n, const char* const* names) {
+  if (!ctx || n < 0 || (n > 0 && !names)) return KOCR_EINVAL;
+  ctx->tap_rows = nullptr;
+  if (ctx->taps) {
+    KOCR_HIP(ctx, hipSetDevice(ctx->device));
+    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    delete ctx->taps;
+    ctx->taps = nullptr;
+  }
+  if (n == 0) return KOCR_OK;
+  CraftTaps* tp = new CraftTaps();
+  for (int i = 0; i < n; ++i) {
+    if (!names[i]) {
+      delete tp;
+      KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_set_taps: null name");
+    }
+    if (!strcmp(names[i], "*")) tp->all = true;
+    tp->sel.emplace_back(names[i]);
+  }
+  ctx->taps = tp;
+  return KOCR_OK;
+}
+
+int kocr_craft_tap_count(kocr_ctx* ctx) {
+  if (!ctx) return KOCR_EINVAL;
+  return ctx->taps ? (int)ctx->taps->rec.size() : 0;
+}
+
+int kocr_craft_tap_info(kocr_ctx* ctx, int i, char* name, char* kernel, int32_t* dims) {
+  if (!ctx) return KOCR_EINVAL;
+  if (!ctx->taps || i < 0 || i >= (int)ctx->taps->rec.size()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_tap_info: no such tap");
+  const CraftTaps::Tap& t = ctx->taps->rec[i];
+  if (name) snprintf(name, 64, "%s", t.name.c_str());
+  if (kernel) {
+    std::string k;
+    for (const std::string& r : t.rows) k += (k.empty() ? "" : "+") + r;
+    snprintf(kernel, 256, "%s", k.c_str());
+  }
+  if (dims)
+    for (int p = 0; p < 3; ++p) {
+      const CraftTaps::Part& pt = t.part[p];
+      dims[p * 4 + 0] = pt.N;
+      dims[p * 4 + 1] = pt.H;
+      dims[p * 4 + 2] = pt.W;
+      dims[p * 4 + 3] = pt.C;
+    }
+  return KOCR_OK;
+}
+
+int kocr_craft_get_tap(kocr_ctx* ctx, const char* name, int which, float* dst, float* amax_dst) {
+  if (!ctx || !name || which < 0 || which > 2) return KOCR_EINVAL;
+  CraftTaps::Tap* t = ctx->taps ? ctx->taps->find(name) : nullptr;
+  if (!t || !t->part[which].N) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_craft_get_tap: nothing recorded for ") + name);
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const CraftTaps::Part& pt = t->part[which];
+  if (dst) memcpy(dst, pt.data.data(), pt.data.size() * sizeof(float));
+  if (amax_dst) memcpy(amax_dst, pt.amax.data(), pt.amax.size() * sizeof(float));
+  return KOCR_OK;
+}
+
+}  // extern "C"
+
 void craft_free(kocr_ctx* ctx) {
   delete ctx->craft;
   ctx->craft = nullptr;
+  delete ctx->taps;
+  ctx->taps = nullptr;
+  ctx->tap_rows = nullptr;
 }
 
 namespace {
@@ -356,58 +523,87 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
   x0.p = (dtype == KOCR_F32) ? (float*)d_img : nullptr;
   const uint8_t* u8 = (dtype == KOCR_U8) ? (const uint8_t*)d_img : nullptr;
   const float* lut = DRY ? nullptr : net->d_lut;
+  // a launch with its taps (kocr_craft_set_taps): `in` as read, then `full` / `pool` as written; no taps -> the launch alone
+  auto tapped = [&](const std::string& name, const Tensor* in, const Tensor* full, const Tensor* pool, auto&& launch) -> int {
+    struct RowsOff {  // the launch's row collection ends with it, also when it fails
+      kocr_ctx* c;
+      ~RowsOff() { c->tap_rows = nullptr; }
+    } rows_off{ctx};
+    CraftTaps::Tap* t = nullptr;
+    KOCR_TRY(tap_begin(ctx, name, in, &t));
+    KOCR_TRY(launch());
+    return tap_end(ctx, t, full, pool);
+  };
+  // The 1x1 layers (slice5.2, the decoder's upconvN.conv.0 and their #y columns) on conv_ds whenever it takes the tensor:
+  // launch_conv's small-GEMM cut-off (dsplit_applicable) counts the pixels of the WHOLE batch, so an image whose level
+  // has fewer than 4096 pixels would otherwise change kernel -- and result -- with the number of images sharing its call.
+  // Where the cut-off is passed anyway (every level of the benchmark's pages) this is the kernel launch_conv chooses.
+  auto conv = [&](const char* name, const Tensor& in, const Tensor& out) -> int {
+    const ConvLayer& Lc = L(name);
+    return tapped(name, &in, &out, nullptr, [&]() {
+      if (Lc.KH == 1 && Lc.KW == 1 && !in.cellW && !out.cellW && out.p && dsplit_usable(ctx, Lc, in)) {
+        kocr_note_dispatch("dsplit", Lc, in);
+        return launch_conv_dsplit(ctx, Lc, in, out);
+      }
+      return launch_conv(ctx, Lc, in, nullptr, nullptr, out);
+    });
+  };
+  auto conv_pool = [&](const char* name, const Tensor& in, const Tensor& out, Tensor* pool, bool need_full) -> int {
+    return tapped(name, &in, need_full ? &out : nullptr, pool,
+                  [&]() { return launch_conv_pool(ctx, L(name), in, nullptr, nullptr, out, pool, need_full); });
+  };
 
   // ---- backbone (detection.py:312-335) ------------------------------------------------
   // conv + 2x2 max-pool: fused epilogue when the shape tiles, else two kernels; need_full: the pre-pool tensor is
   // consumed elsewhere (skip connection).  The full-resolution buffer of an un-needed tensor is returned at once.
   Tensor a1, a2, p1, b1, cat4, p2, c1, cat3, c3, p3, e1, cat2, f1, p4, g1, cat1, h0, h1;
   KOCR_TRY(mk(d.H, d.W, 64, &a1, true));
-  RUN(launch_conv(ctx, L("basenet.slice1.0"), x0, u8, lut, a1));
+  RUN(tapped("basenet.slice1.0", &x0, &a1, nullptr, [&]() { return launch_conv(ctx, L("basenet.slice1.0"), x0, u8, lut, a1); }));
   KOCR_TRY(mk(d.H, d.W, 64, &a2));
   KOCR_TRY(mk(d.H2, d.W2, 64, &p1, true));
-  RUN(launch_conv_pool(ctx, L("basenet.slice1.3"), a1, nullptr, nullptr, a2, &p1, /*need_full=*/false));
+  RUN(conv_pool("basenet.slice1.3", a1, a2, &p1, false));
   done(a1);
   done(a2);
   KOCR_TRY(mk(d.H2, d.W2, 128, &b1, true));
-  RUN(launch_conv(ctx, L("basenet.slice1.7"), p1, nullptr, nullptr, b1));
+  RUN(conv("basenet.slice1.7", p1, b1));
   done(p1);
   KOCR_TRY(mk(d.H2, d.W2, 192, &cat4));
   KOCR_TRY(mk(d.H4, d.W4, 128, &p2, true));
   const Tensor s1 = cat4.slice(64, 128);
-  RUN(launch_conv_pool(ctx, L("basenet.slice1.10"), b1, nullptr, nullptr, s1, &p2, /*need_full=*/true));  // s1: skip tensor
+  RUN(conv_pool("basenet.slice1.10", b1, s1, &p2, true));  // s1: skip tensor
   done(b1);
   KOCR_TRY(mk(d.H4, d.W4, 256, &c1, true));
-  RUN(launch_conv(ctx, L("basenet.slice2.14"), p2, nullptr, nullptr, c1));
+  RUN(conv("basenet.slice2.14", p2, c1));
   done(p2);
   KOCR_TRY(mk(d.H4, d.W4, 384, &cat3, true));
   const Tensor s2 = cat3.slice(128, 256);
-  RUN(launch_conv(ctx, L("basenet.slice2.17"), c1, nullptr, nullptr, s2));
+  RUN(conv("basenet.slice2.17", c1, s2));
   done(c1);
   KOCR_TRY(mk(d.H4, d.W4, 256, &c3));
   KOCR_TRY(mk(d.H8, d.W8, 256, &p3, true));
-  RUN(launch_conv_pool(ctx, L("basenet.slice3.20"), s2, nullptr, nullptr, c3, &p3, false));
+  RUN(conv_pool("basenet.slice3.20", s2, c3, &p3, false));
   done(c3);
   KOCR_TRY(mk(d.H8, d.W8, 512, &e1, true));
-  RUN(launch_conv(ctx, L("basenet.slice3.24"), p3, nullptr, nullptr, e1));
+  RUN(conv("basenet.slice3.24", p3, e1));
   done(p3);
   KOCR_TRY(mk(d.H8, d.W8, 768, &cat2, true));
   const Tensor s3 = cat2.slice(256, 512);
-  RUN(launch_conv(ctx, L("basenet.slice3.27"), e1, nullptr, nullptr, s3));
+  RUN(conv("basenet.slice3.27", e1, s3));
   done(e1);
   KOCR_TRY(mk(d.H8, d.W8, 512, &f1));
   KOCR_TRY(mk(d.H16, d.W16, 512, &p4, true));
-  RUN(launch_conv_pool(ctx, L("basenet.slice4.30"), s3, nullptr, nullptr, f1, &p4, false));
+  RUN(conv_pool("basenet.slice4.30", s3, f1, &p4, false));
   done(f1);
   KOCR_TRY(mk(d.H16, d.W16, 512, &g1, true));
-  RUN(launch_conv(ctx, L("basenet.slice4.34"), p4, nullptr, nullptr, g1));
+  RUN(conv("basenet.slice4.34", p4, g1));
   done(p4);
   KOCR_TRY(mk(d.H16, d.W16, 1536, &cat1, true));
   const Tensor s4 = cat1.slice(1024, 512);
-  RUN(launch_conv(ctx, L("basenet.slice4.37"), g1, nullptr, nullptr, s4));
+  RUN(conv("basenet.slice4.37", g1, s4));
   done(g1);
   // ---- slice5 (detection.py:365-378) ----------------------------------------------------
   KOCR_TRY(mk(d.H16, d.W16, 512, &h0, true));
-  RUN(launch_maxpool3x3s1(ctx, s4, h0));
+  RUN(tapped("maxpool3x3s1", &s4, &h0, nullptr, [&]() { return launch_maxpool3x3s1(ctx, s4, h0); }));
   KOCR_TRY(mk(d.H16, d.W16, 1024, &h1));
   Tensor u1a;
   KOCR_TRY(mk(d.H16, d.W16, 512, &u1a, true));
@@ -418,12 +614,13 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
     if (lin_fold) {  // see craft_load: slice5.1 -> slice5.2 -> upconv1.conv.0 as one dilated 3x3 plus a 1x1 over s4
       Tensor t = h1;  // the first half of h1's buffer, as a contiguous 512-channel tensor
       t.C = t.cs = 512;
-      KOCR_TRY(launch_conv(ctx, L("basenet.slice5#fold"), h0, nullptr, nullptr, t));
-      KOCR_TRY(launch_conv_dsplit(ctx, L("upconv1.conv.0#skip"), s4, u1a, &t));
+      KOCR_TRY(conv("basenet.slice5#fold", h0, t));
+      KOCR_TRY(tapped("upconv1.conv.0#skip", &s4, &u1a, nullptr,
+                      [&]() { return launch_conv_dsplit(ctx, L("upconv1.conv.0#skip"), s4, u1a, &t); }));
     } else {
-      KOCR_TRY(launch_conv(ctx, L("basenet.slice5.1"), h0, nullptr, nullptr, h1));
-      KOCR_TRY(launch_conv(ctx, L("basenet.slice5.2"), h1, nullptr, nullptr, cat1.slice(0, 1024)));
-      KOCR_TRY(launch_conv(ctx, L("upconv1.conv.0"), cat1, nullptr, nullptr, u1a));
+      KOCR_TRY(conv("basenet.slice5.1", h0, h1));
+      KOCR_TRY(conv("basenet.slice5.2", h1, cat1.slice(0, 1024)));
+      KOCR_TRY(conv("upconv1.conv.0", cat1, u1a));
     }
   }
   done(h0);
@@ -447,11 +644,12 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
       const bool fold = ctx->opt_upfold && dsplit_usable(ctx, Ls, skip) &&
                         2 * (size_t)t.H * t.W * t.C * 4 < ((size_t)1 << 31);  // two images of t within 32-bit offsets
       if (fold) {
-        KOCR_TRY(launch_conv(ctx, L((std::string(name) + "#y").c_str()), y, nullptr, nullptr, t));
-        KOCR_TRY(launch_conv_dsplit(ctx, Ls, skip, out, &t));
-      } else {
-        KOCR_TRY(launch_resize_bilinear(ctx, y, cat.slice(0, c_y)));
-        KOCR_TRY(launch_conv(ctx, L(name), cat, nullptr, nullptr, out));
+        KOCR_TRY(conv((std::string(name) + "#y").c_str(), y, t));
+        KOCR_TRY(tapped(Ls.name, &skip, &out, nullptr, [&]() { return launch_conv_dsplit(ctx, Ls, skip, out, &t); }));
+      } else {  // tap "resize:upconvN": the whole concat buffer after the resize (its skip channels included)
+        const std::string up = std::string("resize:") + std::string(name).substr(0, std::string(name).find('.'));
+        KOCR_TRY(tapped(up, &y, &cat, nullptr, [&]() { return launch_resize_bilinear(ctx, y, cat.slice(0, c_y)); }));
+        KOCR_TRY(conv(name, cat, out));
       }
     }
     done(t);
@@ -461,35 +659,41 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
   };
   Tensor u1b, u2a, u2b, u3a, u3b, u4a, feat, k0, k1, k2;
   KOCR_TRY(mk(d.H16, d.W16, 256, &u1b));
-  RUN(launch_conv(ctx, L("upconv1.conv.3"), u1a, nullptr, nullptr, u1b));
+  RUN(conv("upconv1.conv.3", u1a, u1b));
   done(u1a);
   KOCR_TRY(mk(d.H8, d.W8, 256, &u2a, true));
   KOCR_TRY(up_conv("upconv2.conv.0", u1b, cat2, u2a));
   KOCR_TRY(mk(d.H8, d.W8, 128, &u2b));
-  RUN(launch_conv(ctx, L("upconv2.conv.3"), u2a, nullptr, nullptr, u2b));
+  RUN(conv("upconv2.conv.3", u2a, u2b));
   done(u2a);
   KOCR_TRY(mk(d.H4, d.W4, 128, &u3a, true));
   KOCR_TRY(up_conv("upconv3.conv.0", u2b, cat3, u3a));
   KOCR_TRY(mk(d.H4, d.W4, 64, &u3b));
-  RUN(launch_conv(ctx, L("upconv3.conv.3"), u3a, nullptr, nullptr, u3b));
+  RUN(conv("upconv3.conv.3", u3a, u3b));
   done(u3a);
   KOCR_TRY(mk(d.H2, d.W2, 64, &u4a, true));
   KOCR_TRY(up_conv("upconv4.conv.0", u3b, cat4, u4a));
   KOCR_TRY(mk(d.H2, d.W2, 32, &feat, true));
-  RUN(launch_conv(ctx, L("upconv4.conv.3"), u4a, nullptr, nullptr, feat));
+  RUN(conv("upconv4.conv.3", u4a, feat));
   done(u4a);
   // ---- head (detection.py:392-410), linear output ---------------------------------------
   KOCR_TRY(mk(d.H2, d.W2, 32, &k0, true));
-  RUN(launch_conv(ctx, L("conv_cls.0"), feat, nullptr, nullptr, k0));
+  RUN(conv("conv_cls.0", feat, k0));
   done(feat);
   KOCR_TRY(mk(d.H2, d.W2, 32, &k1));
-  RUN(launch_conv(ctx, L("conv_cls.2"), k0, nullptr, nullptr, k1));
+  RUN(conv("conv_cls.2", k0, k1));
   done(k0);
   KOCR_TRY(mk(d.H2, d.W2, 16, &k2));
-  RUN(launch_conv(ctx, L("conv_cls.4"), k1, nullptr, nullptr, k2));
+  RUN(conv("conv_cls.4", k1, k2));
   done(k1);
   // conv_cls.6 + conv_cls.8 (1x1 16 -> 16 ReLU, 1x1 16 -> 2): one fused pass, no 16-channel round trip
-  RUN(launch_head_tail(ctx, L("conv_cls.6"), L("conv_cls.8"), k2, d_heat));
+  Tensor heat;  // tap view of the heat-map
+  heat.N = N;
+  heat.H = d.H2;
+  heat.W = d.W2;
+  heat.C = heat.cs = 2;
+  heat.p = d_heat;
+  RUN(tapped("head_tail", &k2, &heat, nullptr, [&]() { return launch_head_tail(ctx, L("conv_cls.6"), L("conv_cls.8"), k2, d_heat); }));
   done(k2);
 #undef RUN
   if (peak_out) *peak_out = pool.peak;

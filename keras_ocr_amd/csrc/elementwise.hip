@@ -95,7 +95,9 @@ __global__ void resize_bilinear_kernel(EwParams p) {
     const float fly = floorf(fy), flx = floorf(fx);
     const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), p.Hi - 1);
     const int x0 = max((int)flx, 0), x1 = min((int)ceilf(fx), p.Wi - 1);
-    const float yl = fy - fly, xl = fx - flx;
+    // weighted form (1 - l) a + l b: its rounding error is relative to the blend of |a|, |b| (bilinear(|y|)); the lerp
+    // a + (b - a) l rounds b - a at the scale of |a| even where l ~ 1 makes a's weight vanish
+    const float yl = fy - fly, xl = fx - flx, yk = 1.f - yl, xk = 1.f - xl;
     const size_t rb = (size_t)n * p.Hi;
     const float* b0 = p.in + ((rb + y0) * p.Wi) * p.in_cs + p.in_co + c4 * 4;
     const float* b1 = p.in + ((rb + y1) * p.Wi) * p.in_cs + p.in_co + c4 * 4;
@@ -105,20 +107,20 @@ __global__ void resize_bilinear_kernel(EwParams p) {
     const float4 br = *reinterpret_cast<const float4*>(b1 + (size_t)x1 * p.in_cs);
     float4 r;
     {
-      const float top = tl.x + (tr.x - tl.x) * xl, bot = bl.x + (br.x - bl.x) * xl;
-      r.x = top + (bot - top) * yl;
+      const float top = tl.x * xk + tr.x * xl, bot = bl.x * xk + br.x * xl;
+      r.x = top * yk + bot * yl;
     }
     {
-      const float top = tl.y + (tr.y - tl.y) * xl, bot = bl.y + (br.y - bl.y) * xl;
-      r.y = top + (bot - top) * yl;
+      const float top = tl.y * xk + tr.y * xl, bot = bl.y * xk + br.y * xl;
+      r.y = top * yk + bot * yl;
     }
     {
-      const float top = tl.z + (tr.z - tl.z) * xl, bot = bl.z + (br.z - bl.z) * xl;
-      r.z = top + (bot - top) * yl;
+      const float top = tl.z * xk + tr.z * xl, bot = bl.z * xk + br.z * xl;
+      r.z = top * yk + bot * yl;
     }
     {
-      const float top = tl.w + (tr.w - tl.w) * xl, bot = bl.w + (br.w - bl.w) * xl;
-      r.w = top + (bot - top) * yl;
+      const float top = tl.w * xk + tr.w * xl, bot = bl.w * xk + br.w * xl;
+      r.w = top * yk + bot * yl;
     }
     const size_t o = (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.out_cs + p.out_co + c4 * 4;
     *reinterpret_cast<float4*>(p.out + o) = r;

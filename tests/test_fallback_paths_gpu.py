@@ -51,6 +51,9 @@ def _run_config(switches):
     cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
            os.path.join(ROOT, "tests", "test_conv_gpu.py"), os.path.join(ROOT, "tests", "test_craft_gpu.py"),
            os.path.join(ROOT, "tests", "test_crnn_gpu.py"),
+           # every launch of the detector against its float64 bound, at the two small shapes (fused and floor pooling)
+           *(os.path.join(ROOT, "tests", f"test_craft_layers_gpu.py::test_every_layer_within_its_fp32_class_bound[default-{c}]")
+             for c in ("1x64x512_f32", "1x50x70_f32")),
            "-k", "fp32_class or heatmap_u8_input or ragged_page or probs_and_labels"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500, check=False)
     tail = (r.stdout + r.stderr)[-3000:]
@@ -62,8 +65,8 @@ def test_parity_suites_hold_on_the_fallback_paths():
     """Every configuration is its own pytest child process (every context of a child reads its switches), one after the other:
     three at a time was tried in round 5 and took FIVE times longer -- processes sharing one GPU pay a full wave-state
     save / restore of these 512-register, 160-KB-LDS kernels at every switch.  The children run the dispatch-sensitive
-    cases only (every fp64-bounded convolution case, two CRAFT heat-maps incl. the ragged page, the recogniser at 1 / 5 / 40
-    crops): about ten seconds each.  A failure names its configuration."""
+    cases only (every fp64-bounded convolution case, two CRAFT heat-maps incl. the ragged page, every detector layer against
+    its fp64 bound at two small shapes, the recogniser at 1 / 5 / 40 crops): about ten seconds each.  A failure names its configuration."""
     failed = []
     for c in CONFIGS:
         ok, tail = _run_config(c)

@@ -82,3 +82,58 @@ def test_resize_formula_of_the_kernels_is_the_reference_resize():
         got = top + (bot - top) * yl[:, None]
         want = F.interpolate(torch.from_numpy(x)[None, None], size=(ho, wo), mode="bilinear", align_corners=False)[0, 0].numpy()
         assert np.abs(got - want).max() < 1e-12
+
+
+def _graph_by_layers(w, x, fold_linear, fold_up):
+    """The detector, launch by launch as craft.cpp runs it, every launch through oracle.craft.layer_f64 (float64)."""
+    from oracle import craft as ocraft
+
+    def pool(t):
+        return F.max_pool2d(torch.from_numpy(t).permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1).numpy()
+
+    def lay(name, t, up=None):
+        v, bnd, unit = ocraft.layer_f64(w, name, t, up=up, window=3)
+        assert (bnd >= np.abs(v) - 1e-9 * (1 + np.abs(v))).all() and (unit >= 0).all(), name
+        return v
+
+    a = lay("basenet.slice1.0", x)
+    a = lay("basenet.slice1.7", pool(lay("basenet.slice1.3", a)))
+    s1 = lay("basenet.slice1.10", a)
+    s2 = lay("basenet.slice2.17", lay("basenet.slice2.14", pool(s1)))
+    s3 = lay("basenet.slice3.27", lay("basenet.slice3.24", pool(lay("basenet.slice3.20", s2))))
+    s4 = lay("basenet.slice4.37", lay("basenet.slice4.34", pool(lay("basenet.slice4.30", s3))))
+    h0 = F.max_pool2d(torch.from_numpy(s4).permute(0, 3, 1, 2), 3, 1, 1).permute(0, 2, 3, 1).numpy()
+    if fold_linear:
+        y = lay("upconv1.conv.0#skip", s4, up=lay("basenet.slice5#fold", h0))
+    else:
+        s5 = lay("basenet.slice5.2", lay("basenet.slice5.1", h0))
+        y = lay("upconv1.conv.0", np.concatenate([s5, s4], 3))
+    y = lay("upconv1.conv.3", y)
+    for n, skip in ((2, s3), (3, s2), (4, s1)):
+        if fold_up:
+            y = lay(f"upconv{n}.conv.0#skip", skip, up=lay(f"upconv{n}.conv.0#y", y))
+        else:
+            yt = torch.from_numpy(y).permute(0, 3, 1, 2)
+            r = F.interpolate(yt, size=skip.shape[1:3], mode="bilinear", align_corners=False).permute(0, 2, 3, 1).numpy()
+            y = lay(f"upconv{n}.conv.0", np.concatenate([r, skip], 3))
+        y = lay(f"upconv{n}.conv.3", y)
+    for c in (0, 2, 4):
+        y = lay(f"conv_cls.{c}", y)
+    return lay("head_tail", y)
+
+
+def test_layer_f64_reproduces_the_oracle_graph_in_every_schedule():
+    """oracle.craft.layer_f64 (the per-layer reference of tests/test_craft_layers_gpu.py), chained over the whole detector
+    in each of the library's schedules -- plain, folded slice5 chain, split decoder 1x1s, composite head tail -- equals the
+    oracle's fp32 forward to fp32 round-off (odd sizes: floor pooling), and its bound terms dominate the values."""
+    import keras_ocr_amd
+    from oracle import craft as ocraft
+
+    w = keras_ocr_amd.weights.synthetic_craft_weights(1234)
+    x = np.random.default_rng(3).standard_normal((1, 50, 70, 3)).astype(np.float32)
+    want = ocraft.craft_forward(w, x)
+    scale = float(np.abs(want).max())
+    for fl, fu in ((False, False), (True, True), (True, False)):
+        got = _graph_by_layers(w, x.astype(np.float64), fl, fu)
+        err = float(np.abs(got - want).max()) / scale
+        assert got.shape == want.shape and err < 1e-5, (fl, fu, err)
