@@ -274,6 +274,22 @@ int kocr_set_schedule(kocr_ctx* ctx, int fold_linear_chain, int fold_upsample);
 /* The switches as they stand (1 = on): the environment's choice until kocr_set_schedule changes it. */
 int kocr_get_schedule(kocr_ctx* ctx, int* fold_linear_chain, int* fold_upsample);
 
+/* ---- minAreaRect rule of getBoxes ----------------------------------------------------------------------------------------
+ * Which enclosing rectangle kocr_get_boxes, kocr_detect and kocr_pipeline give a word (detection.py:273,
+ * cv2.boxPoints(cv2.minAreaRect(contour))); the diamond test, the roll and the x2 that follow are the same under both:
+ *   KOCR_RECT_EXACT   (default): the min-area rectangle over the hull's edges compared in exact integer arithmetic, equal
+ *                     areas going to the first edge; corners from exact integer numerators and one float64 division
+ *                     (oracle/postproc.py::min_area_box).  Geometrically exact; differs from cv2 by float32 round-off, and
+ *                     where cv2's float32 areas break a tie or a near-tie the other way, by the rectangle chosen;
+ *   KOCR_RECT_OPENCV: OpenCV's own arithmetic: float32 rotating calipers over the hull in cv2.convexHull's order with
+ *                     the last of equal areas kept, the corner solve in float32, the angle through float64 atan2 and
+ *                     degrees, RotatedRect::points with float32 cos / sin (oracle/postproc.py::min_area_box_cv32).
+ * A per-context setting; any other value is KOCR_EINVAL.  kocr_get_min_area_rect returns the rule in force. */
+#define KOCR_RECT_EXACT 0
+#define KOCR_RECT_OPENCV 1
+int kocr_set_min_area_rect(kocr_ctx* ctx, int rule);
+int kocr_get_min_area_rect(const kocr_ctx* ctx);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx
  * stream; kocr_profile_report fills parallel arrays (up to cap rows) with per-kernel-name

@@ -4,6 +4,7 @@ The shared library is built in-tree by ``__graft_entry__.build()`` /
 ``make -C keras_ocr_amd/csrc``.  There is NO CPU fallback: if the library is missing or
 no HIP device is visible, the product fails loudly here.
 """
+import contextlib
 import ctypes
 import os
 
@@ -13,6 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkocr.so")
 
 KOCR_U8, KOCR_F32 = 0, 1
+# minAreaRect rule of getBoxes (include/kocr.h: KOCR_RECT_EXACT / KOCR_RECT_OPENCV)
+MIN_AREA_RECT_RULES = {"exact": 0, "opencv": 1}
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -85,6 +88,8 @@ def load_library():
         "kocr_get_split_mode": (ci, [vp]),
         "kocr_set_schedule": (ci, [vp, ci, ci]),
         "kocr_get_schedule": (ci, [vp, _c_int_p, _c_int_p]),
+        "kocr_set_min_area_rect": (ci, [vp, ci]),
+        "kocr_get_min_area_rect": (ci, [vp]),
         "kocr_profile_enable": (ci, [vp, ci]),
         "kocr_profile_reset": (ci, [vp]),
         "kocr_profile_report": (ci, [vp, ci, ctypes.c_char_p, _c_i64_p, _c_dbl_p, _c_dbl_p, _c_dbl_p]),
@@ -253,12 +258,17 @@ class Context:
 
     # -- detection.getBoxes ----------------------------------------------------------------
     def get_boxes(self, heat, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4,
-                  size_threshold=10, cap=None):
+                  size_threshold=10, cap=None, min_area_rect=None):
         """heat: (N,h,w,2) float32 host array -> list of (n_i,4,2) float32 arrays
-        (``np.array([])`` for an image without boxes, detection.py:286)."""
+        (``np.array([])`` for an image without boxes, detection.py:286).  ``min_area_rect``: ``"exact"`` /
+        ``"opencv"`` for this call only, ``None`` = the context's rule (``set_min_area_rect``)."""
         y = np.ascontiguousarray(heat, dtype=np.float32)
         if y.ndim != 4 or y.shape[3] != 2:
             raise ValueError("heat must have shape (N,h,w,2)")
+        with self._min_area_rect_scope(min_area_rect):
+            return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap)
+
+    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap):
         n, h, w, _ = y.shape
         cap = int(cap) if cap else 1024
         while True:
@@ -278,8 +288,14 @@ class Context:
 
     # -- Detector.detect, device-resident heat-maps -----------------------------------------------
     def detect(self, images, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,
-               micro_batch=0, cap=None):
-        """images: (N,H,W,3) uint8 (raw RGB) or float32 (normalised).  Returns list of (n_i,4,2) boxes."""
+               micro_batch=0, cap=None, min_area_rect=None):
+        """images: (N,H,W,3) uint8 (raw RGB) or float32 (normalised).  Returns list of (n_i,4,2) boxes.
+        ``min_area_rect``: as ``get_boxes``."""
+        with self._min_area_rect_scope(min_area_rect):
+            return self._detect(images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch,
+                                cap)
+
+    def _detect(self, images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap):
         x = np.ascontiguousarray(images)
         dt = KOCR_U8 if x.dtype == np.uint8 else KOCR_F32
         if dt == KOCR_F32:
@@ -408,9 +424,16 @@ class Context:
 
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
-                 link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None):
+                 link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
+                 min_area_rect=None):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns
-        (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32)."""
+        (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``."""
+        with self._min_area_rect_scope(min_area_rect):
+            return self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
+                                  size_threshold, micro_batch, on_device, cap, max_crops)
+
+    def _pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
+                  size_threshold, micro_batch, on_device, cap, max_crops):
         n = len(ptrs)
         keep = [np.ascontiguousarray(p, dtype=np.uint8) if not isinstance(p, (int, np.integer)) else p for p in ptrs]
         c_ptrs = (ctypes.c_void_p * n)(*[int(p) if isinstance(p, (int, np.integer)) else p.ctypes.data for p in keep])
@@ -507,6 +530,30 @@ class Context:
         self._check(self._lib.kocr_get_schedule(self._h, ctypes.byref(lin), ctypes.byref(up)))
         return bool(lin.value), bool(up.value)
 
+    # -- minAreaRect rule of getBoxes (include/kocr.h: kocr_set_min_area_rect) ---------------
+    def set_min_area_rect(self, rule):
+        """``"exact"`` (default: exact-integer min-area rectangle) or ``"opencv"`` (cv2.minAreaRect's float32 rotating
+        calipers and cv2.boxPoints) for every later getBoxes on this context."""
+        self._check(self._lib.kocr_set_min_area_rect(self._h, _min_area_rect_code(rule)))
+
+    def get_min_area_rect(self):
+        code = self._check(self._lib.kocr_get_min_area_rect(self._h))
+        return {v: k for k, v in MIN_AREA_RECT_RULES.items()}[code]
+
+    @contextlib.contextmanager
+    def _min_area_rect_scope(self, rule):
+        """A per-call rule: set for the block, the context's own restored afterwards (None: the context's rule)."""
+        if rule is None:
+            yield
+            return
+        code = _min_area_rect_code(rule)
+        old = self._check(self._lib.kocr_get_min_area_rect(self._h))
+        self._check(self._lib.kocr_set_min_area_rect(self._h, code))
+        try:
+            yield
+        finally:
+            self._check(self._lib.kocr_set_min_area_rect(self._h, old))
+
     # -- measurement -------------------------------------------------------------------
     def profile_enable(self, on=True):
         self._check(self._lib.kocr_profile_enable(self._h, int(bool(on))))
@@ -551,6 +598,12 @@ class Context:
                         "frac_below_2^-4": b4 / nz if nz else 0.0, "frac_below_2^-14": b14 / nz if nz else 0.0,
                         "share_of_sum_abs_below_2^-4": sb / sa if sa else 0.0}
         return rows
+
+
+def _min_area_rect_code(rule):
+    if not isinstance(rule, str) or rule not in MIN_AREA_RECT_RULES:
+        raise ValueError(f"min_area_rect must be one of {sorted(MIN_AREA_RECT_RULES)}, got {rule!r}")
+    return MIN_AREA_RECT_RULES[rule]
 
 
 _default_ctx = None

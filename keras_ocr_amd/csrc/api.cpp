@@ -687,6 +687,15 @@ int kocr_get_schedule(kocr_ctx* ctx, int* fold_linear_chain, int* fold_upsample)
   return KOCR_OK;
 }
 
+int kocr_set_min_area_rect(kocr_ctx* ctx, int rule) {
+  if (!ctx) return KOCR_EINVAL;
+  if (rule != KOCR_RECT_EXACT && rule != KOCR_RECT_OPENCV) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_min_area_rect: unknown rule");
+  ctx->min_area_rect = rule;
+  return KOCR_OK;
+}
+
+int kocr_get_min_area_rect(const kocr_ctx* ctx) { return ctx ? ctx->min_area_rect : KOCR_EINVAL; }
+
 int kocr_profile_enable(kocr_ctx* ctx, int on) {
   if (!ctx) return KOCR_EINVAL;
   KOCR_TRY(ctx->prof_flush());

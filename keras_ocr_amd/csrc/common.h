@@ -139,6 +139,8 @@ struct kocr_ctx {
   // CRAFT schedule options (craft.cpp: folded linear layers); read ONCE from KOCR_LINFOLD / KOCR_UPFOLD when the
   // context is created, changed through kocr_set_schedule
   bool opt_linfold = true, opt_upfold = true;
+  // min-area rectangle rule of getBoxes (postproc.hip K13), changed through kocr_set_min_area_rect
+  int min_area_rect = KOCR_RECT_EXACT;
   // kernel selection switches, read ONCE per context in kocr_create from the environment variable of the same name in
   // upper case with the KOCR_ prefix (KOCR_LSTM16=0 ...): the fallback kernels can be exercised per context, inside
   // one process

@@ -16,12 +16,15 @@
 //       first (max raster-first pixel), K12 per-row extents of that fragment
 //   K13 convex hull (monotone chain over row extents), exact-integer min-area rectangle over
 //       hull edges, diamond test, clockwise roll, x2                      (:273-285)
+//       (or, per context, OpenCV's float32 rotating calipers: kocr_set_min_area_rect)
 //
 // HBM-bound integer/byte work: one pass over the heat-map (8 B/px algorithmic), everything
 // after K5 touches only the kept components' ROIs.  Compiled with -ffp-contract=off: the
 // float32/float64 geometry is compared bit-for-bit with the CPU oracle.
 #include "common.h"
+#include <cfloat>
 #include <climits>
+#include <cmath>
 
 namespace {
 
@@ -441,9 +444,11 @@ __device__ __forceinline__ long cross3(int2 o, int2 a, int2 b) {
 }
 
 // ---- K13: hull + min-area rectangle, one WAVE per component ------------------------------------
-// Lane 0 builds the hull (monotone chain over the row extents, sequential by nature); the O(n^2) search over the hull's
-// edges for the smallest enclosing rectangle runs one edge per lane.  Everything is exact integer arithmetic and the
-// reduction keeps the FIRST edge among equal minima, i.e. what the sequential loop over the edges returns.
+// Lane 0 builds the hull (monotone chain over the row extents, sequential by nature).  RULE == KOCR_RECT_EXACT: the O(n^2)
+// search over the hull's edges for the smallest enclosing rectangle runs one edge per lane.  Everything is exact integer
+// arithmetic and the reduction keeps the FIRST edge among equal minima, i.e. what the sequential loop over the edges
+// returns.  RULE == KOCR_RECT_OPENCV: lane 0 runs OpenCV's O(n) float32 rotating calipers on the same hull
+// (cv_min_area_box above).
 __device__ __forceinline__ long shfl_long(long v, int src) {
   const int lo = __shfl((int)v, src), hi = __shfl((int)(v >> 32), src);
   return (long)(((unsigned long)(unsigned)hi << 32) | (unsigned)lo);
@@ -455,6 +460,166 @@ __device__ __forceinline__ long shfl_xor_long(long v, int mask) {
 // num_a / L_a < num_b / L_b, exactly (all non-negative, L > 0)
 __device__ __forceinline__ bool ratio_less(long num_a, long L_a, long num_b, long L_b) {
   return (unsigned __int128)(unsigned long)num_a * (unsigned long)L_b < (unsigned __int128)(unsigned long)num_b * (unsigned long)L_a;
+}
+
+// ---- KOCR_RECT_OPENCV: cv2.boxPoints(cv2.minAreaRect(hull)) in OpenCV's own arithmetic ---------------------------------
+// oracle/postproc.py::min_area_box_cv32, operation by operation: rotating calipers (rotcalipers.cpp, CALIPERS_MINAREARECT)
+// in float32 where OpenCV computes in float and in double where it computes in double, then RotatedRect::points.  One lane.
+// H: the hull as k_boxes builds it (clockwise on screen, H[0] top-most / left-most); cv2.convexHull lists it in the other
+// orientation from the same first vertex, [H[0]] + H[1:][::-1], so OpenCV's vertex i is H[(n - i) % n].  The edge vectors
+// vect[i] = pt[i+1] - pt[i] and their float32 1/|vect[i]| are recomputed from the vertices where they are needed (integer
+// coordinates < 4096: the float32 differences are exact) instead of being stored; the hull may live in global scratch.
+struct CvEdge {
+  float x, y, il;  // vect[i], inv_len[i]
+};
+
+__device__ __forceinline__ float2 cv_pt(const int2* H, int n, int i) {
+  const int2 p = H[i ? n - i : 0];
+  return make_float2((float)p.x, (float)p.y);
+}
+
+__device__ __forceinline__ CvEdge cv_edge(const int2* H, int n, int i) {
+  const float2 p0 = cv_pt(H, n, i), p1 = cv_pt(H, n, i + 1 < n ? i + 1 : 0);
+  const double dx = (double)p1.x - (double)p0.x, dy = (double)p1.y - (double)p0.y;
+  CvEdge e;
+  e.x = (float)dx;
+  e.y = (float)dy;
+  e.il = (float)(1.0 / sqrt(dx * dx + dy * dy));
+  return e;
+}
+
+__device__ void cv_min_area_box(const int2* H, int n, float* bx, float* by) {
+  if (n == 1) {
+    const float2 p = cv_pt(H, n, 0);
+    for (int i = 0; i < 4; ++i) {
+      bx[i] = p.x;
+      by[i] = p.y;
+    }
+    return;
+  }
+  float cx, cy, width, height, angle;
+  if (n == 2) {  // centre = midpoint, width = |p1 - p0|, height 0, angle = atan2(dy, dx)
+    const float2 p0 = cv_pt(H, n, 0), p1 = cv_pt(H, n, 1);
+    cx = (p0.x + p1.x) * 0.5f;
+    cy = (p0.y + p1.y) * 0.5f;
+    const double dx = (double)(p1.x - p0.x), dy = (double)(p1.y - p0.y);
+    width = (float)sqrt(dx * dx + dy * dy);
+    height = 0.f;
+    angle = (float)atan2(dy, dx);
+  } else {
+    // extreme vertices: the first of equal extremes, in OpenCV's vertex order
+    int left = 0, bottom = 0, right = 0, top = 0;
+    const float2 q0 = cv_pt(H, n, 0);
+    float left_x = q0.x, right_x = q0.x, top_y = q0.y, bottom_y = q0.y;
+    for (int i = 0; i < n; ++i) {
+      const float2 q = cv_pt(H, n, i);
+      if (q.x < left_x) { left_x = q.x; left = i; }
+      if (q.x > right_x) { right_x = q.x; right = i; }
+      if (q.y > top_y) { top_y = q.y; top = i; }
+      if (q.y < bottom_y) { bottom_y = q.y; bottom = i; }
+    }
+    // orientation: sign of the first non-zero cross product of consecutive edges (double)
+    float orientation = 0.f;
+    {
+      const CvEdge last = cv_edge(H, n, n - 1);
+      double ax = (double)last.x, ay = (double)last.y;
+      for (int i = 0; i < n; ++i) {
+        const CvEdge e = cv_edge(H, n, i);
+        const double bxx = (double)e.x, byy = (double)e.y;
+        const double convexity = ax * byy - ay * bxx;
+        if (convexity != 0) {
+          orientation = convexity > 0 ? 1.f : -1.f;
+          break;
+        }
+        ax = bxx;
+        ay = byy;
+      }
+    }
+    float base_a = orientation, base_b = 0.f;
+    int seq[4] = {bottom, right, top, left};
+    CvEdge ed[4];  // vect / inv_len of the four calipers' current edges
+    for (int k = 0; k < 4; ++k) ed[k] = cv_edge(H, n, seq[k]);
+    float minarea = FLT_MAX;
+    int b_li = 0, b_bi = 0;
+    float b_a = 0.f, b_b = 0.f, b_w = 0.f, b_h = 0.f;
+    for (int it = 0; it < n; ++it) {
+      float dp[4];
+      dp[0] = base_a * ed[0].x + base_b * ed[0].y;
+      dp[1] = -base_b * ed[1].x + base_a * ed[1].y;
+      dp[2] = -base_a * ed[2].x - base_b * ed[2].y;
+      dp[3] = base_b * ed[3].x - base_a * ed[3].y;
+      float maxcos = dp[0] * ed[0].il;
+      int main = 0;
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {
+        const float cosalpha = dp[k] * ed[k].il;
+        if (cosalpha > maxcos) {
+          main = k;
+          maxcos = cosalpha;
+        }
+      }
+      // seq / ed are indexed by constants only (unrolled selects): they stay in registers
+      CvEdge pe = ed[0];
+#pragma unroll
+      for (int k = 1; k < 4; ++k)
+        if (k == main) pe = ed[k];
+      const float lead_x = pe.x * pe.il, lead_y = pe.y * pe.il;
+      switch (main) {
+        case 0: base_a = lead_x; base_b = lead_y; break;
+        case 1: base_a = lead_y; base_b = -lead_x; break;
+        case 2: base_a = -lead_x; base_b = -lead_y; break;
+        default: base_a = -lead_y; base_b = lead_x; break;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == main) {
+          seq[k] = seq[k] + 1 < n ? seq[k] + 1 : 0;
+          ed[k] = cv_edge(H, n, seq[k]);
+        }
+      const float2 s0 = cv_pt(H, n, seq[0]), s1 = cv_pt(H, n, seq[1]), s2 = cv_pt(H, n, seq[2]), s3 = cv_pt(H, n, seq[3]);
+      float dx = s1.x - s3.x, dy = s1.y - s3.y;
+      const float w = dx * base_a + dy * base_b;
+      dx = s2.x - s0.x;
+      dy = s2.y - s0.y;
+      const float h = -dx * base_b + dy * base_a;
+      const float area = w * h;
+      if (area <= minarea) {  // the LAST of equal areas
+        minarea = area;
+        b_li = seq[3];
+        b_a = base_a;
+        b_w = w;
+        b_b = base_b;
+        b_h = h;
+        b_bi = seq[0];
+      }
+    }
+    // corner solve
+    const float a1 = b_a, b1 = b_b, a2 = -b_b, b2 = b_a;
+    const float2 pl = cv_pt(H, n, b_li), pb = cv_pt(H, n, b_bi);
+    const float c1 = a1 * pl.x + pl.y * b1;
+    const float c2 = a2 * pb.x + pb.y * b2;
+    const float idet = 1.f / (a1 * b2 - a2 * b1);
+    const float px = (c1 * b2 - c2 * b1) * idet, py = (a1 * c2 - a2 * c1) * idet;
+    const float o1x = a1 * b_w, o1y = b1 * b_w, o2x = a2 * b_h, o2y = b2 * b_h;
+    cx = px + (o1x + o2x) * 0.5f;
+    cy = py + (o1y + o2y) * 0.5f;
+    width = (float)sqrt((double)o1x * (double)o1x + (double)o1y * (double)o1y);
+    height = (float)sqrt((double)o2x * (double)o2x + (double)o2y * (double)o2y);
+    angle = (float)atan2((double)o1y, (double)o1x);
+  }
+  angle = (float)((double)angle * 180.0 / M_PI);  // box.angle = (float)(box.angle*180/CV_PI)
+  // RotatedRect::points
+  const double ang = (double)angle * M_PI / 180.0;
+  const float b = (float)cos(ang) * 0.5f;
+  const float a = (float)sin(ang) * 0.5f;
+  bx[0] = cx - a * height - b * width;
+  by[0] = cy + b * height - a * width;
+  bx[1] = cx + a * height - b * width;
+  by[1] = cy - b * height - a * width;
+  bx[2] = 2.f * cx - bx[0];
+  by[2] = 2.f * cy - by[0];
+  bx[3] = 2.f * cx - bx[1];
+  by[3] = 2.f * cy - by[1];
 }
 
 constexpr int KB_CAP = 1024;  // candidate points up to which k_boxes builds its chains in LDS
@@ -472,6 +637,7 @@ constexpr int KB_CAP = 1024;  // candidate points up to which k_boxes builds its
     t1 = (pt);                                                    \
   } while (0)
 
+template <int RULE>
 __global__ __launch_bounds__(64) void k_boxes(CanvasArgs a) {
   __shared__ int2 hull_s[2 * (KB_CAP + 4)];
   __shared__ int2 cand_s[KB_CAP];
@@ -659,7 +825,7 @@ __global__ __launch_bounds__(64) void k_boxes(CanvasArgs a) {
     const int2* H = lower;
     long bnum = 0, bL = 0, bumin = 0, bumax = 0, bvmin = 0, bvmax = 0;
     int bdx = 0, bdy = 0, bidx = INT_MAX;
-    if (n >= 3) {
+    if (RULE == KOCR_RECT_EXACT && n >= 3) {
       for (int i = lane; i < n; i += 64) {
         const int2 p0 = H[i], p1 = H[i + 1 < n ? i + 1 : 0];
         const long dx = p1.x - p0.x, dy = p1.y - p0.y;
@@ -719,7 +885,9 @@ __global__ __launch_bounds__(64) void k_boxes(CanvasArgs a) {
     }
     if (lane != 0) continue;
     float bx[4], by[4];
-    if (n == 1) {
+    if constexpr (RULE == KOCR_RECT_OPENCV) {
+      cv_min_area_box(H, n, bx, by);
+    } else if (n == 1) {
       for (int i = 0; i < 4; ++i) {
         bx[i] = (float)H[0].x;
         by[i] = (float)H[0].y;
@@ -895,7 +1063,10 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
     hipLaunchKernelGGL(k_merge8, grid_for(a.total), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_flatten_select, grid_for(a.total), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_row_extents, grid_for((size_t)a.total_rows * 64), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_boxes, grid_for(ncomp, 1), dim3(64), 0, s, a);
+    if (ctx->min_area_rect == KOCR_RECT_OPENCV)
+      hipLaunchKernelGGL(k_boxes<KOCR_RECT_OPENCV>, grid_for(ncomp, 1), dim3(64), 0, s, a);
+    else
+      hipLaunchKernelGGL(k_boxes<KOCR_RECT_EXACT>, grid_for(ncomp, 1), dim3(64), 0, s, a);
   }
   KOCR_HIP(ctx, hipGetLastError());
   if (n_empty_out && !dev) {

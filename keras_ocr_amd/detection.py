@@ -28,6 +28,20 @@ def load_torch_state_dict(weights_path):
     return {k: v.numpy() for k, v in pretrained.items() if k.split(".")[-1] != "num_batches_tracked"}
 
 
+def getBoxes(y_pred, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,  # pylint: disable=invalid-name
+             min_area_rect=None):
+    """detection.getBoxes (detection.py:207-287) on the default context: (N,h,w,2) float32 heat-maps -> list of (n_i,4,2)
+    float32 boxes (``np.array([])`` for an image without boxes).
+
+    ``min_area_rect`` picks how ``cv2.boxPoints(cv2.minAreaRect(contour))`` (detection.py:273) is computed:
+    ``"exact"`` -- the min-area rectangle in exact arithmetic (the default); ``"opencv"`` -- OpenCV's own float32 rotating
+    calipers and ``RotatedRect::points`` (include/kocr.h: KOCR_RECT_OPENCV); ``None`` -- the context's rule
+    (``Context.set_min_area_rect``)."""
+    return _lib.default_context().get_boxes(y_pred, detection_threshold=detection_threshold, text_threshold=text_threshold,
+                                            link_threshold=link_threshold, size_threshold=size_threshold,
+                                            min_area_rect=min_area_rect)
+
+
 class _CraftModel:
     """Stands in for ``detector.model`` (inner seam #1): ``predict(X) -> heat-maps``."""
 
@@ -74,9 +88,10 @@ class Detector:
         self.model = _CraftModel(self._ctx)
 
     def detect(self, images: typing.List[typing.Union[np.ndarray, str]], detection_threshold=0.7, text_threshold=0.4,
-               link_threshold=0.4, size_threshold=10, **kwargs):
+               link_threshold=0.4, size_threshold=10, min_area_rect=None, **kwargs):
         """Detector.detect (detection.py:745-785): list/array of same-sized HxWx3 RGB images (or
-        paths) -> list of (n_i,4,2) float32 box arrays."""
+        paths) -> list of (n_i,4,2) float32 box arrays.  ``min_area_rect``: ``"exact"`` / ``"opencv"`` for this
+        call (see ``getBoxes``), ``None`` = the context's rule."""
         images = [tools.read(image) for image in images]
         if not images:
             return []
@@ -90,4 +105,4 @@ class Detector:
             batch /= variance * 255
         return self._ctx.detect(batch, detection_threshold=detection_threshold, text_threshold=text_threshold,
                                 link_threshold=link_threshold, size_threshold=size_threshold,
-                                micro_batch=kwargs.get("batch_size", 0) or 0)
+                                micro_batch=kwargs.get("batch_size", 0) or 0, min_area_rect=min_area_rect)
