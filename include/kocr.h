@@ -172,6 +172,29 @@ int kocr_crnn_classes(kocr_ctx* ctx);
 int kocr_crnn_set_rnn_steps_to_discard(kocr_ctx* ctx, int steps);
 int kocr_crnn_label_width(kocr_ctx* ctx);
 
+/* ---- the recogniser's other two models: recognizer.backbone and recognizer.training_model (recognition.py:319-349) ---- */
+/* keras.backend.ctc_batch_cost(y_true, y_pred, input_length, label_length) (recognition.py:340-347), forward only; the rule
+ * is DESIGN.md section 4: q_t = (y_t + 1e-7) / sum (y_t + 1e-7), blank = C - 1, loss = -log of the summed probability of
+ * every alignment of labels[m][0 .. label_lengths[m]) to the first input_lengths[m] frames.  y_pred: M x T x C float32
+ * probabilities; labels: HOST int32 rows of label_stride entries (entries from label_lengths[m] on are ignored; the
+ * reference pads with -1); label_lengths / input_lengths: HOST int32[M]; loss: float32[M].  y_pred and loss are device
+ * pointers when on_device is set.  KOCR_EINVAL, naming the sample, before anything is launched: input_lengths[m] outside
+ * [1, T], label_lengths[m] outside [0, min(input_lengths[m], label_stride)], a label outside [0, C - 2].  A label that
+ * fits in length but not with a blank between its repeats ("aa" in 2 frames) has loss +inf. */
+int kocr_ctc_batch_cost(kocr_ctx* ctx, const float* y_pred, int M, int T, int C, const int32_t* labels, int label_stride,
+                        const int32_t* label_lengths, const int32_t* input_lengths, float* loss, int on_device);
+/* recognizer.training_model.predict([crops, labels, input_length, label_length]) (recognition.py:334-349): the recogniser
+ * up to fc_12, then kocr_ctc_batch_cost's rule on fc_12's softmax, with T = kocr_crnn_label_width() (the frames after
+ * rnn_steps_to_discard).  The probabilities never leave HBM and are bit for bit those kocr_crnn_forward returns, so the
+ * loss equals kocr_ctc_batch_cost on them bit for bit.  crops: M x 31 x 200 float32 (device when on_device), loss:
+ * float32[M] (device when on_device); labels and lengths as kocr_ctc_batch_cost (HOST arrays). */
+int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* labels, int label_stride,
+                       const int32_t* label_lengths, const int32_t* input_lengths, float* loss, int on_device);
+/* recognizer.backbone.predict (recognition.py:319-320): feats M x 50 x 256 float32, the Concatenate output
+ * [lstm_11 | lstm_11_back] of every RNN step (rnn_steps_to_discard does not apply).  Buffers are device pointers when
+ * on_device is set. */
+int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device);
+
 /* ---- Detector.detect (detection.py:745-785): compute_input + predict + getBoxes in one call; the
  * heat-maps stay in HBM.  Arguments as kocr_craft_forward + kocr_get_boxes; counts is a HOST array. */
 int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W,

@@ -70,6 +70,9 @@ def load_library():
         "kocr_crnn_classes": (ci, [vp]),
         "kocr_crnn_label_width": (ci, [vp]),
         "kocr_crnn_set_rnn_steps_to_discard": (ci, [vp, ci]),
+        "kocr_ctc_batch_cost": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, ci]),
+        "kocr_crnn_ctc_loss": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, ci]),
+        "kocr_crnn_features": (ci, [vp, vp, ci, vp, ci]),
         "kocr_get_boxes": (ci, [vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, vp, vp, ci, ci]),
         "kocr_warp_crops": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, ci]),
         "kocr_warp_quads": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
@@ -255,6 +258,64 @@ class Context:
 
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
+
+    # -- recognizer.backbone / training_model (recognition.py:319-349) ------------------------------------------------
+    def _check_value(self, rc):
+        """_check, but a refused argument (KOCR_EINVAL) is a ValueError: the reference / TF raise one there."""
+        if rc == -1:
+            raise ValueError(self._lib.kocr_last_error(self._h).decode("utf-8", "replace"))
+        return self._check(rc)
+
+    @staticmethod
+    def _ctc_host_args(labels, label_lengths, input_lengths, m):
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim != 2 or lab.shape[0] != m:
+            raise ValueError(f"labels must have shape (M, Lmax) with M = {m}, got {lab.shape}")
+        ll = np.ascontiguousarray(np.reshape(label_lengths, -1), dtype=np.int32)
+        il = np.ascontiguousarray(np.reshape(input_lengths, -1), dtype=np.int32)
+        if ll.shape != (m,) or il.shape != (m,):
+            raise ValueError(f"label_lengths and input_lengths must hold M = {m} values")
+        return lab, ll, il
+
+    def ctc_batch_cost(self, y_pred, labels, label_lengths, input_lengths):
+        """keras.backend.ctc_batch_cost on the GPU (kocr_ctc_batch_cost).  y_pred (M,T,C) float32 probabilities, labels (M,Lmax)
+        integer classes (entries from label_lengths[m] on are ignored), label_lengths / input_lengths M integers.  Returns the
+        per-sample loss (M,) float32.  A refused argument raises ValueError naming the sample."""
+        y = np.ascontiguousarray(y_pred, dtype=np.float32)
+        if y.ndim != 3:
+            raise ValueError(f"y_pred must have shape (M, T, C), got {y.shape}")
+        m, t, c = y.shape
+        lab, ll, il = self._ctc_host_args(labels, label_lengths, input_lengths, m)
+        loss = np.zeros(m, np.float32)
+        self._check_value(self._lib.kocr_ctc_batch_cost(self._h, _ptr(y), m, t, c, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il),
+                                                        _ptr(loss), 0))
+        return loss
+
+    def crnn_ctc_loss(self, crops, labels, label_lengths, input_lengths):
+        """training_model.predict (kocr_crnn_ctc_loss): crops (M,31,200[,1]) float32 in [0,1], labels / lengths as
+        ctc_batch_cost with T = crnn_label_width().  Returns the per-sample loss (M,) float32."""
+        x = self._crops(crops)
+        m = x.shape[0]
+        lab, ll, il = self._ctc_host_args(labels, label_lengths, input_lengths, m)
+        loss = np.zeros(m, np.float32)
+        self._check_value(self._lib.kocr_crnn_ctc_loss(self._h, _ptr(x), m, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il), _ptr(loss), 0))
+        return loss
+
+    def crnn_features(self, crops):
+        """backbone.predict (kocr_crnn_features): crops (M,31,200[,1]) -> the BiLSTM features (M,50,256) float32."""
+        x = self._crops(crops)
+        feats = np.zeros((x.shape[0], 50, 256), np.float32)
+        self._check(self._lib.kocr_crnn_features(self._h, _ptr(x), x.shape[0], _ptr(feats), 0))
+        return feats
+
+    @staticmethod
+    def _crops(crops):
+        x = np.ascontiguousarray(crops, dtype=np.float32)
+        if x.ndim == 4 and x.shape[-1] == 1:
+            x = x[..., 0]
+        if x.ndim != 3 or x.shape[1:] != (31, 200):
+            raise ValueError("crops must have shape (M,31,200[,1])")
+        return np.ascontiguousarray(x)
 
     # -- detection.getBoxes ----------------------------------------------------------------
     def get_boxes(self, heat, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4,

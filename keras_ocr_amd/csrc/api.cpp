@@ -359,6 +359,131 @@ int kocr_crnn_forward(kocr_ctx* ctx, const float* crops, int M, int32_t* labels,
   return KOCR_OK;
 }
 
+// labels rows [s, s + nb) of a validated batch (ctc_validate) into the workspace as [nb][Lmax] | len[nb] | in_len[nb]; the
+// host staging vector is returned so that it outlives the asynchronous copy (the callers synchronise before returning)
+static int ctc_stage_labels(kocr_ctx* ctx, const char* fn, const int32_t* labels, int label_stride, const int32_t* label_lengths,
+                            const int32_t* input_lengths, int s, int nb, int Lmax, std::vector<int32_t>& host, int** d_lab,
+                            int** d_len, int** d_in) {
+  const int ls = std::max(Lmax, 1);
+  host.assign((size_t)nb * (ls + 2), -1);
+  for (int i = 0; i < nb; ++i) {
+    const int m = s + i;
+    for (int k = 0; k < label_lengths[m]; ++k) host[(size_t)i * ls + k] = labels[(size_t)m * label_stride + k];
+    host[(size_t)nb * ls + i] = label_lengths[m];
+    host[(size_t)nb * (ls + 1) + i] = input_lengths[m];
+  }
+  int* d = (int*)ctx->ws_alloc(host.size() * sizeof(int32_t));
+  if (!d) KOCR_FAIL(ctx, KOCR_ENOMEM, std::string(fn) + ": workspace exhausted");
+  KOCR_HIP(ctx, hipMemcpyAsync(d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  *d_lab = d;
+  *d_len = d + (size_t)nb * ls;
+  *d_in = d + (size_t)nb * (ls + 1);
+  return KOCR_OK;
+}
+
+int kocr_ctc_batch_cost(kocr_ctx* ctx, const float* y_pred, int M, int T, int C, const int32_t* labels, int label_stride,
+                        const int32_t* label_lengths, const int32_t* input_lengths, float* loss, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_ctc_batch_cost";
+  if (M < 0 || T < 1 || C < 1 || label_stride < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_ctc_batch_cost: bad sizes");
+  if (M > 0 && (!y_pred || !labels || !label_lengths || !input_lengths || !loss))
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_ctc_batch_cost: null buffer");
+  int Lmax = 0;
+  KOCR_TRY(ctc_validate(ctx, fn, M, T, C, labels, label_stride, label_lengths, input_lengths, &Lmax));
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t yb = (size_t)M * T * C * sizeof(float), lb = (size_t)M * sizeof(float);
+  const size_t ib = (size_t)M * (std::max(Lmax, 1) + 2) * sizeof(int32_t);
+  KOCR_TRY(ctx->ws_reserve(ib + (on_device ? 0 : yb + lb) + 2048));
+  ctx->ws_reset();
+  std::vector<int32_t> staged;
+  int *d_lab, *d_len, *d_in;
+  KOCR_TRY(ctc_stage_labels(ctx, fn, labels, label_stride, label_lengths, input_lengths, 0, M, Lmax, staged, &d_lab, &d_len, &d_in));
+  const float* d_y = y_pred;
+  float* d_loss = loss;
+  if (!on_device) {
+    float* dy = (float*)ctx->ws_alloc(yb);
+    d_loss = (float*)ctx->ws_alloc(lb);
+    if (!dy || !d_loss) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_ctc_batch_cost: workspace exhausted");
+    KOCR_HIP(ctx, hipMemcpyAsync(dy, y_pred, yb, hipMemcpyHostToDevice, ctx->stream));
+    d_y = dy;
+  }
+  KOCR_TRY(launch_ctc_loss(ctx, /*logits=*/false, d_y, M, T, C, 0, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
+  if (!on_device) KOCR_HIP(ctx, hipMemcpyAsync(loss, d_loss, lb, hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KOCR_OK;
+}
+
+int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* labels, int label_stride,
+                       const int32_t* label_lengths, const int32_t* input_lengths, float* loss, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_crnn_ctc_loss";
+  if (M < 0 || label_stride < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_ctc_loss: bad sizes");
+  if (M > 0 && (!crops || !labels || !label_lengths || !input_lengths || !loss))
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_ctc_loss: null buffer");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_ctc_loss: call kocr_load_crnn first");
+  const int LW = crnn_label_width(ctx);
+  int Lmax = 0;
+  KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, labels, label_stride, label_lengths, input_lengths, &Lmax));
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = std::min(M, 1024);
+  const size_t cb = (size_t)31 * 200 * sizeof(float), ib = (std::max(Lmax, 1) + 2) * sizeof(int32_t);
+  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, C) + (ib + (on_device ? 0 : cb + sizeof(float))) * mb + 4096));
+  std::vector<int32_t> staged;
+  for (int s = 0; s < M; s += mb) {
+    const int nb = std::min(mb, M - s);
+    ctx->ws_reset();
+    int *d_lab, *d_len, *d_in;
+    KOCR_TRY(ctc_stage_labels(ctx, fn, labels, label_stride, label_lengths, input_lengths, s, nb, Lmax, staged, &d_lab, &d_len, &d_in));
+    const float* d_c = crops + (size_t)s * 31 * 200;
+    float* d_loss = loss + s;
+    if (!on_device) {
+      float* dc = (float*)ctx->ws_alloc(cb * nb);
+      d_loss = (float*)ctx->ws_alloc(sizeof(float) * nb);
+      if (!dc || !d_loss) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_crnn_ctc_loss: workspace exhausted");
+      KOCR_HIP(ctx, hipMemcpyAsync(dc, d_c, cb * nb, hipMemcpyHostToDevice, ctx->stream));
+      d_c = dc;
+    }
+    KOCR_TRY(crnn_ctc_loss(ctx, d_c, nb, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
+    if (!on_device) KOCR_HIP(ctx, hipMemcpyAsync(loss + s, d_loss, sizeof(float) * nb, hipMemcpyDeviceToHost, ctx->stream));
+    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `staged` is reused by the next batch
+  }
+  return KOCR_OK;
+}
+
+int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (M < 0 || (M > 0 && (!crops || !feats))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_features: null buffer");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_features: call kocr_load_crnn first");
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = std::min(M, 1024);
+  const size_t cb = (size_t)31 * 200 * sizeof(float), fb = (size_t)50 * 256 * sizeof(float);
+  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, C) + (on_device ? 0 : (cb + fb) * mb + 2048)));
+  for (int s = 0; s < M; s += mb) {
+    const int nb = std::min(mb, M - s);
+    ctx->ws_reset();
+    const float* d_c = crops + (size_t)s * 31 * 200;
+    float* d_f = feats + (size_t)s * 50 * 256;
+    if (!on_device) {
+      float* dc = (float*)ctx->ws_alloc(cb * nb);
+      d_f = (float*)ctx->ws_alloc(fb * nb);
+      if (!dc || !d_f) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_crnn_features: workspace exhausted");
+      KOCR_HIP(ctx, hipMemcpyAsync(dc, d_c, cb * nb, hipMemcpyHostToDevice, ctx->stream));
+      d_c = dc;
+    }
+    KOCR_TRY(crnn_forward(ctx, d_c, nb, nullptr, nullptr, CRNN_FEATURES, d_f));
+    if (!on_device) {
+      KOCR_HIP(ctx, hipMemcpyAsync(feats + (size_t)s * 50 * 256, d_f, fb * nb, hipMemcpyDeviceToHost, ctx->stream));
+      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+  }
+  return KOCR_OK;
+}
+
 int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float detection_threshold,
                    float text_threshold, float link_threshold, int size_threshold, float* boxes,
                    int32_t* counts, int cap, int on_device) {

@@ -400,7 +400,24 @@ int crnn_classes(kocr_ctx* ctx);
 int crnn_label_width(kocr_ctx* ctx);  // 50 - rnn_steps_to_discard (48)
 int crnn_set_discard(kocr_ctx* ctx, int d);
 size_t crnn_workspace_bytes(int M, int n_classes);
-int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs);
+// How far crnn_forward runs: the whole recogniser with the greedy decode (kocr_crnn_forward), up to fc_12's logits
+// (kocr_crnn_ctc_loss: *d_logits = [M][50][n_classes] in the workspace), or up to the Concatenate output (kocr_crnn_features:
+// written to d_feats [M][50][256] instead of the workspace).  The launches before the stop are the same in all three.
+enum CrnnStop { CRNN_DECODE, CRNN_LOGITS, CRNN_FEATURES };
+int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
+                 float* d_feats = nullptr, const float** d_logits = nullptr);
+// training_model (recognition.py:334-349): crnn_forward to the logits, then ctc_loss_kernel on fc_12's softmax of frames
+// rnn_steps_to_discard .. + input_length - 1; labels / lengths already validated (ctc_validate) and on the device
+int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
+                  float* d_loss, int Lmax);
+// keras.backend.ctc_batch_cost's refusals on host arrays, before anything is launched: T_m in [1, T],
+// L_m in [0, min(T_m, label_stride)], labels[m][0 .. L_m) in [0, C - 2]; KOCR_EINVAL naming the sample.  *Lmax = max L_m.
+int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32_t* labels, int label_stride,
+                 const int32_t* label_lengths, const int32_t* input_lengths, int* Lmax);
+
+// crnn_kernels.hip
+int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, int C, int t0, const int* d_lab, int lstride,
+                    const int* d_len, const int* d_in_len, float* d_loss, int Lmax);
 
 // postproc.hip
 // dev (optional): device-side results for a caller that keeps going on the stream -- the per-image counts and the

@@ -18,6 +18,7 @@
 //     Add (recognition.py:305) is folded into the next projection by stacking its kernel over
 //     the [forward | backward] channel halves; Concatenate (:319) is the same buffer.
 #include "common.h"
+#include <algorithm>
 #include <cmath>
 
 int launch_crnn_input(kocr_ctx* ctx, const float* d_crops, float* d_x, int M, int Hc, int Wc);
@@ -211,8 +212,10 @@ size_t crnn_workspace_bytes(int M, int n_classes) {
   return t + 8192;
 }
 
-// d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48)
-int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs) {
+// d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
+// `stop` / d_feats / d_logits: common.h
+int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
+                 const float** d_logits) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -377,13 +380,54 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   KOCR_TRY(mk(M, T, 1, 8 * UNITS, &xp));
   KOCR_TRY(mk(M, T, 1, 2 * UNITS, &r1));
   KOCR_TRY(mk(M, T, 1, 2 * UNITS, &r2));
+  if (stop == CRNN_FEATURES) r2.p = d_feats;  // the backbone's output (recognition.py:319-320) goes straight to the caller
   KOCR_TRY(conv("lstm_10_xproj", f9, xp));
   KOCR_TRY(launch_lstm(ctx, xp.p, net->U[0], net->U[1], r1.p, M, T));
   KOCR_TRY(conv("lstm_11_xproj", r1, xp));
   KOCR_TRY(launch_lstm(ctx, xp.p, net->U[2], net->U[3], r2.p, M, T));
+  if (stop == CRNN_FEATURES) return KOCR_OK;
   // fc_12 + softmax + decode (recognition.py:321-328, 169-184)
   KOCR_TRY(mk(M, T, 1, net->n_classes, &lg));
   KOCR_TRY(conv("fc_12", r2, lg));
+  if (stop == CRNN_LOGITS) {
+    *d_logits = lg.p;
+    return KOCR_OK;
+  }
   KOCR_TRY(launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs));
+  return KOCR_OK;
+}
+
+int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
+                  float* d_loss, int Lmax) {
+  const float* d_lg = nullptr;
+  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
+  if (M <= 0) return KOCR_OK;
+  return launch_ctc_loss(ctx, /*logits=*/true, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, d_lab, lstride, d_len, d_in_len,
+                         d_loss, Lmax);
+}
+
+int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32_t* labels, int label_stride,
+                 const int32_t* label_lengths, const int32_t* input_lengths, int* Lmax) {
+  const std::string f = fn;
+  *Lmax = 0;
+  for (int m = 0; m < M; ++m) {
+    const std::string sm = "sample " + std::to_string(m);
+    const int Tm = input_lengths[m], L = label_lengths[m];
+    if (Tm < 1 || Tm > T)
+      KOCR_FAIL(ctx, KOCR_EINVAL, f + ": " + sm + ": input_length " + std::to_string(Tm) + " outside [1, " + std::to_string(T) + "]");
+    if (L < 0 || L > Tm)
+      KOCR_FAIL(ctx, KOCR_EINVAL, f + ": " + sm + ": label_length " + std::to_string(L) + " outside [0, input_length = " +
+                                      std::to_string(Tm) + "] (not enough time for the target transition sequence)");
+    if (L > label_stride)
+      KOCR_FAIL(ctx, KOCR_EINVAL, f + ": " + sm + ": label_length " + std::to_string(L) + " exceeds the label row width " +
+                                      std::to_string(label_stride));
+    for (int i = 0; i < L; ++i) {
+      const int c = labels[(size_t)m * label_stride + i];
+      if (c < 0 || c > C - 2)
+        KOCR_FAIL(ctx, KOCR_EINVAL, f + ": " + sm + ": label " + std::to_string(c) + " at position " + std::to_string(i) +
+                                        " outside [0, " + std::to_string(C - 2) + "] (the blank is " + std::to_string(C - 1) + ")");
+    }
+    *Lmax = std::max(*Lmax, L);
+  }
   return KOCR_OK;
 }

@@ -10,6 +10,8 @@
 //   ctc_kernel          fc_12 softmax + CTCDecoder (recognition.py:169-184, 322-328): one wave per
 //                       crop, lanes = classes, per-step argmax as a wavefront reduction, repeat
 //                       merge + blank removal by lane 0.
+//   ctc_loss_kernel     keras.backend.ctc_batch_cost (recognition.py:340-347): CTC forward algorithm in
+//                       log space, one wave per sample, states over the lanes.
 #include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -278,6 +280,38 @@ __global__ __launch_bounds__(256) void lstm16_kernel(const float* __restrict__ x
   }
 }
 
+// ---- fc_12's softmax (recognition.py:324), shared by ctc_kernel and ctc_loss_kernel<true> so that the loss of the logits is
+// computed on exactly the probabilities kocr_crnn_forward returns: p(c) = expf(row[c] - max) / sum, lane l owning the classes
+// l, l + 64, ...; per-lane sums in ascending class order, then the xor butterfly.
+// Per-lane argmax over its classes (ascending class index: first maximum wins), then the wave-level reduction of
+// (value, index) pairs with lowest index on ties; every lane ends with the row's maximum and its first index.
+__device__ __forceinline__ void ctc_row_argmax(const float* __restrict__ row, int C, int lane, float& bv, int& bi) {
+  bv = -INFINITY;
+  bi = 0x7fffffff;
+  for (int c = lane; c < C; c += 64) {
+    const float v = row[c];
+    if (v > bv) {
+      bv = v;
+      bi = c;
+    }
+  }
+  for (int o = 32; o; o >>= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (ov > bv || (ov == bv && oi < bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+}
+__device__ __forceinline__ float ctc_row_expsum(const float* __restrict__ row, int C, int lane, float mx) {
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += expf(row[c] - mx);
+  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
+  return s;
+}
+__device__ __forceinline__ float ctc_softmax(float v, float mx, float s) { return expf(v - mx) / s; }
+
 // logits: [M][T][C]; labels: [M][T-discard] (-1 padded); probs (nullable): [M][T-discard][C].
 // One wave per crop; lane l owns classes l, l+64, ... (any alphabet size).
 __global__ void ctc_kernel(const float* __restrict__ logits, int M, int T, int C, int discard, int* __restrict__ labels,
@@ -290,30 +324,12 @@ __global__ void ctc_kernel(const float* __restrict__ logits, int M, int T, int C
   int prev = -1, k = 0;
   for (int t = 0; t < To; ++t) {
     const float* row = logits + ((size_t)m * T + t + discard) * C;
-    // per-lane argmax over its classes (ascending class index: first maximum wins), then the
-    // wave-level reduction of (value, index) pairs with lowest index on ties
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-      const float v = row[c];
-      if (v > bv) {
-        bv = v;
-        bi = c;
-      }
-    }
-    for (int o = 32; o; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
+    float bv;
+    int bi;
+    ctc_row_argmax(row, C, lane, bv, bi);
     if (probs) {
-      float s = 0.f;
-      for (int c = lane; c < C; c += 64) s += expf(row[c] - bv);
-      for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
-      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = expf(row[c] - bv) / s;
+      const float s = ctc_row_expsum(row, C, lane, bv);
+      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = ctc_softmax(row[c], bv, s);
     }
     if (lane == 0) {
       if (bi != prev && bi != blank) labels[(size_t)m * To + k++] = bi;
@@ -322,6 +338,81 @@ __global__ void ctc_kernel(const float* __restrict__ logits, int M, int T, int C
   }
   if (lane == 0)
     for (; k < To; ++k) labels[(size_t)m * To + k] = -1;
+}
+
+// ---- CTC loss: keras.backend.ctc_batch_cost (recognition.py:340-347), the forward algorithm of DESIGN.md section 4 ----------
+// q_t(c) = (y[t][c] + eps) / sum_c' (y[t][c'] + eps), eps = 1e-7 (TF ctc_loss's softmax of log(y + eps)); extended label
+// l' = (b, l_1, b, ..., l_L, b), S = 2L + 1 states, blank b = C - 1; loss = -log(alpha_{T_m-1}(S-1) + alpha_{T_m-1}(S-2)).
+// One wave (= one workgroup) per sample; the states are spread over the 64 lanes in chunks of 64, log(alpha) of the previous
+// and the current frame in LDS (2 x Sp floats, Sp = the padded state count of the longest label).  Per frame: one wave
+// reduction of the normaliser over the C classes, then per state a gather of y[t][l'_s].  Float32 log space; a log-sum-exp
+// whose terms are all -inf stays -inf, never NaN.  Masked states: s > 2t + 1 cannot be reached yet, s < S - 2(T_m - t) can no
+// longer reach the end; both are -inf.
+// LOGITS = false: y is [M][T][C] probabilities (kocr_ctc_batch_cost), t0 = 0.
+// LOGITS = true: y is fc_12's output [M][T][C] (kocr_crnn_ctc_loss); frame t is row t0 + t (rnn_steps_to_discard) and its
+// probabilities are ctc_kernel's, bit for bit (ctc_row_argmax / ctc_row_expsum / ctc_softmax).
+// lab: [M][lstride] int32 (entries < len[m] are classes in [0, C-2]), len / in_len: [M]; loss: [M]
+constexpr float CTC_EPS = 1e-7f;  // keras.backend.epsilon()
+
+__device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
+  const float mx = fmaxf(a, fmaxf(b, c));
+  if (mx == -INFINITY) return -INFINITY;
+  return mx + logf(expf(a - mx) + expf(b - mx) + expf(c - mx));
+}
+
+template <bool LOGITS>
+__global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ y, int T, int C, int t0,
+                                                      const int* __restrict__ lab, int lstride, const int* __restrict__ len,
+                                                      const int* __restrict__ in_len, float* __restrict__ loss, int Sp) {
+  extern __shared__ float la[];  // [2][Sp]
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int L = len[m], Tm = in_len[m], S = 2 * L + 1, blank = C - 1;
+  const int* l = lab + (size_t)m * lstride;
+  for (int s = lane; s < 2 * Sp; s += 64) la[s] = -INFINITY;
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < Tm; ++t) {
+    const float* row = y + ((size_t)m * T + t0 + t) * C;
+    float mx = 0.f, es = 1.f;
+    if (LOGITS) {
+      int bi;
+      ctc_row_argmax(row, C, lane, mx, bi);
+      es = ctc_row_expsum(row, C, lane, mx);
+    }
+    float z = 0.f;
+    for (int c = lane; c < C; c += 64) z += (LOGITS ? ctc_softmax(row[c], mx, es) : row[c]) + CTC_EPS;
+    for (int o = 32; o; o >>= 1) z += __shfl_xor(z, o);
+    const float logz = logf(z);
+    const int lo = max(0, S - 2 * (Tm - t)), hi = min(S - 1, 2 * t + 1);
+    const float* prev = la + (cur ^ 1) * Sp;
+    float* nxt = la + cur * Sp;
+    for (int s0 = lo & ~63; s0 <= hi; s0 += 64) {
+      const int s = s0 + lane;
+      if (s >= S) break;
+      float a = -INFINITY;
+      if (s >= lo && s <= hi) {
+        const int cls = (s & 1) ? l[s >> 1] : blank;
+        const float v = row[cls];
+        const float lq = logf((LOGITS ? ctc_softmax(v, mx, es) : v) + CTC_EPS) - logz;
+        if (t == 0) {
+          a = lq;  // s <= 1 here (hi = 1)
+        } else {
+          const float a1 = s >= 1 ? prev[s - 1] : -INFINITY;
+          const float a2 = ((s & 1) && s >= 3 && l[s >> 1] != l[(s >> 1) - 1]) ? prev[s - 2] : -INFINITY;
+          a = ctc_lse3(prev[s], a1, a2) + lq;
+        }
+      }
+      nxt[s] = a;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (lane == 0) {
+    const float* fin = la + (cur ^ 1) * Sp;
+    const float a = fin[S - 1], b = L > 0 ? fin[S - 2] : -INFINITY;
+    const float mxv = fmaxf(a, b);
+    loss[m] = mxv == -INFINITY ? INFINITY : -(mxv + logf(expf(a - mxv) + expf(b - mxv)));
+  }
 }
 
 int launch_crnn_input(kocr_ctx* ctx, const float* d_crops, float* d_x, int M, int Hc, int Wc) {
@@ -457,6 +548,25 @@ int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int di
   ProfScope ps(ctx, "ctc_greedy", 0, 4.0 * M * T * C);
   hipLaunchKernelGGL(ctc_kernel, dim3((M + 3) / 4), dim3(256), 0, ctx->stream, d_logits, M, T, C, discard, d_labels,
                      d_probs);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// y: device [M][T][C] (logits: fc_12's output, frames t0 .. t0 + T_m - 1; else probabilities, t0 = 0); d_lab: device
+// [M][lstride]; d_len / d_in_len: device [M], validated on the host (ctc_check); d_loss: device [M]
+int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, int C, int t0, const int* d_lab, int lstride,
+                    const int* d_len, const int* d_in_len, float* d_loss, int Lmax) {
+  if (M <= 0) return KOCR_OK;
+  const int Sp = (2 * Lmax + 1 + 63) & ~63;
+  const size_t lds = 2 * (size_t)Sp * sizeof(float);
+  if (lds > 64 * 1024) KOCR_FAIL(ctx, KOCR_ECAPACITY, "ctc_loss: labels longer than 8159 are not supported");
+  ProfScope ps(ctx, logits ? "ctc_loss_logits" : "ctc_loss", 0, 4.0 * M * T * C * (logits ? 3 : 1));
+  if (logits)
+    hipLaunchKernelGGL(ctc_loss_kernel<true>, dim3(M), dim3(64), lds, ctx->stream, d_y, T, C, t0, d_lab, lstride, d_len, d_in_len,
+                       d_loss, Sp);
+  else
+    hipLaunchKernelGGL(ctc_loss_kernel<false>, dim3(M), dim3(64), lds, ctx->stream, d_y, T, C, t0, d_lab, lstride, d_len, d_in_len,
+                       d_loss, Sp);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }

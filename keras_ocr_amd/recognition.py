@@ -79,6 +79,153 @@ class _Model:
         return self._ctx.crnn_forward(X)
 
 
+def _integral(a, what):
+    """float / int array -> int64, ValueError unless every value is an integer (Keras feeds lengths and labels as float)."""
+    a = np.asarray(a)
+    if a.dtype.kind in "iub":
+        return a.astype(np.int64)
+    f = a.astype(np.float64)
+    if not np.all(np.isfinite(f)) or np.any(f != np.round(f)) or np.any(np.abs(f) > 2 ** 31 - 1):
+        raise ValueError(f"{what} must hold integers")
+    return f.astype(np.int64)
+
+
+def _ctc_host_inputs(y_true, input_length, label_length, m):
+    """Keras's (M, Lmax) labels and (M, 1) lengths -> int32 labels (entries from label_length on replaced by -1: they are
+    ignored, so they need not be integers) and int32 lengths; ValueError on anything that is not an integer."""
+    ll = np.reshape(_integral(label_length, "label_length"), -1)
+    il = np.reshape(_integral(input_length, "input_length"), -1)
+    if ll.shape != (m,) or il.shape != (m,):
+        raise ValueError(f"input_length and label_length must have shape (M, 1) with M = {m}")
+    y = np.asarray(y_true)
+    if y.ndim != 2 or y.shape[0] != m:
+        raise ValueError(f"y_true must have shape (M, max_string_length) with M = {m}, got {y.shape}")
+    keep = np.arange(y.shape[1])[np.newaxis, :] < np.clip(ll, 0, None)[:, np.newaxis]
+    labels = np.full(y.shape, -1, np.int64)
+    for i in range(m):
+        if keep[i].any():
+            row = _integral(y[i][keep[i]], f"y_true (sample {i})")
+            if np.any(np.abs(row) > 2 ** 31 - 1):
+                raise ValueError(f"y_true (sample {i}) holds a label outside int32")
+            labels[i][keep[i]] = row
+    for what, a in (("label_length", ll), ("input_length", il)):
+        if np.any(np.abs(a) > 2 ** 31 - 1):
+            raise ValueError(f"{what} outside int32")
+    return labels.astype(np.int32), il.astype(np.int32), ll.astype(np.int32)
+
+
+def ctc_batch_cost(y_true, y_pred, input_length, label_length, ctx=None):
+    """keras.backend.ctc_batch_cost (the loss of recognition.py:340-347) on the GPU.
+
+    y_true (M, max_string_length) labels, float or int, padded after label_length (the reference pads with -1); y_pred
+    (M, T, C) probabilities (blank = C - 1); input_length, label_length (M, 1).  Returns the loss (M, 1) float32: the
+    negative log of the summed probability of every alignment, with Keras's log(y_pred + 1e-7).
+    A length outside its range or a label outside [0, C - 2] raises ValueError naming the sample; a label that does not
+    fit with a blank between its repeats gives +inf."""
+    ctx = ctx or _lib.default_context()
+    y = np.asarray(y_pred, dtype=np.float32)
+    if y.ndim != 3:
+        raise ValueError(f"y_pred must have shape (M, T, C), got {y.shape}")
+    labels, il, ll = _ctc_host_inputs(y_true, input_length, label_length, y.shape[0])
+    return ctx.ctc_batch_cost(y, labels, ll, il)[:, np.newaxis]
+
+
+def rgb2gray_u8(image):
+    """cv2.cvtColor(image, cv2.COLOR_RGB2GRAY) of a uint8 image: OpenCV's 15-bit fixed-point coefficients, rounded."""
+    im = np.asarray(image)
+    if im.ndim != 3 or im.shape[-1] not in (3, 4):
+        raise ValueError(f"an RGB image of shape (H, W, 3) is required, got {im.shape}")
+    im = im[..., :3].astype(np.int64)
+    return ((im[..., 0] * 9798 + im[..., 1] * 19235 + im[..., 2] * 3735 + (1 << 14)) >> 15).astype(np.uint8)
+
+
+def _to_gray(image):
+    im = np.asarray(image)
+    if im.dtype == np.uint8:
+        return rgb2gray_u8(im)
+    if im.ndim != 3 or im.shape[-1] not in (3, 4):
+        raise ValueError(f"an RGB image of shape (H, W, 3) is required, got {im.shape}")
+    f = im[..., :3].astype(np.float32)  # cv2.cvtColor of a float image: the float coefficients
+    return f[..., 0] * np.float32(0.299) + f[..., 1] * np.float32(0.587) + f[..., 2] * np.float32(0.114)
+
+
+def batch_generator(image_generator, alphabet, max_string_length, batch_size=8, lowercase=False):
+    """Recognizer.get_batch_generator (recognition.py:406-465) for a gray model: yields
+    ((images (B,H,W,1) float32 /255, labels (B, max_string_length) -1 padded, input_length (B,1), label_length (B,1)), y)
+    and, when the samples are (image, sentence, weight) tuples, the weights as a third element.  Batches are taken with the
+    reference's zip(image_generator, range(batch_size)), so one sample is drawn and dropped between batches as there.  The
+    reference's four assertions hold.  Unlike the reference, an exhausted generator ends the iteration, and a last batch
+    shorter than batch_size gets input_length and y of its own length."""
+    while True:
+        batch = [sample for sample, _ in zip(image_generator, range(batch_size))]
+        if not batch:
+            return
+        images = np.array([_to_gray(sample[0])[..., np.newaxis].astype("float32") / 255 for sample in batch])
+        sentences = [sample[1].strip() for sample in batch]
+        if lowercase:
+            sentences = [sentence.lower() for sentence in sentences]
+        for c in "".join(sentences):
+            assert c in alphabet, f"Found illegal character: {c}"
+        assert all(sentences), "Found a zero length sentence."
+        assert all(len(sentence) <= max_string_length for sentence in sentences), \
+            "A sentence is longer than this model can predict."
+        assert all("  " not in sentence for sentence in sentences), (
+            "Strings with multiple sequential spaces are not permitted. "
+            "See https://github.com/faustomorales/keras-ocr/issues/54")
+        label_length = np.array([len(sentence) for sentence in sentences])[:, np.newaxis]
+        labels = np.array([[alphabet.index(c) for c in sentence] + [-1] * (max_string_length - len(sentence))
+                           for sentence in sentences])
+        input_length = np.ones((len(batch), 1)) * max_string_length
+        y = np.zeros((len(batch), 1))
+        if len(batch[0]) == 3:
+            sample_weights = np.array([sample[2] for sample in batch])
+            yield (images, labels, input_length, label_length), y, sample_weights
+        else:
+            yield (images, labels, input_length, label_length), y
+
+
+_INFERENCE_ONLY = "keras-ocr_amd is inference-only: training (fit / compile) is not implemented"
+
+
+class _TrainingModel:
+    """recognizer.training_model (recognition.py:334-349): [crops, labels, input_length, label_length] -> CTC loss (M, 1)."""
+
+    output_shape = (None, 1)
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+
+    @property
+    def input_shape(self):
+        return [(None, 31, 200, 1), (None, self._ctx.crnn_label_width()), (None, 1), (None, 1)]
+
+    def predict(self, x, batch_size=None, **kwargs):  # pylint: disable=unused-argument
+        """x = [X (M,31,200,1), labels (M, label width), input_length (M,1), label_length (M,1)]; batch_size and the other
+        Keras predict arguments do not change the result."""
+        X, y_true, input_length, label_length = x  # pylint: disable=invalid-name
+        labels, il, ll = _ctc_host_inputs(y_true, input_length, label_length, np.shape(X)[0])
+        return self._ctx.crnn_ctc_loss(X, labels, ll, il)[:, np.newaxis]
+
+    def fit(self, *args, **kwargs):
+        raise NotImplementedError(_INFERENCE_ONLY)
+
+    def compile(self, *args, **kwargs):
+        raise NotImplementedError(_INFERENCE_ONLY)
+
+
+class _Backbone:
+    """recognizer.backbone (recognition.py:319-320): crops -> the BiLSTM features (M, 50, 256)."""
+
+    input_shape = (None, 31, 200, 1)
+    output_shape = (None, 50, 256)
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+
+    def predict(self, X, **kwargs):  # pylint: disable=invalid-name,unused-argument
+        return self._ctx.crnn_features(X)
+
+
 class Recognizer:
     """A text recogniser using the CRNN architecture (recognition.py:353-404).
 
@@ -130,8 +277,18 @@ class Recognizer:
         self.build_params = dict(DEFAULT_BUILD_PARAMS, **dict(build_params))
         self.model = _Model(self._ctx, probs=True)
         self.prediction_model = _Model(self._ctx, probs=False)
-        self.backbone = None
-        self.training_model = None
+        self.backbone = _Backbone(self._ctx)
+        self.training_model = _TrainingModel(self._ctx)
+
+    def get_batch_generator(self, image_generator, batch_size=8, lowercase=False):
+        """Recognizer.get_batch_generator (recognition.py:406-465): batches for training_model.predict; see
+        batch_generator."""
+        return batch_generator(image_generator, self.alphabet, self.training_model.input_shape[1][1], batch_size=batch_size,
+                               lowercase=lowercase)
+
+    def compile(self, *args, **kwargs):
+        """Recognizer.compile (recognition.py:539-545): training is not implemented."""
+        raise NotImplementedError(_INFERENCE_ONLY)
 
     def _decode(self, rows):
         from .pipeline import decode_labels
