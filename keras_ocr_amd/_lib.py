@@ -14,6 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkocr.so")
 
 KOCR_U8, KOCR_F32 = 0, 1
+# return codes (include/kocr.h)
+KOCR_OK, KOCR_EINVAL, KOCR_EHIP, KOCR_ENOWEIGHTS, KOCR_ECAPACITY, KOCR_ENOMEM, KOCR_EEMPTYCONTOUR, KOCR_EZERODIV = range(0, -8, -1)
 # minAreaRect rule of getBoxes (include/kocr.h: KOCR_RECT_EXACT / KOCR_RECT_OPENCV)
 MIN_AREA_RECT_RULES = {"exact": 0, "opencv": 1}
 
@@ -143,11 +145,20 @@ class Context:
         except Exception:  # pragma: no cover
             pass
 
-    def _check(self, rc):
-        if rc < 0:
-            msg = self._lib.kocr_last_error(self._h).decode("utf-8", "replace")
-            raise KocrError(f"libkocr error {rc}: {msg}")
-        return rc
+    def _check(self, rc, value_error=False):
+        """rc, or the exception the reference raises where the call failed: IndexError on an empty contour list
+        (detection.py:272), ZeroDivisionError on a box without width or height (tools.py:95), ValueError for a refused
+        argument (KOCR_EINVAL) when ``value_error`` (the reference / TF raise one there), KocrError otherwise."""
+        if rc >= 0:
+            return rc
+        if rc == KOCR_EEMPTYCONTOUR:
+            raise IndexError("list index out of range")
+        if rc == KOCR_EZERODIV:
+            raise ZeroDivisionError("division by zero")
+        msg = self._lib.kocr_last_error(self._h).decode("utf-8", "replace")
+        if value_error and rc == KOCR_EINVAL:
+            raise ValueError(msg)
+        raise KocrError(f"libkocr error {rc}: {msg}")
 
     # -- plumbing ------------------------------------------------------------------
     def set_stream(self, stream_ptr):
@@ -182,14 +193,9 @@ class Context:
     def craft_forward(self, images, micro_batch=0):
         """images: (N,H,W,3) uint8 (raw RGB) or float32 (normalised) numpy array on the host.
         Returns (N,H//2,W//2,2) float32."""
-        x = np.ascontiguousarray(images)
+        x, dt = _detector_input(images)
         if x.ndim != 4 or x.shape[3] != 3:
             raise ValueError("images must have shape (N,H,W,3)")
-        if x.dtype == np.uint8:
-            dt = KOCR_U8
-        else:
-            x = np.ascontiguousarray(x, dtype=np.float32)
-            dt = KOCR_F32
         n, h, w, _ = x.shape
         out = np.empty((n, h // 2, w // 2, 2), dtype=np.float32)
         self._check(self._lib.kocr_craft_forward(self._h, _ptr(x), dt, n, h, w, _ptr(out), int(micro_batch), 0))
@@ -243,11 +249,7 @@ class Context:
     def crnn_forward(self, crops, return_probs=False):
         """crops: (M,31,200[,1]) float32 in [0,1].  Returns labels (M,48) int32 (-1 padded)
         [, probs (M,48,n_classes)] (48 = crnn_label_width())."""
-        x = np.ascontiguousarray(crops, dtype=np.float32)
-        if x.ndim == 4 and x.shape[-1] == 1:
-            x = x[..., 0]
-        if x.ndim != 3 or x.shape[1:] != (31, 200):
-            raise ValueError("crops must have shape (M,31,200[,1])")
+        x = self._crops(crops)
         m = x.shape[0]
         c = self.crnn_classes()
         lw = self.crnn_label_width()
@@ -260,12 +262,6 @@ class Context:
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
 
     # -- recognizer.backbone / training_model (recognition.py:319-349) ------------------------------------------------
-    def _check_value(self, rc):
-        """_check, but a refused argument (KOCR_EINVAL) is a ValueError: the reference / TF raise one there."""
-        if rc == -1:
-            raise ValueError(self._lib.kocr_last_error(self._h).decode("utf-8", "replace"))
-        return self._check(rc)
-
     @staticmethod
     def _ctc_host_args(labels, label_lengths, input_lengths, m):
         lab = np.ascontiguousarray(labels, dtype=np.int32)
@@ -287,8 +283,8 @@ class Context:
         m, t, c = y.shape
         lab, ll, il = self._ctc_host_args(labels, label_lengths, input_lengths, m)
         loss = np.zeros(m, np.float32)
-        self._check_value(self._lib.kocr_ctc_batch_cost(self._h, _ptr(y), m, t, c, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il),
-                                                        _ptr(loss), 0))
+        self._check(self._lib.kocr_ctc_batch_cost(self._h, _ptr(y), m, t, c, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il),
+                                                  _ptr(loss), 0), value_error=True)
         return loss
 
     def crnn_ctc_loss(self, crops, labels, label_lengths, input_lengths):
@@ -298,7 +294,8 @@ class Context:
         m = x.shape[0]
         lab, ll, il = self._ctc_host_args(labels, label_lengths, input_lengths, m)
         loss = np.zeros(m, np.float32)
-        self._check_value(self._lib.kocr_crnn_ctc_loss(self._h, _ptr(x), m, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il), _ptr(loss), 0))
+        self._check(self._lib.kocr_crnn_ctc_loss(self._h, _ptr(x), m, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il), _ptr(loss), 0),
+                    value_error=True)
         return loss
 
     def crnn_features(self, crops):
@@ -331,21 +328,23 @@ class Context:
 
     def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap):
         n, h, w, _ = y.shape
+        return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_get_boxes(
+            self._h, _ptr(y), n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
+            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0))
+
+    def _boxes_grow_cap(self, n, cap, call):
+        """call(boxes, counts, cap) -> rc into (n, cap) buffers, repeated with the true maximum on KOCR_ECAPACITY (the counts
+        hold it); the boxes as a per-image list"""
         cap = int(cap) if cap else 1024
         while True:
             boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
             counts = np.zeros(n, dtype=np.int32)
-            rc = self._lib.kocr_get_boxes(self._h, _ptr(y), n, h, w, float(detection_threshold),
-                                          float(text_threshold), float(link_threshold), int(size_threshold),
-                                          _ptr(boxes), _ptr(counts), cap, 0)
-            if rc == -4 and n and counts.max() > cap:  # KOCR_ECAPACITY: retry with the true maximum
+            rc = call(boxes, counts, cap)
+            if rc == KOCR_ECAPACITY and n and counts.max() > cap:
                 cap = int(counts.max())
                 continue
-            if rc == -6:
-                raise IndexError("list index out of range")  # detection.py:272 on an empty contour list
             self._check(rc)
-            break
-        return [boxes[i, :counts[i]].copy() if counts[i] else np.array([]) for i in range(n)]
+            return _box_lists(boxes, counts)
 
     # -- Detector.detect, device-resident heat-maps -----------------------------------------------
     def detect(self, images, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,
@@ -357,43 +356,21 @@ class Context:
                                 cap)
 
     def _detect(self, images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap):
-        x = np.ascontiguousarray(images)
-        dt = KOCR_U8 if x.dtype == np.uint8 else KOCR_F32
-        if dt == KOCR_F32:
-            x = np.ascontiguousarray(x, dtype=np.float32)
+        x, dt = _detector_input(images)
         n, h, w, _ = x.shape
-        cap = int(cap) if cap else 1024
-        while True:
-            boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
-            counts = np.zeros(n, dtype=np.int32)
-            rc = self._lib.kocr_detect(self._h, _ptr(x), dt, n, h, w, float(detection_threshold), float(text_threshold),
-                                       float(link_threshold), int(size_threshold), int(micro_batch), _ptr(boxes),
-                                       _ptr(counts), cap, 0)
-            if rc == -4 and n and counts.max() > cap:
-                cap = int(counts.max())
-                continue
-            if rc == -6:
-                raise IndexError("list index out of range")
-            self._check(rc)
-            break
-        return [boxes[i, :counts[i]].copy() if counts[i] else np.array([]) for i in range(n)]
+        return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_detect(
+            self._h, _ptr(x), dt, n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
+            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0))
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
     def recognize_boxes(self, images, box_groups):
         """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32."""
         x = np.ascontiguousarray(images, dtype=np.uint8)
         n, h, w, _ = x.shape
-        counts = np.array([len(b) for b in box_groups], dtype=np.int32)
-        m = int(counts.sum())
-        labels = np.full((m, self.crnn_label_width()), -1, dtype=np.int32)
-        if m == 0:
-            return labels
-        flat = np.ascontiguousarray(
-            np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 4, 2) for b in box_groups if len(b)]))
-        rc = self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(labels), 0)
-        if rc == -7:
-            raise ZeroDivisionError("division by zero")
-        self._check(rc)
+        counts, flat = _flatten_boxes(box_groups)
+        labels = np.full((int(counts.sum()), self.crnn_label_width()), -1, dtype=np.int32)
+        if len(labels):
+            self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(labels), 0))
         return labels
 
     # -- crops --------------------------------------------------------------------------------
@@ -403,18 +380,11 @@ class Context:
         n, h, w, c = x.shape
         if c != 3:
             raise ValueError("images must be RGB")
-        counts = np.array([len(b) for b in box_groups], dtype=np.int32)
-        m = int(counts.sum())
-        out = np.zeros((m, target_height, target_width), dtype=np.float32)
-        if m == 0:
-            return out
-        flat = np.ascontiguousarray(
-            np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 4, 2) for b in box_groups if len(b)]))
-        rc = self._lib.kocr_warp_crops(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), int(target_height),
-                                       int(target_width), _ptr(out), 0)
-        if rc == -7:
-            raise ZeroDivisionError("division by zero")  # tools.py:95
-        self._check(rc)
+        counts, flat = _flatten_boxes(box_groups)
+        out = np.zeros((int(counts.sum()), target_height, target_width), dtype=np.float32)
+        if len(out):
+            self._check(self._lib.kocr_warp_crops(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), int(target_height),
+                                                  int(target_width), _ptr(out), 0))
         return out
 
     def warp_quads(self, images, src_quads, dst_quads, image_index, crop_wh, target_height, target_width,
@@ -469,18 +439,11 @@ class Context:
         n, h, w, c = x.shape
         if c not in (1, 3):
             raise ValueError("images must be RGB or gray")
-        counts = np.array([len(b) for b in box_groups], dtype=np.int32)
-        m = int(counts.sum())
-        out = np.zeros((m, target_height, target_width), dtype=np.float32)
-        if m == 0:
-            return out
-        flat = np.ascontiguousarray(
-            np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 4, 2) for b in box_groups if len(b)]))
-        rc = self._lib.kocr_warp_crops_f32(self._h, _ptr(x), n, h, w, c, _ptr(flat), _ptr(counts), int(target_height),
-                                           int(target_width), _ptr(out))
-        if rc == -7:
-            raise ZeroDivisionError("division by zero")  # tools.py:95
-        self._check(rc)
+        counts, flat = _flatten_boxes(box_groups)
+        out = np.zeros((int(counts.sum()), target_height, target_width), dtype=np.float32)
+        if len(out):
+            self._check(self._lib.kocr_warp_crops_f32(self._h, _ptr(x), n, h, w, c, _ptr(flat), _ptr(counts), int(target_height),
+                                                      int(target_width), _ptr(out)))
         return out
 
     # -- fused Pipeline.recognize ----------------------------------------------------------------
@@ -502,32 +465,25 @@ class Context:
         cap = int(cap)
         max_crops = int(max_crops) if max_crops else max(64, n * cap)
         lw = self.crnn_label_width()
-        while True:
+        boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
+        counts = np.zeros(n, dtype=np.int32)
+        labels = np.full((max_crops, lw), -1, dtype=np.int32)
+        n_crops = np.zeros(1, dtype=np.int32)
+        rc = self._lib.kocr_pipeline(
+            self._h, n, c_ptrs, *[a.ctypes.data_as(_c_int_p) for a in arr], int(hmax), int(wmax),
+            float(detection_threshold), float(text_threshold), float(link_threshold), int(size_threshold),
+            int(micro_batch), _ptr(boxes), _ptr(counts), cap, _ptr(labels), max_crops, _ptr(n_crops),
+            int(bool(on_device)))
+        if rc == KOCR_ECAPACITY and n and (counts.max() > cap or int(n_crops[0]) > max_crops):
+            # KOCR_ECAPACITY with the true counts: the whole chain has run ONCE and its results are resident in HBM (round 6:
+            # no second detector forward) -- fetch them into buffers of the right size
+            cap = max(cap, int(counts.max()))
+            max_crops = max(max_crops, int(n_crops[0]))
             boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
-            counts = np.zeros(n, dtype=np.int32)
             labels = np.full((max_crops, lw), -1, dtype=np.int32)
-            n_crops = np.zeros(1, dtype=np.int32)
-            rc = self._lib.kocr_pipeline(
-                self._h, n, c_ptrs, *[a.ctypes.data_as(_c_int_p) for a in arr], int(hmax), int(wmax),
-                float(detection_threshold), float(text_threshold), float(link_threshold), int(size_threshold),
-                int(micro_batch), _ptr(boxes), _ptr(counts), cap, _ptr(labels), max_crops, _ptr(n_crops),
-                int(bool(on_device)))
-            if rc == -4 and n and (counts.max() > cap or int(n_crops[0]) > max_crops):
-                # KOCR_ECAPACITY with the true counts: the whole chain has run ONCE and its results are resident in HBM (round 6:
-                # no second detector forward) -- fetch them into buffers of the right size
-                cap = max(cap, int(counts.max()))
-                max_crops = max(max_crops, int(n_crops[0]))
-                boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
-                labels = np.full((max_crops, lw), -1, dtype=np.int32)
-                rc = self._lib.kocr_pipeline_results(self._h, _ptr(boxes), cap, _ptr(labels), max_crops)
-            if rc == -6:
-                raise IndexError("list index out of range")
-            if rc == -7:
-                raise ZeroDivisionError("division by zero")
-            self._check(rc)
-            break
-        m = int(n_crops[0])
-        return [boxes[i, :counts[i]].copy() if counts[i] else np.array([]) for i in range(n)], labels[:m].copy()
+            rc = self._lib.kocr_pipeline_results(self._h, _ptr(boxes), cap, _ptr(labels), max_crops)
+        self._check(rc)
+        return _box_lists(boxes, counts), labels[:int(n_crops[0])].copy()
 
     def pipeline_device_results(self):
         """Device pointers of the last `pipeline()` call's results (include/kocr.h: kocr_pipeline_device_results):
@@ -659,6 +615,26 @@ class Context:
                         "frac_below_2^-4": b4 / nz if nz else 0.0, "frac_below_2^-14": b14 / nz if nz else 0.0,
                         "share_of_sum_abs_below_2^-4": sb / sa if sa else 0.0}
         return rows
+
+
+def _detector_input(images):
+    """images as the detector takes them: uint8 (raw RGB, KOCR_U8) as they are, anything else as float32 (KOCR_F32)"""
+    x = np.ascontiguousarray(images)
+    if x.dtype == np.uint8:
+        return x, KOCR_U8
+    return np.ascontiguousarray(x, dtype=np.float32), KOCR_F32
+
+
+def _flatten_boxes(box_groups):
+    """list of (n_i,4,2) -> counts int32[N], boxes float32 (sum n_i,4,2) in image order"""
+    counts = np.array([len(b) for b in box_groups], dtype=np.int32)
+    flat = [np.asarray(b, dtype=np.float32).reshape(-1, 4, 2) for b in box_groups if len(b)]
+    return counts, np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros((0, 4, 2), np.float32))
+
+
+def _box_lists(boxes, counts):
+    """(n, cap, 4, 2) boxes -> per-image list of (n_i,4,2) (``np.array([])`` for an image without boxes, detection.py:286)"""
+    return [boxes[i, :counts[i]].copy() if counts[i] else np.array([]) for i in range(len(counts))]
 
 
 def _min_area_rect_code(rule):

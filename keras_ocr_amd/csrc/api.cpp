@@ -1,6 +1,6 @@
 // api.cpp — the extern "C" surface declared in include/kocr.h (context, memory, profiler,
 // and the entry points that wrap the graphs).  No torch types: plain pointers and sizes.
-#include "common.h"
+#include "abi.h"
 #include <cmath>
 #include <algorithm>
 #include <mutex>
@@ -142,6 +142,34 @@ int kocr_ctx::prof_flush() {
   return KOCR_OK;
 }
 
+int craft_micro_batch(int micro_batch, int N, int H, int W) {
+  int mb = micro_batch > 0 ? micro_batch : 32;
+  while (mb > 1 && craft_workspace_bytes(mb, H, W) > ((size_t)96 << 30)) mb = (mb + 1) / 2;
+  return std::min(mb, N);
+}
+
+long prepare_box_warps(kocr_ctx* ctx, const char* fn, int N, const float* boxes, const int32_t* counts, const void* out, int th,
+                       int tw, std::vector<WarpParam>& prm) {
+  const std::string f(fn);
+  long M = 0;
+  for (int i = 0; i < N; ++i) {
+    if (counts[i] < 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": negative count");
+    M += counts[i];
+  }
+  if (M == 0) return 0;
+  if (!boxes || !out) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  prm.resize((size_t)M);
+  long m = 0;
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < counts[i]; ++j, ++m) {
+      const int rc = warp_prepare(boxes + m * 8, th, tw, &prm[m], nullptr);
+      if (rc == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, f + ": box with zero width or height (ZeroDivisionError at tools.py:95)");
+      if (rc != 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": singular perspective transform");
+      prm[m].img = i;
+    }
+  return M;
+}
+
 // ---------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------
@@ -269,16 +297,11 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
   if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_forward: bad dtype");
   if (N == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  int mb = micro_batch > 0 ? micro_batch : 32;  // Keras predict default batch_size (detection.py:779)
-  // keep the per-micro-batch workspace under ~64 GiB of the 288 GB HBM
-  while (mb > 1 && craft_workspace_bytes(mb, H, W) > ((size_t)96 << 30)) mb = (mb + 1) / 2;
-  mb = std::min(mb, N);
-  const size_t esz = dtype == KOCR_U8 ? 1 : 4;
-  const size_t in_img = (size_t)H * W * 3 * esz;
+  const int mb = craft_micro_batch(micro_batch, N, H, W);
+  const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
   const size_t out_img = (size_t)(H / 2) * (W / 2) * 2 * sizeof(float);
-  size_t need = craft_workspace_bytes(mb, H, W);
-  if (!on_device) need += (in_img + out_img) * mb + 1024;
-  KOCR_TRY(ctx->ws_reserve(need));
+  Staging st{ctx, ctx->ws, "kocr_craft_forward", on_device != 0};
+  KOCR_TRY(st.reserve(craft_workspace_bytes(mb, H, W), {in_img * mb, out_img * mb}));
   KOCR_TRY(craft_taps_begin(ctx, N));
   struct TapsEnd {  // also on an error return: no later launch records into this call's taps
     kocr_ctx* c;
@@ -290,24 +313,12 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
     craft_taps_batch(ctx, s);
     const void* d_in;
     float* d_out;
-    if (on_device) {
-      d_in = (const char*)img + (size_t)s * in_img;
-      d_out = (float*)((char*)heat + (size_t)s * out_img);
-    } else {
-      void* di = ctx->ws_alloc(in_img * nb);
-      void* dout = ctx->ws_alloc(out_img * nb);
-      if (!di || !dout) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_craft_forward: workspace exhausted");
-      KOCR_HIP(ctx, hipMemcpyAsync(di, (const char*)img + (size_t)s * in_img, in_img * nb,
-                                   hipMemcpyHostToDevice, ctx->stream));
-      d_in = di;
-      d_out = (float*)dout;
-    }
+    float* h_out = (float*)((char*)heat + (size_t)s * out_img);
+    KOCR_TRY(st.in((const void*)((const char*)img + (size_t)s * in_img), in_img * nb, d_in));
+    KOCR_TRY(st.out(h_out, out_img * nb, d_out));
     KOCR_TRY(craft_forward(ctx, d_in, dtype, nb, H, W, d_out));
-    if (!on_device) {
-      KOCR_HIP(ctx, hipMemcpyAsync((char*)heat + (size_t)s * out_img, d_out, out_img * nb,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    KOCR_TRY(st.back(h_out, d_out, out_img * nb));
+    KOCR_TRY(st.finish());
   }
   return KOCR_OK;
 }
@@ -330,51 +341,40 @@ int kocr_crnn_forward(kocr_ctx* ctx, const float* crops, int M, int32_t* labels,
   if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = std::min(M, 1024);
+  const int mb = crnn_batch(M);
   const int LW = crnn_label_width(ctx);
-  const size_t cb = (size_t)31 * 200 * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, C) + (on_device ? 0 : (cb + lb + pb) * mb + 2048)));
-  for (int s = 0; s < M; s += mb) {
-    const int nb = std::min(mb, M - s);
-    ctx->ws_reset();
-    const float* d_c = crops + (size_t)s * 31 * 200;
-    int32_t* d_l = labels + (size_t)s * LW;
-    float* d_p = probs ? probs + (size_t)s * LW * C : nullptr;
-    if (!on_device) {
-      float* dc = (float*)ctx->ws_alloc(cb * nb);
-      d_l = (int32_t*)ctx->ws_alloc(lb * nb);
-      d_p = probs ? (float*)ctx->ws_alloc(pb * nb) : nullptr;
-      if (!dc || !d_l || (probs && !d_p)) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_crnn_forward: workspace exhausted");
-      KOCR_HIP(ctx, hipMemcpyAsync(dc, d_c, cb * nb, hipMemcpyHostToDevice, ctx->stream));
-      d_c = dc;
-    }
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
+  Staging st{ctx, ctx->ws, "kocr_crnn_forward", on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0}));
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    const float* d_c;
+    int32_t* d_l;
+    float* d_p = nullptr;
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(labels + s * LW, lb * nb, d_l));
+    if (probs) KOCR_TRY(st.out(probs + (size_t)s * LW * C, pb * nb, d_p));
     KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p));
-    if (!on_device) {
-      KOCR_HIP(ctx, hipMemcpyAsync(labels + (size_t)s * LW, d_l, lb * nb, hipMemcpyDeviceToHost, ctx->stream));
-      if (probs)
-        KOCR_HIP(ctx, hipMemcpyAsync(probs + (size_t)s * LW * C, d_p, pb * nb, hipMemcpyDeviceToHost, ctx->stream));
-      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-  }
-  return KOCR_OK;
+    KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
+    if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
+    return st.finish();
+  });
 }
 
 // labels rows [s, s + nb) of a validated batch (ctc_validate) into the workspace as [nb][Lmax] | len[nb] | in_len[nb]; the
 // host staging vector is returned so that it outlives the asynchronous copy (the callers synchronise before returning)
-static int ctc_stage_labels(kocr_ctx* ctx, const char* fn, const int32_t* labels, int label_stride, const int32_t* label_lengths,
-                            const int32_t* input_lengths, int s, int nb, int Lmax, std::vector<int32_t>& host, int** d_lab,
-                            int** d_len, int** d_in) {
+static int ctc_stage_labels(Staging& st, const int32_t* labels, int label_stride, const int32_t* label_lengths,
+                            const int32_t* input_lengths, long s, int nb, int Lmax, std::vector<int32_t>& host, const int** d_lab,
+                            const int** d_len, const int** d_in) {
   const int ls = std::max(Lmax, 1);
   host.assign((size_t)nb * (ls + 2), -1);
   for (int i = 0; i < nb; ++i) {
-    const int m = s + i;
+    const long m = s + i;
     for (int k = 0; k < label_lengths[m]; ++k) host[(size_t)i * ls + k] = labels[(size_t)m * label_stride + k];
     host[(size_t)nb * ls + i] = label_lengths[m];
     host[(size_t)nb * (ls + 1) + i] = input_lengths[m];
   }
-  int* d = (int*)ctx->ws_alloc(host.size() * sizeof(int32_t));
-  if (!d) KOCR_FAIL(ctx, KOCR_ENOMEM, std::string(fn) + ": workspace exhausted");
-  KOCR_HIP(ctx, hipMemcpyAsync(d, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  const int32_t* d;
+  KOCR_TRY(st.upload(host.data(), host.size() * sizeof(int32_t), d));
   *d_lab = d;
   *d_len = d + (size_t)nb * ls;
   *d_in = d + (size_t)nb * (ls + 1);
@@ -394,23 +394,18 @@ int kocr_ctc_batch_cost(kocr_ctx* ctx, const float* y_pred, int M, int T, int C,
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t yb = (size_t)M * T * C * sizeof(float), lb = (size_t)M * sizeof(float);
   const size_t ib = (size_t)M * (std::max(Lmax, 1) + 2) * sizeof(int32_t);
-  KOCR_TRY(ctx->ws_reserve(ib + (on_device ? 0 : yb + lb) + 2048));
-  ctx->ws_reset();
+  Staging st{ctx, ctx->ws, fn, on_device != 0};
+  KOCR_TRY(st.reserve(0, {yb, lb}, {ib}));
   std::vector<int32_t> staged;
-  int *d_lab, *d_len, *d_in;
-  KOCR_TRY(ctc_stage_labels(ctx, fn, labels, label_stride, label_lengths, input_lengths, 0, M, Lmax, staged, &d_lab, &d_len, &d_in));
-  const float* d_y = y_pred;
-  float* d_loss = loss;
-  if (!on_device) {
-    float* dy = (float*)ctx->ws_alloc(yb);
-    d_loss = (float*)ctx->ws_alloc(lb);
-    if (!dy || !d_loss) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_ctc_batch_cost: workspace exhausted");
-    KOCR_HIP(ctx, hipMemcpyAsync(dy, y_pred, yb, hipMemcpyHostToDevice, ctx->stream));
-    d_y = dy;
-  }
+  const int *d_lab, *d_len, *d_in;
+  KOCR_TRY(ctc_stage_labels(st, labels, label_stride, label_lengths, input_lengths, 0, M, Lmax, staged, &d_lab, &d_len, &d_in));
+  const float* d_y;
+  float* d_loss;
+  KOCR_TRY(st.in(y_pred, yb, d_y));
+  KOCR_TRY(st.out(loss, lb, d_loss));
   KOCR_TRY(launch_ctc_loss(ctx, /*logits=*/false, d_y, M, T, C, 0, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
-  if (!on_device) KOCR_HIP(ctx, hipMemcpyAsync(loss, d_loss, lb, hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  KOCR_TRY(st.back(loss, d_loss, lb));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `staged` goes out of scope
   return KOCR_OK;
 }
 
@@ -428,29 +423,23 @@ int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* 
   KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, labels, label_stride, label_lengths, input_lengths, &Lmax));
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = std::min(M, 1024);
-  const size_t cb = (size_t)31 * 200 * sizeof(float), ib = (std::max(Lmax, 1) + 2) * sizeof(int32_t);
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, C) + (ib + (on_device ? 0 : cb + sizeof(float))) * mb + 4096));
+  const int mb = crnn_batch(M);
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), ib = (std::max(Lmax, 1) + 2) * sizeof(int32_t);
+  Staging st{ctx, ctx->ws, fn, on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, sizeof(float) * mb}, {ib * mb}));
   std::vector<int32_t> staged;
-  for (int s = 0; s < M; s += mb) {
-    const int nb = std::min(mb, M - s);
-    ctx->ws_reset();
-    int *d_lab, *d_len, *d_in;
-    KOCR_TRY(ctc_stage_labels(ctx, fn, labels, label_stride, label_lengths, input_lengths, s, nb, Lmax, staged, &d_lab, &d_len, &d_in));
-    const float* d_c = crops + (size_t)s * 31 * 200;
-    float* d_loss = loss + s;
-    if (!on_device) {
-      float* dc = (float*)ctx->ws_alloc(cb * nb);
-      d_loss = (float*)ctx->ws_alloc(sizeof(float) * nb);
-      if (!dc || !d_loss) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_crnn_ctc_loss: workspace exhausted");
-      KOCR_HIP(ctx, hipMemcpyAsync(dc, d_c, cb * nb, hipMemcpyHostToDevice, ctx->stream));
-      d_c = dc;
-    }
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    const int *d_lab, *d_len, *d_in;
+    KOCR_TRY(ctc_stage_labels(st, labels, label_stride, label_lengths, input_lengths, s, nb, Lmax, staged, &d_lab, &d_len, &d_in));
+    const float* d_c;
+    float* d_loss;
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(loss + s, sizeof(float) * nb, d_loss));
     KOCR_TRY(crnn_ctc_loss(ctx, d_c, nb, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
-    if (!on_device) KOCR_HIP(ctx, hipMemcpyAsync(loss + s, d_loss, sizeof(float) * nb, hipMemcpyDeviceToHost, ctx->stream));
+    KOCR_TRY(st.back(loss + s, d_loss, sizeof(float) * nb));
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `staged` is reused by the next batch
-  }
-  return KOCR_OK;
+    return KOCR_OK;
+  });
 }
 
 int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device) {
@@ -460,28 +449,20 @@ int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, i
   if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_features: call kocr_load_crnn first");
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = std::min(M, 1024);
-  const size_t cb = (size_t)31 * 200 * sizeof(float), fb = (size_t)50 * 256 * sizeof(float);
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, C) + (on_device ? 0 : (cb + fb) * mb + 2048)));
-  for (int s = 0; s < M; s += mb) {
-    const int nb = std::min(mb, M - s);
-    ctx->ws_reset();
-    const float* d_c = crops + (size_t)s * 31 * 200;
-    float* d_f = feats + (size_t)s * 50 * 256;
-    if (!on_device) {
-      float* dc = (float*)ctx->ws_alloc(cb * nb);
-      d_f = (float*)ctx->ws_alloc(fb * nb);
-      if (!dc || !d_f) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_crnn_features: workspace exhausted");
-      KOCR_HIP(ctx, hipMemcpyAsync(dc, d_c, cb * nb, hipMemcpyHostToDevice, ctx->stream));
-      d_c = dc;
-    }
+  const int mb = crnn_batch(M);
+  const size_t fpc = (size_t)CRNN_STEPS * CRNN_FEAT;  // features per crop
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), fb = fpc * sizeof(float);
+  Staging st{ctx, ctx->ws, "kocr_crnn_features", on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, fb * mb}));
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    const float* d_c;
+    float* d_f;
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(feats + s * fpc, fb * nb, d_f));
     KOCR_TRY(crnn_forward(ctx, d_c, nb, nullptr, nullptr, CRNN_FEATURES, d_f));
-    if (!on_device) {
-      KOCR_HIP(ctx, hipMemcpyAsync(feats + (size_t)s * 50 * 256, d_f, fb * nb, hipMemcpyDeviceToHost, ctx->stream));
-      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-  }
-  return KOCR_OK;
+    KOCR_TRY(st.back(feats + s * fpc, d_f, fb * nb));
+    return st.finish();
+  });
 }
 
 int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float detection_threshold,
@@ -492,24 +473,18 @@ int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float 
   if (N == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t hb = (size_t)N * h * w * 2 * sizeof(float), bb = (size_t)N * cap * 8 * sizeof(float);
-  const float* d_heat = heat;
-  float* d_boxes = boxes;
-  if (!on_device) {
-    KOCR_TRY(arena_reserve(ctx, ctx->io, hb + bb + 1024));
-    ctx->io.off = 0;
-    float* dh = (float*)arena_alloc(ctx->io, hb);
-    d_boxes = (float*)arena_alloc(ctx->io, bb);
-    KOCR_HIP(ctx, hipMemcpyAsync(dh, heat, hb, hipMemcpyHostToDevice, ctx->stream));
-    d_heat = dh;
-  }
+  Staging st{ctx, ctx->io, "kocr_get_boxes", on_device != 0};
+  KOCR_TRY(st.reserve(0, {hb, bb}));
+  const float* d_heat;
+  float* d_boxes;
+  KOCR_TRY(st.in(heat, hb, d_heat));
+  KOCR_TRY(st.out(boxes, bb, d_boxes));
   int n_empty = 0;
   const int rc = postproc_get_boxes(ctx, d_heat, N, h, w, detection_threshold, text_threshold, link_threshold,
                                     size_threshold, d_boxes, cap, counts, &n_empty);
   if (rc != KOCR_OK) return rc;
-  if (!on_device) {
-    KOCR_HIP(ctx, hipMemcpyAsync(boxes, d_boxes, bb, hipMemcpyDeviceToHost, ctx->stream));
-    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  KOCR_TRY(st.back(boxes, d_boxes, bb));
+  KOCR_TRY(st.finish());
   if (n_empty > 0)
     KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR,
               "kocr_get_boxes: a component has no pixels left after removing text&link overlap "
@@ -522,40 +497,22 @@ int kocr_warp_crops(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, 
   if (!ctx) return KOCR_EINVAL;
   if (N < 0 || target_h <= 0 || target_w <= 0 || (N > 0 && (!img_rgb || !counts)))
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops: bad argument");
-  long M = 0;
-  for (int i = 0; i < N; ++i) {
-    if (counts[i] < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops: negative count");
-    M += counts[i];
-  }
-  if (M == 0) return KOCR_OK;
-  if (!boxes || !crops) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops: null buffer");
+  std::vector<WarpParam> prm;
+  const long M = prepare_box_warps(ctx, "kocr_warp_crops", N, boxes, counts, crops, target_h, target_w, prm);
+  if (M <= 0) return (int)M;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  std::vector<WarpParam> prm((size_t)M);
-  long m = 0;
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < counts[i]; ++j, ++m) {
-      const int rc = warp_prepare(boxes + m * 8, target_h, target_w, &prm[m], nullptr);
-      if (rc == 1)
-        KOCR_FAIL(ctx, KOCR_EZERODIV, "kocr_warp_crops: box with zero width or height (ZeroDivisionError at tools.py:95)");
-      if (rc != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops: singular perspective transform");
-      prm[m].img = i;
-    }
   const size_t ib = (size_t)N * H * W * 3, cb = (size_t)M * target_h * target_w * sizeof(float);
   const size_t pb = (size_t)M * sizeof(WarpParam);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, pb + (on_device ? 0 : ib + cb) + 2048));
-  ctx->io.off = 0;
-  WarpParam* d_prm = (WarpParam*)arena_alloc(ctx->io, pb);
-  KOCR_HIP(ctx, hipMemcpyAsync(d_prm, prm.data(), pb, hipMemcpyHostToDevice, ctx->stream));
-  const uint8_t* d_img = img_rgb;
-  float* d_crops = crops;
-  if (!on_device) {
-    uint8_t* di = (uint8_t*)arena_alloc(ctx->io, ib);
-    d_crops = (float*)arena_alloc(ctx->io, cb);
-    KOCR_HIP(ctx, hipMemcpyAsync(di, img_rgb, ib, hipMemcpyHostToDevice, ctx->stream));
-    d_img = di;
-  }
+  Staging st{ctx, ctx->io, "kocr_warp_crops", on_device != 0};
+  KOCR_TRY(st.reserve(0, {ib, cb}, {pb}));
+  const WarpParam* d_prm;
+  const uint8_t* d_img;
+  float* d_crops;
+  KOCR_TRY(st.upload(prm.data(), pb, d_prm));
+  KOCR_TRY(st.in(img_rgb, ib, d_img));
+  KOCR_TRY(st.out(crops, cb, d_crops));
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, target_h, target_w, d_crops));
-  if (!on_device) KOCR_HIP(ctx, hipMemcpyAsync(crops, d_crops, cb, hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_TRY(st.back(crops, d_crops, cb));
   // prm is host memory about to go out of scope: the H2D copy must have completed
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KOCR_OK;
@@ -570,15 +527,15 @@ int kocr_resize_pad_f32(kocr_ctx* ctx, const float* src, int n, int sh, int sw, 
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)n * sh * sw * channels * sizeof(float), db = (size_t)n * Hmax * Wmax * channels * sizeof(float);
   const size_t tb = (size_t)(3 * (Wmax + Hmax) + 64) * sizeof(int);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, tb + sb + db + 4096));
-  ctx->io.off = 0;
-  float* ds = (float*)arena_alloc(ctx->io, sb);
-  float* dd = (float*)arena_alloc(ctx->io, db);
-  KOCR_HIP(ctx, hipMemcpyAsync(ds, src, sb, hipMemcpyHostToDevice, ctx->stream));
+  Staging st{ctx, ctx->io, "kocr_resize_pad_f32"};
+  KOCR_TRY(st.reserve(tb, {sb, db}));
+  const float* ds;
+  float* dd;
+  KOCR_TRY(st.in(src, sb, ds));
+  KOCR_TRY(st.out(dst, db, dd));
   KOCR_TRY(launch_resize_pad_f32(ctx, ds, n, sh, sw, channels, dd, dh, dw, Hmax, Wmax, cval, ctx->io));
-  KOCR_HIP(ctx, hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  KOCR_TRY(st.back(dst, dd, db));
+  return st.finish();
 }
 
 int kocr_warp_crops_f32(kocr_ctx* ctx, const float* img, int N, int H, int W, int channels, const float* boxes, const int32_t* counts,
@@ -586,36 +543,23 @@ int kocr_warp_crops_f32(kocr_ctx* ctx, const float* img, int N, int H, int W, in
   if (!ctx) return KOCR_EINVAL;
   if (N < 0 || target_h <= 0 || target_w <= 0 || (channels != 1 && channels != 3) || (N > 0 && (!img || !counts)))
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops_f32: bad argument");
-  long M = 0;
-  for (int i = 0; i < N; ++i) {
-    if (counts[i] < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops_f32: negative count");
-    M += counts[i];
-  }
-  if (M == 0) return KOCR_OK;
-  if (!boxes || !crops) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops_f32: null buffer");
+  std::vector<WarpParam> prm;
+  const long M = prepare_box_warps(ctx, "kocr_warp_crops_f32", N, boxes, counts, crops, target_h, target_w, prm);
+  if (M <= 0) return (int)M;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  std::vector<WarpParam> prm((size_t)M);
-  long m = 0;
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < counts[i]; ++j, ++m) {
-      const int rc = warp_prepare(boxes + m * 8, target_h, target_w, &prm[m], nullptr);
-      if (rc == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, "kocr_warp_crops_f32: box with zero width or height (ZeroDivisionError at tools.py:95)");
-      if (rc != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_crops_f32: singular perspective transform");
-      prm[m].img = i;
-    }
   const size_t ib = (size_t)N * H * W * channels * sizeof(float), cb = (size_t)M * target_h * target_w * sizeof(float);
   const size_t pb = (size_t)M * sizeof(WarpParam);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, pb + ib + cb + 4096));
-  ctx->io.off = 0;
-  WarpParam* d_prm = (WarpParam*)arena_alloc(ctx->io, pb);
-  float* di = (float*)arena_alloc(ctx->io, ib);
-  float* d_crops = (float*)arena_alloc(ctx->io, cb);
-  KOCR_HIP(ctx, hipMemcpyAsync(d_prm, prm.data(), pb, hipMemcpyHostToDevice, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(di, img, ib, hipMemcpyHostToDevice, ctx->stream));
+  Staging st{ctx, ctx->io, "kocr_warp_crops_f32"};
+  KOCR_TRY(st.reserve(0, {ib, cb}, {pb}));
+  const WarpParam* d_prm;
+  const float* di;
+  float* d_crops;
+  KOCR_TRY(st.upload(prm.data(), pb, d_prm));
+  KOCR_TRY(st.in(img, ib, di));
+  KOCR_TRY(st.out(crops, cb, d_crops));
   KOCR_TRY(launch_warp_f32(ctx, di, H, W, channels, d_prm, (int)M, target_h, target_w, d_crops));
-  KOCR_HIP(ctx, hipMemcpyAsync(crops, d_crops, cb, hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  KOCR_TRY(st.back(crops, d_crops, cb));
+  return st.finish();
 }
 
 int kocr_warp_quads(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, int M, const float* src_quads,
@@ -634,34 +578,34 @@ int kocr_warp_quads(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, 
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t ib = (size_t)N * H * W * 3, cb = (size_t)M * target_h * target_w * sizeof(float);
   const size_t qb = (size_t)M * 8 * sizeof(float), nb = (size_t)M * sizeof(int), tb = (size_t)M * 9 * sizeof(double);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, ib + cb + 2 * qb + 3 * nb + tb + (size_t)M * sizeof(WarpParam) + 8192));
-  ctx->io.off = 0;
-  uint8_t* d_img = (uint8_t*)arena_alloc(ctx->io, ib);
-  float* d_crops = (float*)arena_alloc(ctx->io, cb);
-  float* d_src = (float*)arena_alloc(ctx->io, qb);
-  float* d_dst = (float*)arena_alloc(ctx->io, qb);
-  int* d_idx = (int*)arena_alloc(ctx->io, nb);
-  int* d_cw = (int*)arena_alloc(ctx->io, nb);
-  int* d_ch = (int*)arena_alloc(ctx->io, nb);
-  double* d_tf = (double*)arena_alloc(ctx->io, tb);
-  WarpParam* d_prm = (WarpParam*)arena_alloc(ctx->io, (size_t)M * sizeof(WarpParam));
-  int* d_status = (int*)arena_alloc(ctx->io, 256);
-  if (!d_status) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_warp_quads: arena exhausted");
-  hipStream_t s = ctx->stream;
-  KOCR_HIP(ctx, hipMemcpyAsync(d_img, img_rgb, ib, hipMemcpyHostToDevice, s));
-  KOCR_HIP(ctx, hipMemcpyAsync(d_src, src_quads, qb, hipMemcpyHostToDevice, s));
-  KOCR_HIP(ctx, hipMemcpyAsync(d_dst, dst_quads, qb, hipMemcpyHostToDevice, s));
-  KOCR_HIP(ctx, hipMemcpyAsync(d_idx, image_index, nb, hipMemcpyHostToDevice, s));
-  KOCR_HIP(ctx, hipMemcpyAsync(d_cw, crop_w, nb, hipMemcpyHostToDevice, s));
-  KOCR_HIP(ctx, hipMemcpyAsync(d_ch, crop_h, nb, hipMemcpyHostToDevice, s));
-  KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), s));
+  const size_t pb = (size_t)M * sizeof(WarpParam);
+  Staging st{ctx, ctx->io, "kocr_warp_quads"};
+  KOCR_TRY(st.reserve(0, {ib, cb, qb, qb, nb, nb, nb, tb, pb, 256}));
+  const uint8_t* d_img;
+  const float *d_src, *d_dst;
+  const int32_t *d_idx, *d_cw, *d_ch;
+  float* d_crops;
+  double* d_tf;
+  WarpParam* d_prm;
+  int* d_status;
+  KOCR_TRY(st.in(img_rgb, ib, d_img));
+  KOCR_TRY(st.out(crops, cb, d_crops));
+  KOCR_TRY(st.in(src_quads, qb, d_src));
+  KOCR_TRY(st.in(dst_quads, qb, d_dst));
+  KOCR_TRY(st.in(image_index, nb, d_idx));
+  KOCR_TRY(st.in(crop_w, nb, d_cw));
+  KOCR_TRY(st.in(crop_h, nb, d_ch));
+  KOCR_TRY(st.scratch(tb, d_tf));
+  KOCR_TRY(st.scratch(pb, d_prm));
+  KOCR_TRY(st.scratch(256, d_status));
+  KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), ctx->stream));
   KOCR_TRY(launch_warp_quads(ctx, d_src, d_dst, d_idx, d_cw, d_ch, M, d_prm, d_tf, d_status));
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, M, target_h, target_w, d_crops));
   int status = 0;
-  KOCR_HIP(ctx, hipMemcpyAsync(crops, d_crops, cb, hipMemcpyDeviceToHost, s));
-  if (transforms) KOCR_HIP(ctx, hipMemcpyAsync(transforms, d_tf, tb, hipMemcpyDeviceToHost, s));
-  KOCR_HIP(ctx, hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
-  KOCR_HIP(ctx, hipStreamSynchronize(s));
+  KOCR_TRY(st.back(crops, d_crops, cb));
+  if (transforms) KOCR_TRY(st.back(transforms, d_tf, tb));
+  KOCR_TRY(st.download(&status, d_status, sizeof(int)));
+  KOCR_TRY(st.finish());
   if (status != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_warp_quads: singular perspective transform");
   return KOCR_OK;
 }
@@ -674,40 +618,27 @@ int kocr_conv2d_nhwc(kocr_ctx* ctx, const float* in, int N, int H, int W, int Ci
       !(KH & 1) || !(KW & 1))
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_conv2d_nhwc: bad shape (odd kernels, positive sizes)");
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  KOCR_TRY(ctx->amax_begin());  // allocates the slot pool BEFORE the mark below: it outlives this call
-  const size_t first_owned = ctx->owned.size();
+  KOCR_TRY(ctx->amax_begin());  // allocates the slot pool BEFORE the layer's mark: it outlives this call
+  TempLayer layer(ctx);
   ConvLayer L;
   L.name = "kocr_conv2d_nhwc";
-  int rc = prepare_conv(ctx, L, w_hwio, /*oihw=*/false, Cin, Cout, KH, KW, dilation, pre_a, pre_b, relu,
-                        post_a, post_b);
-  const size_t nin = (size_t)N * H * W * Cin, nout = (size_t)N * H * W * Cout;
-  if (rc == KOCR_OK) rc = ctx->ws_reserve((nin + nout) * sizeof(float) + 4096);
-  if (rc == KOCR_OK) {
-    ctx->ws_reset();
-    Tensor ti, to;
-    ti.N = to.N = N;
-    ti.H = to.H = H;
-    ti.W = to.W = W;
-    ti.C = ti.cs = Cin;
-    to.C = to.cs = Cout;
-    ti.p = (float*)ctx->ws_alloc(nin * sizeof(float));
-    to.p = (float*)ctx->ws_alloc(nout * sizeof(float));
-    auto run = [&]() -> int {
-      KOCR_HIP(ctx, hipMemcpyAsync(ti.p, in, nin * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      KOCR_TRY(launch_conv(ctx, L, ti, nullptr, nullptr, to));
-      KOCR_HIP(ctx, hipMemcpyAsync(out, to.p, nout * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      return KOCR_OK;
-    };
-    rc = run();
-  }
-  // release the temporary layer's device buffers
-  hipStreamSynchronize(ctx->stream);
-  while (ctx->owned.size() > first_owned) {
-    hipFree(ctx->owned.back());
-    ctx->owned.pop_back();
-  }
-  return rc;
+  KOCR_TRY(prepare_conv(ctx, L, w_hwio, /*oihw=*/false, Cin, Cout, KH, KW, dilation, pre_a, pre_b, relu, post_a, post_b));
+  const size_t nin = (size_t)N * H * W * Cin * sizeof(float), nout = (size_t)N * H * W * Cout * sizeof(float);
+  Staging st{ctx, ctx->ws, "kocr_conv2d_nhwc"};
+  KOCR_TRY(st.reserve(0, {nin, nout}));
+  Tensor ti, to;
+  ti.N = to.N = N;
+  ti.H = to.H = H;
+  ti.W = to.W = W;
+  ti.C = ti.cs = Cin;
+  to.C = to.cs = Cout;
+  const float* d_in;
+  KOCR_TRY(st.in(in, nin, d_in));
+  KOCR_TRY(st.out(out, nout, to.p));
+  ti.p = (float*)d_in;
+  KOCR_TRY(launch_conv(ctx, L, ti, nullptr, nullptr, to));
+  KOCR_TRY(st.back(out, to.p, nout));
+  return st.finish();
 }
 
 int kocr_conv2d_cells(kocr_ctx* ctx, const float* in, int N, int H, int W, int Cin, const float* w_hwio, int Cout,
@@ -729,64 +660,52 @@ int kocr_conv2d_cells(kocr_ctx* ctx, const float* in, int N, int H, int W, int C
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_conv2d_cells: the grid must tile as 4 x 64 (H % 4 == 0, W % 64 == 0) or 8 x 32");
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   KOCR_TRY(ctx->amax_begin());
-  const size_t first_owned = ctx->owned.size();
+  TempLayer layer(ctx);
   ConvLayer L;
   L.name = "kocr_conv2d_cells";
-  int rc = prepare_conv(ctx, L, w_hwio, /*oihw=*/false, Cin, Cout, 3, 3, 1, pre_a, pre_b, relu, post_a, post_b);
+  KOCR_TRY(prepare_conv(ctx, L, w_hwio, /*oihw=*/false, Cin, Cout, 3, 3, 1, pre_a, pre_b, relu, post_a, post_b));
   const int cn = W / cellW;
-  const size_t nin = (size_t)N * H * W * Cin, nout = (size_t)N * H * W * Cout, npool = nout / 4;
-  if (rc == KOCR_OK) rc = ctx->ws_reserve((nin + (out ? nout : 0) + (pool ? npool : 0)) * sizeof(float) + 8192);
-  if (rc == KOCR_OK) {
-    ctx->ws_reset();
-    Tensor ti, to, tp;
-    ti.N = to.N = tp.N = N;
-    ti.H = to.H = H;
-    ti.W = to.W = W;
-    tp.H = H / 2;
-    tp.W = W / 2;
-    ti.C = ti.cs = Cin;
-    to.C = to.cs = tp.C = tp.cs = Cout;
-    ti.cellW = to.cellW = cellW;
-    ti.cellWv = to.cellWv = cellWv;
-    tp.cellW = cellW / 2;
-    tp.cellWv = cellWv / 2;
-    ti.p = (float*)ctx->ws_alloc(nin * sizeof(float));
-    to.p = out ? (float*)ctx->ws_alloc(nout * sizeof(float)) : nullptr;
-    tp.p = pool ? (float*)ctx->ws_alloc(npool * sizeof(float)) : nullptr;
-    ti.amax = ctx->amax_slots(N * cn);
-    to.amax = ctx->amax_slots(N * cn);
-    tp.amax = ctx->amax_slots(N * cn);
-    // the input's per-cell max |x| (its producer's job in the recogniser): computed here on the host
-    std::vector<float> am((size_t)N * cn, 0.f);
-    for (int n = 0; n < N; ++n)
-      for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-          const float* px = in + (((size_t)n * H + y) * W + x) * Cin;
-          float m = 0.f;
-          for (int c = 0; c < Cin; ++c) m = std::max(m, std::fabs(px[c]));
-          float& a = am[(size_t)n * cn + x / cellW];
-          a = std::max(a, m);
-        }
-    auto run = [&]() -> int {
-      if (!ti.amax || !to.amax || !tp.amax) KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_conv2d_cells: out of max-|x| slots");
-      KOCR_HIP(ctx, hipMemcpyAsync(ti.p, in, nin * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      KOCR_HIP(ctx, hipMemcpyAsync(ti.amax, am.data(), am.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-      KOCR_TRY(launch_conv_pool(ctx, L, ti, nullptr, nullptr, to, pool ? &tp : nullptr, /*need_full=*/out != nullptr));
-      if (out) KOCR_HIP(ctx, hipMemcpyAsync(out, to.p, nout * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      if (pool) KOCR_HIP(ctx, hipMemcpyAsync(pool_out, tp.p, npool * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      if (amax_out)
-        KOCR_HIP(ctx, hipMemcpyAsync(amax_out, pool && !out ? tp.amax : to.amax, am.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      return KOCR_OK;
-    };
-    rc = run();
-  }
-  hipStreamSynchronize(ctx->stream);
-  while (ctx->owned.size() > first_owned) {
-    hipFree(ctx->owned.back());
-    ctx->owned.pop_back();
-  }
-  return rc;
+  const size_t nin = (size_t)N * H * W * Cin * sizeof(float), nout = (size_t)N * H * W * Cout * sizeof(float), npool = nout / 4;
+  Staging st{ctx, ctx->ws, "kocr_conv2d_cells"};
+  KOCR_TRY(st.reserve(0, {nin, out ? nout : 0, pool ? npool : 0}));
+  Tensor ti, to, tp;
+  ti.N = to.N = tp.N = N;
+  ti.H = to.H = H;
+  ti.W = to.W = W;
+  tp.H = H / 2;
+  tp.W = W / 2;
+  ti.C = ti.cs = Cin;
+  to.C = to.cs = tp.C = tp.cs = Cout;
+  ti.cellW = to.cellW = cellW;
+  ti.cellWv = to.cellWv = cellWv;
+  tp.cellW = cellW / 2;
+  tp.cellWv = cellWv / 2;
+  ti.amax = ctx->amax_slots(N * cn);
+  to.amax = ctx->amax_slots(N * cn);
+  tp.amax = ctx->amax_slots(N * cn);
+  if (!ti.amax || !to.amax || !tp.amax) KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_conv2d_cells: out of max-|x| slots");
+  const float* d_in;
+  KOCR_TRY(st.in(in, nin, d_in));
+  ti.p = (float*)d_in;
+  if (out) KOCR_TRY(st.out(out, nout, to.p));
+  if (pool) KOCR_TRY(st.out(pool_out, npool, tp.p));
+  // the input's per-cell max |x| (its producer's job in the recogniser): computed here on the host
+  std::vector<float> am((size_t)N * cn, 0.f);
+  for (int n = 0; n < N; ++n)
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const float* px = in + (((size_t)n * H + y) * W + x) * Cin;
+        float m = 0.f;
+        for (int c = 0; c < Cin; ++c) m = std::max(m, std::fabs(px[c]));
+        float& a = am[(size_t)n * cn + x / cellW];
+        a = std::max(a, m);
+      }
+  KOCR_TRY(st.put((float*)ti.amax, am.data(), am.size() * sizeof(float)));
+  KOCR_TRY(launch_conv_pool(ctx, L, ti, nullptr, nullptr, to, pool ? &tp : nullptr, /*need_full=*/out != nullptr));
+  if (out) KOCR_TRY(st.back(out, to.p, nout));
+  if (pool) KOCR_TRY(st.back(pool_out, tp.p, npool));
+  if (amax_out) KOCR_TRY(st.download(amax_out, (const float*)(pool && !out ? tp.amax : to.amax), am.size() * sizeof(float)));
+  return st.finish();
 }
 
 int kocr_set_split_mode(kocr_ctx* ctx, int mode) {

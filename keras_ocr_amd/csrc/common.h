@@ -393,6 +393,10 @@ int craft_taps_begin(kocr_ctx* ctx, int N);  // kocr_craft_forward with taps on:
 void craft_taps_batch(kocr_ctx* ctx, int n0); // ... the next micro-batch starts at image n0 (-1: the call is over)
 
 // crnn.cpp
+// the recogniser's geometry: crops of CRNN_CROP_H x CRNN_CROP_W, CRNN_STEPS time steps of CRNN_FEAT features (the backbone's
+// [lstm_11 | lstm_11_back] concatenation); a label row has crnn_label_width() = CRNN_STEPS - rnn_steps_to_discard columns
+constexpr int CRNN_CROP_H = 31, CRNN_CROP_W = 200, CRNN_STEPS = 50, CRNN_FEAT = 256;
+constexpr size_t CRNN_CROP_PIXELS = (size_t)CRNN_CROP_H * CRNN_CROP_W;
 void crnn_free(kocr_ctx* ctx);
 int crnn_load(kocr_ctx* ctx, int n, const char* const* names, const float* const* data, const int64_t* shapes,
               const int* ranks);

@@ -41,7 +41,7 @@ struct CrnnNet {
 };
 
 namespace {
-constexpr int HC = 31, WC = 200, UNITS = 128, T = 50, DISCARD = 2;
+constexpr int HC = CRNN_CROP_H, WC = CRNN_CROP_W, UNITS = CRNN_FEAT / 2, T = CRNN_STEPS, DISCARD = 2;
 // the crop batch as a cell grid (Tensor::cellW): CN crops side by side per image; cell = (HC + 1) x 208 at full resolution
 // (one zero row on top, eight zero columns behind the crop), 16 x 104 and 8 x 52 after the two poolings.  208 CN, 104 CN and
 // 52 CN are multiples of 64: the grid tiles as 4 rows x 64 columns at every level.

@@ -3,8 +3,7 @@
 //   ->  Recognizer.recognize_from_boxes (:63-65; recognition.py:491-537).
 // Everything stays resident in HBM between the stages; the host sees only the per-image box
 // counts (a few bytes, needed to size the crop batch), the boxes and the decoded label rows.
-#include "common.h"
-#include <algorithm>
+#include "abi.h"
 
 extern "C" int kocr_resize_pad(kocr_ctx* ctx, const uint8_t* src, int n, int sh, int sw, int dh, int dw, int Hmax,
                                int Wmax, int cval, uint8_t* dst, int on_device) {
@@ -15,22 +14,15 @@ extern "C" int kocr_resize_pad(kocr_ctx* ctx, const uint8_t* src, int n, int sh,
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)n * sh * sw * 3, db = (size_t)n * Hmax * Wmax * 3;
   const size_t tb = (size_t)(4 * (Wmax + Hmax) + 64) * sizeof(int);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, tb + (on_device ? 0 : sb + db) + 4096));
-  ctx->io.off = 0;
-  const uint8_t* d_src = src;
-  uint8_t* d_dst = dst;
-  if (!on_device) {
-    uint8_t* ds = (uint8_t*)arena_alloc(ctx->io, sb);
-    d_dst = (uint8_t*)arena_alloc(ctx->io, db);
-    KOCR_HIP(ctx, hipMemcpyAsync(ds, src, sb, hipMemcpyHostToDevice, ctx->stream));
-    d_src = ds;
-  }
+  Staging st{ctx, ctx->io, "kocr_resize_pad", on_device != 0};
+  KOCR_TRY(st.reserve(tb, {sb, db}));
+  const uint8_t* d_src;
+  uint8_t* d_dst;
+  KOCR_TRY(st.in(src, sb, d_src));
+  KOCR_TRY(st.out(dst, db, d_dst));
   KOCR_TRY(launch_resize_pad(ctx, d_src, n, sh, sw, d_dst, dh, dw, Hmax, Wmax, cval, ctx->io));
-  if (!on_device) {
-    KOCR_HIP(ctx, hipMemcpyAsync(dst, d_dst, db, hipMemcpyDeviceToHost, ctx->stream));
-    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return KOCR_OK;
+  KOCR_TRY(st.back(dst, d_dst, db));
+  return st.finish();
 }
 
 // Detector.detect's device half in one call: CRAFT forward + getBoxes, heat-maps never leave HBM.
@@ -45,38 +37,29 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
   ctx->last_pl.valid = false;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int h2 = H / 2, w2 = W / 2;
-  const size_t esz = dtype == KOCR_U8 ? 1 : 4;
-  const size_t in_b = (size_t)N * H * W * 3 * esz;
+  const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
   const size_t heat_b = (size_t)N * h2 * w2 * 2 * sizeof(float);
   const size_t box_b = (size_t)N * cap * 8 * sizeof(float);
-  KOCR_TRY(arena_reserve(ctx, ctx->pl, heat_b + box_b + (on_device ? 0 : in_b) + 4096));
-  ctx->pl.off = 0;
-  float* d_heat = (float*)arena_alloc(ctx->pl, heat_b);
-  float* d_boxes = on_device ? boxes : (float*)arena_alloc(ctx->pl, box_b);
-  const char* d_in = (const char*)img;
-  if (!on_device) {
-    char* di = (char*)arena_alloc(ctx->pl, in_b);
-    if (!di) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_detect: arena exhausted");
-    KOCR_HIP(ctx, hipMemcpyAsync(di, img, in_b, hipMemcpyHostToDevice, ctx->stream));
-    d_in = di;
-  }
-  if (!d_heat || !d_boxes) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_detect: arena exhausted");
-  int mb = micro_batch > 0 ? micro_batch : 32;
-  while (mb > 1 && craft_workspace_bytes(mb, H, W) > ((size_t)96 << 30)) mb = (mb + 1) / 2;
-  mb = std::min(mb, N);
+  Staging st{ctx, ctx->pl, "kocr_detect", on_device != 0};
+  KOCR_TRY(st.reserve(0, {in_img * N}, {heat_b, box_b}));  // box_b on the device path too: the pl arena keeps its size
+  float* d_heat;
+  float* d_boxes;
+  const char* d_in;
+  KOCR_TRY(st.scratch(heat_b, d_heat));
+  KOCR_TRY(st.out(boxes, box_b, d_boxes));
+  KOCR_TRY(st.in((const char*)img, in_img * N, d_in));
+  const int mb = craft_micro_batch(micro_batch, N, H, W);
   KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(mb, H, W)));
   for (int s = 0; s < N; s += mb) {
     const int nb = std::min(mb, N - s);
     ctx->ws_reset();
-    KOCR_TRY(craft_forward(ctx, d_in + (size_t)s * H * W * 3 * esz, dtype, nb, H, W, d_heat + (size_t)s * h2 * w2 * 2));
+    KOCR_TRY(craft_forward(ctx, d_in + (size_t)s * in_img, dtype, nb, H, W, d_heat + (size_t)s * h2 * w2 * 2));
   }
   int n_empty = 0;
   KOCR_TRY(postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold,
                               size_threshold, d_boxes, cap, counts, &n_empty));
-  if (!on_device) {
-    KOCR_HIP(ctx, hipMemcpyAsync(boxes, d_boxes, box_b, hipMemcpyDeviceToHost, ctx->stream));
-    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  KOCR_TRY(st.back(boxes, d_boxes, box_b));
+  KOCR_TRY(st.finish());
   if (n_empty > 0)
     KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR, "kocr_detect: empty contour list (IndexError at detection.py:272)");
   return KOCR_OK;
@@ -90,48 +73,31 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
   if (N < 0 || (N > 0 && (!img_rgb || !counts))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes: null buffer");
   const int C = crnn_classes(ctx);
   if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_recognize_boxes: call kocr_load_crnn first");
-  long M = 0;
-  for (int i = 0; i < N; ++i) {
-    if (counts[i] < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes: negative count");
-    M += counts[i];
-  }
-  if (M == 0) return KOCR_OK;
-  if (!boxes || !labels) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes: null buffer");
+  std::vector<WarpParam> prm;
+  const long M = prepare_box_warps(ctx, "kocr_recognize_boxes", N, boxes, counts, labels, CRNN_CROP_H, CRNN_CROP_W, prm);
+  if (M <= 0) return (int)M;
   ctx->last_pl.valid = false;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  std::vector<WarpParam> prm((size_t)M);
-  long m = 0;
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < counts[i]; ++j, ++m) {
-      const int rc = warp_prepare(boxes + m * 8, 31, 200, &prm[m], nullptr);
-      if (rc == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, "kocr_recognize_boxes: box with zero width or height (tools.py:95)");
-      if (rc != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes: singular perspective transform");
-      prm[m].img = i;
-    }
-  const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * 31 * 200 * sizeof(float);
-  const size_t lab_b = (size_t)M * crnn_label_width(ctx) * sizeof(int32_t), pb = (size_t)M * sizeof(WarpParam);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, pb + crop_b + lab_b + (on_device ? 0 : ib) + 4096));
-  ctx->io.off = 0;
-  WarpParam* d_prm = (WarpParam*)arena_alloc(ctx->io, pb);
-  float* d_crops = (float*)arena_alloc(ctx->io, crop_b);
-  int32_t* d_lab = (int32_t*)arena_alloc(ctx->io, lab_b);
-  const uint8_t* d_img = img_rgb;
-  if (!on_device) {
-    uint8_t* di = (uint8_t*)arena_alloc(ctx->io, ib);
-    if (!di) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_recognize_boxes: arena exhausted");
-    KOCR_HIP(ctx, hipMemcpyAsync(di, img_rgb, ib, hipMemcpyHostToDevice, ctx->stream));
-    d_img = di;
-  }
-  KOCR_HIP(ctx, hipMemcpyAsync(d_prm, prm.data(), pb, hipMemcpyHostToDevice, ctx->stream));
-  KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, 31, 200, d_crops));
-  const int cmb = (int)std::min<long>(M, 1024);
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(cmb, C)));
-  for (long s = 0; s < M; s += cmb) {
-    const int nb = (int)std::min<long>(cmb, M - s);
-    ctx->ws_reset();
-    KOCR_TRY(crnn_forward(ctx, d_crops + (size_t)s * 31 * 200, nb, d_lab + (size_t)s * crnn_label_width(ctx), nullptr));
-  }
-  KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, lab_b, hipMemcpyDeviceToHost, ctx->stream));
+  const int LW = crnn_label_width(ctx);
+  const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float);
+  const size_t lab_b = (size_t)M * LW * sizeof(int32_t), pb = (size_t)M * sizeof(WarpParam);
+  Staging st{ctx, ctx->io, "kocr_recognize_boxes", on_device != 0};
+  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, lab_b}));
+  const WarpParam* d_prm;
+  float* d_crops;
+  int32_t* d_lab;
+  const uint8_t* d_img;
+  KOCR_TRY(st.scratch(pb, d_prm));
+  KOCR_TRY(st.scratch(crop_b, d_crops));
+  KOCR_TRY(st.scratch(lab_b, d_lab));
+  KOCR_TRY(st.in(img_rgb, ib, d_img));
+  KOCR_TRY(st.put((WarpParam*)d_prm, prm.data(), pb));
+  KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
+  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), C)));
+  KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
+    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr);
+  }));
+  KOCR_TRY(st.download(labels, d_lab, lab_b));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KOCR_OK;
 }
@@ -156,15 +122,15 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   const size_t heat_b = (size_t)N * h2 * w2 * 2 * sizeof(float);
   const size_t box_b = (size_t)N * cap * 8 * sizeof(float);
   // ---- persistent buffers of this call ----
-  KOCR_TRY(arena_reserve(ctx, ctx->pl, bat_b + heat_b + box_b + 4096));
-  ctx->pl.off = 0;
-  uint8_t* d_bat = (uint8_t*)arena_alloc(ctx->pl, bat_b);
-  float* d_heat = (float*)arena_alloc(ctx->pl, heat_b);
-  float* d_boxes = (float*)arena_alloc(ctx->pl, box_b);
-  if (!d_bat || !d_heat || !d_boxes) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_pipeline: arena exhausted");
+  Staging pl{ctx, ctx->pl, "kocr_pipeline"};
+  KOCR_TRY(pl.reserve(0, {}, {bat_b, heat_b, box_b}));
+  uint8_t* d_bat;
+  float *d_heat, *d_boxes;
+  KOCR_TRY(pl.scratch(bat_b, d_bat));
+  KOCR_TRY(pl.scratch(heat_b, d_heat));
+  KOCR_TRY(pl.scratch(box_b, d_boxes));
   // ---- resize + pad, runs of identically-shaped contiguous images in one launch ----
-  size_t max_src = 0;
-  for (int i = 0; i < N; ++i) max_src = std::max(max_src, (size_t)hs[i] * ws[i] * 3);
+  Staging io{ctx, ctx->io, "kocr_pipeline", on_device != 0};
   int i = 0;
   while (i < N) {
     int j = i + 1;
@@ -174,22 +140,15 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     const int run = j - i;
     const size_t sb = (size_t)run * hs[i] * ws[i] * 3;
     const size_t tb = (size_t)(4 * (Wmax + Hmax) + 64) * sizeof(int);
-    KOCR_TRY(arena_reserve(ctx, ctx->io, tb + (on_device ? 0 : sb) + 4096));
-    ctx->io.off = 0;
-    const uint8_t* d_src = imgs[i];
-    if (!on_device) {
-      uint8_t* ds = (uint8_t*)arena_alloc(ctx->io, sb);
-      KOCR_HIP(ctx, hipMemcpyAsync(ds, imgs[i], sb, hipMemcpyHostToDevice, ctx->stream));
-      d_src = ds;
-    }
+    KOCR_TRY(io.reserve(tb, {sb}));
+    const uint8_t* d_src;
+    KOCR_TRY(io.in(imgs[i], sb, d_src));
     KOCR_TRY(launch_resize_pad(ctx, d_src, run, hs[i], ws[i], d_bat + (size_t)i * Hmax * Wmax * 3, dhs[i], dws[i],
                                Hmax, Wmax, 255, ctx->io));
     i = j;
   }
   // ---- detector forward (micro-batched) ----
-  int mb = micro_batch > 0 ? micro_batch : 32;
-  while (mb > 1 && craft_workspace_bytes(mb, Hmax, Wmax) > ((size_t)96 << 30)) mb = (mb + 1) / 2;
-  mb = std::min(mb, N);
+  const int mb = craft_micro_batch(micro_batch, N, Hmax, Wmax);
   KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(mb, Hmax, Wmax)));
   for (int s = 0; s < N; s += mb) {
     const int nb = std::min(mb, N - s);
@@ -215,10 +174,9 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     for (int k = 0; k < N; ++k) need = std::max(need, (int)counts[k]);
     if (need <= d_cap) return rc_pp;  // the other capacity error (dilation canvases beyond 2^31 pixels): not a matter of cap
     d_cap = need;
-    KOCR_TRY(arena_reserve(ctx, ctx->bx, (size_t)N * d_cap * 8 * sizeof(float) + 256));
-    ctx->bx.off = 0;
-    d_boxes = (float*)arena_alloc(ctx->bx, (size_t)N * d_cap * 8 * sizeof(float));
-    if (!d_boxes) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_pipeline: box arena exhausted");
+    Staging bx{ctx, ctx->bx, "kocr_pipeline"};
+    KOCR_TRY(bx.reserve(0, {}, {(size_t)N * d_cap * 8 * sizeof(float)}));
+    KOCR_TRY(bx.scratch((size_t)N * d_cap * 8 * sizeof(float), d_boxes));
     rc_pp = postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold, size_threshold,
                                d_boxes, d_cap, counts, nullptr, &dv);
   }
@@ -248,25 +206,26 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_pipeline: more crops than max_crops");
   }
   // ---- crops: homographies on the device (warp.hip), no host round trip ----
-  const size_t crop_b = (size_t)M * 31 * 200 * sizeof(float), lab_b = (size_t)M * crnn_label_width(ctx) * sizeof(int32_t);
-  KOCR_TRY(arena_reserve(ctx, ctx->io, (size_t)M * sizeof(WarpParam) + crop_b + lab_b + 8192));
-  ctx->io.off = 0;
-  WarpParam* d_prm = (WarpParam*)arena_alloc(ctx->io, (size_t)M * sizeof(WarpParam));
-  float* d_crops = (float*)arena_alloc(ctx->io, crop_b);
-  int32_t* d_lab = (int32_t*)arena_alloc(ctx->io, lab_b);
-  int* d_status = (int*)arena_alloc(ctx->io, 256);
+  const int LW = crnn_label_width(ctx);
+  const size_t crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), lab_b = (size_t)M * LW * sizeof(int32_t);
+  const size_t pb = (size_t)M * sizeof(WarpParam);
+  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, lab_b, 256}));
+  WarpParam* d_prm;
+  float* d_crops;
+  int32_t* d_lab;
+  int* d_status;
+  KOCR_TRY(io.scratch(pb, d_prm));
+  KOCR_TRY(io.scratch(crop_b, d_crops));
+  KOCR_TRY(io.scratch(lab_b, d_lab));
+  KOCR_TRY(io.scratch(256, d_status));
   KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), ctx->stream));
-  KOCR_TRY(launch_warp_prepare(ctx, d_boxes, dv.d_counts, N, d_cap, 31, 200, d_prm, d_status));
-  KOCR_TRY(launch_warp(ctx, d_bat, Hmax, Wmax, d_prm, (int)M, 31, 200, d_crops));
+  KOCR_TRY(launch_warp_prepare(ctx, d_boxes, dv.d_counts, N, d_cap, CRNN_CROP_H, CRNN_CROP_W, d_prm, d_status));
+  KOCR_TRY(launch_warp(ctx, d_bat, Hmax, Wmax, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   // ---- recogniser ----
-  const int C = crnn_classes(ctx);
-  const int cmb = (int)std::min<long>(M, 1024);
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(cmb, C)));
-  for (long s = 0; s < M; s += cmb) {
-    const int nb = (int)std::min<long>(cmb, M - s);
-    ctx->ws_reset();
-    KOCR_TRY(crnn_forward(ctx, d_crops + (size_t)s * 31 * 200, nb, d_lab + (size_t)s * crnn_label_width(ctx), nullptr));
-  }
+  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), crnn_classes(ctx))));
+  KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
+    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr);
+  }));
   if (host_fits) KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, lab_b, hipMemcpyDeviceToHost, ctx->stream));
   KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   KOCR_TRY(finish());
