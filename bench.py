@@ -2,7 +2,12 @@
 """bench.py — images/sec of Pipeline.recognize() on synthetic 768x768 RGB batches (BASELINE.json
 metric; workload = configs[3]: full pipeline, batch 32 x 768x768, scale=2, one MI355X per rank).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up (pages, weights, the head calibration), runs W warm-up and
+K timed steps, writes the outputs if asked and prints one JSON line with the contract's keys and the workload (`config`).
+--full then goes on to everything else described below (the profiled loop and roofline, the extra legs, the CPU oracle and
+parity, the live PMC passes) and prints the compact line of all of it instead.
 
 --dump-outputs DIR writes what the headline loop's last timed step returned (rank 0's boxes, words per page and texts) as
 DIR/<name>.npy; pages and weights are seeded, so the same arguments give the same inputs on every run and two builds can
@@ -325,6 +330,35 @@ def dump_outputs(dirname, out):
         np.save(os.path.join(dirname, name + ".npy"), a)
 
 
+def headline_record(args, world, seen, dt, n_words):
+    """The keys every run reports: the headline loop's figure (`dt` = its max-over-ranks time) and the workload it timed."""
+    return {
+        "metric": "images/sec end-to-end Pipeline.recognize() @768x768",
+        "value": world * args.batch * args.steps / dt,
+        "unit": "images/s",
+        "n_gpus": world,
+        "ranks_seen": seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("f32 (fp32 operands as 3 exact bf16 pieces, 6 MFMA products, fp32 accumulate; fp32-class error vs fp64: "
+                  "tests/test_conv_gpu.py)")
+        if args.split == "bf16x3" else
+        ("f32 (fp32 operands as 2 fp16 pieces [F(4,3) / head layers] or 3 bf16 pieces [1x1, dilated], 3 / 6 MFMA products, fp32 "
+         "accumulate; fp32-class error vs fp64: tests/test_conv_gpu.py)"),
+        "data": "synthetic (seeded rendered-text pages; random-init weights of the reference "
+                "architectures, detector head calibrated to emit word boxes)",
+        "config": {"workload": f"Pipeline.recognize full pipeline, batch {args.batch} x {SIDE}x{SIDE} RGB u8 per GPU, "
+                               f"scale={SCALE} (detector input {SIDE*SCALE}x{SIDE*SCALE}), BASELINE configs[3]",
+                   "global_batch": world * args.batch, "words_per_batch": n_words,
+                   "parallelism": f"dp{world} (images sharded, one process per GPU, RCCL process group; no data-path collective)",
+                   "split_mode": args.split},
+    }
+
+
 def compact_line(res):
     """The ONE stdout line: the contract's keys, `config`, a trimmed `roofline`, `cpu_baseline`, and one number per extra leg --
     short enough that the driver's record holds it whole.  Everything else goes to stderr / gpurun_out/bench_full.json."""
@@ -458,9 +492,15 @@ def main(argv=None, env=None):
                          "same command must agree with (scripts/profile_final.sh)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the headline path computed in its last timed step to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run everything else the benchmark measures and checks (profiled loop and "
+                         "roofline, extra legs, CPU oracle and parity, live PMC traffic); the options above that shape "
+                         "those legs apply to such a run only")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.alt_mode or args.profile_all):
+        ap.error("--alt-mode and --profile-all add to a --full run")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         respawn_under_torchrun(args, env)
@@ -566,6 +606,14 @@ def main(argv=None, env=None):
     n_words = sum(len(g) for g in out)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, out)
+    if not args.full:
+        res = headline_record(args, world, seen, dt, n_words)
+        if rank == 0:
+            json_out.write(json.dumps(res) + "\n")
+            json_out.flush()
+        torch.distributed.destroy_process_group()
+        ctx.close()
+        return res if rank == 0 else None
     # ---- the same K steps with the HIP-event profiler on: stage times + roofline of the dominant kernel --
     fold_process_profile()
     ctx.profile_reset()
@@ -759,7 +807,7 @@ def main(argv=None, env=None):
                 traffic_live = k.pmc.measure_traffic(os.path.abspath(__file__), name)
                 traffic = traffic_live["hbm_bytes_per_launch"]
                 traffic_src = (f"measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                               f"`bench.py --steps 1 --warmup 1 --profile-all`, average over {traffic_live['launches']} launches")
+                               f"`bench.py --full --steps 1 --warmup 1 --profile-all`, average over {traffic_live['launches']} launches")
             except Exception as e:  # noqa: BLE001 -- fall back to the committed summary, say why
                 traffic_src = f"live PMC passes failed ({type(e).__name__}: {str(e)[:120]}); "
         for cand in ([] if traffic is not None else sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json")), reverse=True)):
@@ -770,31 +818,9 @@ def main(argv=None, env=None):
                 traffic_src = (traffic_src if traffic_src.startswith("live PMC") else "") + "profiles/" + os.path.basename(cand) + \
                     f", average over {row['launches']} launches of the bench process"
                 break
-        res = {
-            "metric": "images/sec end-to-end Pipeline.recognize() @768x768",
-            "value": world * args.batch * args.steps / dt,
-            "unit": "images/s",
-            "n_gpus": world,
-            "ranks_seen": seen,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
+        res = headline_record(args, world, seen, dt, n_words)
+        res.update({
             "ms_per_step_profiled": dt_prof / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": ("f32 (fp32 operands as 3 exact bf16 pieces, 6 MFMA products, fp32 accumulate; fp32-class error vs fp64: "
-                      "tests/test_conv_gpu.py)")
-            if args.split == "bf16x3" else
-            ("f32 (fp32 operands as 2 fp16 pieces [F(4,3) / head layers] or 3 bf16 pieces [1x1, dilated], 3 / 6 MFMA products, fp32 "
-             "accumulate; fp32-class error vs fp64: tests/test_conv_gpu.py)"),
-            "data": "synthetic (seeded rendered-text pages; random-init weights of the reference "
-                    "architectures, detector head calibrated to emit word boxes)",
-            "config": {"workload": f"Pipeline.recognize full pipeline, batch {args.batch} x {SIDE}x{SIDE} RGB u8 per GPU, "
-                                   f"scale={SCALE} (detector input {SIDE*SCALE}x{SIDE*SCALE}), BASELINE configs[3]",
-                       "global_batch": world * args.batch, "words_per_batch": n_words,
-                       "parallelism": f"dp{world} (images sharded, one process per GPU, RCCL process group; no data-path collective)",
-                       "split_mode": args.split},
             "roofline": {"bound": "mfma", "kernel": name,
                          "achieved": achieved, "peak": peak,
                          "unit": "TFLOP/s", "frac": achieved / peak,
@@ -827,7 +853,7 @@ def main(argv=None, env=None):
             "crnn_only": {"metric": "ms/crop CRNN (BASELINE configs[2]: 512 crops 31x200, CTC greedy)",
                           "value": crnn_us_per_crop / 1e3, "unit": "ms/crop",
                           "fp32_mfma_floor_ms": 13.444e9 / (FP32_MFMA_PEAK_TF * 1e12) * 1e3},
-        }
+        })
         res.update(extra)
         if alt is not None:
             res["alt_split_mode"] = alt

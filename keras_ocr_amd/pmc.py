@@ -107,8 +107,8 @@ def measure_traffic(bench_path, prof_name, timeout=150, clock=True):
         if v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK",
                  "ROLE_NAME", "ROLE_WORLD_SIZE", "GROUP_WORLD_SIZE", "TORCH_NCCL_ASYNC_ERROR_HANDLING") or v.startswith("TORCHELASTIC_"):
             env.pop(v, None)
-    child = [sys.executable, os.path.abspath(bench_path), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-alt-mode",
-             "--no-extra", "--profile-all", "--no-live-traffic"]
+    child = [sys.executable, os.path.abspath(bench_path), "--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+             "--no-alt-mode", "--no-extra", "--profile-all", "--no-live-traffic"]
     sums, launches, line = {}, {}, None
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):

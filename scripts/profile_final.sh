@@ -6,9 +6,9 @@ cd /tmp && export TMPDIR=/tmp
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/final_$1
 mkdir -p $OUT
-python $REPO/bench.py --steps 10 --warmup 3 2> $OUT/bench.err | tail -1 > $OUT/bench.json
+python $REPO/bench.py --full --steps 10 --warmup 3 2> $OUT/bench.err | tail -1 > $OUT/bench.json
 cp $REPO/gpurun_out/bench_full.json $OUT/bench_full.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $REPO/bench.py --profile-all --no-live-traffic > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $REPO/bench.py --full --profile-all --no-live-traffic > $OUT/trace.log 2>&1
 grep '^\[bench full\] ' $OUT/trace.log | tail -1 | sed 's/^\[bench full\] //' > $OUT/bench_under_rocprof.json
 KOCR_PROF_LAYERS=1 python $REPO/scripts/perf_craft.py 8 1536 1536 5 > $OUT/craft_layers.txt 2>&1
 KOCR_PROF_LAYERS=1 python $REPO/scripts/perf_crnn.py 512 > $OUT/crnn_layers.txt 2>&1

@@ -1,5 +1,6 @@
 """CPU suite: the host-side pieces of bench.py (no GPU): synthetic pages, the parity object, the work model behind
 the roofline object, and the refusal to report a multi-GPU number from fewer devices."""
+import collections
 import subprocess
 import sys
 import os
@@ -229,7 +230,7 @@ def test_bench_main_runs_at_world_2_over_gloo_with_a_mocked_library(capfd):
         port = s.getsockname()[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_bench_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_bench_worker, args=(r, 2, port, q, ("--full",))) for r in range(2)]
     for p in procs:
         p.start()
     got = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
@@ -252,6 +253,85 @@ def test_bench_main_runs_at_world_2_over_gloo_with_a_mocked_library(capfd):
     assert sum(ln.startswith('{"metric"') for ln in out.splitlines()) == 1   # exactly one JSON line on stdout
 
 
+class _CountingMockContext(_BenchMockContext):
+    """The library double, counting the calls of a run that go beyond setting up."""
+
+    def __init__(self):
+        super().__init__()
+        self.calls = collections.Counter()
+
+    def pipeline(self, *a, **kw):
+        self.calls["pipeline"] += 1
+        return super().pipeline(*a, **kw)
+
+    def profile_enable(self, on=True):
+        self.calls["profile_enable(True)"] += bool(on)
+        super().profile_enable(on)
+
+    def crnn_forward_device(self, *a, **kw):
+        self.calls["crnn_forward_device"] += 1
+
+    def craft_forward_device(self, *a, **kw):
+        self.calls["craft_forward_device"] += 1
+
+
+class _CountingHostEnv(_HostEnv):
+    def context(self, k, local_rank):
+        self.ctx = _CountingMockContext()
+        return self.ctx
+
+
+def _plain_bench_worker(rank, world, port, q):
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
+                      MASTER_PORT=str(port))
+    sys.path.insert(0, ROOT)
+    import bench
+
+    env = _CountingHostEnv()
+    res = bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "4"], env=env)
+    q.put((rank, res, +env.ctx.calls))
+
+
+def test_bench_plain_run_does_only_the_headline(capfd):
+    """Without --full, bench.main() at world size 2 runs the warm-up and the timed steps and nothing else (no profiled loop,
+    no extra leg, no solo leg of rank 0), and rank 0 prints the headline keys alone on its one stdout line."""
+    import json
+    import socket
+    import torch.multiprocessing as mp
+
+    with socket.socket() as s_:
+        s_.bind(("127.0.0.1", 0))
+        port = s_.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_plain_bench_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    (_, res, calls0), (_, none, calls1) = got
+    assert none is None and isinstance(res, dict)
+    assert calls0 == calls1 == {"pipeline": 3}                        # 1 warm-up + 2 timed steps per rank
+    assert sorted(res) == sorted(["metric", "value", "unit", "n_gpus", "ranks_seen", "steps", "warmup", "ms_per_step",
+                                  "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"])
+    assert res["n_gpus"] == 2 and res["ranks_seen"] == 2 and res["steps"] == 2 and res["warmup"] == 1
+    assert res["config"]["global_batch"] == 8 and res["higher_is_better"] is True and res["unit"] == "images/s"
+    assert abs(res["value"] - 8 * 2 / (res["ms_per_step"] * 2 / 1e3)) < 1e-6 * res["value"]
+    lines = [ln for ln in capfd.readouterr().out.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1 and json.loads(lines[0]) == res
+
+
+def test_bench_refuses_full_only_options_on_a_plain_run():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    for opt in ("--alt-mode", "--profile-all"):
+        with pytest.raises(SystemExit):
+            bench.main([opt], env=_HostEnv())
+
+
 @pytest.mark.parametrize("pages,blocks", [(14, [4, 4, 4, 2]), (5, [2, 2, 1, 0])], ids=["ragged_last_block", "an_empty_rank"])
 def test_bench_main_at_world_4_with_uneven_shards(pages, blocks, capfd):
     """the sharded / scattered legs of bench.main() at world size 4 when the ONE batch does not divide
@@ -267,7 +347,7 @@ def test_bench_main_at_world_4_with_uneven_shards(pages, blocks, capfd):
         port = s_.getsockname()[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_bench_worker, args=(r, 4, port, q, ("--cfg5-pages", str(pages)))) for r in range(4)]
+    procs = [ctx.Process(target=_bench_worker, args=(r, 4, port, q, ("--full", "--cfg5-pages", str(pages)))) for r in range(4)]
     for p in procs:
         p.start()
     got = sorted((q.get(timeout=300) for _ in procs), key=lambda t: t[0])
@@ -303,7 +383,7 @@ def test_bench_main_at_world_8_the_cfg5_job_shape(pages, blocks, capfd):
         port = s_.getsockname()[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    extra = ("--cfg5-pages", str(pages), "--batch", "32", "--side5", "16")
+    extra = ("--full", "--cfg5-pages", str(pages), "--batch", "32", "--side5", "16")
     procs = [ctx.Process(target=_bench_worker, args=(r, 8, port, q, extra)) for r in range(8)]
     for p in procs:
         p.start()
