@@ -195,6 +195,27 @@ int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* 
  * on_device is set. */
 int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device);
 
+/* ---- the detector's training data and validation loss (detection.py:106-198, :696, :698-743) ---- */
+/* detection.compute_maps for N pages of H x W (both even) with one uint8 heat-map (hh x hw, detection.get_gaussian_heatmap):
+ * maps N x H/2 x W/2 x 2 float32, text then link, equal bit for bit to the full-map statement tests/maps_statement.py
+ * (DESIGN.md section 4).  The characters of all pages, line after line: char_quads n_chars x 4 x 2 float32 (the points as
+ * given; the rotated box is taken here), is_space uint8[n_chars] (a " " character: resets the link chain, draws nothing),
+ * line_offsets int32[n_lines + 1] (line l = characters [line_offsets[l], line_offsets[l + 1]), a non-empty range),
+ * image_line_offsets int32[N + 1] (page i = lines [image_line_offsets[i], image_line_offsets[i + 1])).  All buffers are device
+ * pointers when on_device is set; host offsets are checked (KOCR_EINVAL), device ones are only clamped to the buffers.
+ * KOCR_EINVAL for an odd H or W (the reference's AssertionError). */
+int kocr_compute_maps(kocr_ctx* ctx, const uint8_t* heatmap, int hh, int hw, int N, int H, int W, int n_chars,
+                      const float* char_quads, const uint8_t* is_space, int n_lines, const int32_t* line_offsets,
+                      const int32_t* image_line_offsets, float* maps, int on_device);
+/* The per-image half of Keras' compiled "mse" (detection.py:696) on N maps of h x w x 2: sums[n] = sum over the pixels of
+ * the mean over the two channels of (y_true - y_pred)^2, float64, in a fixed order.  model.evaluate's loss is
+ * sum_n weight_n sums[n] / (N h w).  All buffers are device pointers when on_device is set. */
+int kocr_heat_mse(kocr_ctx* ctx, const float* y_true, const float* y_pred, int N, int h, int w, double* sums, int on_device);
+/* kocr_craft_forward (arguments as there) and kocr_heat_mse against y_true (N x H/2 x W/2 x 2) in one call: the heat-maps
+ * stay in HBM and are bit for bit those kocr_craft_forward returns, so sums equal kocr_heat_mse on them bit for bit. */
+int kocr_craft_mse(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W, const float* y_true, int micro_batch,
+                   double* sums, int on_device);
+
 /* ---- Detector.detect (detection.py:745-785): compute_input + predict + getBoxes in one call; the
  * heat-maps stay in HBM.  Arguments as kocr_craft_forward + kocr_get_boxes; counts is a HOST array. */
 int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W,

@@ -75,6 +75,9 @@ def load_library():
         "kocr_ctc_batch_cost": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, ci]),
         "kocr_crnn_ctc_loss": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, ci]),
         "kocr_crnn_features": (ci, [vp, vp, ci, vp, ci]),
+        "kocr_compute_maps": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, ci]),
+        "kocr_heat_mse": (ci, [vp, vp, vp, ci, ci, ci, vp, ci]),
+        "kocr_craft_mse": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, vp, ci]),
         "kocr_get_boxes": (ci, [vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, vp, vp, ci, ci]),
         "kocr_warp_crops": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, ci]),
         "kocr_warp_quads": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
@@ -572,6 +575,49 @@ class Context:
             self._check(self._lib.kocr_set_min_area_rect(self._h, old))
 
     # -- measurement -------------------------------------------------------------------
+    # -- the detector's training data and validation loss (detection.py:106-198, :696) ----------------------------------
+    def compute_maps(self, heatmap, image_height, image_width, line_groups):
+        """detection.compute_maps for a batch of pages (kocr_compute_maps): ``line_groups`` holds, per page, a list of lines
+        of (points (4, 2), character) -- the ``lines`` argument of the reference.  Returns (N, H/2, W/2, 2) float32.
+        ``heatmap``: 2-D uint8.  The points are taken as float32.  An odd height or width raises AssertionError, an empty
+        line IndexError (as the reference)."""
+        hm = np.ascontiguousarray(heatmap)
+        if hm.ndim != 2 or hm.dtype != np.uint8:
+            raise NotImplementedError(f"compute_maps takes a 2-D uint8 heat-map, got {hm.dtype} of shape {hm.shape}")
+        assert image_height % 2 == 0, "Height must be an even number"
+        assert image_width % 2 == 0, "Width must be an even number"
+        q, sp, loff, ioff = _flatten_lines(line_groups)
+        n = len(ioff) - 1
+        out = np.zeros((n, image_height // 2, image_width // 2, 2), dtype=np.float32)
+        self._check(self._lib.kocr_compute_maps(self._h, _ptr(hm), hm.shape[0], hm.shape[1], n, int(image_height),
+                                                int(image_width), len(q), _ptr(q), _ptr(sp), len(loff) - 1, _ptr(loff),
+                                                _ptr(ioff), _ptr(out), 0))
+        return out
+
+    def heat_mse(self, y_true, y_pred):
+        """Per-image float64 sums of Keras' mse on (N, h, w, 2) maps (kocr_heat_mse): sum over pixels of the channel mean
+        of (y_true - y_pred)^2."""
+        y = np.ascontiguousarray(y_true, dtype=np.float32)
+        p = np.ascontiguousarray(y_pred, dtype=np.float32)
+        if y.shape != p.shape or y.ndim != 4 or y.shape[3] != 2:
+            raise ValueError(f"y_true and y_pred must both have shape (N, h, w, 2), got {y.shape} and {p.shape}")
+        sums = np.zeros(y.shape[0], np.float64)
+        self._check(self._lib.kocr_heat_mse(self._h, _ptr(y), _ptr(p), y.shape[0], y.shape[1], y.shape[2], _ptr(sums), 0))
+        return sums
+
+    def craft_mse(self, images, y_true, micro_batch=0):
+        """craft_forward(images) and heat_mse against y_true in one call (kocr_craft_mse): the heat-maps stay in HBM."""
+        x, dt = _detector_input(images)
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError("images must have shape (N,H,W,3)")
+        n, h, w, _ = x.shape
+        y = np.ascontiguousarray(y_true, dtype=np.float32)
+        if y.shape != (n, h // 2, w // 2, 2):
+            raise ValueError(f"y must have shape {(n, h // 2, w // 2, 2)}, got {y.shape}")
+        sums = np.zeros(n, np.float64)
+        self._check(self._lib.kocr_craft_mse(self._h, _ptr(x), dt, n, h, w, _ptr(y), int(micro_batch), _ptr(sums), 0))
+        return sums
+
     def profile_enable(self, on=True):
         self._check(self._lib.kocr_profile_enable(self._h, int(bool(on))))
 
@@ -623,6 +669,29 @@ def _detector_input(images):
     if x.dtype == np.uint8:
         return x, KOCR_U8
     return np.ascontiguousarray(x, dtype=np.float32), KOCR_F32
+
+
+def _flatten_lines(line_groups):
+    """per page a list of lines of (points, character) -> char_quads float32 (n, 4, 2), is_space uint8 (n,), line_offsets
+    int32 (n_lines + 1,), image_line_offsets int32 (N + 1,): one np.asarray per line.  An empty line raises IndexError (as
+    the reference's fix_line), a non-finite point ValueError."""
+    quads, spaces, line_len, page_len = [], [], [], []
+    for lines in line_groups:
+        page_len.append(len(lines))
+        for line in lines:
+            if len(line) == 0:
+                raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+            boxes, chars = zip(*line)
+            quads.append(np.asarray(boxes, dtype=np.float32).reshape(len(line), 4, 2))
+            spaces.append(np.fromiter((c == " " for c in chars), dtype=np.uint8, count=len(line)))
+            line_len.append(len(line))
+    q = np.ascontiguousarray(np.concatenate(quads) if quads else np.zeros((0, 4, 2), np.float32))
+    if not np.isfinite(q).all():
+        raise ValueError("compute_maps: character points must be finite")
+    sp = np.ascontiguousarray(np.concatenate(spaces) if spaces else np.zeros(0, np.uint8))
+    loff = np.concatenate([[0], np.cumsum(line_len, dtype=np.int64)]).astype(np.int32)
+    ioff = np.concatenate([[0], np.cumsum(page_len, dtype=np.int64)]).astype(np.int32)
+    return q, sp, loff, ioff
 
 
 def _flatten_boxes(box_groups):

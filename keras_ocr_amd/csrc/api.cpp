@@ -465,6 +465,111 @@ int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, i
   });
 }
 
+int kocr_compute_maps(kocr_ctx* ctx, const uint8_t* heatmap, int hh, int hw, int N, int H, int W, int n_chars,
+                      const float* char_quads, const uint8_t* is_space, int n_lines, const int32_t* line_offsets,
+                      const int32_t* image_line_offsets, float* maps, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_compute_maps";
+  if (H % 2 != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_compute_maps: Height must be an even number");
+  if (W % 2 != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_compute_maps: Width must be an even number");
+  if (N < 0 || H < 0 || W < 0 || hh < 1 || hw < 1 || n_chars < 0 || n_lines < 0)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_compute_maps: bad sizes");
+  if (N > 0 && (!heatmap || !line_offsets || !image_line_offsets || !maps || (n_chars > 0 && (!char_quads || !is_space))))
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_compute_maps: null buffer");
+  if (!on_device && N > 0) {
+    bool ok = line_offsets[0] == 0 && line_offsets[n_lines] == n_chars && image_line_offsets[0] == 0 &&
+              image_line_offsets[N] == n_lines;
+    for (int l = 0; ok && l < n_lines; ++l) ok = line_offsets[l] < line_offsets[l + 1];
+    for (int i = 0; ok && i < N; ++i) ok = image_line_offsets[i] <= image_line_offsets[i + 1];
+    if (!ok) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_compute_maps: offsets must run from 0 to n_chars / n_lines, lines non-empty");
+  }
+  const int h = H / 2, w = W / 2;
+  if (N == 0 || (long)h * w == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)n_chars, px = (size_t)N * h * w;
+  const size_t heat_b = (size_t)hh * hw, quad_b = n * 8 * sizeof(float), line_b = ((size_t)n_lines + 1) * sizeof(int32_t);
+  const size_t img_b = ((size_t)N + 1) * sizeof(int32_t), maps_b = px * 2 * sizeof(float);
+  const size_t slot_b = 2 * n * sizeof(MapSlot), plane_b = px * 2 * sizeof(int32_t), tab_b = 256 * sizeof(float);
+  Staging st{ctx, ctx->io, fn, on_device != 0};
+  KOCR_TRY(st.reserve(0, {heat_b, quad_b, n, line_b, img_b, maps_b},
+                      {quad_b, n * 2 * sizeof(float), n * sizeof(int), n * sizeof(int), slot_b, plane_b, tab_b}));
+  const uint8_t *d_heat, *d_space;
+  const float* d_quads;
+  const int32_t *d_loff, *d_ioff;
+  float* d_maps;
+  KOCR_TRY(st.in(heatmap, heat_b, d_heat));
+  KOCR_TRY(st.in(char_quads, quad_b, d_quads));
+  KOCR_TRY(st.in(is_space, n, d_space));
+  KOCR_TRY(st.in(line_offsets, line_b, d_loff));
+  KOCR_TRY(st.in(image_line_offsets, img_b, d_ioff));
+  KOCR_TRY(st.out(maps, maps_b, d_maps));
+  MapsWork wk;
+  KOCR_TRY(st.scratch(quad_b, wk.rbox));
+  KOCR_TRY(st.scratch(n * 2 * sizeof(float), wk.ctr));
+  KOCR_TRY(st.scratch(n * sizeof(int), wk.permx));
+  KOCR_TRY(st.scratch(n * sizeof(int), wk.permy));
+  KOCR_TRY(st.scratch(slot_b, wk.slots));
+  KOCR_TRY(st.scratch(plane_b, wk.planes));
+  // numpy's float32 v / 255 (detection.py:197): IEEE division on the host, so the device's division rule never matters
+  float table[256];
+  for (int v = 0; v < 256; ++v) table[v] = (float)v / 255.0f;
+  KOCR_TRY(st.upload(table, tab_b, wk.table));
+  KOCR_TRY(launch_compute_maps(ctx, d_heat, hh, hw, N, h, w, n_chars, d_quads, d_space, n_lines, d_loff, d_ioff, wk, d_maps));
+  KOCR_TRY(st.back(maps, d_maps, maps_b));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `table` is host memory about to go out of scope
+  return KOCR_OK;
+}
+
+int kocr_heat_mse(kocr_ctx* ctx, const float* y_true, const float* y_pred, int N, int h, int w, double* sums, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (N < 0 || h < 0 || w < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_heat_mse: bad sizes");
+  if (N > 0 && (!y_true || !y_pred || !sums)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_heat_mse: null buffer");
+  if (N == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t yb = (size_t)N * h * w * 2 * sizeof(float), sb = (size_t)N * sizeof(double);
+  Staging st{ctx, ctx->io, "kocr_heat_mse", on_device != 0};
+  KOCR_TRY(st.reserve(0, {yb, yb, sb}));
+  const float *d_t, *d_p;
+  double* d_s;
+  KOCR_TRY(st.in(y_true, yb, d_t));
+  KOCR_TRY(st.in(y_pred, yb, d_p));
+  KOCR_TRY(st.out(sums, sb, d_s));
+  KOCR_TRY(launch_heat_mse(ctx, d_t, d_p, N, h * w, d_s));
+  KOCR_TRY(st.back(sums, d_s, sb));
+  return st.finish();
+}
+
+int kocr_craft_mse(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W, const float* y_true, int micro_batch,
+                   double* sums, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (N < 0 || (N > 0 && (!img || !y_true || !sums))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_mse: null buffer");
+  if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_mse: bad dtype");
+  if (N == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = craft_micro_batch(micro_batch, N, H, W);
+  const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
+  const size_t out_img = (size_t)(H / 2) * (W / 2) * 2 * sizeof(float);
+  Staging st{ctx, ctx->ws, "kocr_craft_mse", on_device != 0};
+  KOCR_TRY(st.reserve(craft_workspace_bytes(mb, H, W), {in_img * mb, out_img * mb, sizeof(double) * mb}, {out_img * mb}));
+  for (int s = 0; s < N; s += mb) {
+    const int nb = std::min(mb, N - s);
+    ctx->ws_reset();
+    const void* d_in;
+    const float* d_y;
+    float* d_heat;
+    double* d_s;
+    KOCR_TRY(st.in((const void*)((const char*)img + (size_t)s * in_img), in_img * nb, d_in));
+    KOCR_TRY(st.in((const float*)((const char*)y_true + (size_t)s * out_img), out_img * nb, d_y));
+    KOCR_TRY(st.out(sums + s, sizeof(double) * nb, d_s));
+    KOCR_TRY(st.scratch(out_img * nb, d_heat));
+    KOCR_TRY(craft_forward(ctx, d_in, dtype, nb, H, W, d_heat));
+    KOCR_TRY(launch_heat_mse(ctx, d_y, d_heat, nb, (H / 2) * (W / 2), d_s));
+    KOCR_TRY(st.back(sums + s, d_s, sizeof(double) * nb));
+    KOCR_TRY(st.finish());
+  }
+  return KOCR_OK;
+}
+
 int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float detection_threshold,
                    float text_threshold, float link_threshold, int size_threshold, float* boxes,
                    int32_t* counts, int cap, int on_device) {

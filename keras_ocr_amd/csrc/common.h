@@ -452,6 +452,29 @@ int launch_warp_prepare(kocr_ctx* ctx, const float* d_boxes, const int* d_counts
 int launch_warp_quads(kocr_ctx* ctx, const float* d_src, const float* d_dst, const int* d_img, const int* d_cw,
                       const int* d_ch, int M, WarpParam* d_prm, double* d_mfwd, int* d_status);
 
+// warp.hip: detection.compute_maps for a batch of pages (kocr_compute_maps).  A slot is one quad drawn into one plane (0 text,
+// 1 link) of one page: the inverse homography and the pixel box [x0, x1] x [y0, y1] it may touch (x1 < x0: nothing).
+struct MapSlot {
+  double mi[9];
+  int x0, y0, x1, y1;
+  int img, plane;
+};
+// device work buffers of launch_compute_maps for n characters of N pages of h x w map pixels
+struct MapsWork {
+  float* rbox;     // [n][8] rotated boxes
+  float* ctr;      // [n][2] centres
+  int* permx;      // [n] reading order by x, per line
+  int* permy;      // [n] by y
+  MapSlot* slots;  // [2n]: ordered character k of a line -> its quad, the link ending at it
+  int* planes;     // [N][2][h][w] integer sums
+  const float* table;  // [256] float32 v / 255
+};
+int launch_compute_maps(kocr_ctx* ctx, const uint8_t* d_heat, int hh, int hw, int N, int h, int w, int n_chars,
+                        const float* d_quads, const uint8_t* d_space, int n_lines, const int* d_line_off, const int* d_img_off,
+                        const MapsWork& wk, float* d_maps);
+// Keras' mse on the maps: per-image float64 sums d_sums[N] of the channel-mean squared error over h w pixels
+int launch_heat_mse(kocr_ctx* ctx, const float* d_true, const float* d_pred, int N, int hw_px, double* d_sums);
+
 // imgproc.hip
 int launch_resize_pad_f32(kocr_ctx* ctx, const float* d_src, int n, int sh, int sw, int C, float* d_dst, int dh, int dw, int Hmax,
                           int Wmax, float cval, Arena& tab_arena);

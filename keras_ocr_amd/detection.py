@@ -1,5 +1,6 @@
 """Host-side mirror of ``keras_ocr.detection.Detector`` (reference ``keras_ocr/detection.py:661-785``).
 The Keras model and the OpenCV post-processing are replaced by libkocr (HIP, gfx950)."""
+import itertools
 import typing
 
 import numpy as np
@@ -28,6 +29,53 @@ def load_torch_state_dict(weights_path):
     return {k: v.numpy() for k, v in pretrained.items() if k.split(".")[-1] != "num_batches_tracked"}
 
 
+def compute_input(image):
+    """detection.compute_input (detection.py:34-42): RGB -> the network's normalised float32 input."""
+    image = image.astype("float32")
+    mean = np.array([0.485, 0.456, 0.406])
+    variance = np.array([0.229, 0.224, 0.225])
+    image -= mean * 255
+    image /= variance * 255
+    return image
+
+
+def invert_input(X):  # pylint: disable=invalid-name
+    """detection.invert_input (detection.py:45-52): compute_input's inverse, clipped to uint8."""
+    X = X.copy()
+    mean = np.array([0.485, 0.456, 0.406])
+    variance = np.array([0.229, 0.224, 0.225])
+    X *= variance * 255
+    X += mean * 255
+    return X.clip(0, 255).astype("uint8")
+
+
+def get_gaussian_heatmap(size=512, distanceRatio=3.34):  # pylint: disable=invalid-name
+    """detection.get_gaussian_heatmap (detection.py:55-62): the uint8 Gaussian compute_maps warps onto every character."""
+    v = np.abs(np.linspace(-size / 2, size / 2, num=size))
+    x, y = np.meshgrid(v, v)
+    g = np.sqrt(x**2 + y**2)
+    g *= distanceRatio / (size / 2)
+    g = np.exp(-(1 / 2) * (g**2))
+    g *= 255
+    return g.clip(0, 255).astype("uint8")
+
+
+def compute_maps(heatmap, image_height, image_width, lines):
+    """detection.compute_maps (detection.py:106-198) on the default context: the CRAFT targets of one page, (H/2, W/2, 2)
+    float32, region (text) map then affinity (link) map.  ``lines``: a list of lines, each a list of (points (4, 2),
+    character).  Runs on the GPU (kocr_compute_maps), bit for bit the reference's full-map warps.
+    Only a 2-D uint8 heat-map is supported."""
+    heatmap = np.asarray(heatmap)
+    if heatmap.dtype != np.uint8 or heatmap.ndim != 2:
+        raise NotImplementedError(f"compute_maps supports a 2-D uint8 heat-map only, got {heatmap.dtype} of shape {heatmap.shape}")
+    return _lib.default_context().compute_maps(heatmap, image_height, image_width, [lines])[0]
+
+
+def map_to_rgb(y):
+    """detection.map_to_rgb (detection.py:201-204): (h, w, 2) maps -> (h, w, 3) uint8 for display."""
+    return (np.concatenate([y, np.zeros((y.shape[0], y.shape[1], 1))], axis=-1) * 255).astype("uint8")
+
+
 def getBoxes(y_pred, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,  # pylint: disable=invalid-name
              min_area_rect=None):
     """detection.getBoxes (detection.py:207-287) on the default context: (N,h,w,2) float32 heat-maps -> list of (n_i,4,2)
@@ -51,6 +99,28 @@ class _CraftModel:
 
     def predict(self, X, batch_size=32, **kwargs):  # pylint: disable=invalid-name,unused-argument
         return self._ctx.craft_forward(np.asarray(X), micro_batch=batch_size or 0)
+
+    def evaluate(self, x, y, batch_size=None, sample_weight=None, **kwargs):  # pylint: disable=unused-argument
+        """The loss of ``model.compile(loss="mse")`` (detection.py:696) as Keras' evaluate reports it: per pixel
+        l = mean over the two maps of (y - y_hat)^2; with SUM_OVER_BATCH_SIZE and batch averages weighted by batch size
+        this is sum_n w_n sum_p l_np / (N h w) whatever ``batch_size``.  The forward and the
+        per-image sums run on the GPU (kocr_craft_mse); ``batch_size`` is the forward's micro-batch."""
+        x = np.asarray(x)
+        sums = self._ctx.craft_mse(x, y, micro_batch=batch_size or 0)
+        n, h, w = np.shape(y)[:3]
+        sw = np.ones(n) if sample_weight is None else np.asarray(sample_weight, np.float64).reshape(n)
+        return float((sw * sums).sum() / (n * h * w))
+
+    def fit(self, *args, **kwargs):
+        """Training is not implemented (gradients are out of scope)."""
+        raise NotImplementedError(_INFERENCE_ONLY)
+
+    def compile(self, *args, **kwargs):
+        """Training is not implemented (gradients are out of scope)."""
+        raise NotImplementedError(_INFERENCE_ONLY)
+
+
+_INFERENCE_ONLY = "keras-ocr_amd is inference-only: training (fit / compile) is not implemented"
 
 
 class Detector:
@@ -86,6 +156,25 @@ class Detector:
             state = _weights.synthetic_craft_weights()
         self._ctx.load_craft(state)
         self.model = _CraftModel(self._ctx)
+
+    def get_batch_generator(self, image_generator, batch_size=8, heatmap_size=512, heatmap_distance_ratio=1.5):
+        """Detector.get_batch_generator (detection.py:698-743): batches (X, y) or, when the samples are
+        (image, lines, sample_weight), (X, y, sample_weights) -- X = compute_input(images), y the compute_maps targets of
+        every page, computed on the GPU in one call per batch.  Unlike the reference, an exhausted generator ends the
+        iteration, and a last batch shorter than batch_size is yielded."""
+        heatmap = get_gaussian_heatmap(size=heatmap_size, distanceRatio=heatmap_distance_ratio)
+        while True:
+            batch = list(itertools.islice(image_generator, batch_size))
+            if not batch:
+                return
+            images = np.array([entry[0] for entry in batch])
+            line_groups = [entry[1] for entry in batch]
+            X = compute_input(images)  # pylint: disable=invalid-name
+            y = self._ctx.compute_maps(heatmap, images.shape[1], images.shape[2], line_groups)
+            if len(batch[0]) == 3:
+                yield X, y, np.array([sample[2] for sample in batch])
+            else:
+                yield X, y
 
     def detect(self, images: typing.List[typing.Union[np.ndarray, str]], detection_threshold=0.7, text_threshold=0.4,
                link_threshold=0.4, size_threshold=10, min_area_rect=None, **kwargs):

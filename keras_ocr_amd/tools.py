@@ -174,6 +174,19 @@ def get_rotated_box(points):
     return np.array([tl, tr, br, bl], dtype="float32"), rotation
 
 
+def fix_line(line):
+    """tools.fix_line (tools.py:584-600): [(points, character)] -> (the line in reading order with [tl, tr, br, bl] float32
+    boxes, "horizontal" | "vertical").  Ties between equal centres keep the given order (a stable sort; numpy's default
+    sort, the reference's, is not stable)."""
+    line = [(get_rotated_box(box)[0], character) for box, character in line]
+    centers = np.array([box.mean(axis=0) for box, _ in line])
+    sortedx = centers[:, 0].argsort(kind="stable")
+    sortedy = centers[:, 1].argsort(kind="stable")
+    if np.diff(centers[sortedy][:, 1]).sum() > np.diff(centers[sortedx][:, 0]).sum():
+        return [line[idx] for idx in sortedy], "vertical"
+    return [line[idx] for idx in sortedx], "horizontal"
+
+
 def warpBox(image, box, target_height=None, target_width=None, margin=0, cval=None, return_transform=False,  # pylint: disable=invalid-name
             skip_rotate=False, ctx=None):
     """tools.warpBox (tools.py:61-117), full signature: warp the quadrilateral ``box`` of ``image`` (HxW or HxWx3
