@@ -111,6 +111,18 @@ int kocr_craft_tap_count(kocr_ctx* ctx);
 int kocr_craft_tap_info(kocr_ctx* ctx, int i, char* name, char* kernel, int32_t* dims);
 int kocr_craft_get_tap(kocr_ctx* ctx, const char* name, int which, float* dst, float* amax_dst);
 
+/* ---- taps of the recogniser forward (the same recorder; its readers are the three above) ------------------------
+ * kocr_crnn_set_taps selects launches of kocr_crnn_forward by name, replacing any detector taps (one network is
+ * recorded at a time; the other network's forward records nothing): conv_1 .. conv_7 (conv_3 / conv_5 on the cell
+ * grid: pooled output only, which = 2), pool_3 / pool_5 (the separate pooling of the dense crop batch), cells_to_keras
+ * or crnn_to_keras, stn_conv_1, stn_conv_2, stn_dense_1 (input viewed as M x 1 x 1 x 11200), stn_dense_2,
+ * stn_sample.theta (no launch: theta as the sampler reads it), stn_sample, fc_9, lstm_10_xproj, lstm_10, lstm_11_xproj,
+ * lstm_11 (input xp = [M][50][1][1024]; output [M][50][1][forward | backward], the backward half in processing order),
+ * fc_12 and ctc (fc_12's logits in; the probabilities M x 1 x 48 x C out, when kocr_crnn_forward is given them).
+ * Tensors in the cell grid (KOCR_CELLS) are recorded one crop per image: the crop's whole cell, H x cellW x C, zero
+ * gutters included, with that cell's max-|x| slot. */
+int kocr_crnn_set_taps(kocr_ctx* ctx, int n, const char* const* names);
+
 /* ---- detection.getBoxes (detection.py:207-287) ---------------------------------------- */
 /* heat: N x h x w x 2 float32.  Thresholds as Detector.detect's keyword arguments
  * (detection.py:748-751).  boxes: N x cap x 4 x 2 float32, corner order and x2 scaling as the

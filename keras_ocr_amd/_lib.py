@@ -68,6 +68,7 @@ def load_library():
         "kocr_craft_tap_count": (ci, [vp]),
         "kocr_craft_tap_info": (ci, [vp, ci, ctypes.c_char_p, ctypes.c_char_p, vp]),
         "kocr_craft_get_tap": (ci, [vp, ctypes.c_char_p, ci, vp, vp]),
+        "kocr_crnn_set_taps": (ci, [vp, ci, ctypes.POINTER(ctypes.c_char_p)]),
         "kocr_crnn_forward": (ci, [vp, vp, ci, vp, vp, ci]),
         "kocr_crnn_classes": (ci, [vp]),
         "kocr_crnn_label_width": (ci, [vp]),
@@ -209,12 +210,24 @@ class Context:
         self._check(self._lib.kocr_craft_forward(self._h, _ptr(d_img), int(dtype), n, h, w, _ptr(d_heat),
                                                  int(micro_batch), 1))
 
+    def _set_taps(self, fn, names):
+        names = [n.encode() for n in names]
+        arr = (ctypes.c_char_p * max(1, len(names)))(*names)
+        self._check(fn(self._h, len(names), arr))
+
     def craft_set_taps(self, names=("*",)):
         """Record the named launches of every following craft_forward (include/kocr.h: kocr_craft_set_taps); "*" = all,
         an empty list turns taps off."""
-        names = [n.encode() for n in names]
-        arr = (ctypes.c_char_p * max(1, len(names)))(*names)
-        self._check(self._lib.kocr_craft_set_taps(self._h, len(names), arr))
+        self._set_taps(self._lib.kocr_craft_set_taps, names)
+
+    def crnn_set_taps(self, names=("*",)):
+        """Record the named launches of every following crnn_forward (include/kocr.h: kocr_crnn_set_taps); "*" = all,
+        an empty list turns taps off.  Replaces detector taps: one network is recorded at a time."""
+        self._set_taps(self._lib.kocr_crnn_set_taps, names)
+
+    def crnn_taps(self):
+        """What the last crnn_forward recorded: as craft_taps (cell-grid tensors: one whole cell per crop)."""
+        return self.craft_taps()
 
     def craft_taps(self):
         """What the last craft_forward recorded, in launch order: {name: {"kernel": profiler rows '+'-joined,

@@ -1,6 +1,7 @@
 // api.cpp — the extern "C" surface declared in include/kocr.h (context, memory, profiler,
 // and the entry points that wrap the graphs).  No torch types: plain pointers and sizes.
 #include "abi.h"
+#include "taps.h"
 #include <cmath>
 #include <algorithm>
 #include <mutex>
@@ -302,15 +303,15 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
   const size_t out_img = (size_t)(H / 2) * (W / 2) * 2 * sizeof(float);
   Staging st{ctx, ctx->ws, "kocr_craft_forward", on_device != 0};
   KOCR_TRY(st.reserve(craft_workspace_bytes(mb, H, W), {in_img * mb, out_img * mb}));
-  KOCR_TRY(craft_taps_begin(ctx, N));
+  KOCR_TRY(taps_begin(ctx, TAPS_CRAFT, N));
   struct TapsEnd {  // also on an error return: no later launch records into this call's taps
     kocr_ctx* c;
-    ~TapsEnd() { craft_taps_batch(c, -1); }
+    ~TapsEnd() { taps_batch(c, TAPS_CRAFT, -1, 0); }
   } taps_end{ctx};
   for (int s = 0; s < N; s += mb) {
     const int nb = std::min(mb, N - s);
     ctx->ws_reset();
-    craft_taps_batch(ctx, s);
+    taps_batch(ctx, TAPS_CRAFT, s, nb);
     const void* d_in;
     float* d_out;
     float* h_out = (float*)((char*)heat + (size_t)s * out_img);
@@ -346,7 +347,13 @@ int kocr_crnn_forward(kocr_ctx* ctx, const float* crops, int M, int32_t* labels,
   const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
   Staging st{ctx, ctx->ws, "kocr_crnn_forward", on_device != 0};
   KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0}));
+  KOCR_TRY(taps_begin(ctx, TAPS_CRNN, M));
+  struct TapsEnd {  // also on an error return: no later launch records into this call's taps
+    kocr_ctx* c;
+    ~TapsEnd() { taps_batch(c, TAPS_CRNN, -1, 0); }
+  } taps_end{ctx};
   return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    taps_batch(ctx, TAPS_CRNN, (int)s, nb);
     const float* d_c;
     int32_t* d_l;
     float* d_p = nullptr;

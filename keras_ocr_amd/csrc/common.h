@@ -126,7 +126,7 @@ struct Arena {
 
 struct CraftNet;
 struct CrnnNet;
-struct CraftTaps;
+struct Taps;
 
 struct kocr_ctx {
   int device = 0;
@@ -190,9 +190,10 @@ struct kocr_ctx {
 
   CraftNet* craft = nullptr;
   CrnnNet* crnn = nullptr;
-  // kocr_craft_set_taps (craft.cpp): the detector tensors recorded during kocr_craft_forward; nullptr = no taps.  While a
-  // tapped launch runs, tap_rows collects the profiler row names of what it launched (ProfScope), i.e. its kernel family.
-  CraftTaps* taps = nullptr;
+  // kocr_craft_set_taps / kocr_crnn_set_taps (taps.h): the tensors recorded during kocr_craft_forward or kocr_crnn_forward;
+  // nullptr = no taps.  While a tapped launch runs, tap_rows collects the profiler row names of what it launched
+  // (ProfScope), i.e. its kernel family.
+  Taps* taps = nullptr;
   std::vector<std::string>* tap_rows = nullptr;
 
   // the device-resident results of the last successful kocr_pipeline call (kocr_pipeline_device_results): boxes in the pl
@@ -389,8 +390,7 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
 int craft_forward(kocr_ctx* ctx, const void* d_img, int dtype, int N, int H, int W, float* d_heat);
 size_t craft_workspace_bytes(int N, int H, int W);
 void craft_free(kocr_ctx* ctx);
-int craft_taps_begin(kocr_ctx* ctx, int N);  // kocr_craft_forward with taps on: restart the record for N images
-void craft_taps_batch(kocr_ctx* ctx, int n0); // ... the next micro-batch starts at image n0 (-1: the call is over)
+void taps_free(kocr_ctx* ctx);  // taps.cpp
 
 // crnn.cpp
 // the recogniser's geometry: crops of CRNN_CROP_H x CRNN_CROP_W, CRNN_STEPS time steps of CRNN_FEAT features (the backbone's

@@ -14,6 +14,7 @@
 // resize(conv1x1_y(y)) + conv1x1_skip(skip) (up_conv, kocr_set_schedule / KOCR_UPFOLD); the up-sampled halves of cat2..4 and s5 are then
 // never written.
 #include "common.h"
+#include "taps.h"
 #include <algorithm>
 #include <cmath>
 #include <thread>
@@ -227,176 +228,10 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
   return KOCR_OK;
 }
 
-// ---- taps (kocr_craft_set_taps): named detector tensors copied to host memory during the forward -----------------
-// A tapped launch enqueues, on ctx->stream, a device-to-host copy of the input view it reads and of its slots just
-// before it, and of what it wrote (full and / or pooled output, with their slots) just after it -- LivePool reuses every
-// buffer, so nothing can be read back later.  Nothing else changes: no kernel, no launch order, no buffer.
-struct CraftTaps {
-  struct Part {
-    int N = 0, H = 0, W = 0, C = 0;  // N = 0: not recorded
-    std::vector<float> data;          // [N][H][W][C] of the whole call (every micro-batch)
-    std::vector<float> amax;          // [N] slot values as floats, -1 = the tensor had no slots
-  };
-  struct Tap {
-    std::string name;
-    std::vector<std::string> rows;  // profiler rows of the launch (ProfScope)
-    Part part[3];                   // input, full output, pooled output
-  };
-  bool all = false;
-  std::vector<std::string> sel;
-  std::vector<Tap> rec;  // launch order; reserved up front so that pointers into it stay valid during the call
-  int N = 0, n0 = -1;    // images of the kocr_craft_forward call, first image of its current micro-batch (-1: none running)
-  Tap* find(const std::string& nm) {
-    for (Tap& t : rec)
-      if (t.name == nm) return &t;
-    return nullptr;
-  }
-};
-
-namespace {
-
-int tap_copy(kocr_ctx* ctx, CraftTaps::Part& pt, const Tensor& t) {
-  CraftTaps* tp = ctx->taps;
-  if (!pt.N) {
-    pt.N = tp->N;
-    pt.H = t.H;
-    pt.W = t.W;
-    pt.C = t.C;
-    pt.data.assign((size_t)pt.N * t.H * t.W * t.C, 0.f);
-    pt.amax.assign(pt.N, -1.f);
-  }
-  if (pt.H != t.H || pt.W != t.W || pt.C != t.C || tp->n0 + t.N > pt.N)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_forward: tap shape changed between micro-batches");
-  float* dst = pt.data.data() + (size_t)tp->n0 * t.H * t.W * t.C;
-  const size_t rows = t.pixels(), row = (size_t)t.C * sizeof(float);
-  if (t.cs == t.C && t.co == 0)
-    KOCR_HIP(ctx, hipMemcpyAsync(dst, t.p, rows * row, hipMemcpyDeviceToHost, ctx->stream));
-  else  // a channel slice of a wider buffer: the logical N x H x W x C tensor
-    KOCR_HIP(ctx, hipMemcpy2DAsync(dst, row, t.p + t.co, (size_t)t.cs * sizeof(float), row, rows, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-  if (t.amax)  // non-negative floats as their bits
-    KOCR_HIP(ctx, hipMemcpyAsync(pt.amax.data() + tp->n0, t.amax, (size_t)t.N * sizeof(unsigned), hipMemcpyDeviceToHost,
-                                 ctx->stream));
-  return KOCR_OK;
-}
-
-// before the launch of `name`: nullptr if it is not tapped, else its record, the input copy enqueued
-int tap_begin(kocr_ctx* ctx, const std::string& name, const Tensor* in, CraftTaps::Tap** out) {
-  *out = nullptr;
-  CraftTaps* tp = ctx->taps;
-  if (!tp || tp->n0 < 0 || !(tp->all || std::find(tp->sel.begin(), tp->sel.end(), name) != tp->sel.end())) return KOCR_OK;
-  CraftTaps::Tap* t = tp->find(name);
-  if (!t) {
-    if (tp->rec.size() == tp->rec.capacity()) KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_craft_forward: too many taps");
-    tp->rec.emplace_back();
-    t = &tp->rec.back();
-    t->name = name;
-  }
-  if (in && in->p) KOCR_TRY(tap_copy(ctx, t->part[0], *in));
-  t->rows.clear();
-  ctx->tap_rows = &t->rows;
-  *out = t;
-  return KOCR_OK;
-}
-
-// after it: what it wrote
-int tap_end(kocr_ctx* ctx, CraftTaps::Tap* t, const Tensor* full, const Tensor* pool) {
-  if (!t) return KOCR_OK;
-  ctx->tap_rows = nullptr;
-  if (full) KOCR_TRY(tap_copy(ctx, t->part[1], *full));
-  if (pool) KOCR_TRY(tap_copy(ctx, t->part[2], *pool));
-  return KOCR_OK;
-}
-
-}  // namespace
-
-int craft_taps_begin(kocr_ctx* ctx, int N) {
-  ctx->tap_rows = nullptr;
-  if (!ctx->taps) return KOCR_OK;
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // no copy of the previous call is still in flight
-  ctx->taps->rec.clear();
-  ctx->taps->rec.reserve(64);
-  ctx->taps->N = N;
-  ctx->taps->n0 = -1;
-  return KOCR_OK;
-}
-
-void craft_taps_batch(kocr_ctx* ctx, int n0) {
-  ctx->tap_rows = nullptr;
-  if (ctx->taps) ctx->taps->n0 = n0;
-}
-
-extern "C" {
-
-int kocr_craft_set_taps(kocr_ctx* ctx, int n, const char* const* names) {
-  if (!ctx || n < 0 || (n > 0 && !names)) return KOCR_EINVAL;
-  ctx->tap_rows = nullptr;
-  if (ctx->taps) {
-    KOCR_HIP(ctx, hipSetDevice(ctx->device));
-    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    delete ctx->taps;
-    ctx->taps = nullptr;
-  }
-  if (n == 0) return KOCR_OK;
-  CraftTaps* tp = new CraftTaps();
-  for (int i = 0; i < n; ++i) {
-    if (!names[i]) {
-      delete tp;
-      KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_set_taps: null name");
-    }
-    if (!strcmp(names[i], "*")) tp->all = true;
-    tp->sel.emplace_back(names[i]);
-  }
-  ctx->taps = tp;
-  return KOCR_OK;
-}
-
-int kocr_craft_tap_count(kocr_ctx* ctx) {
-  if (!ctx) return KOCR_EINVAL;
-  return ctx->taps ? (int)ctx->taps->rec.size() : 0;
-}
-
-int kocr_craft_tap_info(kocr_ctx* ctx, int i, char* name, char* kernel, int32_t* dims) {
-  if (!ctx) return KOCR_EINVAL;
-  if (!ctx->taps || i < 0 || i >= (int)ctx->taps->rec.size()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_tap_info: no such tap");
-  const CraftTaps::Tap& t = ctx->taps->rec[i];
-  if (name) snprintf(name, 64, "%s", t.name.c_str());
-  if (kernel) {
-    std::string k;
-    for (const std::string& r : t.rows) k += (k.empty() ? "" : "+") + r;
-    snprintf(kernel, 256, "%s", k.c_str());
-  }
-  if (dims)
-    for (int p = 0; p < 3; ++p) {
-      const CraftTaps::Part& pt = t.part[p];
-      dims[p * 4 + 0] = pt.N;
-      dims[p * 4 + 1] = pt.H;
-      dims[p * 4 + 2] = pt.W;
-      dims[p * 4 + 3] = pt.C;
-    }
-  return KOCR_OK;
-}
-
-int kocr_craft_get_tap(kocr_ctx* ctx, const char* name, int which, float* dst, float* amax_dst) {
-  if (!ctx || !name || which < 0 || which > 2) return KOCR_EINVAL;
-  CraftTaps::Tap* t = ctx->taps ? ctx->taps->find(name) : nullptr;
-  if (!t || !t->part[which].N) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_craft_get_tap: nothing recorded for ") + name);
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const CraftTaps::Part& pt = t->part[which];
-  if (dst) memcpy(dst, pt.data.data(), pt.data.size() * sizeof(float));
-  if (amax_dst) memcpy(amax_dst, pt.amax.data(), pt.amax.size() * sizeof(float));
-  return KOCR_OK;
-}
-
-}  // extern "C"
-
 void craft_free(kocr_ctx* ctx) {
   delete ctx->craft;
   ctx->craft = nullptr;
-  delete ctx->taps;
-  ctx->taps = nullptr;
-  ctx->tap_rows = nullptr;
+  taps_free(ctx);
 }
 
 namespace {
@@ -525,14 +360,7 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
   const float* lut = DRY ? nullptr : net->d_lut;
   // a launch with its taps (kocr_craft_set_taps): `in` as read, then `full` / `pool` as written; no taps -> the launch alone
   auto tapped = [&](const std::string& name, const Tensor* in, const Tensor* full, const Tensor* pool, auto&& launch) -> int {
-    struct RowsOff {  // the launch's row collection ends with it, also when it fails
-      kocr_ctx* c;
-      ~RowsOff() { c->tap_rows = nullptr; }
-    } rows_off{ctx};
-    CraftTaps::Tap* t = nullptr;
-    KOCR_TRY(tap_begin(ctx, name, in, &t));
-    KOCR_TRY(launch());
-    return tap_end(ctx, t, full, pool);
+    return ::tapped(ctx, name, in, full, pool, launch);
   };
   // The 1x1 layers (slice5.2, the decoder's upconvN.conv.0 and their #y columns) on conv_ds whenever it takes the tensor:
   // launch_conv's small-GEMM cut-off (dsplit_applicable) counts the pixels of the WHOLE batch, so an image whose level

@@ -18,6 +18,7 @@
 //     Add (recognition.py:305) is folded into the next projection by stacking its kernel over
 //     the [forward | backward] channel halves; Concatenate (:319) is the same buffer.
 #include "common.h"
+#include "taps.h"
 #include <algorithm>
 #include <cmath>
 
@@ -254,9 +255,19 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
     v.co = 0;
     return v;
   };
+  // every launch with its taps (kocr_crnn_set_taps, taps.h); with taps off the launch alone
   auto conv = [&](const char* name, const Tensor& in, const Tensor& out) -> int {
-    return launch_conv(ctx, net->L[name], in, nullptr, nullptr, out);
+    return tapped(ctx, name, &in, &out, nullptr, [&]() { return launch_conv(ctx, net->L[name], in, nullptr, nullptr, out); });
   };
+  auto pool = [&](const char* name, const Tensor& in, const Tensor& out) -> int {
+    return tapped(ctx, name, &in, &out, nullptr, [&]() { return launch_maxpool2x2(ctx, in, out, /*row_off=*/1); });
+  };
+  Tensor crops;  // the crop batch as a tap view [M][31][200][1]
+  crops.N = M;
+  crops.H = HC;
+  crops.W = WC;
+  crops.C = crops.cs = 1;
+  crops.p = const_cast<float*>(d_crops);
   Tensor x0, c1, c2, c3, p3, c4, c5, p5, c6, c7n, c7, s1, s2, d1, th, st, f9, xp, r1, r2, lg;
   // Round 5: in the fp16 arithmetic the conv stack runs on a CELL GRID (Tensor::cellW): the crops side by side, CN per image,
   // with zero gutters, so that conv_2 ... conv_7 take the vertical-reuse F(4,3) kernel (conv_w43vh_kernel MODE 2) with both
@@ -282,24 +293,29 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
       return KOCR_OK;
     };
     KOCR_TRY(mkc(HC + 1, CELL_W, WC, 64, true, &c1));
-    KOCR_TRY(launch_crnn_conv1_cells(ctx, net->L["conv_1"], d_crops, M, HC, WC, c1));
+    KOCR_TRY(tapped(ctx, "conv_1", &crops, &c1, nullptr,
+                    [&]() { return launch_crnn_conv1_cells(ctx, net->L["conv_1"], d_crops, M, HC, WC, c1); }));
     KOCR_TRY(mkc(HC + 1, CELL_W, WC, 128, true, &c2));
     KOCR_TRY(conv("conv_2", c1, c2));
     KOCR_TRY(mkc(HC + 1, CELL_W, WC, 256, false, &c3));  // conv_3's full-resolution output is only ever pooled
     KOCR_TRY(mkc(16, CELL_W / 2, WC / 2, 256, true, &p3));
-    KOCR_TRY(launch_conv_pool(ctx, net->L["conv_3"], c2, nullptr, nullptr, c3, &p3, /*need_full=*/false));  // ReLU, bn_3, pool
+    KOCR_TRY(tapped(ctx, "conv_3", &c2, nullptr, &p3, [&]() {  // ReLU, bn_3, pool
+      return launch_conv_pool(ctx, net->L["conv_3"], c2, nullptr, nullptr, c3, &p3, /*need_full=*/false);
+    }));
     KOCR_TRY(mkc(16, CELL_W / 2, WC / 2, 256, true, &c4));
     KOCR_TRY(conv("conv_4", p3, c4));
     KOCR_TRY(mkc(16, CELL_W / 2, WC / 2, 512, false, &c5));
     KOCR_TRY(mkc(8, CELL_W / 4, WC / 4, 512, true, &p5));
-    KOCR_TRY(launch_conv_pool(ctx, net->L["conv_5"], c4, nullptr, nullptr, c5, &p5, /*need_full=*/false));
+    KOCR_TRY(tapped(ctx, "conv_5", &c4, nullptr, &p5, [&]() {
+      return launch_conv_pool(ctx, net->L["conv_5"], c4, nullptr, nullptr, c5, &p5, /*need_full=*/false);
+    }));
     KOCR_TRY(mkc(8, CELL_W / 4, WC / 4, 512, true, &c6));
     KOCR_TRY(conv("conv_6", p5, c6));
     KOCR_TRY(mkc(8, CELL_W / 4, WC / 4, 512, true, &c7n));
     c7n.amax = nullptr;  // nothing downstream reads its scale
     KOCR_TRY(conv("conv_7", c6, c7n));
     KOCR_TRY(mk(M, WC / 4, HC / 4, 512, &c7));
-    KOCR_TRY(launch_crnn_cells_to_keras(ctx, c7n, c7));
+    KOCR_TRY(tapped(ctx, "cells_to_keras", &c7n, &c7, nullptr, [&]() { return launch_crnn_cells_to_keras(ctx, c7n, c7); }));
   } else {
   // conv stack in the crop's natural orientation (see the header): [M,31,200,C]
   x0.N = M;
@@ -319,7 +335,7 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   KOCR_TRY(conv("conv_3", c2, c3));  // ReLU then bn_3
   KOCR_TRY(mk(M, HC / 2, WC / 2, 256, &p3));
   p3.amax = ctx->amax_slots(M);
-  KOCR_TRY(launch_maxpool2x2(ctx, c3, p3, /*row_off=*/1));
+  KOCR_TRY(pool("pool_3", c3, p3));
   KOCR_TRY(mk(M, HC / 2, WC / 2, 256, &c4));
   c4.amax = ctx->amax_slots(M);
   KOCR_TRY(conv("conv_4", p3, c4));
@@ -337,7 +353,7 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   KOCR_TRY(mk(M, HC / 4, W6, 512, &p5));
   p5.Wv = WC / 4;
   if (pad52) p5.amax = ctx->amax_slots(M);
-  KOCR_TRY(launch_maxpool2x2(ctx, c5, p5, /*row_off=*/1));
+  KOCR_TRY(pool("pool_5", c5, p5));
   KOCR_TRY(mk(M, HC / 4, W6, 512, &c6));
   c6.Wv = WC / 4;
   if (pad52) c6.amax = ctx->amax_slots(M);
@@ -347,7 +363,7 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   KOCR_TRY(conv("conv_7", c6, c7n));
   // back to the Keras layout (M, 50, 7, 512) for the STN and everything after it
   KOCR_TRY(mk(M, WC / 4, HC / 4, 512, &c7));
-  KOCR_TRY(launch_crnn_to_keras(ctx, c7n, c7));
+  KOCR_TRY(tapped(ctx, "crnn_to_keras", &c7n, &c7, nullptr, [&]() { return launch_crnn_to_keras(ctx, c7n, c7); }));
   }
   // STN (recognition.py:268-281)
   if (!net->stn) {
@@ -363,15 +379,17 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
     const ConvLayer& Ld = net->L["stn_dense_1"];
     const bool no_sk = !ctx->sw.dense_splitk;
     float* part = no_sk ? nullptr : (float*)ctx->ws_alloc(dense_splitk_workspace(M, 11200));
+    const Tensor flat = view(s2, M, 1, 1, 11200);
     if (part && Ld.Cout == 64 && Ld.Cin == 11200)
-      KOCR_TRY(launch_dense_splitk(ctx, Ld, s2.p, d1.p, part, M));
+      KOCR_TRY(tapped(ctx, "stn_dense_1", &flat, &d1, nullptr, [&]() { return launch_dense_splitk(ctx, Ld, s2.p, d1.p, part, M); }));
     else
       KOCR_TRY(conv("stn_dense_1", view(s2, M, 1, 1, 11200), d1));
   }
   KOCR_TRY(mk(M, 1, 1, 6, &th));
   KOCR_TRY(conv("stn_dense_2", d1, th));
   KOCR_TRY(mk(M, WC / 4, HC / 4, 512, &st));
-  KOCR_TRY(launch_stn_sample(ctx, c7, th.p, st));
+  KOCR_TRY(tapped(ctx, "stn_sample.theta", &th, nullptr, nullptr, []() { return KOCR_OK; }));  // theta as the sampler reads it
+  KOCR_TRY(tapped(ctx, "stn_sample", &c7, &st, nullptr, [&]() { return launch_stn_sample(ctx, c7, th.p, st); }));
   }
   // Reshape + fc_9 (recognition.py:282-290)
   KOCR_TRY(mk(M, T, 1, UNITS, &f9));
@@ -382,9 +400,9 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   KOCR_TRY(mk(M, T, 1, 2 * UNITS, &r2));
   if (stop == CRNN_FEATURES) r2.p = d_feats;  // the backbone's output (recognition.py:319-320) goes straight to the caller
   KOCR_TRY(conv("lstm_10_xproj", f9, xp));
-  KOCR_TRY(launch_lstm(ctx, xp.p, net->U[0], net->U[1], r1.p, M, T));
+  KOCR_TRY(tapped(ctx, "lstm_10", &xp, &r1, nullptr, [&]() { return launch_lstm(ctx, xp.p, net->U[0], net->U[1], r1.p, M, T); }));
   KOCR_TRY(conv("lstm_11_xproj", r1, xp));
-  KOCR_TRY(launch_lstm(ctx, xp.p, net->U[2], net->U[3], r2.p, M, T));
+  KOCR_TRY(tapped(ctx, "lstm_11", &xp, &r2, nullptr, [&]() { return launch_lstm(ctx, xp.p, net->U[2], net->U[3], r2.p, M, T); }));
   if (stop == CRNN_FEATURES) return KOCR_OK;
   // fc_12 + softmax + decode (recognition.py:321-328, 169-184)
   KOCR_TRY(mk(M, T, 1, net->n_classes, &lg));
@@ -393,7 +411,14 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
     *d_logits = lg.p;
     return KOCR_OK;
   }
-  KOCR_TRY(launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs));
+  Tensor probs;  // tap view [M][1][LW][C] (not recorded without d_probs)
+  probs.N = M;
+  probs.H = 1;
+  probs.W = T - net->discard;
+  probs.C = probs.cs = net->n_classes;
+  probs.p = d_probs;
+  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr,
+                  [&]() { return launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs); }));
   return KOCR_OK;
 }
 

@@ -20,10 +20,9 @@ import torch
 import torch.nn.functional as F
 
 from tests import synth
+from tests.layer_bounds import family as _family, kernel_row as _kernel_row, pool2 as _pool2
 
 pytestmark = pytest.mark.gpu
-
-WINDOW = 3  # T|x|: +-3 columns of a Winograd tile
 
 
 @pytest.fixture(scope="module")
@@ -38,28 +37,6 @@ def _image(case):
         return synth.text_page(375, 500, 12, seed=91)[None]
     h, w = {"1x64x512_f32": (64, 512), "1x50x70_f32": (50, 70)}[case]
     return np.random.default_rng(h * w).standard_normal((1, h, w, 3)).astype(np.float32)
-
-
-def _pool2(t):
-    """floor 2x2 max pooling of an NHWC array (keras 'valid')"""
-    return F.max_pool2d(torch.from_numpy(np.ascontiguousarray(t)).permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1).numpy()
-
-
-def _kernel_row(kernel):
-    rows = [r for r in kernel.split("+") if r not in ("absmax", "maxpool2x2")]
-    return rows[0] if rows else kernel
-
-
-def _family(row, weight_shape):
-    """(k, window) of the stated bound of the kernel that wrote a convolution (profiler row)"""
-    if row.startswith(("conv_w4", "conv_wh_", "conv_ws_")):
-        return 5e-6, WINDOW
-    if row.startswith(("conv_dh_", "conv_ds_", "conv_hh_", "conv_hs_", "conv_k5")):
-        return 1.5e-6, 0
-    if row.startswith("conv_mfma"):
-        cout, cin, kh, kw = weight_shape
-        return cin * kh * kw * 2.0 ** -24, 0
-    raise AssertionError(f"no stated bound for kernel row {row}")
 
 
 def _weight_shape(w, name):

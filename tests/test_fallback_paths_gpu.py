@@ -9,6 +9,8 @@ when a context is created): the fp64-bounded convolution tests and the CRAFT hea
   KOCR_LINFOLD=0 KOCR_UPFOLD=0                 -> the layer-by-layer CRAFT schedule (slice5.1, slice5.2, resize + concat)
   KOCR_K5=0      no 5x5 / 16-cout kernel    -> the recogniser's stn_conv_1 on the fp32 MFMA kernel
   KOCR_HS16=0    no 16-wide product tile    -> conv_cls.4 on conv_hs_kernel's 32-column tile
+  KOCR_LSTM16=0  no 16-crop LSTM kernel     -> the recurrences on lstm_kernel (32 crops per workgroup, U from L2)
+  KOCR_DENSE_SPLITK=0 no split-K dense      -> the recogniser's stn_dense_1 through launch_conv
   KOCR_SPLIT=bf16  the exact bf16x3 split everywhere (round 3's default arithmetic)
   KOCR_CELLS=0   no cell grid               -> the recogniser's conv stack on round 4's dense crop batch (flattened fp16 tiles,
                                                conv_6 / conv_7 through the 52-wide layout, separate pooling kernels)
@@ -38,7 +40,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = [
     {"KOCR_W43": "0"},                                                            # (implies no cell grid: the recogniser on round 4's dense crop batch)
     {"KOCR_W43R": "0", "KOCR_K5": "0", "KOCR_HS16": "0", "KOCR_W43DILH": "0",     # 64-cout rows / stn_conv_1 / conv_cls.4 / the dilated composite
-     "KOCR_LINFOLD": "0", "KOCR_UPFOLD": "0"},                                    # ... / the layer-by-layer decoder schedule
+     "KOCR_LINFOLD": "0", "KOCR_UPFOLD": "0",                                     # ... / the layer-by-layer decoder schedule
+     "KOCR_LSTM16": "0", "KOCR_DENSE_SPLITK": "0"},                               # ... / the 32-crop LSTM kernel / stn_dense_1 on launch_conv
     {"KOCR_HSPLIT": "0", "KOCR_FIRST": "0", "KOCR_W43V": "0"},                    # the <= 32-cout layers / the first layer / the wide layers
     {"KOCR_SPLIT": "bf16"},
     {"KOCR_CELLS": "0", "KOCR_W43RAG": "0"},                                      # the recogniser's crop batch / ragged detector pages
