@@ -347,6 +347,41 @@ int kocr_get_schedule(kocr_ctx* ctx, int* fold_linear_chain, int* fold_upsample)
 int kocr_set_min_area_rect(kocr_ctx* ctx, int rule);
 int kocr_get_min_area_rect(const kocr_ctx* ctx);
 
+/* ---- scores: how sure the two networks were ("Scores") ----------------------------------------------
+ * The reference returns none; they are the numbers it computes on the way and drops:
+ *   detection score of a box   the maximum of the text map over the pixels of the box's connected component, the number
+ *                              detection.py:240 compares with detection_threshold (float32, no arithmetic);
+ *   word log-probability       -ctc_batch_cost (the rule of kocr_ctc_batch_cost: epsilon, renormalisation) of the crop's own
+ *                              greedy decode over all kocr_crnn_label_width() frames of fc_12's softmax: the log of the summed
+ *                              probability of every alignment that collapses to the returned text; bit for bit
+ *                              -kocr_crnn_ctc_loss of the crop with its decoded labels.  An empty decode: the all-blank path;
+ *   character scores           for the k-th decoded label the maximum, over the frames of the run of arg-maxes that emitted it,
+ *                              of that label's probability -- each value bit for bit an entry of kocr_crnn_forward's probs;
+ *                              0 in the -1 padded tail.
+ * kocr_set_scores(ctx, 1) (default 0; kocr_get_scores returns the switch) makes kocr_get_boxes / kocr_detect leave the
+ * detection scores, kocr_recognize_boxes the recogniser's two, kocr_pipeline all three resident in HBM next to their
+ * results: the recogniser's decode then runs as ONE launch that also produces the scores (profiler row ctc_scores instead of
+ * ctc_greedy; the decoded labels never visit the host); the label rows, boxes and counts are the same bits either way.  With
+ * the switch off the calls launch what they always launched.
+ * kocr_detection_scores: scores N x cap float32 (HOST; row i holds counts[i] values in box order, the rest undefined), cap >=
+ * the cap the results were produced with -- after KOCR_ECAPACITY from kocr_pipeline that is the largest count, as for
+ * kocr_pipeline_results.  kocr_recognition_scores: log_word [n_crops], char_scores [n_crops][label width] (HOST, image-major,
+ * box order as the label rows); *n_crops / *label_width (either may be NULL) receive the number of crops and the label width
+ * the rows were PRODUCED with, also when the call fails with KOCR_ECAPACITY (max_crops too small).  Both are valid until the
+ * next libkocr call on the context that processes images, and fail with KOCR_EINVAL and a message when nothing is resident
+ * (also after a failed call; kocr_get_boxes / kocr_detect returning KOCR_ECAPACITY leave nothing) or when the results were
+ * produced with the switch off. */
+int kocr_set_scores(kocr_ctx* ctx, int on);
+int kocr_get_scores(const kocr_ctx* ctx);
+int kocr_detection_scores(kocr_ctx* ctx, float* scores, int cap);
+int kocr_recognition_scores(kocr_ctx* ctx, float* log_word, float* char_scores, int max_crops, int32_t* n_crops,
+                            int32_t* label_width);
+/* kocr_crnn_forward (arguments as there; probs may be NULL) that also returns log_word [M] and char_scores
+ * [M][kocr_crnn_label_width()] (device pointers when on_device), whatever the switch says.  labels and probs are bit for bit
+ * kocr_crnn_forward's. */
+int kocr_crnn_forward_scores(kocr_ctx* ctx, const float* crops, int M, int32_t* labels, float* probs, float* log_word,
+                             float* char_scores, int on_device);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx
  * stream; kocr_profile_report fills parallel arrays (up to cap rows) with per-kernel-name

@@ -70,6 +70,11 @@ def load_library():
         "kocr_craft_get_tap": (ci, [vp, ctypes.c_char_p, ci, vp, vp]),
         "kocr_crnn_set_taps": (ci, [vp, ci, ctypes.POINTER(ctypes.c_char_p)]),
         "kocr_crnn_forward": (ci, [vp, vp, ci, vp, vp, ci]),
+        "kocr_crnn_forward_scores": (ci, [vp, vp, ci, vp, vp, vp, vp, ci]),
+        "kocr_set_scores": (ci, [vp, ci]),
+        "kocr_get_scores": (ci, [vp]),
+        "kocr_detection_scores": (ci, [vp, vp, ci]),
+        "kocr_recognition_scores": (ci, [vp, vp, vp, ci, vp, vp]),
         "kocr_crnn_classes": (ci, [vp]),
         "kocr_crnn_label_width": (ci, [vp]),
         "kocr_crnn_set_rnn_steps_to_discard": (ci, [vp, ci]),
@@ -274,6 +279,69 @@ class Context:
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(x), m, _ptr(labels), _ptr(probs), 0))
         return (labels, probs) if return_probs else labels
 
+    def crnn_forward_scores(self, crops, return_probs=False):
+        """crnn_forward with the recogniser's scores (kocr_crnn_forward_scores, one launch for decode and scores): returns
+        labels (M,48) int32, log_word (M,) float32 -- the log-probability of every alignment of the crop's own decode --,
+        char_scores (M,48) float32 -- per decoded label the peak probability of its run, 0 behind the decode -- [, probs]."""
+        x = self._crops(crops)
+        m = x.shape[0]
+        c = self.crnn_classes()
+        lw = self.crnn_label_width()
+        labels = np.full((m, lw), -1, dtype=np.int32)
+        log_word = np.zeros(m, dtype=np.float32)
+        chars = np.zeros((m, lw), dtype=np.float32)
+        probs = np.zeros((m, lw, c), dtype=np.float32) if return_probs else None
+        self._check(self._lib.kocr_crnn_forward_scores(self._h, _ptr(x), m, _ptr(labels), _ptr(probs), _ptr(log_word),
+                                                       _ptr(chars), 0))
+        return (labels, log_word, chars, probs) if return_probs else (labels, log_word, chars)
+
+    def crnn_forward_scores_device(self, d_crops, m, d_labels, d_log_word, d_chars, d_probs=None):
+        self._check(self._lib.kocr_crnn_forward_scores(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs),
+                                                       _ptr(d_log_word), _ptr(d_chars), 1))
+
+    # -- scores (include/kocr.h: "Scores") ---------------------------------------------------------------------------
+    def set_scores(self, on=True):
+        """Whether get_boxes / detect / recognize_boxes / pipeline leave their scores resident (kocr_set_scores)."""
+        self._check(self._lib.kocr_set_scores(self._h, int(bool(on))))
+
+    def get_scores(self):
+        return bool(self._check(self._lib.kocr_get_scores(self._h)))
+
+    @contextlib.contextmanager
+    def _scores_scope(self, on):
+        """The switch for one call (``return_scores=True``); falsy: the context's own setting."""
+        if not on:
+            yield
+            return
+        old = self.get_scores()
+        self.set_scores(True)
+        try:
+            yield
+        finally:
+            self.set_scores(old)
+
+    def detection_scores(self, counts, cap):
+        """The resident detection scores (kocr_detection_scores) as a per-image list of (n_i,) float32 arrays; ValueError
+        when nothing is resident or the results were produced with scores off."""
+        counts = np.asarray(counts, dtype=np.int32)
+        buf = np.zeros((len(counts), int(cap)), dtype=np.float32)
+        self._check(self._lib.kocr_detection_scores(self._h, _ptr(buf), int(cap)), value_error=True)
+        return [buf[i, :counts[i]].copy() for i in range(len(counts))]
+
+    def recognition_scores(self):
+        """The resident recogniser scores (kocr_recognition_scores): log_word (M,) and char_scores (M, label width the rows
+        were produced with) float32; ValueError as detection_scores."""
+        m, lw = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self._lib.kocr_recognition_scores(self._h, None, None, 0, ctypes.byref(m), ctypes.byref(lw))
+        if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
+            self._check(rc, value_error=True)
+        log_word = np.zeros(m.value, dtype=np.float32)
+        chars = np.zeros((m.value, lw.value), dtype=np.float32)
+        if m.value:
+            self._check(self._lib.kocr_recognition_scores(self._h, _ptr(log_word), _ptr(chars), m.value, None, None),
+                        value_error=True)
+        return log_word, chars
+
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
 
@@ -332,25 +400,27 @@ class Context:
 
     # -- detection.getBoxes ----------------------------------------------------------------
     def get_boxes(self, heat, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4,
-                  size_threshold=10, cap=None, min_area_rect=None):
+                  size_threshold=10, cap=None, min_area_rect=None, return_scores=False):
         """heat: (N,h,w,2) float32 host array -> list of (n_i,4,2) float32 arrays
         (``np.array([])`` for an image without boxes, detection.py:286).  ``min_area_rect``: ``"exact"`` /
-        ``"opencv"`` for this call only, ``None`` = the context's rule (``set_min_area_rect``)."""
+        ``"opencv"`` for this call only, ``None`` = the context's rule (``set_min_area_rect``).  ``return_scores``:
+        ``(boxes, scores)``, scores a list of (n_i,) float32 arrays -- each box's detection score, the maximum of the text map
+        over its component."""
         y = np.ascontiguousarray(heat, dtype=np.float32)
         if y.ndim != 4 or y.shape[3] != 2:
             raise ValueError("heat must have shape (N,h,w,2)")
-        with self._min_area_rect_scope(min_area_rect):
-            return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap)
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores):
+            return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores)
 
-    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap):
+    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores=False):
         n, h, w, _ = y.shape
         return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_get_boxes(
             self._h, _ptr(y), n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
-            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0))
+            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0), return_scores)
 
-    def _boxes_grow_cap(self, n, cap, call):
+    def _boxes_grow_cap(self, n, cap, call, return_scores=False):
         """call(boxes, counts, cap) -> rc into (n, cap) buffers, repeated with the true maximum on KOCR_ECAPACITY (the counts
-        hold it); the boxes as a per-image list"""
+        hold it); the boxes as a per-image list [, the resident detection scores of the call that succeeded]"""
         cap = int(cap) if cap else 1024
         while True:
             boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
@@ -360,34 +430,45 @@ class Context:
                 cap = int(counts.max())
                 continue
             self._check(rc)
+            if return_scores:
+                return _box_lists(boxes, counts), (self.detection_scores(counts, cap) if n else [])
             return _box_lists(boxes, counts)
 
     # -- Detector.detect, device-resident heat-maps -----------------------------------------------
     def detect(self, images, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,
-               micro_batch=0, cap=None, min_area_rect=None):
+               micro_batch=0, cap=None, min_area_rect=None, return_scores=False):
         """images: (N,H,W,3) uint8 (raw RGB) or float32 (normalised).  Returns list of (n_i,4,2) boxes.
-        ``min_area_rect``: as ``get_boxes``."""
-        with self._min_area_rect_scope(min_area_rect):
+        ``min_area_rect``, ``return_scores``: as ``get_boxes``."""
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores):
             return self._detect(images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch,
-                                cap)
+                                cap, return_scores)
 
-    def _detect(self, images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap):
+    def _detect(self, images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap,
+                return_scores=False):
         x, dt = _detector_input(images)
         n, h, w, _ = x.shape
         return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_detect(
             self._h, _ptr(x), dt, n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
-            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0))
+            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), return_scores)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
-    def recognize_boxes(self, images, box_groups):
-        """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32."""
+    def recognize_boxes(self, images, box_groups, return_scores=False):
+        """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32 [, log_word (M,), char_scores
+        (M,48) float32 as ``crnn_forward_scores``]."""
         x = np.ascontiguousarray(images, dtype=np.uint8)
         n, h, w, _ = x.shape
         counts, flat = _flatten_boxes(box_groups)
-        labels = np.full((int(counts.sum()), self.crnn_label_width()), -1, dtype=np.int32)
-        if len(labels):
+        lw = self.crnn_label_width()
+        labels = np.full((int(counts.sum()), lw), -1, dtype=np.int32)
+        if not return_scores:
+            if len(labels):
+                self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(labels), 0))
+            return labels
+        if not len(labels):
+            return labels, np.zeros(0, np.float32), np.zeros((0, lw), np.float32)
+        with self._scores_scope(True):
             self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(labels), 0))
-        return labels
+            return (labels,) + self.recognition_scores()
 
     # -- crops --------------------------------------------------------------------------------
     def warp_crops(self, images, box_groups, target_height=31, target_width=200):
@@ -465,15 +546,16 @@ class Context:
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
-                 min_area_rect=None):
+                 min_area_rect=None, return_scores=False):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns
-        (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``."""
-        with self._min_area_rect_scope(min_area_rect):
+        (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``.
+        ``return_scores``: a third element ``(detection list[(n_i,) f32], log_word (M,) f32, char_scores (M,48) f32)``."""
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores):
             return self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                                  size_threshold, micro_batch, on_device, cap, max_crops)
+                                  size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
 
     def _pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                  size_threshold, micro_batch, on_device, cap, max_crops):
+                  size_threshold, micro_batch, on_device, cap, max_crops, return_scores=False):
         n = len(ptrs)
         keep = [np.ascontiguousarray(p, dtype=np.uint8) if not isinstance(p, (int, np.integer)) else p for p in ptrs]
         c_ptrs = (ctypes.c_void_p * n)(*[int(p) if isinstance(p, (int, np.integer)) else p.ctypes.data for p in keep])
@@ -499,6 +581,10 @@ class Context:
             labels = np.full((max_crops, lw), -1, dtype=np.int32)
             rc = self._lib.kocr_pipeline_results(self._h, _ptr(boxes), cap, _ptr(labels), max_crops)
         self._check(rc)
+        if return_scores:
+            scores = (self.detection_scores(counts, cap),) + self.recognition_scores() if n else (
+                [], np.zeros(0, np.float32), np.zeros((0, lw), np.float32))
+            return _box_lists(boxes, counts), labels[:int(n_crops[0])].copy(), scores
         return _box_lists(boxes, counts), labels[:int(n_crops[0])].copy()
 
     def pipeline_device_results(self):

@@ -12,6 +12,7 @@
 // ---------------------------------------------------------------------------------------
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   ctx->last_pl.valid = false;  // whoever sizes an arena is about to overwrite it (kocr_pipeline re-validates at its end)
+  ctx->last_sc.clear();        // the resident scores likewise
   if (bytes <= a.cap) return KOCR_OK;
   if (a.base) {
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -367,6 +368,47 @@ int kocr_crnn_forward(kocr_ctx* ctx, const float* crops, int M, int32_t* labels,
   });
 }
 
+// kocr_crnn_forward with the scores of include/kocr.h ("Scores"): the same batches, ctc_scores_kernel as the last launch
+int kocr_crnn_forward_scores(kocr_ctx* ctx, const float* crops, int M, int32_t* labels, float* probs, float* log_word,
+                             float* char_scores, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (M < 0 || (M > 0 && (!crops || !labels || !log_word || !char_scores)))
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_forward_scores: null buffer");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward_scores: call kocr_load_crnn first");
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = crnn_batch(M);
+  const int LW = crnn_label_width(ctx);
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
+  const size_t wb = sizeof(float), hb = LW * sizeof(float);
+  Staging st{ctx, ctx->ws, "kocr_crnn_forward_scores", on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0, wb * mb, hb * mb}));
+  KOCR_TRY(taps_begin(ctx, TAPS_CRNN, M));
+  struct TapsEnd {  // also on an error return: no later launch records into this call's taps
+    kocr_ctx* c;
+    ~TapsEnd() { taps_batch(c, TAPS_CRNN, -1, 0); }
+  } taps_end{ctx};
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    taps_batch(ctx, TAPS_CRNN, (int)s, nb);
+    const float* d_c;
+    int32_t* d_l;
+    float* d_p = nullptr;
+    CrnnScores sc{nullptr, nullptr};
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(labels + s * LW, lb * nb, d_l));
+    if (probs) KOCR_TRY(st.out(probs + (size_t)s * LW * C, pb * nb, d_p));
+    KOCR_TRY(st.out(log_word + s, wb * nb, sc.d_logw));
+    KOCR_TRY(st.out(char_scores + s * LW, hb * nb, sc.d_chars));
+    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p, CRNN_DECODE, nullptr, nullptr, &sc));
+    KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
+    if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
+    KOCR_TRY(st.back(log_word + s, sc.d_logw, wb * nb));
+    KOCR_TRY(st.back(char_scores + s * LW, sc.d_chars, hb * nb));
+    return st.finish();
+  });
+}
+
 // labels rows [s, s + nb) of a validated batch (ctc_validate) into the workspace as [nb][Lmax] | len[nb] | in_len[nb]; the
 // host staging vector is returned so that it outlives the asynchronous copy (the callers synchronise before returning)
 static int ctc_stage_labels(Staging& st, const int32_t* labels, int label_stride, const int32_t* label_lengths,
@@ -592,11 +634,13 @@ int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float 
   KOCR_TRY(st.in(heat, hb, d_heat));
   KOCR_TRY(st.out(boxes, bb, d_boxes));
   int n_empty = 0;
+  const float* d_scores = nullptr;
   const int rc = postproc_get_boxes(ctx, d_heat, N, h, w, detection_threshold, text_threshold, link_threshold,
-                                    size_threshold, d_boxes, cap, counts, &n_empty);
+                                    size_threshold, d_boxes, cap, counts, &n_empty, nullptr, &d_scores);
   if (rc != KOCR_OK) return rc;
   KOCR_TRY(st.back(boxes, d_boxes, bb));
   KOCR_TRY(st.finish());
+  ctx->keep_det_scores(d_scores, N, cap);
   if (n_empty > 0)
     KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR,
               "kocr_get_boxes: a component has no pixels left after removing text&link overlap "
@@ -851,6 +895,15 @@ int kocr_set_min_area_rect(kocr_ctx* ctx, int rule) {
 }
 
 int kocr_get_min_area_rect(const kocr_ctx* ctx) { return ctx ? ctx->min_area_rect : KOCR_EINVAL; }
+
+int kocr_set_scores(kocr_ctx* ctx, int on) {
+  if (!ctx) return KOCR_EINVAL;
+  if (on != 0 && on != 1) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_scores: on must be 0 or 1");
+  ctx->scores_on = on != 0;
+  return KOCR_OK;
+}
+
+int kocr_get_scores(const kocr_ctx* ctx) { return ctx ? (ctx->scores_on ? 1 : 0) : KOCR_EINVAL; }
 
 int kocr_profile_enable(kocr_ctx* ctx, int on) {
   if (!ctx) return KOCR_EINVAL;

@@ -207,6 +207,42 @@ struct kocr_ctx {
     bool valid = false;
   } last_pl;
 
+  // scores (kocr_set_scores; DESIGN.md section 4, "Scores"): with the switch on, kocr_get_boxes / kocr_detect /
+  // kocr_recognize_boxes / kocr_pipeline leave what they have of the three scores resident for kocr_detection_scores /
+  // kocr_recognition_scores -- detection scores in the post-processing scratch, the recogniser's beside its label rows.
+  // lw: the label width the rows were produced with.  Valid like last_pl: until the next call that sizes an arena.
+  bool scores_on = false;
+  struct LastScores {
+    const float* d_det = nullptr;  // [N][cap]
+    int N = 0, cap = 0;
+    bool det_valid = false, det_off = false;  // det_off: results were produced with the switch off
+    const float* d_logw = nullptr;   // [M]
+    const float* d_chars = nullptr;  // [M][lw]
+    int M = 0, lw = 0;
+    bool rec_valid = false, rec_off = false;
+    void clear() { det_valid = det_off = rec_valid = rec_off = false; }
+  } last_sc;
+  void invalidate_results() {
+    last_pl.valid = false;
+    last_sc.clear();
+  }
+  // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
+  void keep_det_scores(const float* d, int N, int cap) {
+    last_sc.d_det = d;
+    last_sc.N = N;
+    last_sc.cap = cap;
+    last_sc.det_valid = scores_on;
+    last_sc.det_off = !scores_on;
+  }
+  void keep_rec_scores(const float* d_logw, const float* d_chars, int M, int lw) {
+    last_sc.d_logw = d_logw;
+    last_sc.d_chars = d_chars;
+    last_sc.M = M;
+    last_sc.lw = lw;
+    last_sc.rec_valid = scores_on;
+    last_sc.rec_off = !scores_on;
+  }
+
   // developer instrumentation of the fp16x2 range assumption (kocr_range_stats_enable): off = no cost
   bool range_on = false;
   void* d_range = nullptr;
@@ -408,8 +444,14 @@ size_t crnn_workspace_bytes(int M, int n_classes);
 // (kocr_crnn_ctc_loss: *d_logits = [M][50][n_classes] in the workspace), or up to the Concatenate output (kocr_crnn_features:
 // written to d_feats [M][50][256] instead of the workspace).  The launches before the stop are the same in all three.
 enum CrnnStop { CRNN_DECODE, CRNN_LOGITS, CRNN_FEATURES };
+// sc (CRNN_DECODE only): the decode's launch also writes the word log-probabilities [M] and the character scores
+// [M][crnn_label_width()] (ctc_scores_kernel instead of ctc_kernel; the label rows and probabilities are the same bits).
+struct CrnnScores {
+  float* d_logw;
+  float* d_chars;
+};
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
-                 float* d_feats = nullptr, const float** d_logits = nullptr);
+                 float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr);
 // training_model (recognition.py:334-349): crnn_forward to the logits, then ctc_loss_kernel on fc_12's softmax of frames
 // rnn_steps_to_discard .. + input_length - 1; labels / lengths already validated (ctc_validate) and on the device
 int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
@@ -427,13 +469,15 @@ int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, 
 // dev (optional): device-side results for a caller that keeps going on the stream -- the per-image counts and the
 // totals block (totals[2] = components whose contour list is empty); with dev set, the final synchronisation that
 // fetches n_empty is skipped and the caller reads totals[2] itself.  Both pointers live until the next call.
+// d_scores: [N][cap] float32, the detection score (the text map's maximum over the component) of the box in the same slot.
 struct PPDeviceOut {
   int* d_counts = nullptr;
   int* d_totals = nullptr;
+  float* d_scores = nullptr;
 };
 int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, float det_thr,
                        float text_thr, float link_thr, int size_thr, float* d_boxes, int cap,
-                       int* h_counts, int* n_empty_out, PPDeviceOut* dev = nullptr);
+                       int* h_counts, int* n_empty_out, PPDeviceOut* dev = nullptr, const float** d_scores = nullptr);
 
 // warp.hip
 struct WarpParam {

@@ -31,6 +31,8 @@ int launch_lstm(kocr_ctx* ctx, const float* d_xp, const float* d_Uf, const float
 size_t dense_splitk_workspace(int M, int K);
 int launch_dense_splitk(kocr_ctx* ctx, const ConvLayer& L, const float* d_in, float* d_out, float* d_partial, int M);
 int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs);
+int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
+                      float* d_logw, float* d_chars);
 
 struct CrnnNet {
   std::map<std::string, ConvLayer> L;
@@ -214,9 +216,9 @@ size_t crnn_workspace_bytes(int M, int n_classes) {
 }
 
 // d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
-// `stop` / d_feats / d_logits: common.h
+// `stop` / d_feats / d_logits / sc: common.h
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
-                 const float** d_logits) {
+                 const float** d_logits, const CrnnScores* sc) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -417,8 +419,10 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   probs.W = T - net->discard;
   probs.C = probs.cs = net->n_classes;
   probs.p = d_probs;
-  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr,
-                  [&]() { return launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs); }));
+  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() {
+    if (sc) return launch_ctc_scores(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars);
+    return launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs);
+  }));
   return KOCR_OK;
 }
 

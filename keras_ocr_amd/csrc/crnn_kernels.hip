@@ -12,6 +12,8 @@
 //                       merge + blank removal by lane 0.
 //   ctc_loss_kernel     keras.backend.ctc_batch_cost (recognition.py:340-347): CTC forward algorithm in
 //                       log space, one wave per sample, states over the lanes.
+//   ctc_scores_kernel   ctc_kernel's decode + character scores + the word log-probability (ctc_loss_kernel's forward
+//                       algorithm on the crop's own decode) in one launch, one wave per crop.
 #include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -360,19 +362,19 @@ __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
   return mx + logf(expf(a - mx) + expf(b - mx) + expf(c - mx));
 }
 
+// The forward algorithm of one sample by one wave.  y0: the sample's first frame (row t of the loop is y0 + t * C); l: its L
+// labels (global or LDS); la: [2][Sp] floats of LDS, Sp >= 2L + 1.  Returns the loss (every lane computes it from LDS).
+// Shared by ctc_loss_kernel and ctc_scores_kernel, so that the word log-probability of a decode is, bit for bit, minus the
+// loss kocr_crnn_ctc_loss gives for the same labels.
 template <bool LOGITS>
-__global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ y, int T, int C, int t0,
-                                                      const int* __restrict__ lab, int lstride, const int* __restrict__ len,
-                                                      const int* __restrict__ in_len, float* __restrict__ loss, int Sp) {
-  extern __shared__ float la[];  // [2][Sp]
-  const int m = blockIdx.x, lane = threadIdx.x;
-  const int L = len[m], Tm = in_len[m], S = 2 * L + 1, blank = C - 1;
-  const int* l = lab + (size_t)m * lstride;
+__device__ __forceinline__ float ctc_loss_wave(const float* __restrict__ y0, int C, const int* l, int L, int Tm, float* la, int Sp,
+                                               int lane) {
+  const int S = 2 * L + 1, blank = C - 1;
   for (int s = lane; s < 2 * Sp; s += 64) la[s] = -INFINITY;
   __syncthreads();
   int cur = 0;
   for (int t = 0; t < Tm; ++t) {
-    const float* row = y + ((size_t)m * T + t0 + t) * C;
+    const float* row = y0 + (size_t)t * C;
     float mx = 0.f, es = 1.f;
     if (LOGITS) {
       int bi;
@@ -407,12 +409,71 @@ __global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ 
     __syncthreads();
     cur ^= 1;
   }
-  if (lane == 0) {
-    const float* fin = la + (cur ^ 1) * Sp;
-    const float a = fin[S - 1], b = L > 0 ? fin[S - 2] : -INFINITY;
-    const float mxv = fmaxf(a, b);
-    loss[m] = mxv == -INFINITY ? INFINITY : -(mxv + logf(expf(a - mxv) + expf(b - mxv)));
+  const float* fin = la + (cur ^ 1) * Sp;
+  const float a = fin[S - 1], b = L > 0 ? fin[S - 2] : -INFINITY;
+  const float mxv = fmaxf(a, b);
+  return mxv == -INFINITY ? INFINITY : -(mxv + logf(expf(a - mxv) + expf(b - mxv)));
+}
+
+template <bool LOGITS>
+__global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ y, int T, int C, int t0,
+                                                      const int* __restrict__ lab, int lstride, const int* __restrict__ len,
+                                                      const int* __restrict__ in_len, float* __restrict__ loss, int Sp) {
+  extern __shared__ float la[];  // [2][Sp]
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const float v = ctc_loss_wave<LOGITS>(y + ((size_t)m * T + t0) * C, C, lab + (size_t)m * lstride, len[m], in_len[m], la, Sp, lane);
+  if (lane == 0) loss[m] = v;
+}
+
+// ---- scores ("Scores"): ctc_kernel's decode, the character scores and the word log-probability of
+// every crop in one launch.  One wave (= one workgroup) per crop.  Pass 1 is ctc_kernel's loop: lane 0 emits the label row
+// (bit for bit ctc_kernel's: the same arg-max and the same rule) and keeps, per emitted label, the maximum over the frames
+// of its run of the arg-max's softmax probability -- ctc_softmax(max, max, sum), the very entry of `probs`.  Pass 2 is
+// ctc_loss_wave<true> on the decoded label, all To frames: the label row (at most To ints) and its length stay in LDS beside
+// the two alpha rows, so neither the labels, the length nor the states take a trip through the host; a crop's logits
+// (T x C floats) come from cache the second time.  logw = -loss; chars: [M][To], 0 behind the decode.
+__global__ __launch_bounds__(64) void ctc_scores_kernel(const float* __restrict__ logits, int T, int C, int discard,
+                                                        int* __restrict__ labels, float* __restrict__ probs,
+                                                        float* __restrict__ logw, float* __restrict__ chars, int Sp) {
+  extern __shared__ float la[];  // [2][Sp] alpha rows, then int[To + 1]: the decoded label and its length
+  int* dec = reinterpret_cast<int*>(la + 2 * Sp);
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int To = T - discard, blank = C - 1;
+  const float* y0 = logits + ((size_t)m * T + discard) * C;
+  int prev = -1, k = 0;
+  float run = 0.f;  // lane 0: the score of label k - 1 so far
+  for (int t = 0; t < To; ++t) {
+    const float* row = y0 + (size_t)t * C;
+    float bv;
+    int bi;
+    ctc_row_argmax(row, C, lane, bv, bi);
+    const float s = ctc_row_expsum(row, C, lane, bv);
+    if (probs)
+      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = ctc_softmax(row[c], bv, s);
+    if (lane == 0) {
+      const float p = ctc_softmax(bv, bv, s);
+      if (bi != prev && bi != blank) {
+        if (k) chars[(size_t)m * To + k - 1] = run;
+        dec[k] = bi;
+        labels[(size_t)m * To + k++] = bi;
+        run = p;
+      } else if (bi == prev && bi != blank) {
+        run = fmaxf(run, p);
+      }
+      prev = bi;
+    }
   }
+  if (lane == 0) {
+    if (k) chars[(size_t)m * To + k - 1] = run;
+    dec[To] = k;
+    for (; k < To; ++k) {
+      labels[(size_t)m * To + k] = -1;
+      chars[(size_t)m * To + k] = 0.f;
+    }
+  }
+  __syncthreads();
+  const float loss = ctc_loss_wave<true>(y0, C, dec, dec[To], To, la, Sp, lane);
+  if (lane == 0) logw[m] = -loss;
 }
 
 int launch_crnn_input(kocr_ctx* ctx, const float* d_crops, float* d_x, int M, int Hc, int Wc) {
@@ -553,6 +614,20 @@ int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int di
 }
 
 // y: device [M][T][C] (logits: fc_12's output, frames t0 .. t0 + T_m - 1; else probabilities, t0 = 0); d_lab: device
+// ctc_scores_kernel: labels [M][T - discard], probs (nullable), logw [M], chars [M][T - discard]
+int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
+                      float* d_logw, float* d_chars) {
+  if (M <= 0) return KOCR_OK;
+  const int To = T - discard;
+  const int Sp = (2 * To + 1 + 63) & ~63;
+  const size_t lds = (size_t)2 * Sp * sizeof(float) + (size_t)(To + 1) * sizeof(int);
+  ProfScope ps(ctx, "ctc_scores", 0, 4.0 * M * T * C * 4);
+  hipLaunchKernelGGL(ctc_scores_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_labels, d_probs, d_logw,
+                     d_chars, Sp);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
 // [M][lstride]; d_len / d_in_len: device [M], validated on the host (ctc_check); d_loss: device [M]
 int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, int C, int t0, const int* d_lab, int lstride,
                     const int* d_len, const int* d_in_len, float* d_loss, int Lmax) {

@@ -10,7 +10,7 @@ extern "C" int kocr_resize_pad(kocr_ctx* ctx, const uint8_t* src, int n, int sh,
   if (!ctx) return KOCR_EINVAL;
   if (n < 0 || (n > 0 && (!src || !dst))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_resize_pad: null buffer");
   if (n == 0) return KOCR_OK;
-  ctx->last_pl.valid = false;
+  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)n * sh * sw * 3, db = (size_t)n * Hmax * Wmax * 3;
   const size_t tb = (size_t)(4 * (Wmax + Hmax) + 64) * sizeof(int);
@@ -34,7 +34,7 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
   if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detect: bad dtype");
   if (N == 0) return KOCR_OK;
   if (cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detect: cap must be positive");
-  ctx->last_pl.valid = false;
+  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int h2 = H / 2, w2 = W / 2;
   const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
@@ -56,10 +56,12 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
     KOCR_TRY(craft_forward(ctx, d_in + (size_t)s * in_img, dtype, nb, H, W, d_heat + (size_t)s * h2 * w2 * 2));
   }
   int n_empty = 0;
+  const float* d_scores = nullptr;
   KOCR_TRY(postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold,
-                              size_threshold, d_boxes, cap, counts, &n_empty));
+                              size_threshold, d_boxes, cap, counts, &n_empty, nullptr, &d_scores));
   KOCR_TRY(st.back(boxes, d_boxes, box_b));
   KOCR_TRY(st.finish());
+  ctx->keep_det_scores(d_scores, N, cap);
   if (n_empty > 0)
     KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR, "kocr_detect: empty contour list (IndexError at detection.py:272)");
   return KOCR_OK;
@@ -76,29 +78,39 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
   std::vector<WarpParam> prm;
   const long M = prepare_box_warps(ctx, "kocr_recognize_boxes", N, boxes, counts, labels, CRNN_CROP_H, CRNN_CROP_W, prm);
   if (M <= 0) return (int)M;
-  ctx->last_pl.valid = false;
+  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int LW = crnn_label_width(ctx);
   const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float);
   const size_t lab_b = (size_t)M * LW * sizeof(int32_t), pb = (size_t)M * sizeof(WarpParam);
+  const bool scores = ctx->scores_on;
+  const size_t lw_b = scores ? (size_t)M * sizeof(float) : 0, ch_b = lw_b * LW;
   Staging st{ctx, ctx->io, "kocr_recognize_boxes", on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, lab_b}));
+  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, lab_b, lw_b, ch_b}));
   const WarpParam* d_prm;
   float* d_crops;
   int32_t* d_lab;
   const uint8_t* d_img;
+  CrnnScores sc{nullptr, nullptr};
   KOCR_TRY(st.scratch(pb, d_prm));
   KOCR_TRY(st.scratch(crop_b, d_crops));
   KOCR_TRY(st.scratch(lab_b, d_lab));
+  if (scores) {
+    KOCR_TRY(st.scratch(lw_b, sc.d_logw));
+    KOCR_TRY(st.scratch(ch_b, sc.d_chars));
+  }
   KOCR_TRY(st.in(img_rgb, ib, d_img));
   KOCR_TRY(st.put((WarpParam*)d_prm, prm.data(), pb));
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), C)));
   KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
-    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr);
+    const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
+    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
+                        scores ? &part : nullptr);
   }));
   KOCR_TRY(st.download(labels, d_lab, lab_b));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->keep_rec_scores(sc.d_logw, sc.d_chars, (int)M, LW);
   return KOCR_OK;
 }
 
@@ -111,7 +123,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   if (n_crops) *n_crops = 0;
   if (N < 0 || (N > 0 && (!imgs || !hs || !ws || !dhs || !dws || !boxes || !counts)))
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline: null buffer");
-  ctx->last_pl.valid = false;
+  ctx->invalidate_results();
   if (N == 0) return KOCR_OK;
   if (!ctx->craft) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_pipeline: call kocr_load_craft first");
   if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_pipeline: call kocr_load_crnn first");
@@ -199,6 +211,8 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   if (M == 0) {
     KOCR_TRY(finish());
     ctx->last_pl = {d_boxes, dv.d_counts, nullptr, N, cap, 0, true};
+    ctx->keep_det_scores(dv.d_scores, N, d_cap);
+    ctx->keep_rec_scores(nullptr, nullptr, 0, crnn_label_width(ctx));
     return KOCR_OK;
   }
   if (!labels && d_cap == cap) {
@@ -209,27 +223,38 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   const int LW = crnn_label_width(ctx);
   const size_t crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), lab_b = (size_t)M * LW * sizeof(int32_t);
   const size_t pb = (size_t)M * sizeof(WarpParam);
-  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, lab_b, 256}));
+  const bool scores = ctx->scores_on;
+  const size_t lw_b = scores ? (size_t)M * sizeof(float) : 0, ch_b = lw_b * LW;
+  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, lab_b, 256, lw_b, ch_b}));
   WarpParam* d_prm;
   float* d_crops;
   int32_t* d_lab;
   int* d_status;
+  CrnnScores sc{nullptr, nullptr};
   KOCR_TRY(io.scratch(pb, d_prm));
   KOCR_TRY(io.scratch(crop_b, d_crops));
   KOCR_TRY(io.scratch(lab_b, d_lab));
   KOCR_TRY(io.scratch(256, d_status));
+  if (scores) {
+    KOCR_TRY(io.scratch(lw_b, sc.d_logw));
+    KOCR_TRY(io.scratch(ch_b, sc.d_chars));
+  }
   KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), ctx->stream));
   KOCR_TRY(launch_warp_prepare(ctx, d_boxes, dv.d_counts, N, d_cap, CRNN_CROP_H, CRNN_CROP_W, d_prm, d_status));
   KOCR_TRY(launch_warp(ctx, d_bat, Hmax, Wmax, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   // ---- recogniser ----
   KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), crnn_classes(ctx))));
   KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
-    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr);
+    const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
+    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
+                        scores ? &part : nullptr);
   }));
   if (host_fits) KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, lab_b, hipMemcpyDeviceToHost, ctx->stream));
   KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   KOCR_TRY(finish());
   ctx->last_pl = {d_boxes, dv.d_counts, d_lab, N, d_cap, (int)M, true};
+  ctx->keep_det_scores(dv.d_scores, N, d_cap);
+  ctx->keep_rec_scores(sc.d_logw, sc.d_chars, (int)M, LW);
   if (!host_fits) {
     ctx->set_err("kocr_pipeline: an image has more boxes than cap, or there are more crops than max_crops; the results are "
                  "resident -- fetch them with kocr_pipeline_results into buffers sized from counts / n_crops");
@@ -252,6 +277,48 @@ extern "C" int kocr_pipeline_results(kocr_ctx* ctx, float* boxes, int cap, int32
                                  hipMemcpyDeviceToHost, ctx->stream));
   if (r.M > 0)
     KOCR_HIP(ctx, hipMemcpyAsync(labels, r.d_labels, (size_t)r.M * crnn_label_width(ctx) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KOCR_OK;
+}
+
+// The resident scores (see include/kocr.h, "Scores")
+static const char* const SCORES_OFF = ": the results on this context were produced with scores off (kocr_set_scores(ctx, 1) before the call)";
+
+extern "C" int kocr_detection_scores(kocr_ctx* ctx, float* scores, int cap) {
+  if (!ctx) return KOCR_EINVAL;
+  const auto& r = ctx->last_sc;
+  if (r.det_off) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_detection_scores") + SCORES_OFF);
+  if (!r.det_valid)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detection_scores: no detection scores are resident (call it right after kocr_get_boxes, "
+                                "kocr_detect or kocr_pipeline)");
+  if (!scores || cap < r.cap)
+    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_detection_scores: buffer smaller than the resident scores (cap >= " + std::to_string(r.cap) + ")");
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  // device rows are r.cap scores apart, the caller's cap scores
+  KOCR_HIP(ctx, hipMemcpy2DAsync(scores, (size_t)cap * 4, r.d_det, (size_t)r.cap * 4, (size_t)r.cap * 4, (size_t)r.N,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KOCR_OK;
+}
+
+extern "C" int kocr_recognition_scores(kocr_ctx* ctx, float* log_word, float* char_scores, int max_crops, int32_t* n_crops,
+                                       int32_t* label_width) {
+  if (!ctx) return KOCR_EINVAL;
+  const auto& r = ctx->last_sc;
+  if (r.rec_off) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_recognition_scores") + SCORES_OFF);
+  if (!r.rec_valid)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_scores: no recognition scores are resident (call it right after "
+                                "kocr_recognize_boxes or kocr_pipeline)");
+  if (n_crops) *n_crops = r.M;
+  if (label_width) *label_width = r.lw;
+  if (r.M > 0 && (!log_word || !char_scores || max_crops < r.M))
+    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_recognition_scores: buffers smaller than the resident scores (max_crops >= " +
+                                       std::to_string(r.M) + ")");
+  if (r.M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  // rows of the width they were PRODUCED with, whatever kocr_crnn_label_width() says by now
+  KOCR_HIP(ctx, hipMemcpyAsync(log_word, r.d_logw, (size_t)r.M * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipMemcpyAsync(char_scores, r.d_chars, (size_t)r.M * r.lw * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KOCR_OK;
 }

@@ -57,6 +57,7 @@ struct PPArgs {
   int* blk_off;   // [N][bpi]
   int* counts;    // [N] kept components per image (may exceed cap)
   int* comp_root; // [N][cap]
+  float* score;   // [N][cap] tmax of the kept component in the same slot: the detection score of its box
   int bpi, cap;
   CompInfo* info; // [N*cap]
   int* img_base;  // [N+1] first component index of each image
@@ -95,6 +96,7 @@ __device__ __forceinline__ int float_key(float f) {
   const int b = __float_as_int(f);
   return b >= 0 ? b : b ^ 0x7fffffff;
 }
+__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }  // float_key's inverse
 
 // ---- K1 -------------------------------------------------------------------------------
 __global__ void k_threshold(PPArgs p) {
@@ -210,7 +212,10 @@ __global__ void k_assign(PPArgs p) {
     const unsigned long long m = __ballot(kept);
     if (kept) {
       const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
-      if (slot < p.cap) p.comp_root[img * p.cap + slot] = img * hw + px;
+      if (slot < p.cap) {
+        p.comp_root[img * p.cap + slot] = img * hw + px;
+        p.score[img * p.cap + slot] = key_float(p.tmax[(size_t)img * hw + px]);  // what comp_kept compared with det_thr
+      }
     }
     base += __popcll(m);
   }
@@ -956,7 +961,8 @@ dim3 grid_for(size_t n, int block = 256) {
 // Returns KOCR_OK, or KOCR_ECAPACITY (counts still filled with the true numbers).
 int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, float det_thr,
                        float text_thr, float link_thr, int size_thr, float* d_boxes, int cap,
-                       int* h_counts, int* n_empty_out, PPDeviceOut* dev) {
+                       int* h_counts, int* n_empty_out, PPDeviceOut* dev, const float** d_scores) {
+  if (d_scores) *d_scores = nullptr;
   if (n_empty_out) *n_empty_out = 0;
   if (N <= 0) return KOCR_OK;
   if (h <= 0 || w <= 0 || h > 4096 || w > 4096)
@@ -976,7 +982,7 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   p.size_thr = size_thr;
   p.bpi = (h * w + SCAN_BLOCK - 1) / SCAN_BLOCK;
   p.cap = cap;
-  const size_t need = NP * (1 + 7 * 4) + (size_t)N * p.bpi * 8 + (size_t)N * 4 + (size_t)N * cap * 4 +
+  const size_t need = NP * (1 + 7 * 4) + (size_t)N * p.bpi * 8 + (size_t)N * 4 + (size_t)N * cap * 8 +
                       (size_t)N * cap * sizeof(CompInfo) + (size_t)(N + 1) * 4 + 64 + 20 * 256;
   KOCR_TRY(arena_reserve(ctx, ctx->pp, need));
   ctx->pp.off = 0;
@@ -993,6 +999,7 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   p.blk_off = (int*)A((size_t)N * p.bpi * 4);
   p.counts = (int*)A((size_t)N * 4);
   p.comp_root = (int*)A((size_t)N * cap * 4);
+  p.score = (float*)A((size_t)N * cap * 4);
   p.info = (CompInfo*)A((size_t)N * cap * sizeof(CompInfo));
   p.img_base = (int*)A((size_t)(N + 1) * 4);
   p.totals = (int*)A(64);
@@ -1000,7 +1007,9 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   if (dev) {
     dev->d_counts = p.counts;
     dev->d_totals = p.totals;
+    dev->d_scores = p.score;
   }
+  if (d_scores) *d_scores = p.score;
 
   const double hb = 8.0 * NP;
   {

@@ -77,9 +77,11 @@ def map_to_rgb(y):
 
 
 def getBoxes(y_pred, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,  # pylint: disable=invalid-name
-             min_area_rect=None):
+             min_area_rect=None, return_scores=False):
     """detection.getBoxes (detection.py:207-287) on the default context: (N,h,w,2) float32 heat-maps -> list of (n_i,4,2)
-    float32 boxes (``np.array([])`` for an image without boxes).
+    float32 boxes (``np.array([])`` for an image without boxes).  ``return_scores=True``: ``(box_groups, score_groups)``,
+    per image an (n_i,) float32 array of detection scores -- the maximum of the text map over each box's component, the
+    number compared with ``detection_threshold`` (detection.py:240).
 
     ``min_area_rect`` picks how ``cv2.boxPoints(cv2.minAreaRect(contour))`` (detection.py:273) is computed:
     ``"exact"`` -- the min-area rectangle in exact arithmetic (the default); ``"opencv"`` -- OpenCV's own float32 rotating
@@ -87,7 +89,7 @@ def getBoxes(y_pred, detection_threshold=0.7, text_threshold=0.4, link_threshold
     (``Context.set_min_area_rect``)."""
     return _lib.default_context().get_boxes(y_pred, detection_threshold=detection_threshold, text_threshold=text_threshold,
                                             link_threshold=link_threshold, size_threshold=size_threshold,
-                                            min_area_rect=min_area_rect)
+                                            min_area_rect=min_area_rect, return_scores=return_scores)
 
 
 class _CraftModel:
@@ -177,13 +179,14 @@ class Detector:
                 yield X, y
 
     def detect(self, images: typing.List[typing.Union[np.ndarray, str]], detection_threshold=0.7, text_threshold=0.4,
-               link_threshold=0.4, size_threshold=10, min_area_rect=None, **kwargs):
+               link_threshold=0.4, size_threshold=10, min_area_rect=None, return_scores=False, **kwargs):
         """Detector.detect (detection.py:745-785): list/array of same-sized HxWx3 RGB images (or
         paths) -> list of (n_i,4,2) float32 box arrays.  ``min_area_rect``: ``"exact"`` / ``"opencv"`` for this
-        call (see ``getBoxes``), ``None`` = the context's rule."""
+        call (see ``getBoxes``), ``None`` = the context's rule.  ``return_scores=True``: ``(box_groups, score_groups)`` as
+        ``getBoxes``."""
         images = [tools.read(image) for image in images]
         if not images:
-            return []
+            return ([], []) if return_scores else []
         batch = np.stack([np.asarray(im) for im in images])
         if batch.dtype != np.uint8:
             # the reference normalises whatever it is given (detection.py:34-42)
@@ -194,4 +197,5 @@ class Detector:
             batch /= variance * 255
         return self._ctx.detect(batch, detection_threshold=detection_threshold, text_threshold=text_threshold,
                                 link_threshold=link_threshold, size_threshold=size_threshold,
-                                micro_batch=kwargs.get("batch_size", 0) or 0, min_area_rect=min_area_rect)
+                                micro_batch=kwargs.get("batch_size", 0) or 0, min_area_rect=min_area_rect,
+                                return_scores=return_scores)

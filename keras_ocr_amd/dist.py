@@ -256,9 +256,18 @@ class ShardedPipeline:
             return dist.get_rank(self.group), dist.get_world_size(self.group)
         return 0, 1
 
-    def recognize(self, images, detection_kwargs=None, recognition_kwargs=None, timing=None):
-        """``timing`` (optional dict) receives ``gather_s``: the time spent in the three result all-gathers."""
+    @staticmethod
+    def _refuse_scores(return_scores):
+        if return_scores:
+            raise NotImplementedError("ShardedPipeline does not carry scores across ranks: its packed result rows hold boxes and "
+                                      "labels only; use Pipeline.recognize(..., return_scores=True) on each rank's own pages")
+
+    def recognize(self, images, detection_kwargs=None, recognition_kwargs=None, timing=None, return_scores=False):
+        """``timing`` (optional dict) receives ``gather_s``: the time spent in the three result all-gathers.
+        ``return_scores=True`` is refused (NotImplementedError): scores do not cross ranks."""
         from . import tools
+
+        self._refuse_scores(return_scores)
 
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
@@ -273,10 +282,11 @@ class ShardedPipeline:
                                                                    recognition_kwargs),
                                end > start, -(-len(images) // world), timing)
 
-    def recognize_device(self, d_ptr, n_total, h, w, detection_kwargs=None, timing=None):
+    def recognize_device(self, d_ptr, n_total, h, w, detection_kwargs=None, timing=None, return_scores=False):
         """The same for a batch whose images are already resident in THIS rank's HBM (``d_ptr`` = device pointer of this
         rank's contiguous block of images of the (n_total, h, w, 3) uint8 batch): every image has the same size, so the
-        whole batch's padded size is the shard's."""
+        whole batch's padded size is the shard's.  ``return_scores=True`` is refused as in ``recognize``."""
+        self._refuse_scores(return_scores)
         rank, world = self._rank_world()
         start, end = shard_bounds(n_total, world, rank)
         dev_res, scale = self._device_gather(n_total, h, w)

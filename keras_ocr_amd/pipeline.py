@@ -1,7 +1,7 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
 import numpy as np
 
-from . import detection, recognition, tools
+from . import detection, recognition, scores as _scores, tools
 
 
 def decode_labels(alphabet, labels):
@@ -58,23 +58,31 @@ class Pipeline:
         (N,H,W,3) array -> list (per image) of (text, box) tuples, boxes in input-image pixels."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs)
 
-    def recognize_padded(self, images, hmax, wmax, detection_kwargs=None, recognition_kwargs=None):
+    def recognize_with_scores(self, images, detection_kwargs=None, recognition_kwargs=None):
+        """recognize() that also says how sure the two networks were: (text, box, score) tuples, ``score`` a
+        ``scores.Score`` (detection, word, log_word, characters), computed on the GPU in the same pass (DESIGN.md section 4,
+        "Scores").  Texts and boxes are recognize()'s, bit for bit.  A method of its own because recognize() keeps the
+        reference's exact signature; ``recognize_padded`` / ``recognize_device`` take ``return_scores=True`` instead."""
+        return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs, return_scores=True)
+
+    def recognize_padded(self, images, hmax, wmax, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
         """recognize() with the padded detector-input size imposed by the caller (used when a
         larger batch is sharded across GPUs: every shard pads to the WHOLE batch's size)."""
-        box_groups, labels = self.recognize_raw(images, hmax, wmax, detection_kwargs, recognition_kwargs)
-        return self.assemble(box_groups, labels)
+        return self.assemble(*self.recognize_raw(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores))
 
-    def recognize_raw(self, images, hmax=None, wmax=None, detection_kwargs=None, recognition_kwargs=None):
+    def recognize_raw(self, images, hmax=None, wmax=None, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
         """The fused device path up to (but not including) string assembly: returns
         ``(box_groups, label_rows)`` -- per image an (n_i,4,2) float32 array in INPUT-image pixels
         (adjust_boxes already applied, pipeline.py:66-71) and one (sum n_i, 48) int32 array of decoded
         label rows (-1 padded, recognition.py:177-182) in image order.  This fixed-width form is what
-        crosses ranks in ``dist.ShardedPipeline``."""
+        crosses ranks in ``dist.ShardedPipeline``.  ``return_scores=True`` adds a third element ``(detection, log_word,
+        char_scores)``: per image an (n_i,) float32 array, and (sum n_i,) / (sum n_i, 48) float32 arrays in label-row order."""
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
         if not images:
-            return [], np.zeros((0, 48), np.int32)
+            empty = [], np.zeros((0, 48), np.int32)
+            return empty + (([], np.zeros(0, np.float32), np.zeros((0, 48), np.float32)),) if return_scores else empty
         detection_kwargs = dict(detection_kwargs or {})
         del recognition_kwargs  # Keras predict kwargs: no effect on results
         ctx = getattr(self.detector, "_ctx", None)
@@ -82,20 +90,20 @@ class Pipeline:
             # float (or any non-uint8) images: the reference's cv2 calls interpolate them in float (tools.py:394, :107);
             # the stage-wise path does the same with the float kernels (kocr_resize_pad_f32 / kocr_warp_crops_f32, round 5) --
             # off the fused fixed-point path, which is defined for uint8 pixels only
-            return self._recognize_stagewise([im.astype(np.float32) for im in images], detection_kwargs, hmax, wmax)
+            return self._recognize_stagewise([im.astype(np.float32) for im in images], detection_kwargs, hmax, wmax, return_scores)
         if ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx:
             # duck-typed / separately-placed stages: the reference's stage-wise path (pipeline.py:44-75)
-            return self._recognize_stagewise(images, detection_kwargs, hmax, wmax)
+            return self._recognize_stagewise(images, detection_kwargs, hmax, wmax, return_scores)
         scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
         hmax = hmax_ if hmax is None else max(hmax, hmax_)
         wmax = wmax_ if wmax is None else max(wmax, wmax_)
         micro_batch = detection_kwargs.pop("batch_size", 0) or 0
-        box_groups, labels = ctx.pipeline(
+        box_groups, *rest = ctx.pipeline(
             images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, hmax, wmax,
-            micro_batch=micro_batch, **detection_kwargs)
-        return self._adjust(box_groups, scales), labels
+            micro_batch=micro_batch, return_scores=return_scores, **detection_kwargs)
+        return (self._adjust(box_groups, scales), *rest)
 
-    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None):
+    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size)."""
@@ -107,21 +115,34 @@ class Pipeline:
         max_width = max(int(max_width), int(wmax or 0))
         scales = [scale for _, scale in resized]
         padded = np.array([tools.pad(image, width=max_width, height=max_height) for image, _ in resized])
-        box_groups = self.detector.detect(images=padded, **detection_kwargs)
-        texts = self.recognizer.recognize_from_boxes(images=padded, box_groups=box_groups)
+        if return_scores:
+            detect = _scores.need("detector", self.detector, "detect")
+            recognize = _scores.need("recognizer", self.recognizer, "recognize_from_boxes")
+            box_groups, det = detect(images=padded, return_scores=True, **detection_kwargs)
+            pairs = [pair for group in recognize(images=padded, box_groups=box_groups, return_scores=True) for pair in group]
+            rows = [t for t, _ in pairs]
+        else:
+            box_groups = self.detector.detect(images=padded, **detection_kwargs)
+            texts = self.recognizer.recognize_from_boxes(images=padded, box_groups=box_groups)
+            rows = [t for group in texts for t in group]
         alphabet = self.recognizer.alphabet
-        rows = [t for group in texts for t in group]
         labels = np.full((len(rows), max([48] + [len(t) for t in rows])), -1, np.int32)
         for r, t in enumerate(rows):
             labels[r, :len(t)] = [alphabet.index(ch) for ch in t]
+        if return_scores:
+            chars = np.zeros(labels.shape, np.float32)
+            for r, (_, score) in enumerate(pairs):
+                chars[r, :len(score.characters)] = score.characters
+            log_word = np.array([score.log_word for _, score in pairs], np.float32)
+            return self._adjust(box_groups, scales), labels, ([np.asarray(d, np.float32) for d in det], log_word, chars)
         return self._adjust(box_groups, scales), labels
 
-    def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None):
+    def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None, return_scores=False):
         """Same as recognize() for a batch already resident in HBM: ``d_ptr`` = device pointer of an
         (n,h,w,3) uint8 tensor (e.g. ``torch.Tensor.data_ptr()``)."""
-        return self.assemble(*self.recognize_device_raw(d_ptr, n, h, w, detection_kwargs))
+        return self.assemble(*self.recognize_device_raw(d_ptr, n, h, w, detection_kwargs, return_scores=return_scores))
 
-    def recognize_device_raw(self, d_ptr, n, h, w, detection_kwargs=None, device_results=None):
+    def recognize_device_raw(self, d_ptr, n, h, w, detection_kwargs=None, device_results=None, return_scores=False):
         """recognize_device up to (but not including) string assembly: ``(box_groups, label_rows)`` as recognize_raw.
         ``device_results`` (a dict, optional) receives where the same results still lie in HBM (``Context.
         pipeline_device_results``: boxes in DETECTOR-input pixels, before the division by the scale) plus ``scale``, for a
@@ -131,12 +152,13 @@ class Pipeline:
         scales, dhs, dws, hmax, wmax = self._plan([(h, w, 3)] * n)
         micro_batch = detection_kwargs.pop("batch_size", 0) or 0
         stride = h * w * 3
-        box_groups, labels = ctx.pipeline([int(d_ptr) + i * stride for i in range(n)], [h] * n, [w] * n, dhs, dws,
-                                          hmax, wmax, micro_batch=micro_batch, on_device=True, **detection_kwargs)
+        box_groups, *rest = ctx.pipeline([int(d_ptr) + i * stride for i in range(n)], [h] * n, [w] * n, dhs, dws,
+                                         hmax, wmax, micro_batch=micro_batch, on_device=True, return_scores=return_scores,
+                                         **detection_kwargs)
         if device_results is not None and n:
             device_results.update(ctx.pipeline_device_results())
             device_results["scale"] = scales[0]  # one size, one scale
-        return self._adjust(box_groups, scales), labels
+        return (self._adjust(box_groups, scales), *rest)
 
     @staticmethod
     def _adjust(box_groups, scales):
@@ -146,12 +168,21 @@ class Pipeline:
             for boxes, scale in zip(box_groups, scales)
         ]
 
-    def assemble(self, box_groups, labels):
-        """(box_groups, label rows) -> the reference's return value (pipeline.py:72-75)."""
+    def assemble(self, box_groups, labels, score_rows=None):
+        """(box_groups, label rows) -> the reference's return value (pipeline.py:72-75); with ``score_rows`` (recognize_raw's
+        third element) every tuple gets its ``scores.Score``."""
         # recognition.py:527-534: label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding
         predictions = decode_labels(self.recognizer.alphabet, labels)
+        columns = [predictions]
+        if score_rows is not None:
+            det, log_word, chars = score_rows
+            flat = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in det]) if len(det) else np.zeros(0, np.float32)
+            columns.append(_scores.assemble(labels, log_word, chars, flat))
         out, start = [], 0
         for boxes in box_groups:
-            out.append(list(zip(predictions[start:start + len(boxes)], boxes)))
+            if score_rows is None:
+                out.append(list(zip(predictions[start:start + len(boxes)], boxes)))
+            else:
+                out.append(list(zip(predictions[start:start + len(boxes)], boxes, columns[1][start:start + len(boxes)])))
             start += len(boxes)
         return out

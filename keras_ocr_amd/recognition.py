@@ -5,7 +5,7 @@ import typing
 
 import numpy as np
 
-from . import _lib, tools, weights as _weights
+from . import _lib, scores as _scores, tools, weights as _weights
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
     "height": 31,
@@ -294,8 +294,9 @@ class Recognizer:
         from .pipeline import decode_labels
         return decode_labels(self.alphabet, rows)
 
-    def recognize(self, image):
-        """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string."""
+    def recognize(self, image, return_scores=False):
+        """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string; ``return_scores=True``:
+        ``(text, score)``, a ``scores.Score`` whose ``detection`` is None."""
         image = tools.read_and_fit(filepath_or_array=image, width=200, height=31, cval=0)
         if image.shape[-1] == 3:
             # gray conversion on the GPU: warp the full 31x200 rectangle onto itself (identity map)
@@ -303,15 +304,19 @@ class Recognizer:
             crops = self._ctx.warp_crops(image[np.newaxis], [box[np.newaxis]], 31, 200)
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
+        if return_scores:
+            labels, log_word, chars = self._ctx.crnn_forward_scores(crops)
+            return self._decode(labels)[0], _scores.assemble(labels, log_word, chars)[0]
         return self._decode(self._ctx.crnn_forward(crops))[0]
 
-    def recognize_from_boxes(self, images, box_groups, **kwargs) -> typing.List[typing.List[str]]:
-        """Recognizer.recognize_from_boxes (recognition.py:491-537)."""
+    def recognize_from_boxes(self, images, box_groups, return_scores=False, **kwargs) -> typing.List[typing.List[str]]:
+        """Recognizer.recognize_from_boxes (recognition.py:491-537); ``return_scores=True``: per image a list of
+        ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
         assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
         images = [tools.read(image) for image in images]
         if not sum(len(b) for b in box_groups):
-            return [[]] * len(images)
+            return [[] for _ in images] if return_scores else [[]] * len(images)
         start_end: typing.List[typing.Tuple[int, int]] = []
         for boxes in box_groups:
             start = 0 if not start_end else start_end[-1][1]
@@ -325,15 +330,23 @@ class Recognizer:
                 if len(boxes):
                     im = np.asarray(image, np.float32)
                     crops.append(self._ctx.warp_crops_f32((im if im.ndim == 3 else im[..., np.newaxis])[np.newaxis], [boxes], 31, 200))
-            labels = self._ctx.crnn_forward(np.concatenate(crops) / np.float32(255))
-            predictions = self._decode(labels)
+            crops = np.concatenate(crops) / np.float32(255)
+            if return_scores:
+                return self._with_scores(*self._ctx.crnn_forward_scores(crops), start_end)
+            predictions = self._decode(self._ctx.crnn_forward(crops))
             return [predictions[start:end] for start, end in start_end]
         if len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            labels = self._ctx.recognize_boxes(np.stack(images), box_groups)
+            parts = [self._ctx.recognize_boxes(np.stack(images), box_groups, return_scores=return_scores)]
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            labels = np.concatenate([self._ctx.recognize_boxes(image[np.newaxis], [boxes])
-                                     for image, boxes in zip(images, box_groups) if len(boxes)])
-        predictions = self._decode(labels)
+            parts = [self._ctx.recognize_boxes(image[np.newaxis], [boxes], return_scores=return_scores)
+                     for image, boxes in zip(images, box_groups) if len(boxes)]
+        if return_scores:
+            return self._with_scores(*[np.concatenate(column) for column in zip(*parts)], start_end)
+        predictions = self._decode(np.concatenate(parts))
         return [predictions[start:end] for start, end in start_end]
+
+    def _with_scores(self, labels, log_word, chars, start_end):
+        pairs = list(zip(self._decode(labels), _scores.assemble(labels, log_word, chars)))
+        return [pairs[start:end] for start, end in start_end]
