@@ -382,6 +382,33 @@ int kocr_recognition_scores(kocr_ctx* ctx, float* log_word, float* char_scores, 
 int kocr_crnn_forward_scores(kocr_ctx* ctx, const float* crops, int M, int32_t* labels, float* probs, float* log_word,
                              float* char_scores, int on_device);
 
+/* ---- beam search: the other readings of a word ("Beam search") ---------------------------------------
+ * keras.backend.ctc_decode(greedy=False, beam_width, top_paths), which the reference never exposes: CTC prefix beam search
+ * without a language model on the frame probabilities of kocr_ctc_batch_cost (q_t: fc_12's softmax + epsilon, renormalised;
+ * frames rnn_steps_to_discard .. 49).  Per frame a prefix is extended by the min(beam_width, classes - 1) non-blank classes
+ * of the largest logit only; candidates spelling the same prefix are merged; the best beam_width by total probability
+ * survive.  Order everywhere: the higher value first, then the lexicographically smaller label row, -1 sorting after every
+ * label.  Of the final beam the top_paths best are RESCORED with the CTC forward algorithm: log_prob is, bit for bit,
+ * -kocr_crnn_ctc_loss of the crop with that label row (the exact sum over all its alignments, not the beam's running sum),
+ * and the rows come sorted by it.  labels: M x top_paths x kocr_crnn_label_width() int32, -1 padded as kocr_crnn_forward's;
+ * log_prob: M x top_paths float32.  When fewer than top_paths prefixes survive, the remaining rows are all -1 with
+ * log_prob = -inf.  1 <= beam_width <= 64, 1 <= top_paths <= beam_width, else KOCR_EINVAL naming the argument.
+ * beam_width = 1 is NOT the greedy decode (one prefix per frame is not one arg-max per frame).  A crop's result does not
+ * depend on M or on its place in the batch.  on_device as for kocr_crnn_forward. */
+int kocr_crnn_beam(kocr_ctx* ctx, const float* crops, int M, int beam_width, int top_paths, int32_t* labels, float* log_prob,
+                   int on_device);
+/* kocr_set_beam(ctx, beam_width, top_paths) (beam_width = 0, the default: off) makes kocr_recognize_boxes / kocr_pipeline run
+ * the beam search on every crop AFTER their unchanged greedy decode (one more launch per batch, profiler row ctc_beam) and
+ * leave the alternatives resident in HBM; the label rows, boxes, counts and scores they return are the same bits either way.
+ * kocr_recognition_beams copies them out: labels [n_crops][top_paths][label width], log_prob [n_crops][top_paths] (HOST,
+ * image-major, box order as the label rows); *n_crops / *label_width / *top_paths (each may be NULL) receive what the rows
+ * were PRODUCED with, also when the call fails with KOCR_ECAPACITY (max_crops too small).  Validity and errors as for
+ * kocr_recognition_scores. */
+int kocr_set_beam(kocr_ctx* ctx, int beam_width, int top_paths);
+int kocr_get_beam(const kocr_ctx* ctx, int* beam_width, int* top_paths);
+int kocr_recognition_beams(kocr_ctx* ctx, int32_t* labels, float* log_prob, int max_crops, int32_t* n_crops,
+                           int32_t* label_width, int32_t* top_paths);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx
  * stream; kocr_profile_report fills parallel arrays (up to cap rows) with per-kernel-name

@@ -71,6 +71,10 @@ def load_library():
         "kocr_crnn_set_taps": (ci, [vp, ci, ctypes.POINTER(ctypes.c_char_p)]),
         "kocr_crnn_forward": (ci, [vp, vp, ci, vp, vp, ci]),
         "kocr_crnn_forward_scores": (ci, [vp, vp, ci, vp, vp, vp, vp, ci]),
+        "kocr_crnn_beam": (ci, [vp, vp, ci, ci, ci, vp, vp, ci]),
+        "kocr_set_beam": (ci, [vp, ci, ci]),
+        "kocr_get_beam": (ci, [vp, vp, vp]),
+        "kocr_recognition_beams": (ci, [vp, vp, vp, ci, vp, vp, vp]),
         "kocr_set_scores": (ci, [vp, ci]),
         "kocr_get_scores": (ci, [vp]),
         "kocr_detection_scores": (ci, [vp, vp, ci]),
@@ -127,6 +131,17 @@ def _ptr(a):
     if isinstance(a, (int, np.integer)):
         return ctypes.c_void_p(int(a))
     return ctypes.c_void_p(a.ctypes.data)
+
+
+def beam_args(beam_width, top_paths=1):
+    """(beam_width, top_paths) as ints, or ValueError naming the argument: 1 <= beam_width <= 64, 1 <= top_paths <=
+    beam_width (include/kocr.h: "Beam search"; the library checks the same)."""
+    bw, k = int(beam_width), int(top_paths)
+    if not 1 <= bw <= 64:
+        raise ValueError(f"beam_width {bw} outside [1, 64]")
+    if not 1 <= k <= bw:
+        raise ValueError(f"top_paths {k} outside [1, beam_width = {bw}]")
+    return bw, k
 
 
 class Context:
@@ -342,6 +357,59 @@ class Context:
                         value_error=True)
         return log_word, chars
 
+    # -- beam search (include/kocr.h: "Beam search") --------------------------------------------------------------------
+    def crnn_beam(self, crops, beam_width, top_paths=1):
+        """CTC prefix beam search on the crops' logits (kocr_crnn_beam): labels (M, top_paths, 48) int32, -1 padded, best
+        first, and log_prob (M, top_paths) float32 = -crnn_ctc_loss of each row, bit for bit; rows that do not exist are all
+        -1 with -inf.  ValueError naming the argument for beam_width outside [1, 64] or top_paths outside [1, beam_width]."""
+        bw, k = beam_args(beam_width, top_paths)
+        x = self._crops(crops)
+        m = x.shape[0]
+        labels = np.full((m, k, self.crnn_label_width()), -1, dtype=np.int32)
+        log_prob = np.full((m, k), -np.inf, dtype=np.float32)
+        self._check(self._lib.kocr_crnn_beam(self._h, _ptr(x), m, bw, k, _ptr(labels), _ptr(log_prob), 0), value_error=True)
+        return labels, log_prob
+
+    def crnn_beam_device(self, d_crops, m, beam_width, top_paths, d_labels, d_log_prob):
+        self._check(self._lib.kocr_crnn_beam(self._h, _ptr(d_crops), int(m), int(beam_width), int(top_paths), _ptr(d_labels),
+                                             _ptr(d_log_prob), 1), value_error=True)
+
+    def set_beam(self, beam_width=0, top_paths=1):
+        """Whether recognize_boxes / pipeline also leave beam alternatives resident (kocr_set_beam); 0 = off."""
+        self._check(self._lib.kocr_set_beam(self._h, int(beam_width), int(top_paths)), value_error=True)
+
+    def get_beam(self):
+        bw, k = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self._lib.kocr_get_beam(self._h, ctypes.byref(bw), ctypes.byref(k)))
+        return bw.value, k.value
+
+    @contextlib.contextmanager
+    def _beam_scope(self, beam):
+        """The beam for one call (``beam=(beam_width, top_paths)``); None: the context's own setting."""
+        if beam is None:
+            yield
+            return
+        old = self.get_beam()
+        self.set_beam(*beam_args(*beam))
+        try:
+            yield
+        finally:
+            self.set_beam(*old)
+
+    def recognition_beams(self):
+        """The resident beam alternatives (kocr_recognition_beams): labels (M, top_paths, label width) int32 and log_prob
+        (M, top_paths) float32 as they were produced; ValueError when nothing is resident or the beam was off."""
+        m, lw, k = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self._lib.kocr_recognition_beams(self._h, None, None, 0, ctypes.byref(m), ctypes.byref(lw), ctypes.byref(k))
+        if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
+            self._check(rc, value_error=True)
+        labels = np.full((m.value, k.value, lw.value), -1, dtype=np.int32)
+        log_prob = np.full((m.value, k.value), -np.inf, dtype=np.float32)
+        if m.value:
+            self._check(self._lib.kocr_recognition_beams(self._h, _ptr(labels), _ptr(log_prob), m.value, None, None, None),
+                        value_error=True)
+        return labels, log_prob
+
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
 
@@ -452,9 +520,19 @@ class Context:
             int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), return_scores)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
-    def recognize_boxes(self, images, box_groups, return_scores=False):
+    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None):
         """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32 [, log_word (M,), char_scores
-        (M,48) float32 as ``crnn_forward_scores``]."""
+        (M,48) float32 as ``crnn_forward_scores``] [, beam labels (M,K,48), beam log_prob (M,K) as ``crnn_beam``, with
+        ``beam=(beam_width, top_paths)``; the other results are the same bits]."""
+        if beam is not None:
+            bw, k = beam_args(*beam)
+            with self._beam_scope((bw, k)):
+                head = self.recognize_boxes(images, box_groups, return_scores)
+                head = head if return_scores else (head,)
+                if not len(head[0]):
+                    lw = self.crnn_label_width()
+                    return head + (np.zeros((0, k, lw), np.int32), np.zeros((0, k), np.float32))
+                return head + self.recognition_beams()
         x = np.ascontiguousarray(images, dtype=np.uint8)
         n, h, w, _ = x.shape
         counts, flat = _flatten_boxes(box_groups)
@@ -546,13 +624,21 @@ class Context:
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
-                 min_area_rect=None, return_scores=False):
+                 min_area_rect=None, return_scores=False, beam=None):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns
         (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``.
-        ``return_scores``: a third element ``(detection list[(n_i,) f32], log_word (M,) f32, char_scores (M,48) f32)``."""
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores):
-            return self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                                  size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
+        ``return_scores``: a third element ``(detection list[(n_i,) f32], log_word (M,) f32, char_scores (M,48) f32)``.
+        ``beam=(beam_width, top_paths)``: a last element ``(beam labels (M,K,48) int32, beam log_prob (M,K) f32)`` as
+        ``crnn_beam``; boxes, labels and scores are the same bits."""
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam):
+            out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
+                                 size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
+            if beam is None:
+                return out
+            if not len(ptrs):
+                lw = self.crnn_label_width()
+                return out + ((np.zeros((0, beam[1], lw), np.int32), np.zeros((0, beam[1]), np.float32)),)
+            return out + (self.recognition_beams(),)
 
     def _pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
                   size_threshold, micro_batch, on_device, cap, max_crops, return_scores=False):

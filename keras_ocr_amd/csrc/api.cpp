@@ -13,6 +13,7 @@
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   ctx->last_pl.valid = false;  // whoever sizes an arena is about to overwrite it (kocr_pipeline re-validates at its end)
   ctx->last_sc.clear();        // the resident scores likewise
+  ctx->last_beam.clear();      // ... and the resident beam alternatives
   if (bytes <= a.cap) return KOCR_OK;
   if (a.base) {
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -405,6 +406,34 @@ int kocr_crnn_forward_scores(kocr_ctx* ctx, const float* crops, int M, int32_t* 
     if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
     KOCR_TRY(st.back(log_word + s, sc.d_logw, wb * nb));
     KOCR_TRY(st.back(char_scores + s * LW, sc.d_chars, hb * nb));
+    return st.finish();
+  });
+}
+
+// The beam search of include/kocr.h ("Beam search") alone: the forward up to fc_12, then ctc_beam_kernel
+int kocr_crnn_beam(kocr_ctx* ctx, const float* crops, int M, int beam_width, int top_paths, int32_t* labels, float* log_prob,
+                   int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  KOCR_TRY(beam_validate(ctx, "kocr_crnn_beam", beam_width, top_paths));
+  if (M < 0 || (M > 0 && (!crops || !labels || !log_prob))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_beam: null buffer");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_beam: call kocr_load_crnn first");
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = crnn_batch(M);
+  const int LW = crnn_label_width(ctx);
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = (size_t)top_paths * LW * sizeof(int32_t), vb = top_paths * sizeof(float);
+  Staging st{ctx, ctx->ws, "kocr_crnn_beam", on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, vb * mb}));
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    const float* d_c;
+    CrnnBeam bm{beam_width, top_paths, nullptr, nullptr};
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(labels + s * top_paths * LW, lb * nb, bm.d_labels));
+    KOCR_TRY(st.out(log_prob + s * top_paths, vb * nb, bm.d_logp));
+    KOCR_TRY(crnn_beam(ctx, d_c, nb, bm));
+    KOCR_TRY(st.back(labels + s * top_paths * LW, bm.d_labels, lb * nb));
+    KOCR_TRY(st.back(log_prob + s * top_paths, bm.d_logp, vb * nb));
     return st.finish();
   });
 }
@@ -904,6 +933,26 @@ int kocr_set_scores(kocr_ctx* ctx, int on) {
 }
 
 int kocr_get_scores(const kocr_ctx* ctx) { return ctx ? (ctx->scores_on ? 1 : 0) : KOCR_EINVAL; }
+
+int kocr_set_beam(kocr_ctx* ctx, int beam_width, int top_paths) {
+  if (!ctx) return KOCR_EINVAL;
+  if (beam_width == 0) {
+    ctx->beam_width = 0;
+    ctx->beam_top_paths = 1;
+    return KOCR_OK;
+  }
+  KOCR_TRY(beam_validate(ctx, "kocr_set_beam", beam_width, top_paths));
+  ctx->beam_width = beam_width;
+  ctx->beam_top_paths = top_paths;
+  return KOCR_OK;
+}
+
+int kocr_get_beam(const kocr_ctx* ctx, int* beam_width, int* top_paths) {
+  if (!ctx) return KOCR_EINVAL;
+  if (beam_width) *beam_width = ctx->beam_width;
+  if (top_paths) *top_paths = ctx->beam_top_paths;
+  return KOCR_OK;
+}
 
 int kocr_profile_enable(kocr_ctx* ctx, int on) {
   if (!ctx) return KOCR_EINVAL;

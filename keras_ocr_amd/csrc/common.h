@@ -222,9 +222,24 @@ struct kocr_ctx {
     bool rec_valid = false, rec_off = false;
     void clear() { det_valid = det_off = rec_valid = rec_off = false; }
   } last_sc;
+  // beam search (kocr_set_beam; DESIGN.md section 4, "Beam search"): with beam_width > 0, kocr_recognize_boxes /
+  // kocr_pipeline also run ctc_beam_kernel on every batch's logits and leave the alternatives resident beside the label
+  // rows for kocr_recognition_beams.  Valid like last_sc; lw / K: the label width and top_paths they were produced with.
+  int beam_width = 0, beam_top_paths = 1;
+  struct LastBeam {
+    const int* d_labels = nullptr;  // [M][K][lw]
+    const float* d_logp = nullptr;  // [M][K]
+    int M = 0, lw = 0, K = 0;
+    bool valid = false, off = false;  // off: results were produced with the beam off
+    void clear() { valid = off = false; }
+  } last_beam;
+  void keep_beams(const int* d_labels, const float* d_logp, int M, int lw) {
+    last_beam = {d_labels, d_logp, M, lw, beam_top_paths, beam_width > 0, beam_width == 0};
+  }
   void invalidate_results() {
     last_pl.valid = false;
     last_sc.clear();
+    last_beam.clear();
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
@@ -450,8 +465,20 @@ struct CrnnScores {
   float* d_logw;
   float* d_chars;
 };
+// bm (CRNN_DECODE only): after the decode, ctc_beam_kernel on the same logits: d_labels [M][top_paths][crnn_label_width()],
+// d_logp [M][top_paths].  The decode's own launch and results are untouched.
+struct CrnnBeam {
+  int beam_width, top_paths;
+  int* d_labels;
+  float* d_logp;
+};
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
-                 float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr);
+                 float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr,
+                 const CrnnBeam* bm = nullptr);
+// crnn_forward to the logits, then ctc_beam_kernel alone (kocr_crnn_beam)
+int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm);
+// KOCR_EINVAL naming the argument unless 1 <= beam_width <= 64 and 1 <= top_paths <= beam_width
+int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths);
 // training_model (recognition.py:334-349): crnn_forward to the logits, then ctc_loss_kernel on fc_12's softmax of frames
 // rnn_steps_to_discard .. + input_length - 1; labels / lengths already validated (ctc_validate) and on the device
 int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,

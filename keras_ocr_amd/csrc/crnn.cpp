@@ -33,6 +33,8 @@ int launch_dense_splitk(kocr_ctx* ctx, const ConvLayer& L, const float* d_in, fl
 int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs);
 int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
                       float* d_logw, float* d_chars);
+int launch_ctc_beam(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int beam_width, int top_paths,
+                    int* d_labels, float* d_logp);
 
 struct CrnnNet {
   std::map<std::string, ConvLayer> L;
@@ -216,9 +218,9 @@ size_t crnn_workspace_bytes(int M, int n_classes) {
 }
 
 // d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
-// `stop` / d_feats / d_logits / sc: common.h
+// `stop` / d_feats / d_logits / sc / bm: common.h
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
-                 const float** d_logits, const CrnnScores* sc) {
+                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -423,6 +425,24 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
     if (sc) return launch_ctc_scores(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars);
     return launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs);
   }));
+  if (bm)
+    KOCR_TRY(launch_ctc_beam(ctx, lg.p, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp));
+  return KOCR_OK;
+}
+
+int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm) {
+  const float* d_lg = nullptr;
+  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
+  if (M <= 0) return KOCR_OK;
+  return launch_ctc_beam(ctx, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, bm.beam_width, bm.top_paths, bm.d_labels, bm.d_logp);
+}
+
+int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths) {
+  if (beam_width < 1 || beam_width > 64)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": beam_width " + std::to_string(beam_width) + " outside [1, 64]");
+  if (top_paths < 1 || top_paths > beam_width)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": top_paths " + std::to_string(top_paths) + " outside [1, beam_width = " +
+                                    std::to_string(beam_width) + "]");
   return KOCR_OK;
 }
 

@@ -476,6 +476,284 @@ __global__ __launch_bounds__(64) void ctc_scores_kernel(const float* __restrict_
   if (lane == 0) logw[m] = -loss;
 }
 
+// ---- beam search ("Beam search"): CTC prefix beam search without a language model (Graves 2012,
+// Hannun 2014; keras.backend.ctc_decode(greedy=False)), one wave (= one workgroup) per crop, lane i owning beam entry i.
+// Frame probabilities are the loss's q_t (ctc_loss_wave<true>: fc_12's softmax + eps, renormalised), float32 log domain.
+// An entry is a prefix with log p_blank / log p_nonblank (the summed probability of the alignments of the frames so far
+// that collapse to the prefix and end / do not end in a blank).  Per frame every entry proposes
+//   same      the prefix itself: pb' = tot + lq(blank), pnb' = pnb + lq(last label)           (tot = lse(pb, pnb))
+//   ext(e)    the prefix + class cls[e]: pnb' = (cls[e] == last label ? pb : tot) + lq(cls[e]), pb' = -inf
+// for the E = min(B, C - 1) non-blank classes of the largest logit (ties: the smaller class), which is q_t's order.  An
+// ext that spells a prefix already in the beam is MERGED into that entry's `same` (log-add into pnb'): the entry finds its
+// parent through the rolling 64-bit key of its prefix without the last label, confirmed by a full compare.  No two other
+// candidates can spell the same prefix.  The best B candidates by total make the next beam, taken one per round.
+// Tie rule: the higher total first, then the lexicographically smaller label row, -1 sorting after every label.
+// After the last frame the K best entries are copied out by the same rounds, each is rescored by ctc_loss_wave<true> (the
+// exact sum over all alignments: log_prob == -kocr_crnn_ctc_loss of that label, bit for bit) and the rows are written in
+// the order of the rescored value (tie rule as above).  Every reduction has a fixed order and nothing is shared between
+// crops, so a crop's result does not depend on M or on its place in the batch.
+// LDS: two beams of B x (key, parent key, pb, pnb, len, last, prefix[Ls]), the loss's la [2][Sp], cls / lqc / par / pe [64 each]:
+// 2 B (4 Ls + 32) + 8 Sp + 1024 bytes, 32.3 KB at B = 64, To = 50 (Ls = To | 1 keeps the rows off one bank).
+struct BeamBuf {
+  unsigned long long* key;   // rolling key of the prefix
+  unsigned long long* pkey;  // ... of the prefix without its last label
+  float* pb;
+  float* pnb;
+  int* len;
+  int* last;
+  int* pre;  // [B][Ls]
+};
+constexpr unsigned long long BEAM_KEY_MUL = 0x9E3779B97F4A7C15ull;
+constexpr int BEAM_NONE = 0x7fffffff;  // "no label" in row comparisons: sorts after every label
+
+__device__ __forceinline__ float ctc_lse2(float a, float b) {
+  const float mx = fmaxf(a, b);
+  if (mx == -INFINITY) return -INFINITY;
+  return mx + logf(expf(a - mx) + expf(b - mx));
+}
+
+// Position p of the label row of a candidate: entry x's prefix, then class c (BEAM_NONE: none), then BEAM_NONE.
+__device__ __forceinline__ int beam_row_at(const BeamBuf& b, int Ls, int x, int len, int c, int p) {
+  return p < len ? b.pre[x * Ls + p] : (p == len ? c : BEAM_NONE);
+}
+
+// The wave's best candidate: every lane offers (v, its entry's length, the appended class or BEAM_NONE); returns the
+// winning lane, or -1 when every v is -inf.  Equal v: the lexicographically smaller row, compared by the 64 lanes at once
+// (rows are at most 64 long and differ, since equal prefixes were merged).
+__device__ __forceinline__ int beam_pick(const BeamBuf& b, int Ls, float v, int len, int c, int lane) {
+  float vmax = v;
+  for (int o = 32; o; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
+  if (vmax == -INFINITY) return -1;
+  unsigned long long tied = __ballot(v == vmax);
+  int w = __ffsll((long long)tied) - 1;
+  tied &= tied - 1;
+  while (tied) {
+    const int u = __ffsll((long long)tied) - 1;
+    tied &= tied - 1;
+    const int a = beam_row_at(b, Ls, w, __shfl(len, w), __shfl(c, w), lane);
+    const int d = beam_row_at(b, Ls, u, __shfl(len, u), __shfl(c, u), lane);
+    const unsigned long long diff = __ballot(a != d);
+    const int f = __ffsll((long long)diff) - 1;  // diff != 0: the rows differ
+    if (__shfl(d, f) < __shfl(a, f)) w = u;
+  }
+  return w;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logits, int T, int C, int discard, int B, int K,
+                                                      int* __restrict__ labels, float* __restrict__ logp, int Sp, int Ls) {
+  extern __shared__ unsigned long long beam_lds[];
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int To = T - discard, blank = C - 1, E = min(B, C - 1);
+  // both beams side by side, array by array: buffer i starts i * B (i * B * Ls for the prefixes) into each
+  unsigned long long* keys = beam_lds;            // [2][B]
+  unsigned long long* pkeys = keys + 2 * B;       // [2][B]
+  float* la = reinterpret_cast<float*>(pkeys + 2 * B);  // [2][Sp]
+  float* pbs = la + 2 * Sp;                       // [2][B]
+  float* pnbs = pbs + 2 * B;                      // [2][B]
+  float* lqc = pnbs + 2 * B;                      // [64] log q of the frame's extension classes
+  int* cls = reinterpret_cast<int*>(lqc + 64);    // [64] the frame's extension classes
+  int* par = cls + 64;                            // [64] entry -> the entry whose ext it merges (-1: none)
+  int* pe = par + 64;                             // [64] ... and which ext
+  int* lens = pe + 64;                            // [2][B]
+  int* lasts = lens + 2 * B;                      // [2][B]
+  int* pres = lasts + 2 * B;                      // [2][B][Ls]
+  auto beam = [&](int i) { return BeamBuf{keys + i * B, pkeys + i * B, pbs + i * B, pnbs + i * B, lens + i * B, lasts + i * B, pres + i * B * Ls}; };
+  const float* y0 = logits + ((size_t)m * T + discard) * C;
+
+  // the empty prefix: p_blank = 1
+  if (lane == 0) {
+    keys[0] = pkeys[0] = 0;
+    pbs[0] = 0.f;
+    pnbs[0] = -INFINITY;
+    lens[0] = 0;
+    lasts[0] = -1;
+  }
+  int nb = 1, cur = 0;
+  __syncthreads();
+  // frames 0 .. To - 1, then one more pass (t == To) that moves the K best entries, unchanged, into the other buffer
+  for (int t = 0; t <= To; ++t) {
+    const bool fin = t == To;
+    const BeamBuf bc = beam(cur), bn = beam(cur ^ 1);
+    const float* row = y0 + (size_t)t * C;
+    float mx = 0.f, es = 1.f, logz = 0.f;
+    if (!fin) {
+      int bi;
+      ctc_row_argmax(row, C, lane, mx, bi);
+      es = ctc_row_expsum(row, C, lane, mx);
+      float z = 0.f;
+      for (int c = lane; c < C; c += 64) z += ctc_softmax(row[c], mx, es) + CTC_EPS;
+      for (int o = 32; o; o >>= 1) z += __shfl_xor(z, o);
+      logz = logf(z);
+      // the E extension classes: all of them, or E rounds of "the largest logit behind the last pick"
+      if (E == C - 1) {
+        if (lane < E) cls[lane] = lane;
+      } else {
+        float pv = INFINITY;
+        int pc = -1;
+        for (int e = 0; e < E; ++e) {
+          float bv = -INFINITY;
+          int bc_ = BEAM_NONE;
+          for (int c = lane; c < blank; c += 64) {
+            const float v = row[c];
+            if ((v < pv || (v == pv && c > pc)) && (v > bv || (v == bv && c < bc_))) {
+              bv = v;
+              bc_ = c;
+            }
+          }
+          for (int o = 32; o; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oc = __shfl_xor(bc_, o);
+            if (ov > bv || (ov == bv && oc < bc_)) {
+              bv = ov;
+              bc_ = oc;
+            }
+          }
+          pv = bv;
+          pc = bc_;
+          if (lane == e) cls[e] = bc_;
+        }
+      }
+      if (lane < E) lqc[lane] = logf(ctc_softmax(row[cls[lane]], mx, es) + CTC_EPS) - logz;
+      __syncthreads();
+    }
+    // this lane's entry
+    const bool valid = lane < nb;
+    const float pb = valid ? bc.pb[lane] : -INFINITY, pnb = valid ? bc.pnb[lane] : -INFINITY;
+    const int len = valid ? bc.len[lane] : 0, last = valid ? bc.last[lane] : -1;
+    const unsigned long long key = valid ? bc.key[lane] : 0, pkey = valid ? bc.pkey[lane] : 0;
+    const float tot = ctc_lse2(pb, pnb);
+    float same_pb = pb, same_pnb = pnb;
+    unsigned long long taken = E < 64 ? ~0ull << E : 0ull;  // exts that are no candidates of this lane
+    if (fin) {
+      taken = ~0ull;
+    } else {
+      // the entry whose prefix is this one's without the last label, and its ext that spells this prefix
+      int pi = -1, pj = 0;
+      float extv = -INFINITY;
+      if (valid && len > 0) {
+        for (int i = 0; i < nb && pi < 0; ++i) {
+          if (bc.len[i] != len - 1 || bc.key[i] != pkey) continue;
+          bool eq = true;
+          for (int p = 0; p < len - 1 && eq; ++p) eq = bc.pre[i * Ls + p] == bc.pre[lane * Ls + p];
+          if (eq) pi = i;
+        }
+        if (pi >= 0) {
+          int e = 0;
+          while (e < E && cls[e] != last) ++e;
+          if (e < E) {
+            pj = e;
+            extv = (bc.last[pi] == last ? bc.pb[pi] : ctc_lse2(bc.pb[pi], bc.pnb[pi])) + lqc[e];
+          } else {
+            pi = -1;
+          }
+        }
+      }
+      par[lane] = pi;
+      pe[lane] = pj;
+      __syncthreads();
+      for (int j = 0; j < nb; ++j)
+        if (par[j] == lane) taken |= 1ull << pe[j];
+      same_pb = tot + (logf(ctc_softmax(row[blank], mx, es) + CTC_EPS) - logz);
+      same_pnb = len > 0 ? pnb + (logf(ctc_softmax(row[last], mx, es) + CTC_EPS) - logz) : -INFINITY;
+      same_pnb = ctc_lse2(same_pnb, extv);
+    }
+    const float same_tot = valid ? ctc_lse2(same_pb, same_pnb) : -INFINITY;
+    bool same_taken = false;
+    const int rounds = fin ? K : B;
+    int r = 0;
+    bool rescan = true;
+    float best_v = -INFINITY;
+    int best_e = -1, best_c = BEAM_NONE;
+    for (; r < rounds; ++r) {
+      if (rescan) {  // this lane's best remaining candidate: the total, then ext before same, then the smaller class
+        best_v = -INFINITY;
+        best_e = -1;
+        best_c = BEAM_NONE;
+        for (int e = 0; e < E; ++e) {
+          if ((taken >> e) & 1) continue;
+          const int c = cls[e];
+          const float v = (c == last ? pb : tot) + lqc[e];
+          if (v > best_v || (v == best_v && c < best_c)) {
+            best_v = v;
+            best_e = e;
+            best_c = c;
+          }
+        }
+        if (!same_taken && same_tot > best_v) {
+          best_v = same_tot;
+          best_e = -1;
+          best_c = BEAM_NONE;
+        }
+        rescan = false;
+      }
+      const int w = beam_pick(bc, Ls, best_v, len, best_c, lane);
+      if (w < 0) break;
+      // entry r of the next beam: the winner's row, then its values (written by the winner itself)
+      const int wl = __shfl(len, w), wc = __shfl(best_c, w);
+      if (lane < Ls) {
+        const int v = beam_row_at(bc, Ls, w, wl, wc, lane);
+        bn.pre[r * Ls + lane] = v == BEAM_NONE ? -1 : v;
+      }
+      if (lane == w) {
+        if (best_e < 0) {
+          bn.key[r] = key;
+          bn.pkey[r] = pkey;
+          bn.pb[r] = same_pb;
+          bn.pnb[r] = same_pnb;
+          bn.len[r] = len;
+          bn.last[r] = last;
+          same_taken = true;
+        } else {
+          bn.key[r] = key * BEAM_KEY_MUL + (unsigned long long)(best_c + 1);
+          bn.pkey[r] = key;
+          bn.pb[r] = -INFINITY;
+          bn.pnb[r] = best_v;
+          bn.len[r] = len + 1;
+          bn.last[r] = best_c;
+          taken |= 1ull << best_e;
+        }
+        rescan = true;
+      }
+    }
+    nb = r;
+    cur ^= 1;
+    __syncthreads();
+  }
+  // rescoring: nb <= K rows
+  const BeamBuf bo = beam(cur);
+  float lp = -INFINITY;
+  for (int k = 0; k < nb; ++k) {
+    const float loss = ctc_loss_wave<true>(y0, C, bo.pre + k * Ls, bo.len[k], To, la, Sp, lane);
+    if (lane == k) lp = -loss;
+  }
+  // the rows in the order of the rescored value (tie rule), the rest -1 / -inf
+  float* lps = lqc;  // [64]: the rescored values, for the ranks
+  __syncthreads();
+  lps[lane] = lp;
+  __syncthreads();
+  if (lane < K) {
+    int rank = lane;
+    if (lane < nb) {
+      rank = 0;
+      for (int j = 0; j < nb; ++j) {
+        if (j == lane) continue;
+        const float vj = lps[j];
+        bool first = vj > lp;
+        if (vj == lp) {
+          int p = 0;
+          while (p < To && bo.pre[j * Ls + p] == bo.pre[lane * Ls + p]) ++p;
+          const int a = p < To ? bo.pre[j * Ls + p] : -1, d = p < To ? bo.pre[lane * Ls + p] : -1;
+          first = (a < 0 ? BEAM_NONE : a) < (d < 0 ? BEAM_NONE : d);
+        }
+        rank += first ? 1 : 0;
+      }
+    }
+    int* out = labels + ((size_t)m * K + rank) * To;
+    for (int p = 0; p < To; ++p) out[p] = lane < nb ? bo.pre[lane * Ls + p] : -1;
+    logp[(size_t)m * K + rank] = lp;
+  }
+}
+
 int launch_crnn_input(kocr_ctx* ctx, const float* d_crops, float* d_x, int M, int Hc, int Wc) {
   const size_t total = (size_t)M * Hc * Wc;
   if (!total) return KOCR_OK;
@@ -624,6 +902,22 @@ int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C,
   ProfScope ps(ctx, "ctc_scores", 0, 4.0 * M * T * C * 4);
   hipLaunchKernelGGL(ctc_scores_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_labels, d_probs, d_logw,
                      d_chars, Sp);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// ctc_beam_kernel: d_labels [M][top_paths][T - discard], d_logp [M][top_paths]
+int launch_ctc_beam(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int beam_width, int top_paths,
+                    int* d_labels, float* d_logp) {
+  if (M <= 0) return KOCR_OK;
+  const int To = T - discard, B = beam_width;
+  if (To < 1 || To > 63 || B < 1 || B > 64 || top_paths < 1 || top_paths > B || C < 1)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "ctc_beam: bad sizes");
+  const int Sp = (2 * To + 1 + 63) & ~63, Ls = To | 1;
+  const size_t lds = (size_t)2 * B * (4 * Ls + 32) + (size_t)8 * Sp + 1024;
+  ProfScope ps(ctx, "ctc_beam", 0, 4.0 * M * T * C * (2 + top_paths));
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, B, top_paths, d_labels, d_logp, Sp,
+                     Ls);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }

@@ -262,12 +262,21 @@ class ShardedPipeline:
             raise NotImplementedError("ShardedPipeline does not carry scores across ranks: its packed result rows hold boxes and "
                                       "labels only; use Pipeline.recognize(..., return_scores=True) on each rank's own pages")
 
+    @staticmethod
+    def _refuse_beam(recognition_kwargs):
+        if (recognition_kwargs or {}).get("beam_width") is not None:
+            raise NotImplementedError("ShardedPipeline does not carry beam alternatives across ranks: its packed result rows hold "
+                                      "boxes and one label row per word; use Pipeline.recognize(..., recognition_kwargs="
+                                      "{'beam_width': ...}) on each rank's own pages")
+
     def recognize(self, images, detection_kwargs=None, recognition_kwargs=None, timing=None, return_scores=False):
         """``timing`` (optional dict) receives ``gather_s``: the time spent in the three result all-gathers.
-        ``return_scores=True`` is refused (NotImplementedError): scores do not cross ranks."""
+        ``return_scores=True`` and a ``beam_width`` in ``recognition_kwargs`` are refused (NotImplementedError): neither
+        scores nor beam alternatives cross ranks."""
         from . import tools
 
         self._refuse_scores(return_scores)
+        self._refuse_beam(recognition_kwargs)
 
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]

@@ -1,7 +1,16 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
 import numpy as np
 
-from . import detection, recognition, scores as _scores, tools
+from . import _lib, detection, recognition, scores as _scores, tools
+
+
+def beam_of(recognition_kwargs):
+    """``(beam_width, top_paths)`` from recognize()'s ``recognition_kwargs`` (validated: ValueError naming the argument), or
+    None without a ``beam_width``.  Every other key is a Keras predict argument and has no effect on results."""
+    kwargs = recognition_kwargs or {}
+    if kwargs.get("beam_width") is None:
+        return None
+    return _lib.beam_args(kwargs["beam_width"], kwargs.get("top_paths", 1))
 
 
 def decode_labels(alphabet, labels):
@@ -55,14 +64,20 @@ class Pipeline:
 
     def recognize(self, images, detection_kwargs=None, recognition_kwargs=None):
         """Pipeline.recognize (pipeline.py:28-75): list of images (arrays or file paths) or an
-        (N,H,W,3) array -> list (per image) of (text, box) tuples, boxes in input-image pixels."""
+        (N,H,W,3) array -> list (per image) of (text, box) tuples, boxes in input-image pixels.
+
+        ``recognition_kwargs={"beam_width": B, "top_paths": K}`` ("Beam search"): every ``text`` becomes
+        a list of up to K alternatives ``(text, log_prob)``, best first, as ``Recognizer.recognize``; the boxes are the same
+        bits.  The other keys of both dicts are Keras predict arguments without effect."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs)
 
     def recognize_with_scores(self, images, detection_kwargs=None, recognition_kwargs=None):
         """recognize() that also says how sure the two networks were: (text, box, score) tuples, ``score`` a
         ``scores.Score`` (detection, word, log_word, characters), computed on the GPU in the same pass (DESIGN.md section 4,
         "Scores").  Texts and boxes are recognize()'s, bit for bit.  A method of its own because recognize() keeps the
-        reference's exact signature; ``recognize_padded`` / ``recognize_device`` take ``return_scores=True`` instead."""
+        reference's exact signature; ``recognize_padded`` / ``recognize_device`` take ``return_scores=True`` instead.
+        With a ``beam_width`` in ``recognition_kwargs`` the tuples are (alternatives, box, score); ``score.word`` /
+        ``log_word`` / ``characters`` keep referring to the greedy decode, which need not be the first alternative."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs, return_scores=True)
 
     def recognize_padded(self, images, hmax, wmax, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
@@ -76,34 +91,42 @@ class Pipeline:
         (adjust_boxes already applied, pipeline.py:66-71) and one (sum n_i, 48) int32 array of decoded
         label rows (-1 padded, recognition.py:177-182) in image order.  This fixed-width form is what
         crosses ranks in ``dist.ShardedPipeline``.  ``return_scores=True`` adds a third element ``(detection, log_word,
-        char_scores)``: per image an (n_i,) float32 array, and (sum n_i,) / (sum n_i, 48) float32 arrays in label-row order."""
+        char_scores)``: per image an (n_i,) float32 array, and (sum n_i,) / (sum n_i, 48) float32 arrays in label-row order.
+        With a ``beam_width`` in ``recognition_kwargs`` the result has four elements: the third is the scores or None, the
+        fourth ``(beam labels (sum n_i, K, 48) int32, beam log_prob (sum n_i, K) float32)`` as ``Context.crnn_beam``."""
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
+        beam = beam_of(recognition_kwargs)  # the rest: Keras predict kwargs, no effect on results
         if not images:
             empty = [], np.zeros((0, 48), np.int32)
-            return empty + (([], np.zeros(0, np.float32), np.zeros((0, 48), np.float32)),) if return_scores else empty
+            scores = ([], np.zeros(0, np.float32), np.zeros((0, 48), np.float32)) if return_scores else None
+            if beam:
+                return empty + (scores, (np.zeros((0, beam[1], 48), np.int32), np.zeros((0, beam[1]), np.float32)))
+            return empty + (scores,) if return_scores else empty
         detection_kwargs = dict(detection_kwargs or {})
-        del recognition_kwargs  # Keras predict kwargs: no effect on results
         ctx = getattr(self.detector, "_ctx", None)
         if any(im.dtype != np.uint8 for im in images):
             # float (or any non-uint8) images: the reference's cv2 calls interpolate them in float (tools.py:394, :107);
             # the stage-wise path does the same with the float kernels (kocr_resize_pad_f32 / kocr_warp_crops_f32, round 5) --
             # off the fused fixed-point path, which is defined for uint8 pixels only
-            return self._recognize_stagewise([im.astype(np.float32) for im in images], detection_kwargs, hmax, wmax, return_scores)
+            return self._recognize_stagewise([im.astype(np.float32) for im in images], detection_kwargs, hmax, wmax, return_scores,
+                                             beam)
         if ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx:
             # duck-typed / separately-placed stages: the reference's stage-wise path (pipeline.py:44-75)
-            return self._recognize_stagewise(images, detection_kwargs, hmax, wmax, return_scores)
+            return self._recognize_stagewise(images, detection_kwargs, hmax, wmax, return_scores, beam)
         scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
         hmax = hmax_ if hmax is None else max(hmax, hmax_)
         wmax = wmax_ if wmax is None else max(wmax, wmax_)
         micro_batch = detection_kwargs.pop("batch_size", 0) or 0
         box_groups, *rest = ctx.pipeline(
             images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, hmax, wmax,
-            micro_batch=micro_batch, return_scores=return_scores, **detection_kwargs)
+            micro_batch=micro_batch, return_scores=return_scores, beam=beam, **detection_kwargs)
+        if beam and not return_scores:
+            rest.insert(1, None)
         return (self._adjust(box_groups, scales), *rest)
 
-    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False):
+    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size)."""
@@ -129,13 +152,24 @@ class Pipeline:
         labels = np.full((len(rows), max([48] + [len(t) for t in rows])), -1, np.int32)
         for r, t in enumerate(rows):
             labels[r, :len(t)] = [alphabet.index(ch) for ch in t]
+        if beam:
+            # a second recogniser call: the public method returns either the decode or its alternatives
+            words = [w for group in self.recognizer.recognize_from_boxes(images=padded, box_groups=box_groups, beam_width=beam[0],
+                                                                         top_paths=beam[1]) for w in group]
+            beam_rows = (np.full((len(rows), beam[1], labels.shape[1]), -1, np.int32),
+                         np.full((len(rows), beam[1]), -np.inf, np.float32))
+            for r, alternatives in enumerate(words):
+                for k, (t, log_prob) in enumerate(alternatives):
+                    beam_rows[0][r, k, :len(t)] = [alphabet.index(ch) for ch in t]
+                    beam_rows[1][r, k] = log_prob
         if return_scores:
             chars = np.zeros(labels.shape, np.float32)
             for r, (_, score) in enumerate(pairs):
                 chars[r, :len(score.characters)] = score.characters
             log_word = np.array([score.log_word for _, score in pairs], np.float32)
-            return self._adjust(box_groups, scales), labels, ([np.asarray(d, np.float32) for d in det], log_word, chars)
-        return self._adjust(box_groups, scales), labels
+            score_rows = ([np.asarray(d, np.float32) for d in det], log_word, chars)
+            return (self._adjust(box_groups, scales), labels, score_rows) + ((beam_rows,) if beam else ())
+        return (self._adjust(box_groups, scales), labels) + ((None, beam_rows) if beam else ())
 
     def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None, return_scores=False):
         """Same as recognize() for a batch already resident in HBM: ``d_ptr`` = device pointer of an
@@ -168,11 +202,19 @@ class Pipeline:
             for boxes, scale in zip(box_groups, scales)
         ]
 
-    def assemble(self, box_groups, labels, score_rows=None):
+    def assemble(self, box_groups, labels, score_rows=None, beam_rows=None):
         """(box_groups, label rows) -> the reference's return value (pipeline.py:72-75); with ``score_rows`` (recognize_raw's
-        third element) every tuple gets its ``scores.Score``."""
+        third element) every tuple gets its ``scores.Score``; with ``beam_rows`` (its fourth) the texts are replaced by
+        their lists of ``(text, log_prob)`` alternatives."""
         # recognition.py:527-534: label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding
-        predictions = decode_labels(self.recognizer.alphabet, labels)
+        if beam_rows is not None:
+            beam_labels, beam_log_prob = np.asarray(beam_rows[0]), np.asarray(beam_rows[1])
+            m, k = beam_log_prob.shape
+            texts = decode_labels(self.recognizer.alphabet, beam_labels.reshape(m * k, -1)) if m * k else []
+            predictions = [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
+                           for i in range(m)]
+        else:
+            predictions = decode_labels(self.recognizer.alphabet, labels)
         columns = [predictions]
         if score_rows is not None:
             det, log_word, chars = score_rows

@@ -294,9 +294,24 @@ class Recognizer:
         from .pipeline import decode_labels
         return decode_labels(self.alphabet, rows)
 
-    def recognize(self, image, return_scores=False):
+    def _alternatives(self, beam_labels, beam_log_prob):
+        """Beam rows (M, K, width) / (M, K) -> per word a list of up to K ``(text, log_prob)``, best first; the rows that do
+        not exist (all -1, -inf) are dropped."""
+        beam_labels, beam_log_prob = np.asarray(beam_labels), np.asarray(beam_log_prob)
+        m, k = beam_log_prob.shape
+        texts = self._decode(beam_labels.reshape(m * k, -1)) if m * k else []
+        return [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
+                for i in range(m)]
+
+    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1):
         """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string; ``return_scores=True``:
-        ``(text, score)``, a ``scores.Score`` whose ``detection`` is None."""
+        ``(text, score)``, a ``scores.Score`` whose ``detection`` is None.
+
+        ``beam_width=B`` (1..64; default None: the greedy decode above, untouched): instead of the string, a list of up to
+        ``top_paths`` alternatives ``(text, log_prob)``, best first, from a CTC prefix beam search (DESIGN.md section 4,
+        "Beam search"); ``log_prob`` is the exact log-probability of the text, ``-ctc loss``.  With ``return_scores`` the
+        result is ``(alternatives, score)``, the score still that of the greedy decode."""
+        beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         image = tools.read_and_fit(filepath_or_array=image, width=200, height=31, cval=0)
         if image.shape[-1] == 3:
             # gray conversion on the GPU: warp the full 31x200 rectangle onto itself (identity map)
@@ -304,19 +319,28 @@ class Recognizer:
             crops = self._ctx.warp_crops(image[np.newaxis], [box[np.newaxis]], 31, 200)
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
+        if beam is not None:
+            alternatives = self._alternatives(*self._ctx.crnn_beam(crops, *beam))[0]
+            if not return_scores:
+                return alternatives
+            labels, log_word, chars = self._ctx.crnn_forward_scores(crops)
+            return alternatives, _scores.assemble(labels, log_word, chars)[0]
         if return_scores:
             labels, log_word, chars = self._ctx.crnn_forward_scores(crops)
             return self._decode(labels)[0], _scores.assemble(labels, log_word, chars)[0]
         return self._decode(self._ctx.crnn_forward(crops))[0]
 
-    def recognize_from_boxes(self, images, box_groups, return_scores=False, **kwargs) -> typing.List[typing.List[str]]:
+    def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1,
+                             **kwargs) -> typing.List[typing.List[str]]:
         """Recognizer.recognize_from_boxes (recognition.py:491-537); ``return_scores=True``: per image a list of
-        ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None."""
+        ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None.  ``beam_width`` / ``top_paths``: as
+        ``recognize`` -- every text becomes its list of ``(text, log_prob)`` alternatives."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
+        beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
         images = [tools.read(image) for image in images]
         if not sum(len(b) for b in box_groups):
-            return [[] for _ in images] if return_scores else [[]] * len(images)
+            return [[] for _ in images] if return_scores or beam else [[]] * len(images)
         start_end: typing.List[typing.Tuple[int, int]] = []
         for boxes in box_groups:
             start = 0 if not start_end else start_end[-1][1]
@@ -331,21 +355,34 @@ class Recognizer:
                     im = np.asarray(image, np.float32)
                     crops.append(self._ctx.warp_crops_f32((im if im.ndim == 3 else im[..., np.newaxis])[np.newaxis], [boxes], 31, 200))
             crops = np.concatenate(crops) / np.float32(255)
+            if beam is not None:
+                head = self._ctx.crnn_forward_scores(crops) if return_scores else ()
+                return self._with_beams(head + self._ctx.crnn_beam(crops, *beam), start_end)
             if return_scores:
                 return self._with_scores(*self._ctx.crnn_forward_scores(crops), start_end)
             predictions = self._decode(self._ctx.crnn_forward(crops))
             return [predictions[start:end] for start, end in start_end]
         if len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            parts = [self._ctx.recognize_boxes(np.stack(images), box_groups, return_scores=return_scores)]
+            parts = [self._ctx.recognize_boxes(np.stack(images), box_groups, return_scores=return_scores, beam=beam)]
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            parts = [self._ctx.recognize_boxes(image[np.newaxis], [boxes], return_scores=return_scores)
+            parts = [self._ctx.recognize_boxes(image[np.newaxis], [boxes], return_scores=return_scores, beam=beam)
                      for image, boxes in zip(images, box_groups) if len(boxes)]
+        if beam is not None:
+            columns = [np.concatenate(column) for column in zip(*parts)]
+            return self._with_beams(tuple(columns[1:]) if not return_scores else tuple(columns), start_end)
         if return_scores:
             return self._with_scores(*[np.concatenate(column) for column in zip(*parts)], start_end)
         predictions = self._decode(np.concatenate(parts))
         return [predictions[start:end] for start, end in start_end]
+
+    def _with_beams(self, columns, start_end):
+        """columns: ([labels, log_word, chars,] beam labels, beam log_prob) -> per image the alternatives [with scores]"""
+        words = self._alternatives(*columns[-2:])
+        if len(columns) > 2:
+            words = list(zip(words, _scores.assemble(*columns[:3])))
+        return [words[start:end] for start, end in start_end]
 
     def _with_scores(self, labels, log_word, chars, start_end):
         pairs = list(zip(self._decode(labels), _scores.assemble(labels, log_word, chars)))
