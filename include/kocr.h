@@ -409,6 +409,46 @@ int kocr_get_beam(const kocr_ctx* ctx, int* beam_width, int* top_paths);
 int kocr_recognition_beams(kocr_ctx* ctx, int32_t* labels, float* log_prob, int max_crops, int32_t* n_crops,
                            int32_t* label_width, int32_t* top_paths);
 
+/* ---- lexicon: which of the caller's words is this crop ("Lexicon") -----------------------------------
+ * value[m][v] = the exact CTC log-probability of word v given crop m: -kocr_crnn_ctc_loss of the crop with the word's labels
+ * over all kocr_crnn_label_width() frames (q_t: fc_12's softmax + epsilon, renormalised, as kocr_ctc_batch_cost); -inf for
+ * a word that has no alignment (it needs more frames than there are once every repeated label has its blank).
+ * A lexicon is loaded once and stays resident on the context like weights.  kocr_set_lexicon: words = V label rows, int32
+ * [V][stride], lengths int32 [V] (HOST); every label in [0, classes - 2] of the LOADED recogniser (KOCR_ENOWEIGHTS without
+ * one), 1 <= length <= min(KOCR_LEXICON_MAX_WORD, stride), else KOCR_EINVAL naming the argument and the word.  Equal words
+ * may repeat (the tie rule orders them).  V = 0 unloads.  A call replaces the previous lexicon; a refused one changes nothing.
+ * Loading another recogniser with a DIFFERENT class count unloads the lexicon and switches the match off (the labels were
+ * checked against the old alphabet); calls that need one then fail with KOCR_EINVAL saying so.  kocr_lexicon_size: V (0: none).
+ *
+ * kocr_crnn_lexicon: crops as kocr_crnn_forward.  Per crop the top_words best words: index M x top_words int32 (the word's
+ * row in the CALLER's order), log_prob M x top_words float32.  Order: the higher value first, then the smaller index.  The
+ * best are found on the values of the scoring kernel, then each is RESCORED with the loss's own forward recursion:
+ * log_prob is, bit for bit, -kocr_crnn_ctc_loss of the crop with that word, and the rows come sorted by it (same tie rule).
+ * Where fewer than top_words words have an alignment the remaining entries are index -1, log_prob -inf.  all_values
+ * (nullable): M x V float32, the scoring kernel's own value of every pair (within the CTC loss's float32 error of the
+ * definition above, -inf exactly where it is).  1 <= top_words <= 64 (more than V is allowed), else KOCR_EINVAL naming the
+ * argument; no lexicon loaded: KOCR_EINVAL.  M = 0 is valid.  A crop's result does not depend on M, on its place in the
+ * batch or on the scratch chunking.  on_device as for kocr_crnn_forward (all buffers then device pointers).
+ *
+ * kocr_set_lexicon_match(ctx, top_words) (0, the default: off; needs a loaded lexicon otherwise) makes kocr_recognize_boxes /
+ * kocr_pipeline run the match on every crop AFTER their unchanged decode (three more launches per chunk of crops: profiler
+ * rows lexicon_logq, lexicon_score, lexicon_select) and leave index / log_prob resident in HBM; label rows, boxes, counts,
+ * scores and beam rows are the same bits either way.  kocr_recognition_lexicon copies them out: index / log_prob
+ * [n_crops][top_words] (HOST, image-major, box order as the label rows); *n_crops / *top_words (each may be NULL) receive
+ * what the rows were PRODUCED with, also when the call fails with KOCR_ECAPACITY (max_crops too small).  Validity and errors
+ * as for kocr_recognition_beams.
+ * kocr_set_lexicon_scratch: the M x V values of a batch live in workspace scratch of at most `bytes` (0: the default,
+ * 256 MiB); a batch whose values exceed it is processed in chunks of max(1, bytes / (4 V)) crops.  Results do not depend on it. */
+#define KOCR_LEXICON_MAX_WORD 32
+int kocr_set_lexicon(kocr_ctx* ctx, const int32_t* words, int stride, const int32_t* lengths, int V);
+int kocr_lexicon_size(const kocr_ctx* ctx);
+int kocr_crnn_lexicon(kocr_ctx* ctx, const float* crops, int M, int top_words, int32_t* index, float* log_prob, float* all_values,
+                      int on_device);
+int kocr_set_lexicon_match(kocr_ctx* ctx, int top_words);
+int kocr_get_lexicon_match(const kocr_ctx* ctx, int* top_words);
+int kocr_recognition_lexicon(kocr_ctx* ctx, int32_t* index, float* log_prob, int max_crops, int32_t* n_crops, int32_t* top_words);
+int kocr_set_lexicon_scratch(kocr_ctx* ctx, uint64_t bytes);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx
  * stream; kocr_profile_report fills parallel arrays (up to cap rows) with per-kernel-name

@@ -75,6 +75,13 @@ def load_library():
         "kocr_set_beam": (ci, [vp, ci, ci]),
         "kocr_get_beam": (ci, [vp, vp, vp]),
         "kocr_recognition_beams": (ci, [vp, vp, vp, ci, vp, vp, vp]),
+        "kocr_set_lexicon": (ci, [vp, vp, ci, vp, ci]),
+        "kocr_lexicon_size": (ci, [vp]),
+        "kocr_crnn_lexicon": (ci, [vp, vp, ci, ci, vp, vp, vp, ci]),
+        "kocr_set_lexicon_match": (ci, [vp, ci]),
+        "kocr_get_lexicon_match": (ci, [vp, vp]),
+        "kocr_recognition_lexicon": (ci, [vp, vp, vp, ci, vp, vp]),
+        "kocr_set_lexicon_scratch": (ci, [vp, ctypes.c_uint64]),
         "kocr_set_scores": (ci, [vp, ci]),
         "kocr_get_scores": (ci, [vp]),
         "kocr_detection_scores": (ci, [vp, vp, ci]),
@@ -410,6 +417,82 @@ class Context:
                         value_error=True)
         return labels, log_prob
 
+    # -- lexicon (include/kocr.h: "Lexicon") ------------------------------------------------------------------------------
+    def set_lexicon(self, labels=None, lengths=None):
+        """Load the word list (kocr_set_lexicon): labels (V, stride) int32 rows, lengths (V,); it stays resident like weights.
+        ``set_lexicon(None)`` unloads.  ValueError naming the argument and the word for a label outside [0, classes - 2] or a
+        length outside [1, 32]."""
+        if labels is None or len(labels) == 0:
+            self._check(self._lib.kocr_set_lexicon(self._h, None, 0, None, 0), value_error=True)
+            return
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim != 2:
+            raise ValueError(f"lexicon labels must be (V, stride), got shape {lab.shape}")
+        lens = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        if len(lens) != len(lab):
+            raise ValueError(f"lexicon lengths: {len(lens)} entries for {len(lab)} words")
+        self._check(self._lib.kocr_set_lexicon(self._h, _ptr(lab), lab.shape[1], _ptr(lens), len(lab)), value_error=True)
+
+    def lexicon_size(self):
+        return self._check(self._lib.kocr_lexicon_size(self._h))
+
+    def set_lexicon_scratch(self, nbytes=0):
+        """The value scratch one chunk of crops may take (kocr_set_lexicon_scratch); 0: the default.  Results do not depend on it."""
+        self._check(self._lib.kocr_set_lexicon_scratch(self._h, int(nbytes)))
+
+    def crnn_lexicon(self, crops, top_words, return_values=False):
+        """The crops' best lexicon words (kocr_crnn_lexicon): index (M, top_words) int32 into the loaded word list, best first,
+        -1 where fewer words are feasible, and log_prob (M, top_words) float32 = -crnn_ctc_loss of crop and word, bit for bit
+        (-inf there) [, the scoring kernel's own values (M, V) float32].  ValueError for top_words outside [1, 64] or without
+        a lexicon."""
+        x = self._crops(crops)
+        m, k = x.shape[0], int(top_words)
+        index = np.full((m, max(k, 0)), -1, dtype=np.int32)
+        log_prob = np.full((m, max(k, 0)), -np.inf, dtype=np.float32)
+        values = np.full((m, self.lexicon_size()), -np.inf, dtype=np.float32) if return_values else None
+        self._check(self._lib.kocr_crnn_lexicon(self._h, _ptr(x), m, k, _ptr(index), _ptr(log_prob), _ptr(values), 0), value_error=True)
+        return (index, log_prob, values) if return_values else (index, log_prob)
+
+    def crnn_lexicon_device(self, d_crops, m, top_words, d_index, d_log_prob, d_values=None):
+        self._check(self._lib.kocr_crnn_lexicon(self._h, _ptr(d_crops), int(m), int(top_words), _ptr(d_index), _ptr(d_log_prob),
+                                                _ptr(d_values), 1), value_error=True)
+
+    def set_lexicon_match(self, top_words=0):
+        """Whether recognize_boxes / pipeline also leave lexicon matches resident (kocr_set_lexicon_match); 0 = off."""
+        self._check(self._lib.kocr_set_lexicon_match(self._h, int(top_words)), value_error=True)
+
+    def get_lexicon_match(self):
+        k = ctypes.c_int(0)
+        self._check(self._lib.kocr_get_lexicon_match(self._h, ctypes.byref(k)))
+        return k.value
+
+    @contextlib.contextmanager
+    def _lexicon_scope(self, top_words):
+        """The lexicon match for one call; None: the context's own setting."""
+        if top_words is None:
+            yield
+            return
+        old = self.get_lexicon_match()
+        self.set_lexicon_match(top_words)
+        try:
+            yield
+        finally:
+            if self.lexicon_size():  # a lexicon unloaded meanwhile took the switch with it
+                self.set_lexicon_match(old)
+
+    def recognition_lexicon(self):
+        """The resident lexicon matches (kocr_recognition_lexicon): index (M, top_words) int32 and log_prob (M, top_words)
+        float32 as they were produced; ValueError when nothing is resident or the match was off."""
+        m, k = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self._lib.kocr_recognition_lexicon(self._h, None, None, 0, ctypes.byref(m), ctypes.byref(k))
+        if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
+            self._check(rc, value_error=True)
+        index = np.full((m.value, k.value), -1, dtype=np.int32)
+        log_prob = np.full((m.value, k.value), -np.inf, dtype=np.float32)
+        if m.value:
+            self._check(self._lib.kocr_recognition_lexicon(self._h, _ptr(index), _ptr(log_prob), m.value, None, None), value_error=True)
+        return index, log_prob
+
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
 
@@ -520,10 +603,18 @@ class Context:
             int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), return_scores)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
-    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None):
+    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None):
         """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32 [, log_word (M,), char_scores
         (M,48) float32 as ``crnn_forward_scores``] [, beam labels (M,K,48), beam log_prob (M,K) as ``crnn_beam``, with
-        ``beam=(beam_width, top_paths)``; the other results are the same bits]."""
+        ``beam=(beam_width, top_paths)``; the other results are the same bits] [, lexicon index (M,K), log_prob (M,K) as
+        ``crnn_lexicon``, with ``lexicon_top=K``]."""
+        if lexicon_top is not None:
+            with self._lexicon_scope(lexicon_top):
+                head = self.recognize_boxes(images, box_groups, return_scores, beam)
+                head = head if isinstance(head, tuple) else (head,)
+                if not len(head[0]):
+                    return head + (np.zeros((0, lexicon_top), np.int32), np.zeros((0, lexicon_top), np.float32))
+                return head + self.recognition_lexicon()
         if beam is not None:
             bw, k = beam_args(*beam)
             with self._beam_scope((bw, k)):
@@ -624,15 +715,21 @@ class Context:
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
-                 min_area_rect=None, return_scores=False, beam=None):
+                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns
         (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``.
         ``return_scores``: a third element ``(detection list[(n_i,) f32], log_word (M,) f32, char_scores (M,48) f32)``.
         ``beam=(beam_width, top_paths)``: a last element ``(beam labels (M,K,48) int32, beam log_prob (M,K) f32)`` as
-        ``crnn_beam``; boxes, labels and scores are the same bits."""
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam):
+        ``crnn_beam``; boxes, labels and scores are the same bits.  ``lexicon_top=K``: a last element ``(index (M,K) int32,
+        log_prob (M,K) f32)`` as ``crnn_lexicon``."""
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
+                self._lexicon_scope(lexicon_top):
             out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
                                  size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
+            if lexicon_top is not None:
+                if not len(ptrs):
+                    return out + ((np.zeros((0, lexicon_top), np.int32), np.zeros((0, lexicon_top), np.float32)),)
+                return out + (self.recognition_lexicon(),)
             if beam is None:
                 return out
             if not len(ptrs):

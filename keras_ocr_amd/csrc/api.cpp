@@ -14,6 +14,7 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   ctx->last_pl.valid = false;  // whoever sizes an arena is about to overwrite it (kocr_pipeline re-validates at its end)
   ctx->last_sc.clear();        // the resident scores likewise
   ctx->last_beam.clear();      // ... and the resident beam alternatives
+  ctx->last_lex.clear();       // ... and lexicon matches
   if (bytes <= a.cap) return KOCR_OK;
   if (a.base) {
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -330,7 +331,10 @@ int kocr_load_crnn(kocr_ctx* ctx, int n, const char* const* names, const float* 
                    const int64_t* shapes, const int* ranks) {
   if (!ctx || n <= 0 || !names || !data || !shapes || !ranks) return KOCR_EINVAL;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  return crnn_load(ctx, n, names, data, shapes, ranks);
+  KOCR_TRY(crnn_load(ctx, n, names, data, shapes, ranks));
+  // a lexicon's labels were validated against the class count of the recogniser it was loaded under
+  if (ctx->lex.V && ctx->lex.classes != crnn_classes(ctx)) lexicon_unload(ctx, ctx->lex.classes);
+  return KOCR_OK;
 }
 
 int kocr_crnn_classes(kocr_ctx* ctx) { return ctx ? crnn_classes(ctx) : KOCR_EINVAL; }
@@ -434,6 +438,101 @@ int kocr_crnn_beam(kocr_ctx* ctx, const float* crops, int M, int beam_width, int
     KOCR_TRY(crnn_beam(ctx, d_c, nb, bm));
     KOCR_TRY(st.back(labels + s * top_paths * LW, bm.d_labels, lb * nb));
     KOCR_TRY(st.back(log_prob + s * top_paths, bm.d_logp, vb * nb));
+    return st.finish();
+  });
+}
+
+// ---- lexicon (include/kocr.h, "Lexicon") --------------------------------------------------------------------------------
+int kocr_set_lexicon(kocr_ctx* ctx, const int32_t* words, int stride, const int32_t* lengths, int V) {
+  if (!ctx) return KOCR_EINVAL;
+  if (V < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_lexicon: V " + std::to_string(V) + " is negative");
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  if (V == 0) {
+    lexicon_unload(ctx, 0);
+    return KOCR_OK;
+  }
+  if (!words || !lengths || stride < 1) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_lexicon: null buffer or stride < 1");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_set_lexicon: call kocr_load_crnn first (the labels are checked against its classes)");
+  int Lmax = 0;
+  for (int v = 0; v < V; ++v) {
+    const int L = lengths[v];
+    if (L < 1 || L > KOCR_LEXICON_MAX_WORD || L > stride)
+      KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_lexicon: lengths: word " + std::to_string(v) + " has length " + std::to_string(L) +
+                                      " outside [1, min(KOCR_LEXICON_MAX_WORD = " + std::to_string(KOCR_LEXICON_MAX_WORD) +
+                                      ", stride = " + std::to_string(stride) + ")]");
+    for (int i = 0; i < L; ++i) {
+      const int c = words[(size_t)v * stride + i];
+      if (c < 0 || c > C - 2)
+        KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_lexicon: words: word " + std::to_string(v) + ": label " + std::to_string(c) +
+                                        " at position " + std::to_string(i) + " outside [0, " + std::to_string(C - 2) +
+                                        "] (the blank is " + std::to_string(C - 1) + ")");
+    }
+    Lmax = std::max(Lmax, L);
+  }
+  // rows of Lmax labels; the words by ascending length (stable: equal lengths keep the caller's order)
+  std::vector<int32_t> rows((size_t)V * Lmax, -1), order(V);
+  for (int v = 0; v < V; ++v) {
+    std::copy(words + (size_t)v * stride, words + (size_t)v * stride + lengths[v], rows.begin() + (size_t)v * Lmax);
+    order[v] = v;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lengths[a] < lengths[b]; });
+  lexicon_unload(ctx, 0);
+  auto& lex = ctx->lex;
+  auto put = [&](int** d, const int32_t* h, size_t n) -> int {
+    KOCR_TRY(ctx->dev_alloc((void**)d, n * sizeof(int32_t)));
+    KOCR_HIP(ctx, hipMemcpyAsync(*d, h, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return KOCR_OK;
+  };
+  int rc = put(&lex.d_words, rows.data(), rows.size());
+  if (rc == KOCR_OK) rc = put(&lex.d_lens, lengths, V);
+  if (rc == KOCR_OK) rc = put(&lex.d_order, order.data(), V);
+  hipStreamSynchronize(ctx->stream);  // the host vectors go out of scope
+  if (rc != KOCR_OK) {
+    lexicon_unload(ctx, 0);
+    return rc;
+  }
+  lex.V = V;
+  lex.Lmax = Lmax;
+  lex.classes = C;
+  return KOCR_OK;
+}
+
+int kocr_lexicon_size(const kocr_ctx* ctx) { return ctx ? ctx->lex.V : KOCR_EINVAL; }
+
+int kocr_set_lexicon_scratch(kocr_ctx* ctx, uint64_t bytes) {
+  if (!ctx) return KOCR_EINVAL;
+  ctx->lex_scratch = bytes ? (size_t)bytes : kocr_ctx::LEX_SCRATCH_DEFAULT;
+  return KOCR_OK;
+}
+
+// The lexicon match of include/kocr.h ("Lexicon") alone: the forward up to fc_12, then the three lexicon launches
+int kocr_crnn_lexicon(kocr_ctx* ctx, const float* crops, int M, int top_words, int32_t* index, float* log_prob, float* all_values,
+                      int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (top_words < 1 || top_words > 64) KOCR_TRY(lexicon_validate(ctx, "kocr_crnn_lexicon", top_words));
+  if (M < 0 || (M > 0 && (!crops || !index || !log_prob))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_lexicon: null buffer");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_lexicon: call kocr_load_crnn first");
+  KOCR_TRY(lexicon_validate(ctx, "kocr_crnn_lexicon", top_words));
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = crnn_batch(M), V = ctx->lex.V;
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), ib = top_words * sizeof(int32_t), vb = top_words * sizeof(float);
+  const size_t ab = all_values ? (size_t)V * sizeof(float) : 0;
+  Staging st{ctx, ctx->ws, "kocr_crnn_lexicon", on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C) + lexicon_workspace_bytes(ctx, mb, !all_values), {cb * mb, ib * mb, vb * mb, ab * mb}));
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    const float* d_c;
+    CrnnLexicon lx{top_words, nullptr, nullptr, nullptr};
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(index + s * top_words, ib * nb, lx.d_index));
+    KOCR_TRY(st.out(log_prob + s * top_words, vb * nb, lx.d_logp));
+    if (all_values) KOCR_TRY(st.out(all_values + (size_t)s * V, ab * nb, lx.d_all));
+    KOCR_TRY(crnn_lexicon(ctx, d_c, nb, lx));
+    KOCR_TRY(st.back(index + s * top_words, lx.d_index, ib * nb));
+    KOCR_TRY(st.back(log_prob + s * top_words, lx.d_logp, vb * nb));
+    if (all_values) KOCR_TRY(st.back(all_values + (size_t)s * V, lx.d_all, ab * nb));
     return st.finish();
   });
 }
@@ -951,6 +1050,19 @@ int kocr_get_beam(const kocr_ctx* ctx, int* beam_width, int* top_paths) {
   if (!ctx) return KOCR_EINVAL;
   if (beam_width) *beam_width = ctx->beam_width;
   if (top_paths) *top_paths = ctx->beam_top_paths;
+  return KOCR_OK;
+}
+
+int kocr_set_lexicon_match(kocr_ctx* ctx, int top_words) {
+  if (!ctx) return KOCR_EINVAL;
+  if (top_words != 0) KOCR_TRY(lexicon_validate(ctx, "kocr_set_lexicon_match", top_words));
+  ctx->lex_top = top_words;
+  return KOCR_OK;
+}
+
+int kocr_get_lexicon_match(const kocr_ctx* ctx, int* top_words) {
+  if (!ctx) return KOCR_EINVAL;
+  if (top_words) *top_words = ctx->lex_top;
   return KOCR_OK;
 }
 

@@ -236,10 +236,37 @@ struct kocr_ctx {
   void keep_beams(const int* d_labels, const float* d_logp, int M, int lw) {
     last_beam = {d_labels, d_logp, M, lw, beam_top_paths, beam_width > 0, beam_width == 0};
   }
+  // lexicon (kocr_set_lexicon / kocr_set_lexicon_match; DESIGN.md section 4, "Lexicon"): the caller's words, resident like
+  // weights -- label rows and lengths in the caller's order, `order` the words by ascending length (what a wave of
+  // lexicon_score_kernel walks).  classes: the recogniser's class count the labels were validated against; dropped_classes:
+  // that count of a lexicon that loading another recogniser unloaded (for the refusal's text).  With lex_top > 0 (only
+  // while a lexicon is loaded) kocr_recognize_boxes / kocr_pipeline also run the three lexicon launches on every batch's
+  // logits and leave index / log_prob resident beside the label rows for kocr_recognition_lexicon.  Valid like last_beam.
+  // lex_scratch: the bytes of the M x V value scratch one chunk of crops may take (kocr_set_lexicon_scratch).
+  struct Lexicon {
+    int* d_words = nullptr;  // [V][Lmax]
+    int* d_lens = nullptr;   // [V]
+    int* d_order = nullptr;  // [V]
+    int V = 0, Lmax = 0, classes = 0, dropped_classes = 0;
+  } lex;
+  int lex_top = 0;
+  static constexpr size_t LEX_SCRATCH_DEFAULT = (size_t)256 << 20;
+  size_t lex_scratch = LEX_SCRATCH_DEFAULT;
+  struct LastLexicon {
+    const int* d_index = nullptr;   // [M][K]
+    const float* d_logp = nullptr;  // [M][K]
+    int M = 0, K = 0;
+    bool valid = false, off = false;  // off: results were produced with the match off
+    void clear() { valid = off = false; }
+  } last_lex;
+  void keep_lexicon(const int* d_index, const float* d_logp, int M) {
+    last_lex = {d_index, d_logp, M, lex_top, lex_top > 0, lex_top == 0};
+  }
   void invalidate_results() {
     last_pl.valid = false;
     last_sc.clear();
     last_beam.clear();
+    last_lex.clear();
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
@@ -472,9 +499,27 @@ struct CrnnBeam {
   int* d_labels;
   float* d_logp;
 };
+// lx (CRNN_DECODE only): after the decode (and the beam), the three lexicon launches on the same logits: d_index / d_logp
+// [M][top_words]; d_all (nullable) [M][V]: lexicon_score_kernel's own values, else they live in workspace scratch.
+struct CrnnLexicon {
+  int top_words;
+  int* d_index;
+  float* d_logp;
+  float* d_all;
+};
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
                  float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr,
-                 const CrnnBeam* bm = nullptr);
+                 const CrnnBeam* bm = nullptr, const CrnnLexicon* lx = nullptr);
+// crnn_forward to the logits, then the lexicon launches alone (kocr_crnn_lexicon)
+int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx);
+// Crops per chunk of the lexicon launches: as many as lex_scratch bytes of values hold, clamp(lex_scratch / (4 V), 1, M);
+// and the workspace bytes the launches take on top of crnn_workspace_bytes(M) (own_values: no d_all buffer is given)
+int lexicon_chunk(const kocr_ctx* ctx, int M);
+size_t lexicon_workspace_bytes(kocr_ctx* ctx, int M, bool own_values);
+// KOCR_EINVAL naming the argument unless 1 <= top_words <= 64; and unless a lexicon is loaded (saying why not)
+int lexicon_validate(kocr_ctx* ctx, const char* fn, int top_words);
+// the device copies freed, V = 0, the match switched off; dropped_classes as given
+void lexicon_unload(kocr_ctx* ctx, int dropped_classes);
 // crnn_forward to the logits, then ctc_beam_kernel alone (kocr_crnn_beam)
 int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm);
 // KOCR_EINVAL naming the argument unless 1 <= beam_width <= 64 and 1 <= top_paths <= beam_width

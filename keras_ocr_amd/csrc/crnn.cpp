@@ -36,6 +36,12 @@ int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C,
 int launch_ctc_beam(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int beam_width, int top_paths,
                     int* d_labels, float* d_logp);
 
+int launch_lexicon_logq(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, float* d_lq);
+int launch_lexicon_score(kocr_ctx* ctx, const float* d_lq, int M, int To, int C, const int* d_words, int wstride, const int* d_lens,
+                         const int* d_order, int V, int Lmax, float* d_values);
+int launch_lexicon_select(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, const float* d_values, int V,
+                          const int* d_words, int wstride, const int* d_lens, int top_words, int* d_index, float* d_logp);
+
 struct CrnnNet {
   std::map<std::string, ConvLayer> L;
   float* U[4] = {nullptr, nullptr, nullptr, nullptr};  // recurrent kernels 10, 10_back, 11, 11_back
@@ -217,10 +223,43 @@ size_t crnn_workspace_bytes(int M, int n_classes) {
   return t + 8192;
 }
 
+// The chunking rule of the lexicon launches (common.h): a chunk's crops share one table / value scratch; a crop's result does
+// not depend on the chunk it falls into (nothing is shared between crops).
+int lexicon_chunk(const kocr_ctx* ctx, int M) {
+  const size_t per_crop = (size_t)std::max(ctx->lex.V, 1) * sizeof(float);
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(M, 1), ctx->lex_scratch / per_crop));
+}
+
+size_t lexicon_workspace_bytes(kocr_ctx* ctx, int M, bool own_values) {
+  const size_t chunk = (size_t)lexicon_chunk(ctx, M);
+  return chunk * T * (size_t)std::max(crnn_classes(ctx), 1) * sizeof(float) + (own_values ? chunk * ctx->lex.V * sizeof(float) : 0) + 1024;
+}
+
+// lexicon_logq, lexicon_score, lexicon_select on the logits [M][T][C] of a batch, chunk by chunk
+static int lexicon_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnLexicon& lx) {
+  const auto& lex = ctx->lex;
+  const int C = ctx->crnn->n_classes, discard = ctx->crnn->discard, To = T - discard, V = lex.V;
+  if (V <= 0 || lex.classes != C) KOCR_FAIL(ctx, KOCR_EINVAL, "lexicon: no lexicon loaded for this recogniser's class count");
+  const int chunk = lexicon_chunk(ctx, M);
+  float* d_lq = (float*)ctx->ws_alloc((size_t)chunk * To * C * sizeof(float));
+  float* d_vals = lx.d_all ? nullptr : (float*)ctx->ws_alloc((size_t)chunk * V * sizeof(float));
+  if (!d_lq || (!lx.d_all && !d_vals)) KOCR_FAIL(ctx, KOCR_ENOMEM, "lexicon: workspace exhausted");
+  for (int c0 = 0; c0 < M; c0 += chunk) {
+    const int nc = std::min(chunk, M - c0);
+    const float* lg = d_lg + (size_t)c0 * T * C;
+    float* vals = lx.d_all ? lx.d_all + (size_t)c0 * V : d_vals;
+    KOCR_TRY(launch_lexicon_logq(ctx, lg, nc, T, C, discard, d_lq));
+    KOCR_TRY(launch_lexicon_score(ctx, d_lq, nc, To, C, lex.d_words, lex.Lmax, lex.d_lens, lex.d_order, V, lex.Lmax, vals));
+    KOCR_TRY(launch_lexicon_select(ctx, lg, nc, T, C, discard, vals, V, lex.d_words, lex.Lmax, lex.d_lens, lx.top_words,
+                                   lx.d_index + (size_t)c0 * lx.top_words, lx.d_logp + (size_t)c0 * lx.top_words));
+  }
+  return KOCR_OK;
+}
+
 // d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
-// `stop` / d_feats / d_logits / sc / bm: common.h
+// `stop` / d_feats / d_logits / sc / bm / lx: common.h
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
-                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm) {
+                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm, const CrnnLexicon* lx) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -427,7 +466,37 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   }));
   if (bm)
     KOCR_TRY(launch_ctc_beam(ctx, lg.p, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp));
+  if (lx) KOCR_TRY(lexicon_run(ctx, lg.p, M, *lx));
   return KOCR_OK;
+}
+
+int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx) {
+  const float* d_lg = nullptr;
+  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
+  if (M <= 0) return KOCR_OK;
+  return lexicon_run(ctx, d_lg, M, lx);
+}
+
+int lexicon_validate(kocr_ctx* ctx, const char* fn, int top_words) {
+  if (top_words < 1 || top_words > 64)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": top_words " + std::to_string(top_words) + " outside [1, 64]");
+  if (ctx->lex.V == 0 && ctx->lex.dropped_classes)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": the lexicon was loaded for a recogniser of " +
+                                    std::to_string(ctx->lex.dropped_classes) + " classes and was unloaded when one of " +
+                                    std::to_string(crnn_classes(ctx)) + " classes was loaded (class count mismatch): call "
+                                    "kocr_set_lexicon again");
+  if (ctx->lex.V == 0) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": no lexicon is loaded (kocr_set_lexicon first)");
+  return KOCR_OK;
+}
+
+void lexicon_unload(kocr_ctx* ctx, int dropped_classes) {
+  hipStreamSynchronize(ctx->stream);  // no launch still reads the words
+  ctx->release(ctx->lex.d_words);
+  ctx->release(ctx->lex.d_lens);
+  ctx->release(ctx->lex.d_order);
+  ctx->lex = kocr_ctx::Lexicon{};
+  ctx->lex.dropped_classes = dropped_classes;
+  ctx->lex_top = 0;
 }
 
 int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm) {

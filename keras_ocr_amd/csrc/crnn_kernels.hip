@@ -939,3 +939,205 @@ int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, 
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }
+
+// ---- lexicon ("Lexicon"): which of the caller's V words is this crop?  value[m][v] = the exact CTC
+// log-probability of word v given crop m, -kocr_crnn_ctc_loss, for every pair; three launches per chunk of crops.
+//   lexicon_logq_kernel    per (crop, frame) one wave: the To x C table lq_t(c) = logf(ctc_softmax(..) + CTC_EPS) - logz, the
+//                          very expressions of ctc_loss_wave<true>, computed ONCE per crop instead of once per pair
+//   lexicon_score_kernel   the forward algorithm of every (crop, word) pair, one LANE per word
+//   lexicon_select_kernel  per crop the top_words best values, each rescored by ctc_loss_wave<true>
+// The recursion stays in float32 LOG space, state by state the arithmetic of ctc_loss_wave (ctc_lse3 + lq, the same masks):
+// a linear-domain recursion with a per-frame rescale loses the states that lie more than 2^-149 below the frame's largest,
+// and on a peaked network (q of a wrong class at the 1e-7 floor) a word that disagrees with the crop in six or more
+// letters carries its surviving paths through exactly such states until the end mask forces them forward.
+// A lane keeps log(alpha) of its word's 2L + 1 states and the L labels in its own LDS row of R = (3 Lmax + 1) | 1 words (odd:
+// the lanes of a wave touching the same state hit different banks) and updates alpha IN PLACE from the highest live state
+// down: new[s] needs old[s], old[s-1], old[s-2] only, carried in three registers, so a state costs one LDS read, one LDS
+// write and, at odd s, the gather lq_t(label).  TAB_LDS: the crop's table is copied into LDS (To x C floats: 7.1 KB for 37
+// classes) and the gather is an LDS read; when table + rows exceed 64 KB (a 1000-class alphabet: 192 KB) the gather reads
+// the table from global memory, i.e. L2 / the vector cache.  The launcher sorts nothing: `order` (host-made at load time)
+// lists the words by ascending length, so the 64 words of a wave run the same trip count; results land in the CALLER's order.
+// Nothing is shared between crops and every order of evaluation is fixed: a crop's values are the same bits in any batch.
+constexpr int LEX_BLOCK = 128;  // words (= lanes) per workgroup of lexicon_score_kernel, all of one crop
+
+__global__ __launch_bounds__(64) void lexicon_logq_kernel(const float* __restrict__ logits, int T, int C, int discard,
+                                                          float* __restrict__ lq) {
+  const int To = T - discard, m = blockIdx.x / To, t = blockIdx.x % To, lane = threadIdx.x;
+  const float* row = logits + ((size_t)m * T + discard + t) * C;
+  float mx;
+  int bi;
+  ctc_row_argmax(row, C, lane, mx, bi);
+  const float es = ctc_row_expsum(row, C, lane, mx);
+  float z = 0.f;
+  for (int c = lane; c < C; c += 64) z += ctc_softmax(row[c], mx, es) + CTC_EPS;
+  for (int o = 32; o; o >>= 1) z += __shfl_xor(z, o);
+  const float logz = logf(z);
+  float* out = lq + ((size_t)m * To + t) * C;
+  for (int c = lane; c < C; c += 64) out[c] = logf(ctc_softmax(row[c], mx, es) + CTC_EPS) - logz;
+}
+
+// lq: [Mc][To][C]; words: [V][wstride] / lens: [V] in the caller's order; order: [V] sorted position -> caller index;
+// values: [Mc][V] in the caller's order.  Grid (ceil(V / LEX_BLOCK), Mc).  LDS: TAB_LDS ? To * C : 0 floats, then LEX_BLOCK * R.
+template <bool TAB_LDS>
+__global__ __launch_bounds__(LEX_BLOCK) void lexicon_score_kernel(const float* __restrict__ lq, int To, int C,
+                                                                  const int* __restrict__ words, int wstride,
+                                                                  const int* __restrict__ lens, const int* __restrict__ order,
+                                                                  int V, int Lmax, int R, float* __restrict__ values) {
+  extern __shared__ float lex_lds[];
+  const int m = blockIdx.y, j = blockIdx.x * LEX_BLOCK + threadIdx.x;
+  const float* lqm = lq + (size_t)m * To * C;
+  if (TAB_LDS)
+    for (int i = threadIdx.x; i < To * C; i += LEX_BLOCK) lex_lds[i] = lqm[i];
+  float* A = lex_lds + (TAB_LDS ? To * C : 0) + (size_t)threadIdx.x * R;  // [2 Lmax + 1] log alpha
+  int* Lb = reinterpret_cast<int*>(A + 2 * Lmax + 1);                      // [Lmax] the word
+  int w = 0, L = 0;
+  if (j < V) {
+    w = order[j];
+    L = lens[w];
+    for (int i = 0; i < L; ++i) Lb[i] = words[(size_t)w * wstride + i];
+  }
+  __syncthreads();
+  if (j >= V) return;
+  auto Q = [&](int i) { return TAB_LDS ? lex_lds[i] : lqm[i]; };
+  const int S = 2 * L + 1, blank = C - 1;
+  for (int s = 0; s < S; ++s) A[s] = -INFINITY;
+  for (int t = 0; t < To; ++t) {
+    // ctc_loss_wave's masks: s > 2t + 1 cannot be reached yet, s < S - 2 (To - t) can no longer reach the end
+    const int lo = max(0, S - 2 * (To - t)), hi = min(S - 1, 2 * t + 1);
+    const float lqb = Q(t * C + blank);
+    if (t == 0) {
+      for (int s = lo; s <= hi; ++s) A[s] = (s & 1) ? Q(Lb[0]) : lqb;  // hi <= 1
+      continue;
+    }
+    float c0 = A[hi], c1 = hi >= 1 ? A[hi - 1] : -INFINITY;  // old[s], old[s - 1]
+    for (int s = hi; s >= lo; --s) {
+      const float c2 = s >= 2 ? A[s - 2] : -INFINITY;
+      float a2 = -INFINITY, lqs = lqb;
+      if (s & 1) {
+        const int k = s >> 1, lab = Lb[k];
+        lqs = Q(t * C + lab);
+        if (k >= 1 && lab != Lb[k - 1]) a2 = c2;
+      }
+      A[s] = ctc_lse3(c0, c1, a2) + lqs;
+      c0 = c1;
+      c1 = c2;
+    }
+    if (lo >= 1) A[lo - 1] = -INFINITY;
+    if (lo >= 2) A[lo - 2] = -INFINITY;
+  }
+  const float a = A[S - 1], b = A[S - 2];  // L >= 1
+  const float mxv = fmaxf(a, b);
+  values[(size_t)m * V + w] = mxv == -INFINITY ? -INFINITY : mxv + logf(expf(a - mxv) + expf(b - mxv));
+}
+
+// One wave (= one workgroup) per crop.  K rounds of "the largest value behind the last pick" over the crop's V values (the
+// higher value first, then the smaller index; -inf is never picked), then ctc_loss_wave<true> on each pick -- log_prob is,
+// bit for bit, -kocr_crnn_ctc_loss of the crop with that word -- and the rows in the order of the rescored value (same tie
+// rule); behind them index -1, log_prob -inf.  LDS: the loss's la [2][Sp], then val [64], idx [64].
+__global__ __launch_bounds__(64) void lexicon_select_kernel(const float* __restrict__ logits, int T, int C, int discard,
+                                                            const float* __restrict__ values, int V, const int* __restrict__ words,
+                                                            int wstride, const int* __restrict__ lens, int K,
+                                                            int* __restrict__ index, float* __restrict__ logp, int Sp) {
+  extern __shared__ float la[];
+  float* val = la + 2 * Sp;
+  int* idx = reinterpret_cast<int*>(val + 64);
+  const int m = blockIdx.x, lane = threadIdx.x, To = T - discard;
+  const float* y0 = logits + ((size_t)m * T + discard) * C;
+  const float* v = values + (size_t)m * V;
+  float pv = INFINITY;
+  int pi = -1, n = 0;
+  for (; n < K; ++n) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+      const float x = v[i];
+      if ((x < pv || (x == pv && i > pi)) && x > bv) {  // ascending i: the first maximum of a lane wins
+        bv = x;
+        bi = i;
+      }
+    }
+    for (int o = 32; o; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if (bv == -INFINITY) break;  // uniform: fewer than K feasible words
+    pv = bv;
+    pi = bi;
+    if (lane == 0) idx[n] = bi;
+  }
+  __syncthreads();
+  float lp = -INFINITY;
+  int mine = -1;
+  for (int k = 0; k < n; ++k) {
+    const int w = idx[k];
+    const float loss = ctc_loss_wave<true>(y0, C, words + (size_t)w * wstride, lens[w], To, la, Sp, lane);
+    if (lane == k) {
+      lp = -loss;
+      mine = w;
+    }
+  }
+  __syncthreads();
+  val[lane] = lp;
+  __syncthreads();
+  if (lane < K) {
+    int rank = lane;
+    if (lane < n) {
+      rank = 0;
+      for (int j = 0; j < n; ++j) {
+        if (j == lane) continue;
+        const float vj = val[j];
+        rank += (vj > lp || (vj == lp && idx[j] < mine)) ? 1 : 0;
+      }
+    }
+    index[(size_t)m * K + rank] = mine;
+    logp[(size_t)m * K + rank] = lp;
+  }
+}
+
+// d_lq: [M][T - discard][C] scratch
+int launch_lexicon_logq(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, float* d_lq) {
+  if (M <= 0) return KOCR_OK;
+  ProfScope ps(ctx, "lexicon_logq", 0, 4.0 * M * (T - discard) * C * 2);
+  hipLaunchKernelGGL(lexicon_logq_kernel, dim3(M * (T - discard)), dim3(64), 0, ctx->stream, d_logits, T, C, discard, d_lq);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// d_values: [M][V], the caller's word order
+int launch_lexicon_score(kocr_ctx* ctx, const float* d_lq, int M, int To, int C, const int* d_words, int wstride, const int* d_lens,
+                         const int* d_order, int V, int Lmax, float* d_values) {
+  if (M <= 0 || V <= 0) return KOCR_OK;
+  if (Lmax < 1 || Lmax > KOCR_LEXICON_MAX_WORD || To < 1 || C < 2) KOCR_FAIL(ctx, KOCR_EINVAL, "lexicon_score: bad sizes");
+  const int R = (3 * Lmax + 1) | 1;
+  const size_t rows = (size_t)LEX_BLOCK * R * sizeof(float), tab = (size_t)To * C * sizeof(float);
+  const bool tab_lds = rows + tab <= 64 * 1024;
+  const dim3 grid((V + LEX_BLOCK - 1) / LEX_BLOCK, M);
+  // per pair To frames of about 2L + 1 states, each three expf, a logf and some twenty other operations
+  ProfScope ps(ctx, "lexicon_score", 30.0 * M * V * To * (Lmax + 1), 4.0 * M * V);
+  if (tab_lds)
+    hipLaunchKernelGGL(lexicon_score_kernel<true>, grid, dim3(LEX_BLOCK), rows + tab, ctx->stream, d_lq, To, C, d_words, wstride,
+                       d_lens, d_order, V, Lmax, R, d_values);
+  else
+    hipLaunchKernelGGL(lexicon_score_kernel<false>, grid, dim3(LEX_BLOCK), rows, ctx->stream, d_lq, To, C, d_words, wstride, d_lens,
+                       d_order, V, Lmax, R, d_values);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// d_index / d_logp: [M][top_words]
+int launch_lexicon_select(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, const float* d_values, int V,
+                          const int* d_words, int wstride, const int* d_lens, int top_words, int* d_index, float* d_logp) {
+  if (M <= 0) return KOCR_OK;
+  if (top_words < 1 || top_words > 64 || V < 1) KOCR_FAIL(ctx, KOCR_EINVAL, "lexicon_select: bad sizes");
+  const int Sp = (2 * KOCR_LEXICON_MAX_WORD + 1 + 63) & ~63;
+  const size_t lds = (size_t)2 * Sp * sizeof(float) + 64 * sizeof(float) + 64 * sizeof(int);
+  ProfScope ps(ctx, "lexicon_select", 0, 4.0 * M * V * top_words);
+  hipLaunchKernelGGL(lexicon_select_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_values, V, d_words,
+                     wstride, d_lens, top_words, d_index, d_logp, Sp);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}

@@ -87,8 +87,10 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
   const size_t lw_b = scores ? (size_t)M * sizeof(float) : 0, ch_b = lw_b * LW;
   const int BW = ctx->beam_width, BK = ctx->beam_top_paths;
   const size_t bl_b = BW ? (size_t)M * BK * LW * sizeof(int32_t) : 0, bv_b = BW ? (size_t)M * BK * sizeof(float) : 0;
+  const int LK = ctx->lex_top;
+  const size_t li_b = LK ? (size_t)M * LK * sizeof(int32_t) : 0, lv_b = LK ? (size_t)M * LK * sizeof(float) : 0;
   Staging st{ctx, ctx->io, "kocr_recognize_boxes", on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, lab_b, lw_b, ch_b, bl_b, bv_b}));
+  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, lab_b, lw_b, ch_b, bl_b, bv_b, li_b, lv_b}));
   const WarpParam* d_prm;
   float* d_crops;
   int32_t* d_lab;
@@ -106,20 +108,27 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
     KOCR_TRY(st.scratch(bl_b, bm.d_labels));
     KOCR_TRY(st.scratch(bv_b, bm.d_logp));
   }
+  CrnnLexicon lx{LK, nullptr, nullptr, nullptr};
+  if (LK) {
+    KOCR_TRY(st.scratch(li_b, lx.d_index));
+    KOCR_TRY(st.scratch(lv_b, lx.d_logp));
+  }
   KOCR_TRY(st.in(img_rgb, ib, d_img));
   KOCR_TRY(st.put((WarpParam*)d_prm, prm.data(), pb));
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), C)));
+  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), C) + (LK ? lexicon_workspace_bytes(ctx, crnn_batch(M), true) : 0)));
   KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
     const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
     const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
+    const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
     return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
-                        scores ? &part : nullptr, BW ? &bpart : nullptr);
+                        scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr);
   }));
   KOCR_TRY(st.download(labels, d_lab, lab_b));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->keep_rec_scores(sc.d_logw, sc.d_chars, (int)M, LW);
   ctx->keep_beams(bm.d_labels, bm.d_logp, (int)M, LW);
+  ctx->keep_lexicon(lx.d_index, lx.d_logp, (int)M);
   return KOCR_OK;
 }
 
@@ -223,6 +232,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     ctx->keep_det_scores(dv.d_scores, N, d_cap);
     ctx->keep_rec_scores(nullptr, nullptr, 0, crnn_label_width(ctx));
     ctx->keep_beams(nullptr, nullptr, 0, crnn_label_width(ctx));
+    ctx->keep_lexicon(nullptr, nullptr, 0);
     return KOCR_OK;
   }
   if (!labels && d_cap == cap) {
@@ -237,7 +247,9 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   const size_t lw_b = scores ? (size_t)M * sizeof(float) : 0, ch_b = lw_b * LW;
   const int BW = ctx->beam_width, BK = ctx->beam_top_paths;
   const size_t bl_b = BW ? (size_t)M * BK * LW * sizeof(int32_t) : 0, bv_b = BW ? (size_t)M * BK * sizeof(float) : 0;
-  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, lab_b, 256, lw_b, ch_b, bl_b, bv_b}));
+  const int LK = ctx->lex_top;
+  const size_t li_b = LK ? (size_t)M * LK * sizeof(int32_t) : 0, lv_b = LK ? (size_t)M * LK * sizeof(float) : 0;
+  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, lab_b, 256, lw_b, ch_b, bl_b, bv_b, li_b, lv_b}));
   WarpParam* d_prm;
   float* d_crops;
   int32_t* d_lab;
@@ -256,16 +268,23 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     KOCR_TRY(io.scratch(bl_b, bm.d_labels));
     KOCR_TRY(io.scratch(bv_b, bm.d_logp));
   }
+  CrnnLexicon lx{LK, nullptr, nullptr, nullptr};
+  if (LK) {
+    KOCR_TRY(io.scratch(li_b, lx.d_index));
+    KOCR_TRY(io.scratch(lv_b, lx.d_logp));
+  }
   KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), ctx->stream));
   KOCR_TRY(launch_warp_prepare(ctx, d_boxes, dv.d_counts, N, d_cap, CRNN_CROP_H, CRNN_CROP_W, d_prm, d_status));
   KOCR_TRY(launch_warp(ctx, d_bat, Hmax, Wmax, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   // ---- recogniser ----
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), crnn_classes(ctx))));
+  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), crnn_classes(ctx)) +
+                           (LK ? lexicon_workspace_bytes(ctx, crnn_batch(M), true) : 0)));
   KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
     const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
     const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
+    const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
     return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
-                        scores ? &part : nullptr, BW ? &bpart : nullptr);
+                        scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr);
   }));
   if (host_fits) KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, lab_b, hipMemcpyDeviceToHost, ctx->stream));
   KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -274,6 +293,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   ctx->keep_det_scores(dv.d_scores, N, d_cap);
   ctx->keep_rec_scores(sc.d_logw, sc.d_chars, (int)M, LW);
   ctx->keep_beams(bm.d_labels, bm.d_logp, (int)M, LW);
+  ctx->keep_lexicon(lx.d_index, lx.d_logp, (int)M);
   if (!host_fits) {
     ctx->set_err("kocr_pipeline: an image has more boxes than cap, or there are more crops than max_crops; the results are "
                  "resident -- fetch them with kocr_pipeline_results into buffers sized from counts / n_crops");
@@ -363,6 +383,31 @@ extern "C" int kocr_recognition_beams(kocr_ctx* ctx, int32_t* labels, float* log
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   // rows of the width and top_paths they were PRODUCED with
   KOCR_HIP(ctx, hipMemcpyAsync(labels, r.d_labels, (size_t)r.M * r.K * r.lw * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipMemcpyAsync(log_prob, r.d_logp, (size_t)r.M * r.K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KOCR_OK;
+}
+
+// The resident lexicon matches (see include/kocr.h, "Lexicon")
+extern "C" int kocr_recognition_lexicon(kocr_ctx* ctx, int32_t* index, float* log_prob, int max_crops, int32_t* n_crops,
+                                        int32_t* top_words) {
+  if (!ctx) return KOCR_EINVAL;
+  const auto& r = ctx->last_lex;
+  if (r.off)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_lexicon: the results on this context were produced with the lexicon match off "
+                                "(kocr_set_lexicon_match(ctx, top_words) before the call)");
+  if (!r.valid)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_lexicon: no lexicon matches are resident (call it right after "
+                                "kocr_recognize_boxes or kocr_pipeline)");
+  if (n_crops) *n_crops = r.M;
+  if (top_words) *top_words = r.K;
+  if (r.M > 0 && (!index || !log_prob || max_crops < r.M))
+    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_recognition_lexicon: buffers smaller than the resident matches (max_crops >= " +
+                                       std::to_string(r.M) + ")");
+  if (r.M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  // rows of the top_words they were PRODUCED with
+  KOCR_HIP(ctx, hipMemcpyAsync(index, r.d_index, (size_t)r.M * r.K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   KOCR_HIP(ctx, hipMemcpyAsync(log_prob, r.d_logp, (size_t)r.M * r.K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KOCR_OK;

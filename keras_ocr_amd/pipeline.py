@@ -1,7 +1,7 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
 import numpy as np
 
-from . import _lib, detection, recognition, scores as _scores, tools
+from . import _lib, detection, lexicon as _lexicon, recognition, scores as _scores, tools
 
 
 def beam_of(recognition_kwargs):
@@ -11,6 +11,17 @@ def beam_of(recognition_kwargs):
     if kwargs.get("beam_width") is None:
         return None
     return _lib.beam_args(kwargs["beam_width"], kwargs.get("top_paths", 1))
+
+
+def lexicon_of(recognition_kwargs):
+    """``lexicon_top`` from recognize()'s ``recognition_kwargs`` (validated: ValueError naming the argument, or saying that
+    it cannot be combined with ``beam_width``), or None without one."""
+    kwargs = recognition_kwargs or {}
+    if kwargs.get("lexicon_top") is None:
+        return None
+    if kwargs.get("beam_width") is not None:
+        raise ValueError("lexicon_top and beam_width cannot be combined: ask for one of the two")
+    return _lexicon.top_arg(kwargs["lexicon_top"])
 
 
 def decode_labels(alphabet, labels):
@@ -68,7 +79,9 @@ class Pipeline:
 
         ``recognition_kwargs={"beam_width": B, "top_paths": K}`` ("Beam search"): every ``text`` becomes
         a list of up to K alternatives ``(text, log_prob)``, best first, as ``Recognizer.recognize``; the boxes are the same
-        bits.  The other keys of both dicts are Keras predict arguments without effect."""
+        bits.  ``recognition_kwargs={"lexicon_top": K}`` (section 4, "Lexicon"; after ``recognizer.set_lexicon(words)``): every
+        ``text`` becomes a list of up to K ``(word, log_prob)`` lexicon matches, best first.  Not both (ValueError).  The other
+        keys of both dicts are Keras predict arguments without effect."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs)
 
     def recognize_with_scores(self, images, detection_kwargs=None, recognition_kwargs=None):
@@ -93,14 +106,21 @@ class Pipeline:
         crosses ranks in ``dist.ShardedPipeline``.  ``return_scores=True`` adds a third element ``(detection, log_word,
         char_scores)``: per image an (n_i,) float32 array, and (sum n_i,) / (sum n_i, 48) float32 arrays in label-row order.
         With a ``beam_width`` in ``recognition_kwargs`` the result has four elements: the third is the scores or None, the
-        fourth ``(beam labels (sum n_i, K, 48) int32, beam log_prob (sum n_i, K) float32)`` as ``Context.crnn_beam``."""
+        fourth ``(beam labels (sum n_i, K, 48) int32, beam log_prob (sum n_i, K) float32)`` as ``Context.crnn_beam``.  With a
+        ``lexicon_top`` it has five: scores or None, None, ``(index (sum n_i, K) int32, log_prob (sum n_i, K) float32)`` as
+        ``Context.crnn_lexicon``."""
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
+        lexicon_top = lexicon_of(recognition_kwargs)
         beam = beam_of(recognition_kwargs)  # the rest: Keras predict kwargs, no effect on results
+        if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
+            raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         if not images:
             empty = [], np.zeros((0, 48), np.int32)
             scores = ([], np.zeros(0, np.float32), np.zeros((0, 48), np.float32)) if return_scores else None
+            if lexicon_top:
+                return empty + (scores, None, (np.zeros((0, lexicon_top), np.int32), np.zeros((0, lexicon_top), np.float32)))
             if beam:
                 return empty + (scores, (np.zeros((0, beam[1], 48), np.int32), np.zeros((0, beam[1]), np.float32)))
             return empty + (scores,) if return_scores else empty
@@ -111,22 +131,24 @@ class Pipeline:
             # the stage-wise path does the same with the float kernels (kocr_resize_pad_f32 / kocr_warp_crops_f32, round 5) --
             # off the fused fixed-point path, which is defined for uint8 pixels only
             return self._recognize_stagewise([im.astype(np.float32) for im in images], detection_kwargs, hmax, wmax, return_scores,
-                                             beam)
+                                             beam, lexicon_top)
         if ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx:
             # duck-typed / separately-placed stages: the reference's stage-wise path (pipeline.py:44-75)
-            return self._recognize_stagewise(images, detection_kwargs, hmax, wmax, return_scores, beam)
+            return self._recognize_stagewise(images, detection_kwargs, hmax, wmax, return_scores, beam, lexicon_top)
         scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
         hmax = hmax_ if hmax is None else max(hmax, hmax_)
         wmax = wmax_ if wmax is None else max(wmax, wmax_)
         micro_batch = detection_kwargs.pop("batch_size", 0) or 0
         box_groups, *rest = ctx.pipeline(
             images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, hmax, wmax,
-            micro_batch=micro_batch, return_scores=return_scores, beam=beam, **detection_kwargs)
-        if beam and not return_scores:
+            micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top, **detection_kwargs)
+        if (beam or lexicon_top) and not return_scores:
             rest.insert(1, None)
+        if lexicon_top:
+            rest.insert(2, None)
         return (self._adjust(box_groups, scales), *rest)
 
-    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None):
+    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size)."""
@@ -162,14 +184,24 @@ class Pipeline:
                 for k, (t, log_prob) in enumerate(alternatives):
                     beam_rows[0][r, k, :len(t)] = [alphabet.index(ch) for ch in t]
                     beam_rows[1][r, k] = log_prob
+        if lexicon_top:
+            # likewise a second recogniser call; the words go back to their indices in the recogniser's lexicon
+            where = {word: v for v, word in enumerate(self.recognizer.lexicon.words)}
+            lexicon_rows = (np.full((len(rows), lexicon_top), -1, np.int32), np.full((len(rows), lexicon_top), -np.inf, np.float32))
+            matched = self.recognizer.recognize_from_boxes(images=padded, box_groups=box_groups, lexicon_top=lexicon_top)
+            for r, matches in enumerate(m for group in matched for m in group):
+                for k, (word, log_prob) in enumerate(matches):
+                    lexicon_rows[0][r, k] = where[word]
+                    lexicon_rows[1][r, k] = log_prob
         if return_scores:
             chars = np.zeros(labels.shape, np.float32)
             for r, (_, score) in enumerate(pairs):
                 chars[r, :len(score.characters)] = score.characters
             log_word = np.array([score.log_word for _, score in pairs], np.float32)
             score_rows = ([np.asarray(d, np.float32) for d in det], log_word, chars)
-            return (self._adjust(box_groups, scales), labels, score_rows) + ((beam_rows,) if beam else ())
-        return (self._adjust(box_groups, scales), labels) + ((None, beam_rows) if beam else ())
+            return (self._adjust(box_groups, scales), labels, score_rows) + ((beam_rows,) if beam else ()) + \
+                ((None, lexicon_rows) if lexicon_top else ())
+        return (self._adjust(box_groups, scales), labels) + ((None, beam_rows) if beam else ()) + ((None, None, lexicon_rows) if lexicon_top else ())
 
     def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None, return_scores=False):
         """Same as recognize() for a batch already resident in HBM: ``d_ptr`` = device pointer of an
@@ -202,12 +234,17 @@ class Pipeline:
             for boxes, scale in zip(box_groups, scales)
         ]
 
-    def assemble(self, box_groups, labels, score_rows=None, beam_rows=None):
+    def assemble(self, box_groups, labels, score_rows=None, beam_rows=None, lexicon_rows=None):
         """(box_groups, label rows) -> the reference's return value (pipeline.py:72-75); with ``score_rows`` (recognize_raw's
         third element) every tuple gets its ``scores.Score``; with ``beam_rows`` (its fourth) the texts are replaced by
-        their lists of ``(text, log_prob)`` alternatives."""
+        their lists of ``(text, log_prob)`` alternatives; with ``lexicon_rows`` (its fifth) by their lists of ``(word,
+        log_prob)`` matches, the words looked up in ``recognizer.lexicon.words``."""
         # recognition.py:527-534: label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding
-        if beam_rows is not None:
+        if lexicon_rows is not None:
+            words = self.recognizer.lexicon.words
+            predictions = [[(words[i], float(v)) for i, v in zip(row, vals) if i >= 0]
+                           for row, vals in zip(np.asarray(lexicon_rows[0]).tolist(), np.asarray(lexicon_rows[1]))]
+        elif beam_rows is not None:
             beam_labels, beam_log_prob = np.asarray(beam_rows[0]), np.asarray(beam_rows[1])
             m, k = beam_log_prob.shape
             texts = decode_labels(self.recognizer.alphabet, beam_labels.reshape(m * k, -1)) if m * k else []

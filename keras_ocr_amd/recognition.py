@@ -5,7 +5,7 @@ import typing
 
 import numpy as np
 
-from . import _lib, scores as _scores, tools, weights as _weights
+from . import _lib, lexicon as _lexicon, scores as _scores, tools, weights as _weights
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
     "height": 31,
@@ -279,6 +279,44 @@ class Recognizer:
         self.prediction_model = _Model(self._ctx, probs=False)
         self.backbone = _Backbone(self._ctx)
         self.training_model = _TrainingModel(self._ctx)
+        self.lexicon = None
+
+    def set_lexicon(self, words, lowercase=False):
+        """The word list for ``lexicon_top=`` ("Lexicon"): an iterable of strings or a
+        ``lexicon.Lexicon`` built with this recogniser's alphabet; it is loaded into the context once and stays there like
+        weights.  ``None`` unloads.  ValueError naming the word for one the alphabet cannot spell, an empty or an over-long
+        one; naming the class counts for a Lexicon of another alphabet."""
+        if words is None:
+            self._ctx.set_lexicon(None)
+            self.lexicon = None
+            return
+        lex = words if isinstance(words, _lexicon.Lexicon) else _lexicon.Lexicon(words, self.alphabet, lowercase=lowercase)
+        if lex.classes != len(self.alphabet) + 1 or lex.alphabet != self.alphabet:
+            raise ValueError(f"the lexicon was built for an alphabet of {lex.classes} classes (blank included), the recogniser "
+                             f"has {len(self.alphabet) + 1}: class count / alphabet mismatch")
+        if not len(lex):
+            raise ValueError("the lexicon has no words")
+        self._ctx.set_lexicon(lex.labels, lex.lengths)
+        self.lexicon = lex
+
+    def _lexicon_top(self, lexicon_top, beam_width):
+        """``lexicon_top`` validated (None stays None): ValueError naming the argument, without a loaded lexicon, or together
+        with ``beam_width``."""
+        if lexicon_top is None:
+            return None
+        if beam_width is not None:
+            raise ValueError("lexicon_top and beam_width cannot be combined: ask for one of the two")
+        k = _lexicon.top_arg(lexicon_top)
+        if self.lexicon is None or self._ctx.lexicon_size() != len(self.lexicon):
+            raise ValueError("lexicon_top needs a loaded lexicon: call Recognizer.set_lexicon(words) first (a lexicon is "
+                             "unloaded when a recogniser of another class count is loaded on its context)")
+        return k
+
+    def _matches(self, index, log_prob):
+        """Lexicon rows (M, K) / (M, K) -> per word a list of up to K ``(word, log_prob)``, best first; the entries that do
+        not exist (-1, -inf) are dropped.  The words come from ``self.lexicon.words``, not through the label rows."""
+        words = self.lexicon.words
+        return [[(words[i], float(v)) for i, v in zip(row, vals) if i >= 0] for row, vals in zip(np.asarray(index).tolist(), np.asarray(log_prob))]
 
     def get_batch_generator(self, image_generator, batch_size=8, lowercase=False):
         """Recognizer.get_batch_generator (recognition.py:406-465): batches for training_model.predict; see
@@ -303,14 +341,19 @@ class Recognizer:
         return [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
                 for i in range(m)]
 
-    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1):
+    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None):
         """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string; ``return_scores=True``:
         ``(text, score)``, a ``scores.Score`` whose ``detection`` is None.
 
         ``beam_width=B`` (1..64; default None: the greedy decode above, untouched): instead of the string, a list of up to
         ``top_paths`` alternatives ``(text, log_prob)``, best first, from a CTC prefix beam search (DESIGN.md section 4,
         "Beam search"); ``log_prob`` is the exact log-probability of the text, ``-ctc loss``.  With ``return_scores`` the
-        result is ``(alternatives, score)``, the score still that of the greedy decode."""
+        result is ``(alternatives, score)``, the score still that of the greedy decode.
+
+        ``lexicon_top=K`` (1..64, after ``set_lexicon``): instead of the string, a list of up to K ``(word, log_prob)``, the
+        lexicon's words of the highest exact CTC log-probability given the crop, best first (DESIGN.md section 4,
+        "Lexicon").  Not together with ``beam_width`` (ValueError)."""
+        lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         image = tools.read_and_fit(filepath_or_array=image, width=200, height=31, cval=0)
         if image.shape[-1] == 3:
@@ -319,8 +362,11 @@ class Recognizer:
             crops = self._ctx.warp_crops(image[np.newaxis], [box[np.newaxis]], 31, 200)
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
-        if beam is not None:
-            alternatives = self._alternatives(*self._ctx.crnn_beam(crops, *beam))[0]
+        if beam is not None or lexicon_top is not None:
+            if beam is not None:
+                alternatives = self._alternatives(*self._ctx.crnn_beam(crops, *beam))[0]
+            else:
+                alternatives = self._matches(*self._ctx.crnn_lexicon(crops, lexicon_top))[0]
             if not return_scores:
                 return alternatives
             labels, log_word, chars = self._ctx.crnn_forward_scores(crops)
@@ -330,17 +376,19 @@ class Recognizer:
             return self._decode(labels)[0], _scores.assemble(labels, log_word, chars)[0]
         return self._decode(self._ctx.crnn_forward(crops))[0]
 
-    def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1,
+    def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None,
                              **kwargs) -> typing.List[typing.List[str]]:
         """Recognizer.recognize_from_boxes (recognition.py:491-537); ``return_scores=True``: per image a list of
         ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None.  ``beam_width`` / ``top_paths``: as
-        ``recognize`` -- every text becomes its list of ``(text, log_prob)`` alternatives."""
+        ``recognize`` -- every text becomes its list of ``(text, log_prob)`` alternatives; ``lexicon_top``: as ``recognize`` --
+        every text becomes its list of ``(word, log_prob)`` lexicon matches."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
+        lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
         images = [tools.read(image) for image in images]
         if not sum(len(b) for b in box_groups):
-            return [[] for _ in images] if return_scores or beam else [[]] * len(images)
+            return [[] for _ in images] if return_scores or beam or lexicon_top else [[]] * len(images)
         start_end: typing.List[typing.Tuple[int, int]] = []
         for boxes in box_groups:
             start = 0 if not start_end else start_end[-1][1]
@@ -358,28 +406,35 @@ class Recognizer:
             if beam is not None:
                 head = self._ctx.crnn_forward_scores(crops) if return_scores else ()
                 return self._with_beams(head + self._ctx.crnn_beam(crops, *beam), start_end)
+            if lexicon_top is not None:
+                head = self._ctx.crnn_forward_scores(crops) if return_scores else ()
+                return self._with_beams(head + self._ctx.crnn_lexicon(crops, lexicon_top), start_end, self._matches)
             if return_scores:
                 return self._with_scores(*self._ctx.crnn_forward_scores(crops), start_end)
             predictions = self._decode(self._ctx.crnn_forward(crops))
             return [predictions[start:end] for start, end in start_end]
         if len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            parts = [self._ctx.recognize_boxes(np.stack(images), box_groups, return_scores=return_scores, beam=beam)]
+            parts = [self._ctx.recognize_boxes(np.stack(images), box_groups, return_scores=return_scores, beam=beam,
+                                               lexicon_top=lexicon_top)]
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            parts = [self._ctx.recognize_boxes(image[np.newaxis], [boxes], return_scores=return_scores, beam=beam)
+            parts = [self._ctx.recognize_boxes(image[np.newaxis], [boxes], return_scores=return_scores, beam=beam,
+                                               lexicon_top=lexicon_top)
                      for image, boxes in zip(images, box_groups) if len(boxes)]
-        if beam is not None:
+        if beam is not None or lexicon_top is not None:
             columns = [np.concatenate(column) for column in zip(*parts)]
-            return self._with_beams(tuple(columns[1:]) if not return_scores else tuple(columns), start_end)
+            return self._with_beams(tuple(columns[1:]) if not return_scores else tuple(columns), start_end,
+                                    self._alternatives if beam is not None else self._matches)
         if return_scores:
             return self._with_scores(*[np.concatenate(column) for column in zip(*parts)], start_end)
         predictions = self._decode(np.concatenate(parts))
         return [predictions[start:end] for start, end in start_end]
 
-    def _with_beams(self, columns, start_end):
-        """columns: ([labels, log_word, chars,] beam labels, beam log_prob) -> per image the alternatives [with scores]"""
-        words = self._alternatives(*columns[-2:])
+    def _with_beams(self, columns, start_end, rows_to_words=None):
+        """columns: ([labels, log_word, chars,] beam labels, beam log_prob) -> per image the alternatives [with scores];
+        ``rows_to_words``: ``_alternatives`` (the default) or ``_matches`` (columns end with the lexicon index, log_prob)"""
+        words = (rows_to_words or self._alternatives)(*columns[-2:])
         if len(columns) > 2:
             words = list(zip(words, _scores.assemble(*columns[:3])))
         return [words[start:end] for start, end in start_end]
