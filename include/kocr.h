@@ -228,6 +228,41 @@ int kocr_heat_mse(kocr_ctx* ctx, const float* y_true, const float* y_pred, int N
 int kocr_craft_mse(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W, const float* y_true, int micro_batch,
                    double* sums, int on_device);
 
+/* ---- evaluation: scoring predictions against labelled pages (evaluation.py:13-53 iou_score, :56-147 score) ----------------
+ * The rule is tests/evaluation_statement.py ("Evaluation"): a box is four int32 corners (the caller
+ * expands a 2-point box and truncates to int32 as evaluation.py:31-38 does); each quad is put into counter-clockwise order and
+ * cut into two triangles by ear clipping, the intersection is the sum over the 2 x 2 triangle pairs of the Sutherland-Hodgman
+ * clip, all in float64 in the statement's operation order -- the IoUs equal the statement's bit for bit.
+ * N images; truth_quads int32 [nt][4][2] with truth_offsets int32 [N + 1] (image i = truths [truth_offsets[i],
+ * truth_offsets[i + 1])), pred_quads / pred_offsets likewise.  Pairs are numbered image-major, truth-major inside an image:
+ * P = sum_i nt_i * np_i.  `P` is the capacity, in pairs, of the caller's per-pair buffers; when it is too small the call
+ * returns KOCR_ECAPACITY.  *P_true (may be NULL) receives the true P whenever the offsets were accepted.
+ * kocr_iou_table (evaluation.py:13-53 for every pair): iou float64 [P]; a box of zero area gives 0.
+ * kocr_score (evaluation.py:56-147): ignore uint8 [nt]; truth_text / pred_text: the texts (translator already applied) as
+ * concatenated int32 code points with truth_text_offsets int32 [nt + 1] / pred_text_offsets int32 [np + 1], at most
+ * KOCR_SCORE_MAX_TEXT code points each.  Outputs: pair_class uint8 [P] -- 0 iou < iou_threshold; 1 true positive; 2 near true
+ * positive (text similarity 1 - levenshtein / longest < similarity_threshold, float64; two empty texts: 1); 3 overlap with an
+ * ignored truth --, truth_missed uint8 [nt] (not ignored and no pair of class != 0), pred_unclaimed uint8 [np] (no pair of
+ * class != 0, ignored truths included), counts int64 [3] = {truths with a class-1 pair, unclaimed predictions, missed truths}
+ * (precision = counts[0] / (counts[0] + counts[1]), recall = counts[0] / (counts[0] + counts[2])), iou float64 [P] or NULL.
+ * Three launches (profiler rows eval_iou, eval_text, eval_reduce); the Levenshtein distance is computed only for the pairs of
+ * class 1 / 2.  An image's results do not depend on what else is in the batch.  N = 0, images without truths or without
+ * predictions and P = 0 are valid.
+ * on_device: every buffer except P_true is then a device pointer.  The four offset arrays are read back to the host (the call
+ * synchronises for that) and checked either way: they start at 0, never decrease, and no text is longer than
+ * KOCR_SCORE_MAX_TEXT -- KOCR_EINVAL naming the image or annotation, before anything is launched; host quads are also checked
+ * for |coordinate| < 2^24 (KOCR_EINVAL naming image and annotation); device quads are not looked at: larger coordinates
+ * lose exactness, nothing else.  The results are complete on return, also on_device.  Workspace comes from the context's staging arena: like every other call that processes
+ * images, the two end the validity of resident pipeline results, scores, beams and lexicon matches. */
+#define KOCR_SCORE_MAX_TEXT 256
+int kocr_iou_table(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* truth_offsets, const int32_t* pred_quads,
+                   const int32_t* pred_offsets, double* iou, int64_t P, int64_t* P_true, int on_device);
+int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* truth_offsets, const int32_t* pred_quads,
+               const int32_t* pred_offsets, const uint8_t* ignore, const int32_t* truth_text, const int32_t* truth_text_offsets,
+               const int32_t* pred_text, const int32_t* pred_text_offsets, double iou_threshold, double similarity_threshold,
+               uint8_t* pair_class, uint8_t* truth_missed, uint8_t* pred_unclaimed, int64_t* counts, double* iou, int64_t P,
+               int64_t* P_true, int on_device);
+
 /* ---- Detector.detect (detection.py:745-785): compute_input + predict + getBoxes in one call; the
  * heat-maps stay in HBM.  Arguments as kocr_craft_forward + kocr_get_boxes; counts is a HOST array. */
 int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W,

@@ -95,6 +95,9 @@ def load_library():
         "kocr_compute_maps": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, ci]),
         "kocr_heat_mse": (ci, [vp, vp, vp, ci, ci, ci, vp, ci]),
         "kocr_craft_mse": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, vp, ci]),
+        "kocr_iou_table": (ci, [vp, ci, vp, vp, vp, vp, vp, ctypes.c_int64, vp, ci]),
+        "kocr_score": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp,
+                            ctypes.c_int64, vp, ci]),
         "kocr_get_boxes": (ci, [vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, vp, vp, ci, ci]),
         "kocr_warp_crops": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, ci]),
         "kocr_warp_quads": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
@@ -900,6 +903,44 @@ class Context:
         self._check(self._lib.kocr_craft_mse(self._h, _ptr(x), dt, n, h, w, _ptr(y), int(micro_batch), _ptr(sums), 0))
         return sums
 
+    # -- evaluation (include/kocr.h: "evaluation"; evaluation.py:13-147) ------------------------------------------------
+    def iou_table(self, truth_quads, truth_offsets, pred_quads, pred_offsets):
+        """IoU of every (truth, prediction) pair of N images (kocr_iou_table): quads int32 (n, 4, 2), offsets (N + 1,).
+        Returns float64 (P,), P = sum nt_i * np_i, image-major, truth-major inside an image.  ValueError for offsets that
+        do not start at 0 or decrease and for a coordinate outside (-2^24, 2^24), naming image and annotation."""
+        tq, toff, pq, poff = _eval_quads(truth_quads, truth_offsets, pred_quads, pred_offsets)
+        pairs = max(0, int((np.diff(toff).astype(np.int64) * np.diff(poff).astype(np.int64)).sum()))
+        iou = np.zeros(pairs, np.float64)
+        self._check(self._lib.kocr_iou_table(self._h, len(toff) - 1, _ptr(tq), _ptr(toff), _ptr(pq), _ptr(poff), _ptr(iou), pairs,
+                                             None, 0), value_error=True)
+        return iou
+
+    def score_tables(self, truth_quads, truth_offsets, pred_quads, pred_offsets, ignore, truth_text, truth_text_offsets,
+                     pred_text, pred_text_offsets, iou_threshold=0.5, similarity_threshold=0.5, return_iou=False):
+        """evaluation.score's tables for N images in one call (kocr_score): quads / offsets as iou_table, ``ignore`` uint8
+        (nt,), texts as concatenated int32 code points with offsets (nt + 1,) / (np + 1,), at most 256 code points each.
+        Returns ``(pair_class uint8 (P,), truth_missed uint8 (nt,), pred_unclaimed uint8 (np,), counts int64 (3,)[, iou
+        float64 (P,)])``: class 0 no overlap, 1 true positive, 2 near true positive, 3 overlap with an ignored truth;
+        counts = truths with a class-1 pair, unclaimed predictions, missed truths.  ValueError as iou_table, and for a
+        longer text."""
+        tq, toff, pq, poff = _eval_quads(truth_quads, truth_offsets, pred_quads, pred_offsets)
+        ign = np.ascontiguousarray(ignore, dtype=np.uint8)
+        tt, tto = np.ascontiguousarray(truth_text, dtype=np.int32), np.ascontiguousarray(truth_text_offsets, dtype=np.int32)
+        pt, pto = np.ascontiguousarray(pred_text, dtype=np.int32), np.ascontiguousarray(pred_text_offsets, dtype=np.int32)
+        if len(ign) != len(tq) or len(tto) != len(tq) + 1 or len(pto) != len(pq) + 1:
+            raise ValueError("score_tables: ignore / text offsets do not match the number of boxes")
+        if len(tt) < tto[-1] or len(pt) < pto[-1]:
+            raise ValueError("score_tables: text offsets run past the texts")
+        pairs = max(0, int((np.diff(toff).astype(np.int64) * np.diff(poff).astype(np.int64)).sum()))
+        cls, missed, unclaimed = np.zeros(pairs, np.uint8), np.zeros(len(tq), np.uint8), np.zeros(len(pq), np.uint8)
+        counts = np.zeros(3, np.int64)
+        iou = np.zeros(pairs, np.float64) if return_iou else None
+        self._check(self._lib.kocr_score(self._h, len(toff) - 1, _ptr(tq), _ptr(toff), _ptr(pq), _ptr(poff), _ptr(ign), _ptr(tt),
+                                         _ptr(tto), _ptr(pt), _ptr(pto), float(iou_threshold), float(similarity_threshold),
+                                         _ptr(cls), _ptr(missed), _ptr(unclaimed), _ptr(counts), _ptr(iou), pairs, None, 0),
+                    value_error=True)
+        return (cls, missed, unclaimed, counts) + ((iou,) if return_iou else ())
+
     def profile_enable(self, on=True):
         self._check(self._lib.kocr_profile_enable(self._h, int(bool(on))))
 
@@ -951,6 +992,19 @@ def _detector_input(images):
     if x.dtype == np.uint8:
         return x, KOCR_U8
     return np.ascontiguousarray(x, dtype=np.float32), KOCR_F32
+
+
+def _eval_quads(truth_quads, truth_offsets, pred_quads, pred_offsets):
+    """iou_table / score_tables arguments as contiguous int32 arrays, shapes checked against the offsets' last entries"""
+    tq = np.ascontiguousarray(truth_quads, dtype=np.int32).reshape(-1, 4, 2)
+    pq = np.ascontiguousarray(pred_quads, dtype=np.int32).reshape(-1, 4, 2)
+    toff = np.ascontiguousarray(truth_offsets, dtype=np.int32).reshape(-1)
+    poff = np.ascontiguousarray(pred_offsets, dtype=np.int32).reshape(-1)
+    if len(toff) < 1 or len(toff) != len(poff):
+        raise ValueError("truth_offsets and pred_offsets must both hold N + 1 entries")
+    if toff[-1] != len(tq) or poff[-1] != len(pq):
+        raise ValueError(f"offsets end at {toff[-1]} / {poff[-1]} but there are {len(tq)} / {len(pq)} boxes")
+    return tq, toff, pq, poff
 
 
 def _flatten_lines(line_groups):

@@ -591,6 +591,31 @@ int launch_compute_maps(kocr_ctx* ctx, const uint8_t* d_heat, int hh, int hw, in
 // Keras' mse on the maps: per-image float64 sums d_sums[N] of the channel-mean squared error over h w pixels
 int launch_heat_mse(kocr_ctx* ctx, const float* d_true, const float* d_pred, int N, int hw_px, double* d_sums);
 
+// evaluate.hip: evaluation.score on the device (kocr_iou_table / kocr_score).  The device view of a batch of N images: quads
+// int32 [n][4][2] with offsets [N + 1], pair_off[i] = the flat index of image i's first (truth, prediction) pair (truth-major),
+// P = pair_off[N], words = truths + predictions of the batch; ignore / texts only for kocr_score (code-point rows with
+// offsets [n + 1]).
+struct EvalBatch {
+  int N = 0;
+  long long P = 0, words = 0;
+  const int32_t *d_tq = nullptr, *d_toff = nullptr, *d_pq = nullptr, *d_poff = nullptr;
+  const long long* d_pair_off = nullptr;
+  const uint8_t* d_ignore = nullptr;
+  const int32_t *d_ttext = nullptr, *d_ttoff = nullptr, *d_ptext = nullptr, *d_ptoff = nullptr;
+};
+// a pair whose texts eval_text_kernel compares: flat pair index, truth and prediction index in the batch
+struct EvalWork {
+  long long k;
+  int t, p;
+};
+// d_iou / d_class may be null (kocr_score without the table / kocr_iou_table); d_work holds P entries, *d_work_count is zero
+int launch_eval_iou(kocr_ctx* ctx, const EvalBatch& b, double* d_iou, double iou_threshold, uint8_t* d_class, EvalWork* d_work,
+                    unsigned* d_work_count);
+int launch_eval_text(kocr_ctx* ctx, const EvalBatch& b, const EvalWork* d_work, const unsigned* d_work_count, double similarity_threshold,
+                     uint8_t* d_class);
+// d_counts: int64[3], zeroed by the caller
+int launch_eval_reduce(kocr_ctx* ctx, const EvalBatch& b, const uint8_t* d_class, uint8_t* d_missed, uint8_t* d_unclaimed, int64_t* d_counts);
+
 // imgproc.hip
 int launch_resize_pad_f32(kocr_ctx* ctx, const float* d_src, int n, int sh, int sw, int C, float* d_dst, int dh, int dw, int Hmax,
                           int Wmax, float cval, Arena& tab_arena);

@@ -1,7 +1,8 @@
-"""Host-side mirror of ``keras_ocr.evaluation`` (reference ``keras_ocr/evaluation.py:13-147``):
-polygon IoU and precision/recall scoring of pipeline output.  SURVEY.md §8(f) item 4 — off the hot
-path, pure numpy/Python: pyclipper, cv2.contourArea and editdistance are re-stated (simple polygons
-are triangulated by ear clipping and intersected triangle by triangle with Sutherland-Hodgman)."""
+"""Mirror of ``keras_ocr.evaluation`` (reference ``keras_ocr/evaluation.py:13-147``): polygon IoU and
+precision/recall scoring of pipeline output.  SURVEY.md §8(f) item 4.  Two paths: the host one, pure
+numpy/Python, where pyclipper, cv2.contourArea and editdistance are re-stated (simple polygons
+are triangulated by ear clipping and intersected triangle by triangle with Sutherland-Hodgman); and, with
+``ctx``, the same rule for 2- and 4-corner boxes on the GPU (kocr_score: DESIGN.md section 4, "Evaluation")."""
 import typing
 import warnings
 
@@ -121,7 +122,106 @@ def _text_similarity(a, b):
     return 1 if longest == 0 else 1 - _edit_distance(a, b) / longest
 
 
-def score(true, pred, iou_threshold=0.5, similarity_threshold=0.5, translator=None):
+def _int_quad(box, image_id, kind, index):
+    """A 2- or 4-point box as iou_score takes it: the (4, 2) int32 array it hands to the clipper."""
+    if len(box) == 2:
+        (x1, y1), (x2, y2) = box
+        box = np.array([[x1, y1], [x2, y1], [x2, y2], [x1, y2]])
+    quad = np.array(box, dtype="int32")
+    if quad.shape != (4, 2):
+        raise ValueError(f"image {image_id!r}, {kind} {index}: the device path takes boxes of 2 or 4 corners, got vertices of "
+                         f"shape {quad.shape}")
+    return quad
+
+
+def _context(ctx):
+    from . import _lib  # pylint: disable=import-outside-toplevel
+    return _lib.default_context() if ctx is True else ctx
+
+
+def iou_matrix(boxes_a, boxes_b, ctx=None):
+    """iou_score of every pair of two lists of boxes of one image on the GPU (kocr_iou_table): (A, B) float64.  2-point
+    and 4-point boxes, truncated to int32 exactly as iou_score does."""
+    qa = [_int_quad(b, 0, "box of the first list", i) for i, b in enumerate(boxes_a)]
+    qb = [_int_quad(b, 0, "box of the second list", i) for i, b in enumerate(boxes_b)]
+    qa = np.array(qa, dtype=np.int32).reshape(-1, 4, 2)
+    qb = np.array(qb, dtype=np.int32).reshape(-1, 4, 2)
+    if _zero_area(qa).any() or _zero_area(qb).any():
+        if len(qa) and len(qb):
+            warnings.warn("A box with zero area was detected.")
+    table = _context(True if ctx is None else ctx).iou_table(qa, [0, len(qa)], qb, [0, len(qb)])
+    return table.reshape(len(qa), len(qb))
+
+
+def _zero_area(quads):
+    """per (n, 4, 2) int32 quad: is its shoelace area zero (exact in int64 for |coordinate| < 2^24)"""
+    q = quads.astype(np.int64)
+    x, y = q[:, :, 0], q[:, :, 1]
+    return (x * np.roll(y, -1, axis=1) - y * np.roll(x, -1, axis=1)).sum(axis=1) == 0
+
+
+def _code_points(texts, image_ids, kind):
+    """texts -> (concatenated int32 code points, int32 offsets); ValueError for one over 256 code points"""
+    lengths = np.fromiter((len(t) for _, _, t in texts), dtype=np.int64, count=len(texts))
+    if len(lengths) and lengths.max() > 256:
+        image, index, text = texts[int(np.argmax(lengths > 256))]
+        raise ValueError(f"image {image_ids[image]!r}, {kind} {index}: text of {len(text)} code points, the device path takes at "
+                         "most 256")
+    joined = "".join(t for _, _, t in texts)
+    points = np.frombuffer(joined.encode("utf-32-le", "surrogatepass"), dtype="<u4").astype(np.int32)
+    return points, np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+
+
+def _score_device(true, pred, iou_threshold, similarity_threshold, translator, ctx, return_results):
+    """score() through one kocr_score call; the dictionaries are rebuilt from its flag arrays in the host path's order."""
+    image_ids = sorted(true)
+    assert all(a == b for a, b in zip(image_ids, sorted(pred))), "true and pred dictionaries must have the same keys"
+    clean = (lambda t: t.translate(translator)) if translator is not None else (lambda t: t)
+    quads, texts, counts, ignore = ([], []), ([], []), ([], []), []
+    for n, image_id in enumerate(image_ids):
+        for side, (kind, annotations) in enumerate((("truth", true[image_id]), ("prediction", pred[image_id]))):
+            counts[side].append(len(annotations))
+            for index, annotation in enumerate(annotations):
+                quads[side].append(_int_quad(annotation["vertices"], image_id, kind, index))
+                texts[side].append((n, index, annotation["text"]))
+        ignore += [bool(t.get("ignore", False)) for t in true[image_id]]
+    nt, npred = np.array(counts[0], np.int64), np.array(counts[1], np.int64)
+    # the translator runs only where the host path runs it: it cannot be known before the IoUs which pairs those are,
+    # so every text is cleaned once (a translator is a pure table lookup)
+    texts = tuple([(n, i, clean(t)) for n, i, t in side] for side in texts)
+    tq = np.array(quads[0], dtype=np.int32).reshape(-1, 4, 2)
+    pq = np.array(quads[1], dtype=np.int32).reshape(-1, 4, 2)
+    toff = np.concatenate([[0], np.cumsum(nt)]).astype(np.int32)
+    poff = np.concatenate([[0], np.cumsum(npred)]).astype(np.int32)
+    tt, tto = _code_points(texts[0], image_ids, "truth")
+    pt, pto = _code_points(texts[1], image_ids, "prediction")
+    paired = np.repeat((nt > 0) & (npred > 0), nt), np.repeat((nt > 0) & (npred > 0), npred)
+    if (_zero_area(tq) & paired[0]).any() or (_zero_area(pq) & paired[1]).any():
+        warnings.warn("A box with zero area was detected.")
+    cls, missed, unclaimed, totals = _context(ctx).score_tables(tq, toff, pq, poff, np.array(ignore, np.uint8), tt, tto, pt, pto,
+                                                                iou_threshold, similarity_threshold)
+    n_tp, n_fp, n_fn = (int(v) for v in totals)
+    if not return_results:
+        return None, (n_tp / (n_tp + n_fp), n_tp / (n_tp + n_fn))
+    results = {"true_positives": [], "false_positives": [], "near_true_positives": [], "false_negatives": []}
+    pair_off = np.concatenate([[0], np.cumsum(nt * npred)])
+    for key, value in (("true_positives", 1), ("near_true_positives", 2)):
+        flat = np.flatnonzero(cls == value)
+        image = np.searchsorted(pair_off, flat, side="right") - 1
+        local = flat - pair_off[image]
+        width = npred[image]
+        results[key] = [{"true_idx": ti, "pred_idx": pi, "image_id": image_ids[n]}
+                        for n, ti, pi in zip(image.tolist(), (local // width).tolist(), (local % width).tolist())]
+    flat = np.flatnonzero(missed)
+    image = np.searchsorted(toff, flat, side="right") - 1
+    results["false_negatives"] = [{"image_id": image_ids[n], "true_idx": ti} for n, ti in zip(image.tolist(), (flat - toff[image]).tolist())]
+    flat = np.flatnonzero(unclaimed)
+    image = np.searchsorted(poff, flat, side="right") - 1
+    results["false_positives"] = [{"pred_index": pi, "image_id": image_ids[n]} for n, pi in zip(image.tolist(), (flat - poff[image]).tolist())]
+    return results, (n_tp / (n_tp + n_fp), n_tp / (n_tp + n_fn))
+
+
+def score(true, pred, iou_threshold=0.5, similarity_threshold=0.5, translator=None, ctx=None, return_results=True):
     """evaluation.score (evaluation.py:56-147): detection + recognition precision / recall.
 
     ``true`` / ``pred``: ``{image_id: [{"text", "vertices"[, "ignore"]}]}`` with the same keys.  Returns
@@ -131,7 +231,19 @@ def score(true, pred, iou_threshold=0.5, similarity_threshold=0.5, translator=No
     absorbs the predictions it overlaps and is itself never counted.  Precision and recall count distinct matched
     truths, as the reference does (so two predictions on one truth are one true positive).
 
-    Written as: IoU table per image -> pair classification -> bookkeeping (the reference interleaves the three)."""
+    Written as: IoU table per image -> pair classification -> bookkeeping (the reference interleaves the three).
+
+    ``ctx`` (a ``Context``, or True for the default one) scores the whole dictionary in one GPU call and returns an equal
+    value; boxes then have 2 or 4 corners and texts at most 256 code points (ValueError naming image id and annotation
+    index otherwise: the host path remains for those).  Both limits hold for every annotation of the dictionaries, also
+    for one that plays no part in the score (an ignored truth, a box that overlaps nothing): which texts the score needs
+    is known only after the IoUs, so every text is translated and staged.  The host path translates and compares only
+    the texts of overlapping pairs with a truth that is not ignored.
+
+    ``return_results=False`` returns ``(None, (precision, recall))`` on either path; with ``ctx`` it also skips the
+    assembly of the dictionary (on the host path the lists are the computation, so it saves nothing there)."""
+    if ctx is not None and ctx is not False:
+        return _score_device(true, pred, iou_threshold, similarity_threshold, translator, ctx, return_results)
     image_ids = sorted(true)
     assert all(a == b for a, b in zip(image_ids, sorted(pred))), "true and pred dictionaries must have the same keys"
     clean = (lambda t: t.translate(translator)) if translator is not None else (lambda t: t)
@@ -156,4 +268,4 @@ def score(true, pred, iou_threshold=0.5, similarity_threshold=0.5, translator=No
         results["false_positives"] += [{"pred_index": pi, "image_id": image_id} for pi in range(len(preds)) if pi not in claimed]
     n_fn, n_fp = len(results["false_negatives"]), len(results["false_positives"])
     n_tp = len({(m["image_id"], m["true_idx"]) for m in results["true_positives"]})
-    return results, (n_tp / (n_tp + n_fp), n_tp / (n_tp + n_fn))
+    return (results if return_results else None), (n_tp / (n_tp + n_fp), n_tp / (n_tp + n_fn))

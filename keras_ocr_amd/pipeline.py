@@ -1,7 +1,7 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
 import numpy as np
 
-from . import _lib, detection, lexicon as _lexicon, recognition, scores as _scores, tools
+from . import _lib, detection, evaluation as _evaluation, lexicon as _lexicon, recognition, scores as _scores, tools
 
 
 def beam_of(recognition_kwargs):
@@ -92,6 +92,25 @@ class Pipeline:
         With a ``beam_width`` in ``recognition_kwargs`` the tuples are (alternatives, box, score); ``score.word`` /
         ``log_word`` / ``characters`` keep referring to the greedy decode, which need not be the first alternative."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs, return_scores=True)
+
+    def evaluate(self, images, true, detection_kwargs=None, recognition_kwargs=None, **score_kwargs):
+        """recognize() scored against labelled pages on the GPU (evaluation.score with the detector's context; DESIGN.md
+        section 4, "Evaluation").  ``true``: one list of annotations ``{"text", "vertices"[, "ignore"]}`` per image;
+        ``score_kwargs``: ``iou_threshold``, ``similarity_threshold``, ``translator``, ``return_results``.  Returns
+        ``(predictions, results, (precision, recall))``: ``predictions`` is what recognize() returns, ``results`` and the two
+        numbers what ``evaluation.score({i: true[i]}, {i: [{"text", "vertices"} per word]})`` returns, the image ids being
+        the positions in ``images``.  ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list."""
+        for key in ("beam_width", "lexicon_top"):
+            if (recognition_kwargs or {}).get(key) is not None:
+                raise ValueError(f"evaluate scores one text per word: {key} in recognition_kwargs makes every text a list of alternatives")
+        true = list(true)
+        predictions = self.recognize(images, detection_kwargs, recognition_kwargs)
+        if len(true) != len(predictions):
+            raise ValueError(f"{len(predictions)} images but {len(true)} lists of annotations")
+        pred = {i: [{"text": text, "vertices": box} for text, box in group] for i, group in enumerate(predictions)}
+        ctx = getattr(self.detector, "_ctx", None)
+        results, precision_recall = _evaluation.score(dict(enumerate(true)), pred, ctx=True if ctx is None else ctx, **score_kwargs)
+        return predictions, results, precision_recall
 
     def recognize_padded(self, images, hmax, wmax, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
         """recognize() with the padded detector-input size imposed by the caller (used when a
