@@ -53,8 +53,13 @@ enum { KOCR_U8 = 0, KOCR_F32 = 1 };
 int kocr_create(kocr_ctx** out, int hip_device);
 void kocr_destroy(kocr_ctx* ctx);
 const char* kocr_last_error(const kocr_ctx* ctx);
-/* Run on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream);
- * NULL restores the ctx's own stream. */
+/* Run on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream of a NON-default torch stream).  The
+ * call first synchronises the stream the ctx was on, so work queued there is complete when it returns.
+ * Handle 0 / NULL selects the ctx's own stream, created with hipStreamNonBlocking.  That includes torch's default stream,
+ * whose handle is 0: the library never runs on the legacy default stream.  The ctx's own stream is NOT ordered against the
+ * legacy default stream in either direction, so a caller whose device buffers are produced or consumed on the default stream
+ * synchronises on both sides -- the device (torch.cuda.synchronize()) before the call, kocr_synchronize() after it -- or
+ * works on a non-default stream and hands that one over. */
 int kocr_set_stream(kocr_ctx* ctx, void* hip_stream);
 int kocr_synchronize(kocr_ctx* ctx);
 /* Device-buffer helpers so a host without torch can still keep data resident. */
@@ -142,7 +147,8 @@ int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float 
  * images' boxes concatenated in image order; counts: HOST int32[N], sum = M.  crops:
  * M x target_h x target_w float32 = gray/255, zero outside the warped region (device if
  * on_device).  KOCR_EZERODIV where the reference raises ZeroDivisionError (box with integer
- * width or height 0, tools.py:95). */
+ * width or height 0, tools.py:95).  The call synchronises, on_device too: the warp parameters
+ * come from the HOST boxes, and the crops are complete on return. */
 int kocr_warp_crops(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
                     const int32_t* counts, int target_h, int target_w, float* crops, int on_device);
 
@@ -192,14 +198,18 @@ int kocr_crnn_label_width(kocr_ctx* ctx);
  * reference pads with -1); label_lengths / input_lengths: HOST int32[M]; loss: float32[M].  y_pred and loss are device
  * pointers when on_device is set.  KOCR_EINVAL, naming the sample, before anything is launched: input_lengths[m] outside
  * [1, T], label_lengths[m] outside [0, min(input_lengths[m], label_stride)], a label outside [0, C - 2].  A label that
- * fits in length but not with a blank between its repeats ("aa" in 2 frames) has loss +inf. */
+ * fits in length but not with a blank between its repeats ("aa" in 2 frames) has loss +inf.
+ * The call SYNCHRONISES the ctx stream before it returns, on_device too: the labels and lengths are packed into a host
+ * staging buffer of the call and copied from there on the stream, and the call waits for the stream at its end so that the
+ * buffer may go.  The loss is therefore complete on return. */
 int kocr_ctc_batch_cost(kocr_ctx* ctx, const float* y_pred, int M, int T, int C, const int32_t* labels, int label_stride,
                         const int32_t* label_lengths, const int32_t* input_lengths, float* loss, int on_device);
 /* recognizer.training_model.predict([crops, labels, input_length, label_length]) (recognition.py:334-349): the recogniser
  * up to fc_12, then kocr_ctc_batch_cost's rule on fc_12's softmax, with T = kocr_crnn_label_width() (the frames after
  * rnn_steps_to_discard).  The probabilities never leave HBM and are bit for bit those kocr_crnn_forward returns, so the
  * loss equals kocr_ctc_batch_cost on them bit for bit.  crops: M x 31 x 200 float32 (device when on_device), loss:
- * float32[M] (device when on_device); labels and lengths as kocr_ctc_batch_cost (HOST arrays). */
+ * float32[M] (device when on_device); labels and lengths as kocr_ctc_batch_cost (HOST arrays), and for the same reason the
+ * call SYNCHRONISES the ctx stream at the end of every batch of 1024 crops, on_device too: the loss is complete on return. */
 int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* labels, int label_stride,
                        const int32_t* label_lengths, const int32_t* input_lengths, float* loss, int on_device);
 /* recognizer.backbone.predict (recognition.py:319-320): feats M x 50 x 256 float32, the Concatenate output
@@ -280,7 +290,10 @@ int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, in
 /* src: n x sh x sw x 3 uint8 (n images of one size); each is resized to dh x dw exactly as
  * cv2.resize(image, dsize=(dw, dh)) (INTER_LINEAR, uint8 fixed point) and written to the
  * top-left of an Hmax x Wmax canvas filled with cval (255 for tools.pad, tools.py:356; 0 for the
- * letterbox of Recognizer.recognize, tools.py:442, recognition.py:473-478).  dst: n x Hmax x Wmax x 3. */
+ * letterbox of Recognizer.recognize, tools.py:442, recognition.py:473-478).  dst: n x Hmax x Wmax x 3.
+ * The interpolation tables of the two axes are built in a host vector local to the call and copied to the device on the
+ * stream; the call SYNCHRONISES the ctx stream right after that copy, on_device too, so that the vector may go.  The resize
+ * launch behind it is asynchronous: on return everything queued ahead of the call has finished, dst has not. */
 int kocr_resize_pad(kocr_ctx* ctx, const uint8_t* src, int n, int sh, int sw, int dh, int dw,
                     int Hmax, int Wmax, int cval, uint8_t* dst, int on_device);
 

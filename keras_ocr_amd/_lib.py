@@ -196,6 +196,12 @@ class Context:
 
     # -- plumbing ------------------------------------------------------------------
     def set_stream(self, stream_ptr):
+        """Run this context on the caller's HIP stream (kocr_set_stream), e.g. ``torch.cuda.Stream().cuda_stream``; the
+        stream it was on is synchronised first.  ``0`` / ``None`` selects the context's own non-blocking stream -- and ``0``
+        is also the handle of torch's default stream, so ``set_stream(torch.cuda.current_stream().cuda_stream)`` on the
+        default stream does NOT put the library there.  The context's own stream is not ordered against the legacy default
+        stream: a caller working on the default stream calls ``torch.cuda.synchronize()`` before a device-pointer call and
+        ``synchronize()`` after it, or uses a non-default stream."""
         self._check(self._lib.kocr_set_stream(self._h, ctypes.c_void_p(stream_ptr or 0)))
 
     def synchronize(self):

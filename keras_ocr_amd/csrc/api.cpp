@@ -666,10 +666,10 @@ int kocr_compute_maps(kocr_ctx* ctx, const uint8_t* heatmap, int hh, int hw, int
   const size_t n = (size_t)n_chars, px = (size_t)N * h * w;
   const size_t heat_b = (size_t)hh * hw, quad_b = n * 8 * sizeof(float), line_b = ((size_t)n_lines + 1) * sizeof(int32_t);
   const size_t img_b = ((size_t)N + 1) * sizeof(int32_t), maps_b = px * 2 * sizeof(float);
-  const size_t slot_b = 2 * n * sizeof(MapSlot), plane_b = px * 2 * sizeof(int32_t), tab_b = 256 * sizeof(float);
+  const size_t slot_b = 2 * n * sizeof(MapSlot), plane_b = px * 2 * sizeof(int32_t);
   Staging st{ctx, ctx->io, fn, on_device != 0};
   KOCR_TRY(st.reserve(0, {heat_b, quad_b, n, line_b, img_b, maps_b},
-                      {quad_b, n * 2 * sizeof(float), n * sizeof(int), n * sizeof(int), slot_b, plane_b, tab_b}));
+                      {quad_b, n * 2 * sizeof(float), n * sizeof(int), n * sizeof(int), slot_b, plane_b}));
   const uint8_t *d_heat, *d_space;
   const float* d_quads;
   const int32_t *d_loff, *d_ioff;
@@ -687,14 +687,18 @@ int kocr_compute_maps(kocr_ctx* ctx, const uint8_t* heatmap, int hh, int hw, int
   KOCR_TRY(st.scratch(n * sizeof(int), wk.permy));
   KOCR_TRY(st.scratch(slot_b, wk.slots));
   KOCR_TRY(st.scratch(plane_b, wk.planes));
-  // numpy's float32 v / 255 (detection.py:197): IEEE division on the host, so the device's division rule never matters
-  float table[256];
-  for (int v = 0; v < 256; ++v) table[v] = (float)v / 255.0f;
-  KOCR_TRY(st.upload(table, tab_b, wk.table));
+  // numpy's float32 v / 255 (detection.py:197): IEEE division on the host, so the device's division rule never matters.  The
+  // table stays resident on the context (a blocking upload by the first call), so a device-pointer call copies nothing from
+  // host memory and stays asynchronous
+  if (!ctx->d_div255) {
+    std::vector<float> table(256);
+    for (int v = 0; v < 256; ++v) table[v] = (float)v / 255.0f;
+    KOCR_TRY(ctx->upload(&ctx->d_div255, table));
+  }
+  wk.table = ctx->d_div255;
   KOCR_TRY(launch_compute_maps(ctx, d_heat, hh, hw, N, h, w, n_chars, d_quads, d_space, n_lines, d_loff, d_ioff, wk, d_maps));
   KOCR_TRY(st.back(maps, d_maps, maps_b));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `table` is host memory about to go out of scope
-  return KOCR_OK;
+  return st.finish();
 }
 
 int kocr_heat_mse(kocr_ctx* ctx, const float* y_true, const float* y_pred, int N, int h, int w, double* sums, int on_device) {

@@ -187,6 +187,7 @@ struct kocr_ctx {
   int dev_alloc(void** out, size_t bytes);
   int upload(float** out, const std::vector<float>& host);
   void release(void* p);  // hipFree one persistent allocation (a re-prepared layer's previous weights); nullptr is ignored
+  float* d_div255 = nullptr;  // [256] float32 v / 255 of kocr_compute_maps, uploaded by its first call on the context
 
   CraftNet* craft = nullptr;
   CrnnNet* crnn = nullptr;
