@@ -273,6 +273,34 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
                uint8_t* pair_class, uint8_t* truth_missed, uint8_t* pred_unclaimed, int64_t* counts, double* iou, int64_t P,
                int64_t* P_true, int on_device);
 
+/* ---- lines: recognised words grouped into text lines, in reading order (no reference counterpart) ---------------------------
+ * The rule is tests/lines_statement.py ("Lines"), float64 in the statement's operation order: the
+ * integers equal the statement's and the line boxes carry its float32 bits.  A word is a quad [tl, tr, br, bl] as
+ * kocr_get_boxes returns it.  Two words link when their directions differ by at most max_angle (cos_max = cos(max_angle), a
+ * double the caller computes once; max_angle in [0, 90) degrees, so cos_max in (0, 1]), the smaller height is at least
+ * min_height_ratio (in [0, 1]) of the larger, their centres lie at most max_offset (>= 0) smaller heights apart across the
+ * joint axis, and the gap between them along it is at most max_gap (>= 0) larger heights.  Lines are the connected
+ * components; a word without width or height is a line of its own.  Inside a line the words are ordered along the summed
+ * direction of its members; the line box is the bounding rectangle ALONG that axis (not a min-area rectangle); lines are
+ * ordered by the y, then the x of the box centre, then the smallest member.  Columns are not detected.
+ * N pages; quads float32 [total][4][2] with offsets int32 [N + 1] (page i = words [offsets[i], offsets[i + 1])), at most
+ * KOCR_LINES_MAX_WORDS words on a page.  Outputs: line_of int32 [total], the index of word j's line among its page's lines;
+ * order int32 [total], per page (at the page's offset) the page-local word indices in reading order, line 0's words, then
+ * line 1's, ...; line_counts int32 [N]; line_boxes float32 [cap_lines][4][2], all lines of all pages in that order
+ * (tl, tr, br, bl along the line).  cap_lines is the capacity of line_boxes in lines: with more lines the call returns
+ * KOCR_ECAPACITY; *true_lines (may be NULL) receives the number of lines whenever the kernel ran, and line_of / order /
+ * line_counts are complete then too (total is always enough).  line_boxes == NULL with cap_lines == 0 skips the boxes.
+ * KOCR_EINVAL with a message, before anything is launched: offsets that do not start at 0 or decrease, a page above
+ * KOCR_LINES_MAX_WORDS (naming the page and its count), a non-finite coordinate (naming page and word), a rule parameter out of
+ * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is reserved and must be 0.  Two
+ * launches on the ctx stream (profiler rows lines_group, lines_pack), one workgroup per page; a page's results do not
+ * depend on what else is in the batch.  The results are complete on return.  Workspace comes from the staging arena: like
+ * every other call that processes images it ends the validity of resident pipeline results. */
+#define KOCR_LINES_MAX_WORDS 2048
+int kocr_group_lines(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, double cos_max, double min_height_ratio,
+                     double max_offset, double max_gap, int32_t* line_of, int32_t* order, int32_t* line_counts, float* line_boxes,
+                     int64_t cap_lines, int64_t* true_lines, int flags);
+
 /* ---- Detector.detect (detection.py:745-785): compute_input + predict + getBoxes in one call; the
  * heat-maps stay in HBM.  Arguments as kocr_craft_forward + kocr_get_boxes; counts is a HOST array. */
 int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W,

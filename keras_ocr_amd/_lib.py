@@ -6,6 +6,7 @@ no HIP device is visible, the product fails loudly here.
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -98,6 +99,8 @@ def load_library():
         "kocr_iou_table": (ci, [vp, ci, vp, vp, vp, vp, vp, ctypes.c_int64, vp, ci]),
         "kocr_score": (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp, vp,
                             ctypes.c_int64, vp, ci]),
+        "kocr_group_lines": (ci, [vp, ci, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp,
+                                  ctypes.c_int64, vp, ci]),
         "kocr_get_boxes": (ci, [vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, vp, vp, ci, ci]),
         "kocr_warp_crops": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, ci]),
         "kocr_warp_quads": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
@@ -946,6 +949,31 @@ class Context:
                                          _ptr(cls), _ptr(missed), _ptr(unclaimed), _ptr(counts), _ptr(iou), pairs, None, 0),
                     value_error=True)
         return (cls, missed, unclaimed, counts) + ((iou,) if return_iou else ())
+
+    # -- lines (include/kocr.h: "lines") ------------------------------------------------------------------------------------
+    def group_lines(self, quads, offsets, max_angle=15.0, min_height_ratio=0.5, max_offset=0.5, max_gap=1.5, return_boxes=True):
+        """The words of N pages grouped into text lines in reading order, in one call (kocr_group_lines; DESIGN.md section 4,
+        "Lines"): ``quads`` float32 (total, 4, 2), the pages' word boxes [tl, tr, br, bl] one after the other, ``offsets``
+        (N + 1,), at most 2048 words on a page.  Returns ``(line_of int32 (total,), order int32 (total,), line_counts int32
+        (N,), line_boxes float32 (lines, 4, 2) or None)``: the index of each word's line among its page's lines; per page
+        the page-local word indices in reading order, line after line; the lines per page; the box of every line of every
+        page in that order.  ValueError for ``max_angle`` outside [0, 90), another rule parameter out of range, offsets that
+        do not start at 0 or decrease, a page of more than 2048 words and a non-finite coordinate (naming page and word)."""
+        max_angle = float(max_angle)
+        if not 0 <= max_angle < 90:
+            raise ValueError(f"group_lines: max_angle {max_angle} outside [0, 90)")
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 4, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        if len(off) < 1 or off[-1] != len(q):
+            raise ValueError(f"group_lines: offsets must hold N + 1 entries and end at the number of boxes, {len(q)}")
+        n, total = len(off) - 1, len(q)
+        line_of, order, counts = np.zeros(total, np.int32), np.zeros(total, np.int32), np.zeros(n, np.int32)
+        boxes = np.zeros((total, 4, 2), np.float32) if return_boxes else None  # a page has at most as many lines as words
+        lines = ctypes.c_int64(0)
+        self._check(self._lib.kocr_group_lines(self._h, n, _ptr(q), _ptr(off), math.cos(math.radians(max_angle)), float(min_height_ratio),
+                                               float(max_offset), float(max_gap), _ptr(line_of), _ptr(order), _ptr(counts), _ptr(boxes),
+                                               total if return_boxes else 0, ctypes.byref(lines), 0), value_error=True)
+        return line_of, order, counts, (boxes[:lines.value].copy() if return_boxes else None)
 
     def profile_enable(self, on=True):
         self._check(self._lib.kocr_profile_enable(self._h, int(bool(on))))

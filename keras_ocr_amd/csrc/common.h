@@ -617,6 +617,18 @@ int launch_eval_text(kocr_ctx* ctx, const EvalBatch& b, const EvalWork* d_work, 
 // d_counts: int64[3], zeroed by the caller
 int launch_eval_reduce(kocr_ctx* ctx, const EvalBatch& b, const uint8_t* d_class, uint8_t* d_missed, uint8_t* d_unclaimed, int64_t* d_counts);
 
+// lines.hip: recognised words grouped into text lines (kocr_group_lines; DESIGN.md section 4, "Lines").  d_quads float32
+// [total][4][2] with d_off [N + 1]; max_words: the largest page (at most KOCR_LINES_MAX_WORDS; it sizes the LDS).  d_boxes
+// (nullable) [total][4][2]: the lines of page i at its WORD offset d_off[i], in page order; launch_lines_pack moves them to
+// d_line_off[i] of the packed buffer once the host has the counts.
+struct LinesRule {
+  double cos_max, min_height_ratio, max_offset, max_gap;
+};
+size_t lines_lds_bytes(int max_words);
+int launch_lines_group(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_words, const LinesRule& rule,
+                       int32_t* d_line_of, int32_t* d_order, int32_t* d_line_counts, float* d_boxes);
+int launch_lines_pack(kocr_ctx* ctx, const float* d_scratch, const int32_t* d_off, const long long* d_line_off, int N, float* d_boxes);
+
 // imgproc.hip
 int launch_resize_pad_f32(kocr_ctx* ctx, const float* d_src, int n, int sh, int sw, int C, float* d_dst, int dh, int dw, int Hmax,
                           int Wmax, float cval, Arena& tab_arena);

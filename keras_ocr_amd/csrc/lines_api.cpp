@@ -1,0 +1,102 @@
+// lines_api.cpp — kocr_group_lines (include/kocr.h, "lines"): argument checks, staging, the two launches of lines.hip.
+#include "abi.h"
+#include <cmath>
+
+namespace {
+
+int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, const LinesRule& rule, int32_t* line_of, int32_t* order,
+              int32_t* line_counts, float* line_boxes, int64_t cap_lines, int64_t* true_lines, int flags) {
+  const std::string fn("kocr_group_lines");
+  if (N < 0 || cap_lines < 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": bad sizes");
+  if (flags != 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": flags must be 0");
+  if (!line_boxes && cap_lines != 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": null line_boxes with cap_lines " + std::to_string((long long)cap_lines));
+  // !(a <= x) also refuses a NaN
+  if (!(rule.cos_max > 0 && rule.cos_max <= 1))
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": cos_max " + std::to_string(rule.cos_max) + " outside (0, 1] (max_angle must lie in [0, 90) degrees)");
+  if (!(rule.min_height_ratio >= 0 && rule.min_height_ratio <= 1))
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": min_height_ratio " + std::to_string(rule.min_height_ratio) + " outside [0, 1]");
+  if (!(rule.max_offset >= 0 && std::isfinite(rule.max_offset)))
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": max_offset " + std::to_string(rule.max_offset) + " is not a finite number >= 0");
+  if (!(rule.max_gap >= 0 && std::isfinite(rule.max_gap)))
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": max_gap " + std::to_string(rule.max_gap) + " is not a finite number >= 0");
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  if (true_lines) *true_lines = 0;
+  if (N == 0) return KOCR_OK;
+  if (!offsets || !line_counts) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": null offsets or line_counts");
+  if (offsets[0] != 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": offsets must start at 0");
+  int max_words = 0;
+  for (int i = 0; i < N; ++i) {
+    if (offsets[i + 1] < offsets[i]) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": offsets decreases at entry " + std::to_string(i + 1));
+    const int words = offsets[i + 1] - offsets[i];
+    if (words > KOCR_LINES_MAX_WORDS)
+      KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": page " + std::to_string(i) + " holds " + std::to_string(words) +
+                                      " words, more than KOCR_LINES_MAX_WORDS = " + std::to_string(KOCR_LINES_MAX_WORDS));
+    max_words = std::max(max_words, words);
+  }
+  const size_t total = (size_t)offsets[N];
+  if (total && (!quads || !line_of || !order)) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": null buffer");
+  for (int i = 0; i < N; ++i)
+    for (int j = offsets[i]; j < offsets[i + 1]; ++j)
+      for (int c = 0; c < 8; ++c)
+        if (!std::isfinite(quads[(size_t)j * 8 + c]))
+          KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": page " + std::to_string(i) + ", word " + std::to_string(j - offsets[i]) + ": non-finite coordinate");
+  if (total == 0) {
+    std::fill(line_counts, line_counts + N, 0);
+    return KOCR_OK;
+  }
+
+  std::vector<long long> line_off((size_t)N + 1, 0);
+  // line_off is uploaded asynchronously: the stream is drained on every return path before the vector goes
+  struct Drain {
+    hipStream_t stream;
+    ~Drain() { (void)hipStreamSynchronize(stream); }
+  } drain{ctx->stream};
+  const size_t quads_b = total * 8 * sizeof(float), off_b = ((size_t)N + 1) * sizeof(int32_t), words_b = total * sizeof(int32_t);
+  const size_t counts_b = (size_t)N * sizeof(int32_t), line_off_b = ((size_t)N + 1) * sizeof(long long);
+  const size_t boxes_b = line_boxes ? quads_b : 0;  // a page has at most as many lines as words
+  Staging st{ctx, ctx->io, "kocr_group_lines", false};
+  KOCR_TRY(st.reserve(0, {quads_b, off_b, words_b, words_b, counts_b}, {boxes_b, boxes_b, line_off_b}));
+  const float* d_quads;
+  const int32_t* d_off;
+  int32_t *d_line_of, *d_order, *d_counts;
+  float *d_scratch = nullptr, *d_boxes = nullptr;
+  KOCR_TRY(st.in(quads, quads_b, d_quads));
+  KOCR_TRY(st.in(offsets, off_b, d_off));
+  KOCR_TRY(st.out(line_of, words_b, d_line_of));
+  KOCR_TRY(st.out(order, words_b, d_order));
+  KOCR_TRY(st.out(line_counts, counts_b, d_counts));
+  if (line_boxes) KOCR_TRY(st.scratch(boxes_b, d_scratch));
+  KOCR_TRY(launch_lines_group(ctx, d_quads, d_off, N, max_words, rule, d_line_of, d_order, d_counts, d_scratch));
+  KOCR_TRY(st.back(line_of, d_line_of, words_b));
+  KOCR_TRY(st.back(order, d_order, words_b));
+  KOCR_TRY(st.back(line_counts, d_counts, counts_b));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the counts size the packed boxes; a failure is reported
+  for (int i = 0; i < N; ++i) line_off[i + 1] = line_off[i] + line_counts[i];
+  const long long lines = line_off[N];
+  if (true_lines) *true_lines = lines;
+  if (!line_boxes) return KOCR_OK;
+  if (lines > cap_lines)
+    KOCR_FAIL(ctx, KOCR_ECAPACITY, fn + ": " + std::to_string(lines) + " lines, line_boxes holds " + std::to_string((long long)cap_lines));
+  const size_t packed_b = (size_t)lines * 8 * sizeof(float);
+  const long long* d_line_off;
+  KOCR_TRY(st.upload((const long long*)line_off.data(), line_off_b, d_line_off));
+  KOCR_TRY(st.scratch(packed_b, d_boxes));
+  KOCR_TRY(launch_lines_pack(ctx, d_scratch, d_off, d_line_off, N, d_boxes));
+  KOCR_TRY(st.download(line_boxes, (const float*)d_boxes, packed_b));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // results are complete on return; a failure is reported
+  return KOCR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kocr_group_lines(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, double cos_max, double min_height_ratio,
+                     double max_offset, double max_gap, int32_t* line_of, int32_t* order, int32_t* line_counts, float* line_boxes,
+                     int64_t cap_lines, int64_t* true_lines, int flags) {
+  if (!ctx) return KOCR_EINVAL;
+  const LinesRule rule{cos_max, min_height_ratio, max_offset, max_gap};
+  return lines_run(ctx, N, quads, offsets, rule, line_of, order, line_counts, line_boxes, cap_lines, true_lines, flags);
+}
+
+}  // extern "C"

@@ -1,0 +1,47 @@
+"""What follows recognition: the words of a page grouped into text lines, in reading order, on the GPU (kocr_group_lines;
+DESIGN.md section 4, "Lines").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
+labels that are already grouped -- and there is no host path."""
+import typing
+
+import numpy as np
+
+from . import _lib
+
+
+class Line(typing.NamedTuple):
+    """One text line of a page: ``box`` (4, 2) float32, the bounding rectangle along the line's axis [tl, tr, br, bl];
+    ``words``: the indices of its words in the page's list of boxes, in reading order."""
+    box: np.ndarray
+    words: typing.List[int]
+
+
+def _context(ctx):
+    return _lib.default_context() if ctx is None or ctx is True else ctx
+
+
+def group_lines(box_groups, ctx=None, **rule):
+    """Per image the text lines of its word boxes: ``box_groups`` is a list (one entry per image) of (n_i, 4, 2) boxes
+    [tl, tr, br, bl], e.g. ``Detector.detect``'s result or the boxes of ``Pipeline.recognize``.  Returns, per image, a list
+    of ``Line(box, words)`` from the top of the page to its bottom.  One GPU call for the whole batch; ``ctx`` is a
+    ``Context`` (None or True: the default one).  ``rule``: ``max_angle`` (degrees, default 15), ``min_height_ratio`` (0.5),
+    ``max_offset`` (0.5), ``max_gap`` (1.5) -- when two words belong to one line, see ``Context.group_lines``.  The defaults
+    are judgement, not fitted to real pages.  Columns are not detected: two columns side by side interleave.  At most 2048
+    words per image (ValueError)."""
+    unknown = set(rule) - {"max_angle", "min_height_ratio", "max_offset", "max_gap"}
+    if unknown:
+        raise TypeError(f"group_lines: unknown rule parameter(s) {sorted(unknown)}")
+    counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
+    offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
+    line_of, order, line_counts, boxes = _context(ctx).group_lines(quads, offsets, **rule)
+    pages, line = [], 0
+    for i, lines in enumerate(line_counts.tolist()):
+        words = order[offsets[i]:offsets[i + 1]].tolist()
+        # `order` lists the words line after line; line_of says how many each line has
+        page, at = [], 0
+        lengths = np.bincount(line_of[offsets[i]:offsets[i + 1]], minlength=lines).tolist() if lines else []
+        for k in range(lines):
+            page.append(Line(boxes[line + k], words[at:at + lengths[k]]))
+            at += lengths[k]
+        pages.append(page)
+        line += lines
+    return pages

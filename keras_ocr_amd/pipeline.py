@@ -1,7 +1,7 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
 import numpy as np
 
-from . import _lib, detection, evaluation as _evaluation, lexicon as _lexicon, recognition, scores as _scores, tools
+from . import _lib, detection, evaluation as _evaluation, layout as _layout, lexicon as _lexicon, recognition, scores as _scores, tools
 
 
 def beam_of(recognition_kwargs):
@@ -111,6 +111,22 @@ class Pipeline:
         ctx = getattr(self.detector, "_ctx", None)
         results, precision_recall = _evaluation.score(dict(enumerate(true)), pred, ctx=True if ctx is None else ctx, **score_kwargs)
         return predictions, results, precision_recall
+
+    def recognize_lines(self, images, detection_kwargs=None, recognition_kwargs=None, **rule):
+        """recognize() with the words of every image grouped into text lines on the GPU (layout.group_lines with the
+        detector's context; DESIGN.md section 4, "Lines").  Returns, per image, a list of ``(text, box, words)`` from the top
+        of the page to its bottom: ``words`` are recognize()'s own ``(text, box)`` tuples of the line in reading order,
+        ``text`` their texts joined by single spaces, ``box`` the (4, 2) float32 rectangle around the line along its axis.
+        ``rule``: ``max_angle``, ``min_height_ratio``, ``max_offset``, ``max_gap`` as ``layout.group_lines``.
+        ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list."""
+        for key in ("beam_width", "lexicon_top"):
+            if (recognition_kwargs or {}).get(key) is not None:
+                raise ValueError(f"recognize_lines joins one text per word: {key} in recognition_kwargs makes every text a list of alternatives")
+        predictions = self.recognize(images, detection_kwargs, recognition_kwargs)
+        ctx = getattr(self.detector, "_ctx", None)
+        pages = _layout.group_lines([[box for _, box in group] for group in predictions], ctx=ctx, **rule)
+        return [[(" ".join(group[j][0] for j in line.words), line.box, [group[j] for j in line.words]) for line in lines]
+                for group, lines in zip(predictions, pages)]
 
     def recognize_padded(self, images, hmax, wmax, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
         """recognize() with the padded detector-input size imposed by the caller (used when a
