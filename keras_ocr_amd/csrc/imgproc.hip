@@ -114,9 +114,10 @@ int launch_resize_pad(kocr_ctx* ctx, const uint8_t* d_src, int n, int sh, int sw
 // ---------------------------------------------------------------------------------------------------------------------
 // Float images (round 5): cv2.resize of a float32 image interpolates in float (tools.py:394 hands cv2 whatever dtype it
 // is given): source coordinate (d + 0.5) (src / dst) - 0.5 in double, tap index = floor, weight a = float(f - floor(f)) (0
-// left of the image), taps clamped to the image (replicated border), horizontal pass then vertical pass, float32
-// arithmetic in exactly that order -- this file is built with -ffp-contract=off, so the result equals the numpy statement of
-// the same steps (oracle/tools.py::resize_linear_float) bit for bit.  Pads to (Hmax, Wmax) with cval like resize_pad_kernel.
+// left of the image and on or right of its last pixel, where both taps are the same clamped pixel), taps clamped to the
+// image (replicated border), horizontal pass then vertical pass, float32 arithmetic in exactly that order -- this file is
+// built with -ffp-contract=off, so the result equals the numpy statement of the same steps
+// (oracle/tools.py::resize_linear_float) bit for bit.  Pads to (Hmax, Wmax) with cval like resize_pad_kernel.
 // ---------------------------------------------------------------------------------------------------------------------
 struct ResizeTablesF {
   int* xi0;
@@ -159,7 +160,7 @@ int launch_resize_pad_f32(kocr_ctx* ctx, const float* d_src, int n, int sh, int 
       const double f = (d + 0.5) * ((double)src_n / (double)dst_n) - 0.5;
       long s = (long)std::floor(f);
       float w = (float)(f - (double)s);
-      if (s < 0) w = 0.f;
+      if (s < 0 || s >= src_n - 1) w = 0.f;  // both taps are the one clamped pixel: the pass returns it unchanged
       const long c0 = std::min<long>(std::max<long>(s, 0), src_n - 1);
       i0[d] = (int)c0;
       i1[d] = (int)std::min<long>(c0 + 1, src_n - 1);

@@ -280,21 +280,13 @@ def invert3(M):
     return t
 
 
-def warp_perspective_u8(image, M, dsize, assoc="pixel"):
-    """cv2.warpPerspective(image, M, dsize) — 2-D uint8, INTER_LINEAR, BORDER_CONSTANT 0.
-
-    ``assoc``: floating-point association of the coordinate numerators.  "pixel" (the oracle's and the device code's
-    order) evaluates ``(Mi0 x + Mi1 y) + Mi2`` per pixel.  "blockwise" is the order OpenCV's WarpPerspectiveInvoker is
-    believed to use (imgwarp.cpp; not executable here, no cv2): per block of 64 columns starting at bx,
-    ``X0 = (Mi0 bx + Mi1 y) + Mi2`` and per pixel ``X0 + Mi0 x1`` with x = bx + x1 (likewise Y and W).  The two differ
-    by one float64 rounding; that can move a 1/32-pixel coordinate across a rounding tie and with it a crop pixel by
-    one grey level.  tests/test_oracle_cpu.py::test_warp_association_orders_differ_in_few_pixels counts how often."""
+def warp_coordinates(M, dsize, assoc="pixel"):
+    """The source coordinates cv2.warpPerspective samples at, in 1/32 pixel: (X, Y) int64 arrays of shape (dh, dw).
+    M^-1 by the adjugate, the three sums per pixel in float64, ``32 / W0`` (0 where W0 == 0, so such a pixel samples source
+    pixel (0, 0)), the products clamped to the int32 range BEFORE rounding half to even (saturate_cast<int>).  Shared by the
+    uint8 and the float warp: the coordinate does not depend on the image type.  ``assoc``: see warp_perspective_u8."""
     dw, dh = int(dsize[0]), int(dsize[1])
-    H, W = image.shape[:2]
     Mi = np.array(invert3(M), dtype=np.float64)
-    out = np.zeros((dh, dw), dtype=np.uint8)
-    if dw <= 0 or dh <= 0:
-        return out
     xs = np.arange(dw, dtype=np.float64)[None, :]
     ys = np.arange(dh, dtype=np.float64)[:, None]
     if assoc == "pixel":
@@ -316,6 +308,24 @@ def warp_perspective_u8(image, M, dsize, assoc="pixel"):
     fY = np.clip(Y0 * Wi, -2147483648.0, 2147483647.0)
     X = np.rint(fX).astype(np.int64)  # saturate_cast<int>: round half to even
     Y = np.rint(fY).astype(np.int64)
+    return np.broadcast_to(X, (dh, dw)), np.broadcast_to(Y, (dh, dw))
+
+
+def warp_perspective_u8(image, M, dsize, assoc="pixel"):
+    """cv2.warpPerspective(image, M, dsize) — 2-D uint8, INTER_LINEAR, BORDER_CONSTANT 0.
+
+    ``assoc``: floating-point association of the coordinate numerators.  "pixel" (the oracle's and the device code's
+    order) evaluates ``(Mi0 x + Mi1 y) + Mi2`` per pixel.  "blockwise" is the order OpenCV's WarpPerspectiveInvoker is
+    believed to use (imgwarp.cpp; not executable here, no cv2): per block of 64 columns starting at bx,
+    ``X0 = (Mi0 bx + Mi1 y) + Mi2`` and per pixel ``X0 + Mi0 x1`` with x = bx + x1 (likewise Y and W).  The two differ
+    by one float64 rounding; that can move a 1/32-pixel coordinate across a rounding tie and with it a crop pixel by
+    one grey level.  tests/test_oracle_cpu.py::test_warp_association_orders_differ_in_few_pixels counts how often."""
+    dw, dh = int(dsize[0]), int(dsize[1])
+    H, W = image.shape[:2]
+    out = np.zeros((dh, dw), dtype=np.uint8)
+    if dw <= 0 or dh <= 0:
+        return out
+    X, Y = warp_coordinates(M, (dw, dh), assoc)
     sx, sy = X >> 5, Y >> 5
     ax, ay = X & 31, Y & 31
     img = image.astype(np.int64)
@@ -360,6 +370,20 @@ def warp_box(image, box, target_height, target_width):
 # from this image: checked against torch's half-pixel bilinear interpolation and against the fixed-point uint8 warp only
 # (tests/test_oracle_cpu.py) -- "parity unpinned" for the float path.
 # ---------------------------------------------------------------------------------------------------------------------
+def resize_float_taps(dst_n, src_n):
+    """One axis of resize_linear_float: (i0, i1, a) -- the two source indices of every destination index and the float32
+    weight of the second (0 wherever the index was clamped: left of the first pixel, on or right of the last).  Until the
+    geometry edge tests the weight was zeroed on the left only, so at the right / bottom border and on a 1-pixel axis the pass
+    computed v * (1 - a) + v * a, an ulp off v for some v."""
+    f = (np.arange(dst_n, dtype=np.float64) + 0.5) * (src_n / dst_n) - 0.5
+    i0 = np.floor(f).astype(np.int64)
+    a = (f - i0).astype(np.float32)
+    a[(i0 < 0) | (i0 >= src_n - 1)] = 0  # both taps are the one clamped pixel: OpenCV zeroes the weight, the pass returns the pixel
+    i0 = np.clip(i0, 0, src_n - 1)
+    i1 = np.clip(i0 + 1, 0, src_n - 1)
+    return i0, i1, a
+
+
 def resize_linear_float(image, dsize):
     """cv2.resize(image, dsize=(width, height)) for a float image, INTER_LINEAR: source coordinate
     (d + 0.5) * (src / dst) - 0.5, taps clamped to the image (replicated border), horizontal pass then vertical
@@ -369,18 +393,8 @@ def resize_linear_float(image, dsize):
     sh, sw = src.shape[:2]
     if (dw, dh) == (sw, sh):
         return src.copy()
-
-    def taps(dst_n, src_n):
-        f = (np.arange(dst_n, dtype=np.float64) + 0.5) * (src_n / dst_n) - 0.5
-        i0 = np.floor(f).astype(np.int64)
-        a = (f - i0).astype(np.float32)
-        a[i0 < 0] = 0
-        i0 = np.clip(i0, 0, src_n - 1)
-        i1 = np.clip(i0 + 1, 0, src_n - 1)
-        return i0, i1, a
-
-    x0, x1, ax = taps(dw, sw)
-    y0, y1, ay = taps(dh, sh)
+    x0, x1, ax = resize_float_taps(dw, sw)
+    y0, y1, ay = resize_float_taps(dh, sh)
     ax = ax.reshape((1, dw) + (1,) * (src.ndim - 2))
     ay = ay.reshape((dh, 1) + (1,) * (src.ndim - 2))
     rows = src[:, x0] * (np.float32(1) - ax) + src[:, x1] * ax
@@ -393,36 +407,18 @@ def rgb2gray_float(image):
     return im[..., 0] * np.float32(0.299) + im[..., 1] * np.float32(0.587) + im[..., 2] * np.float32(0.114)
 
 
-def warp_box_float(gray, box, target_height=31, target_width=200):
-    """tools.warpBox (tools.py:61-117, margin 0, cval 0) of a 2-D float image: get_rotated_box, integer width / height,
-    homography box -> [[0,0],[s w,0],[s w,s h],[0,s h]], cv2.warpPerspective with INTER_LINEAR (source coordinates rounded
-    to 1/32 pixel as OpenCV's remap does, float weights, constant-0 border), pasted top-left into target_height x
-    target_width zeros."""
-    box, _ = get_rotated_box(box)
-    w, h = get_rotated_width_height(box)
-    scale = min(target_width / w, target_height / h)  # ZeroDivisionError for an empty box, as in the reference
-    dst = np.array([[0, 0], [scale * w, 0], [scale * w, scale * h], [0, scale * h]], np.float32).astype(np.float64)
-    srcq = np.asarray(box, np.float32).astype(np.float64)
-    a, b = [], []
-    for (x, y), (u, v) in zip(srcq, dst):  # getPerspectiveTransform: 8 x 8 system for M (src -> dst)
-        a.append([x, y, 1, 0, 0, 0, -x * u, -y * u])
-        a.append([0, 0, 0, x, y, 1, -x * v, -y * v])
-        b += [u, v]
-    m = np.append(np.linalg.solve(np.array(a), np.array(b)), 1.0).reshape(3, 3)
-    mi = np.linalg.inv(m)
-    cw, ch = int(scale * w), int(scale * h)
-    out = np.zeros((target_height, target_width), np.float32)
-    cw, ch = min(cw, target_width), min(ch, target_height)
-    if cw <= 0 or ch <= 0:
+def warp_perspective_float(image, M, dsize):
+    """cv2.warpPerspective(image, M, dsize) of a 2-D float image, INTER_LINEAR, BORDER_CONSTANT 0: the source coordinates of
+    the uint8 warp (warp_coordinates: 1/32 pixel, as OpenCV's remap tables), float32 weights a / 32, the four products
+    summed in the order t00 w00 + t01 w01 + t10 w10 + t11 w11."""
+    dw, dh = int(dsize[0]), int(dsize[1])
+    out = np.zeros((max(dh, 0), max(dw, 0)), np.float32)
+    if dw <= 0 or dh <= 0:
         return out
-    xs, ys = np.meshgrid(np.arange(cw, dtype=np.float64), np.arange(ch, dtype=np.float64))
-    den = mi[2, 0] * xs + mi[2, 1] * ys + mi[2, 2]
-    den = np.where(den != 0, 1.0 / den, 0.0)
-    fx = np.rint((mi[0, 0] * xs + mi[0, 1] * ys + mi[0, 2]) * den * 32).astype(np.int64)
-    fy = np.rint((mi[1, 0] * xs + mi[1, 1] * ys + mi[1, 2]) * den * 32).astype(np.int64)
+    fx, fy = warp_coordinates(M, (dw, dh))
     x0, y0 = fx >> 5, fy >> 5
     ax, ay = ((fx & 31) / 32.0).astype(np.float32), ((fy & 31) / 32.0).astype(np.float32)
-    g = np.asarray(gray, np.float32)
+    g = np.asarray(image, np.float32)
     hh, ww = g.shape
 
     def tap(yy, xx):
@@ -430,6 +426,22 @@ def warp_box_float(gray, box, target_height=31, target_width=200):
         return np.where(ok, g[np.clip(yy, 0, hh - 1), np.clip(xx, 0, ww - 1)], np.float32(0))
 
     one = np.float32(1)
-    out[:ch, :cw] = (tap(y0, x0) * ((one - ax) * (one - ay)) + tap(y0, x0 + 1) * (ax * (one - ay))
-                     + tap(y0 + 1, x0) * ((one - ax) * ay) + tap(y0 + 1, x0 + 1) * (ax * ay))
+    out[:] = (tap(y0, x0) * ((one - ax) * (one - ay)) + tap(y0, x0 + 1) * (ax * (one - ay))
+              + tap(y0 + 1, x0) * ((one - ax) * ay) + tap(y0 + 1, x0 + 1) * (ax * ay))
+    return out
+
+
+def warp_box_float(gray, box, target_height=31, target_width=200):
+    """tools.warpBox (tools.py:61-117, margin 0, cval 0) of a 2-D float image: the scalar half of the uint8 statement
+    (warp_box_params: get_rotated_box, integer width / height, the homography by the fixed-order LU, ZeroDivisionError for an
+    empty box as in the reference), warp_perspective_float, pasted top-left into target_height x target_width zeros.
+
+    Until the geometry edge tests this function solved the homography with numpy.linalg (LAPACK) and formed the coordinate
+    as ``X0 * (1 / W0) * 32`` without the int32 clamp: a second, unpinned statement of what warp_perspective_u8 already
+    states, one rounding away from it and from the device code at a few pixels per crop."""
+    _, _, _, M, (cw, ch), _ = warp_box_params(box, target_height, target_width)
+    out = np.zeros((target_height, target_width), np.float32)
+    cw, ch = min(cw, target_width), min(ch, target_height)
+    if cw > 0 and ch > 0:
+        out[:ch, :cw] = warp_perspective_float(gray, M, (cw, ch))
     return out

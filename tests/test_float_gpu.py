@@ -7,6 +7,8 @@ differ in the last bit and a source coordinate crosses a 1/32-pixel tie."""
 import numpy as np
 import pytest
 
+from tests.geometry_cases import oracle_crops_f32
+
 pytestmark = pytest.mark.gpu
 
 
@@ -47,7 +49,7 @@ def test_float_warp_equals_the_oracle_statement(ctx):
                       [[5, 5], [60, 9], [58, 30], [3, 26]], [[100, 50], [138, 50], [138, 88], [100, 88]]], np.float32)
     got = ctx.warp_crops_f32(rgb[None], [boxes], 31, 200)
     gray = otools.rgb2gray_float(rgb)
-    want = np.stack([otools.warp_box_float(gray, b, 31, 200) for b in boxes])
+    want = oracle_crops_f32(rgb[None], [boxes], 31, 200)
     assert got.shape == want.shape == (4, 31, 200)
     differs = got != want
     print(f"float warp: {int(differs.sum())} of {differs.size} crop pixels differ from the numpy statement, max |d| "

@@ -5,19 +5,9 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.geometry_cases import oracle_crops as _oracle_crops
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle_crops(images, box_groups):
-    from oracle import tools as otools
-
-    crops = []
-    for im, boxes in zip(images, box_groups):
-        gray = otools.rgb2gray_u8(im)
-        for box in boxes:
-            crops.append(otools.warp_box(gray, box, 31, 200))
-    return np.array(crops, dtype="float32") / 255 if crops else np.zeros((0, 31, 200), np.float32)
 
 
 def test_crops_match_oracle(ctx):
