@@ -92,11 +92,19 @@ __device__ __forceinline__ void uf_union(int* L, int a, int b) {
   }
 }
 
+// Order-preserving int key of a float, for the integer atomicMax of K4 and the comparison of K5: it orders values as np.max
+// followed by < does (detection.py:240).  A zero of either sign has key 0 (-0.0 == +0.0); a NaN of either sign has key
+// INT_MAX, above every number, so one NaN pixel makes the component's maximum NaN.  Integer tests only: no float compare
+// that a denormal mode could change.
 __device__ __forceinline__ int float_key(float f) {
   const int b = __float_as_int(f);
+  const int mag = b & 0x7fffffff;
+  if (mag > 0x7f800000) return INT_MAX;
+  if (mag == 0) return 0;
   return b >= 0 ? b : b ^ 0x7fffffff;
 }
-__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }  // float_key's inverse
+// float_key's inverse: key 0 -> +0.0, INT_MAX -> a NaN (bits 0x7fffffff)
+__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
 
 // ---- K1 -------------------------------------------------------------------------------
 __global__ void k_threshold(PPArgs p) {
@@ -151,7 +159,8 @@ __global__ void k_flatten_stats(PPArgs p) {
 __device__ __forceinline__ bool comp_kept(const PPArgs& p, size_t i) {
   if (!(p.flags[i] & 1) || p.label[i] != (int)i) return false;
   if (p.area[i] < p.size_thr) return false;                 // detection.py:233-236
-  if (p.tmax[i] < float_key(p.det_thr)) return false;       // detection.py:240-241
+  const int kthr = float_key(p.det_thr);
+  if (kthr != INT_MAX && p.tmax[i] < kthr) return false;    // detection.py:240-241; max < NaN is false, NaN < thr is false
   return true;
 }
 

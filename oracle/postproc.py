@@ -185,7 +185,7 @@ def get_boxes(y_pred, detection_threshold=0.7, text_threshold=0.4, link_threshol
             else:
                 box = np.array(np.roll(box, 4 - box.sum(axis=1).argmin(), 0))
             boxes.append(f32(2) * box)
-            dbg.append(dict(component=component_id, size=size, niter=niter, hull=hull))
+            dbg.append(dict(component=component_id, size=size, niter=niter, roi=(sx, sy, ex, ey), hull=hull))
         box_groups.append(np.array(boxes))
         debug.append(dbg)
     if return_debug:

@@ -7,6 +7,9 @@ character scores       for the k-th emitted label, the maximum of probs[t, label
                        that emitted it (first maximum on ties), 0 behind the decode;
 detection score        the maximum of the text map over the pixels of a box's connected component (scipy.ndimage.label,
                        cross structure), the component ids being those oracle.postproc.get_boxes reports for the kept boxes.
+                       It is the number ``np.max`` gives and ``<`` compares with detection_threshold: a NaN anywhere in the
+                       component makes it NaN, and a zero maximum is reported as +0.0 whatever the signs of the zeros it was
+                       taken over (-0.0 == +0.0, and np.max may return either).
 """
 import itertools
 
@@ -87,7 +90,8 @@ def no_ties(probs):
 
 def detection_scores(heat, debug, text_threshold=0.4, link_threshold=0.4):
     """heat: (N, h, w, 2) float32; debug: oracle.postproc.get_boxes(..., return_debug=True)[1] for the SAME heat-maps and
-    thresholds.  Returns per image a float32 array: max of the text map over each kept box's component."""
+    thresholds.  Returns per image a float32 array: max of the text map over each kept box's component (NaN if it holds one;
+    a zero as +0.0)."""
     from scipy import ndimage
 
     cross = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]], bool)
@@ -96,5 +100,5 @@ def detection_scores(heat, debug, text_threshold=0.4, link_threshold=0.4):
         text = np.asarray(y[..., 0], np.float32)
         link = np.asarray(y[..., 1], np.float32)
         labels, _ = ndimage.label((text > np.float32(text_threshold)) | (link > np.float32(link_threshold)), structure=cross)
-        out.append(np.array([text[labels == d["component"]].max() for d in dbg], np.float32))
+        out.append(np.array([text[labels == d["component"]].max() for d in dbg], np.float32) + np.float32(0))  # -0.0 + 0.0 = +0.0
     return out

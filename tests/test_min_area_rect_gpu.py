@@ -24,21 +24,9 @@ def _check(got, want):
 def _statements(y, **kw):
     """(exact boxes, cv32 boxes, per-component max corner deviation between the two) of the oracle's getBoxes on y."""
     from oracle import postproc
+    from tests.postproc_cases import rule_statements
 
-    want, dbg = postproc.get_boxes(y, return_debug=True, **kw)
-    exact, cv32, dev = [], [], []
-    for boxes, comps in zip(want, dbg):
-        e, c = [], []
-        for comp in comps:
-            hull = comp["hull"]
-            hx, hy = np.array([p[0] for p in hull]), np.array([p[1] for p in hull])
-            e.append(postproc.box_from_hull(hull, hx, hy, cv32=False))
-            c.append(postproc.box_from_hull(hull, hx, hy, cv32=True))
-            dev.append(float(np.abs(e[-1] - c[-1]).max()))
-        assert len(e) == len(boxes) and all(np.array_equal(a, b) for a, b in zip(e, boxes))
-        exact.append(np.array(e) if e else np.array([]))
-        cv32.append(np.array(c) if c else np.array([]))
-    return exact, cv32, np.array(dev)
+    return rule_statements(*postproc.get_boxes(y, return_debug=True, **kw))
 
 
 def _hull_shapes():
