@@ -301,6 +301,49 @@ int kocr_group_lines(kocr_ctx* ctx, int N, const float* quads, const int32_t* of
                      double max_offset, double max_gap, int32_t* line_of, int32_t* order, int32_t* line_counts, float* line_boxes,
                      int64_t cap_lines, int64_t* true_lines, int flags);
 
+/* ---- characters: the character boxes of word boxes, read off the detector's region map (no reference counterpart) ----------
+ * The rule is tests/chars_statement.py ("Characters"), float64 in the statement's operation order: the
+ * counts equal the statement's and the quads and scores carry its float32 bits.  Channel 0 of a heat-map is a per-character
+ * Gaussian score.  A word is a quad [tl, tr, br, bl] in detector-input pixels as kocr_get_boxes returns it (heat-map pixels
+ * x 2).  Its region is sampled bilinearly (pixels outside the map count as 0) on a grid of n_cols = min(KOCR_CHARS_MAX_COLS,
+ * ceil(width)) by n_rows = min(KOCR_CHARS_MAX_ROWS, ceil(height)) cells, width and height in heat-map pixels; the profile
+ * is the maximum over the rows per column.  Columns below extent_threshold at either end are trimmed; a column is a peak
+ * candidate when it reaches peak_threshold, exceeds its left and is not below its right neighbour; scanning from the left,
+ * a candidate starts a new character when the profile's minimum since the current peak is at most valley_ratio x the lower
+ * of the two peaks (the cut is that minimum's first column), and otherwise replaces the current peak when it is higher.
+ * Every character is a slice of the word quad between two cuts, at the word's full height; its score is the profile at
+ * its peak.  The profile runs along tl -> tr whatever the text's direction; characters whose blobs merge above
+ * valley_ratio come out as one box; a word without width or height, or without a peak, has no characters.
+ * heat N x h x w x 2 float32 (a device pointer when on_device is set); quads float32 [total][4][2] with offsets int32
+ * [N + 1] (page i = words [offsets[i], offsets[i + 1])), both HOST arrays.  Outputs, all HOST: char_counts int32 [total];
+ * char_quads float32 [cap_chars][4][2] and char_scores float32 [cap_chars], all characters of all words in word order.
+ * cap_chars is their capacity in characters: with more the call returns KOCR_ECAPACITY; *true_chars (may be NULL) receives
+ * the number of characters whenever the kernel ran, and char_counts is complete then too.  char_quads == NULL with cap_chars
+ * == 0 skips the boxes and scores.  KOCR_EINVAL with a message, before anything is launched: offsets that do not start at 0
+ * or decrease, a non-finite coordinate (naming page and word), a parameter out of range -- all finite, 0 < peak_threshold,
+ * 0 <= valley_ratio <= 1, 0 <= extent_threshold <= peak_threshold.  N == 0 and pages without words are valid; flags is
+ * reserved and must be 0.  Two launches on the ctx stream (profiler rows chars_split, chars_pack), one wave per word; a
+ * word's results do not depend on what else is in the batch.  The results are complete on return.  Like every other call that
+ * processes images it ends the validity of resident results.
+ * kocr_set_char_boxes(ctx, 1, ...) (default off; kocr_get_char_boxes returns the switch and the parameters, any pointer may
+ * be NULL) makes kocr_get_boxes / kocr_detect / kocr_pipeline run the same two launches on the heat-maps and boxes they have
+ * in HBM, after the post-processing that succeeded, and leave the characters resident; with on == 0 the parameters are
+ * ignored and kept, and the calls launch and allocate what they always did.  kocr_detection_char_boxes fetches them:
+ * char_counts N x cap int32 (row i holds counts[i] values in box order, the rest 0), cap >= the cap the results were produced
+ * with (as kocr_detection_scores); char_quads / char_scores / cap_chars / true_chars as above (KOCR_ECAPACITY with
+ * *true_chars and char_counts complete; NULL with 0 skips them).  Valid and refused like kocr_detection_scores: until the next
+ * call on the context that processes images, KOCR_EINVAL when nothing is resident or when the results were produced with the
+ * switch off; after KOCR_ECAPACITY from kocr_pipeline they are resident together with kocr_pipeline_results'. */
+#define KOCR_CHARS_MAX_COLS 512
+#define KOCR_CHARS_MAX_ROWS 32
+int kocr_char_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, const float* quads, const int32_t* offsets,
+                    double peak_threshold, double valley_ratio, double extent_threshold, int32_t* char_counts, float* char_quads,
+                    float* char_scores, int64_t cap_chars, int64_t* true_chars, int on_device, int flags);
+int kocr_set_char_boxes(kocr_ctx* ctx, int on, double peak_threshold, double valley_ratio, double extent_threshold);
+int kocr_get_char_boxes(const kocr_ctx* ctx, int* on, double* peak_threshold, double* valley_ratio, double* extent_threshold);
+int kocr_detection_char_boxes(kocr_ctx* ctx, int32_t* char_counts, float* char_quads, float* char_scores, int cap, int64_t cap_chars,
+                              int64_t* true_chars);
+
 /* ---- Detector.detect (detection.py:745-785): compute_input + predict + getBoxes in one call; the
  * heat-maps stay in HBM.  Arguments as kocr_craft_forward + kocr_get_boxes; counts is a HOST array. */
 int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int W,

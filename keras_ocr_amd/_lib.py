@@ -101,6 +101,11 @@ def load_library():
                             ctypes.c_int64, vp, ci]),
         "kocr_group_lines": (ci, [vp, ci, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp,
                                   ctypes.c_int64, vp, ci]),
+        "kocr_char_boxes": (ci, [vp, vp, ci, ci, ci, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp, vp, ctypes.c_int64,
+                                 vp, ci, ci]),
+        "kocr_set_char_boxes": (ci, [vp, ci, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+        "kocr_get_char_boxes": (ci, [vp, vp, vp, vp, vp]),
+        "kocr_detection_char_boxes": (ci, [vp, vp, vp, vp, ci, ctypes.c_int64, vp]),
         "kocr_get_boxes": (ci, [vp, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, vp, vp, ci, ci]),
         "kocr_warp_crops": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, ci]),
         "kocr_warp_quads": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
@@ -144,6 +149,34 @@ def _ptr(a):
     if isinstance(a, (int, np.integer)):
         return ctypes.c_void_p(int(a))
     return ctypes.c_void_p(a.ctypes.data)
+
+
+CHAR_RULE_DEFAULTS = {"peak_threshold": 0.4, "valley_ratio": 0.7, "extent_threshold": 0.2}
+
+
+def char_rule(char_boxes):
+    """``char_boxes=True`` or a dict of rule parameters -> the three parameters of include/kocr.h ("characters") as a dict of
+    floats, None for a falsy value.  TypeError for an unknown parameter; the library checks the ranges (ValueError)."""
+    if not char_boxes and not isinstance(char_boxes, dict):
+        return None
+    given = {} if char_boxes is True else dict(char_boxes)
+    unknown = set(given) - set(CHAR_RULE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"char_boxes: unknown rule parameter(s) {sorted(unknown)}")
+    return {k: float(given.get(k, d)) for k, d in CHAR_RULE_DEFAULTS.items()}
+
+
+def _char_lists(counts, quads, scores):
+    """per image an array of per-word character counts + the packed quads and scores -> per image a list of one
+    ``(quads (K, 4, 2), scores (K,))`` pair per word"""
+    pages, at = [], 0
+    for page in counts:
+        words = []
+        for k in np.asarray(page).tolist():
+            words.append((quads[at:at + k].copy(), scores[at:at + k].copy()))
+            at += k
+        pages.append(words)
+    return pages
 
 
 def beam_args(beam_width, top_paths=1):
@@ -354,6 +387,80 @@ class Context:
         finally:
             self.set_scores(old)
 
+    # -- character boxes (include/kocr.h: "characters") ----------------------------------------------------------------
+    def set_char_boxes(self, on=True, peak_threshold=0.4, valley_ratio=0.7, extent_threshold=0.2):
+        """Whether get_boxes / detect / pipeline leave the character boxes of their word boxes resident
+        (kocr_set_char_boxes); ValueError for a rule parameter out of range."""
+        self._check(self._lib.kocr_set_char_boxes(self._h, int(bool(on)), float(peak_threshold), float(valley_ratio),
+                                                  float(extent_threshold)), value_error=True)
+
+    def get_char_boxes(self):
+        """``(on, {"peak_threshold", "valley_ratio", "extent_threshold"})`` (kocr_get_char_boxes)"""
+        on = ctypes.c_int(0)
+        p, r, e = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        self._check(self._lib.kocr_get_char_boxes(self._h, ctypes.byref(on), ctypes.byref(p), ctypes.byref(r), ctypes.byref(e)))
+        return bool(on.value), {"peak_threshold": p.value, "valley_ratio": r.value, "extent_threshold": e.value}
+
+    @contextlib.contextmanager
+    def _char_boxes_scope(self, char_boxes):
+        """The switch for one call (``char_boxes=True`` or a dict of rule parameters); falsy: the context's own setting."""
+        rule = char_rule(char_boxes)
+        if rule is None:
+            yield
+            return
+        old_on, old_rule = self.get_char_boxes()
+        self.set_char_boxes(True, **rule)
+        try:
+            yield
+        finally:
+            self.set_char_boxes(True, **old_rule)  # the parameters, then the switch
+            self.set_char_boxes(old_on, **old_rule)
+
+    def detection_char_boxes(self, counts, cap):
+        """The resident character boxes (kocr_detection_char_boxes): per image a list of one ``(quads (K, 4, 2) float32,
+        scores (K,) float32)`` pair per word box; ValueError when nothing is resident or the results were produced with
+        character boxes off."""
+        counts = np.asarray(counts, dtype=np.int32)
+        per_word = np.zeros((len(counts), int(cap)), dtype=np.int32)
+        chars = ctypes.c_int64(0)
+        self._check(self._lib.kocr_detection_char_boxes(self._h, _ptr(per_word), None, None, int(cap), 0, ctypes.byref(chars)),
+                    value_error=True)
+        quads, scores = np.zeros((chars.value, 4, 2), np.float32), np.zeros(chars.value, np.float32)
+        if chars.value:
+            self._check(self._lib.kocr_detection_char_boxes(self._h, _ptr(per_word), _ptr(quads), _ptr(scores), int(cap), chars.value,
+                                                            ctypes.byref(chars)), value_error=True)
+        return _char_lists([per_word[i, :counts[i]] for i in range(len(counts))], quads, scores)
+
+    def char_boxes(self, heat, box_groups, peak_threshold=0.4, valley_ratio=0.7, extent_threshold=0.2):
+        """The character boxes of word boxes, read off the detector's region map in one call (kocr_char_boxes; DESIGN.md
+        section 4, "Characters"): ``heat`` (N, h, w, 2) float32 heat-maps (host array), ``box_groups`` per image (n_i, 4, 2)
+        word boxes [tl, tr, br, bl] in detector-input pixels as ``get_boxes`` returns them.  Returns, per image, a list of one
+        ``(quads (K, 4, 2) float32, scores (K,) float32)`` pair per word: the characters from tl towards tr, each a slice of
+        the word box at its full height, and the region map's value at each character's peak.  ValueError for a rule
+        parameter out of range (all finite, 0 < peak_threshold, 0 <= valley_ratio <= 1, 0 <= extent_threshold <=
+        peak_threshold) and for a non-finite coordinate (naming page and word)."""
+        y = np.ascontiguousarray(heat, dtype=np.float32)
+        if y.ndim != 4 or y.shape[3] != 2:
+            raise ValueError("heat must have shape (N,h,w,2)")
+        if len(box_groups) != len(y):
+            raise ValueError(f"{len(y)} heat-maps but {len(box_groups)} groups of boxes")
+        n, h, w, _ = y.shape
+        counts, quads = _flatten_boxes(box_groups)
+        off = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
+        per_word = np.zeros(len(quads), np.int32)
+        chars = ctypes.c_int64(0)
+        rule = (float(peak_threshold), float(valley_ratio), float(extent_threshold))
+        cap = max(64, 16 * len(quads))  # a guess; KOCR_ECAPACITY reports the true number
+        while True:
+            out_q, out_s = np.zeros((cap, 4, 2), np.float32), np.zeros(cap, np.float32)
+            rc = self._lib.kocr_char_boxes(self._h, _ptr(y), n, h, w, _ptr(quads), _ptr(off), *rule, _ptr(per_word), _ptr(out_q),
+                                           _ptr(out_s), cap, ctypes.byref(chars), 0, 0)
+            if rc == KOCR_ECAPACITY and chars.value > cap:
+                cap = chars.value
+                continue
+            self._check(rc, value_error=True)
+            return _char_lists([per_word[off[i]:off[i + 1]] for i in range(n)], out_q[:chars.value], out_s[:chars.value])
+
     def detection_scores(self, counts, cap):
         """The resident detection scores (kocr_detection_scores) as a per-image list of (n_i,) float32 arrays; ValueError
         when nothing is resident or the results were produced with scores off."""
@@ -563,27 +670,32 @@ class Context:
 
     # -- detection.getBoxes ----------------------------------------------------------------
     def get_boxes(self, heat, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4,
-                  size_threshold=10, cap=None, min_area_rect=None, return_scores=False):
+                  size_threshold=10, cap=None, min_area_rect=None, return_scores=False, char_boxes=None):
         """heat: (N,h,w,2) float32 host array -> list of (n_i,4,2) float32 arrays
         (``np.array([])`` for an image without boxes, detection.py:286).  ``min_area_rect``: ``"exact"`` /
         ``"opencv"`` for this call only, ``None`` = the context's rule (``set_min_area_rect``).  ``return_scores``:
         ``(boxes, scores)``, scores a list of (n_i,) float32 arrays -- each box's detection score, the maximum of the text map
-        over its component."""
+        over its component.  ``char_boxes`` (True, or a dict of ``char_boxes``' rule parameters): a last element, per image a
+        list of one ``(quads (K,4,2), scores (K,))`` pair per box -- its characters as ``char_boxes`` gives them, computed in
+        the same call on the heat-maps in HBM."""
         y = np.ascontiguousarray(heat, dtype=np.float32)
         if y.ndim != 4 or y.shape[3] != 2:
             raise ValueError("heat must have shape (N,h,w,2)")
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores):
-            return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores)
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._char_boxes_scope(char_boxes):
+            return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores,
+                                   char_rule(char_boxes) is not None)
 
-    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores=False):
+    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores=False,
+                   return_chars=False):
         n, h, w, _ = y.shape
         return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_get_boxes(
             self._h, _ptr(y), n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
-            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0), return_scores)
+            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0), return_scores, return_chars)
 
-    def _boxes_grow_cap(self, n, cap, call, return_scores=False):
+    def _boxes_grow_cap(self, n, cap, call, return_scores=False, return_chars=False):
         """call(boxes, counts, cap) -> rc into (n, cap) buffers, repeated with the true maximum on KOCR_ECAPACITY (the counts
-        hold it); the boxes as a per-image list [, the resident detection scores of the call that succeeded]"""
+        hold it); the boxes as a per-image list [, the resident detection scores of the call that succeeded] [, its resident
+        character boxes]"""
         cap = int(cap) if cap else 1024
         while True:
             boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
@@ -593,26 +705,29 @@ class Context:
                 cap = int(counts.max())
                 continue
             self._check(rc)
+            out = (_box_lists(boxes, counts),)
             if return_scores:
-                return _box_lists(boxes, counts), (self.detection_scores(counts, cap) if n else [])
-            return _box_lists(boxes, counts)
+                out += (self.detection_scores(counts, cap) if n else [],)
+            if return_chars:
+                out += (self.detection_char_boxes(counts, cap) if n else [],)
+            return out if len(out) > 1 else out[0]
 
     # -- Detector.detect, device-resident heat-maps -----------------------------------------------
     def detect(self, images, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,
-               micro_batch=0, cap=None, min_area_rect=None, return_scores=False):
+               micro_batch=0, cap=None, min_area_rect=None, return_scores=False, char_boxes=None):
         """images: (N,H,W,3) uint8 (raw RGB) or float32 (normalised).  Returns list of (n_i,4,2) boxes.
-        ``min_area_rect``, ``return_scores``: as ``get_boxes``."""
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores):
+        ``min_area_rect``, ``return_scores``, ``char_boxes``: as ``get_boxes``."""
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._char_boxes_scope(char_boxes):
             return self._detect(images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch,
-                                cap, return_scores)
+                                cap, return_scores, char_rule(char_boxes) is not None)
 
     def _detect(self, images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap,
-                return_scores=False):
+                return_scores=False, return_chars=False):
         x, dt = _detector_input(images)
         n, h, w, _ = x.shape
         return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_detect(
             self._h, _ptr(x), dt, n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
-            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), return_scores)
+            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), return_scores, return_chars)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
     def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None):
@@ -727,13 +842,22 @@ class Context:
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
-                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None):
+                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns
         (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``.
         ``return_scores``: a third element ``(detection list[(n_i,) f32], log_word (M,) f32, char_scores (M,48) f32)``.
         ``beam=(beam_width, top_paths)``: a last element ``(beam labels (M,K,48) int32, beam log_prob (M,K) f32)`` as
         ``crnn_beam``; boxes, labels and scores are the same bits.  ``lexicon_top=K``: a last element ``(index (M,K) int32,
-        log_prob (M,K) f32)`` as ``crnn_lexicon``."""
+        log_prob (M,K) f32)`` as ``crnn_lexicon``.  ``char_boxes`` (True or a dict of rule parameters): the very last element,
+        the character boxes of every word box as ``get_boxes`` gives them (detector-input px)."""
+        if char_rule(char_boxes) is not None:
+            with self._char_boxes_scope(char_boxes):
+                out = self.pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
+                                    size_threshold, micro_batch, on_device, cap, max_crops, min_area_rect, return_scores, beam,
+                                    lexicon_top)
+                # the boxes' own counts and the cap they were produced with (the largest count after a capacity overflow)
+                counts = [len(b) for b in out[0]]
+                return out + (self.detection_char_boxes(counts, max([int(cap)] + counts)) if len(ptrs) else [],)
         with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
                 self._lexicon_scope(lexicon_top):
             out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,

@@ -15,6 +15,7 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   ctx->last_sc.clear();        // the resident scores likewise
   ctx->last_beam.clear();      // ... and the resident beam alternatives
   ctx->last_lex.clear();       // ... and lexicon matches
+  ctx->last_ch.clear();        // ... and character boxes
   if (bytes <= a.cap) return KOCR_OK;
   if (a.base) {
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -233,7 +234,7 @@ void kocr_destroy(kocr_ctx* ctx) {
   craft_free(ctx);
   crnn_free(ctx);
   for (void* p : ctx->owned) hipFree(p);
-  for (Arena* a : {&ctx->ws, &ctx->pp, &ctx->pp2, &ctx->io, &ctx->pl, &ctx->bx})
+  for (Arena* a : {&ctx->ws, &ctx->pp, &ctx->pp2, &ctx->io, &ctx->pl, &ctx->bx, &ctx->chw, &ctx->chr})
     if (a->base) hipFree(a->base);
   for (auto& pd : ctx->pending) {
     hipEventDestroy(pd.a);
@@ -770,6 +771,7 @@ int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float 
   const int rc = postproc_get_boxes(ctx, d_heat, N, h, w, detection_threshold, text_threshold, link_threshold,
                                     size_threshold, d_boxes, cap, counts, &n_empty, nullptr, &d_scores);
   if (rc != KOCR_OK) return rc;
+  KOCR_TRY(chars_resident(ctx, "kocr_get_boxes", d_heat, N, h, w, d_boxes, cap, counts));
   KOCR_TRY(st.back(boxes, d_boxes, bb));
   KOCR_TRY(st.finish());
   ctx->keep_det_scores(d_scores, N, cap);

@@ -128,6 +128,11 @@ struct CraftNet;
 struct CrnnNet;
 struct Taps;
 
+// the rule of chars.hip (tests/chars_statement.py: check_rule)
+struct CharsRule {
+  double peak_threshold, valley_ratio, extent_threshold;
+};
+
 struct kocr_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -263,11 +268,30 @@ struct kocr_ctx {
   void keep_lexicon(const int* d_index, const float* d_logp, int M) {
     last_lex = {d_index, d_logp, M, lex_top, lex_top > 0, lex_top == 0};
   }
+  // character boxes (kocr_set_char_boxes; DESIGN.md section 4, "Characters"): with the switch on, kocr_get_boxes /
+  // kocr_detect / kocr_pipeline run the two launches of chars.hip on the heat-maps and boxes in HBM (chars_resident) and leave
+  // the packed quads and scores resident for kocr_detection_char_boxes.  Workspace and results live in two arenas of their
+  // own (chw, chr: never allocated while the switch stays off and kocr_char_boxes is not called), because the callers' arenas
+  // are spoken for.  counts / off are host copies: the per-word counts in packed word order and the pages' word offsets.  Valid
+  // like last_sc.
+  bool chars_on = false;
+  CharsRule chars_rule{0.4, 0.7, 0.2};
+  Arena chw, chr;
+  struct LastChars {
+    const float* d_quads = nullptr;   // [total][4][2]
+    const float* d_scores = nullptr;  // [total]
+    std::vector<int32_t> counts, off;
+    int N = 0, cap = 0;
+    long long total = 0;
+    bool valid = false, off_switch = false;  // off_switch: results were produced with the switch off
+    void clear() { valid = off_switch = false; }
+  } last_ch;
   void invalidate_results() {
     last_pl.valid = false;
     last_sc.clear();
     last_beam.clear();
     last_lex.clear();
+    last_ch.clear();
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
@@ -276,6 +300,11 @@ struct kocr_ctx {
     last_sc.cap = cap;
     last_sc.det_valid = scores_on;
     last_sc.det_off = !scores_on;
+    // ... and the character boxes that chars_resident has put beside them
+    last_ch.N = N;
+    last_ch.cap = cap;
+    last_ch.valid = chars_on;
+    last_ch.off_switch = !chars_on;
   }
   void keep_rec_scores(const float* d_logw, const float* d_chars, int M, int lw) {
     last_sc.d_logw = d_logw;
@@ -628,6 +657,28 @@ size_t lines_lds_bytes(int max_words);
 int launch_lines_group(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_words, const LinesRule& rule,
                        int32_t* d_line_of, int32_t* d_order, int32_t* d_line_counts, float* d_boxes);
 int launch_lines_pack(kocr_ctx* ctx, const float* d_scratch, const int32_t* d_off, const long long* d_line_off, int N, float* d_boxes);
+
+// chars.hip: the characters of word boxes from the region map (kocr_char_boxes; DESIGN.md section 4, "Characters").  d_heat
+// [N][h][w][2]; M words in packed word order with d_off [N + 1]; word j of page i is quad d_off[i] + j of d_quads with
+// stride == 0, quad i * stride + j otherwise.  launch_chars_split fills the workspace rows of every word, launch_chars_pack
+// writes the characters of all words in word order: d_char_quads [sum of counts][4][2], d_char_scores [sum of counts].
+constexpr int KOCR_CHARS_MAX_PER_WORD = KOCR_CHARS_MAX_COLS / 2;        // two neighbouring columns are never both peaks
+constexpr int KOCR_CHARS_BOUNDS_STRIDE = KOCR_CHARS_MAX_PER_WORD + 2;  // K + 1 bounds, rows kept 4-byte aligned
+struct CharsWork {
+  int32_t *counts = nullptr, *ncols = nullptr;  // [M]
+  uint16_t* bounds = nullptr;                   // [M][KOCR_CHARS_BOUNDS_STRIDE] column bounds of the characters
+  float* scores = nullptr;                      // [M][KOCR_CHARS_MAX_PER_WORD] profile at the peaks
+};
+size_t chars_workspace_bytes(int N, long M);
+int launch_chars_split(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, const float* d_quads, const int32_t* d_off, int stride,
+                       int M, const CharsRule& rule, const CharsWork& wk);
+int launch_chars_pack(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int stride, int M, const CharsWork& wk,
+                      float* d_char_quads, float* d_char_scores);
+// chars_api.cpp: the two launches on heat-maps and boxes that an entry point has in HBM (boxes [N][cap][4][2], h_counts the
+// host's per-page counts); the results go to ctx->last_ch, which the entry point's keep_det_scores validates.  Nothing happens
+// with the switch off.
+int chars_resident(kocr_ctx* ctx, const char* fn, const float* d_heat, int N, int h, int w, const float* d_boxes, int cap,
+                   const int32_t* h_counts);
 
 // imgproc.hip
 int launch_resize_pad_f32(kocr_ctx* ctx, const float* d_src, int n, int sh, int sw, int C, float* d_dst, int dh, int dw, int Hmax,

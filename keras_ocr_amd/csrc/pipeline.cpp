@@ -59,6 +59,7 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
   const float* d_scores = nullptr;
   KOCR_TRY(postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold,
                               size_threshold, d_boxes, cap, counts, &n_empty, nullptr, &d_scores));
+  KOCR_TRY(chars_resident(ctx, "kocr_detect", d_heat, N, h2, w2, d_boxes, cap, counts));
   KOCR_TRY(st.back(boxes, d_boxes, box_b));
   KOCR_TRY(st.finish());
   ctx->keep_det_scores(d_scores, N, cap);
@@ -211,6 +212,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
                                d_boxes, d_cap, counts, nullptr, &dv);
   }
   KOCR_TRY(rc_pp);
+  KOCR_TRY(chars_resident(ctx, "kocr_pipeline", d_heat, N, h2, w2, d_boxes, d_cap, counts));
   long M = 0;
   for (int k = 0; k < N; ++k) M += counts[k];
   if (n_crops) *n_crops = (int32_t)M;

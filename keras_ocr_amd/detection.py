@@ -5,7 +5,7 @@ import typing
 
 import numpy as np
 
-from . import _lib, tools, weights as _weights
+from . import _lib, layout as _layout, tools, weights as _weights
 
 PRETRAINED_WEIGHTS = {  # detection.py:647-658
     ("clovaai_general", True): {
@@ -90,6 +90,21 @@ def getBoxes(y_pred, detection_threshold=0.7, text_threshold=0.4, link_threshold
     return _lib.default_context().get_boxes(y_pred, detection_threshold=detection_threshold, text_threshold=text_threshold,
                                             link_threshold=link_threshold, size_threshold=size_threshold,
                                             min_area_rect=min_area_rect, return_scores=return_scores)
+
+
+def get_char_boxes(y_pred, box_groups, ctx=None, **rule):
+    """The character boxes of word boxes, read off the region map the detector wrote (channel 0 of ``y_pred``) on the GPU
+    (kocr_char_boxes; DESIGN.md section 4, "Characters"; the reference has no counterpart): ``y_pred`` (N,h,w,2) float32
+    heat-maps, ``box_groups`` what ``getBoxes(y_pred)`` returned.  Returns, per image, one ``layout.Characters(boxes
+    (K,4,2), scores (K,))`` per word box, in detector-input pixels like the boxes.  ``ctx``: a ``Context`` (None: the default
+    one).  ``rule``: ``peak_threshold`` (default 0.4), ``valley_ratio`` (0.7), ``extent_threshold`` (0.2); the defaults are
+    judgement, not fitted to real text.  The profile runs along tl -> tr: vertical text gives slices of the word; characters
+    whose blobs merge come out as one box."""
+    unknown = set(rule) - set(_lib.CHAR_RULE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"get_char_boxes: unknown rule parameter(s) {sorted(unknown)}")
+    context = _lib.default_context() if ctx is None or ctx is True else ctx
+    return _layout.characters_of(context.char_boxes(y_pred, box_groups, **rule))
 
 
 class _CraftModel:
@@ -179,14 +194,17 @@ class Detector:
                 yield X, y
 
     def detect(self, images: typing.List[typing.Union[np.ndarray, str]], detection_threshold=0.7, text_threshold=0.4,
-               link_threshold=0.4, size_threshold=10, min_area_rect=None, return_scores=False, **kwargs):
+               link_threshold=0.4, size_threshold=10, min_area_rect=None, return_scores=False, char_boxes=None, **kwargs):
         """Detector.detect (detection.py:745-785): list/array of same-sized HxWx3 RGB images (or
         paths) -> list of (n_i,4,2) float32 box arrays.  ``min_area_rect``: ``"exact"`` / ``"opencv"`` for this
         call (see ``getBoxes``), ``None`` = the context's rule.  ``return_scores=True``: ``(box_groups, score_groups)`` as
-        ``getBoxes``."""
+        ``getBoxes``.  ``char_boxes`` (True, or a dict of ``get_char_boxes``' rule parameters): a last element
+        ``char_groups``, per image one ``layout.Characters`` per box as ``get_char_boxes`` gives them, computed in the same
+        call from the heat-maps in HBM -- ``(box_groups, char_groups)`` without scores."""
         images = [tools.read(image) for image in images]
+        want_chars = _lib.char_rule(char_boxes) is not None
         if not images:
-            return ([], []) if return_scores else []
+            return ([],) * (1 + bool(return_scores) + want_chars) if return_scores or want_chars else []
         batch = np.stack([np.asarray(im) for im in images])
         if batch.dtype != np.uint8:
             # the reference normalises whatever it is given (detection.py:34-42)
@@ -195,7 +213,8 @@ class Detector:
             batch = batch.astype("float32")
             batch -= mean * 255
             batch /= variance * 255
-        return self._ctx.detect(batch, detection_threshold=detection_threshold, text_threshold=text_threshold,
-                                link_threshold=link_threshold, size_threshold=size_threshold,
-                                micro_batch=kwargs.get("batch_size", 0) or 0, min_area_rect=min_area_rect,
-                                return_scores=return_scores)
+        out = self._ctx.detect(batch, detection_threshold=detection_threshold, text_threshold=text_threshold,
+                               link_threshold=link_threshold, size_threshold=size_threshold,
+                               micro_batch=kwargs.get("batch_size", 0) or 0, min_area_rect=min_area_rect,
+                               return_scores=return_scores, char_boxes=char_boxes)
+        return out[:-1] + (_layout.characters_of(out[-1]),) if want_chars else out

@@ -1,5 +1,5 @@
-"""What follows recognition: the words of a page grouped into text lines, in reading order, on the GPU (kocr_group_lines;
-DESIGN.md section 4, "Lines").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
+"""What follows detection and recognition: the words of a page grouped into text lines, in reading order, on the GPU
+(kocr_group_lines; DESIGN.md section 4, "Lines"), and the type of a word's character boxes (kocr_char_boxes; "Characters").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
 labels that are already grouped -- and there is no host path."""
 import typing
 
@@ -13,6 +13,20 @@ class Line(typing.NamedTuple):
     ``words``: the indices of its words in the page's list of boxes, in reading order."""
     box: np.ndarray
     words: typing.List[int]
+
+
+class Characters(typing.NamedTuple):
+    """The characters of one word box, read off the detector's region map ("Characters"): ``boxes``
+    (K, 4, 2) float32, one quad [tl, tr, br, bl] per character from the word's tl towards its tr, each a slice of the word
+    box at its full height; ``scores`` (K,) float32, the region map's value at each character's peak.  K counts the blobs
+    of the region map, not the letters the recogniser read: the two need not agree."""
+    boxes: np.ndarray
+    scores: np.ndarray
+
+
+def characters_of(char_groups):
+    """``Context.char_boxes``' per-image lists of ``(quads, scores)`` pairs as lists of ``Characters``"""
+    return [[Characters(quads, scores) for quads, scores in page] for page in char_groups]
 
 
 def _context(ctx):

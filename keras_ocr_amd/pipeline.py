@@ -128,12 +128,35 @@ class Pipeline:
         return [[(" ".join(group[j][0] for j in line.words), line.box, [group[j] for j in line.words]) for line in lines]
                 for group, lines in zip(predictions, pages)]
 
+    def recognize_characters(self, images, detection_kwargs=None, recognition_kwargs=None, **rule):
+        """recognize() with the character boxes of every word, read off the detector's region map on the GPU in the same
+        pass ("Characters").  Returns, per image, a list of ``(text, box, characters)``: ``characters``
+        is a ``layout.Characters(boxes (K, 4, 2) float32, scores (K,) float32)``, the characters from the box's tl towards
+        its tr in input-image pixels (like ``box``, through ``tools.adjust_boxes``), and the region map's value at each
+        character's peak.  Texts and word boxes are recognize()'s, bit for bit.  The detector counts blobs of its region
+        map, the recogniser reads letters: ``characters.boxes[k]`` belongs to ``text[k]`` only when ``K == len(text)`` --
+        the caller checks that.  ``rule``: ``peak_threshold``, ``valley_ratio``, ``extent_threshold`` as
+        ``detection.get_char_boxes``.  ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list.
+        A method of its own because recognize() keeps the reference's exact signature."""
+        for key in ("beam_width", "lexicon_top"):
+            if (recognition_kwargs or {}).get(key) is not None:
+                raise ValueError(f"recognize_characters pairs one text per word with its characters: {key} in recognition_kwargs makes "
+                                 "every text a list of alternatives")
+        unknown = set(rule) - set(_lib.CHAR_RULE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"recognize_characters: unknown rule parameter(s) {sorted(unknown)}")
+        box_groups, labels, char_groups = self.recognize_raw(images, None, None, detection_kwargs, recognition_kwargs,
+                                                             char_boxes=_lib.char_rule(dict(rule)))
+        return [[(text, box, characters) for (text, box), characters in zip(words, chars)]
+                for words, chars in zip(self.assemble(box_groups, labels), char_groups)]
+
     def recognize_padded(self, images, hmax, wmax, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
         """recognize() with the padded detector-input size imposed by the caller (used when a
         larger batch is sharded across GPUs: every shard pads to the WHOLE batch's size)."""
         return self.assemble(*self.recognize_raw(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores))
 
-    def recognize_raw(self, images, hmax=None, wmax=None, detection_kwargs=None, recognition_kwargs=None, return_scores=False):
+    def recognize_raw(self, images, hmax=None, wmax=None, detection_kwargs=None, recognition_kwargs=None, return_scores=False,
+                      char_boxes=None):
         """The fused device path up to (but not including) string assembly: returns
         ``(box_groups, label_rows)`` -- per image an (n_i,4,2) float32 array in INPUT-image pixels
         (adjust_boxes already applied, pipeline.py:66-71) and one (sum n_i, 48) int32 array of decoded
@@ -143,7 +166,10 @@ class Pipeline:
         With a ``beam_width`` in ``recognition_kwargs`` the result has four elements: the third is the scores or None, the
         fourth ``(beam labels (sum n_i, K, 48) int32, beam log_prob (sum n_i, K) float32)`` as ``Context.crnn_beam``.  With a
         ``lexicon_top`` it has five: scores or None, None, ``(index (sum n_i, K) int32, log_prob (sum n_i, K) float32)`` as
-        ``Context.crnn_lexicon``."""
+        ``Context.crnn_lexicon``.  ``char_boxes`` (True or a dict of rule parameters): a very last element, per image one
+        ``layout.Characters`` per box, in input-image pixels like the boxes."""
+        if char_boxes is not None and char_boxes is not False:
+            return self._recognize_raw_characters(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
@@ -183,10 +209,59 @@ class Pipeline:
             rest.insert(2, None)
         return (self._adjust(box_groups, scales), *rest)
 
-    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None):
+    def _recognize_raw_characters(self, images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes):
+        """recognize_raw with ``char_boxes``: the same routes, the detector also asked for its character boxes"""
+        if not isinstance(images, np.ndarray):
+            images = [tools.read(image) for image in images]
+        images = [np.ascontiguousarray(im) for im in images]
+        if not images:
+            return self.recognize_raw(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores) + ([],)
+        detection_kwargs = dict(detection_kwargs or {})
+        ctx = getattr(self.detector, "_ctx", None)
+        stagewise = any(im.dtype != np.uint8 for im in images) or ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx
+        if stagewise:
+            import inspect
+
+            try:
+                params = inspect.signature(self.detector.detect).parameters
+            except (TypeError, ValueError):
+                params = {}
+            if "char_boxes" not in params:
+                raise TypeError(f"char_boxes: the detector ({type(self.detector).__name__}.detect) cannot give character boxes "
+                                "(it takes no char_boxes argument)")
+            detection_kwargs["char_boxes"] = char_boxes
+            # the stage-wise route calls detector.detect(**detection_kwargs): its result then ends with the character groups
+            *head, scales, char_groups = self._recognize_stagewise(
+                [im.astype(np.float32) for im in images] if any(im.dtype != np.uint8 for im in images) else images,
+                detection_kwargs, hmax, wmax, return_scores,
+                beam_of(recognition_kwargs), lexicon_of(recognition_kwargs), with_characters=True)
+        else:
+            scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
+            hmax = hmax_ if hmax is None else max(hmax, hmax_)
+            wmax = wmax_ if wmax is None else max(wmax, wmax_)
+            micro_batch = detection_kwargs.pop("batch_size", 0) or 0
+            lexicon_top, beam = lexicon_of(recognition_kwargs), beam_of(recognition_kwargs)
+            box_groups, *rest, groups = ctx.pipeline(
+                images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, hmax, wmax,
+                micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top, char_boxes=char_boxes,
+                **detection_kwargs)
+            if (beam or lexicon_top) and not return_scores:
+                rest.insert(1, None)
+            if lexicon_top:
+                rest.insert(2, None)
+            head = [self._adjust(box_groups, scales), *rest]
+            char_groups = _layout.characters_of(groups)
+        adjusted = [[_layout.Characters(tools.adjust_boxes(boxes=c.boxes, boxes_format="boxes", scale=1 / scale) if scale != 1 else c.boxes,
+                                        c.scores) for c in page] for page, scale in zip(char_groups, scales)]
+        return (*head, adjusted)
+
+    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None,
+                             with_characters=False):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
-        ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size)."""
+        ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size).
+        ``with_characters``: ``detection_kwargs`` holds ``char_boxes``, so ``detect`` also returns its character groups; the
+        result then ends with ``scales, char_groups`` (the groups still in detector-input pixels)."""
         own = getattr(self.detector, "_ctx", None)  # a libkocr-backed detector: its context also resizes (else the default one)
         resized = [tools.resize_image(image, max_scale=self.scale, max_size=self.max_size, **({"ctx": own} if own is not None else {}))
                    for image in images]
@@ -198,11 +273,13 @@ class Pipeline:
         if return_scores:
             detect = _scores.need("detector", self.detector, "detect")
             recognize = _scores.need("recognizer", self.recognizer, "recognize_from_boxes")
-            box_groups, det = detect(images=padded, return_scores=True, **detection_kwargs)
+            box_groups, det, *char_groups = detect(images=padded, return_scores=True, **detection_kwargs)
             pairs = [pair for group in recognize(images=padded, box_groups=box_groups, return_scores=True) for pair in group]
             rows = [t for t, _ in pairs]
         else:
             box_groups = self.detector.detect(images=padded, **detection_kwargs)
+            if with_characters:
+                box_groups, *char_groups = box_groups
             texts = self.recognizer.recognize_from_boxes(images=padded, box_groups=box_groups)
             rows = [t for group in texts for t in group]
         alphabet = self.recognizer.alphabet
@@ -234,9 +311,12 @@ class Pipeline:
                 chars[r, :len(score.characters)] = score.characters
             log_word = np.array([score.log_word for _, score in pairs], np.float32)
             score_rows = ([np.asarray(d, np.float32) for d in det], log_word, chars)
-            return (self._adjust(box_groups, scales), labels, score_rows) + ((beam_rows,) if beam else ()) + \
+            out = (self._adjust(box_groups, scales), labels, score_rows) + ((beam_rows,) if beam else ()) + \
                 ((None, lexicon_rows) if lexicon_top else ())
-        return (self._adjust(box_groups, scales), labels) + ((None, beam_rows) if beam else ()) + ((None, None, lexicon_rows) if lexicon_top else ())
+        else:
+            out = (self._adjust(box_groups, scales), labels) + ((None, beam_rows) if beam else ()) + \
+                ((None, None, lexicon_rows) if lexicon_top else ())
+        return out + (scales, char_groups[0]) if with_characters else out
 
     def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None, return_scores=False):
         """Same as recognize() for a batch already resident in HBM: ``d_ptr`` = device pointer of an
