@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from .results import Results, empty_beam, empty_lexicon, empty_scores
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkocr.so")
 
@@ -177,6 +179,21 @@ def _char_lists(counts, quads, scores):
             at += k
         pages.append(words)
     return pages
+
+
+@contextlib.contextmanager
+def _option_scope(get, set_, value, restore=None):
+    """One of a context's switches for one call: read the old setting, set ``value``, and afterwards hand the old setting to
+    ``restore`` (default: ``set_``).  ``value`` None: the context's own setting, and no call at all."""
+    if value is None:
+        yield
+        return
+    old = get()
+    set_(value)
+    try:
+        yield
+    finally:
+        (restore or set_)(old)
 
 
 def beam_args(beam_width, top_paths=1):
@@ -374,18 +391,9 @@ class Context:
     def get_scores(self):
         return bool(self._check(self._lib.kocr_get_scores(self._h)))
 
-    @contextlib.contextmanager
     def _scores_scope(self, on):
         """The switch for one call (``return_scores=True``); falsy: the context's own setting."""
-        if not on:
-            yield
-            return
-        old = self.get_scores()
-        self.set_scores(True)
-        try:
-            yield
-        finally:
-            self.set_scores(old)
+        return _option_scope(self.get_scores, self.set_scores, True if on else None)
 
     # -- character boxes (include/kocr.h: "characters") ----------------------------------------------------------------
     def set_char_boxes(self, on=True, peak_threshold=0.4, valley_ratio=0.7, extent_threshold=0.2):
@@ -401,20 +409,14 @@ class Context:
         self._check(self._lib.kocr_get_char_boxes(self._h, ctypes.byref(on), ctypes.byref(p), ctypes.byref(r), ctypes.byref(e)))
         return bool(on.value), {"peak_threshold": p.value, "valley_ratio": r.value, "extent_threshold": e.value}
 
-    @contextlib.contextmanager
     def _char_boxes_scope(self, char_boxes):
         """The switch for one call (``char_boxes=True`` or a dict of rule parameters); falsy: the context's own setting."""
         rule = char_rule(char_boxes)
-        if rule is None:
-            yield
-            return
-        old_on, old_rule = self.get_char_boxes()
-        self.set_char_boxes(True, **rule)
-        try:
-            yield
-        finally:
-            self.set_char_boxes(True, **old_rule)  # the parameters, then the switch
-            self.set_char_boxes(old_on, **old_rule)
+
+        def restore(old):
+            self.set_char_boxes(True, **old[1])  # the parameters, then the switch
+            self.set_char_boxes(old[0], **old[1])
+        return _option_scope(self.get_char_boxes, lambda new: self.set_char_boxes(new[0], **new[1]), rule and (True, rule), restore)
 
     def detection_char_boxes(self, counts, cap):
         """The resident character boxes (kocr_detection_char_boxes): per image a list of one ``(quads (K, 4, 2) float32,
@@ -472,16 +474,20 @@ class Context:
     def recognition_scores(self):
         """The resident recogniser scores (kocr_recognition_scores): log_word (M,) and char_scores (M, label width the rows
         were produced with) float32; ValueError as detection_scores."""
-        m, lw = ctypes.c_int32(0), ctypes.c_int32(0)
-        rc = self._lib.kocr_recognition_scores(self._h, None, None, 0, ctypes.byref(m), ctypes.byref(lw))
+        return self._fetch_resident(self._lib.kocr_recognition_scores, 2, lambda m, lw: (
+            np.zeros(m, dtype=np.float32), np.zeros((m, lw), dtype=np.float32)))
+
+    def _fetch_resident(self, fn, n_sizes, allocate):
+        """The protocol of the three recognition_* fetchers: a call with null buffers reports the sizes (crops first) with
+        KOCR_ECAPACITY; ``allocate(*sizes)`` makes the two arrays; a second call fills them (none for zero crops)."""
+        sizes = [ctypes.c_int32(0) for _ in range(n_sizes)]
+        rc = fn(self._h, None, None, 0, *[ctypes.byref(v) for v in sizes])
         if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
             self._check(rc, value_error=True)
-        log_word = np.zeros(m.value, dtype=np.float32)
-        chars = np.zeros((m.value, lw.value), dtype=np.float32)
-        if m.value:
-            self._check(self._lib.kocr_recognition_scores(self._h, _ptr(log_word), _ptr(chars), m.value, None, None),
-                        value_error=True)
-        return log_word, chars
+        first, second = allocate(*[v.value for v in sizes])
+        if sizes[0].value:
+            self._check(fn(self._h, _ptr(first), _ptr(second), sizes[0].value, *[None] * n_sizes), value_error=True)
+        return first, second
 
     # -- beam search (include/kocr.h: "Beam search") --------------------------------------------------------------------
     def crnn_beam(self, crops, beam_width, top_paths=1):
@@ -509,32 +515,15 @@ class Context:
         self._check(self._lib.kocr_get_beam(self._h, ctypes.byref(bw), ctypes.byref(k)))
         return bw.value, k.value
 
-    @contextlib.contextmanager
     def _beam_scope(self, beam):
         """The beam for one call (``beam=(beam_width, top_paths)``); None: the context's own setting."""
-        if beam is None:
-            yield
-            return
-        old = self.get_beam()
-        self.set_beam(*beam_args(*beam))
-        try:
-            yield
-        finally:
-            self.set_beam(*old)
+        return _option_scope(self.get_beam, lambda new: self.set_beam(*new), None if beam is None else beam_args(*beam))
 
     def recognition_beams(self):
         """The resident beam alternatives (kocr_recognition_beams): labels (M, top_paths, label width) int32 and log_prob
         (M, top_paths) float32 as they were produced; ValueError when nothing is resident or the beam was off."""
-        m, lw, k = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        rc = self._lib.kocr_recognition_beams(self._h, None, None, 0, ctypes.byref(m), ctypes.byref(lw), ctypes.byref(k))
-        if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
-            self._check(rc, value_error=True)
-        labels = np.full((m.value, k.value, lw.value), -1, dtype=np.int32)
-        log_prob = np.full((m.value, k.value), -np.inf, dtype=np.float32)
-        if m.value:
-            self._check(self._lib.kocr_recognition_beams(self._h, _ptr(labels), _ptr(log_prob), m.value, None, None, None),
-                        value_error=True)
-        return labels, log_prob
+        return self._fetch_resident(self._lib.kocr_recognition_beams, 3, lambda m, lw, k: (
+            np.full((m, k, lw), -1, dtype=np.int32), np.full((m, k), -np.inf, dtype=np.float32)))
 
     # -- lexicon (include/kocr.h: "Lexicon") ------------------------------------------------------------------------------
     def set_lexicon(self, labels=None, lengths=None):
@@ -585,32 +574,17 @@ class Context:
         self._check(self._lib.kocr_get_lexicon_match(self._h, ctypes.byref(k)))
         return k.value
 
-    @contextlib.contextmanager
     def _lexicon_scope(self, top_words):
-        """The lexicon match for one call; None: the context's own setting."""
-        if top_words is None:
-            yield
-            return
-        old = self.get_lexicon_match()
-        self.set_lexicon_match(top_words)
-        try:
-            yield
-        finally:
-            if self.lexicon_size():  # a lexicon unloaded meanwhile took the switch with it
-                self.set_lexicon_match(old)
+        """The lexicon match for one call; None: the context's own setting.  A lexicon unloaded meanwhile took the switch
+        with it: then nothing is restored."""
+        return _option_scope(self.get_lexicon_match, self.set_lexicon_match, top_words,
+                             lambda old: self.lexicon_size() and self.set_lexicon_match(old))
 
     def recognition_lexicon(self):
         """The resident lexicon matches (kocr_recognition_lexicon): index (M, top_words) int32 and log_prob (M, top_words)
         float32 as they were produced; ValueError when nothing is resident or the match was off."""
-        m, k = ctypes.c_int32(0), ctypes.c_int32(0)
-        rc = self._lib.kocr_recognition_lexicon(self._h, None, None, 0, ctypes.byref(m), ctypes.byref(k))
-        if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
-            self._check(rc, value_error=True)
-        index = np.full((m.value, k.value), -1, dtype=np.int32)
-        log_prob = np.full((m.value, k.value), -np.inf, dtype=np.float32)
-        if m.value:
-            self._check(self._lib.kocr_recognition_lexicon(self._h, _ptr(index), _ptr(log_prob), m.value, None, None), value_error=True)
-        return index, log_prob
+        return self._fetch_resident(self._lib.kocr_recognition_lexicon, 2, lambda m, k: (
+            np.full((m, k), -1, dtype=np.int32), np.full((m, k), -np.inf, dtype=np.float32)))
 
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
@@ -681,53 +655,53 @@ class Context:
         y = np.ascontiguousarray(heat, dtype=np.float32)
         if y.ndim != 4 or y.shape[3] != 2:
             raise ValueError("heat must have shape (N,h,w,2)")
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._char_boxes_scope(char_boxes):
-            return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores,
-                                   char_rule(char_boxes) is not None)
+        return self._get_boxes(y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, min_area_rect,
+                               return_scores, char_boxes).render_detection()
 
-    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, return_scores=False,
-                   return_chars=False):
+    def _get_boxes(self, y, detection_threshold, text_threshold, link_threshold, size_threshold, cap, min_area_rect=None,
+                   return_scores=False, char_boxes=None):
         n, h, w, _ = y.shape
         return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_get_boxes(
             self._h, _ptr(y), n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
-            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0), return_scores, return_chars)
+            int(size_threshold), _ptr(boxes), _ptr(counts), cap, 0), min_area_rect, return_scores, char_boxes)
 
-    def _boxes_grow_cap(self, n, cap, call, return_scores=False, return_chars=False):
-        """call(boxes, counts, cap) -> rc into (n, cap) buffers, repeated with the true maximum on KOCR_ECAPACITY (the counts
-        hold it); the boxes as a per-image list [, the resident detection scores of the call that succeeded] [, its resident
-        character boxes]"""
+    def _boxes_grow_cap(self, n, cap, call, min_area_rect=None, return_scores=False, char_boxes=None):
+        """call(boxes, counts, cap) -> rc into (n, cap) buffers, under the per-call switches, repeated with the true maximum
+        on KOCR_ECAPACITY (the counts hold it): a ``Results`` of the boxes [, the resident detection scores of the call that
+        succeeded] [, its resident character boxes]"""
         cap = int(cap) if cap else 1024
-        while True:
-            boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
-            counts = np.zeros(n, dtype=np.int32)
-            rc = call(boxes, counts, cap)
-            if rc == KOCR_ECAPACITY and n and counts.max() > cap:
-                cap = int(counts.max())
-                continue
-            self._check(rc)
-            out = (_box_lists(boxes, counts),)
-            if return_scores:
-                out += (self.detection_scores(counts, cap) if n else [],)
-            if return_chars:
-                out += (self.detection_char_boxes(counts, cap) if n else [],)
-            return out if len(out) > 1 else out[0]
+        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._char_boxes_scope(char_boxes):
+            while True:
+                boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
+                counts = np.zeros(n, dtype=np.int32)
+                rc = call(boxes, counts, cap)
+                if rc == KOCR_ECAPACITY and n and counts.max() > cap:
+                    cap = int(counts.max())
+                    continue
+                self._check(rc)
+                out = Results(_box_lists(boxes, counts), None)
+                if return_scores:
+                    out.scores = (self.detection_scores(counts, cap) if n else [], None, None)
+                if char_rule(char_boxes) is not None:
+                    out.characters = self.detection_char_boxes(counts, cap) if n else []
+                return out
 
     # -- Detector.detect, device-resident heat-maps -----------------------------------------------
     def detect(self, images, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,
                micro_batch=0, cap=None, min_area_rect=None, return_scores=False, char_boxes=None):
         """images: (N,H,W,3) uint8 (raw RGB) or float32 (normalised).  Returns list of (n_i,4,2) boxes.
         ``min_area_rect``, ``return_scores``, ``char_boxes``: as ``get_boxes``."""
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._char_boxes_scope(char_boxes):
-            return self._detect(images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch,
-                                cap, return_scores, char_rule(char_boxes) is not None)
+        return self._detect(images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap,
+                            min_area_rect, return_scores, char_boxes).render_detection()
 
     def _detect(self, images, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch, cap,
-                return_scores=False, return_chars=False):
+                min_area_rect=None, return_scores=False, char_boxes=None):
+        """detect's ``Results``"""
         x, dt = _detector_input(images)
         n, h, w, _ = x.shape
         return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_detect(
             self._h, _ptr(x), dt, n, h, w, float(detection_threshold), float(text_threshold), float(link_threshold),
-            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), return_scores, return_chars)
+            int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), min_area_rect, return_scores, char_boxes)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
     def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None):
@@ -735,36 +709,31 @@ class Context:
         (M,48) float32 as ``crnn_forward_scores``] [, beam labels (M,K,48), beam log_prob (M,K) as ``crnn_beam``, with
         ``beam=(beam_width, top_paths)``; the other results are the same bits] [, lexicon index (M,K), log_prob (M,K) as
         ``crnn_lexicon``, with ``lexicon_top=K``]."""
-        if lexicon_top is not None:
-            with self._lexicon_scope(lexicon_top):
-                head = self.recognize_boxes(images, box_groups, return_scores, beam)
-                head = head if isinstance(head, tuple) else (head,)
-                if not len(head[0]):
-                    return head + (np.zeros((0, lexicon_top), np.int32), np.zeros((0, lexicon_top), np.float32))
-                return head + self.recognition_lexicon()
-        if beam is not None:
-            bw, k = beam_args(*beam)
-            with self._beam_scope((bw, k)):
-                head = self.recognize_boxes(images, box_groups, return_scores)
-                head = head if return_scores else (head,)
-                if not len(head[0]):
-                    lw = self.crnn_label_width()
-                    return head + (np.zeros((0, k, lw), np.int32), np.zeros((0, k), np.float32))
-                return head + self.recognition_beams()
-        x = np.ascontiguousarray(images, dtype=np.uint8)
-        n, h, w, _ = x.shape
-        counts, flat = _flatten_boxes(box_groups)
-        lw = self.crnn_label_width()
-        labels = np.full((int(counts.sum()), lw), -1, dtype=np.int32)
-        if not return_scores:
-            if len(labels):
-                self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(labels), 0))
-            return labels
-        if not len(labels):
-            return labels, np.zeros(0, np.float32), np.zeros((0, lw), np.float32)
-        with self._scores_scope(True):
-            self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(labels), 0))
-            return (labels,) + self.recognition_scores()
+        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top).render_recognition()
+
+    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None):
+        """recognize_boxes' ``Results`` (no boxes; the detection part of its scores is None); no library call for zero boxes
+        beyond the switches"""
+        beam = None if beam is None else beam_args(*beam)
+        with self._lexicon_scope(lexicon_top):
+            with self._beam_scope(beam):
+                x = np.ascontiguousarray(images, dtype=np.uint8)
+                n, h, w, _ = x.shape
+                counts, flat = _flatten_boxes(box_groups)
+                lw = self.crnn_label_width()
+                out = Results(None, np.full((int(counts.sum()), lw), -1, dtype=np.int32))
+                m = len(out.labels)
+                with self._scores_scope(return_scores and m):
+                    if m:
+                        self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
+                                                                   _ptr(out.labels), 0))
+                    if return_scores:
+                        out.scores = (None,) + self.recognition_scores() if m else empty_scores(lw)
+                if beam is not None:
+                    out.beam = self.recognition_beams() if m else empty_beam(beam[1], lw)
+            if lexicon_top is not None:
+                out.lexicon = self.recognition_lexicon() if m else empty_lexicon(lexicon_top)
+        return out
 
     # -- crops --------------------------------------------------------------------------------
     def warp_crops(self, images, box_groups, target_height=31, target_width=200):
@@ -843,35 +812,25 @@ class Context:
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
                  min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None):
-        """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns
-        (boxes list[(n_i,4,2) f32, detector-input px], labels (M,48) int32).  ``min_area_rect``: as ``get_boxes``.
-        ``return_scores``: a third element ``(detection list[(n_i,) f32], log_word (M,) f32, char_scores (M,48) f32)``.
-        ``beam=(beam_width, top_paths)``: a last element ``(beam labels (M,K,48) int32, beam log_prob (M,K) f32)`` as
-        ``crnn_beam``; boxes, labels and scores are the same bits.  ``lexicon_top=K``: a last element ``(index (M,K) int32,
-        log_prob (M,K) f32)`` as ``crnn_lexicon``.  ``char_boxes`` (True or a dict of rule parameters): the very last element,
-        the character boxes of every word box as ``get_boxes`` gives them (detector-input px)."""
-        if char_rule(char_boxes) is not None:
-            with self._char_boxes_scope(char_boxes):
-                out = self.pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                                    size_threshold, micro_batch, on_device, cap, max_crops, min_area_rect, return_scores, beam,
-                                    lexicon_top)
+        """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns ``Results.render_context()``: (boxes
+        list[(n_i,4,2) f32, detector-input px], labels (M,48) int32), then one element per extra asked for, as the fields of
+        ``results.Results`` describe them -- ``return_scores``: its ``scores``; ``beam=(beam_width, top_paths)``: its ``beam``,
+        or ``lexicon_top=K``: its ``lexicon`` (boxes, labels and scores are the same bits); ``char_boxes`` (True or a dict of
+        rule parameters): its ``characters``, always last (detector-input px).  ``min_area_rect``: as ``get_boxes``."""
+        with self._char_boxes_scope(char_boxes):
+            with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
+                    self._lexicon_scope(lexicon_top):
+                out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
+                                     size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
+                if lexicon_top is not None:
+                    out.lexicon = self.recognition_lexicon() if len(ptrs) else empty_lexicon(lexicon_top)
+                elif beam is not None:
+                    out.beam = self.recognition_beams() if len(ptrs) else empty_beam(beam[1], self.crnn_label_width())
+            if char_rule(char_boxes) is not None:
                 # the boxes' own counts and the cap they were produced with (the largest count after a capacity overflow)
-                counts = [len(b) for b in out[0]]
-                return out + (self.detection_char_boxes(counts, max([int(cap)] + counts)) if len(ptrs) else [],)
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
-                self._lexicon_scope(lexicon_top):
-            out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                                 size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
-            if lexicon_top is not None:
-                if not len(ptrs):
-                    return out + ((np.zeros((0, lexicon_top), np.int32), np.zeros((0, lexicon_top), np.float32)),)
-                return out + (self.recognition_lexicon(),)
-            if beam is None:
-                return out
-            if not len(ptrs):
-                lw = self.crnn_label_width()
-                return out + ((np.zeros((0, beam[1], lw), np.int32), np.zeros((0, beam[1]), np.float32)),)
-            return out + (self.recognition_beams(),)
+                counts = [len(b) for b in out.boxes]
+                out.characters = self.detection_char_boxes(counts, max([int(cap)] + counts)) if len(ptrs) else []
+        return out.render_context()
 
     def _pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
                   size_threshold, micro_batch, on_device, cap, max_crops, return_scores=False):
@@ -900,11 +859,10 @@ class Context:
             labels = np.full((max_crops, lw), -1, dtype=np.int32)
             rc = self._lib.kocr_pipeline_results(self._h, _ptr(boxes), cap, _ptr(labels), max_crops)
         self._check(rc)
+        out = Results(_box_lists(boxes, counts), labels[:int(n_crops[0])].copy())
         if return_scores:
-            scores = (self.detection_scores(counts, cap),) + self.recognition_scores() if n else (
-                [], np.zeros(0, np.float32), np.zeros((0, lw), np.float32))
-            return _box_lists(boxes, counts), labels[:int(n_crops[0])].copy(), scores
-        return _box_lists(boxes, counts), labels[:int(n_crops[0])].copy()
+            out.scores = (self.detection_scores(counts, cap),) + self.recognition_scores() if n else empty_scores(lw, [])
+        return out
 
     def pipeline_device_results(self):
         """Device pointers of the last `pipeline()` call's results (include/kocr.h: kocr_pipeline_device_results):
@@ -978,19 +936,9 @@ class Context:
         code = self._check(self._lib.kocr_get_min_area_rect(self._h))
         return {v: k for k, v in MIN_AREA_RECT_RULES.items()}[code]
 
-    @contextlib.contextmanager
     def _min_area_rect_scope(self, rule):
         """A per-call rule: set for the block, the context's own restored afterwards (None: the context's rule)."""
-        if rule is None:
-            yield
-            return
-        code = _min_area_rect_code(rule)
-        old = self._check(self._lib.kocr_get_min_area_rect(self._h))
-        self._check(self._lib.kocr_set_min_area_rect(self._h, code))
-        try:
-            yield
-        finally:
-            self._check(self._lib.kocr_set_min_area_rect(self._h, old))
+        return _option_scope(self.get_min_area_rect, self.set_min_area_rect, rule)
 
     # -- measurement -------------------------------------------------------------------
     # -- the detector's training data and validation loss (detection.py:106-198, :696) ----------------------------------

@@ -213,8 +213,8 @@ class Detector:
             batch = batch.astype("float32")
             batch -= mean * 255
             batch /= variance * 255
-        out = self._ctx.detect(batch, detection_threshold=detection_threshold, text_threshold=text_threshold,
-                               link_threshold=link_threshold, size_threshold=size_threshold,
-                               micro_batch=kwargs.get("batch_size", 0) or 0, min_area_rect=min_area_rect,
-                               return_scores=return_scores, char_boxes=char_boxes)
-        return out[:-1] + (_layout.characters_of(out[-1]),) if want_chars else out
+        out = self._ctx._detect(batch, detection_threshold, text_threshold, link_threshold, size_threshold,  # pylint: disable=protected-access
+                                kwargs.get("batch_size", 0) or 0, None, min_area_rect, return_scores, char_boxes)
+        if want_chars:
+            out.characters = _layout.characters_of(out.characters)
+        return out.render_detection()

@@ -6,6 +6,7 @@ import typing
 import numpy as np
 
 from . import _lib, lexicon as _lexicon, scores as _scores, tools, weights as _weights
+from .results import Results
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
     "height": 31,
@@ -362,19 +363,21 @@ class Recognizer:
             crops = self._ctx.warp_crops(image[np.newaxis], [box[np.newaxis]], 31, 200)
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
-        if beam is not None or lexicon_top is not None:
-            if beam is not None:
-                alternatives = self._alternatives(*self._ctx.crnn_beam(crops, *beam))[0]
-            else:
-                alternatives = self._matches(*self._ctx.crnn_lexicon(crops, lexicon_top))[0]
-            if not return_scores:
-                return alternatives
-            labels, log_word, chars = self._ctx.crnn_forward_scores(crops)
-            return alternatives, _scores.assemble(labels, log_word, chars)[0]
+        return self._words(self._recognize_crops(crops, return_scores, beam, lexicon_top))[0]
+
+    def _recognize_crops(self, crops, return_scores, beam, lexicon_top):
+        """The ``Results`` of crops on the host: the decode [with its scores], and the alternatives or matches asked for"""
+        out = Results(None, None)
         if return_scores:
-            labels, log_word, chars = self._ctx.crnn_forward_scores(crops)
-            return self._decode(labels)[0], _scores.assemble(labels, log_word, chars)[0]
-        return self._decode(self._ctx.crnn_forward(crops))[0]
+            out.labels, *scores = self._ctx.crnn_forward_scores(crops)
+            out.scores = (None, *scores)
+        if beam is not None:
+            out.beam = self._ctx.crnn_beam(crops, *beam)
+        elif lexicon_top is not None:
+            out.lexicon = self._ctx.crnn_lexicon(crops, lexicon_top)
+        elif not return_scores:
+            out.labels = self._ctx.crnn_forward(crops)
+        return out
 
     def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None,
                              **kwargs) -> typing.List[typing.List[str]]:
@@ -402,43 +405,22 @@ class Recognizer:
                 if len(boxes):
                     im = np.asarray(image, np.float32)
                     crops.append(self._ctx.warp_crops_f32((im if im.ndim == 3 else im[..., np.newaxis])[np.newaxis], [boxes], 31, 200))
-            crops = np.concatenate(crops) / np.float32(255)
-            if beam is not None:
-                head = self._ctx.crnn_forward_scores(crops) if return_scores else ()
-                return self._with_beams(head + self._ctx.crnn_beam(crops, *beam), start_end)
-            if lexicon_top is not None:
-                head = self._ctx.crnn_forward_scores(crops) if return_scores else ()
-                return self._with_beams(head + self._ctx.crnn_lexicon(crops, lexicon_top), start_end, self._matches)
-            if return_scores:
-                return self._with_scores(*self._ctx.crnn_forward_scores(crops), start_end)
-            predictions = self._decode(self._ctx.crnn_forward(crops))
-            return [predictions[start:end] for start, end in start_end]
-        if len({im.shape for im in images}) == 1:
+            out = self._recognize_crops(np.concatenate(crops) / np.float32(255), return_scores, beam, lexicon_top)
+        elif len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            parts = [self._ctx.recognize_boxes(np.stack(images), box_groups, return_scores=return_scores, beam=beam,
-                                               lexicon_top=lexicon_top)]
+            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top)  # pylint: disable=protected-access
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            parts = [self._ctx.recognize_boxes(image[np.newaxis], [boxes], return_scores=return_scores, beam=beam,
-                                               lexicon_top=lexicon_top)
-                     for image, boxes in zip(images, box_groups) if len(boxes)]
-        if beam is not None or lexicon_top is not None:
-            columns = [np.concatenate(column) for column in zip(*parts)]
-            return self._with_beams(tuple(columns[1:]) if not return_scores else tuple(columns), start_end,
-                                    self._alternatives if beam is not None else self._matches)
-        if return_scores:
-            return self._with_scores(*[np.concatenate(column) for column in zip(*parts)], start_end)
-        predictions = self._decode(np.concatenate(parts))
-        return [predictions[start:end] for start, end in start_end]
-
-    def _with_beams(self, columns, start_end, rows_to_words=None):
-        """columns: ([labels, log_word, chars,] beam labels, beam log_prob) -> per image the alternatives [with scores];
-        ``rows_to_words``: ``_alternatives`` (the default) or ``_matches`` (columns end with the lexicon index, log_prob)"""
-        words = (rows_to_words or self._alternatives)(*columns[-2:])
-        if len(columns) > 2:
-            words = list(zip(words, _scores.assemble(*columns[:3])))
+            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top)  # pylint: disable=protected-access
+                                       for image, boxes in zip(images, box_groups) if len(boxes)])
+        words = self._words(out)
         return [words[start:end] for start, end in start_end]
 
-    def _with_scores(self, labels, log_word, chars, start_end):
-        pairs = list(zip(self._decode(labels), _scores.assemble(labels, log_word, chars)))
-        return [pairs[start:end] for start, end in start_end]
+    def _words(self, out):
+        """A ``Results``' crops as what recognize_from_boxes returns for each: the text, or its alternatives (``beam``), or
+        its matches (``lexicon``) [paired with the ``Score`` of the greedy decode]"""
+        if out.beam is not None:
+            words = self._alternatives(*out.beam)
+        else:
+            words = self._decode(out.labels) if out.lexicon is None else self._matches(*out.lexicon)
+        return words if out.scores is None else list(zip(words, _scores.assemble(out.labels, *out.scores[1:])))

@@ -1,0 +1,93 @@
+"""The one record that carries what detection and recognition produce, the optional results included, between the C calls
+and the public return values; it owns the legacy tuple layouts of those return values and the empty value of every extra."""
+import dataclasses
+import typing
+
+import numpy as np
+
+
+def empty_scores(label_width=48, detection=None):
+    return detection, np.zeros(0, np.float32), np.zeros((0, label_width), np.float32)
+
+
+def empty_beam(top_paths, label_width=48):
+    return np.zeros((0, top_paths, label_width), np.int32), np.zeros((0, top_paths), np.float32)
+
+
+def empty_lexicon(top_words):
+    return np.zeros((0, top_words), np.int32), np.zeros((0, top_words), np.float32)
+
+
+@dataclasses.dataclass
+class Results:
+    """What one call produced for N images with n_i boxes each, M = sum n_i crops in image order.  A stage that did not run
+    leaves its field (or its part of ``scores``) None; an extra that was not asked for is None.
+
+    boxes: per image an (n_i, 4, 2) float32 array [tl, tr, br, bl] (``np.array([])`` for an image without boxes).
+    labels: (M, label width = 48) int32 decoded label rows, -1 padded.
+    scores: ``(detection, log_word, char_scores)`` -- per image an (n_i,) float32 array, the maximum of the text map over each
+        box's component; (M,) float32, the log-probability of every alignment of the crop's own (greedy) decode; (M, label
+        width) float32, per decoded label the peak probability of its run, 0 behind the decode.
+    beam: ``(labels (M, K, label width) int32, log_prob (M, K) float32)`` as ``Context.crnn_beam``, best first; rows that do
+        not exist are all -1 with -inf.
+    lexicon: ``(index (M, K) int32, log_prob (M, K) float32)`` as ``Context.crnn_lexicon``, best first, -1 / -inf where fewer
+        words are feasible.
+    characters: per image a list of one entry per box, its characters from tl towards tr: a ``(quads (K, 4, 2) float32, scores
+        (K,) float32)`` pair below ``Detector`` / ``Pipeline``, a ``layout.Characters`` from there on.
+
+    For zero images (``empty``) or zero crops the extras are zero-row arrays of these shapes and dtypes."""
+    boxes: typing.Any
+    labels: typing.Any
+    scores: typing.Any = None
+    beam: typing.Any = None
+    lexicon: typing.Any = None
+    characters: typing.Any = None
+
+    @classmethod
+    def empty(cls, scores=False, beam=None, lexicon=None, characters=False, label_width=48):
+        """The results of zero images; ``beam`` = (beam_width, top_paths), ``lexicon`` = top_words"""
+        return cls([], np.zeros((0, label_width), np.int32), empty_scores(label_width, []) if scores else None,
+                   empty_beam(beam[1], label_width) if beam else None, empty_lexicon(lexicon) if lexicon else None,
+                   [] if characters else None)
+
+    def render_context(self):
+        """``Context.pipeline``'s layout: ``(boxes, labels[, scores][, beam | lexicon][, characters])``, nothing padded"""
+        alternatives = self.beam if self.lexicon is None else self.lexicon
+        return tuple([self.boxes, self.labels] + [v for v in (self.scores, alternatives, self.characters) if v is not None])
+
+    @classmethod
+    def parse_context(cls, out, scores=False, beam=False, lexicon=False, characters=False):
+        """``render_context``'s inverse, given which extras were asked for (with both ``beam`` and ``lexicon``: the lexicon)"""
+        wanted = (True, True, scores, beam and not lexicon, lexicon, characters)
+        if len(out) != sum(map(bool, wanted)):
+            raise ValueError(f"{len(out)} results do not fit scores={scores}, beam={beam}, lexicon={lexicon}, characters={characters}")
+        values = iter(out)
+        return cls(*[next(values) if w else None for w in wanted])
+
+    def render_raw(self):
+        """``Pipeline.recognize_raw``'s layout: ``(boxes, labels[, scores_or_None[, beam_or_None[, lexicon]]][, characters])``
+        -- as short as the extras allow, None in the place of an earlier extra that was not asked for"""
+        extras = [self.scores, self.beam, self.lexicon]
+        while extras and extras[-1] is None:
+            extras.pop()
+        return (self.boxes, self.labels, *extras) + (() if self.characters is None else (self.characters,))
+
+    def render_detection(self):
+        """``Context.get_boxes`` / ``detect``: the boxes, or ``(boxes[, detection scores][, characters])`` with an extra"""
+        if self.scores is None and self.characters is None:
+            return self.boxes
+        return (self.boxes,) + (() if self.scores is None else (self.scores[0],)) + (() if self.characters is None else (self.characters,))
+
+    def render_recognition(self):
+        """``Context.recognize_boxes``: the labels, or ``(labels[, log_word, char_scores][, beam pair][, lexicon pair])``, flat"""
+        if self.scores is None and self.beam is None and self.lexicon is None:
+            return self.labels
+        return (self.labels, *(self.scores or (None,))[1:], *(self.beam or ()), *(self.lexicon or ()))
+
+    @classmethod
+    def concatenate(cls, parts):
+        """The crops of several ``Context.recognize_boxes`` calls, one behind the other (no boxes: those belong to the caller)"""
+        def join(field):
+            values = [getattr(part, field) for part in parts]
+            return None if values[0] is None else tuple(None if v[0] is None else np.concatenate(v) for v in zip(*values))
+        return cls(None, np.concatenate([part.labels for part in parts]), join("scores"), join("beam"), join("lexicon"))

@@ -30,16 +30,20 @@ def assemble(labels, log_word, char_scores, detection=None):
     return out
 
 
-def need(stage, obj, method):
-    """The bound ``method`` of a (possibly duck-typed) stage if it takes ``return_scores``, else TypeError naming the stage."""
+def parameters(fn):
+    """The parameter names of a (possibly duck-typed) stage's method; none where its signature cannot be read"""
     import inspect
 
-    fn = getattr(obj, method)
     try:
-        params = inspect.signature(fn).parameters
+        return inspect.signature(fn).parameters
     except (TypeError, ValueError):
-        params = {}
-    if "return_scores" not in params:
+        return {}
+
+
+def need(stage, obj, method):
+    """The bound ``method`` of a (possibly duck-typed) stage if it takes ``return_scores``, else TypeError naming the stage."""
+    fn = getattr(obj, method)
+    if "return_scores" not in parameters(fn):
         raise TypeError(f"return_scores=True: the {stage} ({type(obj).__name__}.{method}) cannot give scores "
                         "(it takes no return_scores argument)")
     return fn
