@@ -419,6 +419,24 @@ int kocr_conv2d_cells(kocr_ctx* ctx, const float* in, int N, int H, int W, int C
                       const float* pre_a, const float* pre_b, int relu, const float* post_a, const float* post_b,
                       int cellW, int cellWv, int pool, float* out, float* pool_out, float* amax_out);
 
+/* ---- the decode launches on the caller's logits (unit-test seam for the CTC kernels) ---------- */
+/* Everything kocr_crnn_forward[_scores], kocr_crnn_beam, kocr_crnn_lexicon and kocr_crnn_ctc_loss launch BEHIND fc_12, on
+ * logits the caller made: the same launch functions with the same arguments, so a test decides what the kernels see
+ * (saturated frames, exact ties) instead of whatever a network produces.  Bound to the loaded recogniser: C =
+ * kocr_crnn_classes(), LW = kocr_crnn_label_width() (rows 50 - LW .. 49 of a crop's logits are decoded), the lexicon is the
+ * context's.  logits: M x 50 x C float32, M <= 1024 (one recogniser batch; more is KOCR_EINVAL).  Always: labels [M][LW],
+ * probs [M][LW][C] or NULL -- kocr_crnn_forward's.  Each further part is off when its switch is 0 / NULL:
+ *   log_word [M] and char_scores [M][LW], both or neither: kocr_crnn_forward_scores' launch instead of the plain decode;
+ *   beam_width != 0: beam_labels [M][top_paths][LW], beam_log_prob [M][top_paths] as kocr_crnn_beam (same refusals);
+ *   top_words != 0: lex_index / lex_log_prob [M][top_words], lex_values [M][V] or NULL as kocr_crnn_lexicon (same refusals);
+ *   loss_labels != NULL: loss [M] as kocr_crnn_ctc_loss for these labels and lengths (same refusals).
+ * KOCR_ENOWEIGHTS without a recogniser.  Host pointers only.  Runs on the ctx stream and is complete on return.  Records no
+ * taps and leaves the resident pipeline results alone. */
+int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
+                            float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
+                            int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
+                            int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss);
+
 /* ---- arithmetic of the wide convolutions --------------------------------------------- */
 /* The 3x3 / 1x1 / dilated convolutions with Cout > 32 run on the 16-bit matrix cores with fp32 operands split into
  * 16-bit pieces and fp32 accumulation:

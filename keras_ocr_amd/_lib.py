@@ -95,6 +95,7 @@ def load_library():
         "kocr_ctc_batch_cost": (ci, [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, ci]),
         "kocr_crnn_ctc_loss": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, ci]),
         "kocr_crnn_features": (ci, [vp, vp, ci, vp, ci]),
+        "kocr_crnn_decode_logits": (ci, [vp, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp]),
         "kocr_compute_maps": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, ci]),
         "kocr_heat_mse": (ci, [vp, vp, vp, ci, ci, ci, vp, ci]),
         "kocr_craft_mse": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, vp, ci]),
@@ -625,6 +626,47 @@ class Context:
         self._check(self._lib.kocr_crnn_ctc_loss(self._h, _ptr(x), m, _ptr(lab), lab.shape[1], _ptr(ll), _ptr(il), _ptr(loss), 0),
                     value_error=True)
         return loss
+
+    def crnn_decode_logits(self, logits, return_probs=False, scores=False, beam=None, top_words=0, return_values=False,
+                           loss_labels=None):
+        """Development entry (kocr_crnn_decode_logits): the launches behind fc_12 on the caller's logits (M, 50, classes)
+        float32, M <= 1024.  Returns a dict: "labels" (M, LW) int32 [, "probs" (M, LW, C)] as crnn_forward; with ``scores``
+        "log_word" (M,) and "chars" (M, LW) as crnn_forward_scores; with ``beam=(beam_width, top_paths)`` "beam_labels" /
+        "beam_log_prob" as crnn_beam; with ``top_words`` "lex_index" / "lex_log_prob" [, "lex_values"] as crnn_lexicon; with
+        ``loss_labels=(labels, label_lengths, input_lengths)`` "loss" (M,) as crnn_ctc_loss.  Refusals as those calls."""
+        x = np.ascontiguousarray(logits, dtype=np.float32)
+        c, lw = self.crnn_classes(), self.crnn_label_width()
+        if x.ndim != 3 or x.shape[1:] != (50, c):
+            raise ValueError(f"logits must have shape (M, 50, {c}), got {x.shape}")
+        m = x.shape[0]
+        out = {"labels": np.full((m, lw), -1, dtype=np.int32)}
+        if return_probs:
+            out["probs"] = np.zeros((m, lw, c), np.float32)
+        if scores:
+            out["log_word"] = np.zeros(m, np.float32)
+            out["chars"] = np.zeros((m, lw), np.float32)
+        bw, k = beam_args(*beam) if beam is not None else (0, 1)
+        if bw:
+            out["beam_labels"] = np.full((m, k, lw), -1, dtype=np.int32)
+            out["beam_log_prob"] = np.full((m, k), -np.inf, dtype=np.float32)
+        tw = int(top_words or 0)
+        if tw:
+            out["lex_index"] = np.full((m, max(tw, 0)), -1, dtype=np.int32)
+            out["lex_log_prob"] = np.full((m, max(tw, 0)), -np.inf, dtype=np.float32)
+            if return_values:
+                out["lex_values"] = np.full((m, self.lexicon_size()), -np.inf, dtype=np.float32)
+        lab = ll = il = None
+        stride = 0
+        if loss_labels is not None:
+            lab, ll, il = self._ctc_host_args(*loss_labels, m)
+            stride = lab.shape[1]
+            out["loss"] = np.zeros(m, np.float32)
+        g = out.get
+        self._check(self._lib.kocr_crnn_decode_logits(
+            self._h, _ptr(x), m, _ptr(out["labels"]), _ptr(g("probs")), _ptr(g("log_word")), _ptr(g("chars")), bw, k,
+            _ptr(g("beam_labels")), _ptr(g("beam_log_prob")), tw, _ptr(g("lex_index")), _ptr(g("lex_log_prob")), _ptr(g("lex_values")),
+            _ptr(lab), stride, _ptr(ll), _ptr(il), _ptr(g("loss"))), value_error=True)
+        return out
 
     def crnn_features(self, crops):
         """backbone.predict (kocr_crnn_features): crops (M,31,200[,1]) -> the BiLSTM features (M,50,256) float32."""

@@ -620,6 +620,97 @@ int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* 
   });
 }
 
+// Development entry (include/kocr.h): crnn_forward's launches behind fc_12 on the caller's logits
+int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
+                            float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
+                            int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
+                            int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_crnn_decode_logits";
+  if (M < 0 || (M > 0 && (!logits || !labels))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null buffer");
+  if (!log_word != !char_scores) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: log_word and char_scores go together");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_decode_logits: call kocr_load_crnn first");
+  if (M > CRNN_BATCH)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: M " + std::to_string(M) + " exceeds one recogniser batch of " +
+                                    std::to_string(CRNN_BATCH));
+  if (beam_width) {
+    KOCR_TRY(beam_validate(ctx, fn, beam_width, top_paths));
+    if (M > 0 && (!beam_labels || !beam_log_prob)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null beam buffer");
+  }
+  if (top_words) {
+    KOCR_TRY(lexicon_validate(ctx, fn, top_words));
+    if (M > 0 && (!lex_index || !lex_log_prob)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null lexicon buffer");
+  }
+  const int LW = crnn_label_width(ctx);
+  int Lmax = 0;
+  if (loss_labels) {
+    if (label_stride < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: bad sizes");
+    if (M > 0 && (!label_lengths || !input_lengths || !loss)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null loss buffer");
+    KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, loss_labels, label_stride, label_lengths, input_lengths, &Lmax));
+  }
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t m = (size_t)M, f = sizeof(float), V = top_words ? (size_t)ctx->lex.V : 0;
+  const size_t gb = m * CRNN_STEPS * C * f, lb = m * LW * sizeof(int32_t), pb = probs ? m * LW * C * f : 0;
+  const size_t wb = log_word ? m * f : 0, hb = log_word ? m * LW * f : 0;
+  const size_t bl = beam_width ? m * top_paths * LW * sizeof(int32_t) : 0, bv = beam_width ? m * top_paths * f : 0;
+  const size_t xi = top_words ? m * top_words * sizeof(int32_t) : 0, xv = top_words ? m * top_words * f : 0;
+  const size_t xa = lex_values ? m * V * f : 0, sb = loss_labels ? m * f : 0;
+  const size_t ib = loss_labels ? m * (std::max(Lmax, 1) + 2) * sizeof(int32_t) : 0;
+  Staging st{ctx, ctx->ws, fn, false};
+  KOCR_TRY(st.reserve(top_words ? lexicon_workspace_bytes(ctx, M, !lex_values) : 0,
+                      {gb, lb, pb, wb, hb, bl, bv, xi, xv, xa, sb}, {ib}));
+  const float* d_lg;
+  int32_t* d_l;
+  float* d_p = nullptr;
+  CrnnScores sc{nullptr, nullptr};
+  CrnnBeam bm{beam_width, top_paths, nullptr, nullptr};
+  CrnnLexicon lx{top_words, nullptr, nullptr, nullptr};
+  KOCR_TRY(st.in(logits, gb, d_lg));
+  KOCR_TRY(st.out(labels, lb, d_l));
+  if (probs) KOCR_TRY(st.out(probs, pb, d_p));
+  if (log_word) {
+    KOCR_TRY(st.out(log_word, wb, sc.d_logw));
+    KOCR_TRY(st.out(char_scores, hb, sc.d_chars));
+  }
+  if (beam_width) {
+    KOCR_TRY(st.out(beam_labels, bl, bm.d_labels));
+    KOCR_TRY(st.out(beam_log_prob, bv, bm.d_logp));
+  }
+  if (top_words) {
+    KOCR_TRY(st.out(lex_index, xi, lx.d_index));
+    KOCR_TRY(st.out(lex_log_prob, xv, lx.d_logp));
+    if (lex_values) KOCR_TRY(st.out(lex_values, xa, lx.d_all));
+  }
+  KOCR_TRY(crnn_decode_logits(ctx, d_lg, M, d_l, d_p, log_word ? &sc : nullptr, beam_width ? &bm : nullptr, top_words ? &lx : nullptr));
+  KOCR_TRY(st.back(labels, d_l, lb));
+  if (probs) KOCR_TRY(st.back(probs, d_p, pb));
+  if (log_word) {
+    KOCR_TRY(st.back(log_word, sc.d_logw, wb));
+    KOCR_TRY(st.back(char_scores, sc.d_chars, hb));
+  }
+  if (beam_width) {
+    KOCR_TRY(st.back(beam_labels, bm.d_labels, bl));
+    KOCR_TRY(st.back(beam_log_prob, bm.d_logp, bv));
+  }
+  if (top_words) {
+    KOCR_TRY(st.back(lex_index, lx.d_index, xi));
+    KOCR_TRY(st.back(lex_log_prob, lx.d_logp, xv));
+    if (lex_values) KOCR_TRY(st.back(lex_values, lx.d_all, xa));
+  }
+  std::vector<int32_t> staged;
+  if (loss_labels) {
+    const int *d_lab, *d_len, *d_in;
+    float* d_loss;
+    KOCR_TRY(ctc_stage_labels(st, loss_labels, label_stride, label_lengths, input_lengths, 0, M, Lmax, staged, &d_lab, &d_len, &d_in));
+    KOCR_TRY(st.out(loss, sb, d_loss));
+    KOCR_TRY(crnn_logits_loss(ctx, d_lg, M, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
+    KOCR_TRY(st.back(loss, d_loss, sb));
+  }
+  return st.finish();  // also keeps `staged` alive until its copy is done
+}
+
 int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device) {
   if (!ctx) return KOCR_EINVAL;
   if (M < 0 || (M > 0 && (!crops || !feats))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_features: null buffer");

@@ -558,6 +558,13 @@ int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths);
 // rnn_steps_to_discard .. + input_length - 1; labels / lengths already validated (ctc_validate) and on the device
 int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
                   float* d_loss, int Lmax);
+// the same loss launch on logits [M][50][n_classes] that are already on the device (crnn_ctc_loss's tail; kocr_crnn_decode_logits)
+int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
+                     float* d_loss, int Lmax);
+// crnn_forward's launches behind fc_12 on the caller's logits [M][50][n_classes] (device): the decode (with sc: the scores), then
+// the beam, then the lexicon match -- the same launch functions with the same arguments.  No taps, nothing resident changes.
+int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
+                       const CrnnBeam* bm, const CrnnLexicon* lx);
 // keras.backend.ctc_batch_cost's refusals on host arrays, before anything is launched: T_m in [1, T],
 // L_m in [0, min(T_m, label_stride)], labels[m][0 .. L_m) in [0, C - 2]; KOCR_EINVAL naming the sample.  *Lmax = max L_m.
 int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32_t* labels, int label_stride,

@@ -256,6 +256,22 @@ static int lexicon_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnLexico
   return KOCR_OK;
 }
 
+// The launches behind fc_12 on the logits [M][T][C] of a batch, shared by crnn_forward and crnn_decode_logits: the greedy decode
+// (with the scores when sc is given) ...
+static int decode_launch(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc) {
+  const CrnnNet* net = ctx->crnn;
+  if (sc) return launch_ctc_scores(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars);
+  return launch_ctc(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs);
+}
+// ... then the beam search and the lexicon match, each where asked for
+static int decode_extras(kocr_ctx* ctx, const float* d_lg, int M, const CrnnBeam* bm, const CrnnLexicon* lx) {
+  const CrnnNet* net = ctx->crnn;
+  if (bm)
+    KOCR_TRY(launch_ctc_beam(ctx, d_lg, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp));
+  if (lx) KOCR_TRY(lexicon_run(ctx, d_lg, M, *lx));
+  return KOCR_OK;
+}
+
 // d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
 // `stop` / d_feats / d_logits / sc / bm / lx: common.h
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
@@ -460,14 +476,16 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   probs.W = T - net->discard;
   probs.C = probs.cs = net->n_classes;
   probs.p = d_probs;
-  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() {
-    if (sc) return launch_ctc_scores(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars);
-    return launch_ctc(ctx, lg.p, M, T, net->n_classes, net->discard, d_labels, d_probs);
-  }));
-  if (bm)
-    KOCR_TRY(launch_ctc_beam(ctx, lg.p, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp));
-  if (lx) KOCR_TRY(lexicon_run(ctx, lg.p, M, *lx));
-  return KOCR_OK;
+  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() { return decode_launch(ctx, lg.p, M, d_labels, d_probs, sc); }));
+  return decode_extras(ctx, lg.p, M, bm, lx);
+}
+
+int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
+                       const CrnnBeam* bm, const CrnnLexicon* lx) {
+  if (!ctx->crnn || !ctx->crnn->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_decode_logits: call kocr_load_crnn first");
+  if (M <= 0) return KOCR_OK;
+  KOCR_TRY(decode_launch(ctx, d_lg, M, d_labels, d_probs, sc));
+  return decode_extras(ctx, d_lg, M, bm, lx);
 }
 
 int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx) {
@@ -519,6 +537,12 @@ int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, 
                   float* d_loss, int Lmax) {
   const float* d_lg = nullptr;
   KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
+  return crnn_logits_loss(ctx, d_lg, M, d_lab, lstride, d_len, d_in_len, d_loss, Lmax);
+}
+
+int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
+                     float* d_loss, int Lmax) {
+  if (!ctx->crnn || !ctx->crnn->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "ctc loss: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
   return launch_ctc_loss(ctx, /*logits=*/true, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, d_lab, lstride, d_len, d_in_len,
                          d_loss, Lmax);

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void lstm16_kernel(const float* __restrict__ x
 }
 
 // ---- fc_12's softmax (recognition.py:324), shared by ctc_kernel and ctc_loss_kernel<true> so that the loss of the logits is
-// computed on exactly the probabilities kocr_crnn_forward returns: p(c) = expf(row[c] - max) / sum, lane l owning the classes
+// computed on exactly the probabilities kocr_crnn_forward returns: p(c) = e^(row[c] - max) / sum, lane l owning the classes
 // l, l + 64, ...; per-lane sums in ascending class order, then the xor butterfly.
 // Per-lane argmax over its classes (ascending class index: first maximum wins), then the wave-level reduction of
 // (value, index) pairs with lowest index on ties; every lane ends with the row's maximum and its first index.
@@ -306,13 +306,25 @@ __device__ __forceinline__ void ctc_row_argmax(const float* __restrict__ row, in
     }
   }
 }
+// e^(v - mx) without the rounding error of the float32 difference.  On a saturated frame (a trained recogniser: the losers
+// 30 below the winner) that error alone is up to 2^-20, 16 u relative to the probability -- more than the whole stated bound
+// (C + 8) u of a 4-class softmax (tests/crnn_layer_check.py: check_ctc).  TwoSum (Knuth) gives it exactly:
+// d + err == v - mx, and e^(d + err) = e^d (1 + err) to within err^2 <= 2^-40.
+// (v = -inf: err is NaN but e^d is 0; a row's maximum has d = err = 0 and stays exactly 1.)
+__device__ __forceinline__ float ctc_exp_diff(float v, float mx) {
+  const float d = v - mx;
+  const float t = d - v;
+  const float err = (v - (d - t)) + (-mx - t);
+  const float e = expf(d);
+  return e == 0.f ? 0.f : fmaf(e, err, e);
+}
 __device__ __forceinline__ float ctc_row_expsum(const float* __restrict__ row, int C, int lane, float mx) {
   float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += expf(row[c] - mx);
+  for (int c = lane; c < C; c += 64) s += ctc_exp_diff(row[c], mx);
   for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
   return s;
 }
-__device__ __forceinline__ float ctc_softmax(float v, float mx, float s) { return expf(v - mx) / s; }
+__device__ __forceinline__ float ctc_softmax(float v, float mx, float s) { return ctc_exp_diff(v, mx) / s; }
 
 // logits: [M][T][C]; labels: [M][T-discard] (-1 padded); probs (nullable): [M][T-discard][C].
 // One wave per crop; lane l owns classes l, l+64, ... (any alphabet size).

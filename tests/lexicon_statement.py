@@ -50,3 +50,35 @@ def top_words(value, K):
                 continue
             margin[m] = min(margin[m], (a - b) / scale)
     return index, log_prob, margin
+
+
+def top_words_ties(value, K, larger_index_first=False):
+    """top_words for inputs with exact ties -> index, log_prob, margin, ties (M,): a gap between two values that compare EQUAL
+    in float64 is no margin -- the tie rule decides it on both sides -- and is counted in `ties` instead.
+    larger_index_first turns the tie rule: the OPPOSITE rule, for showing that an input's answer hangs on it."""
+    value = np.asarray(value, np.float64)
+    M, V = value.shape
+    index = np.full((M, K), -1, np.int64)
+    log_prob = np.full((M, K), -np.inf)
+    margin = np.full(M, np.inf)
+    ties = np.zeros(M, np.int64)
+    for m in range(M):
+        order = sorted(range(V), key=lambda v: (-value[m, v], -v if larger_index_first else v))
+        n = K + 1  # ranks 1 .. K + 1; where a tie straddles the cut, on to the first value that differs
+        if V > K and value[m, order[K]] == value[m, order[K - 1]]:
+            while n < V and value[m, order[n]] == value[m, order[K]]:
+                n += 1
+            n += 1
+        ranked = value[m, order[:n]]
+        keep = [v for v in order[:K] if value[m, v] > -np.inf]
+        index[m, :len(keep)] = keep
+        log_prob[m, :len(keep)] = value[m, keep]
+        scale = max(1.0, abs(ranked[K])) if len(ranked) > K and np.isfinite(ranked[K]) else 1.0
+        for a, b in zip(ranked, ranked[1:]):
+            if a == -np.inf:
+                continue
+            if a == b:
+                ties[m] += 1
+            else:
+                margin[m] = min(margin[m], (a - b) / scale)
+    return index, log_prob, margin, ties
