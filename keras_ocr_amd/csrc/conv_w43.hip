@@ -35,6 +35,7 @@
 // max-pool (POOL = 1) additionally needs even H and W % 64 == 0 (M-tile = 2 rows x 64 columns, the two rows of a
 // pooling window are accumulator registers r and r + 8 of one lane).  Everything else stays on conv_wsplit.hip.
 #include "w43_common.h"
+#include <utility>
 
 
 // DBG (developer timing experiments, wrong results; only instantiated with -DKOCR_DEV_SWITCHES): 1 = no input
@@ -142,21 +143,7 @@ __global__ __launch_bounds__(256) void conv_w43_kernel(W4Params p) {
       *reinterpret_cast<u2v*>(dst0 + 2 * PLANE) = r;
       return;
     }
-    v4f V;
-    switch (xi) {
-      case 0: V = (W4_A2B2 * d[0] - W4_A2PB2 * d[2]) + d[4]; break;
-      case 1: V = (d[4] - W4_B2 * d[2]) + W4_A * (d[3] - W4_B2 * d[1]); break;
-      case 2: V = (d[4] - W4_B2 * d[2]) - W4_A * (d[3] - W4_B2 * d[1]); break;
-      case 3: V = (d[4] - W4_A2 * d[2]) + W4_B * (d[3] - W4_A2 * d[1]); break;
-      case 4: V = (d[4] - W4_A2 * d[2]) - W4_B * (d[3] - W4_A2 * d[1]); break;
-      default: V = (W4_A2B2 * d[1] - W4_A2PB2 * d[3]) + d[5]; break;
-    }
-    u2v h, m, l;
-    kocr_split4(V, h, m, l);
-    unsigned short* dst = bufp + xi * 3 * PLANE + ldst;
-    *reinterpret_cast<u2v*>(dst) = h;
-    *reinterpret_cast<u2v*>(dst + PLANE) = m;
-    *reinterpret_cast<u2v*>(dst + 2 * PLANE) = l;
+    w4_split_store(w4_transform(d, xi), bufp + xi * 3 * PLANE, ldst, PLANE);
   };
 
   // ------------------------------------------------------------------------------------------------
@@ -184,20 +171,7 @@ __global__ __launch_bounds__(256) void conv_w43_kernel(W4Params p) {
         for (int s = 0; s < 3; ++s) acc[xi][m][s] += __builtin_bit_cast(v4f, a[m][s])[0] + __builtin_bit_cast(v4f, bw[xi][s])[0];
       return;
     }
-    const bf8 b0 = bw[xi][0], b1 = bw[xi][1], b2 = bw[xi][2];
-    // smallest terms first; the two M-tiles alternate so consecutive MFMAs are independent
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b0, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b2, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b1, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b0, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b1, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b0, acc[xi][m], 0, 0, 0);
+    w4_mfma12(acc[xi], a, bw[xi]);
   };
   // One K-step: consume `bufc` (6 points x 12 MFMAs) while producing the NEXT step from `raw` into `bufn`.  Per point:
   // fetch the next point's A operands from LDS, transform + split + store one point of the next step (VALU work that
@@ -211,8 +185,7 @@ __global__ __launch_bounds__(256) void conv_w43_kernel(W4Params p) {
                   const unsigned short* w_next) __attribute__((always_inline)) {
     auto load_b = [&](int xi) __attribute__((always_inline)) {
       if constexpr (DBG & 2) return;
-#pragma unroll
-      for (int s = 0; s < 3; ++s) bw[xi][s] = *reinterpret_cast<const bf8*>(w_next + (size_t)(xi * 3 + s) * 64 * 8);
+      w4_load_w(bw[xi], w_next, xi);
     };
     auto interleave = [&]() __attribute__((always_inline)) {
       __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);  // the 6 LDS fetches of the next point first
@@ -264,9 +237,7 @@ __global__ __launch_bounds__(256) void conv_w43_kernel(W4Params p) {
     w4_decode(p, kocr_xcd_remap(blockIdx.x, total), nblk_n, mp0, nt0);
     const unsigned short* w0 = w_tile(nt0);
 #pragma unroll
-    for (int xi = 0; xi < 6; ++xi)
-#pragma unroll
-      for (int s = 0; s < 3; ++s) bw[xi][s] = *reinterpret_cast<const bf8*>(w0 + (size_t)(xi * 3 + s) * 64 * 8);
+    for (int xi = 0; xi < 6; ++xi) w4_load_w(bw[xi], w0, xi);
   }
 #pragma unroll
   for (int xi = 0; xi < 6; ++xi) produce_point(rawA, As, xi);
@@ -314,7 +285,8 @@ __global__ __launch_bounds__(256) void conv_w43_kernel(W4Params p) {
       // as its own pass under a wave-uniform branch instead of a per-element select
       const float lo = p.relu ? 0.f : -INFINITY;
       auto act = [&](float v) { return fmaxf(v * pa + pb, lo); };
-      // inverse transform + BN + ReLU in place: acc[0..3][m][r] become the quad's four outputs
+      // inverse transform + BN + ReLU in place: acc[0..3][m][r] become the quad's four outputs (written out here, not through
+      // w4_inverse: see there)
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -335,12 +307,7 @@ __global__ __launch_bounds__(256) void conv_w43_kernel(W4Params p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][m][r] = acc[j][m][r] * qa + qb;
       }
-      // the output pixel stride is made opaque per tile: hoisted out of the persistent loop the 128 store offsets would be
-      // kept in (spilled) scalar registers and fetched back with one v_readlane per store
-      int ocs4 = p.out_cs * 4;
-      asm volatile("" : "+s"(ocs4));
-      int pcs4 = p.pool_cs * 4;
-      asm volatile("" : "+s"(pcs4));
+      const int ocs4 = w4_opaque_stride(p.out_cs), pcs4 = w4_opaque_stride(p.pool_cs);
       if (p.amax_out || p.amax_pool) {
         float mx = 0.f;
 #pragma unroll
@@ -529,21 +496,7 @@ __global__ __launch_bounds__(256) void conv_w43n_kernel(W4Params p) {
     ld_next = ld_next || wrap_cg;
   };
   auto produce_point = [&](const v4f (&d)[6], unsigned short* bufp, int xi, int it) __attribute__((always_inline)) {
-    v4f V;
-    switch (xi) {
-      case 0: V = (W4_A2B2 * d[0] - W4_A2PB2 * d[2]) + d[4]; break;
-      case 1: V = (d[4] - W4_B2 * d[2]) + W4_A * (d[3] - W4_B2 * d[1]); break;
-      case 2: V = (d[4] - W4_B2 * d[2]) - W4_A * (d[3] - W4_B2 * d[1]); break;
-      case 3: V = (d[4] - W4_A2 * d[2]) + W4_B * (d[3] - W4_A2 * d[1]); break;
-      case 4: V = (d[4] - W4_A2 * d[2]) - W4_B * (d[3] - W4_A2 * d[1]); break;
-      default: V = (W4_A2B2 * d[1] - W4_A2PB2 * d[3]) + d[5]; break;
-    }
-    u2v h, m, l;
-    kocr_split4(V, h, m, l);
-    unsigned short* dst = bufp + xi * 3 * PLANE_N + ldst[it];
-    *reinterpret_cast<u2v*>(dst) = h;
-    *reinterpret_cast<u2v*>(dst + PLANE_N) = m;
-    *reinterpret_cast<u2v*>(dst + 2 * PLANE_N) = l;
+    w4_split_store(w4_transform(d, xi), bufp + xi * 3 * PLANE_N, ldst[it], PLANE_N);
   };
 
   // ---- consumer state ------------------------------------------------------------------------------------------
@@ -561,19 +514,7 @@ __global__ __launch_bounds__(256) void conv_w43n_kernel(W4Params p) {
       for (int m = 0; m < 2; ++m) a[m][s] = *reinterpret_cast<const bf8*>(base + s * PLANE_N + m * 2 * KH_STRIDE);
   };
   auto mfma12 = [&](const bf8 (&a)[2][3], int xi) __attribute__((always_inline)) {
-    const bf8 b0 = bw[xi][0], b1 = bw[xi][1], b2 = bw[xi][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b0, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b2, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b1, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b0, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b1, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b0, acc[xi][m], 0, 0, 0);
+    w4_mfma12(acc[xi], a, bw[xi]);
   };
   // One K-step: per point, the LDS fetches of the next point, two transform-split-store chunks of the NEXT step
   // (item 0's six points during points 0-2, item 1's during points 3-5) interleaved 1 MFMA : 5 VALU, 12 MFMAs, the
@@ -581,8 +522,7 @@ __global__ __launch_bounds__(256) void conv_w43n_kernel(W4Params p) {
   bf8 a0[2][3], a1[2][3];
   auto step = [&](const unsigned short* bufc, unsigned short* bufn, const unsigned short* w_next) __attribute__((always_inline)) {
     auto load_b = [&](int xi) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) bw[xi][s] = *reinterpret_cast<const bf8*>(w_next + (size_t)(xi * 3 + s) * 64 * 8);
+      w4_load_w(bw[xi], w_next, xi);
     };
     auto interleave = [&]() __attribute__((always_inline)) {
       __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
@@ -638,9 +578,7 @@ __global__ __launch_bounds__(256) void conv_w43n_kernel(W4Params p) {
     w4_decode(p, kocr_xcd_remap(blockIdx.x, total), nblk_n, mp0, nt0);
     const unsigned short* w0 = w_tile(nt0);
 #pragma unroll
-    for (int xi = 0; xi < 6; ++xi)
-#pragma unroll
-      for (int s = 0; s < 3; ++s) bw[xi][s] = *reinterpret_cast<const bf8*>(w0 + (size_t)(xi * 3 + s) * 64 * 8);
+    for (int xi = 0; xi < 6; ++xi) w4_load_w(bw[xi], w0, xi);
   }
 #pragma unroll
   for (int xi = 0; xi < 6; ++xi) {
@@ -691,13 +629,9 @@ __global__ __launch_bounds__(256) void conv_w43n_kernel(W4Params p) {
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float m0 = acc[0][m][r], m1 = acc[1][m][r], m2 = acc[2][m][r], m3 = acc[3][m][r], m4 = acc[4][m][r],
-                      m5 = acc[5][m][r];
-          const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-          acc[0][m][r] = act((m0 + s12) + s34);
-          acc[1][m][r] = act(W4_A * d12 + W4_B * d34);
-          acc[2][m][r] = act(W4_A2 * s12 + W4_B2 * s34);
-          acc[3][m][r] = act((W4_A3 * d12 + W4_B3 * d34) + m5);
+          const v4f o = w4_inverse(act, acc[0][m][r], acc[1][m][r], acc[2][m][r], acc[3][m][r], acc[4][m][r], acc[5][m][r]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[j][m][r] = o[j];
         }
       if (has_post) {
 #pragma unroll
@@ -707,12 +641,7 @@ __global__ __launch_bounds__(256) void conv_w43n_kernel(W4Params p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][m][r] = acc[j][m][r] * qa + qb;
       }
-      // the output pixel stride is made opaque per tile: hoisted out of the persistent loop the 128 store offsets would be
-      // kept in (spilled) scalar registers and fetched back with one v_readlane per store
-      int ocs4 = p.out_cs * 4;
-      asm volatile("" : "+s"(ocs4));
-      int pcs4 = p.pool_cs * 4;
-      asm volatile("" : "+s"(pcs4));
+      const int ocs4 = w4_opaque_stride(p.out_cs), pcs4 = w4_opaque_stride(p.pool_cs);
       if (p.amax_out || p.amax_pool) {
         float mx = 0.f;
 #pragma unroll
@@ -894,28 +823,12 @@ __global__ __launch_bounds__(256) void conv_w43r_kernel(W4Params p) {
         raw[k] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (off0 + k * stride) | padk, soff, 0));
     }
   };
-  auto advance = [&]() __attribute__((always_inline)) {
-    const bool wrap = ld_cg == ncg - 1;
-    ld_cg = wrap ? 0 : ld_cg + 1;
-    ld_next = ld_next || wrap;
-  };
+  auto advance = [&]() __attribute__((always_inline)) { w4_advance(ld_cg, ld_next, ncg); };
   auto produce4 = [&](const v4f (&d)[6], unsigned short* bufp, int xi, int it) __attribute__((always_inline)) {
-    const v4f V = w4_transform(d, xi);
-    u2v h, m, l;
-    kocr_split4(V, h, m, l);
-    unsigned short* dst = bufp + xi * 3 * PLANE_R + ldst[it];
-    *reinterpret_cast<u2v*>(dst) = h;
-    *reinterpret_cast<u2v*>(dst + PLANE_R) = m;
-    *reinterpret_cast<u2v*>(dst + 2 * PLANE_R) = l;
+    w4_split_store(w4_transform(d, xi), bufp + xi * 3 * PLANE_R, ldst[it], PLANE_R);
   };
   auto produce2 = [&](const v2f (&d)[6], unsigned short* bufp, int xi) __attribute__((always_inline)) {
-    const v2f V = w4_transform(d, xi);
-    unsigned h, m, l;
-    kocr_split2(V, h, m, l);
-    unsigned short* dst = bufp + xi * 3 * PLANE_R + ldst[1];
-    *reinterpret_cast<unsigned*>(dst) = h;
-    *reinterpret_cast<unsigned*>(dst + PLANE_R) = m;
-    *reinterpret_cast<unsigned*>(dst + 2 * PLANE_R) = l;
+    w4_split_store(w4_transform(d, xi), bufp + xi * 3 * PLANE_R, ldst[1], PLANE_R);
   };
   v4f raw0[6];
   raw1_t raw1[6];
@@ -943,20 +856,7 @@ __global__ __launch_bounds__(256) void conv_w43r_kernel(W4Params p) {
       for (int m = 0; m < 2; ++m) a[m][s] = *reinterpret_cast<const bf8*>(base + s * PLANE_R + m * M_OFF);
   };
   auto mfma12 = [&](const bf8 (&a)[2][3], int pl) __attribute__((always_inline)) {
-    const bf8 b0 = bw[pl][0], b1 = bw[pl][1], b2 = bw[pl][2];
-    // smallest terms first; the two M-tiles alternate so consecutive MFMAs are independent
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[pl][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b0, acc[pl][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[pl][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b2, acc[pl][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[pl][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b1, acc[pl][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[pl][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b0, acc[pl][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[pl][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b1, acc[pl][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[pl][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b0, acc[pl][m], 0, 0, 0);
+    w4_mfma12(acc[pl], a, bw[pl]);
   };
   // One channel group: consume `bufc` in 9 groups (ky, point pair) while transforming the NEXT channel group from
   // raw0 / raw1 into `bufn` (chunks 2,1,1 per three groups; item 0 is finished after group 3 and its registers are refilled
@@ -1018,9 +918,7 @@ __global__ __launch_bounds__(256) void conv_w43r_kernel(W4Params p) {
       {  // this point pair's weights of the next step
         int sn = s0 + ky + 1;
         sn = sn >= ns ? sn - ns : sn;
-        const unsigned short* wq = w_ptr + (size_t)sn * w_step;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) bw[pp][s] = *reinterpret_cast<const bf8*>(wq + (size_t)((3 * ph + pp) * 3 + s) * 64 * 8);
+        w4_load_w(bw[pp], w_ptr + (size_t)sn * w_step, 3 * ph + pp);
       }
       if (g == 3) load_item0(raw0);
     }
@@ -1035,9 +933,7 @@ __global__ __launch_bounds__(256) void conv_w43r_kernel(W4Params p) {
   load_item1(raw1);
   advance();  // channel group 0 loaded
 #pragma unroll
-  for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) bw[pl][s] = *reinterpret_cast<const bf8*>(w_ptr + (size_t)((3 * ph + pl) * 3 + s) * 64 * 8);
+  for (int pl = 0; pl < 3; ++pl) w4_load_w(bw[pl], w_ptr, 3 * ph + pl);
 #pragma unroll
   for (int xi = 0; xi < 6; ++xi) {
     produce4(raw0, As, xi, 0);
@@ -1138,10 +1034,7 @@ __global__ __launch_bounds__(256) void conv_w43r_kernel(W4Params p) {
           for (int j = 0; j < 4; ++j) out[j][r] = out[j][r] * qa + qb;
       }
       __syncthreads();  // the next channel group is transformed into this buffer
-      int ocs4 = p.out_cs * 4;
-      asm volatile("" : "+s"(ocs4));
-      int pcs4 = p.pool_cs * 4;
-      asm volatile("" : "+s"(pcs4));
+      const int ocs4 = w4_opaque_stride(p.out_cs), pcs4 = w4_opaque_stride(p.pool_cs);
       int y0, x0;
       const long pm = w4_mtile_pm0<1>(p, tile_mt(mp, ph), y0, x0);
       if (p.amax_out || p.amax_pool) {  // per-image max |x| (Tensor::amax): the M-tile lies inside one image
@@ -1313,28 +1206,12 @@ __global__ __launch_bounds__(256) void conv_w43v_kernel(W4Params p) {
       raw[k] = __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(rsrc, (off0 + k * stride) | padk, soff, 0));
     }
   };
-  auto advance = [&]() __attribute__((always_inline)) {
-    const bool wrap = ld_cg == ncg - 1;
-    ld_cg = wrap ? 0 : ld_cg + 1;
-    ld_next = ld_next || wrap;
-  };
+  auto advance = [&]() __attribute__((always_inline)) { w4_advance(ld_cg, ld_next, ncg); };
   auto produce4 = [&](const v4f (&d)[6], unsigned short* bufp, int xi, int it) __attribute__((always_inline)) {
-    const v4f V = w4_transform(d, xi);
-    u2v h, m, l;
-    kocr_split4(V, h, m, l);
-    unsigned short* dst = bufp + xi * 3 * PLANE_R + ldst[it];
-    *reinterpret_cast<u2v*>(dst) = h;
-    *reinterpret_cast<u2v*>(dst + PLANE_R) = m;
-    *reinterpret_cast<u2v*>(dst + 2 * PLANE_R) = l;
+    w4_split_store(w4_transform(d, xi), bufp + xi * 3 * PLANE_R, ldst[it], PLANE_R);
   };
   auto produce2 = [&](const v2f (&d)[6], unsigned short* bufp, int xi) __attribute__((always_inline)) {
-    const v2f V = w4_transform(d, xi);
-    unsigned h, m, l;
-    kocr_split2(V, h, m, l);
-    unsigned short* dst = bufp + xi * 3 * PLANE_R + ldst[1];
-    *reinterpret_cast<unsigned*>(dst) = h;
-    *reinterpret_cast<unsigned*>(dst + PLANE_R) = m;
-    *reinterpret_cast<unsigned*>(dst + 2 * PLANE_R) = l;
+    w4_split_store(w4_transform(d, xi), bufp + xi * 3 * PLANE_R, ldst[1], PLANE_R);
   };
   v4f raw0[6];
   v2f raw1[6];
@@ -1368,20 +1245,7 @@ __global__ __launch_bounds__(256) void conv_w43v_kernel(W4Params p) {
       }
   };
   auto mfma12 = [&](const bf8 (&a)[2][3], int xi) __attribute__((always_inline)) {
-    const bf8 b0 = bw[xi][0], b1 = bw[xi][1], b2 = bw[xi][2];
-    // smallest terms first; the two M-tiles alternate so consecutive MFMAs are independent
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b0, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b2, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b1, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b0, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b1, acc[xi][m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) acc[xi][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b0, acc[xi][m], 0, 0, 0);
+    w4_mfma12(acc[xi], a, bw[xi]);
   };
   // One (channel group, ky) step: consume rows ky .. (+ M-tile offset) of `bufc` (6 points x 12 MFMAs); KY = 0 / 1
   // also transforms item 0 / 1 of the NEXT channel group into `bufn`, one point per MFMA group.  The weights of the next
@@ -1391,8 +1255,7 @@ __global__ __launch_bounds__(256) void conv_w43v_kernel(W4Params p) {
   auto step = [&](auto ky_c, const unsigned short* bufc, unsigned short* bufn, const unsigned short* w_next) __attribute__((always_inline)) {
     constexpr int KY = decltype(ky_c)::value;
     auto load_b = [&](int xi) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 3; ++s) bw[xi][s] = *reinterpret_cast<const bf8*>(w_next + (size_t)(xi * 3 + s) * 64 * 8);
+      w4_load_w(bw[xi], w_next, xi);
     };
     auto produce = [&](int xi) __attribute__((always_inline)) {
       if constexpr (KY == 0) produce4(raw0, bufn, xi, 0);
@@ -1462,9 +1325,7 @@ __global__ __launch_bounds__(256) void conv_w43v_kernel(W4Params p) {
     w4_decode(p, kocr_xcd_remap(blockIdx.x, total), nblk_n, mp0, nt0);
     const unsigned short* w0 = w_tile(nt0);
 #pragma unroll
-    for (int xi = 0; xi < 6; ++xi)
-#pragma unroll
-      for (int s = 0; s < 3; ++s) bw[xi][s] = *reinterpret_cast<const bf8*>(w0 + (size_t)(xi * 3 + s) * 64 * 8);
+    for (int xi = 0; xi < 6; ++xi) w4_load_w(bw[xi], w0, xi);
   }
 #pragma unroll
   for (int xi = 0; xi < 6; ++xi) {
@@ -1529,13 +1390,9 @@ __global__ __launch_bounds__(256) void conv_w43v_kernel(W4Params p) {
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float m0 = acc[0][m][r], m1 = acc[1][m][r], m2 = acc[2][m][r], m3 = acc[3][m][r], m4 = acc[4][m][r],
-                      m5 = acc[5][m][r];
-          const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-          acc[0][m][r] = act((m0 + s12) + s34);
-          acc[1][m][r] = act(W4_A * d12 + W4_B * d34);
-          acc[2][m][r] = act(W4_A2 * s12 + W4_B2 * s34);
-          acc[3][m][r] = act((W4_A3 * d12 + W4_B3 * d34) + m5);
+          const v4f o = w4_inverse(act, acc[0][m][r], acc[1][m][r], acc[2][m][r], acc[3][m][r], acc[4][m][r], acc[5][m][r]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[j][m][r] = o[j];
         }
       if (has_post) {
 #pragma unroll
@@ -1545,12 +1402,7 @@ __global__ __launch_bounds__(256) void conv_w43v_kernel(W4Params p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][m][r] = acc[j][m][r] * qa + qb;
       }
-      // the output pixel stride is made opaque per tile: hoisted out of the persistent loop the 128 store offsets would be
-      // kept in (spilled) scalar registers and fetched back with one v_readlane per store
-      int ocs4 = p.out_cs * 4;
-      asm volatile("" : "+s"(ocs4));
-      int pcs4 = p.pool_cs * 4;
-      asm volatile("" : "+s"(pcs4));
+      const int ocs4 = w4_opaque_stride(p.out_cs), pcs4 = w4_opaque_stride(p.pool_cs);
       if (p.amax_out || p.amax_pool) {
         float mx = 0.f;
 #pragma unroll
@@ -1799,6 +1651,15 @@ static int w4_launch(kocr_ctx* ctx, W4Params& p) {
   return launch_persistent<conv_w43_kernel<POOL, DBG, DIL>>(ctx, p, p.total_tiles, 256, LDS_BYTES, LDS_BYTES);
 }
 
+#ifdef KOCR_DEV_SWITCHES
+// KOCR_W43_DBG = 1 .. 15: the developer timing variants conv_w43_kernel<0, DBG> (wrong results)
+template <int... D>
+static int w4_launch_dbg(kocr_ctx* ctx, W4Params& p, int dbg, std::integer_sequence<int, D...>) {
+  static int (*const variant[])(kocr_ctx*, W4Params&) = {w4_launch<0, D + 1>...};
+  return variant[dbg - 1](ctx, p);
+}
+#endif
+
 template <int POOL>
 static int w4n_launch(kocr_ctx* ctx, W4Params& p) {
   constexpr int LDSN = 2 * LDS_BYTES;  // 2 x 72 KB
@@ -1922,26 +1783,7 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
     ProfScope ps(ctx, nm.c_str(), flops, bytes);
 #ifdef KOCR_DEV_SWITCHES
     static const int dbg = getenv("KOCR_W43_DBG") ? atoi(getenv("KOCR_W43_DBG")) : 0;
-    if (dbg && !fuse) {
-      switch (dbg) {
-        case 1: return w4_launch<0, 1>(ctx, p);
-        case 2: return w4_launch<0, 2>(ctx, p);
-        case 3: return w4_launch<0, 3>(ctx, p);
-        case 4: return w4_launch<0, 4>(ctx, p);
-        case 5: return w4_launch<0, 5>(ctx, p);
-        case 6: return w4_launch<0, 6>(ctx, p);
-        case 7: return w4_launch<0, 7>(ctx, p);
-        case 8: return w4_launch<0, 8>(ctx, p);
-        case 9: return w4_launch<0, 9>(ctx, p);
-        case 10: return w4_launch<0, 10>(ctx, p);
-        case 11: return w4_launch<0, 11>(ctx, p);
-        case 12: return w4_launch<0, 12>(ctx, p);
-        case 13: return w4_launch<0, 13>(ctx, p);
-        case 14: return w4_launch<0, 14>(ctx, p);
-        case 15: return w4_launch<0, 15>(ctx, p);
-        default: break;
-      }
-    }
+    if (dbg >= 1 && dbg <= 15 && !fuse) return w4_launch_dbg(ctx, p, dbg, std::make_integer_sequence<int, 15>{});
 #endif
     switch (q.arr) {
       case 'v':

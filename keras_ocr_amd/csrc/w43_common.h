@@ -144,3 +144,79 @@ __device__ __forceinline__ T w4_transform(const T (&d)[6], int xi) {
     default: return (W4_A2B2 * d[1] - W4_A2PB2 * d[3]) + d[5];
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Building blocks of the exact bf16x3 kernels (conv_w43.hip).  What differs between those kernels -- gather geometry, LDS
+// layout, K-loop schedule -- stays with each kernel; the algebra below exists once.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// split a transformed value into its three bf16 pieces and store them `plane` ushorts apart (a full item / a half item)
+__device__ __forceinline__ void w4_split_store(v4f V, unsigned short* pt, int slot, int plane) {
+  u2v h, m, l;
+  kocr_split4(V, h, m, l);
+  unsigned short* dst = pt + slot;
+  *reinterpret_cast<u2v*>(dst) = h;
+  *reinterpret_cast<u2v*>(dst + plane) = m;
+  *reinterpret_cast<u2v*>(dst + 2 * plane) = l;
+}
+__device__ __forceinline__ void w4_split_store(v2f V, unsigned short* pt, int slot, int plane) {
+  unsigned h, m, l;
+  kocr_split2(V, h, m, l);
+  unsigned short* dst = pt + slot;
+  *reinterpret_cast<unsigned*>(dst) = h;
+  *reinterpret_cast<unsigned*>(dst + plane) = m;
+  *reinterpret_cast<unsigned*>(dst + 2 * plane) = l;
+}
+
+// the three weight pieces of point xi for this lane; w = the wave's 32-cout tile of one K-step + lane * 8
+__device__ __forceinline__ void w4_load_w(bf8 (&bw)[3], const unsigned short* w, int xi) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) bw[s] = *reinterpret_cast<const bf8*>(w + (size_t)(xi * 3 + s) * 64 * 8);
+}
+
+// one point of one K-step: the six kept piece products, for two M-tiles
+__device__ __forceinline__ void w4_mfma12(f16v (&acc)[2], const bf8 (&a)[2][3], const bf8 (&bw)[3]) {
+  const bf8 b0 = bw[0], b1 = bw[1], b2 = bw[2];
+  // smallest terms first; the two M-tiles alternate so consecutive MFMAs are independent
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][2], b0, acc[m], 0, 0, 0);
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b2, acc[m], 0, 0, 0);
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b1, acc[m], 0, 0, 0);
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][1], b0, acc[m], 0, 0, 0);
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b1, acc[m], 0, 0, 0);
+#pragma unroll
+  for (int m = 0; m < 2; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m][0], b0, acc[m], 0, 0, 0);
+}
+
+// channel group of the NEXT load inside its tile, and whether that tile is already the next one (K loop over channel
+// groups; the flattened kernels' (ky, channel group) form stays inline there: as a function it moves ncg - 1 out of the K
+// loop's preheader and renumbers the loop's scalar registers)
+__device__ __forceinline__ void w4_advance(int& ld_cg, bool& ld_next, int ncg) {
+  const bool wrap = ld_cg == ncg - 1;
+  ld_cg = wrap ? 0 : ld_cg + 1;
+  ld_next = ld_next || wrap;
+}
+
+// ---- epilogue pieces ------------------------------------------------------------------------------------------------------
+
+// inverse transform of one accumulator element: the six points' sums -> the quad's four outputs, each through act (the
+// kernel's BN + ReLU).  conv_w43_kernel keeps its own copy: through this function its K loop grows from 768 to 772
+// instructions (the allocator of a 512-register kernel notices everything)
+template <class Act>
+__device__ __forceinline__ v4f w4_inverse(Act&& act, float m0, float m1, float m2, float m3, float m4, float m5) {
+  const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
+  return v4f{act((m0 + s12) + s34), act(W4_A * d12 + W4_B * d34), act(W4_A2 * s12 + W4_B2 * s34),
+             act((W4_A3 * d12 + W4_B3 * d34) + m5)};
+}
+
+// a byte stride of the epilogue's stores, made opaque per tile: hoisted out of the persistent loop the 128 store offsets
+// would be kept in (spilled) scalar registers and fetched back with one v_readlane per store
+__device__ __forceinline__ int w4_opaque_stride(int cs) {
+  int cs4 = cs * 4;
+  asm volatile("" : "+s"(cs4));
+  return cs4;
+}

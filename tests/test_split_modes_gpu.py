@@ -265,3 +265,64 @@ def test_fast_mode_heatmaps_and_boxes(fast_ctx, craft_weights):
     assert err <= 5e-3
     for i in range(2):
         assert np.array_equal(fast_ctx.craft_forward(img[i:i + 1]), got[i:i + 1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The epilogues of the exact bf16x3 F(4,3) kernels (csrc/conv_w43.hip) with the affines a network gives them: pre_a != 1,
+# a bias, ReLU, the CRNN's post-ReLU BatchNorm.  One small shape per arrangement of that file.
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture
+def bf16x3_ctx(ctx):
+    old = ctx.get_split_mode()
+    ctx.set_split_mode("bf16x3")
+    yield ctx
+    ctx.set_split_mode(old)
+
+
+AFFINE_CASES = [
+    # N, H, W, Cin, Cout, dil, profiler row family
+    (3, 8, 4, 32, 96, 1, "conv_w4s_256x128"),     # flattened pixels
+    (2, 17, 36, 64, 128, 1, "conv_w4s_256x128"),  # flattened pixels, the last tile partly outside
+    (1, 12, 24, 32, 96, 2, "conv_w4s_256x128"),   # flattened pixels, dilated
+    (1, 17, 36, 32, 48, 1, "conv_w4s_512x64"),    # 64 couts, flattened pixels
+    (1, 6, 128, 32, 48, 1, "conv_w4s_256x64"),    # 64 couts, row reuse on 2 x 128 tiles
+    (3, 12, 64, 32, 33, 1, "conv_w4s_256x64"),    # 64 couts, row reuse on 4 x 64 tiles
+    (1, 4, 192, 32, 130, 1, "conv_w4v_256x128"),  # vertical reuse on 4 x 64 tiles
+    (1, 8, 32, 32, 130, 1, "conv_w4t_256x128"),   # vertical reuse on 8 x 32 tiles
+]
+
+
+@pytest.mark.parametrize("case", AFFINE_CASES, ids=[str(c) for c in AFFINE_CASES])
+@pytest.mark.parametrize("variant", ["bias_relu", "relu_then_bn", "linear"])
+def test_bf16x3_w43_epilogue_affines(bf16x3_ctx, case, variant):
+    """|err| <= 1.25e-6 * B elementwise against fp64, with S = |x| conv |w| and B = (S |pre_a| + |pre_b|) |post_a| + |post_b|
+    (B = S |pre_a| + |pre_b| without a post affine): 1e-6 S is the kernels' stated bound, the two affines add at most four
+    fp32 roundings of 2^-24 each on quantities no larger than B, and ReLU is 1-Lipschitz."""
+    n, h, w, cin, cout, dil, family = case
+    rng = np.random.default_rng([AFFINE_CASES.index(case), ["bias_relu", "relu_then_bn", "linear"].index(variant)])
+    x = rng.standard_normal((n, h, w, cin), dtype=np.float32)
+    wt = (rng.standard_normal((3, 3, cin, cout)) * np.sqrt(2.0 / (cin * 9))).astype(np.float32)
+    pre_a = rng.uniform(0.5, 1.5, cout).astype(np.float32)
+    pre_b = rng.uniform(-0.3, 0.3, cout).astype(np.float32)
+    post_a = post_b = None
+    relu = variant != "linear"
+    if variant == "relu_then_bn":
+        post_a = rng.uniform(0.5, 1.5, cout).astype(np.float32)
+        post_b = rng.uniform(-0.3, 0.3, cout).astype(np.float32)
+    got, rows = _conv_rows(bf16x3_ctx, x, wt, dilation=dil, pre_a=pre_a, pre_b=pre_b, relu=relu, post_a=post_a, post_b=post_b)
+    if _plain_env():
+        assert len(rows) == 1 and rows[0].startswith(family), f"expected {family}*, profiler rows {rows}"
+        assert not rows[0].startswith(("conv_w4h", "conv_w4q")), rows
+    conv, s, _ = _ref64(x, wt, dil)
+    want = conv * pre_a.astype(np.float64) + pre_b.astype(np.float64)
+    bound = s * np.abs(pre_a).astype(np.float64) + np.abs(pre_b).astype(np.float64)
+    if relu:
+        want = np.maximum(want, 0.0)
+    if post_a is not None:
+        want = want * post_a.astype(np.float64) + post_b.astype(np.float64)
+        bound = bound * np.abs(post_a).astype(np.float64) + np.abs(post_b).astype(np.float64)
+    err = np.abs(got.astype(np.float64) - want)
+    worst = float((err / (1.25e-6 * bound)).max())
+    print(f"bf16x3 F(4,3) epilogue {case[:6]} {variant}: max err / (1.25e-6 B) = {worst:.3f}")
+    assert np.isfinite(got).all()
+    assert worst <= 1.0, f"max err / bound = {worst:.3f}"
