@@ -164,3 +164,66 @@ def exact_batch():
     for i, case in enumerate(cases):
         heat[i, :case[1].shape[0], :case[1].shape[1], 0] = case[1]
     return heat, [case[2].reshape(1, 4, 2) for case in cases]
+
+
+MANY_WORDS = (0, 255, 256, 257, 1, 0, 300)  # 1069 words: five blocks of chars_pack_kernel (256 words each)
+DEAD_WORDS = (512, 768)  # the flat word range without characters: the whole of block 2
+FULLEST_VALUES = [0.9, 0.1] * 256  # under EXACT_RULE: 512 columns, 256 peaks, bounds [0, 1, 3, ..., 509, 511]
+
+
+def _dead(rng, quad, w, h):
+    """a quad without characters: of zero width, of zero height, or wholly off the map"""
+    kind = int(rng.integers(3))
+    dead = quad.copy()
+    if kind == 0:
+        dead[1], dead[2] = dead[0], dead[3]
+    elif kind == 1:
+        dead[3], dead[2] = dead[0], dead[1]
+    else:
+        dead += np.array([4 * w, -4 * h] if rng.random() < 0.5 else [-4 * w, 4 * h], F32)
+    return dead
+
+
+def many_words_batch(seed=11, shape=(48, 160)):
+    """Seven pages of MANY_WORDS words, to be run under EXACT_RULE.  Returns ``(heat, pages, fullest)``: the maps padded to
+    one size as in ``exact_batch()``, the quads per page, and the flat index of the fullest word, the first of the last
+    page: ``exact_word(FULLEST_VALUES)``, 256 characters, on a map of its own width.
+
+    A 48 x 160 map has no room for 300 separate words, so every page ``render``s ten words of five blobs on a 5 x 2 grid
+    below row 8, and each of its words is the quad over a run of 1 to 5 neighbouring blobs of one of them (grown by 2 pixels,
+    as ``render``'s).  Flat words DEAD_WORDS[0] .. DEAD_WORDS[1] - 1 have no characters (a mix of ``_dead``'s kinds);
+    elsewhere about one word in six is dead."""
+    rng = np.random.default_rng(seed)
+    h, w = shape
+    full_map, full_quad = exact_word(FULLEST_VALUES, shape=(h, 3 + len(FULLEST_VALUES) + 4))
+    width = max(w, full_map.shape[1])
+    heat = np.zeros((len(MANY_WORDS), h, width, 2), F32)
+    heat[..., 1] = rng.random((len(MANY_WORDS), h, width), dtype=F32)
+    pages, flat = [], 0
+    for i, words in enumerate(MANY_WORDS):
+        text_map = np.zeros((h, width), F32)
+        sites = []
+        for k in range(10):
+            pitch, angle = float(rng.uniform(5, 6)), float(rng.uniform(-0.15, 0.15))
+            height = pitch * float(rng.uniform(1.0, 1.5))
+            cx, cy = 16.0 + 32.0 * (k % 5) + float(rng.uniform(-1, 1)), 18.0 + 20.0 * (k // 5) + float(rng.uniform(-1, 1))
+            render(text_map[:, :w], cx, cy, 5, pitch, height, angle)
+            sites.append((cx, cy, pitch, height, angle))
+        quads = []
+        for k in range(words):
+            cx, cy, pitch, height, angle = sites[int(rng.integers(len(sites)))]
+            n = int(rng.integers(1, 6))
+            first = int(rng.integers(0, 6 - n))  # blobs first .. first + n - 1 of the site's five
+            along = (first + n / 2.0) * pitch - 5 * pitch / 2.0
+            quad = (rectangle(cx + math.cos(angle) * along, cy + math.sin(angle) * along, n * pitch + 4.0, height + 4.0, angle) * 2.0).astype(F32)
+            if i == len(MANY_WORDS) - 1 and k == 0:
+                quad = full_quad
+            elif DEAD_WORDS[0] <= flat < DEAD_WORDS[1] or rng.random() < 1 / 6:
+                quad = _dead(rng, quad, w, h)
+            quads.append(quad)
+            flat += 1
+        if i == len(MANY_WORDS) - 1:
+            text_map[:4] = full_map[:4]
+        heat[i, :, :, 0] = text_map
+        pages.append(np.array(quads, F32).reshape(-1, 4, 2))
+    return heat, pages, sum(MANY_WORDS[:-1])

@@ -1,5 +1,5 @@
 """Inputs shared by tests/test_evaluation_statement_cpu.py and tests/test_evaluation_gpu.py: generated pairs of quads, the
-two scoring scenarios of tests/test_evaluation_cpu.py and a generated set of 32 labelled pages."""
+two scoring scenarios of tests/test_evaluation_cpu.py, a generated set of 32 labelled pages and four crowded images."""
 import math
 import string
 
@@ -178,8 +178,48 @@ def scenario_pages(seed=PAGES_SEED, pages=32, words=22):
     return true, pred, {"translator": str.maketrans(string.ascii_uppercase, string.ascii_lowercase, string.punctuation)}
 
 
+CROWDED_LENGTHS = (0, 1, 64, 65, 256)
+
+
+def scenario_crowded(seed=17):
+    """Four images, ids in sorted order, whose work outgrows one block and one grid of the scoring kernels:
+
+    ``a``  40 truths on sq(0, 0) and 40 predictions on sq(1, 0): all 1600 pairs overlap (IoU 9 / 11).  Truth 7 is ignored, the
+           other 1560 pairs are listed for the text kernel.  The texts are random words over "ab" of 3 to 12 code points, and
+           of CROWDED_LENGTHS code points at five places among the truths and five among the predictions: two words of like
+           length mostly agree in half their places (class 1), a long word against a short one does not (class 2).
+    ``b``  300 truths on a 20 x 15 grid and 5 predictions on truths 3, 100, 256, 257 (ignored) and 299.
+    ``c``  5 truths, on predictions 2, 255, 256 and 299 of 300 on the same grid, and one (ignored) on prediction 150.
+    ``d``  no truths and no predictions."""
+    rng = np.random.default_rng(seed)
+
+    def text(n):
+        return "".join("ab"[int(v)] for v in rng.integers(0, 2, n))
+
+    def texts(places):
+        out = [text(int(rng.integers(3, 13))) for _ in range(40)]
+        for at, n in zip(places, CROWDED_LENGTHS):
+            out[at] = text(n)
+        return out
+
+    grid = [sq(30 * (k % 20), 30 * (k // 20)) for k in range(300)]
+    true = {"a": [{"text": t, "vertices": sq(0, 0)} for t in texts((2, 11, 19, 20, 33))],
+            "b": [{"text": text(4), "vertices": q} for q in grid],
+            "c": [{"text": text(4), "vertices": _shift(grid[k], 0, 1)} for k in (2, 255, 150, 256, 299)],
+            "d": []}
+    true["a"][7]["ignore"] = True
+    true["b"][257]["ignore"] = True
+    true["c"][2]["ignore"] = True
+    pred = {"a": [{"text": t, "vertices": sq(1, 0)} for t in texts((5, 6, 21, 30, 38))],
+            "b": [{"text": true["b"][k]["text"] if k != 100 else "zzzzzzzz", "vertices": _shift(grid[k], 1, 0)} for k in (299, 3, 257, 100, 256)],
+            "c": [{"text": text(4), "vertices": q} for q in grid],
+            "d": []}
+    return true, pred, {}
+
+
 def scenarios():
-    return {"precision_recall": scenario_precision_recall(), "bookkeeping": scenario_bookkeeping(), "pages": scenario_pages()}
+    return {"precision_recall": scenario_precision_recall(), "bookkeeping": scenario_bookkeeping(), "pages": scenario_pages(),
+            "crowded": scenario_crowded()}
 
 
 def tables_input(true, pred, translator=None):

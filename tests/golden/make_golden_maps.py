@@ -13,6 +13,8 @@ Calls the reference's ``detection.compute_maps`` (detection.py:106-198), ``get_g
 
 Everything else -- the ordering and orientation of fix_line, the clamp, the half-scale quads, the link endpoints, the
 link chain and its reset at spaces, the accumulation and the final clip / 255 -- is the reference's code.
+
+A case is only ever appended: the arrays the file already holds are checked to stay byte for byte before it is rewritten.
 """
 import os
 import sys
@@ -90,6 +92,11 @@ def cases():
                            [(np.full((4, 2), 17.0, np.float32), "p")], [(rect(-40, -30, 150, 120, 0.2), "B")]]))
     # 5: no lines
     pages.append((32, 48, []))
+    # 6: a 258-character diagonal line whose orientation comes down to the order of numpy's float32 sum (257 differences:
+    # split twice), and a short line
+    seed, n = ms.LONG_TIE_SEEDS[3]
+    assert n == 258
+    pages.append((300, 300, [ms.long_tie_line(seed, n), word(200, 40, "short", cw=8, ch=11)]))
     return pages
 
 
@@ -127,6 +134,12 @@ def main():
     out["rgb_in"] = out["case1_maps0"]
     out["rgb_out"] = detection.map_to_rgb(out["case1_maps0"])
     path = os.path.join(HERE, "maps_golden.npz")
+    if os.path.exists(path):  # a case is only ever appended: what the file holds already stays byte for byte
+        old = dict(np.load(path))
+        for key, value in old.items():
+            assert key in out and out[key].dtype == value.dtype and out[key].shape == value.shape, key
+            assert out[key].tobytes() == value.tobytes(), key
+        print("kept", len(old), "arrays; new:", sorted(set(out) - set(old)))
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes")
 

@@ -168,12 +168,34 @@ def mse_loss_f64(y_true, y_pred, sample_weight=None):
     return float((sw * per_image).sum() / (y.shape[0] * y.shape[1] * y.shape[2]))
 
 
-def tie_line(seed, n):
+def one_leaf_sum_f32(a):
+    """The 8 <= n <= 128 rule of pairwise_sum_f32 applied to the whole array without the split: what a summation that never
+    splits gives.  Equal to pairwise_sum_f32 up to 128 elements."""
+    a = np.asarray(a, F32)
+    n = len(a)
+    if n <= 128:
+        return pairwise_sum_f32(a)
+    r = [F32(v) for v in a[:8]]
+    i = 8
+    while i < n - n % 8:
+        for j in range(8):
+            r[j] = F32(r[j] + a[i + j])
+        i += 8
+    res = F32(F32(F32(r[0] + r[1]) + F32(r[2] + r[3])) + F32(F32(r[4] + r[5]) + F32(r[6] + r[7])))
+    while i < n:
+        res = F32(res + a[i])
+        i += 1
+    return res
+
+
+def tie_line(seed, n, pitch=(3, 9), jitter=0.3):
     """A diagonal line of n axis-aligned characters whose x and y spans are equal in real arithmetic: the orientation
-    comes down to float32 rounding, and for some seeds numpy's pairwise order and a plain left-to-right sum disagree."""
+    comes down to float32 rounding, and for some seeds numpy's pairwise order and a plain left-to-right sum disagree.
+    ``pitch`` is the range of the step between characters, ``jitter`` the half-range of y - x; a small pitch lets a long
+    line fit a small map (the jitter has to stay below half the smallest pitch for the line to arrive sorted)."""
     rng = np.random.default_rng(seed)
-    x = np.cumsum(rng.uniform(3, 9, n))
-    y = x + rng.uniform(-0.3, 0.3, n)
+    x = np.cumsum(rng.uniform(pitch[0], pitch[1], n))
+    y = x + rng.uniform(-jitter, jitter, n)
     y[-1] = y[0] + (x[-1] - x[0])
     line = []
     for i in range(n):
@@ -183,3 +205,67 @@ def tie_line(seed, n):
 
 
 TIE_SEEDS = ((11, 20), (13, 22), (16, 25), (20, 29))  # (seed, n): lines on which the two summation orders disagree
+
+# Long tie lines: tie_line(seed, n, LONG_TIE_PITCH, LONG_TIE_JITTER) on a LONG_TIE_HW input (a 166 x 166 map).  n - 1
+# differences are summed: 64 (one stride past a wave of characters), 128 (the last leaf), 129 (the first split), 257 (the
+# first second-level split: 257 -> 128 + 129 -> 128 + (64 + 65)) and 299.
+LONG_TIE_PITCH = (0.5, 1.5)
+LONG_TIE_JITTER = 0.1
+LONG_TIE_HW = (332, 332)
+# (seed, n): for every n the first seed of range(400) on which numpy's pairwise order and a left-to-right sum decide the
+# orientation differently and, from n = 130 on, the pairwise order and one_leaf_sum_f32 do too
+LONG_TIE_SEEDS = ((13, 65), (0, 129), (1, 130), (23, 258), (2, 300))
+
+
+def long_tie_line(seed, n):
+    return tie_line(seed, n, LONG_TIE_PITCH, LONG_TIE_JITTER)
+
+
+LONG_PAGE_HW = (148, 148)
+
+
+def long_lines_page():
+    """A page of four lines of 64, 65, 129 and 130 characters whose characters arrive in a scrambled order.  Returns
+    ``(lines, expected)``: ``lines`` as compute_maps takes them, ``expected`` per line ``([(box, character)] in reading order,
+    orientation)``.  All coordinates are multiples of 1 / 8, so every centre is exact in float32.
+
+    * lines 1 and 3 are vertical (the 130-character one leans 1 : 2.5), lines 0 and 2 horizontal;
+    * spaces sit inside every line, one at ordered position 63 of line 1 and one at position 64 of lines 2 and 3;
+    * line 2 holds a character and a space on one centre, the character first (input indices 10 and 100); line 3 a space and
+      a character on one centre, the space first (input indices 20 and 70): the index decides which of the two the link
+      chain reaches, and the two indices lie on different sides of 64;
+    * the input order of every line is a permutation with a fixed seed."""
+    rng = np.random.default_rng(2025)
+    letters = "abcdefghijklmnopqrstuvwxyz"
+
+    def box(cx, cy, w, h):
+        return np.array([[cx - w / 2, cy - h / 2], [cx + w / 2, cy - h / 2], [cx + w / 2, cy + h / 2], [cx - w / 2, cy + h / 2]], F32)
+
+    # (n, vertical, start along, start across, lean across per step, spaces at ordered positions, twin (first, second, slots))
+    specs = [(64, False, 6.0, 8.0, 0.0, (20, 41), None),
+             (65, True, 30.0, 14.0, 0.0, (7, 63), None),
+             (129, False, 5.0, 24.0, 0.125, (30, 64, 90), (50, "char", (10, 100))),
+             (130, True, 4.0, 62.0, 0.375, (12, 64, 101), (77, "space", (20, 70)))]
+    lines, expected = [], []
+    for n, vertical, along0, across0, lean, spaces, twin in specs:
+        ordered = []
+        along = along0
+        for k in range(n):
+            if twin is not None and k == twin[0] + 1:
+                # the twin of the character before: the same box, so the same centre
+                ordered.append((ordered[-1][0].copy(), " " if twin[1] == "char" else letters[k % 26]))
+                continue
+            along += float(rng.integers(7, 10)) / 8.0  # a step of 0.875, 1 or 1.125
+            across = across0 + lean * k + float(rng.integers(0, 5)) / 8.0
+            cx, cy = (across, along) if vertical else (along, across)
+            ordered.append((box(cx, cy, 3.0, 4.5) if not vertical else box(cx, cy, 4.5, 3.0), " " if k in spaces else letters[k % 26]))
+        if twin is not None and twin[1] == "space":
+            ordered[twin[0]] = (ordered[twin[0]][0], " ")
+        order = [int(v) for v in rng.permutation(n)]  # order[slot] = ordered position of the character given at input slot
+        if twin is not None:
+            for member, slot in zip((twin[0], twin[0] + 1), twin[2]):
+                at = order.index(member)
+                order[at], order[slot] = order[slot], order[at]
+        lines.append([ordered[k] for k in order])
+        expected.append((ordered, "vertical" if vertical else "horizontal"))
+    return lines, expected

@@ -91,6 +91,38 @@ def test_batch_independence(ctx, batch):
         _assert_same(_flat(alone), _flat(together[k:k + 1]), f"page {k} of {len(page)} words alone")
 
 
+@pytest.fixture(scope="module")
+def many_words():
+    """the batch of 1069 words and the statement's answer under EXACT_RULE, computed once"""
+    heat, pages, fullest = cc.many_words_batch()
+    return heat, pages, fullest, cs.char_batch(heat, pages, **cc.EXACT_RULE)
+
+
+def test_many_words_equal_the_statement(ctx, many_words):
+    """five blocks of chars_pack_kernel, one of them without characters, and a word of 256 characters behind it"""
+    heat, pages, fullest, want = many_words
+    got = ctx.char_boxes(heat, pages, **cc.EXACT_RULE)
+    assert [len(p) for p in got] == list(cc.MANY_WORDS)
+    _assert_same(_flat(got), want, "many words")
+    assert want[0][fullest] == 256 and not want[0][cc.DEAD_WORDS[0]:cc.DEAD_WORDS[1]].any()
+
+
+def test_many_words_batch_independence(ctx, many_words):
+    """every page alone equals its slice of the batch, and so does the fullest word as a batch of one"""
+    heat, pages, fullest, want = many_words
+    together = ctx.char_boxes(heat, pages, **cc.EXACT_RULE)
+    for k, page in enumerate(pages):
+        alone = ctx.char_boxes(heat[k:k + 1], [page], **cc.EXACT_RULE)
+        _assert_same(_flat(alone), _flat(together[k:k + 1]), f"page {k} of {len(page)} words alone")
+    last = len(pages) - 1
+    assert fullest == sum(len(p) for p in pages[:last])
+    one = ctx.char_boxes(heat[last:], [pages[last][:1]], **cc.EXACT_RULE)
+    _assert_same(_flat(one), _flat([together[last][:1]]), "the fullest word alone")
+    before = int(want[0][:fullest].sum())
+    _assert_same(_flat(one), (want[0][fullest:fullest + 1], want[1][before:before + 256], want[2][before:before + 256]), "the fullest word against the statement")
+    assert len(one[0][0][0]) == 256
+
+
 def _raw(lib, ctx, heat, n, quads, offsets, cap, boxes=True, rule=(0.4, 0.7, 0.2), on_device=0, flags=0, d_heat=None):
     from keras_ocr_amd import _lib
 

@@ -72,6 +72,33 @@ def test_the_batch_holds_what_its_generator_guarantees():
     assert (flat < 0).any() and (flat[:, 0] > heat.shape[2]).any()
 
 
+def test_the_many_words_batch_holds_what_its_generator_guarantees():
+    """1069 words in five blocks of 256: a block without characters between blocks with, ragged counts elsewhere, and one
+    word with as many characters as a word can have, in a block with characters before it"""
+    heat, pages, fullest = cc.many_words_batch()
+    assert [len(p) for p in pages] == list(cc.MANY_WORDS) == [0, 255, 256, 257, 1, 0, 300]
+    assert heat.shape[:2] == (7, 48) and heat.shape[2] >= 3 + 512 and heat.dtype == np.float32
+    counts, quads, scores = cs.char_batch(heat, pages, **cc.EXACT_RULE)
+    assert len(counts) == 1069 and len(quads) == len(scores) == counts.sum()
+    # the dead block: words 512 .. 767 are block 2 of a pack kernel that takes 256 words a block
+    assert cc.DEAD_WORDS == (512, 768) and (counts[512:768] == 0).all()
+    assert counts[:512].sum() > 0 and counts[768:].sum() > 0 and counts[:256].sum() > 0 and counts[256:512].sum() > 0 and counts[1024:].sum() > 0
+    dead = np.concatenate(pages[3][1:257]).reshape(-1, 4, 2).astype(np.float64)
+    zero_width = (dead[:, 0] == dead[:, 1]).all(axis=1)
+    zero_height = (dead[:, 0] == dead[:, 3]).all(axis=1)
+    off_the_map = ((dead[..., 0] / 2 < -1).all(axis=1) | (dead[..., 1] / 2 < -1).all(axis=1)) & ~zero_width & ~zero_height
+    assert min(zero_width.sum(), zero_height.sum(), off_the_map.sum()) >= 40 and (zero_width | zero_height | off_the_map).all()
+    # the two shares, outside the dead block
+    live = np.concatenate([counts[:512], counts[768:]])
+    assert (live == 0).mean() >= 0.1 and (live >= 3).mean() >= 0.1
+    # the fullest word: the first of the last page, so in block 3 behind characters of earlier blocks
+    assert fullest == sum(cc.MANY_WORDS[:-1]) == 769 and fullest // 256 == 3 and fullest % 256 > 0
+    assert counts[fullest] == 256 == cs.MAX_COLS // 2
+    got = cs.word_chars(heat[6, :, :, 0], pages[6][0], **cc.EXACT_RULE)
+    assert got["n_cols"] == 512 and got["n_rows"] == 1 and got["profile"] == [float(np.float32(v)) for v in cc.FULLEST_VALUES]
+    assert got["peaks"] == list(range(0, 512, 2)) and got["bounds"] == [0] + list(range(1, 511, 2)) + [511]
+
+
 @pytest.mark.parametrize("rule, name", [
     ({"peak_threshold": 0.0}, "peak_threshold"), ({"peak_threshold": -1.0}, "peak_threshold"),
     ({"peak_threshold": float("inf")}, "peak_threshold"), ({"peak_threshold": float("nan")}, "peak_threshold"),

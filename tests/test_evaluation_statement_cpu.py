@@ -80,7 +80,7 @@ def test_statement_against_host_iou():
     assert worst <= gate
 
 
-@pytest.mark.parametrize("name", ["precision_recall", "bookkeeping", "pages"])
+@pytest.mark.parametrize("name", ["precision_recall", "bookkeeping", "pages", "crowded"])
 def test_score_tables_against_host(name):
     from keras_ocr_amd import evaluation
 
@@ -107,6 +107,39 @@ def test_pages_scenario_is_rich_and_clear_of_the_threshold():
     texts = {(t["text"], p["text"]) for i in ids for t in true[i] for p in pred[i]}
     assert ("ab", "ax") in texts and ("", "") in texts
     assert es.similarity([ord("a"), ord("b")], [ord("a"), ord("x")]) == 0.5 and es.similarity([], []) == 1.0
+
+
+def test_crowded_scenario_outgrows_a_grid_and_a_block():
+    """the text kernel's grid is min(pairs, words, 1024) one-wave blocks (launch_eval_text in csrc/evaluate.hip), the
+    reduction runs 256 threads over an image's truths and then its predictions: the scenario lists more pairs than the grid
+    has blocks, and has an image wider than 256 of either kind"""
+    true, pred, kwargs = ec.scenario_crowded()
+    ids, tables_in = ec.tables_input(true, pred, kwargs.get("translator"))
+    assert ids == ["a", "b", "c", "d"] == list(true) == list(pred)
+    tables = es.score_tables(iou_threshold=0.5, similarity_threshold=0.5, **tables_in)
+    classes = [c for image in tables["pair_class"] for row in image for c in row]
+    pairs = sum(len(true[i]) * len(pred[i]) for i in ids)
+    words = sum(len(true[i]) + len(pred[i]) for i in ids)
+    grid = min(pairs, words, 1024)
+    listed = classes.count(1) + classes.count(2)
+    assert len(classes) == pairs == 4600 and words == 690 and listed == 1560 + 8 > 2 * grid
+    assert min(classes.count(c) for c in (1, 2)) > 500 and classes.count(3) == 42
+    assert len(true["b"]) > 256 and len(pred["c"]) > 256 and not true["d"] and not pred["d"]
+    # beyond the 256th truth / prediction there are both kinds of flag
+    assert {0, 1} == set(tables["truth_missed"][1][256:]) == set(tables["pred_unclaimed"][2][256:])
+    flat = [v for image in tables["iou"] for row in image for v in row]
+    assert min(abs(v - 0.5) for v in flat) > 1e-6
+    # image a: every pair overlaps, and the lengths 0, 1, 64, 65 and 256 occur on both sides
+    assert all(v >= 0.5 for row in tables["iou"][0] for v in row)
+    for texts in (tables_in["truth_texts"][0], tables_in["pred_texts"][0]):
+        assert set(ec.CROWDED_LENGTHS) <= {len(t) for t in texts} and max(len(t) for t in texts) == es.MAX_TEXT
+    lengths = [(len(t), len(p)) for ti, t in enumerate(tables_in["truth_texts"][0]) if not tables_in["truth_ignore"][0][ti]
+               for p in tables_in["pred_texts"][0]]
+    assert sum(1 for (a, b), (c, d) in zip(lengths, lengths[1:]) if max(a, b) > 60 and max(c, d) < 16) >= 8  # a long pair, then a short one
+    # both classes where a 256-point text is involved, and ("", "") is a true positive
+    row = tables["pair_class"][0][[len(t) for t in tables_in["truth_texts"][0]].index(256)]
+    assert 1 in row and 2 in row
+    assert tables["pair_class"][0][2][5] == 1 and tables_in["truth_texts"][0][2] == [] == tables_in["pred_texts"][0][5]
 
 
 def test_levenshtein():

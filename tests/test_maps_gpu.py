@@ -1,6 +1,7 @@
 """GPU: kocr_compute_maps (warp.hip) against the full-map statement tests/maps_statement.py bit for bit, the detector's
 get_batch_generator, and model.evaluate (kocr_craft_mse / kocr_heat_mse) against the float64 mse statement."""
 import itertools
+import math
 import os
 
 import numpy as np
@@ -80,7 +81,7 @@ def test_fixture_pages(ctx):
                 assert_bits(got[p], g[f"case{i}_maps{k}"], f"case {i} heatmap {k} page {p}")
             assert not got[1].any()
         i += 1
-    assert i == 5
+    assert i == 6
 
 
 @pytest.mark.parametrize("H,W", [(256, 192), (130, 202), (96, 254)])
@@ -98,6 +99,30 @@ def test_orientation_ties(ctx, seed, n):
     hm = ms.get_gaussian_heatmap(64, 1.5)
     lines = [ms.tie_line(seed, n)]
     assert_bits(ctx.compute_maps(hm, 160, 320, [lines])[0], ms.compute_maps(hm, 160, 320, lines), f"tie {seed}")
+
+
+@pytest.mark.parametrize("seed,n", ms.LONG_TIE_SEEDS)
+def test_long_tie_lines(ctx, seed, n):
+    """lines longer than the 64 lanes of maps_line_kernel and than the 128 terms of one pairwise leaf, on which a sum in
+    another order turns the line the other way (tests/test_maps_statement_cpu.py asserts that of every one)"""
+    hm = ms.get_gaussian_heatmap(64, 1.5)
+    H, W = ms.LONG_TIE_HW
+    lines = [ms.long_tie_line(seed, n)]
+    assert_bits(ctx.compute_maps(hm, H, W, [lines])[0], ms.compute_maps(hm, H, W, lines), f"long tie {seed}, {n} characters")
+
+
+def test_long_scrambled_lines(ctx):
+    """lines of 64, 65, 129 and 130 characters in a scrambled order: the rank sort, the tie by index and the link chain's
+    reset across the kernel's strides; alone and as page 1 of a batch"""
+    page, _ = ms.long_lines_page()
+    H, W = ms.LONG_PAGE_HW
+    for name in ("odd", "rand"):
+        hm = heatmaps()[name]
+        alone = ctx.compute_maps(hm, H, W, [page])[0]
+        assert_bits(alone, ms.compute_maps(hm, H, W, page), f"long page, heatmap {name}")
+        batch = ctx.compute_maps(hm, H, W, [[], page, page[:2]])
+        assert_bits(batch[1], alone, f"long page inside a batch, heatmap {name}")
+        assert not batch[0].any() and batch[2].any()
 
 
 def test_pages_without_lines_and_errors(ctx):
@@ -175,6 +200,40 @@ def test_get_batch_generator(ctx, craft_weights):
     assert list(det.get_batch_generator(iter([]))) == []
 
 
+def _exact_sum(y_true, y_pred):
+    """math.fsum of the per-pixel terms ((y0 - p0)^2 + (y1 - p1)^2) / 2, each evaluated in float64 from the float32 values:
+    the correctly rounded sum of the terms as the kernel forms them (the differences are exact)"""
+    d = y_true.astype(np.float64) - y_pred.astype(np.float64)
+    terms = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) / 2.0
+    return np.array([math.fsum(image.ravel().tolist()) for image in terms], np.float64)
+
+
+@pytest.mark.parametrize("h,w", [(1, 1), (5, 7), (16, 16), (17, 19), (32, 48)])
+def test_heat_mse_sums(ctx, h, w):
+    """pixel counts below the block's 256 threads, off its multiples and on them"""
+    rng = np.random.default_rng(100 * h + w)
+    N = 3
+    # multiples of 1 / 16 in [0, 1]: every term is a multiple of 1 / 512 and every partial sum exact, in any order
+    y = (rng.integers(0, 17, (N, h, w, 2)) / 16).astype(F32)
+    p = (rng.integers(0, 17, (N, h, w, 2)) / 16).astype(F32)
+    d = np.rint((y.astype(np.float64) - p) * 16).astype(np.int64)
+    want = ((d * d).sum(axis=(1, 2, 3)) / 512.0).astype(np.float64)
+    assert np.array_equal(want, _exact_sum(y, p)) and (want > 0).all()
+    got = ctx.heat_mse(y, p)
+    assert got.dtype == np.float64 and np.array_equal(got.view(np.uint64), want.view(np.uint64)), (got, want)
+    # random float32 maps: each term carries at most three roundings (two squares, their sum; the halving is exact) and a
+    # sum of h w non-negative terms in any order at most h w - 1 more, each relative 2^-53, to first order
+    y, p = rng.random((N, h, w, 2), dtype=F32), rng.random((N, h, w, 2), dtype=F32)
+    ref = _exact_sum(y, p)
+    got = ctx.heat_mse(y, p)
+    bound = (h * w + 4) * 2.0 ** -53 * ref
+    print(f"heat_mse {h}x{w}: |got - ref| / ref = {np.abs(got - ref) / ref}, gate {(h * w + 4) * 2.0 ** -53:.3e}")
+    assert (ref > 0).all() and (np.abs(got - ref) <= bound).all(), (got, ref, bound)
+    # image k alone: the same bits as inside the batch
+    for k in range(N):
+        assert ctx.heat_mse(y[k:k + 1], p[k:k + 1]).view(np.uint64)[0] == got.view(np.uint64)[k]
+
+
 def test_evaluate_mse(ctx, craft_weights):
     from keras_ocr_amd import detection
 
@@ -187,6 +246,11 @@ def test_evaluate_mse(ctx, craft_weights):
     # the fused path keeps the heat-maps in HBM and equals the given-prediction path bit for bit
     fused = ctx.craft_mse(x, y, micro_batch=2)
     assert np.array_equal(fused.view(np.uint64), ctx.heat_mse(y, pred).view(np.uint64))
+    # and at 25 x 35 = 875 pixels, no multiple of heat_mse_kernel's 256 threads
+    x2 = detection.compute_input(rng.integers(0, 256, (3, 50, 70, 3), dtype=np.uint8))
+    y2 = rng.random((3, 25, 35, 2)).astype(F32)
+    fused2 = ctx.craft_mse(x2, y2, micro_batch=2)
+    assert np.array_equal(fused2.view(np.uint64), ctx.heat_mse(y2, det.model.predict(x2, batch_size=2)).view(np.uint64))
     for bs, w in ((2, sw), (None, None)):
         got = det.model.evaluate(x, y, batch_size=bs, sample_weight=w)
         want = ms.mse_loss_f64(y, pred, w)

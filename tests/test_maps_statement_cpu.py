@@ -34,7 +34,7 @@ def golden_cases(g):
 def test_statement_equals_reference_compute_maps(golden):
     hms = [golden["heatmap0"], golden["heatmap1"]]
     cases = golden_cases(golden)
-    assert len(cases) == 5
+    assert len(cases) == 6
     for i, (H, W, lines) in enumerate(cases):
         for k, hm in enumerate(hms):
             got = ms.compute_maps(hm, H, W, lines)
@@ -95,19 +95,75 @@ def _naive_sum(a):
     return r
 
 
-@pytest.mark.parametrize("seed,n", ms.TIE_SEEDS)
-def test_orientation_follows_the_pairwise_order(seed, n):
+TIE_LINES = [(seed, n, False) for seed, n in ms.TIE_SEEDS] + [(seed, n, True) for seed, n in ms.LONG_TIE_SEEDS]
+
+
+@pytest.mark.parametrize("seed,n,long", TIE_LINES, ids=[f"{seed}-{n}" for seed, n, _ in TIE_LINES])
+def test_orientation_follows_the_pairwise_order(seed, n, long):
     from keras_ocr_amd import tools
 
-    line = ms.tie_line(seed, n)
+    line = ms.long_tie_line(seed, n) if long else ms.tie_line(seed, n)
     c = np.array([ms.box_center(otools.get_rotated_box(b)[0]) for b, _ in line], F32)
     ddx = np.diff(c[np.argsort(c[:, 0], kind="stable")][:, 0])
     ddy = np.diff(c[np.argsort(c[:, 1], kind="stable")][:, 1])
+    assert ms.pairwise_sum_f32(ddx).tobytes() == ddx.sum().tobytes() and ms.pairwise_sum_f32(ddy).tobytes() == ddy.sum().tobytes()
     pairwise = ms.pairwise_sum_f32(ddy) > ms.pairwise_sum_f32(ddx)
     assert pairwise != (_naive_sum(ddy) > _naive_sum(ddx)), "the line no longer separates the two orders"
+    if n >= 130:  # more than 128 differences: a sum that never splits gets the orientation wrong
+        assert len(ddx) > 128
+        assert pairwise != (ms.one_leaf_sum_f32(ddy) > ms.one_leaf_sum_f32(ddx)), "the line no longer separates the split from one leaf"
     want = "vertical" if pairwise else "horizontal"
     assert ms.fix_line(line)[1] == want
     assert tools.fix_line(line)[1] == want
+
+
+def test_long_tie_lines_cover_the_boundaries_and_fit_their_map():
+    assert [n for _, n in ms.LONG_TIE_SEEDS] == [65, 129, 130, 258, 300]
+    H, W = ms.LONG_TIE_HW
+    assert H // 2 <= 170 and W // 2 <= 170
+    for seed, n in ms.LONG_TIE_SEEDS:
+        line = ms.long_tie_line(seed, n)
+        c = np.array([ms.box_center(b) for b, _ in line], F32)
+        assert len(line) == n and (np.diff(c[:, 0]) > 0).all() and (np.diff(c[:, 1]) > 0).all()  # it arrives sorted
+        assert c[:, 0].max() < W + 16 and c[:, 1].max() < H + 16 and (c[:64] < [W, H]).all()
+    a = np.random.default_rng(1).standard_normal(128).astype(F32)
+    assert ms.one_leaf_sum_f32(a).tobytes() == a.sum().tobytes()
+    assert len(ms.tie_line(11, 20)) == 20 and np.array_equal(ms.tie_line(11, 20)[3][0], ms.tie_line(11, 20, (3, 9), 0.3)[3][0])
+
+
+def test_long_lines_page_is_what_it_says():
+    """four scrambled lines of 64, 65, 129 and 130 characters: fix_line gives the constructed reading order and orientation"""
+    lines, expected = ms.long_lines_page()
+    H, W = ms.LONG_PAGE_HW
+    assert [len(line) for line in lines] == [64, 65, 129, 130] and H // 2 <= 170 and W // 2 <= 170
+    assert [o for _, o in expected] == ["horizontal", "vertical", "horizontal", "vertical"]
+    at_the_stride, twins = 0, 0
+    for line, (ordered, orientation) in zip(lines, expected):
+        fixed, got = ms.fix_line(line)
+        assert got == orientation
+        assert [c for _, c in fixed] == [c for _, c in ordered]
+        assert all(np.array_equal(a, otools.get_rotated_box(b)[0]) for (a, _), (b, _) in zip(fixed, ordered))
+        centers = np.array([ms.box_center(otools.get_rotated_box(b)[0]) for b, _ in ordered], F32)
+        assert centers.min() > 0 and (centers < [W, H]).all()
+        if orientation == "vertical":  # truly vertical: at least 2 : 1
+            assert np.ptp(centers[:, 1]) >= 2 * np.ptp(centers[:, 0])
+        else:
+            assert np.ptp(centers[:, 0]) >= 2 * np.ptp(centers[:, 1])
+        # scrambled: no input stride of 64 holds a run of the reading order
+        given = [next(k for k, (b, c) in enumerate(ordered) if b is box) for box, _ in line]
+        assert sorted(given) == list(range(len(line))) and given != sorted(given)
+        assert sum(1 for a, b in zip(given, given[1:]) if b == a + 1) < len(line) // 8
+        spaces = [k for k, (_, c) in enumerate(ordered) if c == " "]
+        assert spaces and 0 < spaces[0] and spaces[-1] < len(ordered) - 1
+        at_the_stride += sum(1 for k in spaces if k in (63, 64))
+        main = 1 if orientation == "vertical" else 0
+        for k in np.flatnonzero(np.diff(centers[:, main]) == 0):  # two characters on one centre
+            assert np.array_equal(centers[k], centers[k + 1])
+            first, second = given.index(int(k)), given.index(int(k) + 1)
+            assert first < 64 <= second, "the tie is not decided between two strides"
+            assert (ordered[k][1] == " ") != (ordered[k + 1][1] == " ")  # the order decides which of them the links reach
+            twins += 1
+    assert at_the_stride >= 1 and twins == 2
 
 
 def test_empty_line_and_odd_sizes():
