@@ -148,7 +148,7 @@ SPLIT_CASES = [
     (1, 75, 125, 64, 64, "conv_w4hr_256x64_rag"),     # 64 couts (slice1.3 class) on a ragged image: row reuse, exchange epilogue
     (2, 94, 250, 128, 48, "conv_w4hr_256x64_rag"),    # ... ragged couts, two images
     (3, 5, 66, 32, 64, "conv_w4hr_256x64_rag"),       # two live columns in the second tile column, H % 4 == 1
-    # Cout <= 32 (conv_hsplit.hip: haloed 8x32 tile split once into LDS; needs >= 4096 pixels)
+    # Cout <= 32 (conv_hsplit.hip: haloed 8x32 tile split once into LDS; any size since round 6 -- the small ones are in tests/dispatch_cases.py)
     (1, 64, 64, 32, 32, "conv_hh_256x32"),         # conv_cls.0 / .2 class, tiles exact
     (2, 70, 45, 64, 32, "conv_hh_256x32"),         # upconv4.conv.3 class: 4 chunks, ragged tiles in both directions, two images
     (1, 67, 100, 32, 16, "conv_hs_256x16"),        # conv_cls.4 class: the 16-wide product tile

@@ -12,8 +12,8 @@ s, b: the folded BatchNorm scale and shift (oracle.craft.layer_f64).  Pooled out
 where the full tensor is written too, equal maxpool2x2(full) bit for bit; maxpool3x3s1 and the skip channels of the concat
 buffers are exact; resize is within 1e-6 bilinear(|y|).  Every tracked input's per-image max-|x| slot is an upper bound of
 that image's max |x| when its consumer is launched, and at most twice it (exactly the source's slot where the producer
-copies it).  The checker is shown to be sensitive: the reduced-precision KOCR_SPLIT_F16X1 mode fails it on every F(4,3)
-layer."""
+copies it; the first layer's slot on uint8 input is a constant bound, within that factor on pages: see _image).  The
+checker is shown to be sensitive: the reduced-precision KOCR_SPLIT_F16X1 mode fails it on every F(4,3) layer."""
 import numpy as np
 import pytest
 import torch
@@ -33,10 +33,19 @@ def lctx(ctx, craft_weights):
 
 
 def _image(case):
+    """"page_375x500_u8", or "NxHxW_f32" (normalised input, standard normal) / "1xHxW_u8" (a synthetic page, raw RGB bytes).
+    The uint8 inputs are pages -- white with dark, striped words -- because the first layer's output slot is not measured
+    but is the layer's constant bound over all uint8 inputs (prepare_conv: ConvLayer::first_bound), and "at most twice
+    the image's maximum" is then a property of images that hold black next to white: 1.88 - 1.97 on these pages, but
+    2.3 - 2.4 on uniform noise, 2.27 on a blank white page and 27 on a uniformly grey one (float64, from the weights)."""
     if case == "page_375x500_u8":
         return synth.text_page(375, 500, 12, seed=91)[None]
-    h, w = {"1x64x512_f32": (64, 512), "1x50x70_f32": (50, 70)}[case]
-    return np.random.default_rng(h * w).standard_normal((1, h, w, 3)).astype(np.float32)
+    shape, _, dtype = case.partition("_")
+    n, h, w = (int(v) for v in shape.split("x"))
+    if dtype == "u8":
+        assert n == 1
+        return synth.text_page(h, w, 2, seed=h * w, scale=0.2)[None]
+    return np.random.default_rng(h * w).standard_normal((n, h, w, 3)).astype(np.float32)
 
 
 def _weight_shape(w, name):
@@ -176,7 +185,13 @@ def _check_forward(ctx, w, img, label, quiet=False):
 
 _CASES = [("default", "1x64x512_f32"), ("default", "1x50x70_f32"), ("default", "page_375x500_u8"),
           ("bf16x3", "1x64x512_f32"), ("bf16x3", "1x50x70_f32"), ("bf16x3", "page_375x500_u8"),
-          ("bf16x3_unfolded", "page_375x500_u8")]
+          ("bf16x3_unfolded", "page_375x500_u8"),
+          # the smallest and the most lopsided pages.  16 x 16 is the smallest legal one (levels 8, 4, 2, 1: the deepest
+          # layers run on ONE pixel); 17 x 19 has every level odd or 1 x 1 (floor pooling everywhere); three 18 x 22 images
+          # put all three into one flattened tile at the deep levels; 16 x 272 is a strip (widths 272, 136, 68, 34, 17)
+          ("default", "1x16x16_u8"), ("default", "1x16x16_f32"), ("default", "1x17x19_u8"), ("default", "3x18x22_f32"),
+          ("default", "1x16x272_f32"), ("default", "1x33x16_f32"),
+          ("bf16x3", "1x17x19_u8"), ("bf16x3", "3x18x22_f32"), ("bf16x3_unfolded", "1x17x19_u8")]
 
 
 @pytest.mark.parametrize("mode,case", _CASES, ids=[f"{m}-{c}" for m, c in _CASES])
@@ -184,6 +199,9 @@ def test_every_layer_within_its_fp32_class_bound(lctx, craft_weights, mode, case
     """Every launch of the detector within the bound of the kernel that ran it, on its own input (module docstring).
     "default": the context's arithmetic (fp16x2 unless the environment says otherwise); "bf16x3": the exact split;
     "_unfolded": also the layer-by-layer slice5 chain and resize + concat decoder (kocr_set_schedule(0, 0))."""
+    from oracle import craft as ocraft
+    from tests.test_craft_gpu import HEAT_TOL
+
     img = _image(case)
     prev, sched = lctx.get_split_mode(), lctx.get_schedule()  # a context made under KOCR_LINFOLD / KOCR_UPFOLD keeps them
     try:
@@ -191,10 +209,16 @@ def test_every_layer_within_its_fp32_class_bound(lctx, craft_weights, mode, case
             lctx.set_split_mode("bf16x3")
         if mode.endswith("unfolded"):
             lctx.set_schedule(False, False)
-        report, taps, _ = _check_forward(lctx, craft_weights, img, f"{mode} {case}")
+        report, taps, heat = _check_forward(lctx, craft_weights, img, f"{mode} {case}")
     finally:
         lctx.set_split_mode(prev)
         lctx.set_schedule(*sched)
+    # ... and the heat-map they add up to within the forward's own tolerance of the oracle
+    want = ocraft.detector_predict(craft_weights, img) if img.dtype == np.uint8 else ocraft.craft_forward(craft_weights, img)
+    assert heat.shape == want.shape == (img.shape[0], img.shape[1] // 2, img.shape[2] // 2, 2)
+    heat_err = float(np.abs(heat - want).max())
+    print(f"heat-map error against the oracle: {heat_err:.2e}")
+    assert heat_err <= HEAT_TOL, f"max abs heat-map error {heat_err}"
     worst = max(report.items(), key=lambda kv: kv[1][0])
     print(f"largest: {worst[0]} {worst[1][0]:.3f} ({worst[1][2]})")
     assert sum(1 for n in taps if n.startswith(("basenet", "upconv", "conv_cls"))) >= 25
@@ -217,6 +241,22 @@ def test_fp32_class_checker_rejects_the_f16x1_mode(lctx, craft_weights):
     print(f"one-piece F(4,3) layers, max err / stated bound: {one_piece}")
     assert len(one_piece) >= 3, report
     assert all(r > 1.0 for r in one_piece.values()), one_piece
+
+
+@pytest.mark.parametrize("h,w", [(15, 16), (16, 15)])
+def test_page_below_16x16_is_refused_and_harmless(lctx, h, w):
+    """A page with a side under 16 pixels has no 1/16 level: KOCR_EINVAL with its reason, and the next forward on the same
+    context gives what it gave before."""
+    import keras_ocr_amd
+
+    page = _image("1x16x16_u8")
+    before = lctx.craft_forward(page)
+    for dtype in (np.uint8, np.float32):
+        with pytest.raises(keras_ocr_amd.KocrError, match=r"libkocr error -1: .*smaller than 16x16"):  # -1: KOCR_EINVAL
+            lctx.craft_forward(np.zeros((1, h, w, 3), dtype))
+    after = lctx.craft_forward(page)
+    assert before.shape == (1, 8, 8, 2) and np.isfinite(before).all()
+    assert np.array_equal(before.view(np.uint32), after.view(np.uint32))
 
 
 def _part0(taps):

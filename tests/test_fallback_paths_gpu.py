@@ -54,9 +54,13 @@ def _run_config(switches):
     cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
            os.path.join(ROOT, "tests", "test_conv_gpu.py"), os.path.join(ROOT, "tests", "test_craft_gpu.py"),
            os.path.join(ROOT, "tests", "test_crnn_gpu.py"),
-           # every launch of the detector against its float64 bound, at the two small shapes (fused and floor pooling)
+           # every dispatch threshold from both sides: the boundary shapes on the kernels behind the switches (value bounds
+           # only; the row assertion skips itself under a switch)
+           os.path.join(ROOT, "tests", "test_dispatch_edges_gpu.py"),
+           # every launch of the detector against its float64 bound, at the two small shapes (fused and floor pooling) and
+           # at the smallest pages (16 x 16: the deepest level is one pixel; 17 x 19: every level odd or 1 x 1)
            *(os.path.join(ROOT, "tests", f"test_craft_layers_gpu.py::test_every_layer_within_its_fp32_class_bound[default-{c}]")
-             for c in ("1x64x512_f32", "1x50x70_f32")),
+             for c in ("1x64x512_f32", "1x50x70_f32", "1x16x16_f32", "1x17x19_u8")),
            "-k", "fp32_class or heatmap_u8_input or ragged_page or probs_and_labels"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500, check=False)
     tail = (r.stdout + r.stderr)[-3000:]
