@@ -586,6 +586,46 @@ int kocr_get_lexicon_match(const kocr_ctx* ctx, int* top_words);
 int kocr_recognition_lexicon(kocr_ctx* ctx, int32_t* index, float* log_prob, int max_crops, int32_t* n_crops, int32_t* top_words);
 int kocr_set_lexicon_scratch(kocr_ctx* ctx, uint64_t bytes);
 
+/* ---- orientation: read each box both ways and keep the better reading ("Orientation") ----------------
+ * The reference's get_rotated_box always names the upper of the two leftmost corners tl, so an upside-down word is warped
+ * upside down and a vertical one into a sliver.  With the switch on, every box is read in two orientations: its ordered box
+ * ob = get_rotated_box(box) with (w, h) = get_rotated_width_height(ob) has the base turn b = 1 when mode is KOCR_ORIENT_ANY
+ * and float(h) >= tall_ratio * float(w) (float64), else 0; candidate c = 0, 1 has t_c = b + 2 c quarter turns and the source
+ * quad q_c[i] = ob[(i + t_c) % 4] -- the same four float32 corners renamed: turn 1 reads text running down the page, turn 3
+ * up the page, turn 2 upside down.  Everything behind that is the crop stage's arithmetic on q_c in place of ob (width and
+ * height come from q_c and swap for odd turns; a zero width or height stays KOCR_EZERODIV), the unchanged warp, and the
+ * unchanged recogniser with its scores on the 2 M crops, a word's two crops side by side.  Candidate 1 wins iff
+ * (n_1 > 0 and n_0 == 0) or ((n_1 > 0) == (n_0 > 0) and v_1 > v_0), n_c the number of decoded labels and v_c the word
+ * log-probability ("Scores") of candidate c: an empty decode loses to a non-empty one, otherwise the larger exact
+ * log-probability wins, a tie or a NaN keeps candidate 0.  Two candidates per box, never four.
+ * kocr_set_orientation(ctx, mode, tall_ratio): mode KOCR_ORIENT_OFF (default), KOCR_ORIENT_FLIP (turns 0 / 2 for every box)
+ * or KOCR_ORIENT_ANY; KOCR_EINVAL for another mode, for a tall_ratio that is not finite and positive, and while a beam, a
+ * lexicon match or character boxes are switched on -- kocr_recognize_boxes / kocr_pipeline refuse those combinations as well.
+ * With the switch on the two calls return the WINNERS' label rows, leave the winners' scores resident (with scores on) and
+ * kocr_pipeline_results / kocr_pipeline_device_results carry the winners' rows, M of them as ever; two more launches per call
+ * (profiler rows warp_prepare_turned in kocr_pipeline, orient_select in both) and ctc_scores in place of ctc_greedy.  The box
+ * buffers keep getBoxes' boxes, bit for bit.  With the switch off the calls launch what they always launched.
+ * kocr_recognition_orientation: turns [n_crops] int32, quads [n_crops][4][2] float32 -- the winner's q, [tl, tr, br, bl] of the
+ * text AS READ, so quads[m][0] -> quads[m][1] is the reading direction --, log_words [n_crops][2] float32 = (v_0, v_1) (HOST,
+ * image-major, box order as the label rows); *n_crops (may be NULL) receives the number of crops, also when the call fails
+ * with KOCR_ECAPACITY (max_crops too small).  Validity and errors as for kocr_recognition_scores. */
+#define KOCR_ORIENT_OFF 0
+#define KOCR_ORIENT_FLIP 1
+#define KOCR_ORIENT_ANY 2
+int kocr_set_orientation(kocr_ctx* ctx, int mode, double tall_ratio);
+int kocr_get_orientation(const kocr_ctx* ctx, int* mode, double* tall_ratio);
+int kocr_recognition_orientation(kocr_ctx* ctx, int32_t* turns, float* quads, float* log_words, int max_crops, int32_t* n_crops);
+/* The two stages alone (unit-test seams).  kocr_warp_crops_turned: kocr_warp_crops' arguments (HOST) plus mode (FLIP / ANY) and
+ * tall_ratio; the set-up runs on the device as in kocr_pipeline.  crops [2 M][target_h][target_w], turns [2 M], quads
+ * [2 M][4][2], crop 2 m + c = candidate c of box m.  kocr_orient_select: the choice on the caller's rows (HOST): labels
+ * [M][2][L] int32, log_word [M][2], char_scores [M][2][L], turns [M][2], quads [M][2][4][2] -> out_labels [M][L], out_log_word
+ * [M], out_char_scores [M][L], out_turns [M], out_quads [M][4][2], out_log_words [M][2]; L >= 1. */
+int kocr_warp_crops_turned(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes, const int32_t* counts,
+                           int mode, double tall_ratio, int target_h, int target_w, float* crops, int32_t* turns, float* quads);
+int kocr_orient_select(kocr_ctx* ctx, int M, int L, const int32_t* labels, const float* log_word, const float* char_scores,
+                       const int32_t* turns, const float* quads, int32_t* out_labels, float* out_log_word, float* out_char_scores,
+                       int32_t* out_turns, float* out_quads, float* out_log_words);
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx
  * stream; kocr_profile_report fills parallel arrays (up to cap rows) with per-kernel-name

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .results import Results, empty_beam, empty_lexicon, empty_scores
+from .results import Results, empty_beam, empty_lexicon, empty_orientation, empty_scores
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkocr.so")
@@ -85,6 +85,11 @@ def load_library():
         "kocr_get_lexicon_match": (ci, [vp, vp]),
         "kocr_recognition_lexicon": (ci, [vp, vp, vp, ci, vp, vp]),
         "kocr_set_lexicon_scratch": (ci, [vp, ctypes.c_uint64]),
+        "kocr_set_orientation": (ci, [vp, ci, ctypes.c_double]),
+        "kocr_get_orientation": (ci, [vp, vp, vp]),
+        "kocr_recognition_orientation": (ci, [vp, vp, vp, vp, ci, vp]),
+        "kocr_warp_crops_turned": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ctypes.c_double, ci, ci, vp, vp, vp]),
+        "kocr_orient_select": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "kocr_set_scores": (ci, [vp, ci]),
         "kocr_get_scores": (ci, [vp]),
         "kocr_detection_scores": (ci, [vp, vp, ci]),
@@ -206,6 +211,31 @@ def beam_args(beam_width, top_paths=1):
     if not 1 <= k <= bw:
         raise ValueError(f"top_paths {k} outside [1, beam_width = {bw}]")
     return bw, k
+
+
+# orientation modes (include/kocr.h: KOCR_ORIENT_FLIP / KOCR_ORIENT_ANY; 0 is off)
+ORIENTATION_MODES = {"flip": 1, "any": 2}
+
+
+def orientation_args(orientation, tall_ratio=1.5):
+    """(mode code, tall_ratio) from ``orientation`` = "flip" / "any" and ``tall_ratio``, or ValueError naming the argument:
+    tall_ratio must be finite and positive (include/kocr.h: "orientation"; the library checks the same)."""
+    if not isinstance(orientation, str) or orientation not in ORIENTATION_MODES:
+        raise ValueError(f"orientation must be one of {sorted(ORIENTATION_MODES)}, got {orientation!r}")
+    ratio = float(tall_ratio)
+    if not (math.isfinite(ratio) and ratio > 0):
+        raise ValueError(f"tall_ratio {tall_ratio!r} must be finite and positive")
+    return ORIENTATION_MODES[orientation], ratio
+
+
+def refuse_orientation_with(orientation, **others):
+    """ValueError naming both arguments when ``orientation`` is asked for together with one of ``others`` (name=value; None
+    and False count as not asked for): beam alternatives, lexicon matches and character boxes describe ONE reading."""
+    if orientation is None:
+        return
+    for name, value in others.items():
+        if value is not None and value is not False:
+            raise ValueError(f"orientation and {name} cannot be combined: ask for one of the two")
 
 
 class Context:
@@ -395,6 +425,79 @@ class Context:
     def _scores_scope(self, on):
         """The switch for one call (``return_scores=True``); falsy: the context's own setting."""
         return _option_scope(self.get_scores, self.set_scores, True if on else None)
+
+    # -- orientation (include/kocr.h: "orientation") --------------------------------------------------------------------
+    def set_orientation(self, mode=0, tall_ratio=1.5):
+        """Whether recognize_boxes / pipeline read every box in two orientations and keep the better reading
+        (kocr_set_orientation): ``mode`` 0 / None (off), "flip" / 1 (turns 0 and 2) or "any" / 2 (turns 1 and 3 for a box with
+        h >= tall_ratio * w).  ValueError for another mode, a tall_ratio that is not finite and positive, or while a beam, a
+        lexicon match or character boxes are switched on."""
+        code = ORIENTATION_MODES.get(mode, mode) if isinstance(mode, str) else int(mode or 0)
+        if isinstance(code, str):
+            raise ValueError(f"orientation must be one of {sorted(ORIENTATION_MODES)}, got {mode!r}")
+        self._check(self._lib.kocr_set_orientation(self._h, code, float(tall_ratio)), value_error=True)
+
+    def get_orientation(self):
+        """``(mode code, tall_ratio)`` (kocr_get_orientation)"""
+        mode, ratio = ctypes.c_int(0), ctypes.c_double(0)
+        self._check(self._lib.kocr_get_orientation(self._h, ctypes.byref(mode), ctypes.byref(ratio)))
+        return mode.value, ratio.value
+
+    def _orientation_scope(self, orientation):
+        """The switch for one call (``orientation=(mode, tall_ratio)``, mode "flip" / "any" or its code); None: the context's
+        own setting."""
+        return _option_scope(self.get_orientation, lambda new: self.set_orientation(*new), orientation)
+
+    def recognition_orientation(self):
+        """The resident orientation of the last recognize_boxes / pipeline (kocr_recognition_orientation): turns (M,) int32,
+        quads (M, 4, 2) float32 -- [tl, tr, br, bl] of the text as read --, log_words (M, 2) float32, the two candidates'
+        word log-probabilities; ValueError when nothing is resident or the results were produced with orientation off."""
+        m = ctypes.c_int32(0)
+        rc = self._lib.kocr_recognition_orientation(self._h, None, None, None, 0, ctypes.byref(m))
+        if rc != KOCR_ECAPACITY:  # KOCR_OK: no crops; anything else: nothing to fetch
+            self._check(rc, value_error=True)
+        turns, quads, pairs = np.zeros(m.value, np.int32), np.zeros((m.value, 4, 2), np.float32), np.zeros((m.value, 2), np.float32)
+        if m.value:
+            self._check(self._lib.kocr_recognition_orientation(self._h, _ptr(turns), _ptr(quads), _ptr(pairs), m.value, None),
+                        value_error=True)
+        return turns, quads, pairs
+
+    def warp_crops_turned(self, images, box_groups, orientation="any", tall_ratio=1.5, target_height=31, target_width=200):
+        """The crop stage in both orientations (kocr_warp_crops_turned): images (N,H,W,3) uint8, box_groups a list of
+        (n_i,4,2).  Returns crops (2M,th,tw) float32, turns (2M,) int32 and quads (2M,4,2) float32; crop 2m + c is candidate c
+        of box m."""
+        mode, ratio = orientation_args(orientation, tall_ratio)
+        x = np.ascontiguousarray(images, dtype=np.uint8)
+        n, h, w, c = x.shape
+        if c != 3:
+            raise ValueError("images must be RGB")
+        counts, flat = _flatten_boxes(box_groups)
+        m2 = 2 * int(counts.sum())
+        crops = np.zeros((m2, target_height, target_width), dtype=np.float32)
+        turns, quads = np.zeros(m2, np.int32), np.zeros((m2, 4, 2), np.float32)
+        if m2:
+            self._check(self._lib.kocr_warp_crops_turned(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), mode, ratio,
+                                                         int(target_height), int(target_width), _ptr(crops), _ptr(turns), _ptr(quads)),
+                        value_error=True)
+        return crops, turns, quads
+
+    def orient_select(self, labels, log_word, char_scores, turns=None, quads=None):
+        """The choice between two candidates per word (kocr_orient_select): labels (M, 2, L) int32, log_word (M, 2), char_scores
+        (M, 2, L) float32 [, turns (M, 2) int32, default (0, 2); quads (M, 2, 4, 2) float32, default zeros].  Returns the
+        winners' labels (M, L), log_word (M,), char_scores (M, L), turns (M,), quads (M, 4, 2) and the pairs (M, 2)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.ndim != 3 or lab.shape[1] != 2 or lab.shape[2] < 1:
+            raise ValueError(f"labels must have shape (M, 2, L), got {lab.shape}")
+        m, _, width = lab.shape
+        logw = np.ascontiguousarray(log_word, dtype=np.float32).reshape(m, 2)
+        chars = np.ascontiguousarray(char_scores, dtype=np.float32).reshape(m, 2, width)
+        turns = np.ascontiguousarray(np.tile(np.array([0, 2], np.int32), (m, 1)) if turns is None else turns, dtype=np.int32).reshape(m, 2)
+        quads = np.ascontiguousarray(np.zeros((m, 2, 4, 2), np.float32) if quads is None else quads, dtype=np.float32).reshape(m, 2, 4, 2)
+        out = (np.full((m, width), -1, np.int32), np.zeros(m, np.float32), np.zeros((m, width), np.float32), np.zeros(m, np.int32),
+               np.zeros((m, 4, 2), np.float32), np.zeros((m, 2), np.float32))
+        self._check(self._lib.kocr_orient_select(self._h, m, width, _ptr(lab), _ptr(logw), _ptr(chars), _ptr(turns), _ptr(quads),
+                                                 *[_ptr(a) for a in out]), value_error=True)
+        return out
 
     # -- character boxes (include/kocr.h: "characters") ----------------------------------------------------------------
     def set_char_boxes(self, on=True, peak_threshold=0.4, valley_ratio=0.7, extent_threshold=0.2):
@@ -746,18 +849,22 @@ class Context:
             int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), min_area_rect, return_scores, char_boxes)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
-    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None):
+    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None):
         """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32 [, log_word (M,), char_scores
         (M,48) float32 as ``crnn_forward_scores``] [, beam labels (M,K,48), beam log_prob (M,K) as ``crnn_beam``, with
         ``beam=(beam_width, top_paths)``; the other results are the same bits] [, lexicon index (M,K), log_prob (M,K) as
-        ``crnn_lexicon``, with ``lexicon_top=K``]."""
-        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top).render_recognition()
+        ``crnn_lexicon``, with ``lexicon_top=K``] [, turns (M,), quads (M,4,2), log_words (M,2) as ``recognition_orientation``,
+        with ``orientation=(mode, tall_ratio)``: labels and scores are then those of each word's better reading; not
+        together with ``beam`` or ``lexicon_top`` (ValueError)]."""
+        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top, orientation).render_recognition()
 
-    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None):
+    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None):
         """recognize_boxes' ``Results`` (no boxes; the detection part of its scores is None); no library call for zero boxes
         beyond the switches"""
         beam = None if beam is None else beam_args(*beam)
-        with self._lexicon_scope(lexicon_top):
+        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top)
+        orientation = None if orientation is None else orientation_args(*orientation)
+        with self._lexicon_scope(lexicon_top), self._orientation_scope(orientation):
             with self._beam_scope(beam):
                 x = np.ascontiguousarray(images, dtype=np.uint8)
                 n, h, w, _ = x.shape
@@ -775,6 +882,8 @@ class Context:
                     out.beam = self.recognition_beams() if m else empty_beam(beam[1], lw)
             if lexicon_top is not None:
                 out.lexicon = self.recognition_lexicon() if m else empty_lexicon(lexicon_top)
+            if orientation is not None:
+                out.orientation = self.recognition_orientation() if m else empty_orientation()
         return out
 
     # -- crops --------------------------------------------------------------------------------
@@ -853,17 +962,25 @@ class Context:
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
-                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None):
+                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None, orientation=None):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns ``Results.render_context()``: (boxes
         list[(n_i,4,2) f32, detector-input px], labels (M,48) int32), then one element per extra asked for, as the fields of
         ``results.Results`` describe them -- ``return_scores``: its ``scores``; ``beam=(beam_width, top_paths)``: its ``beam``,
         or ``lexicon_top=K``: its ``lexicon`` (boxes, labels and scores are the same bits); ``char_boxes`` (True or a dict of
-        rule parameters): its ``characters``, always last (detector-input px).  ``min_area_rect``: as ``get_boxes``."""
+        rule parameters): its ``characters`` (detector-input px).  ``min_area_rect``: as ``get_boxes``.
+        ``orientation=(mode, tall_ratio)``, mode "flip" / "any": every box is read in two orientations (include/kocr.h:
+        "orientation"); labels and scores are those of each word's better reading, the boxes stay getBoxes' bits, and its
+        ``orientation`` comes last (quads in detector-input px).  Not together with ``beam``, ``lexicon_top`` or ``char_boxes``
+        (ValueError)."""
+        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, char_boxes=None if char_rule(char_boxes) is None else True)
+        orientation = None if orientation is None else orientation_args(*orientation)
         with self._char_boxes_scope(char_boxes):
             with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
-                    self._lexicon_scope(lexicon_top):
+                    self._lexicon_scope(lexicon_top), self._orientation_scope(orientation):
                 out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
                                      size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
+                if orientation is not None:
+                    out.orientation = self.recognition_orientation() if len(ptrs) else empty_orientation()
                 if lexicon_top is not None:
                     out.lexicon = self.recognition_lexicon() if len(ptrs) else empty_lexicon(lexicon_top)
                 elif beam is not None:

@@ -286,12 +286,31 @@ struct kocr_ctx {
     bool valid = false, off_switch = false;  // off_switch: results were produced with the switch off
     void clear() { valid = off_switch = false; }
   } last_ch;
+  // orientation (kocr_set_orientation; DESIGN.md section 4, "Orientation"): with orient_mode != KOCR_ORIENT_OFF,
+  // kocr_recognize_boxes / kocr_pipeline warp and read every box in two orientations (2 M crops, candidate-interleaved), and
+  // orient_select_kernel leaves the winners' rows in compact [M] buffers beside them: the label rows (what last_pl.d_labels
+  // and the callers' labels get), the scores, and the turns, quads and log_word pairs for kocr_recognition_orientation.
+  // Valid like last_sc.
+  int orient_mode = KOCR_ORIENT_OFF;
+  double orient_ratio = 1.5;
+  struct LastOrient {
+    const int* d_turns = nullptr;    // [M]
+    const float* d_quads = nullptr;  // [M][4][2]
+    const float* d_pairs = nullptr;  // [M][2]
+    int M = 0;
+    bool valid = false, off = false;  // off: results were produced with the switch off
+    void clear() { valid = off = false; }
+  } last_or;
+  void keep_orientation(const int* d_turns, const float* d_quads, const float* d_pairs, int M) {
+    last_or = {d_turns, d_quads, d_pairs, M, orient_mode != KOCR_ORIENT_OFF, orient_mode == KOCR_ORIENT_OFF};
+  }
   void invalidate_results() {
     last_pl.valid = false;
     last_sc.clear();
     last_beam.clear();
     last_lex.clear();
     last_ch.clear();
+    last_or.clear();
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
@@ -604,6 +623,17 @@ int launch_warp_prepare(kocr_ctx* ctx, const float* d_boxes, const int* d_counts
                         WarpParam* d_prm, int* d_status);
 int launch_warp_quads(kocr_ctx* ctx, const float* d_src, const float* d_dst, const int* d_img, const int* d_cw,
                       const int* d_ch, int M, WarpParam* d_prm, double* d_mfwd, int* d_status);
+// Orientation: candidate c (0 / 1) of a box in mode KOCR_ORIENT_FLIP / KOCR_ORIENT_ANY -- its quarter turns, its source quad
+// (8 floats: the ordered box's corners renamed) and the warp parameters of that quad; return code as warp_prepare.  The
+// launch does the same on the device, one thread per (box slot, candidate), for crop 2 (offset + b) + c.
+int warp_prepare_turned(const float* box, int mode, double tall_ratio, int c, int target_h, int target_w, WarpParam* out, int* turn,
+                        float* quad);
+int launch_warp_prepare_turned(kocr_ctx* ctx, const float* d_boxes, const int* d_counts, int N, int cap, int mode, double tall_ratio,
+                               int th, int tw, WarpParam* d_prm, int* d_turns, float* d_quads, int* d_status);
+// orient.hip: per word the winner of its two candidates (rows [M][2][..]) into compact [M] buffers
+int launch_orient_select(kocr_ctx* ctx, const int* d_lab, const float* d_logw, const float* d_chars, const int* d_turns,
+                         const float* d_quads, long M, int LW, int* o_lab, float* o_logw, float* o_chars, int* o_turn, float* o_quad,
+                         float* o_pair);
 
 // warp.hip: detection.compute_maps for a batch of pages (kocr_compute_maps).  A slot is one quad drawn into one plane (0 text,
 // 1 link) of one page: the inverse homography and the pixel box [x0, x1] x [y0, y1] it may touch (x1 < x0: nothing).

@@ -224,23 +224,19 @@ HD void rotated_box(const float* box, float* ob) {
   ob[7] = (float)bl.y;
 }
 
-// tools.warpBox's scalar half (tools.py:86-107), margin 0.  box: 4x2 float32.  rc: 0 ok, 1 zero width/height
-// (the reference raises ZeroDivisionError), 2 singular system.
-HD int warp_prepare_hd(const float* box, int target_h, int target_w, WarpParam* out, float* ordered_box) {
-  float ob[8];
-  rotated_box(box, ob);
-  if (ordered_box)
-    for (int i = 0; i < 8; ++i) ordered_box[i] = ob[i];
+// tools.warpBox's scalar half (tools.py:86-107), margin 0, on an ORDERED source quad q [tl, tr, br, bl] (4x2 float32).
+// rc: 0 ok, 1 zero width/height (the reference raises ZeroDivisionError), 2 singular system.
+HD int warp_prepare_quad(const float* q, int target_h, int target_w, WarpParam* out) {
   // ---- get_rotated_width_height (tools.py:41-57) ----
-  const int w = (int)((dist2(ob + 0, ob + 2) + dist2(ob + 4, ob + 6)) / 2);
-  const int h = (int)((dist2(ob + 0, ob + 6) + dist2(ob + 2, ob + 4)) / 2);
+  const int w = (int)((dist2(q + 0, q + 2) + dist2(q + 4, q + 6)) / 2);
+  const int h = (int)((dist2(q + 0, q + 6) + dist2(q + 2, q + 4)) / 2);
   if (w == 0 || h == 0) return 1;
   // ---- scale, destination quad, homography (tools.py:95-106) ----
   const double sw = (double)target_w / (double)w, sh = (double)target_h / (double)h;
   const double scale = sw < sh ? sw : sh;
   const float dst[8] = {0.f, 0.f, (float)(scale * w), 0.f, (float)(scale * w), (float)(scale * h),
                         0.f, (float)(scale * h)};
-  if (!quad_homography(ob, dst, nullptr, out->mi)) return 2;
+  if (!quad_homography(q, dst, nullptr, out->mi)) return 2;
   const int cw = (int)(scale * w), ch = (int)(scale * h);
   out->cw = cw < target_w ? cw : target_w;
   out->ch = ch < target_h ? ch : target_h;
@@ -248,10 +244,45 @@ HD int warp_prepare_hd(const float* box, int target_h, int target_w, WarpParam* 
   return 0;
 }
 
+// ... on a box as getBoxes gives it: 4x2 float32, ordered by get_rotated_box first.
+HD int warp_prepare_hd(const float* box, int target_h, int target_w, WarpParam* out, float* ordered_box) {
+  float ob[8];
+  rotated_box(box, ob);
+  if (ordered_box)
+    for (int i = 0; i < 8; ++i) ordered_box[i] = ob[i];
+  return warp_prepare_quad(ob, target_h, target_w, out);
+}
+
+// Orientation (tests/orientation_statement.py; DESIGN.md section 4, "Orientation"): candidate c (0 or 1) of a box reads its
+// ordered box ob through t = b + 2 c quarter turns, b = 1 for a tall box in mode KOCR_ORIENT_ANY (float(h) >= tall_ratio *
+// float(w) in float64, (w, h) = get_rotated_width_height(ob)), else 0: the source quad is q[i] = ob[(i + t) % 4], the same
+// four float32 corners renamed, and everything behind it is warp_prepare_quad.  t = 0 is warp_prepare_hd, operation for
+// operation.  quad: q (8 floats); rc as warp_prepare_quad.
+HD int warp_prepare_turned_hd(const float* box, int mode, double tall_ratio, int c, int target_h, int target_w, WarpParam* out,
+                              int* turn, float* quad) {
+  float ob[8];
+  rotated_box(box, ob);
+  const int w = (int)((dist2(ob + 0, ob + 2) + dist2(ob + 4, ob + 6)) / 2);
+  const int h = (int)((dist2(ob + 0, ob + 6) + dist2(ob + 2, ob + 4)) / 2);
+  const bool tall = mode == KOCR_ORIENT_ANY && (double)h >= tall_ratio * (double)w;
+  const int t = (tall ? 1 : 0) + 2 * c;
+  for (int i = 0; i < 4; ++i) {
+    quad[2 * i] = ob[2 * ((i + t) % 4)];
+    quad[2 * i + 1] = ob[2 * ((i + t) % 4) + 1];
+  }
+  *turn = t;
+  return warp_prepare_quad(quad, target_h, target_w, out);
+}
+
 }  // namespace
 
 int warp_prepare(const float* box, int target_h, int target_w, WarpParam* out, float* ordered_box) {
   return warp_prepare_hd(box, target_h, target_w, out, ordered_box);
+}
+
+int warp_prepare_turned(const float* box, int mode, double tall_ratio, int c, int target_h, int target_w, WarpParam* out, int* turn,
+                        float* quad) {
+  return warp_prepare_turned_hd(box, mode, tall_ratio, c, target_h, target_w, out, turn, quad);
 }
 
 // One thread per box slot (image k, slot b < cap): boxes[k][b] -> prm[offset(k) + b], where offset(k) = number of
@@ -284,6 +315,49 @@ int launch_warp_prepare(kocr_ctx* ctx, const float* d_boxes, const int* d_counts
   const int n = N * cap;
   hipLaunchKernelGGL(warp_prepare_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d_boxes, d_counts, N, cap, th, tw,
                      d_prm, d_status);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// The turned set-up: one thread per (box slot, candidate), boxes and counts read exactly as warp_prepare_kernel reads them.
+// Crop 2 (offset(k) + b) + c is candidate c of box b of image k -- a word's two crops sit side by side --, with its turn
+// and its source quad beside the WarpParam.
+__global__ void warp_prepare_turned_kernel(const float* __restrict__ boxes, const int* __restrict__ counts, int N, int cap, int mode,
+                                           double tall_ratio, int th, int tw, WarpParam* __restrict__ prm, int* __restrict__ turns,
+                                           float* __restrict__ quads, int* __restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)N * cap * 2) return;
+  const long slot = i >> 1;
+  const int c = (int)(i & 1);
+  const int k = (int)(slot / cap), b = (int)(slot - (long)k * cap);
+  if (b >= counts[k]) return;
+  long off = 0;
+  for (int j = 0; j < k; ++j) off += counts[j];
+  WarpParam p;
+  int t;
+  float q[8];
+  const int rc = warp_prepare_turned_hd(boxes + (size_t)slot * 8, mode, tall_ratio, c, th, tw, &p, &t, q);
+  if (rc != 0) {
+    // keep the slot harmless: an empty crop
+    for (int j = 0; j < 9; ++j) p.mi[j] = 0.0;
+    p.cw = p.ch = 0;
+    p.pad = 0;
+    atomicMax(status, rc);
+  }
+  p.img = k;
+  const size_t m = 2 * (size_t)(off + b) + c;
+  prm[m] = p;
+  turns[m] = t;
+  for (int j = 0; j < 8; ++j) quads[m * 8 + j] = q[j];
+}
+
+int launch_warp_prepare_turned(kocr_ctx* ctx, const float* d_boxes, const int* d_counts, int N, int cap, int mode, double tall_ratio,
+                               int th, int tw, WarpParam* d_prm, int* d_turns, float* d_quads, int* d_status) {
+  if (N <= 0 || cap <= 0) return KOCR_OK;
+  ProfScope ps(ctx, "warp_prepare_turned", 0, 0);
+  const long n = (long)N * cap * 2;
+  hipLaunchKernelGGL(warp_prepare_turned_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_boxes, d_counts, N, cap,
+                     mode, tall_ratio, th, tw, d_prm, d_turns, d_quads, d_status);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }

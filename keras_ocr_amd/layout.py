@@ -24,6 +24,22 @@ class Characters(typing.NamedTuple):
     scores: np.ndarray
 
 
+class Orientation(typing.NamedTuple):
+    """How one word was read ("Orientation"): ``turns``, the quarter turns of the better of the two
+    readings (0 as detected, 1 text running down the page, 2 upside down, 3 up the page); ``box`` (4, 2) float32, the word's
+    box [tl, tr, br, bl] of the text AS READ -- ``box[0] -> box[1]`` is the reading direction; ``log_words``, the exact CTC
+    log-probabilities ``(v_0, v_1)`` of the two candidates' own decodes (turns ``t`` and ``t + 2`` of the fewer-turns
+    candidate), so that a caller sees the margin of the choice."""
+    turns: int
+    box: np.ndarray
+    log_words: typing.Tuple[float, float]
+
+
+def orientations_of(turns, quads, log_words):
+    """``Context.recognition_orientation``'s arrays as one ``Orientation`` per word"""
+    return [Orientation(int(t), q, (float(v[0]), float(v[1]))) for t, q, v in zip(np.asarray(turns).tolist(), quads, np.asarray(log_words))]
+
+
 def characters_of(char_groups):
     """``Context.char_boxes``' per-image lists of ``(quads, scores)`` pairs as lists of ``Characters``"""
     return [[Characters(quads, scores) for quads, scores in page] for page in char_groups]

@@ -25,6 +25,18 @@ def lexicon_of(recognition_kwargs):
     return _lexicon.top_arg(kwargs["lexicon_top"])
 
 
+def orientation_of(recognition_kwargs, char_boxes=None):
+    """``(orientation, tall_ratio)`` from recognize()'s ``recognition_kwargs`` (validated: ValueError naming the argument, or
+    naming both when it is combined with ``beam_width``, ``lexicon_top`` or character boxes), or None without an
+    ``orientation``."""
+    kwargs = recognition_kwargs or {}
+    if kwargs.get("orientation") is None:
+        return None
+    _lib.refuse_orientation_with(kwargs["orientation"], beam_width=kwargs.get("beam_width"), lexicon_top=kwargs.get("lexicon_top"),
+                                 char_boxes=char_boxes)
+    return kwargs["orientation"], _lib.orientation_args(kwargs["orientation"], kwargs.get("tall_ratio", 1.5))[1]
+
+
 def _one_text_per_word(recognition_kwargs, why):
     """ValueError for ``beam_width`` / ``lexicon_top``: the caller needs every ``text`` to be one string"""
     for key in ("beam_width", "lexicon_top"):
@@ -93,7 +105,14 @@ class Pipeline:
         a list of up to K alternatives ``(text, log_prob)``, best first, as ``Recognizer.recognize``; the boxes are the same
         bits.  ``recognition_kwargs={"lexicon_top": K}`` (section 4, "Lexicon"; after ``recognizer.set_lexicon(words)``): every
         ``text`` becomes a list of up to K ``(word, log_prob)`` lexicon matches, best first.  Not both (ValueError).  The other
-        keys of both dicts are Keras predict arguments without effect."""
+        keys of both dicts are Keras predict arguments without effect.
+
+        ``recognition_kwargs={"orientation": "flip" | "any", "tall_ratio": r}`` (section 4, "Orientation"): every box is read
+        in two orientations on the GPU and the better reading kept, as ``Recognizer.recognize_from_boxes``; each ``text`` is
+        the winner's and each ``box`` the word's box [tl, tr, br, bl] of the text as read (the detector's rectangle, its corners
+        renamed), so ``box[0] -> box[1]`` is the reading direction.  Not together with ``beam_width``, ``lexicon_top`` or
+        character boxes (ValueError); uint8 images only (NotImplementedError).  ``recognize_with_scores``, ``recognize_lines``,
+        ``evaluate``, ``recognize_padded`` and ``recognize_raw`` take it in the same way."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs)
 
     def recognize_with_scores(self, images, detection_kwargs=None, recognition_kwargs=None):
@@ -147,6 +166,7 @@ class Pipeline:
         ``detection.get_char_boxes``.  ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list.
         A method of its own because recognize() keeps the reference's exact signature."""
         _one_text_per_word(recognition_kwargs, "recognize_characters pairs one text per word with its characters")
+        orientation_of(recognition_kwargs, char_boxes=True)  # ValueError naming both
         unknown = set(rule) - set(_lib.CHAR_RULE_DEFAULTS)
         if unknown:
             raise TypeError(f"recognize_characters: unknown rule parameter(s) {sorted(unknown)}")
@@ -179,15 +199,19 @@ class Pipeline:
         lexicon_top = lexicon_of(recognition_kwargs)
         beam = beam_of(recognition_kwargs)  # the rest: Keras predict kwargs, no effect on results
         want_characters = _wants_characters(char_boxes)
+        orientation = orientation_of(recognition_kwargs, char_boxes if want_characters else None)
         if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
             raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         if not images:
-            return Results.empty(return_scores, beam, lexicon_top, want_characters)
+            return Results.empty(return_scores, beam, lexicon_top, want_characters, orientation=orientation is not None)
         detection_kwargs = dict(detection_kwargs or {})
         if want_characters:
             detection_kwargs["char_boxes"] = char_boxes
         ctx = getattr(self.detector, "_ctx", None)
         floats = any(im.dtype != np.uint8 for im in images)
+        if floats and orientation is not None:
+            raise NotImplementedError("orientation: only uint8 images are read in two orientations (the float crop path has no "
+                                      "turned set-up)")
         if floats or ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx:
             # float (or any non-uint8) images: the reference's cv2 calls interpolate them in float (tools.py:394, :107); the
             # stage-wise path does the same with the float kernels (kocr_resize_pad_f32 / kocr_warp_crops_f32, round 5) -- off
@@ -197,7 +221,7 @@ class Pipeline:
                 raise TypeError(f"char_boxes: the detector ({type(self.detector).__name__}.detect) cannot give character boxes "
                                 "(it takes no char_boxes argument)")
             out, scales = self._recognize_stagewise([im.astype(np.float32) for im in images] if floats else images, detection_kwargs,
-                                                    hmax, wmax, return_scores, beam, lexicon_top)
+                                                    hmax, wmax, return_scores, beam, lexicon_top, orientation)
         else:
             scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
             hmax = hmax_ if hmax is None else max(hmax, hmax_)
@@ -205,17 +229,27 @@ class Pipeline:
             micro_batch = detection_kwargs.pop("batch_size", 0) or 0
             out = Results.parse_context(ctx.pipeline(
                 images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, hmax, wmax,
-                micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top, **detection_kwargs),
-                return_scores, beam is not None, lexicon_top is not None, want_characters)
+                micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top,
+                **({} if orientation is None else {"orientation": orientation}), **detection_kwargs),
+                return_scores, beam is not None, lexicon_top is not None, want_characters, orientation is not None)
             if want_characters:
                 out.characters = _layout.characters_of(out.characters)
+        if orientation is not None:
+            # every word's box becomes its oriented quad: the same corners, renamed
+            turns, quads, log_words = out.orientation
+            ends = np.cumsum([len(b) for b in out.boxes])
+            out.boxes = [quads[end - len(b):end] if len(b) else b for b, end in zip(out.boxes, ends)]
         out.boxes = self._adjust(out.boxes, scales)
+        if orientation is not None:
+            filled = [b for b in out.boxes if len(b)]
+            out.orientation = (turns, np.concatenate(filled) if filled else quads, log_words)
         if want_characters:
             out.characters = [[_layout.Characters(self._adjust([c.boxes], [scale])[0], c.scores) for c in page]
                               for page, scale in zip(out.characters, scales)]
         return out
 
-    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None):
+    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None,
+                             orientation=None):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size).
@@ -229,16 +263,31 @@ class Pipeline:
         max_width = max(int(max_width), int(wmax or 0))
         padded = np.array([tools.pad(image, width=max_width, height=max_height) for image, _ in resized])
         with_characters = _wants_characters(detection_kwargs.get("char_boxes"))
+        turned = {}
+        if orientation is not None:
+            # passed on only to a recogniser that takes the two arguments
+            takes = _scores.parameters(self.recognizer.recognize_from_boxes)
+            if "orientation" not in takes or "tall_ratio" not in takes or "return_orientation" not in takes:
+                raise TypeError(f"orientation: the recognizer ({type(self.recognizer).__name__}.recognize_from_boxes) cannot read "
+                                "boxes in two orientations (it takes no orientation / tall_ratio / return_orientation argument)")
+            turned = {"orientation": orientation[0], "tall_ratio": orientation[1], "return_orientation": True}
+        how = []
         if return_scores:
             detect = _scores.need("detector", self.detector, "detect")
             recognize = _scores.need("recognizer", self.recognizer, "recognize_from_boxes")
             detected = detect(images=padded, return_scores=True, **detection_kwargs)
-            pairs = [pair for group in recognize(images=padded, box_groups=detected[0], return_scores=True) for pair in group]
+            pairs = [pair for group in recognize(images=padded, box_groups=detected[0], return_scores=True, **turned) for pair in group]
+            if turned:
+                how = [o for _, _, o in pairs]
+                pairs = [(t, score) for t, score, _ in pairs]
             rows = [t for t, _ in pairs]
         else:
             detected = self.detector.detect(images=padded, **detection_kwargs)
             detected = detected if with_characters else (detected,)
-            rows = [t for group in self.recognizer.recognize_from_boxes(images=padded, box_groups=detected[0]) for t in group]
+            rows = [t for group in self.recognizer.recognize_from_boxes(images=padded, box_groups=detected[0], **turned) for t in group]
+            if turned:
+                how = [o for _, o in rows]
+                rows = [t for t, _ in rows]
         alphabet = self.recognizer.alphabet
         out = Results(detected[0], np.full((len(rows), max([48] + [len(t) for t in rows])), -1, np.int32),
                       characters=detected[-1] if with_characters else None)
@@ -268,6 +317,9 @@ class Pipeline:
             for r, (_, score) in enumerate(pairs):
                 chars[r, :len(score.characters)] = score.characters
             out.scores = ([np.asarray(d, np.float32) for d in detected[1]], np.array([score.log_word for _, score in pairs], np.float32), chars)
+        if turned:
+            out.orientation = (np.array([o.turns for o in how], np.int32), np.array([o.box for o in how], np.float32).reshape(-1, 4, 2),
+                               np.array([o.log_words for o in how], np.float32).reshape(-1, 2))
         return out, [scale for _, scale in resized]
 
     def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None, return_scores=False):

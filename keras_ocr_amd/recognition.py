@@ -5,7 +5,7 @@ import typing
 
 import numpy as np
 
-from . import _lib, lexicon as _lexicon, scores as _scores, tools, weights as _weights
+from . import _lib, layout as _layout, lexicon as _lexicon, scores as _scores, tools, weights as _weights
 from .results import Results
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
@@ -380,18 +380,32 @@ class Recognizer:
         return out
 
     def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None,
-                             **kwargs) -> typing.List[typing.List[str]]:
+                             orientation=None, tall_ratio=1.5, return_orientation=False, **kwargs) -> typing.List[typing.List[str]]:
         """Recognizer.recognize_from_boxes (recognition.py:491-537); ``return_scores=True``: per image a list of
         ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None.  ``beam_width`` / ``top_paths``: as
         ``recognize`` -- every text becomes its list of ``(text, log_prob)`` alternatives; ``lexicon_top``: as ``recognize`` --
-        every text becomes its list of ``(word, log_prob)`` lexicon matches."""
+        every text becomes its list of ``(word, log_prob)`` lexicon matches.
+
+        ``orientation="flip"`` / ``"any"`` ("Orientation"; default None: off): every box is read in two
+        orientations on the GPU -- as detected and upside down, or, with ``"any"``, down and up the page for a box whose
+        height is at least ``tall_ratio`` times its width -- and each text (and score) is that of the reading with the larger
+        exact CTC log-probability, an empty reading losing to a non-empty one.  ``return_orientation=True`` (needs
+        ``orientation``): every word becomes ``(text[, score], layout.Orientation(turns, box, log_words))``.  Not together
+        with ``beam_width`` or ``lexicon_top`` (ValueError naming both); uint8 images only (NotImplementedError)."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
         lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
+        _lib.refuse_orientation_with(orientation, beam_width=beam_width, lexicon_top=lexicon_top)
+        if return_orientation and orientation is None:
+            raise ValueError("return_orientation=True needs orientation='flip' or 'any'")
+        oriented = None if orientation is None else (orientation, _lib.orientation_args(orientation, tall_ratio)[1])
         assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
         images = [tools.read(image) for image in images]
+        if oriented and any(np.asarray(image).dtype != np.uint8 for image in images):
+            raise NotImplementedError("orientation: only uint8 images are read in two orientations (the float crop path has no "
+                                      "turned set-up)")
         if not sum(len(b) for b in box_groups):
-            return [[] for _ in images] if return_scores or beam or lexicon_top else [[]] * len(images)
+            return [[] for _ in images] if return_scores or beam or lexicon_top or return_orientation else [[]] * len(images)
         start_end: typing.List[typing.Tuple[int, int]] = []
         for boxes in box_groups:
             start = 0 if not start_end else start_end[-1][1]
@@ -408,12 +422,15 @@ class Recognizer:
             out = self._recognize_crops(np.concatenate(crops) / np.float32(255), return_scores, beam, lexicon_top)
         elif len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top)  # pylint: disable=protected-access
+            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top, oriented)  # pylint: disable=protected-access
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top)  # pylint: disable=protected-access
+            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top, oriented)  # pylint: disable=protected-access
                                        for image, boxes in zip(images, box_groups) if len(boxes)])
         words = self._words(out)
+        if return_orientation:
+            how = _layout.orientations_of(*out.orientation)
+            words = [(*word, o) if return_scores else (word, o) for word, o in zip(words, how)]
         return [words[start:end] for start, end in start_end]
 
     def _words(self, out):

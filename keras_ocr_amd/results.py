@@ -18,6 +18,10 @@ def empty_lexicon(top_words):
     return np.zeros((0, top_words), np.int32), np.zeros((0, top_words), np.float32)
 
 
+def empty_orientation():
+    return np.zeros(0, np.int32), np.zeros((0, 4, 2), np.float32), np.zeros((0, 2), np.float32)
+
+
 @dataclasses.dataclass
 class Results:
     """What one call produced for N images with n_i boxes each, M = sum n_i crops in image order.  A stage that did not run
@@ -34,6 +38,10 @@ class Results:
         words are feasible.
     characters: per image a list of one entry per box, its characters from tl towards tr: a ``(quads (K, 4, 2) float32, scores
         (K,) float32)`` pair below ``Detector`` / ``Pipeline``, a ``layout.Characters`` from there on.
+    orientation: ``(turns (M,) int32, quads (M, 4, 2) float32, log_words (M, 2) float32)`` as
+        ``Context.recognition_orientation``: with it, labels and the recogniser's scores are those of each word's better
+        reading, ``quads[m]`` is [tl, tr, br, bl] of the text as read and ``log_words[m]`` the two candidates' values.  While it
+        is None every layout below is what it was; where present it comes last.
 
     For zero images (``empty``) or zero crops the extras are zero-row arrays of these shapes and dtypes."""
     boxes: typing.Any
@@ -42,35 +50,39 @@ class Results:
     beam: typing.Any = None
     lexicon: typing.Any = None
     characters: typing.Any = None
+    orientation: typing.Any = None
 
     @classmethod
-    def empty(cls, scores=False, beam=None, lexicon=None, characters=False, label_width=48):
+    def empty(cls, scores=False, beam=None, lexicon=None, characters=False, label_width=48, orientation=False):
         """The results of zero images; ``beam`` = (beam_width, top_paths), ``lexicon`` = top_words"""
         return cls([], np.zeros((0, label_width), np.int32), empty_scores(label_width, []) if scores else None,
                    empty_beam(beam[1], label_width) if beam else None, empty_lexicon(lexicon) if lexicon else None,
-                   [] if characters else None)
+                   [] if characters else None, empty_orientation() if orientation else None)
 
     def render_context(self):
-        """``Context.pipeline``'s layout: ``(boxes, labels[, scores][, beam | lexicon][, characters])``, nothing padded"""
+        """``Context.pipeline``'s layout: ``(boxes, labels[, scores][, beam | lexicon][, characters][, orientation])``, nothing
+        padded"""
         alternatives = self.beam if self.lexicon is None else self.lexicon
-        return tuple([self.boxes, self.labels] + [v for v in (self.scores, alternatives, self.characters) if v is not None])
+        return tuple([self.boxes, self.labels] + [v for v in (self.scores, alternatives, self.characters, self.orientation) if v is not None])
 
     @classmethod
-    def parse_context(cls, out, scores=False, beam=False, lexicon=False, characters=False):
+    def parse_context(cls, out, scores=False, beam=False, lexicon=False, characters=False, orientation=False):
         """``render_context``'s inverse, given which extras were asked for (with both ``beam`` and ``lexicon``: the lexicon)"""
-        wanted = (True, True, scores, beam and not lexicon, lexicon, characters)
+        wanted = (True, True, scores, beam and not lexicon, lexicon, characters, orientation)
         if len(out) != sum(map(bool, wanted)):
-            raise ValueError(f"{len(out)} results do not fit scores={scores}, beam={beam}, lexicon={lexicon}, characters={characters}")
+            raise ValueError(f"{len(out)} results do not fit scores={scores}, beam={beam}, lexicon={lexicon}, characters={characters}"
+                             + (f", orientation={orientation}" if orientation else ""))
         values = iter(out)
         return cls(*[next(values) if w else None for w in wanted])
 
     def render_raw(self):
-        """``Pipeline.recognize_raw``'s layout: ``(boxes, labels[, scores_or_None[, beam_or_None[, lexicon]]][, characters])``
-        -- as short as the extras allow, None in the place of an earlier extra that was not asked for"""
+        """``Pipeline.recognize_raw``'s layout: ``(boxes, labels[, scores_or_None[, beam_or_None[, lexicon]]][, characters]
+        [, orientation])`` -- as short as the extras allow, None in the place of an earlier extra that was not asked for"""
         extras = [self.scores, self.beam, self.lexicon]
         while extras and extras[-1] is None:
             extras.pop()
-        return (self.boxes, self.labels, *extras) + (() if self.characters is None else (self.characters,))
+        return (self.boxes, self.labels, *extras) + (() if self.characters is None else (self.characters,)) + \
+            (() if self.orientation is None else (self.orientation,))
 
     def render_detection(self):
         """``Context.get_boxes`` / ``detect``: the boxes, or ``(boxes[, detection scores][, characters])`` with an extra"""
@@ -79,10 +91,11 @@ class Results:
         return (self.boxes,) + (() if self.scores is None else (self.scores[0],)) + (() if self.characters is None else (self.characters,))
 
     def render_recognition(self):
-        """``Context.recognize_boxes``: the labels, or ``(labels[, log_word, char_scores][, beam pair][, lexicon pair])``, flat"""
-        if self.scores is None and self.beam is None and self.lexicon is None:
+        """``Context.recognize_boxes``: the labels, or ``(labels[, log_word, char_scores][, beam pair][, lexicon pair][, turns,
+        quads, log_words])``, flat"""
+        if self.scores is None and self.beam is None and self.lexicon is None and self.orientation is None:
             return self.labels
-        return (self.labels, *(self.scores or (None,))[1:], *(self.beam or ()), *(self.lexicon or ()))
+        return (self.labels, *(self.scores or (None,))[1:], *(self.beam or ()), *(self.lexicon or ()), *(self.orientation or ()))
 
     @classmethod
     def concatenate(cls, parts):
@@ -90,4 +103,5 @@ class Results:
         def join(field):
             values = [getattr(part, field) for part in parts]
             return None if values[0] is None else tuple(None if v[0] is None else np.concatenate(v) for v in zip(*values))
-        return cls(None, np.concatenate([part.labels for part in parts]), join("scores"), join("beam"), join("lexicon"))
+        return cls(None, np.concatenate([part.labels for part in parts]), join("scores"), join("beam"), join("lexicon"),
+                   orientation=join("orientation"))
