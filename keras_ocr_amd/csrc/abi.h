@@ -68,6 +68,20 @@ struct Staging {
   }
 };
 
+// A buffer list L has each(f): f(pointer&, bytes) for every device buffer it describes, stopping at the first failure.  Its
+// bytes as Staging::reserve counts them, and the buffers themselves from an arena:
+template <class L> size_t staging_bytes(L& list) {
+  size_t total = 0;
+  list.each([&](auto*&, size_t b) {
+    total += b + 256;
+    return KOCR_OK;
+  });
+  return total;
+}
+template <class L> int staging_take(Staging& st, L& list) {
+  return list.each([&](auto*& p, size_t b) { return st.scratch(b, p); });
+}
+
 // Detector images per craft_forward: micro_batch (default 32, the Keras predict batch_size, detection.py:779), halved while
 // its workspace exceeds 96 GiB of the 288 GB HBM, at most N.
 int craft_micro_batch(int micro_batch, int N, int H, int W);
@@ -83,6 +97,95 @@ template <class Body> int crnn_batches(kocr_ctx* ctx, long M, Body body) {
   }
   return KOCR_OK;
 }
+
+// The detector's twin: body(s, nb) for images [s, s + nb) of N, craft_micro_batch at a time, the workspace reset before each
+// batch.  The caller has reserved ctx->ws for craft_micro_batch(micro_batch, N, H, W) images.
+template <class Body> int craft_batches(kocr_ctx* ctx, int micro_batch, int N, int H, int W, Body body) {
+  const int mb = craft_micro_batch(micro_batch, N, H, W);
+  for (int s = 0; s < N; s += mb) {
+    ctx->ws_reset();
+    KOCR_TRY(body(s, std::min(mb, N - s)));
+  }
+  return KOCR_OK;
+}
+
+// The compact rows of the `words` winners that orient_select_kernel writes in an oriented run (pipeline.cpp)
+struct OrientWinners {
+  long words = 0;
+  int32_t* lab = nullptr;   // [words][LW]
+  float* logw = nullptr;    // [words]
+  float* chars = nullptr;   // [words][LW]
+  int32_t* turn = nullptr;  // [words]
+  float* quad = nullptr;    // [words][8]
+  float* pair = nullptr;    // [words][2]
+};
+
+// The recogniser stage of kocr_recognize_boxes / kocr_pipeline: its outputs for M crops on a context -- the label rows, and
+// what the context's switches add: score rows (scores), beam rows (BW > 0), lexicon rows (LK > 0).  An oriented run is the
+// same stage over its 2 M candidate crops with scores forced on (no beam, no lexicon: orient_refusal).  each() is the one
+// list of the buffers: every pointer with its size.
+struct RecStage {
+  kocr_ctx* ctx;
+  long M;
+  int LW, BW, BK, LK;
+  bool scores;
+  int32_t* lab = nullptr;
+  CrnnScores sc{nullptr, nullptr};
+  CrnnBeam bm;
+  CrnnLexicon lx;
+  RecStage(kocr_ctx* c, long m, bool force_scores = false)
+      : ctx(c), M(m), LW(crnn_label_width(c)), BW(c->beam_width), BK(c->beam_top_paths), LK(c->lex_top),
+        scores(c->scores_on || force_scores), bm{BW, BK, nullptr, nullptr}, lx{LK, nullptr, nullptr, nullptr} {}
+
+  template <class F> int each(F f) {
+    const size_t m = (size_t)M, i4 = sizeof(int32_t), f4 = sizeof(float);
+    KOCR_TRY(f(lab, m * LW * i4));
+    if (scores) {
+      KOCR_TRY(f(sc.d_logw, m * f4));
+      KOCR_TRY(f(sc.d_chars, m * LW * f4));
+    }
+    if (BW) {
+      KOCR_TRY(f(bm.d_labels, m * BK * LW * i4));
+      KOCR_TRY(f(bm.d_logp, m * BK * f4));
+    }
+    if (LK) {
+      KOCR_TRY(f(lx.d_index, m * LK * i4));
+      KOCR_TRY(f(lx.d_logp, m * LK * f4));
+    }
+    return KOCR_OK;
+  }
+  // (a) what take() needs of an arena, counted as Staging::reserve counts its buffers
+  size_t bytes() { return staging_bytes(*this); }
+  // (b) the buffers from `st`
+  int take(Staging& st) { return staging_take(st, *this); }
+  // (c) the recogniser over d_crops [M][31][200]: ctx->ws sized for one batch (with the lexicon's share), every batch given
+  // its rows of the buffers
+  int run(const float* d_crops) {
+    const int mb = crnn_batch(M);
+    KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, crnn_classes(ctx)) + (LK ? lexicon_workspace_bytes(ctx, mb, true) : 0)));
+    return crnn_batches(ctx, M, [&](long s, int nb) {
+      const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
+      const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
+      const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
+      return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
+                          scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr);
+    });
+  }
+  // (d) what the stage leaves resident for the getters, each record with the state of its switch.  An oriented run keeps its
+  // winners' rows in place of the stage's own.  A stage of no crops that never ran keeps "nothing, M = 0".
+  void keep(const OrientWinners* won = nullptr) const {
+    const OrientWinners w = won ? *won : OrientWinners{};
+    const int m = (int)(won ? w.words : M);
+    ctx->keep_rec_scores(won ? w.logw : sc.d_logw, won ? w.chars : sc.d_chars, m, LW);
+    ctx->keep_beams(bm.d_labels, bm.d_logp, m, LW);
+    ctx->keep_lexicon(lx.d_index, lx.d_logp, m);
+    ctx->keep_orientation(w.turn, w.quad, w.pair, (int)w.words);
+  }
+};
+
+// The status word of the warp set-up (warp_prepare and its kin: 0, 1 = a box with zero width or height, the reference's
+// ZeroDivisionError, else a singular transform) as the entry point's error; `at`: how the entry point cites the reference
+int warp_status_error(kocr_ctx* ctx, const char* fn, int status, const char* at = "ZeroDivisionError at tools.py:95");
 
 // The warp parameters of the boxes [M][4][2] (HOST) of N images, counts[i] (HOST) of them in image i, for crops of
 // th x tw; `out` is the caller's result buffer (checked once there are boxes).  Returns M, or a negative KOCR_* code: a

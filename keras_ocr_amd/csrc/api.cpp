@@ -11,11 +11,7 @@
 // ctx internals
 // ---------------------------------------------------------------------------------------
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
-  ctx->last_pl.valid = false;  // whoever sizes an arena is about to overwrite it (kocr_pipeline re-validates at its end)
-  ctx->last_sc.clear();        // the resident scores likewise
-  ctx->last_beam.clear();      // ... and the resident beam alternatives
-  ctx->last_lex.clear();       // ... and lexicon matches
-  ctx->last_ch.clear();        // ... and character boxes
+  ctx->invalidate_results();  // whoever sizes an arena is about to overwrite it (the entry points re-validate at their end)
   if (bytes <= a.cap) return KOCR_OK;
   if (a.base) {
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -153,6 +149,12 @@ int craft_micro_batch(int micro_batch, int N, int H, int W) {
   return std::min(mb, N);
 }
 
+int warp_status_error(kocr_ctx* ctx, const char* fn, int status, const char* at) {
+  if (status == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, std::string(fn) + ": box with zero width or height (" + at + ")");
+  if (status != 0) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": singular perspective transform");
+  return KOCR_OK;
+}
+
 long prepare_box_warps(kocr_ctx* ctx, const char* fn, int N, const float* boxes, const int32_t* counts, const void* out, int th,
                        int tw, std::vector<WarpParam>& prm) {
   const std::string f(fn);
@@ -167,12 +169,53 @@ long prepare_box_warps(kocr_ctx* ctx, const char* fn, int N, const float* boxes,
   long m = 0;
   for (int i = 0; i < N; ++i)
     for (int j = 0; j < counts[i]; ++j, ++m) {
-      const int rc = warp_prepare(boxes + m * 8, th, tw, &prm[m], nullptr);
-      if (rc == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, f + ": box with zero width or height (ZeroDivisionError at tools.py:95)");
-      if (rc != 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": singular perspective transform");
+      KOCR_TRY(warp_status_error(ctx, fn, warp_prepare(boxes + m * 8, th, tw, &prm[m], nullptr)));
       prm[m].img = i;
     }
   return M;
+}
+
+// kocr_crnn_forward, and with log_word / char_scores kocr_crnn_forward_scores (`fn`: the one that was called): the same
+// batches, with the score buffers ctc_scores_kernel as the last launch
+static int crnn_forward_call(kocr_ctx* ctx, const char* fn, const float* crops, int M, int32_t* labels, float* probs, float* log_word,
+                             float* char_scores, int on_device) {
+  const std::string f(fn);
+  if (M < 0 || (M > 0 && (!crops || !labels))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const bool scores = log_word != nullptr;
+  const int mb = crnn_batch(M);
+  const int LW = crnn_label_width(ctx);
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
+  const size_t wb = sizeof(float), hb = LW * sizeof(float);
+  Staging st{ctx, ctx->ws, fn, on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0, scores ? wb * mb : 0, scores ? hb * mb : 0}));
+  KOCR_TRY(taps_begin(ctx, TAPS_CRNN, M));
+  TapsEnd taps_end{ctx, TAPS_CRNN};
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    taps_batch(ctx, TAPS_CRNN, (int)s, nb);
+    const float* d_c;
+    int32_t* d_l;
+    float* d_p = nullptr;
+    CrnnScores sc{nullptr, nullptr};
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(labels + s * LW, lb * nb, d_l));
+    if (probs) KOCR_TRY(st.out(probs + (size_t)s * LW * C, pb * nb, d_p));
+    if (scores) {
+      KOCR_TRY(st.out(log_word + s, wb * nb, sc.d_logw));
+      KOCR_TRY(st.out(char_scores + s * LW, hb * nb, sc.d_chars));
+    }
+    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p, CRNN_DECODE, nullptr, nullptr, scores ? &sc : nullptr));
+    KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
+    if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
+    if (scores) {
+      KOCR_TRY(st.back(log_word + s, sc.d_logw, wb * nb));
+      KOCR_TRY(st.back(char_scores + s * LW, sc.d_chars, hb * nb));
+    }
+    return st.finish();
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -308,13 +351,8 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
   Staging st{ctx, ctx->ws, "kocr_craft_forward", on_device != 0};
   KOCR_TRY(st.reserve(craft_workspace_bytes(mb, H, W), {in_img * mb, out_img * mb}));
   KOCR_TRY(taps_begin(ctx, TAPS_CRAFT, N));
-  struct TapsEnd {  // also on an error return: no later launch records into this call's taps
-    kocr_ctx* c;
-    ~TapsEnd() { taps_batch(c, TAPS_CRAFT, -1, 0); }
-  } taps_end{ctx};
-  for (int s = 0; s < N; s += mb) {
-    const int nb = std::min(mb, N - s);
-    ctx->ws_reset();
+  TapsEnd taps_end{ctx, TAPS_CRAFT};
+  return craft_batches(ctx, micro_batch, N, H, W, [&](int s, int nb) -> int {
     taps_batch(ctx, TAPS_CRAFT, s, nb);
     const void* d_in;
     float* d_out;
@@ -323,9 +361,8 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
     KOCR_TRY(st.out(h_out, out_img * nb, d_out));
     KOCR_TRY(craft_forward(ctx, d_in, dtype, nb, H, W, d_out));
     KOCR_TRY(st.back(h_out, d_out, out_img * nb));
-    KOCR_TRY(st.finish());
-  }
-  return KOCR_OK;
+    return st.finish();
+  });
 }
 
 int kocr_load_crnn(kocr_ctx* ctx, int n, const char* const* names, const float* const* data,
@@ -343,76 +380,15 @@ int kocr_crnn_label_width(kocr_ctx* ctx) { return ctx ? crnn_label_width(ctx) : 
 int kocr_crnn_set_rnn_steps_to_discard(kocr_ctx* ctx, int steps) { return ctx ? crnn_set_discard(ctx, steps) : KOCR_EINVAL; }
 
 int kocr_crnn_forward(kocr_ctx* ctx, const float* crops, int M, int32_t* labels, float* probs, int on_device) {
-  if (!ctx) return KOCR_EINVAL;
-  if (M < 0 || (M > 0 && (!crops || !labels))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_forward: null buffer");
-  const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = crnn_batch(M);
-  const int LW = crnn_label_width(ctx);
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
-  Staging st{ctx, ctx->ws, "kocr_crnn_forward", on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0}));
-  KOCR_TRY(taps_begin(ctx, TAPS_CRNN, M));
-  struct TapsEnd {  // also on an error return: no later launch records into this call's taps
-    kocr_ctx* c;
-    ~TapsEnd() { taps_batch(c, TAPS_CRNN, -1, 0); }
-  } taps_end{ctx};
-  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    taps_batch(ctx, TAPS_CRNN, (int)s, nb);
-    const float* d_c;
-    int32_t* d_l;
-    float* d_p = nullptr;
-    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
-    KOCR_TRY(st.out(labels + s * LW, lb * nb, d_l));
-    if (probs) KOCR_TRY(st.out(probs + (size_t)s * LW * C, pb * nb, d_p));
-    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p));
-    KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
-    if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
-    return st.finish();
-  });
+  return ctx ? crnn_forward_call(ctx, "kocr_crnn_forward", crops, M, labels, probs, nullptr, nullptr, on_device) : KOCR_EINVAL;
 }
 
-// kocr_crnn_forward with the scores of include/kocr.h ("Scores"): the same batches, ctc_scores_kernel as the last launch
+// kocr_crnn_forward with the scores of include/kocr.h ("Scores")
 int kocr_crnn_forward_scores(kocr_ctx* ctx, const float* crops, int M, int32_t* labels, float* probs, float* log_word,
                              float* char_scores, int on_device) {
   if (!ctx) return KOCR_EINVAL;
-  if (M < 0 || (M > 0 && (!crops || !labels || !log_word || !char_scores)))
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_forward_scores: null buffer");
-  const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward_scores: call kocr_load_crnn first");
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = crnn_batch(M);
-  const int LW = crnn_label_width(ctx);
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
-  const size_t wb = sizeof(float), hb = LW * sizeof(float);
-  Staging st{ctx, ctx->ws, "kocr_crnn_forward_scores", on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0, wb * mb, hb * mb}));
-  KOCR_TRY(taps_begin(ctx, TAPS_CRNN, M));
-  struct TapsEnd {  // also on an error return: no later launch records into this call's taps
-    kocr_ctx* c;
-    ~TapsEnd() { taps_batch(c, TAPS_CRNN, -1, 0); }
-  } taps_end{ctx};
-  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    taps_batch(ctx, TAPS_CRNN, (int)s, nb);
-    const float* d_c;
-    int32_t* d_l;
-    float* d_p = nullptr;
-    CrnnScores sc{nullptr, nullptr};
-    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
-    KOCR_TRY(st.out(labels + s * LW, lb * nb, d_l));
-    if (probs) KOCR_TRY(st.out(probs + (size_t)s * LW * C, pb * nb, d_p));
-    KOCR_TRY(st.out(log_word + s, wb * nb, sc.d_logw));
-    KOCR_TRY(st.out(char_scores + s * LW, hb * nb, sc.d_chars));
-    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p, CRNN_DECODE, nullptr, nullptr, &sc));
-    KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
-    if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
-    KOCR_TRY(st.back(log_word + s, sc.d_logw, wb * nb));
-    KOCR_TRY(st.back(char_scores + s * LW, sc.d_chars, hb * nb));
-    return st.finish();
-  });
+  if (M > 0 && (!log_word || !char_scores)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_forward_scores: null buffer");
+  return crnn_forward_call(ctx, "kocr_crnn_forward_scores", crops, M, labels, probs, log_word, char_scores, on_device);
 }
 
 // The beam search of include/kocr.h ("Beam search") alone: the forward up to fc_12, then ctc_beam_kernel
@@ -824,9 +800,7 @@ int kocr_craft_mse(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int 
   const size_t out_img = (size_t)(H / 2) * (W / 2) * 2 * sizeof(float);
   Staging st{ctx, ctx->ws, "kocr_craft_mse", on_device != 0};
   KOCR_TRY(st.reserve(craft_workspace_bytes(mb, H, W), {in_img * mb, out_img * mb, sizeof(double) * mb}, {out_img * mb}));
-  for (int s = 0; s < N; s += mb) {
-    const int nb = std::min(mb, N - s);
-    ctx->ws_reset();
+  return craft_batches(ctx, micro_batch, N, H, W, [&](int s, int nb) -> int {
     const void* d_in;
     const float* d_y;
     float* d_heat;
@@ -838,9 +812,8 @@ int kocr_craft_mse(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int 
     KOCR_TRY(craft_forward(ctx, d_in, dtype, nb, H, W, d_heat));
     KOCR_TRY(launch_heat_mse(ctx, d_y, d_heat, nb, (H / 2) * (W / 2), d_s));
     KOCR_TRY(st.back(sums + s, d_s, sizeof(double) * nb));
-    KOCR_TRY(st.finish());
-  }
-  return KOCR_OK;
+    return st.finish();
+  });
 }
 
 int kocr_get_boxes(kocr_ctx* ctx, const float* heat, int N, int h, int w, float detection_threshold,

@@ -156,10 +156,10 @@ int kocr_detection_char_boxes(kocr_ctx* ctx, int32_t* char_counts, float* char_q
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_ch;
   const std::string fn("kocr_detection_char_boxes");
-  if (r.off_switch)
+  if (r.state == Resident::OFF)
     KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": the results on this context were produced with character boxes off (kocr_set_char_boxes(ctx, 1, "
                                      "...) before the call)");
-  if (!r.valid)
+  if (r.state == Resident::NONE)
     KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": no character boxes are resident (call it right after kocr_get_boxes, kocr_detect or kocr_pipeline)");
   if (true_chars) *true_chars = r.total;
   if (cap_chars < 0 || ((!char_quads || !char_scores) && cap_chars != 0))

@@ -128,6 +128,11 @@ struct CraftNet;
 struct CrnnNet;
 struct Taps;
 
+// What a resident-result record of kocr_ctx holds: nothing (never produced, or an arena has been sized since), only the fact
+// that the results were produced with the record's switch off, or rows that a getter may copy.
+enum class Resident { NONE, OFF, VALID };
+inline Resident resident(bool on) { return on ? Resident::VALID : Resident::OFF; }
+
 // the rule of chars.hip (tests/chars_statement.py: check_rule)
 struct CharsRule {
   double peak_threshold, valley_ratio, extent_threshold;
@@ -204,13 +209,13 @@ struct kocr_ctx {
 
   // the device-resident results of the last successful kocr_pipeline call (kocr_pipeline_device_results): boxes in the pl
   // arena, counts in the post-processing scratch, label rows in the io arena -- all valid until the next call that uses
-  // those arenas, which clears `valid` first
+  // those arenas, which resets `state` first (arena_reserve)
   struct LastPipeline {
     const float* d_boxes = nullptr;
     const int32_t* d_counts = nullptr;
     const int32_t* d_labels = nullptr;
     int N = 0, cap = 0, M = 0;
-    bool valid = false;
+    Resident state = Resident::NONE;  // never OFF: the call has no switch
   } last_pl;
 
   // scores (kocr_set_scores; DESIGN.md section 4, "Scores"): with the switch on, kocr_get_boxes / kocr_detect /
@@ -221,12 +226,11 @@ struct kocr_ctx {
   struct LastScores {
     const float* d_det = nullptr;  // [N][cap]
     int N = 0, cap = 0;
-    bool det_valid = false, det_off = false;  // det_off: results were produced with the switch off
+    Resident det = Resident::NONE;
     const float* d_logw = nullptr;   // [M]
     const float* d_chars = nullptr;  // [M][lw]
     int M = 0, lw = 0;
-    bool rec_valid = false, rec_off = false;
-    void clear() { det_valid = det_off = rec_valid = rec_off = false; }
+    Resident rec = Resident::NONE;
   } last_sc;
   // beam search (kocr_set_beam; DESIGN.md section 4, "Beam search"): with beam_width > 0, kocr_recognize_boxes /
   // kocr_pipeline also run ctc_beam_kernel on every batch's logits and leave the alternatives resident beside the label
@@ -236,11 +240,10 @@ struct kocr_ctx {
     const int* d_labels = nullptr;  // [M][K][lw]
     const float* d_logp = nullptr;  // [M][K]
     int M = 0, lw = 0, K = 0;
-    bool valid = false, off = false;  // off: results were produced with the beam off
-    void clear() { valid = off = false; }
+    Resident state = Resident::NONE;
   } last_beam;
   void keep_beams(const int* d_labels, const float* d_logp, int M, int lw) {
-    last_beam = {d_labels, d_logp, M, lw, beam_top_paths, beam_width > 0, beam_width == 0};
+    last_beam = {d_labels, d_logp, M, lw, beam_top_paths, resident(beam_width > 0)};
   }
   // lexicon (kocr_set_lexicon / kocr_set_lexicon_match; DESIGN.md section 4, "Lexicon"): the caller's words, resident like
   // weights -- label rows and lengths in the caller's order, `order` the words by ascending length (what a wave of
@@ -262,11 +265,10 @@ struct kocr_ctx {
     const int* d_index = nullptr;   // [M][K]
     const float* d_logp = nullptr;  // [M][K]
     int M = 0, K = 0;
-    bool valid = false, off = false;  // off: results were produced with the match off
-    void clear() { valid = off = false; }
+    Resident state = Resident::NONE;
   } last_lex;
   void keep_lexicon(const int* d_index, const float* d_logp, int M) {
-    last_lex = {d_index, d_logp, M, lex_top, lex_top > 0, lex_top == 0};
+    last_lex = {d_index, d_logp, M, lex_top, resident(lex_top > 0)};
   }
   // character boxes (kocr_set_char_boxes; DESIGN.md section 4, "Characters"): with the switch on, kocr_get_boxes /
   // kocr_detect / kocr_pipeline run the two launches of chars.hip on the heat-maps and boxes in HBM (chars_resident) and leave
@@ -283,8 +285,7 @@ struct kocr_ctx {
     std::vector<int32_t> counts, off;
     int N = 0, cap = 0;
     long long total = 0;
-    bool valid = false, off_switch = false;  // off_switch: results were produced with the switch off
-    void clear() { valid = off_switch = false; }
+    Resident state = Resident::NONE;
   } last_ch;
   // orientation (kocr_set_orientation; DESIGN.md section 4, "Orientation"): with orient_mode != KOCR_ORIENT_OFF,
   // kocr_recognize_boxes / kocr_pipeline warp and read every box in two orientations (2 M crops, candidate-interleaved), and
@@ -298,40 +299,33 @@ struct kocr_ctx {
     const float* d_quads = nullptr;  // [M][4][2]
     const float* d_pairs = nullptr;  // [M][2]
     int M = 0;
-    bool valid = false, off = false;  // off: results were produced with the switch off
-    void clear() { valid = off = false; }
+    Resident state = Resident::NONE;
   } last_or;
   void keep_orientation(const int* d_turns, const float* d_quads, const float* d_pairs, int M) {
-    last_or = {d_turns, d_quads, d_pairs, M, orient_mode != KOCR_ORIENT_OFF, orient_mode == KOCR_ORIENT_OFF};
+    last_or = {d_turns, d_quads, d_pairs, M, resident(orient_mode != KOCR_ORIENT_OFF)};
   }
+  // Whoever sizes an arena is about to overwrite what the records point at: arena_reserve calls this, and so does an entry
+  // point that replaces the results without sizing one.  The one list of what there is to forget.
   void invalidate_results() {
-    last_pl.valid = false;
-    last_sc.clear();
-    last_beam.clear();
-    last_lex.clear();
-    last_ch.clear();
-    last_or.clear();
+    last_pl.state = last_sc.det = last_sc.rec = last_beam.state = last_lex.state = last_ch.state = last_or.state = Resident::NONE;
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
     last_sc.d_det = d;
     last_sc.N = N;
     last_sc.cap = cap;
-    last_sc.det_valid = scores_on;
-    last_sc.det_off = !scores_on;
+    last_sc.det = resident(scores_on);
     // ... and the character boxes that chars_resident has put beside them
     last_ch.N = N;
     last_ch.cap = cap;
-    last_ch.valid = chars_on;
-    last_ch.off_switch = !chars_on;
+    last_ch.state = resident(chars_on);
   }
   void keep_rec_scores(const float* d_logw, const float* d_chars, int M, int lw) {
     last_sc.d_logw = d_logw;
     last_sc.d_chars = d_chars;
     last_sc.M = M;
     last_sc.lw = lw;
-    last_sc.rec_valid = scores_on;
-    last_sc.rec_off = !scores_on;
+    last_sc.rec = resident(scores_on);
   }
 
   // developer instrumentation of the fp16x2 range assumption (kocr_range_stats_enable): off = no cost

@@ -10,7 +10,6 @@ extern "C" int kocr_resize_pad(kocr_ctx* ctx, const uint8_t* src, int n, int sh,
   if (!ctx) return KOCR_EINVAL;
   if (n < 0 || (n > 0 && (!src || !dst))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_resize_pad: null buffer");
   if (n == 0) return KOCR_OK;
-  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t sb = (size_t)n * sh * sw * 3, db = (size_t)n * Hmax * Wmax * 3;
   const size_t tb = (size_t)(4 * (Wmax + Hmax) + 64) * sizeof(int);
@@ -34,7 +33,6 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
   if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detect: bad dtype");
   if (N == 0) return KOCR_OK;
   if (cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detect: cap must be positive");
-  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int h2 = H / 2, w2 = W / 2;
   const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
@@ -48,13 +46,10 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
   KOCR_TRY(st.scratch(heat_b, d_heat));
   KOCR_TRY(st.out(boxes, box_b, d_boxes));
   KOCR_TRY(st.in((const char*)img, in_img * N, d_in));
-  const int mb = craft_micro_batch(micro_batch, N, H, W);
-  KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(mb, H, W)));
-  for (int s = 0; s < N; s += mb) {
-    const int nb = std::min(mb, N - s);
-    ctx->ws_reset();
-    KOCR_TRY(craft_forward(ctx, d_in + (size_t)s * in_img, dtype, nb, H, W, d_heat + (size_t)s * h2 * w2 * 2));
-  }
+  KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(craft_micro_batch(micro_batch, N, H, W), H, W)));
+  KOCR_TRY(craft_batches(ctx, micro_batch, N, H, W, [&](int s, int nb) {
+    return craft_forward(ctx, d_in + (size_t)s * in_img, dtype, nb, H, W, d_heat + (size_t)s * h2 * w2 * 2);
+  }));
   int n_empty = 0;
   const float* d_scores = nullptr;
   KOCR_TRY(postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold,
@@ -69,73 +64,40 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
 }
 
 // ---- orientation (include/kocr.h, "orientation") ----
-// The device buffers of one oriented run over M words: what the crop stage and the recogniser produce for the 2 M
-// candidate-interleaved crops, and the compact rows of the M winners that orient_select_kernel writes.
+// The device buffers of one oriented run over M words: what the crop stage produces for the 2 M candidate-interleaved crops,
+// the recogniser stage over them (its label rows and scores are the candidates'), and the compact rows of the M winners.
 namespace {
 struct OrientRun {
-  WarpParam* prm;  // [2M]
-  float* crops;    // [2M][31][200]
-  int32_t* lab2;   // [2M][LW]
-  float* logw2;    // [2M]
-  float* chars2;   // [2M][LW]
-  int32_t* turns2; // [2M]
-  float* quads2;   // [2M][8]
-  int32_t* lab;    // [M][LW]
-  float* logw;     // [M]
-  float* chars;    // [M][LW]
-  int32_t* turn;   // [M]
-  float* quad;     // [M][8]
-  float* pair;     // [M][2]
+  RecStage rec;
+  OrientWinners won;
+  WarpParam* prm = nullptr;   // [2M]
+  float* crops = nullptr;     // [2M][31][200]
+  int32_t* turns2 = nullptr;  // [2M]
+  float* quads2 = nullptr;    // [2M][8]
+  OrientRun(kocr_ctx* ctx, long M) : rec(ctx, 2 * M, true) { won.words = M; }
+  template <class F> int each(F f) {
+    const size_t m = (size_t)won.words, lw = (size_t)rec.LW, i4 = sizeof(int32_t), f4 = sizeof(float);
+    KOCR_TRY(f(prm, 2 * m * sizeof(WarpParam)));
+    KOCR_TRY(f(crops, 2 * m * CRNN_CROP_PIXELS * f4));
+    KOCR_TRY(rec.each(f));
+    KOCR_TRY(f(turns2, 2 * m * i4));
+    KOCR_TRY(f(quads2, 2 * m * 8 * f4));
+    KOCR_TRY(f(won.lab, m * lw * i4));
+    KOCR_TRY(f(won.logw, m * f4));
+    KOCR_TRY(f(won.chars, m * lw * f4));
+    KOCR_TRY(f(won.turn, m * i4));
+    KOCR_TRY(f(won.quad, m * 8 * f4));
+    return f(won.pair, 2 * m * f4);
+  }
 };
 
-std::vector<size_t> orient_sizes(long M, int LW) {
-  const size_t m = (size_t)M, f = sizeof(float);
-  return {2 * m * sizeof(WarpParam), 2 * m * CRNN_CROP_PIXELS * f, 2 * m * LW * sizeof(int32_t), 2 * m * f, 2 * m * LW * f,
-          2 * m * sizeof(int32_t), 2 * m * 8 * f, m * LW * sizeof(int32_t), m * f, m * LW * f, m * sizeof(int32_t), m * 8 * f, 2 * m * f};
-}
-
-// the bytes orient_alloc takes from an arena, as Staging::reserve counts one buffer
-size_t orient_bytes(long M, int LW) {
-  size_t total = 0;
-  for (size_t b : orient_sizes(M, LW)) total += b + 256;
-  return total;
-}
-
-int orient_alloc(Staging& st, long M, int LW, OrientRun& r) {
-  const std::vector<size_t> b = orient_sizes(M, LW);
-  KOCR_TRY(st.scratch(b[0], r.prm));
-  KOCR_TRY(st.scratch(b[1], r.crops));
-  KOCR_TRY(st.scratch(b[2], r.lab2));
-  KOCR_TRY(st.scratch(b[3], r.logw2));
-  KOCR_TRY(st.scratch(b[4], r.chars2));
-  KOCR_TRY(st.scratch(b[5], r.turns2));
-  KOCR_TRY(st.scratch(b[6], r.quads2));
-  KOCR_TRY(st.scratch(b[7], r.lab));
-  KOCR_TRY(st.scratch(b[8], r.logw));
-  KOCR_TRY(st.scratch(b[9], r.chars));
-  KOCR_TRY(st.scratch(b[10], r.turn));
-  KOCR_TRY(st.scratch(b[11], r.quad));
-  KOCR_TRY(st.scratch(b[12], r.pair));
-  return KOCR_OK;
-}
-
 // Warp, recogniser with scores, choice: r.prm / r.turns2 / r.quads2 are set up, the winners' rows are written.
-int orient_run(kocr_ctx* ctx, const uint8_t* d_img, int H, int W, long M, int LW, const OrientRun& r) {
+int orient_run(kocr_ctx* ctx, const uint8_t* d_img, int H, int W, OrientRun& r) {
+  const long M = r.won.words;
   KOCR_TRY(launch_warp(ctx, d_img, H, W, r.prm, (int)(2 * M), CRNN_CROP_H, CRNN_CROP_W, r.crops));
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(2 * M), crnn_classes(ctx))));
-  KOCR_TRY(crnn_batches(ctx, 2 * M, [&](long s, int nb) {
-    const CrnnScores part{r.logw2 + s, r.chars2 + s * LW};
-    return crnn_forward(ctx, r.crops + s * CRNN_CROP_PIXELS, nb, r.lab2 + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr, &part);
-  }));
-  return launch_orient_select(ctx, r.lab2, r.logw2, r.chars2, r.turns2, r.quads2, M, LW, r.lab, r.logw, r.chars, r.turn, r.quad, r.pair);
-}
-
-// what an oriented run leaves resident: the winners' scores (with scores on), no alternatives, the orientation
-void orient_keep(kocr_ctx* ctx, const OrientRun& r, long M, int LW) {
-  ctx->keep_rec_scores(r.logw, r.chars, (int)M, LW);
-  ctx->keep_beams(nullptr, nullptr, 0, LW);
-  ctx->keep_lexicon(nullptr, nullptr, 0);
-  ctx->keep_orientation(r.turn, r.quad, r.pair, (int)M);
+  KOCR_TRY(r.rec.run(r.crops));
+  return launch_orient_select(ctx, r.rec.lab, r.rec.sc.d_logw, r.rec.sc.d_chars, r.turns2, r.quads2, M, r.rec.LW, r.won.lab, r.won.logw,
+                              r.won.chars, r.won.turn, r.won.quad, r.won.pair);
 }
 
 const char* orient_refusal(const kocr_ctx* ctx, bool with_chars) {
@@ -173,28 +135,25 @@ int recognize_boxes_oriented(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H
         int t = 0;
         const int rc = warp_prepare_turned(boxes + m * 8, ctx->orient_mode, ctx->orient_ratio, c, CRNN_CROP_H, CRNN_CROP_W, &prm[k], &t,
                                            &quads[k * 8]);
-        if (rc == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, std::string(fn) + ": box with zero width or height (ZeroDivisionError at tools.py:95)");
-        if (rc != 0) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": singular perspective transform");
+        KOCR_TRY(warp_status_error(ctx, fn, rc));
         prm[k].img = i;
         turns[k] = t;
       }
-  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int LW = crnn_label_width(ctx);
   const size_t ib = (size_t)N * H * W * 3;
+  OrientRun r(ctx, M);
   Staging st{ctx, ctx->io, fn, on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {orient_bytes(M, LW)}));
-  OrientRun r;
+  KOCR_TRY(st.reserve(0, {ib}, {staging_bytes(r)}));
   const uint8_t* d_img;
-  KOCR_TRY(orient_alloc(st, M, LW, r));
+  KOCR_TRY(staging_take(st, r));
   KOCR_TRY(st.in(img_rgb, ib, d_img));
   KOCR_TRY(st.put(r.prm, (const WarpParam*)prm.data(), prm.size() * sizeof(WarpParam)));
   KOCR_TRY(st.put(r.turns2, (const int32_t*)turns.data(), turns.size() * sizeof(int32_t)));
   KOCR_TRY(st.put(r.quads2, (const float*)quads.data(), quads.size() * sizeof(float)));
-  KOCR_TRY(orient_run(ctx, d_img, H, W, M, LW, r));
-  KOCR_TRY(st.download(labels, (const int32_t*)r.lab, (size_t)M * LW * sizeof(int32_t)));
+  KOCR_TRY(orient_run(ctx, d_img, H, W, r));
+  KOCR_TRY(st.download(labels, (const int32_t*)r.won.lab, (size_t)M * r.rec.LW * sizeof(int32_t)));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // also: the host vectors' copies are done
-  orient_keep(ctx, r, M, LW);
+  r.rec.keep(&r.won);
   return KOCR_OK;
 }
 }  // namespace
@@ -205,64 +164,29 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
                                     const int32_t* counts, int32_t* labels, int on_device) {
   if (!ctx) return KOCR_EINVAL;
   if (N < 0 || (N > 0 && (!img_rgb || !counts))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes: null buffer");
-  const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_recognize_boxes: call kocr_load_crnn first");
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_recognize_boxes: call kocr_load_crnn first");
   if (ctx->orient_mode != KOCR_ORIENT_OFF) return recognize_boxes_oriented(ctx, img_rgb, N, H, W, boxes, counts, labels, on_device);
   std::vector<WarpParam> prm;
   const long M = prepare_box_warps(ctx, "kocr_recognize_boxes", N, boxes, counts, labels, CRNN_CROP_H, CRNN_CROP_W, prm);
   if (M <= 0) return (int)M;
-  ctx->invalidate_results();
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int LW = crnn_label_width(ctx);
-  const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float);
-  const size_t lab_b = (size_t)M * LW * sizeof(int32_t), pb = (size_t)M * sizeof(WarpParam);
-  const bool scores = ctx->scores_on;
-  const size_t lw_b = scores ? (size_t)M * sizeof(float) : 0, ch_b = lw_b * LW;
-  const int BW = ctx->beam_width, BK = ctx->beam_top_paths;
-  const size_t bl_b = BW ? (size_t)M * BK * LW * sizeof(int32_t) : 0, bv_b = BW ? (size_t)M * BK * sizeof(float) : 0;
-  const int LK = ctx->lex_top;
-  const size_t li_b = LK ? (size_t)M * LK * sizeof(int32_t) : 0, lv_b = LK ? (size_t)M * LK * sizeof(float) : 0;
+  const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), pb = (size_t)M * sizeof(WarpParam);
+  RecStage rec(ctx, M);
   Staging st{ctx, ctx->io, "kocr_recognize_boxes", on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, lab_b, lw_b, ch_b, bl_b, bv_b, li_b, lv_b}));
-  const WarpParam* d_prm;
+  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, rec.bytes()}));
+  WarpParam* d_prm;
   float* d_crops;
-  int32_t* d_lab;
   const uint8_t* d_img;
-  CrnnScores sc{nullptr, nullptr};
   KOCR_TRY(st.scratch(pb, d_prm));
   KOCR_TRY(st.scratch(crop_b, d_crops));
-  KOCR_TRY(st.scratch(lab_b, d_lab));
-  if (scores) {
-    KOCR_TRY(st.scratch(lw_b, sc.d_logw));
-    KOCR_TRY(st.scratch(ch_b, sc.d_chars));
-  }
-  CrnnBeam bm{BW, BK, nullptr, nullptr};
-  if (BW) {
-    KOCR_TRY(st.scratch(bl_b, bm.d_labels));
-    KOCR_TRY(st.scratch(bv_b, bm.d_logp));
-  }
-  CrnnLexicon lx{LK, nullptr, nullptr, nullptr};
-  if (LK) {
-    KOCR_TRY(st.scratch(li_b, lx.d_index));
-    KOCR_TRY(st.scratch(lv_b, lx.d_logp));
-  }
+  KOCR_TRY(rec.take(st));
   KOCR_TRY(st.in(img_rgb, ib, d_img));
-  KOCR_TRY(st.put((WarpParam*)d_prm, prm.data(), pb));
+  KOCR_TRY(st.put(d_prm, (const WarpParam*)prm.data(), pb));
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), C) + (LK ? lexicon_workspace_bytes(ctx, crnn_batch(M), true) : 0)));
-  KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
-    const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
-    const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
-    const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
-    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
-                        scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr);
-  }));
-  KOCR_TRY(st.download(labels, d_lab, lab_b));
+  KOCR_TRY(rec.run(d_crops));
+  KOCR_TRY(st.download(labels, (const int32_t*)rec.lab, (size_t)M * rec.LW * sizeof(int32_t)));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->keep_rec_scores(sc.d_logw, sc.d_chars, (int)M, LW);
-  ctx->keep_beams(bm.d_labels, bm.d_logp, (int)M, LW);
-  ctx->keep_lexicon(lx.d_index, lx.d_logp, (int)M);
-  ctx->keep_orientation(nullptr, nullptr, nullptr, 0);
+  rec.keep();
   return KOCR_OK;
 }
 
@@ -275,7 +199,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   if (n_crops) *n_crops = 0;
   if (N < 0 || (N > 0 && (!imgs || !hs || !ws || !dhs || !dws || !boxes || !counts)))
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline: null buffer");
-  ctx->invalidate_results();
+  ctx->invalidate_results();  // also for the returns before the first arena is sized: N == 0 replaces the results by none
   if (N == 0) return KOCR_OK;
   if (!ctx->craft) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_pipeline: call kocr_load_craft first");
   if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_pipeline: call kocr_load_crnn first");
@@ -315,14 +239,10 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     i = j;
   }
   // ---- detector forward (micro-batched) ----
-  const int mb = craft_micro_batch(micro_batch, N, Hmax, Wmax);
-  KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(mb, Hmax, Wmax)));
-  for (int s = 0; s < N; s += mb) {
-    const int nb = std::min(mb, N - s);
-    ctx->ws_reset();
-    KOCR_TRY(craft_forward(ctx, d_bat + (size_t)s * Hmax * Wmax * 3, KOCR_U8, nb, Hmax, Wmax,
-                           d_heat + (size_t)s * h2 * w2 * 2));
-  }
+  KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(craft_micro_batch(micro_batch, N, Hmax, Wmax), Hmax, Wmax)));
+  KOCR_TRY(craft_batches(ctx, micro_batch, N, Hmax, Wmax, [&](int s, int nb) {
+    return craft_forward(ctx, d_bat + (size_t)s * Hmax * Wmax * 3, KOCR_U8, nb, Hmax, Wmax, d_heat + (size_t)s * h2 * w2 * 2);
+  }));
   // ---- boxes: the host learns only the per-image counts here (needed to size the crop batch); the boxes themselves
   // go to the caller asynchronously while the device already derives the crop homographies from its own copy ----
   // CAPACITY WITHOUT RECOMPUTATION (round 6; the reference has no cap, detection.py:230-286): `cap` and `max_crops` size the
@@ -360,172 +280,144 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (host_flags[2] > 0)
       KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR, "kocr_pipeline: empty contour list (IndexError at detection.py:272)");
-    if (host_flags[4] == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, "kocr_pipeline: box with zero width or height (tools.py:95)");
-    if (host_flags[4] != 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline: singular perspective transform");
-    return KOCR_OK;
+    return warp_status_error(ctx, "kocr_pipeline", host_flags[4], "tools.py:95");
   };
   if (M == 0) {
     KOCR_TRY(finish());
-    ctx->last_pl = {d_boxes, dv.d_counts, nullptr, N, cap, 0, true};
+    ctx->last_pl = {d_boxes, dv.d_counts, nullptr, N, cap, 0, Resident::VALID};
     ctx->keep_det_scores(dv.d_scores, N, d_cap);
-    ctx->keep_rec_scores(nullptr, nullptr, 0, crnn_label_width(ctx));
-    ctx->keep_beams(nullptr, nullptr, 0, crnn_label_width(ctx));
-    ctx->keep_lexicon(nullptr, nullptr, 0);
-    ctx->keep_orientation(nullptr, nullptr, nullptr, 0);
+    RecStage(ctx, 0).keep();
     return KOCR_OK;
   }
   if (!labels && d_cap == cap) {
     KOCR_TRY(finish());  // an empty contour list (the reference's IndexError) takes precedence over the capacity error
     KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_pipeline: more crops than max_crops");
   }
-  const int LW = crnn_label_width(ctx);
-  const char* const over_capacity =
-      "kocr_pipeline: an image has more boxes than cap, or there are more crops than max_crops; the results are "
-      "resident -- fetch them with kocr_pipeline_results into buffers sized from counts / n_crops";
+  // ---- the end of both routes: the label rows `d_lab` of `rec` (an oriented run's: of its winners) to the caller, the
+  // status words to the host, what stays resident ----
+  int* d_status;
+  auto finish_crops = [&](const RecStage& rec, const OrientWinners* won) -> int {
+    const int32_t* d_lab = won ? won->lab : rec.lab;
+    if (host_fits)
+      KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, (size_t)M * rec.LW * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    KOCR_TRY(finish());
+    ctx->last_pl = {d_boxes, dv.d_counts, d_lab, N, d_cap, (int)M, Resident::VALID};
+    ctx->keep_det_scores(dv.d_scores, N, d_cap);
+    rec.keep(won);
+    if (!host_fits)
+      KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_pipeline: an image has more boxes than cap, or there are more crops than max_crops; the results are "
+                                     "resident -- fetch them with kocr_pipeline_results into buffers sized from counts / n_crops");
+    return KOCR_OK;
+  };
   if (oriented) {
     // ---- both orientations of every box: turned set-up on the device, 2 M crops, recogniser with scores, choice ----
-    OrientRun r;
-    int* d_status;
-    KOCR_TRY(io.reserve(0, {}, {orient_bytes(M, LW), 256}));
-    KOCR_TRY(orient_alloc(io, M, LW, r));
+    OrientRun r(ctx, M);
+    KOCR_TRY(io.reserve(0, {}, {staging_bytes(r), 256}));
+    KOCR_TRY(staging_take(io, r));
     KOCR_TRY(io.scratch(256, d_status));
     KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), ctx->stream));
     KOCR_TRY(launch_warp_prepare_turned(ctx, d_boxes, dv.d_counts, N, d_cap, ctx->orient_mode, ctx->orient_ratio, CRNN_CROP_H,
                                         CRNN_CROP_W, r.prm, r.turns2, r.quads2, d_status));
-    KOCR_TRY(orient_run(ctx, d_bat, Hmax, Wmax, M, LW, r));
-    if (host_fits)
-      KOCR_HIP(ctx, hipMemcpyAsync(labels, r.lab, (size_t)M * LW * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    KOCR_TRY(finish());
-    ctx->last_pl = {d_boxes, dv.d_counts, r.lab, N, d_cap, (int)M, true};
-    ctx->keep_det_scores(dv.d_scores, N, d_cap);
-    orient_keep(ctx, r, M, LW);
-    if (!host_fits) {
-      ctx->set_err(over_capacity);
-      return KOCR_ECAPACITY;
-    }
-    return KOCR_OK;
+    KOCR_TRY(orient_run(ctx, d_bat, Hmax, Wmax, r));
+    return finish_crops(r.rec, &r.won);
   }
-  // ---- crops: homographies on the device (warp.hip), no host round trip ----
-  const size_t crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), lab_b = (size_t)M * LW * sizeof(int32_t);
-  const size_t pb = (size_t)M * sizeof(WarpParam);
-  const bool scores = ctx->scores_on;
-  const size_t lw_b = scores ? (size_t)M * sizeof(float) : 0, ch_b = lw_b * LW;
-  const int BW = ctx->beam_width, BK = ctx->beam_top_paths;
-  const size_t bl_b = BW ? (size_t)M * BK * LW * sizeof(int32_t) : 0, bv_b = BW ? (size_t)M * BK * sizeof(float) : 0;
-  const int LK = ctx->lex_top;
-  const size_t li_b = LK ? (size_t)M * LK * sizeof(int32_t) : 0, lv_b = LK ? (size_t)M * LK * sizeof(float) : 0;
-  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, lab_b, 256, lw_b, ch_b, bl_b, bv_b, li_b, lv_b}));
+  // ---- crops: homographies on the device (warp.hip), no host round trip; then the recogniser ----
+  const size_t crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), pb = (size_t)M * sizeof(WarpParam);
+  RecStage rec(ctx, M);
+  KOCR_TRY(io.reserve(0, {}, {pb, crop_b, 256, rec.bytes()}));
   WarpParam* d_prm;
   float* d_crops;
-  int32_t* d_lab;
-  int* d_status;
-  CrnnScores sc{nullptr, nullptr};
   KOCR_TRY(io.scratch(pb, d_prm));
   KOCR_TRY(io.scratch(crop_b, d_crops));
-  KOCR_TRY(io.scratch(lab_b, d_lab));
   KOCR_TRY(io.scratch(256, d_status));
-  if (scores) {
-    KOCR_TRY(io.scratch(lw_b, sc.d_logw));
-    KOCR_TRY(io.scratch(ch_b, sc.d_chars));
-  }
-  CrnnBeam bm{BW, BK, nullptr, nullptr};
-  if (BW) {
-    KOCR_TRY(io.scratch(bl_b, bm.d_labels));
-    KOCR_TRY(io.scratch(bv_b, bm.d_logp));
-  }
-  CrnnLexicon lx{LK, nullptr, nullptr, nullptr};
-  if (LK) {
-    KOCR_TRY(io.scratch(li_b, lx.d_index));
-    KOCR_TRY(io.scratch(lv_b, lx.d_logp));
-  }
+  KOCR_TRY(rec.take(io));
   KOCR_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int), ctx->stream));
   KOCR_TRY(launch_warp_prepare(ctx, d_boxes, dv.d_counts, N, d_cap, CRNN_CROP_H, CRNN_CROP_W, d_prm, d_status));
   KOCR_TRY(launch_warp(ctx, d_bat, Hmax, Wmax, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
-  // ---- recogniser ----
-  KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(crnn_batch(M), crnn_classes(ctx)) +
-                           (LK ? lexicon_workspace_bytes(ctx, crnn_batch(M), true) : 0)));
-  KOCR_TRY(crnn_batches(ctx, M, [&](long s, int nb) {
-    const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
-    const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
-    const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
-    return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, d_lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
-                        scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr);
-  }));
-  if (host_fits) KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, lab_b, hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_TRY(finish());
-  ctx->last_pl = {d_boxes, dv.d_counts, d_lab, N, d_cap, (int)M, true};
-  ctx->keep_det_scores(dv.d_scores, N, d_cap);
-  ctx->keep_rec_scores(sc.d_logw, sc.d_chars, (int)M, LW);
-  ctx->keep_beams(bm.d_labels, bm.d_logp, (int)M, LW);
-  ctx->keep_lexicon(lx.d_index, lx.d_logp, (int)M);
-  ctx->keep_orientation(nullptr, nullptr, nullptr, 0);
-  if (!host_fits) {
-    ctx->set_err(over_capacity);
-    return KOCR_ECAPACITY;
-  }
+  KOCR_TRY(rec.run(d_crops));
+  return finish_crops(rec, nullptr);
+}
+
+namespace {
+// The getters of resident results (include/kocr.h) share one sequence: produced with the switch off -> KOCR_EINVAL; nothing
+// resident -> KOCR_EINVAL; the sizes reported; buffers too small -> KOCR_ECAPACITY; nothing to copy -> KOCR_OK; the copies on
+// the ctx stream; synchronise.  What is copied: one pitched block (the detector side: `rows` device rows of dev_pitch bytes
+// into the caller's rows host_pitch apart; `fits`: the caller's buffer is there and wide enough), then M crops of every flat
+// row (the recogniser side: `bytes` per crop, as they were PRODUCED, whatever the context's settings say by now).
+struct FetchSize {
+  int32_t* out;
+  int value;
+};
+struct FetchBlock {
+  void* host;
+  size_t host_pitch;
+  const void* dev;
+  size_t dev_pitch;
+  int rows;
+  bool fits;
+};
+struct FetchRow {
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+
+int fetch_resident(kocr_ctx* ctx, const char* fn, Resident state, const char* off_tail, const char* none_tail, const std::string& small_tail,
+                   std::initializer_list<FetchSize> sizes, const FetchBlock* block, int M, int max_crops,
+                   std::initializer_list<FetchRow> rows) {
+  if (state == Resident::OFF) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + off_tail);
+  if (state == Resident::NONE) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + none_tail);
+  for (const FetchSize& s : sizes)
+    if (s.out) *s.out = s.value;
+  bool fits = (!block || block->fits) && (M == 0 || max_crops >= M);
+  for (const FetchRow& r : rows) fits = fits && (M == 0 || r.host);
+  if (!fits) KOCR_FAIL(ctx, KOCR_ECAPACITY, std::string(fn) + small_tail);
+  if (!block && M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  if (block)
+    KOCR_HIP(ctx, hipMemcpy2DAsync(block->host, block->host_pitch, block->dev, block->dev_pitch, block->dev_pitch, (size_t)block->rows,
+                                   hipMemcpyDeviceToHost, ctx->stream));
+  if (M > 0)
+    for (const FetchRow& r : rows) KOCR_HIP(ctx, hipMemcpyAsync(r.host, r.dev, (size_t)M * r.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KOCR_OK;
 }
+
+std::string smaller_than(const char* what, int M) {
+  return std::string(": buffers smaller than the resident ") + what + " (max_crops >= " + std::to_string(M) + ")";
+}
+const char* const SCORES_OFF = ": the results on this context were produced with scores off (kocr_set_scores(ctx, 1) before the call)";
+}  // namespace
 
 // The resident results of the last kocr_pipeline call copied into the caller's (larger) buffers: see include/kocr.h
 extern "C" int kocr_pipeline_results(kocr_ctx* ctx, float* boxes, int cap, int32_t* labels, int max_crops) {
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_pl;
-  if (!r.valid) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline_results: no kocr_pipeline result is resident (call it right after kocr_pipeline)");
-  if (!boxes || cap < r.cap || (r.M > 0 && (!labels || max_crops < r.M)))
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_pipeline_results: buffers smaller than the resident results (cap >= " + std::to_string(r.cap) +
-                                       ", max_crops >= " + std::to_string(r.M) + ")");
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  // device rows are r.cap boxes apart, the caller's cap boxes
-  KOCR_HIP(ctx, hipMemcpy2DAsync(boxes, (size_t)cap * 32, r.d_boxes, (size_t)r.cap * 32, (size_t)r.cap * 32, (size_t)r.N,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-  if (r.M > 0)
-    KOCR_HIP(ctx, hipMemcpyAsync(labels, r.d_labels, (size_t)r.M * crnn_label_width(ctx) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  const FetchBlock rows{boxes, (size_t)cap * 32, r.d_boxes, (size_t)r.cap * 32, r.N, boxes && cap >= r.cap};
+  return fetch_resident(ctx, "kocr_pipeline_results", r.state, "", ": no kocr_pipeline result is resident (call it right after kocr_pipeline)",
+                        ": buffers smaller than the resident results (cap >= " + std::to_string(r.cap) + ", max_crops >= " +
+                            std::to_string(r.M) + ")",
+                        {}, &rows, r.M, max_crops, {{labels, r.d_labels, crnn_label_width(ctx) * sizeof(int32_t)}});
 }
 
 // The resident scores (see include/kocr.h, "Scores")
-static const char* const SCORES_OFF = ": the results on this context were produced with scores off (kocr_set_scores(ctx, 1) before the call)";
-
 extern "C" int kocr_detection_scores(kocr_ctx* ctx, float* scores, int cap) {
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_sc;
-  if (r.det_off) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_detection_scores") + SCORES_OFF);
-  if (!r.det_valid)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detection_scores: no detection scores are resident (call it right after kocr_get_boxes, "
-                                "kocr_detect or kocr_pipeline)");
-  if (!scores || cap < r.cap)
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_detection_scores: buffer smaller than the resident scores (cap >= " + std::to_string(r.cap) + ")");
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  // device rows are r.cap scores apart, the caller's cap scores
-  KOCR_HIP(ctx, hipMemcpy2DAsync(scores, (size_t)cap * 4, r.d_det, (size_t)r.cap * 4, (size_t)r.cap * 4, (size_t)r.N,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  const FetchBlock rows{scores, (size_t)cap * 4, r.d_det, (size_t)r.cap * 4, r.N, scores && cap >= r.cap};
+  return fetch_resident(ctx, "kocr_detection_scores", r.det, SCORES_OFF,
+                        ": no detection scores are resident (call it right after kocr_get_boxes, kocr_detect or kocr_pipeline)",
+                        ": buffer smaller than the resident scores (cap >= " + std::to_string(r.cap) + ")", {}, &rows, 0, 0, {});
 }
 
 extern "C" int kocr_recognition_scores(kocr_ctx* ctx, float* log_word, float* char_scores, int max_crops, int32_t* n_crops,
                                        int32_t* label_width) {
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_sc;
-  if (r.rec_off) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_recognition_scores") + SCORES_OFF);
-  if (!r.rec_valid)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_scores: no recognition scores are resident (call it right after "
-                                "kocr_recognize_boxes or kocr_pipeline)");
-  if (n_crops) *n_crops = r.M;
-  if (label_width) *label_width = r.lw;
-  if (r.M > 0 && (!log_word || !char_scores || max_crops < r.M))
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_recognition_scores: buffers smaller than the resident scores (max_crops >= " +
-                                       std::to_string(r.M) + ")");
-  if (r.M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  // rows of the width they were PRODUCED with, whatever kocr_crnn_label_width() says by now
-  KOCR_HIP(ctx, hipMemcpyAsync(log_word, r.d_logw, (size_t)r.M * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(char_scores, r.d_chars, (size_t)r.M * r.lw * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  return fetch_resident(ctx, "kocr_recognition_scores", r.rec, SCORES_OFF, ": no recognition scores are resident (call it right after kocr_recognize_boxes or kocr_pipeline)",
+                        smaller_than("scores", r.M), {{n_crops, r.M}, {label_width, r.lw}}, nullptr, r.M, max_crops,
+                        {{log_word, r.d_logw, sizeof(float)}, {char_scores, r.d_chars, r.lw * sizeof(float)}});
 }
 
 // The resident beam alternatives (see include/kocr.h, "Beam search")
@@ -533,25 +425,11 @@ extern "C" int kocr_recognition_beams(kocr_ctx* ctx, int32_t* labels, float* log
                                       int32_t* label_width, int32_t* top_paths) {
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_beam;
-  if (r.off)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_beams: the results on this context were produced with the beam off "
-                                "(kocr_set_beam(ctx, beam_width, top_paths) before the call)");
-  if (!r.valid)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_beams: no beam alternatives are resident (call it right after "
-                                "kocr_recognize_boxes or kocr_pipeline)");
-  if (n_crops) *n_crops = r.M;
-  if (label_width) *label_width = r.lw;
-  if (top_paths) *top_paths = r.K;
-  if (r.M > 0 && (!labels || !log_prob || max_crops < r.M))
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_recognition_beams: buffers smaller than the resident alternatives (max_crops >= " +
-                                       std::to_string(r.M) + ")");
-  if (r.M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  // rows of the width and top_paths they were PRODUCED with
-  KOCR_HIP(ctx, hipMemcpyAsync(labels, r.d_labels, (size_t)r.M * r.K * r.lw * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(log_prob, r.d_logp, (size_t)r.M * r.K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  return fetch_resident(ctx, "kocr_recognition_beams", r.state,
+                        ": the results on this context were produced with the beam off (kocr_set_beam(ctx, beam_width, top_paths) before the call)",
+                        ": no beam alternatives are resident (call it right after kocr_recognize_boxes or kocr_pipeline)", smaller_than("alternatives", r.M),
+                        {{n_crops, r.M}, {label_width, r.lw}, {top_paths, r.K}}, nullptr, r.M, max_crops,
+                        {{labels, r.d_labels, (size_t)r.K * r.lw * sizeof(int32_t)}, {log_prob, r.d_logp, r.K * sizeof(float)}});
 }
 
 // The resident lexicon matches (see include/kocr.h, "Lexicon")
@@ -559,31 +437,20 @@ extern "C" int kocr_recognition_lexicon(kocr_ctx* ctx, int32_t* index, float* lo
                                         int32_t* top_words) {
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_lex;
-  if (r.off)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_lexicon: the results on this context were produced with the lexicon match off "
-                                "(kocr_set_lexicon_match(ctx, top_words) before the call)");
-  if (!r.valid)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_lexicon: no lexicon matches are resident (call it right after "
-                                "kocr_recognize_boxes or kocr_pipeline)");
-  if (n_crops) *n_crops = r.M;
-  if (top_words) *top_words = r.K;
-  if (r.M > 0 && (!index || !log_prob || max_crops < r.M))
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_recognition_lexicon: buffers smaller than the resident matches (max_crops >= " +
-                                       std::to_string(r.M) + ")");
-  if (r.M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  // rows of the top_words they were PRODUCED with
-  KOCR_HIP(ctx, hipMemcpyAsync(index, r.d_index, (size_t)r.M * r.K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(log_prob, r.d_logp, (size_t)r.M * r.K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  return fetch_resident(ctx, "kocr_recognition_lexicon", r.state,
+                        ": the results on this context were produced with the lexicon match off (kocr_set_lexicon_match(ctx, top_words) before "
+                        "the call)",
+                        ": no lexicon matches are resident (call it right after kocr_recognize_boxes or kocr_pipeline)", smaller_than("matches", r.M),
+                        {{n_crops, r.M}, {top_words, r.K}}, nullptr, r.M, max_crops,
+                        {{index, r.d_index, r.K * sizeof(int32_t)}, {log_prob, r.d_logp, r.K * sizeof(float)}});
 }
 
 // The results of the last successful kocr_pipeline call as they lie in HBM (see include/kocr.h)
 extern "C" int kocr_pipeline_device_results(kocr_ctx* ctx, const float** d_boxes, const int32_t** d_counts, const int32_t** d_labels,
                                             int32_t* N, int32_t* cap, int32_t* M) {
   if (!ctx) return KOCR_EINVAL;
-  if (!ctx->last_pl.valid) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline_device_results: no kocr_pipeline result is resident (call it right after kocr_pipeline)");
+  if (ctx->last_pl.state != Resident::VALID)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline_device_results: no kocr_pipeline result is resident (call it right after kocr_pipeline)");
   if (d_boxes) *d_boxes = ctx->last_pl.d_boxes;
   if (d_counts) *d_counts = ctx->last_pl.d_counts;
   if (d_labels) *d_labels = ctx->last_pl.d_labels;
@@ -616,23 +483,12 @@ extern "C" int kocr_recognition_orientation(kocr_ctx* ctx, int32_t* turns, float
                                             int32_t* n_crops) {
   if (!ctx) return KOCR_EINVAL;
   const auto& r = ctx->last_or;
-  if (r.off)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_orientation: the results on this context were produced with orientation off "
-                                "(kocr_set_orientation(ctx, mode, tall_ratio) before the call)");
-  if (!r.valid)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognition_orientation: no orientation is resident (call it right after "
-                                "kocr_recognize_boxes or kocr_pipeline)");
-  if (n_crops) *n_crops = r.M;
-  if (r.M > 0 && (!turns || !quads || !log_words || max_crops < r.M))
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_recognition_orientation: buffers smaller than the resident orientation (max_crops >= " +
-                                       std::to_string(r.M) + ")");
-  if (r.M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  KOCR_HIP(ctx, hipMemcpyAsync(turns, r.d_turns, (size_t)r.M * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(quads, r.d_quads, (size_t)r.M * 8 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipMemcpyAsync(log_words, r.d_pairs, (size_t)r.M * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KOCR_OK;
+  return fetch_resident(ctx, "kocr_recognition_orientation", r.state,
+                        ": the results on this context were produced with orientation off (kocr_set_orientation(ctx, mode, tall_ratio) before "
+                        "the call)",
+                        ": no orientation is resident (call it right after kocr_recognize_boxes or kocr_pipeline)", smaller_than("orientation", r.M), {{n_crops, r.M}}, nullptr,
+                        r.M, max_crops,
+                        {{turns, r.d_turns, sizeof(int32_t)}, {quads, r.d_quads, 8 * sizeof(float)}, {log_words, r.d_pairs, 2 * sizeof(float)}});
 }
 
 // The turned crop stage alone: the boxes go into the [N][cap] layout getBoxes leaves (cap = the largest count), the set-up
@@ -689,9 +545,7 @@ extern "C" int kocr_warp_crops_turned(kocr_ctx* ctx, const uint8_t* img_rgb, int
   KOCR_TRY(st.download(quads, (const float*)d_quads, qb));
   KOCR_TRY(st.download(&status, (const int*)d_status, sizeof(int)));
   KOCR_TRY(st.finish());
-  if (status == 1) KOCR_FAIL(ctx, KOCR_EZERODIV, std::string(fn) + ": box with zero width or height (ZeroDivisionError at tools.py:95)");
-  if (status != 0) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": singular perspective transform");
-  return KOCR_OK;
+  return warp_status_error(ctx, fn, status);
 }
 
 // The choice alone, on the caller's rows

@@ -36,6 +36,12 @@ struct Taps {
 int taps_begin(kocr_ctx* ctx, TapNet net, int N);
 // ... its next micro-batch holds images n0 .. n0 + nb - 1 (n0 = -1: the call is over)
 void taps_batch(kocr_ctx* ctx, TapNet net, int n0, int nb);
+// the end of a forward call of `net`, also on an error return: no later launch records into this call's taps
+struct TapsEnd {
+  kocr_ctx* c;
+  TapNet net;
+  ~TapsEnd() { taps_batch(c, net, -1, 0); }
+};
 // before the launch of `name`: *out = nullptr if it is not tapped, else its record, the input copy enqueued
 int tap_begin(kocr_ctx* ctx, const std::string& name, const Tensor* in, Taps::Tap** out);
 // after it: what it wrote

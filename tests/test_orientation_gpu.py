@@ -209,11 +209,29 @@ def test_recognize_boxes_equals_the_composition(crnn_ctx, m):
         _same((labels, want[1], want[2], turns, quads, pairs), want)
         # and off again: today's results, and nothing of the orientation resident
         off = c.recognize_boxes(pages, groups, return_scores=True)
-        plain = c.crnn_forward_scores(c.warp_crops(pages, groups))
-        for g, w in zip(off, plain):
-            assert np.array_equal(g, w)
         with pytest.raises(ValueError, match="orientation off"):
             c.recognition_orientation()
+        plain = c.crnn_forward_scores(c.warp_crops(pages, groups))  # sizes the arenas: nothing is resident after it
+        for g, w in zip(off, plain):
+            assert np.array_equal(g, w)
+        with pytest.raises(ValueError, match="no orientation is resident"):
+            c.recognition_orientation()
+
+
+def test_sizing_an_arena_forgets_the_orientation_with_the_scores(crnn_ctx, page):
+    """The resident rows lie in the io arena: a call that sizes it may overwrite them, so every resident result is forgotten
+    there, the orientation together with the scores"""
+    c = crnn_ctx
+    c.recognize_boxes(page[None], [BOXES[:3]], return_scores=True, orientation=ANY)
+    turns, quads, pairs = c.recognition_orientation()
+    assert turns.shape == (3,) and quads.shape == (3, 4, 2) and pairs.shape == (3, 2)
+    assert c.recognition_scores()[0].shape == (3,)
+    maps = np.zeros((1, 1, 1, 2), np.float32)
+    assert c.heat_mse(maps, maps).tolist() == [0.0]  # unrelated, and sizes the io arena
+    with pytest.raises(ValueError, match="no orientation is resident"):
+        c.recognition_orientation()
+    with pytest.raises(ValueError, match="no recognition scores are resident"):
+        c.recognition_scores()
 
 
 def test_recognizer_returns_the_winners(crnn_ctx, crnn_weights):
