@@ -139,6 +139,40 @@ def test_crnn_forward(abi, dctx, crops):
     assert np.array_equal(_host(d_lab2), labels)
 
 
+def test_crnn_beam(abi, dctx, crops):
+    bw, k = 4, 2
+    labels, log_prob = dctx.crnn_beam(crops, bw, k)
+    assert labels.shape == (N_CROPS, k, dctx.crnn_label_width()) and (labels[:, 0] >= 0).any()
+    d_lab, d_logp = _dev(np.full_like(labels, -1)), _dev(np.full_like(log_prob, -np.inf))
+    assert abi("kocr_crnn_beam", _dev(crops), N_CROPS, bw, k, d_lab, d_logp, 1) == 0
+    assert np.array_equal(_host(d_lab), labels)
+    assert np.array_equal(_host(d_logp).view(np.uint32), log_prob.view(np.uint32))
+
+
+def test_crnn_lexicon(abi, dctx, crops):
+    from tests import batch_edge_cases as bc
+
+    k = 3
+    words, lengths = bc.lexicon(dctx.crnn_classes())
+    try:
+        dctx.set_lexicon(words, lengths)
+        index, log_prob, values = dctx.crnn_lexicon(crops, k, return_values=True)
+        assert values.shape == (N_CROPS, len(words)) and index.min() >= 0
+        d_idx, d_logp = _dev(np.full_like(index, -1)), _dev(np.full_like(log_prob, -np.inf))
+        d_val = _dev(np.full_like(values, -np.inf))
+        assert abi("kocr_crnn_lexicon", _dev(crops), N_CROPS, k, d_idx, d_logp, d_val, 1) == 0
+        assert np.array_equal(_host(d_idx), index)
+        assert np.array_equal(_host(d_logp).view(np.uint32), log_prob.view(np.uint32))
+        assert np.array_equal(_host(d_val).view(np.uint32), values.view(np.uint32))
+        # without the values
+        d_idx2, d_logp2 = _dev(np.full_like(index, -1)), _dev(np.full_like(log_prob, -np.inf))
+        assert abi("kocr_crnn_lexicon", _dev(crops), N_CROPS, k, d_idx2, d_logp2, None, 1) == 0
+        assert np.array_equal(_host(d_idx2), index)
+        assert np.array_equal(_host(d_logp2).view(np.uint32), log_prob.view(np.uint32))
+    finally:
+        dctx.set_lexicon(None)
+
+
 def test_ctc_batch_cost(abi, dctx):
     m, t, c = 9, 20, 11
     y = np.random.default_rng(5).random((m, t, c), dtype=np.float32)
