@@ -399,6 +399,52 @@ int kocr_pipeline_results(kocr_ctx* ctx, float* boxes, int cap, int32_t* labels,
 int kocr_pipeline_device_results(kocr_ctx* ctx, const float** d_boxes, const int32_t** d_counts, const int32_t** d_labels,
                                  int32_t* N, int32_t* cap, int32_t* M);
 
+/* ---- tiled pages: a page larger than the detector takes in one image, read in overlapping tiles (DESIGN.md section 4,
+ * "Tiled pages"; statement: tests/tiling_statement.py) ------------------------------------------------------------------------
+ * The detector addresses one image with 32-bit byte offsets, which ends below one A4 page at 300 dpi.  It is fully
+ * convolutional, so a page is read as tiles with a halo: the resized page lies in the top-left corner of a canvas padded with
+ * 255 (tools.pad), tile_gather copies the overlapping tiles into one batch, the detector runs on that batch, and heat_stitch
+ * copies every pixel of the page's heat-map, bit for bit, from the one tile whose core contains it (no blending).  Everything
+ * behind the heat-map runs unchanged on the stitched map.
+ *
+ * The plan, with tile T and overlap O in detector-input pixels: T a multiple of 32, T >= 64; O a multiple of 16, O >= 0; the
+ * stride S = T - 2 O >= 32.  Per axis of length d >= 1: n = 1 tiles if d <= T, else ceil((d - T) / S) + 1; tile k starts at
+ * k S; the canvas is (n - 1) S + T long; the core of tile k is [k S + (O if k > 0 else 0), k S + T - (O if k < n - 1 else 0)).
+ * The cores partition the canvas; a tile's 2-D core is the product of its axis cores; tiles are numbered row-major.  Every
+ * origin and core bound is a multiple of 16, so a tile's pooling grid is the page's.  kocr_tile_plan writes
+ * out[6] = {ny, nx, Hc, Wc, S, nT = ny nx} for an H x W page; KOCR_EINVAL names a refused argument.
+ *
+ * A halo of O pixels does not reproduce a whole-page pass: pixels nearer than the detector's receptive field to a tile edge
+ * see the tile's zero padding instead of the page (DESIGN.md states how much).
+ *
+ * kocr_gather_tiles / kocr_stitch_heat: the two copies alone (test seams; host or, with on_device, 16-byte aligned device
+ * pointers).  canvas: N x Hc x Wc x 3 uint8, Hc x Wc a canvas of (tile, overlap) -- KOCR_EINVAL otherwise; tiles: N x nT x T x T
+ * x 3 uint8; tile_heat: N x nT x T/2 x T/2 x 2 float32; heat: N x Hc/2 x Wc/2 x 2 float32.
+ * kocr_craft_forward_tiled: gather -> kocr_craft_forward's forward over the N nT tiles, micro_batch TILES at a time -> stitch.
+ * kocr_detect_tiled: kocr_detect with that in place of the forward; the canvases are uint8.
+ * kocr_pipeline_tiled: kocr_pipeline's arguments with (tile, overlap) in place of (Hmax, Wmax): the batch is padded to the
+ * canvas of the largest dhs x the largest dws, the detector runs tiled, and the REST OF THE CALL IS kocr_pipeline's own code.
+ * So every context switch (scores, beam, lexicon match, orientation, character boxes, min-area-rect rule) acts on it, and every
+ * getter of resident results (kocr_pipeline_results, kocr_detection_scores, kocr_recognition_scores / _beams / _lexicon /
+ * _orientation, kocr_detection_char_boxes, kocr_pipeline_device_results) answers after it, exactly as after kocr_pipeline;
+ * boxes are in canvas = detector-input pixels.
+ * Limit of the last three: a canvas side of 8192 (the post-processing takes heat-map sides up to 4096, the first bound a
+ * growing canvas meets); beyond it KOCR_EINVAL names the limit. */
+int kocr_tile_plan(kocr_ctx* ctx, int H, int W, int tile, int overlap, int32_t* out);
+int kocr_gather_tiles(kocr_ctx* ctx, const uint8_t* canvas, int N, int Hc, int Wc, int tile, int overlap, uint8_t* tiles,
+                      int on_device);
+int kocr_stitch_heat(kocr_ctx* ctx, const float* tile_heat, int N, int Hc, int Wc, int tile, int overlap, float* heat,
+                     int on_device);
+int kocr_craft_forward_tiled(kocr_ctx* ctx, const uint8_t* canvas, int N, int Hc, int Wc, int tile, int overlap, float* heat,
+                             int micro_batch, int on_device);
+int kocr_detect_tiled(kocr_ctx* ctx, const uint8_t* canvas, int N, int Hc, int Wc, int tile, int overlap,
+                      float detection_threshold, float text_threshold, float link_threshold, int size_threshold,
+                      int micro_batch, float* boxes, int32_t* counts, int cap, int on_device);
+int kocr_pipeline_tiled(kocr_ctx* ctx, int N, const uint8_t* const* imgs, const int32_t* hs, const int32_t* ws,
+                        const int32_t* dhs, const int32_t* dws, int tile, int overlap, float detection_threshold,
+                        float text_threshold, float link_threshold, int size_threshold, int micro_batch, float* boxes,
+                        int32_t* counts, int cap, int32_t* labels, int max_crops, int32_t* n_crops, int on_device);
+
 /* ---- single fused-epilogue convolution (unit-test seam for the MFMA kernel) ---------- */
 /* out = post_a * act(pre_a * conv(in, w) + pre_b) + post_b, NHWC, stride 1, 'same'
  * padding; w is HWIO (the Keras kernel layout, detection.py:461).  pre_a/pre_b/post_a/

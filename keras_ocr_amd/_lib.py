@@ -123,6 +123,13 @@ def load_library():
         "kocr_pipeline": (ci, [vp, ci, ctypes.POINTER(vp), _c_int_p, _c_int_p, _c_int_p, _c_int_p, ci, ci,
                                ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, ci, vp, vp, ci, vp, ci, vp, ci]),
         "kocr_pipeline_device_results": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "kocr_tile_plan": (ci, [vp, ci, ci, ci, ci, vp]),
+        "kocr_gather_tiles": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci]),
+        "kocr_stitch_heat": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci]),
+        "kocr_craft_forward_tiled": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, ci]),
+        "kocr_detect_tiled": (ci, [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, ci, vp, vp, ci, ci]),
+        "kocr_pipeline_tiled": (ci, [vp, ci, ctypes.POINTER(vp), _c_int_p, _c_int_p, _c_int_p, _c_int_p, ci, ci,
+                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, ci, vp, vp, ci, vp, ci, vp, ci]),
         "kocr_pipeline_results": (ci, [vp, vp, ci, vp, ci]),
         "kocr_resize_pad_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]),
         "kocr_warp_crops_f32": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
@@ -962,7 +969,8 @@ class Context:
     # -- fused Pipeline.recognize ----------------------------------------------------------------
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
-                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None, orientation=None):
+                 min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None, orientation=None,
+                 tiled=False):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns ``Results.render_context()``: (boxes
         list[(n_i,4,2) f32, detector-input px], labels (M,48) int32), then one element per extra asked for, as the fields of
         ``results.Results`` describe them -- ``return_scores``: its ``scores``; ``beam=(beam_width, top_paths)``: its ``beam``,
@@ -971,14 +979,14 @@ class Context:
         ``orientation=(mode, tall_ratio)``, mode "flip" / "any": every box is read in two orientations (include/kocr.h:
         "orientation"); labels and scores are those of each word's better reading, the boxes stay getBoxes' bits, and its
         ``orientation`` comes last (quads in detector-input px).  Not together with ``beam``, ``lexicon_top`` or ``char_boxes``
-        (ValueError)."""
+        (ValueError).  ``tiled`` (``pipeline_tiled``): ``hmax`` / ``wmax`` are the tile and the overlap of kocr_pipeline_tiled."""
         refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, char_boxes=None if char_rule(char_boxes) is None else True)
         orientation = None if orientation is None else orientation_args(*orientation)
         with self._char_boxes_scope(char_boxes):
             with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
                     self._lexicon_scope(lexicon_top), self._orientation_scope(orientation):
                 out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                                     size_threshold, micro_batch, on_device, cap, max_crops, return_scores)
+                                     size_threshold, micro_batch, on_device, cap, max_crops, return_scores, tiled)
                 if orientation is not None:
                     out.orientation = self.recognition_orientation() if len(ptrs) else empty_orientation()
                 if lexicon_top is not None:
@@ -992,7 +1000,7 @@ class Context:
         return out.render_context()
 
     def _pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                  size_threshold, micro_batch, on_device, cap, max_crops, return_scores=False):
+                  size_threshold, micro_batch, on_device, cap, max_crops, return_scores=False, tiled=False):
         n = len(ptrs)
         keep = [np.ascontiguousarray(p, dtype=np.uint8) if not isinstance(p, (int, np.integer)) else p for p in ptrs]
         c_ptrs = (ctypes.c_void_p * n)(*[int(p) if isinstance(p, (int, np.integer)) else p.ctypes.data for p in keep])
@@ -1004,7 +1012,7 @@ class Context:
         counts = np.zeros(n, dtype=np.int32)
         labels = np.full((max_crops, lw), -1, dtype=np.int32)
         n_crops = np.zeros(1, dtype=np.int32)
-        rc = self._lib.kocr_pipeline(
+        rc = (self._lib.kocr_pipeline_tiled if tiled else self._lib.kocr_pipeline)(
             self._h, n, c_ptrs, *[a.ctypes.data_as(_c_int_p) for a in arr], int(hmax), int(wmax),
             float(detection_threshold), float(text_threshold), float(link_threshold), int(size_threshold),
             int(micro_batch), _ptr(boxes), _ptr(counts), cap, _ptr(labels), max_crops, _ptr(n_crops),
@@ -1022,6 +1030,79 @@ class Context:
         if return_scores:
             out.scores = (self.detection_scores(counts, cap),) + self.recognition_scores() if n else empty_scores(lw, [])
         return out
+
+    # -- tiled pages (include/kocr.h: "tiled pages") ------------------------------------------------
+    def pipeline_tiled(self, ptrs, hs, ws, dhs, dws, tile, overlap, **kwargs):
+        """``pipeline`` with the detector run in overlapping tiles (kocr_pipeline_tiled): ``tile`` / ``overlap`` as
+        ``tools.tile_plan`` in place of ``hmax`` / ``wmax`` -- the batch is padded to the plan's canvas of the largest
+        ``dhs`` x ``dws``.  Every keyword and every element of the result as ``pipeline``; boxes in canvas = detector-input
+        pixels.  ValueError for a refused tile or overlap."""
+        from . import tools  # pylint: disable=import-outside-toplevel,cyclic-import
+        if len(ptrs):
+            tools.tile_plan(max(int(v) for v in dhs), max(int(v) for v in dws), tile, overlap)
+        return self.pipeline(ptrs, hs, ws, dhs, dws, int(tile), int(overlap), tiled=True, **kwargs)
+
+    def tile_plan(self, height, width, tile, overlap):
+        """kocr_tile_plan: ``(ny, nx, Hc, Wc, S, nT)`` as the library computes them (``tools.tile_plan`` is the same plan
+        without a library call); ValueError for refused parameters."""
+        out = np.zeros(6, dtype=np.int32)
+        self._check(self._lib.kocr_tile_plan(self._h, int(height), int(width), int(tile), int(overlap), _ptr(out)), value_error=True)
+        return tuple(int(v) for v in out)
+
+    def _canvases(self, canvas, tile, overlap):
+        """(N,Hc,Wc,3) uint8 canvases of the plan -> (array, n, hc, wc, tiles per canvas); ValueError otherwise"""
+        from . import tools  # pylint: disable=import-outside-toplevel,cyclic-import
+        x = np.ascontiguousarray(canvas, dtype=np.uint8)
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError("canvas must have shape (N,Hc,Wc,3)")
+        n, hc, wc, _ = x.shape
+        plan = tools.tile_plan(hc, wc, tile, overlap)
+        if plan.canvas != (hc, wc):
+            raise ValueError(f"{hc} x {wc} is not a canvas of tile {tile} and overlap {overlap}: tile_plan gives {plan.canvas}")
+        return x, n, hc, wc, plan.counts[0] * plan.counts[1]
+
+    def gather_tiles(self, canvas, tile, overlap):
+        """canvas: (N,Hc,Wc,3) uint8, Hc x Wc a canvas of ``tools.tile_plan``.  Returns the tiles (N * nT, T, T, 3) uint8,
+        canvas-major, row-major within a canvas: a pure copy (tile_gather)."""
+        x, n, hc, wc, n_tiles = self._canvases(canvas, tile, overlap)
+        out = np.empty((n * n_tiles, int(tile), int(tile), 3), dtype=np.uint8)
+        self._check(self._lib.kocr_gather_tiles(self._h, _ptr(x), n, hc, wc, int(tile), int(overlap), _ptr(out), 0))
+        return out
+
+    def stitch_heat(self, tile_heat, canvas_hw, tile, overlap):
+        """tile_heat: (N * nT, T/2, T/2, 2) float32 heat-maps of the tiles of N canvases of ``canvas_hw`` = (Hc, Wc).  Returns
+        (N, Hc/2, Wc/2, 2) float32: every pixel the bits of the one tile whose core contains it (heat_stitch)."""
+        from . import tools  # pylint: disable=import-outside-toplevel,cyclic-import
+        hc, wc = int(canvas_hw[0]), int(canvas_hw[1])
+        plan = tools.tile_plan(hc, wc, tile, overlap)
+        if plan.canvas != (hc, wc):
+            raise ValueError(f"{hc} x {wc} is not a canvas of tile {tile} and overlap {overlap}: tile_plan gives {plan.canvas}")
+        n_tiles, t2 = plan.counts[0] * plan.counts[1], int(tile) // 2
+        y = np.ascontiguousarray(tile_heat, dtype=np.float32)
+        if y.ndim != 4 or y.shape[1:] != (t2, t2, 2) or y.shape[0] % n_tiles:
+            raise ValueError(f"tile_heat must have shape (N * {n_tiles}, {t2}, {t2}, 2)")
+        n = y.shape[0] // n_tiles
+        out = np.empty((n, hc // 2, wc // 2, 2), dtype=np.float32)
+        self._check(self._lib.kocr_stitch_heat(self._h, _ptr(y), n, hc, wc, int(tile), int(overlap), _ptr(out), 0))
+        return out
+
+    def craft_forward_tiled(self, canvas, tile, overlap, micro_batch=0):
+        """canvas: (N,Hc,Wc,3) uint8 as ``gather_tiles``.  Returns the stitched heat-maps (N, Hc/2, Wc/2, 2) float32 of a
+        detector pass over the tiles, ``micro_batch`` tiles at a time (kocr_craft_forward_tiled)."""
+        x, n, hc, wc, _ = self._canvases(canvas, tile, overlap)
+        out = np.empty((n, hc // 2, wc // 2, 2), dtype=np.float32)
+        self._check(self._lib.kocr_craft_forward_tiled(self._h, _ptr(x), n, hc, wc, int(tile), int(overlap), _ptr(out),
+                                                       int(micro_batch), 0))
+        return out
+
+    def _detect_tiled(self, canvas, tile, overlap, detection_threshold, text_threshold, link_threshold, size_threshold, micro_batch,
+                      cap, min_area_rect=None, return_scores=False, char_boxes=None):
+        """``_detect`` on canvases read in tiles (kocr_detect_tiled)"""
+        x, n, hc, wc, _ = self._canvases(canvas, tile, overlap)
+        return self._boxes_grow_cap(n, cap, lambda boxes, counts, cap: self._lib.kocr_detect_tiled(
+            self._h, _ptr(x), n, hc, wc, int(tile), int(overlap), float(detection_threshold), float(text_threshold),
+            float(link_threshold), int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0),
+            min_area_rect, return_scores, char_boxes)
 
     def pipeline_device_results(self):
         """Device pointers of the last `pipeline()` call's results (include/kocr.h: kocr_pipeline_device_results):

@@ -711,6 +711,17 @@ int launch_chars_pack(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off,
 int chars_resident(kocr_ctx* ctx, const char* fn, const float* d_heat, int N, int h, int w, const float* d_boxes, int cap,
                    const int32_t* h_counts);
 
+// tiles.hip: a page read in overlapping detector tiles ("Tiled pages"; kocr_tile_plan in include/kocr.h
+// states the plan).  T = tile, O = overlap, S = T - 2 O the stride, ny x nx tiles (nT of them, row-major) over a canvas of
+// Hc x Wc detector-input pixels.
+struct TilePlan {
+  int T, O, S, ny, nx, Hc, Wc, nT;
+};
+// The plan of an H x W page, or KOCR_EINVAL naming the refused argument (`fn`: the entry point)
+int tile_plan(kocr_ctx* ctx, const char* fn, int H, int W, int tile, int overlap, TilePlan& p);
+int launch_tile_gather(kocr_ctx* ctx, const uint8_t* d_canvas, int N, const TilePlan& p, uint8_t* d_tiles);
+int launch_heat_stitch(kocr_ctx* ctx, const float* d_tile_heat, int N, const TilePlan& p, float* d_heat);
+
 // imgproc.hip
 int launch_resize_pad_f32(kocr_ctx* ctx, const float* d_src, int n, int sh, int sw, int C, float* d_dst, int dh, int dw, int Hmax,
                           int Wmax, float cval, Arena& tab_arena);

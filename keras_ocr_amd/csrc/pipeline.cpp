@@ -3,6 +3,7 @@
 //   ->  Recognizer.recognize_from_boxes (:63-65; recognition.py:491-537).
 // Everything stays resident in HBM between the stages; the host sees only the per-image box
 // counts (a few bytes, needed to size the crop batch), the boxes and the decoded label rows.
+// kocr_pipeline_tiled (at the end of the file) is the same path with the detector run on overlapping tiles of the page.
 #include "abi.h"
 
 extern "C" int kocr_resize_pad(kocr_ctx* ctx, const uint8_t* src, int n, int sh, int sw, int dh, int dw, int Hmax,
@@ -190,23 +191,81 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
   return KOCR_OK;
 }
 
+namespace {
+// What kocr_pipeline and kocr_pipeline_tiled share.  The caller's side of both: the images with their sizes before and after
+// tools.resize_image, the thresholds of getBoxes, the buffers the results go to.
+struct PipelineCall {
+  const char* fn;
+  int N;
+  const uint8_t* const* imgs;
+  const int32_t *hs, *ws, *dhs, *dws;
+  float detection_threshold, text_threshold, link_threshold;
+  int size_threshold, micro_batch;
+  float* boxes;
+  int32_t* counts;
+  int cap;
+  int32_t* labels;
+  int max_crops;
+  int32_t* n_crops;
+  bool on_device;
+};
+
+// The checks ahead of any work; *go = false: the call is over (nothing to do, rc KOCR_OK)
+int pipeline_begin(kocr_ctx* ctx, const PipelineCall& c, bool sizes_ok, bool* go) {
+  const std::string f(c.fn);
+  *go = false;
+  if (c.n_crops) *c.n_crops = 0;
+  if (c.N < 0 || (c.N > 0 && (!c.imgs || !c.hs || !c.ws || !c.dhs || !c.dws || !c.boxes || !c.counts)))
+    KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  ctx->invalidate_results();  // also for the returns before the first arena is sized: N == 0 replaces the results by none
+  if (c.N == 0) return KOCR_OK;
+  if (!ctx->craft) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_craft first");
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+  if (!sizes_ok || c.cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": bad sizes");
+  if (ctx->orient_mode != KOCR_ORIENT_OFF)
+    if (const char* why = orient_refusal(ctx, true)) KOCR_FAIL(ctx, KOCR_EINVAL, f + why);
+  *go = true;
+  return KOCR_OK;
+}
+
+// resize + pad into d_bat [N][Hmax][Wmax][3], runs of identically-shaped contiguous images in one launch
+int pipeline_resize(kocr_ctx* ctx, const PipelineCall& c, int Hmax, int Wmax, uint8_t* d_bat) {
+  Staging io{ctx, ctx->io, c.fn, c.on_device};
+  const uint8_t* const* imgs = c.imgs;
+  const int32_t *hs = c.hs, *ws = c.ws, *dhs = c.dhs, *dws = c.dws;
+  int i = 0;
+  while (i < c.N) {
+    int j = i + 1;
+    while (j < c.N && hs[j] == hs[i] && ws[j] == ws[i] && dhs[j] == dhs[i] && dws[j] == dws[i] &&
+           imgs[j] == imgs[j - 1] + (size_t)hs[i] * ws[i] * 3)
+      ++j;
+    const int run = j - i;
+    const size_t sb = (size_t)run * hs[i] * ws[i] * 3;
+    const size_t tb = (size_t)(4 * (Wmax + Hmax) + 64) * sizeof(int);
+    KOCR_TRY(io.reserve(tb, {sb}));
+    const uint8_t* d_src;
+    KOCR_TRY(io.in(imgs[i], sb, d_src));
+    KOCR_TRY(launch_resize_pad(ctx, d_src, run, hs[i], ws[i], d_bat + (size_t)i * Hmax * Wmax * 3, dhs[i], dws[i],
+                               Hmax, Wmax, 255, ctx->io));
+    i = j;
+  }
+  return KOCR_OK;
+}
+
+int pipeline_tail(kocr_ctx* ctx, const PipelineCall& c, const uint8_t* d_bat, int Hmax, int Wmax, const float* d_heat, float* d_boxes);
+}  // namespace
+
 extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, const int32_t* hs, const int32_t* ws,
                              const int32_t* dhs, const int32_t* dws, int Hmax, int Wmax, float detection_threshold,
                              float text_threshold, float link_threshold, int size_threshold, int micro_batch,
                              float* boxes, int32_t* counts, int cap, int32_t* labels, int max_crops,
                              int32_t* n_crops, int on_device) {
   if (!ctx) return KOCR_EINVAL;
-  if (n_crops) *n_crops = 0;
-  if (N < 0 || (N > 0 && (!imgs || !hs || !ws || !dhs || !dws || !boxes || !counts)))
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline: null buffer");
-  ctx->invalidate_results();  // also for the returns before the first arena is sized: N == 0 replaces the results by none
-  if (N == 0) return KOCR_OK;
-  if (!ctx->craft) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_pipeline: call kocr_load_craft first");
-  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_pipeline: call kocr_load_crnn first");
-  if (Hmax < 16 || Wmax < 16 || cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline: bad sizes");
-  const bool oriented = ctx->orient_mode != KOCR_ORIENT_OFF;
-  if (oriented)
-    if (const char* why = orient_refusal(ctx, true)) KOCR_FAIL(ctx, KOCR_EINVAL, std::string("kocr_pipeline") + why);
+  const PipelineCall c{"kocr_pipeline", N, imgs, hs, ws, dhs, dws, detection_threshold, text_threshold, link_threshold, size_threshold,
+                       micro_batch, boxes, counts, cap, labels, max_crops, n_crops, on_device != 0};
+  bool go;
+  KOCR_TRY(pipeline_begin(ctx, c, Hmax >= 16 && Wmax >= 16, &go));
+  if (!go) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int h2 = Hmax / 2, w2 = Wmax / 2;
   const size_t bat_b = (size_t)N * Hmax * Wmax * 3;
@@ -220,29 +279,28 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   KOCR_TRY(pl.scratch(bat_b, d_bat));
   KOCR_TRY(pl.scratch(heat_b, d_heat));
   KOCR_TRY(pl.scratch(box_b, d_boxes));
-  // ---- resize + pad, runs of identically-shaped contiguous images in one launch ----
-  Staging io{ctx, ctx->io, "kocr_pipeline", on_device != 0};
-  int i = 0;
-  while (i < N) {
-    int j = i + 1;
-    while (j < N && hs[j] == hs[i] && ws[j] == ws[i] && dhs[j] == dhs[i] && dws[j] == dws[i] &&
-           imgs[j] == imgs[j - 1] + (size_t)hs[i] * ws[i] * 3)
-      ++j;
-    const int run = j - i;
-    const size_t sb = (size_t)run * hs[i] * ws[i] * 3;
-    const size_t tb = (size_t)(4 * (Wmax + Hmax) + 64) * sizeof(int);
-    KOCR_TRY(io.reserve(tb, {sb}));
-    const uint8_t* d_src;
-    KOCR_TRY(io.in(imgs[i], sb, d_src));
-    KOCR_TRY(launch_resize_pad(ctx, d_src, run, hs[i], ws[i], d_bat + (size_t)i * Hmax * Wmax * 3, dhs[i], dws[i],
-                               Hmax, Wmax, 255, ctx->io));
-    i = j;
-  }
+  KOCR_TRY(pipeline_resize(ctx, c, Hmax, Wmax, d_bat));
   // ---- detector forward (micro-batched) ----
   KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(craft_micro_batch(micro_batch, N, Hmax, Wmax), Hmax, Wmax)));
   KOCR_TRY(craft_batches(ctx, micro_batch, N, Hmax, Wmax, [&](int s, int nb) {
     return craft_forward(ctx, d_bat + (size_t)s * Hmax * Wmax * 3, KOCR_U8, nb, Hmax, Wmax, d_heat + (size_t)s * h2 * w2 * 2);
   }));
+  return pipeline_tail(ctx, c, d_bat, Hmax, Wmax, d_heat, d_boxes);
+}
+
+namespace {
+// The end that kocr_pipeline and kocr_pipeline_tiled share: everything behind the heat-maps d_heat [N][Hmax / 2][Wmax / 2][2]
+// of the batch d_bat [N][Hmax][Wmax][3]; d_boxes [N][cap][4][2] lies in the pl arena beside them.
+int pipeline_tail(kocr_ctx* ctx, const PipelineCall& c, const uint8_t* d_bat, int Hmax, int Wmax, const float* d_heat, float* d_boxes) {
+  const std::string fn(c.fn);
+  const int N = c.N, cap = c.cap, max_crops = c.max_crops, h2 = Hmax / 2, w2 = Wmax / 2;
+  const float detection_threshold = c.detection_threshold, text_threshold = c.text_threshold, link_threshold = c.link_threshold;
+  const int size_threshold = c.size_threshold;
+  float* const boxes = c.boxes;
+  int32_t *const counts = c.counts, *const labels = c.labels, *const n_crops = c.n_crops;
+  const size_t box_b = (size_t)N * cap * 8 * sizeof(float);
+  const bool oriented = ctx->orient_mode != KOCR_ORIENT_OFF;
+  Staging io{ctx, ctx->io, c.fn, c.on_device};
   // ---- boxes: the host learns only the per-image counts here (needed to size the crop batch); the boxes themselves
   // go to the caller asynchronously while the device already derives the crop homographies from its own copy ----
   // CAPACITY WITHOUT RECOMPUTATION (round 6; the reference has no cap, detection.py:230-286): `cap` and `max_crops` size the
@@ -261,14 +319,14 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     for (int k = 0; k < N; ++k) need = std::max(need, (int)counts[k]);
     if (need <= d_cap) return rc_pp;  // the other capacity error (dilation canvases beyond 2^31 pixels): not a matter of cap
     d_cap = need;
-    Staging bx{ctx, ctx->bx, "kocr_pipeline"};
+    Staging bx{ctx, ctx->bx, c.fn};
     KOCR_TRY(bx.reserve(0, {}, {(size_t)N * d_cap * 8 * sizeof(float)}));
     KOCR_TRY(bx.scratch((size_t)N * d_cap * 8 * sizeof(float), d_boxes));
     rc_pp = postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold, size_threshold,
                                d_boxes, d_cap, counts, nullptr, &dv);
   }
   KOCR_TRY(rc_pp);
-  KOCR_TRY(chars_resident(ctx, "kocr_pipeline", d_heat, N, h2, w2, d_boxes, d_cap, counts));
+  KOCR_TRY(chars_resident(ctx, c.fn, d_heat, N, h2, w2, d_boxes, d_cap, counts));
   long M = 0;
   for (int k = 0; k < N; ++k) M += counts[k];
   if (n_crops) *n_crops = (int32_t)M;
@@ -279,8 +337,8 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     KOCR_HIP(ctx, hipMemcpyAsync(host_flags, dv.d_totals, 16, hipMemcpyDeviceToHost, ctx->stream));
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (host_flags[2] > 0)
-      KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR, "kocr_pipeline: empty contour list (IndexError at detection.py:272)");
-    return warp_status_error(ctx, "kocr_pipeline", host_flags[4], "tools.py:95");
+      KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR, fn + ": empty contour list (IndexError at detection.py:272)");
+    return warp_status_error(ctx, c.fn, host_flags[4], "tools.py:95");
   };
   if (M == 0) {
     KOCR_TRY(finish());
@@ -291,7 +349,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   }
   if (!labels && d_cap == cap) {
     KOCR_TRY(finish());  // an empty contour list (the reference's IndexError) takes precedence over the capacity error
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_pipeline: more crops than max_crops");
+    KOCR_FAIL(ctx, KOCR_ECAPACITY, fn + ": more crops than max_crops");
   }
   // ---- the end of both routes: the label rows `d_lab` of `rec` (an oriented run's: of its winners) to the caller, the
   // status words to the host, what stays resident ----
@@ -306,7 +364,7 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
     ctx->keep_det_scores(dv.d_scores, N, d_cap);
     rec.keep(won);
     if (!host_fits)
-      KOCR_FAIL(ctx, KOCR_ECAPACITY, "kocr_pipeline: an image has more boxes than cap, or there are more crops than max_crops; the results are "
+      KOCR_FAIL(ctx, KOCR_ECAPACITY, fn + ": an image has more boxes than cap, or there are more crops than max_crops; the results are "
                                      "resident -- fetch them with kocr_pipeline_results into buffers sized from counts / n_crops");
     return KOCR_OK;
   };
@@ -339,7 +397,6 @@ extern "C" int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, c
   return finish_crops(rec, nullptr);
 }
 
-namespace {
 // The getters of resident results (include/kocr.h) share one sequence: produced with the switch off -> KOCR_EINVAL; nothing
 // resident -> KOCR_EINVAL; the sizes reported; buffers too small -> KOCR_ECAPACITY; nothing to copy -> KOCR_OK; the copies on
 // the ctx stream; synchronise.  What is copied: one pitched block (the detector side: `rows` device rows of dev_pitch bytes
@@ -587,4 +644,213 @@ extern "C" int kocr_orient_select(kocr_ctx* ctx, int M, int L, const int32_t* la
   KOCR_TRY(st.back(out_quads, o_quad, 8 * m * f));
   KOCR_TRY(st.back(out_log_words, o_pair, 2 * m * f));
   return st.finish();
+}
+
+// ---- tiled pages (include/kocr.h, "tiled pages"; DESIGN.md section 4, "Tiled pages") ----
+int tile_plan(kocr_ctx* ctx, const char* fn, int H, int W, int tile, int overlap, TilePlan& p) {
+  const std::string f(fn);
+  if (H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": page sides must be in [1, 2^20]");
+  if (tile < 64 || tile % 32 != 0 || tile > (1 << 15)) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": tile must be a multiple of 32 in [64, 32768]");
+  if (overlap < 0 || overlap % 16 != 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": overlap must be a non-negative multiple of 16");
+  if (tile - 2 * overlap < 32) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": the stride tile - 2 overlap must be at least 32");
+  p.T = tile;
+  p.O = overlap;
+  p.S = tile - 2 * overlap;
+  auto count = [&](int d) { return d <= p.T ? 1 : (d - p.T + p.S - 1) / p.S + 1; };
+  p.ny = count(H);
+  p.nx = count(W);
+  p.Hc = (p.ny - 1) * p.S + p.T;
+  p.Wc = (p.nx - 1) * p.S + p.T;
+  p.nT = p.ny * p.nx;
+  return KOCR_OK;
+}
+
+namespace {
+// The plan of N canvases that already have the plan's size, or KOCR_EINVAL
+int canvas_plan(kocr_ctx* ctx, const char* fn, int N, int Hc, int Wc, int tile, int overlap, TilePlan& p) {
+  KOCR_TRY(tile_plan(ctx, fn, Hc, Wc, tile, overlap, p));
+  if (p.Hc != Hc || p.Wc != Wc)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": " + std::to_string(Hc) + " x " + std::to_string(Wc) + " is not a canvas of this tile and overlap (kocr_tile_plan gives " +
+                                    std::to_string(p.Hc) + " x " + std::to_string(p.Wc) + ")");
+  if ((size_t)N * p.nT > 0x7fffffffu) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": too many tiles");
+  return KOCR_OK;
+}
+
+// The stitched heat-map goes to the post-processing, whose heat-map sides end at 4096 (postproc_get_boxes): the first limit a
+// growing canvas meets
+constexpr int TILED_MAX_CANVAS = 8192;
+int tiled_limit(kocr_ctx* ctx, const char* fn, const TilePlan& p) {
+  if (p.Hc > TILED_MAX_CANVAS || p.Wc > TILED_MAX_CANVAS)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": the canvas " + std::to_string(p.Hc) + " x " + std::to_string(p.Wc) +
+                                    " exceeds 8192 x 8192 detector-input pixels (the post-processing takes heat-maps of at most 4096 x 4096)");
+  return KOCR_OK;
+}
+
+size_t tiles_bytes(int N, const TilePlan& p) { return (size_t)N * p.nT * p.T * p.T * 3; }
+size_t tile_heat_bytes(int N, const TilePlan& p) { return (size_t)N * p.nT * (p.T / 2) * (p.T / 2) * 2 * sizeof(float); }
+size_t page_heat_bytes(int N, const TilePlan& p) { return (size_t)N * (p.Hc / 2) * (p.Wc / 2) * 2 * sizeof(float); }
+
+// gather -> detector forward over the N nT tiles (micro_batch of them at a time) -> stitch, all on buffers in HBM
+int forward_tiled(kocr_ctx* ctx, const uint8_t* d_canvas, int N, const TilePlan& p, int micro_batch, uint8_t* d_tiles, float* d_tile_heat,
+                  float* d_heat) {
+  const int NT = N * p.nT, T = p.T;
+  const size_t tile_px = (size_t)T * T, heat_px = (size_t)(T / 2) * (T / 2);
+  KOCR_TRY(launch_tile_gather(ctx, d_canvas, N, p, d_tiles));
+  KOCR_TRY(ctx->ws_reserve(craft_workspace_bytes(craft_micro_batch(micro_batch, NT, T, T), T, T)));
+  KOCR_TRY(craft_batches(ctx, micro_batch, NT, T, T, [&](int s, int nb) {
+    return craft_forward(ctx, d_tiles + s * tile_px * 3, KOCR_U8, nb, T, T, d_tile_heat + s * heat_px * 2);
+  }));
+  return launch_heat_stitch(ctx, d_tile_heat, N, p, d_heat);
+}
+}  // namespace
+
+extern "C" int kocr_tile_plan(kocr_ctx* ctx, int H, int W, int tile, int overlap, int32_t* out) {
+  if (!ctx || !out) return KOCR_EINVAL;
+  TilePlan p;
+  KOCR_TRY(tile_plan(ctx, "kocr_tile_plan", H, W, tile, overlap, p));
+  const int32_t v[6] = {p.ny, p.nx, p.Hc, p.Wc, p.S, p.nT};
+  std::memcpy(out, v, sizeof(v));
+  return KOCR_OK;
+}
+
+extern "C" int kocr_gather_tiles(kocr_ctx* ctx, const uint8_t* canvas, int N, int Hc, int Wc, int tile, int overlap, uint8_t* tiles,
+                                 int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (N < 0 || (N > 0 && (!canvas || !tiles))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_gather_tiles: null buffer");
+  if (N == 0) return KOCR_OK;
+  TilePlan p;
+  KOCR_TRY(canvas_plan(ctx, "kocr_gather_tiles", N, Hc, Wc, tile, overlap, p));
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t cb = (size_t)N * Hc * Wc * 3, tb = tiles_bytes(N, p);
+  Staging st{ctx, ctx->io, "kocr_gather_tiles", on_device != 0};
+  KOCR_TRY(st.reserve(0, {cb, tb}));
+  const uint8_t* d_canvas;
+  uint8_t* d_tiles;
+  KOCR_TRY(st.in(canvas, cb, d_canvas));
+  KOCR_TRY(st.out(tiles, tb, d_tiles));
+  KOCR_TRY(launch_tile_gather(ctx, d_canvas, N, p, d_tiles));
+  KOCR_TRY(st.back(tiles, d_tiles, tb));
+  return st.finish();
+}
+
+extern "C" int kocr_stitch_heat(kocr_ctx* ctx, const float* tile_heat, int N, int Hc, int Wc, int tile, int overlap, float* heat,
+                                int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  if (N < 0 || (N > 0 && (!tile_heat || !heat))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_stitch_heat: null buffer");
+  if (N == 0) return KOCR_OK;
+  TilePlan p;
+  KOCR_TRY(canvas_plan(ctx, "kocr_stitch_heat", N, Hc, Wc, tile, overlap, p));
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t tb = tile_heat_bytes(N, p), hb = page_heat_bytes(N, p);
+  Staging st{ctx, ctx->io, "kocr_stitch_heat", on_device != 0};
+  KOCR_TRY(st.reserve(0, {tb, hb}));
+  const float* d_tile_heat;
+  float* d_heat;
+  KOCR_TRY(st.in(tile_heat, tb, d_tile_heat));
+  KOCR_TRY(st.out(heat, hb, d_heat));
+  KOCR_TRY(launch_heat_stitch(ctx, d_tile_heat, N, p, d_heat));
+  KOCR_TRY(st.back(heat, d_heat, hb));
+  return st.finish();
+}
+
+extern "C" int kocr_craft_forward_tiled(kocr_ctx* ctx, const uint8_t* canvas, int N, int Hc, int Wc, int tile, int overlap, float* heat,
+                                        int micro_batch, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_craft_forward_tiled";
+  if (N < 0 || (N > 0 && (!canvas || !heat))) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": null buffer");
+  if (N == 0) return KOCR_OK;
+  TilePlan p;
+  KOCR_TRY(canvas_plan(ctx, fn, N, Hc, Wc, tile, overlap, p));
+  KOCR_TRY(tiled_limit(ctx, fn, p));
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t cb = (size_t)N * Hc * Wc * 3, hb = page_heat_bytes(N, p), tb = tiles_bytes(N, p), thb = tile_heat_bytes(N, p);
+  Staging st{ctx, ctx->pl, fn, on_device != 0};
+  KOCR_TRY(st.reserve(0, {cb, hb}, {tb, thb}));
+  const uint8_t* d_canvas;
+  uint8_t* d_tiles;
+  float *d_tile_heat, *d_heat;
+  KOCR_TRY(st.in(canvas, cb, d_canvas));
+  KOCR_TRY(st.out(heat, hb, d_heat));
+  KOCR_TRY(st.scratch(tb, d_tiles));
+  KOCR_TRY(st.scratch(thb, d_tile_heat));
+  KOCR_TRY(forward_tiled(ctx, d_canvas, N, p, micro_batch, d_tiles, d_tile_heat, d_heat));
+  KOCR_TRY(st.back(heat, d_heat, hb));
+  return st.finish();
+}
+
+// kocr_detect on canvases read in tiles: the getBoxes half runs on the stitched maps
+extern "C" int kocr_detect_tiled(kocr_ctx* ctx, const uint8_t* canvas, int N, int Hc, int Wc, int tile, int overlap,
+                                 float detection_threshold, float text_threshold, float link_threshold, int size_threshold,
+                                 int micro_batch, float* boxes, int32_t* counts, int cap, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_detect_tiled";
+  if (N < 0 || (N > 0 && (!canvas || !boxes || !counts))) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": null buffer");
+  if (N == 0) return KOCR_OK;
+  if (cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": cap must be positive");
+  TilePlan p;
+  KOCR_TRY(canvas_plan(ctx, fn, N, Hc, Wc, tile, overlap, p));
+  KOCR_TRY(tiled_limit(ctx, fn, p));
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int h2 = Hc / 2, w2 = Wc / 2;
+  const size_t cb = (size_t)N * Hc * Wc * 3, hb = page_heat_bytes(N, p), tb = tiles_bytes(N, p), thb = tile_heat_bytes(N, p);
+  const size_t box_b = (size_t)N * cap * 8 * sizeof(float);
+  Staging st{ctx, ctx->pl, fn, on_device != 0};
+  KOCR_TRY(st.reserve(0, {cb}, {hb, box_b, tb, thb}));
+  const uint8_t* d_canvas;
+  uint8_t* d_tiles;
+  float *d_tile_heat, *d_heat, *d_boxes;
+  KOCR_TRY(st.scratch(hb, d_heat));
+  KOCR_TRY(st.out(boxes, box_b, d_boxes));
+  KOCR_TRY(st.in(canvas, cb, d_canvas));
+  KOCR_TRY(st.scratch(tb, d_tiles));
+  KOCR_TRY(st.scratch(thb, d_tile_heat));
+  KOCR_TRY(forward_tiled(ctx, d_canvas, N, p, micro_batch, d_tiles, d_tile_heat, d_heat));
+  int n_empty = 0;
+  const float* d_scores = nullptr;
+  KOCR_TRY(postproc_get_boxes(ctx, d_heat, N, h2, w2, detection_threshold, text_threshold, link_threshold, size_threshold, d_boxes, cap,
+                              counts, &n_empty, nullptr, &d_scores));
+  KOCR_TRY(chars_resident(ctx, fn, d_heat, N, h2, w2, d_boxes, cap, counts));
+  KOCR_TRY(st.back(boxes, d_boxes, box_b));
+  KOCR_TRY(st.finish());
+  ctx->keep_det_scores(d_scores, N, cap);
+  if (n_empty > 0) KOCR_FAIL(ctx, KOCR_EEMPTYCONTOUR, std::string(fn) + ": empty contour list (IndexError at detection.py:272)");
+  return KOCR_OK;
+}
+
+// kocr_pipeline with the detector run in tiles: resize + pad to the canvas of the largest page -> gather -> forward -> stitch
+// -> the shared tail
+extern "C" int kocr_pipeline_tiled(kocr_ctx* ctx, int N, const uint8_t* const* imgs, const int32_t* hs, const int32_t* ws,
+                                   const int32_t* dhs, const int32_t* dws, int tile, int overlap, float detection_threshold,
+                                   float text_threshold, float link_threshold, int size_threshold, int micro_batch, float* boxes,
+                                   int32_t* counts, int cap, int32_t* labels, int max_crops, int32_t* n_crops, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  const PipelineCall c{"kocr_pipeline_tiled", N, imgs, hs, ws, dhs, dws, detection_threshold, text_threshold, link_threshold, size_threshold,
+                       micro_batch, boxes, counts, cap, labels, max_crops, n_crops, on_device != 0};
+  bool go;
+  KOCR_TRY(pipeline_begin(ctx, c, true, &go));
+  if (!go) return KOCR_OK;
+  int dh = 0, dw = 0;
+  for (int i = 0; i < N; ++i) {
+    dh = std::max(dh, (int)dhs[i]);
+    dw = std::max(dw, (int)dws[i]);
+  }
+  TilePlan p;
+  KOCR_TRY(tile_plan(ctx, c.fn, dh, dw, tile, overlap, p));
+  if ((size_t)N * p.nT > 0x7fffffffu) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline_tiled: too many tiles");
+  KOCR_TRY(tiled_limit(ctx, c.fn, p));
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bat_b = (size_t)N * p.Hc * p.Wc * 3, heat_b = page_heat_bytes(N, p), box_b = (size_t)N * cap * 8 * sizeof(float);
+  const size_t tb = tiles_bytes(N, p), thb = tile_heat_bytes(N, p);
+  Staging pl{ctx, ctx->pl, c.fn};
+  KOCR_TRY(pl.reserve(0, {}, {bat_b, heat_b, box_b, tb, thb}));
+  uint8_t *d_bat, *d_tiles;
+  float *d_heat, *d_boxes, *d_tile_heat;
+  KOCR_TRY(pl.scratch(bat_b, d_bat));
+  KOCR_TRY(pl.scratch(heat_b, d_heat));
+  KOCR_TRY(pl.scratch(box_b, d_boxes));
+  KOCR_TRY(pl.scratch(tb, d_tiles));
+  KOCR_TRY(pl.scratch(thb, d_tile_heat));
+  KOCR_TRY(pipeline_resize(ctx, c, p.Hc, p.Wc, d_bat));
+  KOCR_TRY(forward_tiled(ctx, d_bat, N, p, micro_batch, d_tiles, d_tile_heat, d_heat));
+  return pipeline_tail(ctx, c, d_bat, p.Hc, p.Wc, d_heat, d_boxes);
 }

@@ -218,3 +218,25 @@ class Detector:
         if want_chars:
             out.characters = _layout.characters_of(out.characters)
         return out.render_detection()
+
+    def detect_tiled(self, images, tile=1024, overlap=128, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4,
+                     size_threshold=10, min_area_rect=None, return_scores=False, char_boxes=None, **kwargs):
+        """``detect`` for pages larger than the detector takes in one image ("Tiled pages"): every page
+        is padded with 255 (``tools.pad``) to the canvas of ``tools.tile_plan(height, width, tile, overlap)``, the detector
+        runs on its overlapping tiles, ``batch_size`` tiles at a time, and getBoxes on the heat-map stitched from the tiles'
+        cores in HBM.  Same-sized uint8 images (NotImplementedError otherwise); every other argument and the return value
+        as ``detect``.  Pixels nearer than the detector's receptive field to a tile edge differ from a whole-page pass."""
+        images = [tools.read(image) for image in images]
+        want_chars = _lib.char_rule(char_boxes) is not None
+        if not images:
+            return ([],) * (1 + bool(return_scores) + want_chars) if return_scores or want_chars else []
+        batch = np.stack([np.asarray(im) for im in images])
+        if batch.dtype != np.uint8:
+            raise NotImplementedError("detect_tiled: only uint8 images are read in tiles (the tile copy moves RGB bytes)")
+        plan = tools.tile_plan(batch.shape[1], batch.shape[2], tile, overlap)
+        canvas = np.stack([tools.pad(im, width=plan.canvas[1], height=plan.canvas[0]) for im in batch])
+        out = self._ctx._detect_tiled(canvas, tile, overlap, detection_threshold, text_threshold, link_threshold,  # pylint: disable=protected-access
+                                      size_threshold, kwargs.get("batch_size", 0) or 0, None, min_area_rect, return_scores, char_boxes)
+        if want_chars:
+            out.characters = _layout.characters_of(out.characters)
+        return out.render_detection()

@@ -226,14 +226,27 @@ class Pipeline:
             scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
             hmax = hmax_ if hmax is None else max(hmax, hmax_)
             wmax = wmax_ if wmax is None else max(wmax, wmax_)
-            micro_batch = detection_kwargs.pop("batch_size", 0) or 0
-            out = Results.parse_context(ctx.pipeline(
-                images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, hmax, wmax,
-                micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top,
-                **({} if orientation is None else {"orientation": orientation}), **detection_kwargs),
-                return_scores, beam is not None, lexicon_top is not None, want_characters, orientation is not None)
-            if want_characters:
-                out.characters = _layout.characters_of(out.characters)
+            out = self._fused(ctx.pipeline, images, dhs, dws, (hmax, wmax), detection_kwargs, return_scores, beam, lexicon_top,
+                              want_characters, orientation)
+        return self._to_input_pixels(out, scales, orientation, want_characters)
+
+    @staticmethod
+    def _fused(call, images, dhs, dws, sizes, detection_kwargs, return_scores, beam, lexicon_top, want_characters, orientation):
+        """One fused call (``Context.pipeline`` with ``sizes`` = (hmax, wmax), ``Context.pipeline_tiled`` with (tile, overlap))
+        on uint8 images -> its ``Results``, boxes and characters in detector-input pixels"""
+        micro_batch = detection_kwargs.pop("batch_size", 0) or 0
+        out = Results.parse_context(call(
+            images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, *sizes,
+            micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top,
+            **({} if orientation is None else {"orientation": orientation}), **detection_kwargs),
+            return_scores, beam is not None, lexicon_top is not None, want_characters, orientation is not None)
+        if want_characters:
+            out.characters = _layout.characters_of(out.characters)
+        return out
+
+    def _to_input_pixels(self, out, scales, orientation, want_characters):
+        """``Results`` in detector-input pixels -> the same in input-image pixels (pipeline.py:66-71), an oriented run's boxes
+        replaced by its quads"""
         if orientation is not None:
             # every word's box becomes its oriented quad: the same corners, renamed
             turns, quads, log_words = out.orientation
@@ -247,6 +260,54 @@ class Pipeline:
             out.characters = [[_layout.Characters(self._adjust([c.boxes], [scale])[0], c.scores) for c in page]
                               for page, scale in zip(out.characters, scales)]
         return out
+
+    def recognize_tiled(self, images, tile=1024, overlap=128, scale=None, detection_kwargs=None, recognition_kwargs=None,
+                        return_scores=False, char_boxes=None):
+        """recognize() for pages larger than the detector takes in one image, such as a scanned document at its own
+        resolution ("Tiled pages").  Every page is resized by ``scale`` (default ``self.scale``) to
+        ``int(h * scale) x int(w * scale)`` -- ``max_size`` does not apply -- and read in a call of its own: the detector runs
+        on overlapping ``tile`` x ``tile`` pieces of the page, ``overlap`` pixels of halo on every inner side
+        (``tools.tile_plan``), ``detection_kwargs["batch_size"]`` tiles at a time; their heat-maps are stitched in HBM and
+        everything behind them is recognize()'s own path.  Returns what recognize() returns, boxes in input-image pixels; with
+        ``return_scores`` the tuples are ``recognize_with_scores``', with ``char_boxes`` (True or a dict of rule parameters)
+        ``recognize_characters``' (not both).  ``recognition_kwargs`` takes ``beam_width`` / ``top_paths``, ``lexicon_top`` and
+        ``orientation`` / ``tall_ratio`` as recognize() does, with the same refusals.  uint8 images only (NotImplementedError);
+        detector and recogniser must share one ``Context`` (TypeError).  A halo narrower than the detector's receptive field
+        does not reproduce a whole-page pass exactly: see DESIGN.md."""
+        if not isinstance(images, np.ndarray):
+            images = [tools.read(image) for image in images]
+        images = [np.ascontiguousarray(im) for im in images]
+        lexicon_top = lexicon_of(recognition_kwargs)
+        beam = beam_of(recognition_kwargs)
+        want_characters = _wants_characters(char_boxes)
+        if want_characters:
+            _one_text_per_word(recognition_kwargs, "character boxes pair one text per word with its characters")
+            if return_scores:
+                raise ValueError("return_scores and char_boxes cannot be combined: ask for one of the two")
+        orientation = orientation_of(recognition_kwargs, char_boxes if want_characters else None)
+        if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
+            raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
+        ctx = getattr(self.detector, "_ctx", None)
+        if ctx is None or not hasattr(ctx, "pipeline_tiled"):
+            raise TypeError(f"recognize_tiled: the detector ({type(self.detector).__name__}) has no libkocr context to run tiles on")
+        if getattr(self.recognizer, "_ctx", None) is not ctx:
+            raise TypeError(f"recognize_tiled: the recognizer ({type(self.recognizer).__name__}) is not on the detector's context")
+        if any(im.dtype != np.uint8 for im in images):
+            raise NotImplementedError("recognize_tiled: only uint8 images are read in tiles (the tile copy moves RGB bytes)")
+        tools.tile_plan(1, 1, tile, overlap)  # ValueError for a refused tile or overlap, pages or not
+        scale = self.scale if scale is None else scale
+        pages = []
+        for im in images:
+            kwargs = dict(detection_kwargs or {})
+            if want_characters:
+                kwargs["char_boxes"] = char_boxes
+            out = self._fused(ctx.pipeline_tiled, [im], [int(im.shape[0] * scale)], [int(im.shape[1] * scale)], (tile, overlap), kwargs,
+                              return_scores, beam, lexicon_top, want_characters, orientation)
+            out = self._to_input_pixels(out, [scale], orientation, want_characters)
+            words = self._assemble(out)[0]
+            pages.append([(text, box, characters) for (text, box), characters in zip(words, out.characters[0])] if want_characters
+                         else words)
+        return pages
 
     def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None,
                              orientation=None):

@@ -95,6 +95,43 @@ def resize_image(image, max_scale, max_size, ctx=None):
     return out, scale
 
 
+class TilePlan(typing.NamedTuple):
+    """``tile_plan``'s result.  ``counts`` (ny, nx) tiles; ``canvas`` (Hc, Wc) detector-input pixels; ``stride``;
+    ``origins`` per tile (y, x), row-major; ``cores`` per tile (y0, y1, x0, x1), half-open, in canvas pixels."""
+    counts: typing.Tuple[int, int]
+    canvas: typing.Tuple[int, int]
+    stride: int
+    origins: typing.List[typing.Tuple[int, int]]
+    cores: typing.List[typing.Tuple[int, int, int, int]]
+
+
+def tile_plan(height, width, tile, overlap):
+    """How a ``height`` x ``width`` detector input is read in overlapping tiles (include/kocr.h, "tiled pages"; DESIGN.md
+    section 4, "Tiled pages"): ``tile`` T a multiple of 32, at least 64; ``overlap`` O a non-negative multiple of 16; the
+    stride S = T - 2 O at least 32 -- ValueError otherwise.  Per axis of length d: one tile if d <= T, else
+    ceil((d - T) / S) + 1; tile k starts at k S; the canvas is (n - 1) S + T long; tile k's core is
+    [k S + (O if k > 0 else 0), k S + T - (O if k < n - 1 else 0)).  Needs no GPU."""
+    height, width, tile, overlap = int(height), int(width), int(tile), int(overlap)
+    if height < 1 or width < 1:
+        raise ValueError(f"tile_plan: a {height} x {width} page has no pixels")
+    if tile < 64 or tile % 32:
+        raise ValueError(f"tile {tile} must be a multiple of 32, at least 64")
+    if overlap < 0 or overlap % 16:
+        raise ValueError(f"overlap {overlap} must be a non-negative multiple of 16")
+    stride = tile - 2 * overlap
+    if stride < 32:
+        raise ValueError(f"the stride tile - 2 overlap = {stride} must be at least 32")
+
+    def axis(d):
+        n = 1 if d <= tile else -((tile - d) // stride) + 1
+        return n, [(k * stride + (overlap if k > 0 else 0), k * stride + tile - (overlap if k < n - 1 else 0)) for k in range(n)]
+
+    (ny, ys), (nx, xs) = axis(height), axis(width)
+    return TilePlan((ny, nx), ((ny - 1) * stride + tile, (nx - 1) * stride + tile), stride,
+                    [(ky * stride, kx * stride) for ky in range(ny) for kx in range(nx)],
+                    [(y0, y1, x0, x1) for y0, y1 in ys for x0, x1 in xs])
+
+
 def pad(image, width: int, height: int, cval: int = 255):
     """tools.pad (tools.py:356-375)."""
     if len(image.shape) == 3:
