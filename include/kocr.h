@@ -482,6 +482,14 @@ int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* 
                             float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
                             int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
                             int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss);
+/* The same with character sets ("Character sets" below): set_of int32 [M] (HOST), each in [-1, kocr_charset_count()) else
+ * KOCR_EINVAL naming the crop; NULL: the context's kocr_set_charset switch, which kocr_crnn_decode_logits follows too.  The
+ * decode, the scores, the beam and the lexicon parts run under the sets; the loss part stays unmasked. */
+int kocr_crnn_decode_logits_charsets(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
+                                     float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
+                                     int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values,
+                                     const int32_t* loss_labels, int label_stride, const int32_t* label_lengths,
+                                     const int32_t* input_lengths, float* loss, const int32_t* set_of);
 
 /* ---- arithmetic of the wide convolutions --------------------------------------------- */
 /* The 3x3 / 1x1 / dilated convolutions with Cout > 32 run on the 16-bit matrix cores with fp32 operands split into
@@ -631,6 +639,35 @@ int kocr_set_lexicon_match(kocr_ctx* ctx, int top_words);
 int kocr_get_lexicon_match(const kocr_ctx* ctx, int* top_words);
 int kocr_recognition_lexicon(kocr_ctx* ctx, int32_t* index, float* log_prob, int max_crops, int32_t* n_crops, int32_t* top_words);
 int kocr_set_lexicon_scratch(kocr_ctx* ctx, uint64_t bytes);
+
+/* ---- character sets: which characters may this crop hold ("Character sets") ---------------------------
+ * A character set A is a non-empty subset of the non-blank classes [0, classes - 2] of the loaded recogniser; the blank is
+ * always allowed.  A crop decoded under A is decoded as if fc_12 had written -inf for every class outside A and the blank,
+ * and everything behind that is the unchanged rule on the masked row: the arg-max (ties to the smaller class), the softmax
+ * (masked classes exactly 0), q_t = (p + 1e-7) / sum over ALL classes, the word log-probability, the character scores, the
+ * lexicon values (a word with a masked character keeps a finite, very small value: it is not removed) and the beam search,
+ * whose prefixes are extended only by classes of A -- per frame the min(beam_width, |A|) of them with the largest logit.
+ * The mask is applied where the decode kernels read the row: no launch is added, the logits, the taps (fc_12, ctc input),
+ * kocr_ctc_batch_cost, kocr_crnn_ctc_loss and kocr_crnn_features are never masked.
+ * kocr_set_charsets: allowed = S rows of classes - 1 bytes (HOST; non-zero: the class is in the set); classes must equal
+ * kocr_crnn_classes() (KOCR_ENOWEIGHTS without a recogniser), 0 <= S <= KOCR_CHARSETS_MAX and every set non-empty, else
+ * KOCR_EINVAL naming the argument and the set.  The table stays resident on the context like a lexicon.  S = 0 unloads and
+ * switches off.  A call replaces the previous table (and switches off); a refused one changes nothing.  Loading another
+ * recogniser with a DIFFERENT class count unloads the table and switches off.  kocr_charset_count: S (0: none).
+ * kocr_set_charset(ctx, set): -1 (the default) is off -- the calls launch the kernels they always launched and return the
+ * same bits; set in [0, S) makes every decode of kocr_crnn_forward[_scores], kocr_crnn_beam, kocr_crnn_lexicon,
+ * kocr_recognize_boxes and kocr_pipeline[_tiled] run under that set, with every other switch (scores, beam, lexicon match,
+ * orientation, character boxes) as before and every resident-result getter answering as before; anything else KOCR_EINVAL.
+ * kocr_recognize_boxes_charsets: kocr_recognize_boxes with one set per box, set_of int32 [sum of counts] (HOST, image-major,
+ * box order), each in [-1, S) (-1: unconstrained); anything else is KOCR_EINVAL naming the box, before any launch.  The
+ * context's uniform switch is not consulted.  With orientation on, both candidates of box m are read under set_of[m]. */
+#define KOCR_CHARSETS_MAX 256
+int kocr_set_charsets(kocr_ctx* ctx, const uint8_t* allowed, int S, int classes);
+int kocr_charset_count(const kocr_ctx* ctx);
+int kocr_set_charset(kocr_ctx* ctx, int set);
+int kocr_get_charset(const kocr_ctx* ctx, int* set);
+int kocr_recognize_boxes_charsets(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                                  const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of);
 
 /* ---- orientation: read each box both ways and keep the better reading ("Orientation") ----------------
  * The reference's get_rotated_box always names the upper of the two leftmost corners tl, so an upside-down word is warped

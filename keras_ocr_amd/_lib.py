@@ -85,6 +85,12 @@ def load_library():
         "kocr_get_lexicon_match": (ci, [vp, vp]),
         "kocr_recognition_lexicon": (ci, [vp, vp, vp, ci, vp, vp]),
         "kocr_set_lexicon_scratch": (ci, [vp, ctypes.c_uint64]),
+        "kocr_set_charsets": (ci, [vp, vp, ci, ci]),
+        "kocr_charset_count": (ci, [vp]),
+        "kocr_set_charset": (ci, [vp, ci]),
+        "kocr_get_charset": (ci, [vp, vp]),
+        "kocr_recognize_boxes_charsets": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
+        "kocr_crnn_decode_logits_charsets": (ci, [vp, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
         "kocr_set_orientation": (ci, [vp, ci, ctypes.c_double]),
         "kocr_get_orientation": (ci, [vp, vp, vp]),
         "kocr_recognition_orientation": (ci, [vp, vp, vp, vp, ci, vp]),
@@ -697,6 +703,44 @@ class Context:
         return self._fetch_resident(self._lib.kocr_recognition_lexicon, 2, lambda m, k: (
             np.full((m, k), -1, dtype=np.int32), np.full((m, k), -np.inf, dtype=np.float32)))
 
+    # -- character sets (include/kocr.h: "Character sets") ---------------------------------------------------------------
+    def set_charsets(self, allowed=None):
+        """Load the sets (kocr_set_charsets): allowed (S, classes - 1) of 0 / 1, row s = the non-blank classes of set s; the
+        table stays resident like a lexicon.  ``set_charsets(None)`` unloads and switches off.  ValueError naming the set for
+        an empty one, for more than 256 sets and for a row length other than ``crnn_classes() - 1``."""
+        if allowed is None or len(allowed) == 0:
+            self._check(self._lib.kocr_set_charsets(self._h, None, 0, 0), value_error=True)
+            return
+        a = np.ascontiguousarray(np.asarray(allowed) != 0, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError(f"charsets must be (S, classes - 1), got shape {a.shape}")
+        self._check(self._lib.kocr_set_charsets(self._h, _ptr(a), a.shape[0], a.shape[1] + 1), value_error=True)
+
+    def charset_count(self):
+        return self._check(self._lib.kocr_charset_count(self._h))
+
+    def set_charset(self, index=-1):
+        """The set every decode of the context runs under (kocr_set_charset); -1 = off."""
+        self._check(self._lib.kocr_set_charset(self._h, int(index)), value_error=True)
+
+    def get_charset(self):
+        k = ctypes.c_int(0)
+        self._check(self._lib.kocr_get_charset(self._h, ctypes.byref(k)))
+        return k.value
+
+    def _charset_scope(self, index):
+        """The character set for one call; None: the context's own setting.  A table unloaded meanwhile took the switch with
+        it: then nothing is restored."""
+        return _option_scope(self.get_charset, self.set_charset, None if index is None else int(index),
+                             lambda old: old < self.charset_count() and self.set_charset(old))
+
+    def _set_of(self, set_of, m, what):
+        """``set_of`` as (m,) int32, or ValueError naming the count"""
+        s = np.ascontiguousarray(np.reshape(set_of, -1), dtype=np.int32)
+        if s.shape != (m,):
+            raise ValueError(f"set_of must hold one character set per {what}: {m}, got {s.shape[0]}")
+        return s
+
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
 
@@ -738,12 +782,14 @@ class Context:
         return loss
 
     def crnn_decode_logits(self, logits, return_probs=False, scores=False, beam=None, top_words=0, return_values=False,
-                           loss_labels=None):
+                           loss_labels=None, set_of=None):
         """Development entry (kocr_crnn_decode_logits): the launches behind fc_12 on the caller's logits (M, 50, classes)
         float32, M <= 1024.  Returns a dict: "labels" (M, LW) int32 [, "probs" (M, LW, C)] as crnn_forward; with ``scores``
         "log_word" (M,) and "chars" (M, LW) as crnn_forward_scores; with ``beam=(beam_width, top_paths)`` "beam_labels" /
         "beam_log_prob" as crnn_beam; with ``top_words`` "lex_index" / "lex_log_prob" [, "lex_values"] as crnn_lexicon; with
-        ``loss_labels=(labels, label_lengths, input_lengths)`` "loss" (M,) as crnn_ctc_loss.  Refusals as those calls."""
+        ``loss_labels=(labels, label_lengths, input_lengths)`` "loss" (M,) as crnn_ctc_loss.  Refusals as those calls.
+        ``set_of`` (M integers in [-1, charset_count())): each crop's character set (kocr_crnn_decode_logits_charsets), -1 =
+        unconstrained; None: the context's ``set_charset`` switch.  The loss is never masked."""
         x = np.ascontiguousarray(logits, dtype=np.float32)
         c, lw = self.crnn_classes(), self.crnn_label_width()
         if x.ndim != 3 or x.shape[1:] != (50, c):
@@ -772,10 +818,14 @@ class Context:
             stride = lab.shape[1]
             out["loss"] = np.zeros(m, np.float32)
         g = out.get
-        self._check(self._lib.kocr_crnn_decode_logits(
-            self._h, _ptr(x), m, _ptr(out["labels"]), _ptr(g("probs")), _ptr(g("log_word")), _ptr(g("chars")), bw, k,
-            _ptr(g("beam_labels")), _ptr(g("beam_log_prob")), tw, _ptr(g("lex_index")), _ptr(g("lex_log_prob")), _ptr(g("lex_values")),
-            _ptr(lab), stride, _ptr(ll), _ptr(il), _ptr(g("loss"))), value_error=True)
+        args = (self._h, _ptr(x), m, _ptr(out["labels"]), _ptr(g("probs")), _ptr(g("log_word")), _ptr(g("chars")), bw, k,
+                _ptr(g("beam_labels")), _ptr(g("beam_log_prob")), tw, _ptr(g("lex_index")), _ptr(g("lex_log_prob")), _ptr(g("lex_values")),
+                _ptr(lab), stride, _ptr(ll), _ptr(il), _ptr(g("loss")))
+        if set_of is None:
+            self._check(self._lib.kocr_crnn_decode_logits(*args), value_error=True)
+        else:
+            sets = self._set_of(set_of, m, "crop")
+            self._check(self._lib.kocr_crnn_decode_logits_charsets(*args, _ptr(sets)), value_error=True)
         return out
 
     def crnn_features(self, crops):
@@ -856,16 +906,18 @@ class Context:
             int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), min_area_rect, return_scores, char_boxes)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
-    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None):
+    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None):
         """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32 [, log_word (M,), char_scores
         (M,48) float32 as ``crnn_forward_scores``] [, beam labels (M,K,48), beam log_prob (M,K) as ``crnn_beam``, with
         ``beam=(beam_width, top_paths)``; the other results are the same bits] [, lexicon index (M,K), log_prob (M,K) as
         ``crnn_lexicon``, with ``lexicon_top=K``] [, turns (M,), quads (M,4,2), log_words (M,2) as ``recognition_orientation``,
         with ``orientation=(mode, tall_ratio)``: labels and scores are then those of each word's better reading; not
-        together with ``beam`` or ``lexicon_top`` (ValueError)]."""
-        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top, orientation).render_recognition()
+        together with ``beam`` or ``lexicon_top`` (ValueError)].  ``set_of`` (one integer per box, image-major, in
+        [-1, charset_count())): each box's character set (kocr_recognize_boxes_charsets), -1 = unconstrained; None: the
+        context's ``set_charset`` switch."""
+        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top, orientation, set_of).render_recognition()
 
-    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None):
+    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None):
         """recognize_boxes' ``Results`` (no boxes; the detection part of its scores is None); no library call for zero boxes
         beyond the switches"""
         beam = None if beam is None else beam_args(*beam)
@@ -879,8 +931,12 @@ class Context:
                 lw = self.crnn_label_width()
                 out = Results(None, np.full((int(counts.sum()), lw), -1, dtype=np.int32))
                 m = len(out.labels)
+                sets = None if set_of is None else self._set_of(set_of, m, "box")
                 with self._scores_scope(return_scores and m):
-                    if m:
+                    if m and sets is not None:
+                        self._check(self._lib.kocr_recognize_boxes_charsets(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
+                                                                            _ptr(out.labels), 0, _ptr(sets)), value_error=True)
+                    elif m:
                         self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
                                                                    _ptr(out.labels), 0))
                     if return_scores:

@@ -123,7 +123,8 @@ struct OrientWinners {
 // The recogniser stage of kocr_recognize_boxes / kocr_pipeline: its outputs for M crops on a context -- the label rows, and
 // what the context's switches add: score rows (scores), beam rows (BW > 0), lexicon rows (LK > 0).  An oriented run is the
 // same stage over its 2 M candidate crops with scores forced on (no beam, no lexicon: orient_refusal).  each() is the one
-// list of the buffers: every pointer with its size.
+// list of the buffers: every pointer with its size.  cm: the character sets the crops are decoded under -- the context's
+// uniform switch unless the caller puts a per-crop list in its place (kocr_recognize_boxes_charsets).
 struct RecStage {
   kocr_ctx* ctx;
   long M;
@@ -133,9 +134,10 @@ struct RecStage {
   CrnnScores sc{nullptr, nullptr};
   CrnnBeam bm;
   CrnnLexicon lx;
+  CharMask cm;
   RecStage(kocr_ctx* c, long m, bool force_scores = false)
       : ctx(c), M(m), LW(crnn_label_width(c)), BW(c->beam_width), BK(c->beam_top_paths), LK(c->lex_top),
-        scores(c->scores_on || force_scores), bm{BW, BK, nullptr, nullptr}, lx{LK, nullptr, nullptr, nullptr} {}
+        scores(c->scores_on || force_scores), bm{BW, BK, nullptr, nullptr}, lx{LK, nullptr, nullptr, nullptr}, cm(c->charmask()) {}
 
   template <class F> int each(F f) {
     const size_t m = (size_t)M, i4 = sizeof(int32_t), f4 = sizeof(float);
@@ -168,7 +170,7 @@ struct RecStage {
       const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
       const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
       return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
-                          scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr);
+                          scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr, cm.from((int)s));
     });
   }
   // (d) what the stage leaves resident for the getters, each record with the state of its switch.  An oriented run keeps its

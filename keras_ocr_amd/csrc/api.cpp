@@ -207,7 +207,7 @@ static int crnn_forward_call(kocr_ctx* ctx, const char* fn, const float* crops, 
       KOCR_TRY(st.out(log_word + s, wb * nb, sc.d_logw));
       KOCR_TRY(st.out(char_scores + s * LW, hb * nb, sc.d_chars));
     }
-    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p, CRNN_DECODE, nullptr, nullptr, scores ? &sc : nullptr));
+    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p, CRNN_DECODE, nullptr, nullptr, scores ? &sc : nullptr, nullptr, nullptr, ctx->charmask()));
     KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
     if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
     if (scores) {
@@ -372,6 +372,8 @@ int kocr_load_crnn(kocr_ctx* ctx, int n, const char* const* names, const float* 
   KOCR_TRY(crnn_load(ctx, n, names, data, shapes, ranks));
   // a lexicon's labels were validated against the class count of the recogniser it was loaded under
   if (ctx->lex.V && ctx->lex.classes != crnn_classes(ctx)) lexicon_unload(ctx, ctx->lex.classes);
+  // ... and so were the character sets' class indices
+  if (ctx->charsets.S && ctx->charsets.classes != crnn_classes(ctx)) charsets_unload(ctx);
   return KOCR_OK;
 }
 
@@ -412,7 +414,7 @@ int kocr_crnn_beam(kocr_ctx* ctx, const float* crops, int M, int beam_width, int
     KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
     KOCR_TRY(st.out(labels + s * top_paths * LW, lb * nb, bm.d_labels));
     KOCR_TRY(st.out(log_prob + s * top_paths, vb * nb, bm.d_logp));
-    KOCR_TRY(crnn_beam(ctx, d_c, nb, bm));
+    KOCR_TRY(crnn_beam(ctx, d_c, nb, bm, ctx->charmask()));
     KOCR_TRY(st.back(labels + s * top_paths * LW, bm.d_labels, lb * nb));
     KOCR_TRY(st.back(log_prob + s * top_paths, bm.d_logp, vb * nb));
     return st.finish();
@@ -506,7 +508,7 @@ int kocr_crnn_lexicon(kocr_ctx* ctx, const float* crops, int M, int top_words, i
     KOCR_TRY(st.out(index + s * top_words, ib * nb, lx.d_index));
     KOCR_TRY(st.out(log_prob + s * top_words, vb * nb, lx.d_logp));
     if (all_values) KOCR_TRY(st.out(all_values + (size_t)s * V, ab * nb, lx.d_all));
-    KOCR_TRY(crnn_lexicon(ctx, d_c, nb, lx));
+    KOCR_TRY(crnn_lexicon(ctx, d_c, nb, lx, ctx->charmask()));
     KOCR_TRY(st.back(index + s * top_words, lx.d_index, ib * nb));
     KOCR_TRY(st.back(log_prob + s * top_words, lx.d_logp, vb * nb));
     if (all_values) KOCR_TRY(st.back(all_values + (size_t)s * V, lx.d_all, ab * nb));
@@ -596,13 +598,77 @@ int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* 
   });
 }
 
-// Development entry (include/kocr.h): crnn_forward's launches behind fc_12 on the caller's logits
-int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
-                            float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
-                            int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
-                            int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss) {
+// ---- character sets (include/kocr.h, "Character sets") ------------------------------------------------------------------
+int kocr_set_charsets(kocr_ctx* ctx, const uint8_t* allowed, int S, int classes) {
   if (!ctx) return KOCR_EINVAL;
-  const char* fn = "kocr_crnn_decode_logits";
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  if (S == 0) {
+    charsets_unload(ctx);
+    return KOCR_OK;
+  }
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_set_charsets: call kocr_load_crnn first (the sets are subsets of its classes)");
+  if (S < 0 || S > KOCR_CHARSETS_MAX)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_charsets: S " + std::to_string(S) + " outside [0, KOCR_CHARSETS_MAX = " +
+                                    std::to_string(KOCR_CHARSETS_MAX) + "]");
+  if (classes != C)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_charsets: classes " + std::to_string(classes) + " is not the recogniser's " +
+                                    std::to_string(C) + " (class count mismatch)");
+  if (!allowed) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_charsets: null buffer");
+  // the bit table: bit c of set s for an allowed class, the blank's bit always, the bits from C on clear
+  const int nw = (C + 31) / 32;
+  std::vector<uint32_t> bits((size_t)S * nw, 0u);
+  for (int s = 0; s < S; ++s) {
+    int n = 0;
+    for (int c = 0; c < C - 1; ++c)
+      if (allowed[(size_t)s * (C - 1) + c]) {
+        bits[(size_t)s * nw + (c >> 5)] |= 1u << (c & 31);
+        ++n;
+      }
+    if (n == 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_charsets: allowed: set " + std::to_string(s) + " is empty (a set needs at least one class)");
+    bits[(size_t)s * nw + ((C - 1) >> 5)] |= 1u << ((C - 1) & 31);
+  }
+  charsets_unload(ctx);
+  auto& cs = ctx->charsets;
+  int rc = ctx->dev_alloc((void**)&cs.d_bits, bits.size() * sizeof(uint32_t));
+  if (rc == KOCR_OK && hipMemcpyAsync(cs.d_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+    ctx->set_err("kocr_set_charsets: the copy of the table failed");
+    rc = KOCR_EHIP;
+  }
+  hipStreamSynchronize(ctx->stream);  // the host vector goes out of scope
+  if (rc != KOCR_OK) {
+    charsets_unload(ctx);
+    return rc;
+  }
+  cs.S = S;
+  cs.classes = C;
+  return KOCR_OK;
+}
+
+int kocr_charset_count(const kocr_ctx* ctx) { return ctx ? ctx->charsets.S : KOCR_EINVAL; }
+
+int kocr_set_charset(kocr_ctx* ctx, int set) {
+  if (!ctx) return KOCR_EINVAL;
+  if (set < -1 || set >= ctx->charsets.S)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_charset: set " + std::to_string(set) + " outside [-1, " + std::to_string(ctx->charsets.S) +
+                                    ") (" + std::to_string(ctx->charsets.S) + " sets are loaded: kocr_set_charsets)");
+  ctx->charset = set;
+  return KOCR_OK;
+}
+
+int kocr_get_charset(const kocr_ctx* ctx, int* set) {
+  if (!ctx || !set) return KOCR_EINVAL;
+  *set = ctx->charset;
+  return KOCR_OK;
+}
+
+// Development entry (include/kocr.h): crnn_forward's launches behind fc_12 on the caller's logits; set_of (HOST, nullable):
+// the crops' character sets in place of the context's switch
+static int decode_logits_call(kocr_ctx* ctx, const char* fn, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
+                              float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
+                              int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
+                              int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss,
+                              const int32_t* set_of) {
   if (M < 0 || (M > 0 && (!logits || !labels))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null buffer");
   if (!log_word != !char_scores) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: log_word and char_scores go together");
   const int C = crnn_classes(ctx);
@@ -625,6 +691,7 @@ int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* 
     if (M > 0 && (!label_lengths || !input_lengths || !loss)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null loss buffer");
     KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, loss_labels, label_stride, label_lengths, input_lengths, &Lmax));
   }
+  if (set_of) KOCR_TRY(charsets_validate(ctx, fn, set_of, M, "crop"));
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t m = (size_t)M, f = sizeof(float), V = top_words ? (size_t)ctx->lex.V : 0;
@@ -636,8 +703,10 @@ int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* 
   const size_t ib = loss_labels ? m * (std::max(Lmax, 1) + 2) * sizeof(int32_t) : 0;
   Staging st{ctx, ctx->ws, fn, false};
   KOCR_TRY(st.reserve(top_words ? lexicon_workspace_bytes(ctx, M, !lex_values) : 0,
-                      {gb, lb, pb, wb, hb, bl, bv, xi, xv, xa, sb}, {ib}));
+                      {gb, lb, pb, wb, hb, bl, bv, xi, xv, xa, sb}, {ib, set_of ? m * sizeof(int32_t) : 0}));
   const float* d_lg;
+  const int32_t* d_set = nullptr;  // the caller's array outlives the copy: finish() synchronises
+  if (set_of) KOCR_TRY(st.upload(set_of, m * sizeof(int32_t), d_set));
   int32_t* d_l;
   float* d_p = nullptr;
   CrnnScores sc{nullptr, nullptr};
@@ -659,7 +728,8 @@ int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* 
     KOCR_TRY(st.out(lex_log_prob, xv, lx.d_logp));
     if (lex_values) KOCR_TRY(st.out(lex_values, xa, lx.d_all));
   }
-  KOCR_TRY(crnn_decode_logits(ctx, d_lg, M, d_l, d_p, log_word ? &sc : nullptr, beam_width ? &bm : nullptr, top_words ? &lx : nullptr));
+  KOCR_TRY(crnn_decode_logits(ctx, d_lg, M, d_l, d_p, log_word ? &sc : nullptr, beam_width ? &bm : nullptr, top_words ? &lx : nullptr,
+                              ctx->charmask(d_set, 0)));
   KOCR_TRY(st.back(labels, d_l, lb));
   if (probs) KOCR_TRY(st.back(probs, d_p, pb));
   if (log_word) {
@@ -685,6 +755,27 @@ int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* 
     KOCR_TRY(st.back(loss, d_loss, sb));
   }
   return st.finish();  // also keeps `staged` alive until its copy is done
+}
+
+int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
+                            float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
+                            int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
+                            int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss) {
+  if (!ctx) return KOCR_EINVAL;
+  return decode_logits_call(ctx, "kocr_crnn_decode_logits", logits, M, labels, probs, log_word, char_scores, beam_width, top_paths,
+                            beam_labels, beam_log_prob, top_words, lex_index, lex_log_prob, lex_values, loss_labels, label_stride,
+                            label_lengths, input_lengths, loss, nullptr);
+}
+
+int kocr_crnn_decode_logits_charsets(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
+                                     float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
+                                     int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values,
+                                     const int32_t* loss_labels, int label_stride, const int32_t* label_lengths,
+                                     const int32_t* input_lengths, float* loss, const int32_t* set_of) {
+  if (!ctx) return KOCR_EINVAL;
+  return decode_logits_call(ctx, "kocr_crnn_decode_logits_charsets", logits, M, labels, probs, log_word, char_scores, beam_width,
+                            top_paths, beam_labels, beam_log_prob, top_words, lex_index, lex_log_prob, lex_values, loss_labels,
+                            label_stride, label_lengths, input_lengths, loss, set_of);
 }
 
 int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device) {

@@ -138,6 +138,26 @@ struct CharsRule {
   double peak_threshold, valley_ratio, extent_threshold;
 };
 
+// Character sets (kocr_set_charsets; DESIGN.md section 4, "Character sets"): what the decode kernels of crnn_kernels.hip take
+// by value.  bits: the device table [S][ceil(C / 32)], bit c of set s = class c is allowed (the blank's bit is always set,
+// the bits from C on are clear).  Crop m of a launch decodes under set set_of[(first + m) >> shift] (device, one entry per
+// crop; shift = 1: per box of an oriented run's candidate pairs), or under `uniform` when set_of is null; set -1 allows
+// every class.  first: the place of the launch's crop 0 in the whole call's crops (the batch and chunk loops advance it).
+// Off (no table, or neither a per-crop list nor a uniform set): the launchers take the unmasked instantiations.
+struct CharMask {
+  const uint32_t* bits = nullptr;
+  const int32_t* set_of = nullptr;
+  int uniform = -1;
+  int shift = 0;
+  int first = 0;
+  bool on() const { return bits && (set_of || uniform >= 0); }
+  CharMask from(int crop) const {
+    CharMask c = *this;
+    c.first += crop;
+    return c;
+  }
+};
+
 struct kocr_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -269,6 +289,19 @@ struct kocr_ctx {
   } last_lex;
   void keep_lexicon(const int* d_index, const float* d_logp, int M) {
     last_lex = {d_index, d_logp, M, lex_top, resident(lex_top > 0)};
+  }
+  // character sets (kocr_set_charsets / kocr_set_charset; DESIGN.md section 4, "Character sets"): the caller's S sets as a
+  // bit table, resident like the lexicon; classes: the recogniser's class count it was built for.  charset: the set every
+  // decode of the context runs under (-1: none -- the unmasked kernels); only ever >= 0 while a table is loaded.
+  struct Charsets {
+    uint32_t* d_bits = nullptr;  // [S][ceil(classes / 32)]
+    int S = 0, classes = 0;
+  } charsets;
+  int charset = -1;
+  CharMask charmask() const { return CharMask{charsets.d_bits, nullptr, charsets.d_bits ? charset : -1, 0, 0}; }
+  // ... with a per-crop list (device) in place of the uniform set
+  CharMask charmask(const int32_t* d_set_of, int shift) const {
+    return d_set_of ? CharMask{charsets.d_bits, d_set_of, -1, shift, 0} : charmask();
   }
   // character boxes (kocr_set_char_boxes; DESIGN.md section 4, "Characters"): with the switch on, kocr_get_boxes /
   // kocr_detect / kocr_pipeline run the two launches of chars.hip on the heat-maps and boxes in HBM (chars_resident) and leave
@@ -550,11 +583,14 @@ struct CrnnLexicon {
   float* d_logp;
   float* d_all;
 };
+// cm: the character sets of the batch's crops (CharMask above; off by default).  Every decode launch behind fc_12 -- the greedy
+// decode or the scores, the beam, the lexicon launches -- reads its rows through it; the logits themselves, the taps, the loss
+// and the features are never masked.
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
                  float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr,
-                 const CrnnBeam* bm = nullptr, const CrnnLexicon* lx = nullptr);
+                 const CrnnBeam* bm = nullptr, const CrnnLexicon* lx = nullptr, const CharMask& cm = CharMask{});
 // crnn_forward to the logits, then the lexicon launches alone (kocr_crnn_lexicon)
-int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx);
+int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx, const CharMask& cm = CharMask{});
 // Crops per chunk of the lexicon launches: as many as lex_scratch bytes of values hold, clamp(lex_scratch / (4 V), 1, M);
 // and the workspace bytes the launches take on top of crnn_workspace_bytes(M) (own_values: no d_all buffer is given)
 int lexicon_chunk(const kocr_ctx* ctx, int M);
@@ -563,8 +599,12 @@ size_t lexicon_workspace_bytes(kocr_ctx* ctx, int M, bool own_values);
 int lexicon_validate(kocr_ctx* ctx, const char* fn, int top_words);
 // the device copies freed, V = 0, the match switched off; dropped_classes as given
 void lexicon_unload(kocr_ctx* ctx, int dropped_classes);
+// the character-set table freed, S = 0, the uniform switch off
+void charsets_unload(kocr_ctx* ctx);
+// KOCR_EINVAL naming the entry unless each of set_of[0 .. M) (HOST) lies in [-1, S); `what`: what an entry belongs to ("box")
+int charsets_validate(kocr_ctx* ctx, const char* fn, const int32_t* set_of, long M, const char* what);
 // crnn_forward to the logits, then ctc_beam_kernel alone (kocr_crnn_beam)
-int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm);
+int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm, const CharMask& cm = CharMask{});
 // KOCR_EINVAL naming the argument unless 1 <= beam_width <= 64 and 1 <= top_paths <= beam_width
 int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths);
 // training_model (recognition.py:334-349): crnn_forward to the logits, then ctc_loss_kernel on fc_12's softmax of frames
@@ -577,7 +617,7 @@ int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const int* d_lab, 
 // crnn_forward's launches behind fc_12 on the caller's logits [M][50][n_classes] (device): the decode (with sc: the scores), then
 // the beam, then the lexicon match -- the same launch functions with the same arguments.  No taps, nothing resident changes.
 int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
-                       const CrnnBeam* bm, const CrnnLexicon* lx);
+                       const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm = CharMask{});
 // keras.backend.ctc_batch_cost's refusals on host arrays, before anything is launched: T_m in [1, T],
 // L_m in [0, min(T_m, label_stride)], labels[m][0 .. L_m) in [0, C - 2]; KOCR_EINVAL naming the sample.  *Lmax = max L_m.
 int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32_t* labels, int label_stride,

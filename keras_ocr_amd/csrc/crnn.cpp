@@ -30,17 +30,19 @@ int launch_stn_sample(kocr_ctx* ctx, const Tensor& x, const float* d_theta, cons
 int launch_lstm(kocr_ctx* ctx, const float* d_xp, const float* d_Uf, const float* d_Ub, float* d_out, int M, int T);
 size_t dense_splitk_workspace(int M, int K);
 int launch_dense_splitk(kocr_ctx* ctx, const ConvLayer& L, const float* d_in, float* d_out, float* d_partial, int M);
-int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs);
+int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
+               const CharMask& cm);
 int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
-                      float* d_logw, float* d_chars);
+                      float* d_logw, float* d_chars, const CharMask& cm);
 int launch_ctc_beam(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int beam_width, int top_paths,
-                    int* d_labels, float* d_logp);
+                    int* d_labels, float* d_logp, const CharMask& cm);
 
-int launch_lexicon_logq(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, float* d_lq);
+int launch_lexicon_logq(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, float* d_lq, const CharMask& cm);
 int launch_lexicon_score(kocr_ctx* ctx, const float* d_lq, int M, int To, int C, const int* d_words, int wstride, const int* d_lens,
                          const int* d_order, int V, int Lmax, float* d_values);
 int launch_lexicon_select(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, const float* d_values, int V,
-                          const int* d_words, int wstride, const int* d_lens, int top_words, int* d_index, float* d_logp);
+                          const int* d_words, int wstride, const int* d_lens, int top_words, int* d_index, float* d_logp,
+                          const CharMask& cm);
 
 struct CrnnNet {
   std::map<std::string, ConvLayer> L;
@@ -235,8 +237,9 @@ size_t lexicon_workspace_bytes(kocr_ctx* ctx, int M, bool own_values) {
   return chunk * T * (size_t)std::max(crnn_classes(ctx), 1) * sizeof(float) + (own_values ? chunk * ctx->lex.V * sizeof(float) : 0) + 1024;
 }
 
-// lexicon_logq, lexicon_score, lexicon_select on the logits [M][T][C] of a batch, chunk by chunk
-static int lexicon_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnLexicon& lx) {
+// lexicon_logq, lexicon_score, lexicon_select on the logits [M][T][C] of a batch, chunk by chunk; cm: the batch's character
+// sets, advanced to each chunk's first crop
+static int lexicon_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnLexicon& lx, const CharMask& cm) {
   const auto& lex = ctx->lex;
   const int C = ctx->crnn->n_classes, discard = ctx->crnn->discard, To = T - discard, V = lex.V;
   if (V <= 0 || lex.classes != C) KOCR_FAIL(ctx, KOCR_EINVAL, "lexicon: no lexicon loaded for this recogniser's class count");
@@ -248,34 +251,36 @@ static int lexicon_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnLexico
     const int nc = std::min(chunk, M - c0);
     const float* lg = d_lg + (size_t)c0 * T * C;
     float* vals = lx.d_all ? lx.d_all + (size_t)c0 * V : d_vals;
-    KOCR_TRY(launch_lexicon_logq(ctx, lg, nc, T, C, discard, d_lq));
+    const CharMask cc = cm.from(c0);
+    KOCR_TRY(launch_lexicon_logq(ctx, lg, nc, T, C, discard, d_lq, cc));
     KOCR_TRY(launch_lexicon_score(ctx, d_lq, nc, To, C, lex.d_words, lex.Lmax, lex.d_lens, lex.d_order, V, lex.Lmax, vals));
     KOCR_TRY(launch_lexicon_select(ctx, lg, nc, T, C, discard, vals, V, lex.d_words, lex.Lmax, lex.d_lens, lx.top_words,
-                                   lx.d_index + (size_t)c0 * lx.top_words, lx.d_logp + (size_t)c0 * lx.top_words));
+                                   lx.d_index + (size_t)c0 * lx.top_words, lx.d_logp + (size_t)c0 * lx.top_words, cc));
   }
   return KOCR_OK;
 }
 
 // The launches behind fc_12 on the logits [M][T][C] of a batch, shared by crnn_forward and crnn_decode_logits: the greedy decode
 // (with the scores when sc is given) ...
-static int decode_launch(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc) {
+static int decode_launch(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
+                         const CharMask& cm) {
   const CrnnNet* net = ctx->crnn;
-  if (sc) return launch_ctc_scores(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars);
-  return launch_ctc(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs);
+  if (sc) return launch_ctc_scores(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars, cm);
+  return launch_ctc(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, cm);
 }
 // ... then the beam search and the lexicon match, each where asked for
-static int decode_extras(kocr_ctx* ctx, const float* d_lg, int M, const CrnnBeam* bm, const CrnnLexicon* lx) {
+static int decode_extras(kocr_ctx* ctx, const float* d_lg, int M, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm) {
   const CrnnNet* net = ctx->crnn;
   if (bm)
-    KOCR_TRY(launch_ctc_beam(ctx, d_lg, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp));
-  if (lx) KOCR_TRY(lexicon_run(ctx, d_lg, M, *lx));
+    KOCR_TRY(launch_ctc_beam(ctx, d_lg, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp, cm));
+  if (lx) KOCR_TRY(lexicon_run(ctx, d_lg, M, *lx, cm));
   return KOCR_OK;
 }
 
 // d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
 // `stop` / d_feats / d_logits / sc / bm / lx: common.h
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
-                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm, const CrnnLexicon* lx) {
+                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -476,23 +481,23 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   probs.W = T - net->discard;
   probs.C = probs.cs = net->n_classes;
   probs.p = d_probs;
-  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() { return decode_launch(ctx, lg.p, M, d_labels, d_probs, sc); }));
-  return decode_extras(ctx, lg.p, M, bm, lx);
+  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() { return decode_launch(ctx, lg.p, M, d_labels, d_probs, sc, cm); }));
+  return decode_extras(ctx, lg.p, M, bm, lx, cm);
 }
 
 int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
-                       const CrnnBeam* bm, const CrnnLexicon* lx) {
+                       const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm) {
   if (!ctx->crnn || !ctx->crnn->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_decode_logits: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
-  KOCR_TRY(decode_launch(ctx, d_lg, M, d_labels, d_probs, sc));
-  return decode_extras(ctx, d_lg, M, bm, lx);
+  KOCR_TRY(decode_launch(ctx, d_lg, M, d_labels, d_probs, sc, cm));
+  return decode_extras(ctx, d_lg, M, bm, lx, cm);
 }
 
-int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx) {
+int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx, const CharMask& cm) {
   const float* d_lg = nullptr;
   KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
   if (M <= 0) return KOCR_OK;
-  return lexicon_run(ctx, d_lg, M, lx);
+  return lexicon_run(ctx, d_lg, M, lx, cm);
 }
 
 int lexicon_validate(kocr_ctx* ctx, const char* fn, int top_words) {
@@ -507,6 +512,23 @@ int lexicon_validate(kocr_ctx* ctx, const char* fn, int top_words) {
   return KOCR_OK;
 }
 
+void charsets_unload(kocr_ctx* ctx) {
+  hipStreamSynchronize(ctx->stream);  // no launch still reads the table
+  ctx->release(ctx->charsets.d_bits);
+  ctx->charsets = kocr_ctx::Charsets{};
+  ctx->charset = -1;
+}
+
+int charsets_validate(kocr_ctx* ctx, const char* fn, const int32_t* set_of, long M, const char* what) {
+  const int S = ctx->charsets.S;
+  for (long m = 0; m < M; ++m)
+    if (set_of[m] < -1 || set_of[m] >= S)
+      KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": set_of: " + what + " " + std::to_string(m) + " has set " +
+                                      std::to_string(set_of[m]) + " outside [-1, " + std::to_string(S) + ") (" + std::to_string(S) +
+                                      " sets are loaded: kocr_set_charsets)");
+  return KOCR_OK;
+}
+
 void lexicon_unload(kocr_ctx* ctx, int dropped_classes) {
   hipStreamSynchronize(ctx->stream);  // no launch still reads the words
   ctx->release(ctx->lex.d_words);
@@ -517,11 +539,11 @@ void lexicon_unload(kocr_ctx* ctx, int dropped_classes) {
   ctx->lex_top = 0;
 }
 
-int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm) {
+int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm, const CharMask& cm) {
   const float* d_lg = nullptr;
   KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
   if (M <= 0) return KOCR_OK;
-  return launch_ctc_beam(ctx, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, bm.beam_width, bm.top_paths, bm.d_labels, bm.d_logp);
+  return launch_ctc_beam(ctx, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, bm.beam_width, bm.top_paths, bm.d_labels, bm.d_logp, cm);
 }
 
 int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths) {

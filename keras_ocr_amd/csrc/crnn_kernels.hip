@@ -287,11 +287,43 @@ __global__ __launch_bounds__(256) void lstm16_kernel(const float* __restrict__ x
 // l, l + 64, ...; per-lane sums in ascending class order, then the xor butterfly.
 // Per-lane argmax over its classes (ascending class index: first maximum wins), then the wave-level reduction of
 // (value, index) pairs with lowest index on ties; every lane ends with the row's maximum and its first index.
-__device__ __forceinline__ void ctc_row_argmax(const float* __restrict__ row, int C, int lane, float& bv, int& bi) {
+//
+// Character sets ("Character sets"; CharMask in common.h): the MASKED instantiations of the decode
+// kernels read a row only through cm_at, which answers -inf for a class outside the crop's set -- the row fc_12 would have
+// written had it known the set -- so every rule behind it is the unmasked rule on that row.  The crop's mask words
+// (ceil(C / 32) of them, the blank's bit set) are loaded ONCE per crop into LDS (cm_load), never per frame from HBM.
+// MASKED = false compiles to the code without the feature: cm_at is row[c] and nothing else is generated.
+template <bool MASKED>
+__device__ __forceinline__ bool cm_allowed(const uint32_t* w, int c) {
+  if constexpr (MASKED) return (w[c >> 5] >> (c & 31)) & 1u;
+  return true;
+}
+template <bool MASKED>
+__device__ __forceinline__ float cm_at(const float* __restrict__ row, const uint32_t* w, int c) {
+  if constexpr (MASKED) return cm_allowed<true>(w, c) ? row[c] : -INFINITY;
+  return row[c];
+}
+// The mask words of crop m of the launch into w [ceil(C / 32)] (LDS), by one wave; set -1: every class.  The caller
+// synchronises before the first cm_at.
+__device__ __forceinline__ void cm_load(const uint32_t* __restrict__ bits, const int32_t* __restrict__ set_of, int uniform, int shift,
+                                        int first, int m, int C, int lane, uint32_t* w) {
+  const int nw = (C + 31) >> 5;
+  int set = uniform;
+  if (set_of) set = set_of[(first + m) >> shift];
+  for (int i = lane; i < nw; i += 64) {
+    uint32_t v = (i == nw - 1 && (C & 31)) ? (1u << (C & 31)) - 1u : ~0u;
+    if (set >= 0) v = bits[(size_t)set * nw + i];
+    w[i] = v;
+  }
+}
+
+template <bool MASKED = false>
+__device__ __forceinline__ void ctc_row_argmax(const float* __restrict__ row, int C, int lane, float& bv, int& bi,
+                                               const uint32_t* w = nullptr) {
   bv = -INFINITY;
   bi = 0x7fffffff;
   for (int c = lane; c < C; c += 64) {
-    const float v = row[c];
+    const float v = cm_at<MASKED>(row, w, c);
     if (v > bv) {
       bv = v;
       bi = c;
@@ -318,9 +350,10 @@ __device__ __forceinline__ float ctc_exp_diff(float v, float mx) {
   const float e = expf(d);
   return e == 0.f ? 0.f : fmaf(e, err, e);
 }
-__device__ __forceinline__ float ctc_row_expsum(const float* __restrict__ row, int C, int lane, float mx) {
+template <bool MASKED = false>
+__device__ __forceinline__ float ctc_row_expsum(const float* __restrict__ row, int C, int lane, float mx, const uint32_t* w = nullptr) {
   float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += ctc_exp_diff(row[c], mx);
+  for (int c = lane; c < C; c += 64) s += ctc_exp_diff(cm_at<MASKED>(row, w, c), mx);
   for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
   return s;
 }
@@ -328,10 +361,20 @@ __device__ __forceinline__ float ctc_softmax(float v, float mx, float s) { retur
 
 // logits: [M][T][C]; labels: [M][T-discard] (-1 padded); probs (nullable): [M][T-discard][C].
 // One wave per crop; lane l owns classes l, l+64, ... (any alphabet size).
+// MASKED: cm's sets (dynamic LDS: ceil(C / 32) words per wave of the block).
+template <bool MASKED>
 __global__ void ctc_kernel(const float* __restrict__ logits, int M, int T, int C, int discard, int* __restrict__ labels,
-                           float* __restrict__ probs) {
+                           float* __restrict__ probs, CharMask cm) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const uint32_t* w = nullptr;
+  if constexpr (MASKED) {
+    extern __shared__ uint32_t cm_words[];
+    uint32_t* mine = cm_words + (threadIdx.x >> 6) * ((C + 31) >> 5);
+    if (m < M) cm_load(cm.bits, cm.set_of, cm.uniform, cm.shift, cm.first, m, C, lane, mine);
+    __syncthreads();
+    w = mine;
+  }
   if (m >= M) return;
   const int To = T - discard;
   const int blank = C - 1;
@@ -340,10 +383,10 @@ __global__ void ctc_kernel(const float* __restrict__ logits, int M, int T, int C
     const float* row = logits + ((size_t)m * T + t + discard) * C;
     float bv;
     int bi;
-    ctc_row_argmax(row, C, lane, bv, bi);
+    ctc_row_argmax<MASKED>(row, C, lane, bv, bi, w);
     if (probs) {
-      const float s = ctc_row_expsum(row, C, lane, bv);
-      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = ctc_softmax(row[c], bv, s);
+      const float s = ctc_row_expsum<MASKED>(row, C, lane, bv, w);
+      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = ctc_softmax(cm_at<MASKED>(row, w, c), bv, s);
     }
     if (lane == 0) {
       if (bi != prev && bi != blank) labels[(size_t)m * To + k++] = bi;
@@ -378,9 +421,10 @@ __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
 // labels (global or LDS); la: [2][Sp] floats of LDS, Sp >= 2L + 1.  Returns the loss (every lane computes it from LDS).
 // Shared by ctc_loss_kernel and ctc_scores_kernel, so that the word log-probability of a decode is, bit for bit, minus the
 // loss kocr_crnn_ctc_loss gives for the same labels.
-template <bool LOGITS>
+// MASKED (LOGITS only): the rows are read through the crop's mask words w (cm_at).
+template <bool LOGITS, bool MASKED = false>
 __device__ __forceinline__ float ctc_loss_wave(const float* __restrict__ y0, int C, const int* l, int L, int Tm, float* la, int Sp,
-                                               int lane) {
+                                               int lane, const uint32_t* w = nullptr) {
   const int S = 2 * L + 1, blank = C - 1;
   for (int s = lane; s < 2 * Sp; s += 64) la[s] = -INFINITY;
   __syncthreads();
@@ -390,11 +434,11 @@ __device__ __forceinline__ float ctc_loss_wave(const float* __restrict__ y0, int
     float mx = 0.f, es = 1.f;
     if (LOGITS) {
       int bi;
-      ctc_row_argmax(row, C, lane, mx, bi);
-      es = ctc_row_expsum(row, C, lane, mx);
+      ctc_row_argmax<MASKED>(row, C, lane, mx, bi, w);
+      es = ctc_row_expsum<MASKED>(row, C, lane, mx, w);
     }
     float z = 0.f;
-    for (int c = lane; c < C; c += 64) z += (LOGITS ? ctc_softmax(row[c], mx, es) : row[c]) + CTC_EPS;
+    for (int c = lane; c < C; c += 64) z += (LOGITS ? ctc_softmax(cm_at<MASKED>(row, w, c), mx, es) : row[c]) + CTC_EPS;
     for (int o = 32; o; o >>= 1) z += __shfl_xor(z, o);
     const float logz = logf(z);
     const int lo = max(0, S - 2 * (Tm - t)), hi = min(S - 1, 2 * t + 1);
@@ -406,7 +450,7 @@ __device__ __forceinline__ float ctc_loss_wave(const float* __restrict__ y0, int
       float a = -INFINITY;
       if (s >= lo && s <= hi) {
         const int cls = (s & 1) ? l[s >> 1] : blank;
-        const float v = row[cls];
+        const float v = cm_at<MASKED>(row, w, cls);
         const float lq = logf((LOGITS ? ctc_softmax(v, mx, es) : v) + CTC_EPS) - logz;
         if (t == 0) {
           a = lq;  // s <= 1 here (hi = 1)
@@ -444,24 +488,33 @@ __global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ 
 // ctc_loss_wave<true> on the decoded label, all To frames: the label row (at most To ints) and its length stay in LDS beside
 // the two alpha rows, so neither the labels, the length nor the states take a trip through the host; a crop's logits
 // (T x C floats) come from cache the second time.  logw = -loss; chars: [M][To], 0 behind the decode.
+// MASKED: behind them the crop's ceil(C / 32) mask words.
+template <bool MASKED>
 __global__ __launch_bounds__(64) void ctc_scores_kernel(const float* __restrict__ logits, int T, int C, int discard,
                                                         int* __restrict__ labels, float* __restrict__ probs,
-                                                        float* __restrict__ logw, float* __restrict__ chars, int Sp) {
+                                                        float* __restrict__ logw, float* __restrict__ chars, int Sp, CharMask cm) {
   extern __shared__ float la[];  // [2][Sp] alpha rows, then int[To + 1]: the decoded label and its length
   int* dec = reinterpret_cast<int*>(la + 2 * Sp);
   const int m = blockIdx.x, lane = threadIdx.x;
   const int To = T - discard, blank = C - 1;
   const float* y0 = logits + ((size_t)m * T + discard) * C;
+  const uint32_t* w = nullptr;
+  if constexpr (MASKED) {
+    uint32_t* mine = reinterpret_cast<uint32_t*>(dec + To + 1);
+    cm_load(cm.bits, cm.set_of, cm.uniform, cm.shift, cm.first, m, C, lane, mine);
+    __syncthreads();
+    w = mine;
+  }
   int prev = -1, k = 0;
   float run = 0.f;  // lane 0: the score of label k - 1 so far
   for (int t = 0; t < To; ++t) {
     const float* row = y0 + (size_t)t * C;
     float bv;
     int bi;
-    ctc_row_argmax(row, C, lane, bv, bi);
-    const float s = ctc_row_expsum(row, C, lane, bv);
+    ctc_row_argmax<MASKED>(row, C, lane, bv, bi, w);
+    const float s = ctc_row_expsum<MASKED>(row, C, lane, bv, w);
     if (probs)
-      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = ctc_softmax(row[c], bv, s);
+      for (int c = lane; c < C; c += 64) probs[((size_t)m * To + t) * C + c] = ctc_softmax(cm_at<MASKED>(row, w, c), bv, s);
     if (lane == 0) {
       const float p = ctc_softmax(bv, bv, s);
       if (bi != prev && bi != blank) {
@@ -484,7 +537,7 @@ __global__ __launch_bounds__(64) void ctc_scores_kernel(const float* __restrict_
     }
   }
   __syncthreads();
-  const float loss = ctc_loss_wave<true>(y0, C, dec, dec[To], To, la, Sp, lane);
+  const float loss = ctc_loss_wave<true, MASKED>(y0, C, dec, dec[To], To, la, Sp, lane, w);
   if (lane == 0) logw[m] = -loss;
 }
 
@@ -551,11 +604,16 @@ __device__ __forceinline__ int beam_pick(const BeamBuf& b, int Ls, float v, int 
   return w;
 }
 
+// MASKED (character sets): a prefix is extended only by classes of the crop's set A -- E = min(B, |A|), the selection rounds
+// pass over the other classes, and the "all of them" shortcut holds only when |A| = C - 1; the mask words lie behind the
+// prefixes in LDS.
+template <bool MASKED>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logits, int T, int C, int discard, int B, int K,
-                                                      int* __restrict__ labels, float* __restrict__ logp, int Sp, int Ls) {
+                                                      int* __restrict__ labels, float* __restrict__ logp, int Sp, int Ls, CharMask cm) {
   extern __shared__ unsigned long long beam_lds[];
   const int m = blockIdx.x, lane = threadIdx.x;
-  const int To = T - discard, blank = C - 1, E = min(B, C - 1);
+  const int To = T - discard, blank = C - 1;
+  int E = min(B, C - 1);
   // both beams side by side, array by array: buffer i starts i * B (i * B * Ls for the prefixes) into each
   unsigned long long* keys = beam_lds;            // [2][B]
   unsigned long long* pkeys = keys + 2 * B;       // [2][B]
@@ -571,6 +629,17 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   int* pres = lasts + 2 * B;                      // [2][B][Ls]
   auto beam = [&](int i) { return BeamBuf{keys + i * B, pkeys + i * B, pbs + i * B, pnbs + i * B, lens + i * B, lasts + i * B, pres + i * B * Ls}; };
   const float* y0 = logits + ((size_t)m * T + discard) * C;
+  const uint32_t* w = nullptr;
+  if constexpr (MASKED) {
+    uint32_t* mine = reinterpret_cast<uint32_t*>(pres + 2 * B * Ls);  // [ceil(C / 32)]
+    cm_load(cm.bits, cm.set_of, cm.uniform, cm.shift, cm.first, m, C, lane, mine);
+    __syncthreads();
+    int na = 0;  // |A|: the set bits without the blank's
+    for (int i = lane; i < (C + 31) >> 5; i += 64) na += __popc(mine[i]);
+    for (int o = 32; o; o >>= 1) na += __shfl_xor(na, o);
+    E = min(B, na - 1);
+    w = mine;
+  }
 
   // the empty prefix: p_blank = 1
   if (lane == 0) {
@@ -590,10 +659,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
     float mx = 0.f, es = 1.f, logz = 0.f;
     if (!fin) {
       int bi;
-      ctc_row_argmax(row, C, lane, mx, bi);
-      es = ctc_row_expsum(row, C, lane, mx);
+      ctc_row_argmax<MASKED>(row, C, lane, mx, bi, w);
+      es = ctc_row_expsum<MASKED>(row, C, lane, mx, w);
       float z = 0.f;
-      for (int c = lane; c < C; c += 64) z += ctc_softmax(row[c], mx, es) + CTC_EPS;
+      for (int c = lane; c < C; c += 64) z += ctc_softmax(cm_at<MASKED>(row, w, c), mx, es) + CTC_EPS;
       for (int o = 32; o; o >>= 1) z += __shfl_xor(z, o);
       logz = logf(z);
       // the E extension classes: all of them, or E rounds of "the largest logit behind the last pick"
@@ -606,6 +675,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
           float bv = -INFINITY;
           int bc_ = BEAM_NONE;
           for (int c = lane; c < blank; c += 64) {
+            if (!cm_allowed<MASKED>(w, c)) continue;
             const float v = row[c];
             if ((v < pv || (v == pv && c > pc)) && (v > bv || (v == bv && c < bc_))) {
               bv = v;
@@ -625,7 +695,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
           if (lane == e) cls[e] = bc_;
         }
       }
-      if (lane < E) lqc[lane] = logf(ctc_softmax(row[cls[lane]], mx, es) + CTC_EPS) - logz;
+      if (lane < E) lqc[lane] = logf(ctc_softmax(cm_at<MASKED>(row, w, cls[lane]), mx, es) + CTC_EPS) - logz;
       __syncthreads();
     }
     // this lane's entry
@@ -665,8 +735,8 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
       __syncthreads();
       for (int j = 0; j < nb; ++j)
         if (par[j] == lane) taken |= 1ull << pe[j];
-      same_pb = tot + (logf(ctc_softmax(row[blank], mx, es) + CTC_EPS) - logz);
-      same_pnb = len > 0 ? pnb + (logf(ctc_softmax(row[last], mx, es) + CTC_EPS) - logz) : -INFINITY;
+      same_pb = tot + (logf(ctc_softmax(cm_at<MASKED>(row, w, blank), mx, es) + CTC_EPS) - logz);
+      same_pnb = len > 0 ? pnb + (logf(ctc_softmax(cm_at<MASKED>(row, w, last), mx, es) + CTC_EPS) - logz) : -INFINITY;
       same_pnb = ctc_lse2(same_pnb, extv);
     }
     const float same_tot = valid ? ctc_lse2(same_pb, same_pnb) : -INFINITY;
@@ -735,7 +805,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   const BeamBuf bo = beam(cur);
   float lp = -INFINITY;
   for (int k = 0; k < nb; ++k) {
-    const float loss = ctc_loss_wave<true>(y0, C, bo.pre + k * Ls, bo.len[k], To, la, Sp, lane);
+    const float loss = ctc_loss_wave<true, MASKED>(y0, C, bo.pre + k * Ls, bo.len[k], To, la, Sp, lane, w);
     if (lane == k) lp = -loss;
   }
   // the rows in the order of the rescored value (tie rule), the rest -1 / -inf
@@ -894,11 +964,20 @@ int launch_lstm(kocr_ctx* ctx, const float* d_xp, const float* d_Uf, const float
   return KOCR_OK;
 }
 
-int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs) {
+// The decode launchers take the batch's character sets `cm` (CharMask, common.h): on -> the MASKED instantiation, with
+// cm_bytes more LDS per wave for the crop's mask words; off -> the unmasked one.  The profiler row and the grid are the same.
+static size_t cm_bytes(const CharMask& cm, int C) { return cm.on() ? (size_t)((C + 31) / 32) * sizeof(uint32_t) : 0; }
+
+int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
+               const CharMask& cm) {
   if (M <= 0) return KOCR_OK;
   ProfScope ps(ctx, "ctc_greedy", 0, 4.0 * M * T * C);
-  hipLaunchKernelGGL(ctc_kernel, dim3((M + 3) / 4), dim3(256), 0, ctx->stream, d_logits, M, T, C, discard, d_labels,
-                     d_probs);
+  if (cm.on())
+    hipLaunchKernelGGL(ctc_kernel<true>, dim3((M + 3) / 4), dim3(256), 4 * cm_bytes(cm, C), ctx->stream, d_logits, M, T, C, discard,
+                       d_labels, d_probs, cm);
+  else
+    hipLaunchKernelGGL(ctc_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, ctx->stream, d_logits, M, T, C, discard, d_labels,
+                       d_probs, cm);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }
@@ -906,21 +985,25 @@ int launch_ctc(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int di
 // y: device [M][T][C] (logits: fc_12's output, frames t0 .. t0 + T_m - 1; else probabilities, t0 = 0); d_lab: device
 // ctc_scores_kernel: labels [M][T - discard], probs (nullable), logw [M], chars [M][T - discard]
 int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int* d_labels, float* d_probs,
-                      float* d_logw, float* d_chars) {
+                      float* d_logw, float* d_chars, const CharMask& cm) {
   if (M <= 0) return KOCR_OK;
   const int To = T - discard;
   const int Sp = (2 * To + 1 + 63) & ~63;
   const size_t lds = (size_t)2 * Sp * sizeof(float) + (size_t)(To + 1) * sizeof(int);
   ProfScope ps(ctx, "ctc_scores", 0, 4.0 * M * T * C * 4);
-  hipLaunchKernelGGL(ctc_scores_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_labels, d_probs, d_logw,
-                     d_chars, Sp);
+  if (cm.on())
+    hipLaunchKernelGGL(ctc_scores_kernel<true>, dim3(M), dim3(64), lds + cm_bytes(cm, C), ctx->stream, d_logits, T, C, discard, d_labels,
+                       d_probs, d_logw, d_chars, Sp, cm);
+  else
+    hipLaunchKernelGGL(ctc_scores_kernel<false>, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_labels, d_probs, d_logw,
+                       d_chars, Sp, cm);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }
 
 // ctc_beam_kernel: d_labels [M][top_paths][T - discard], d_logp [M][top_paths]
 int launch_ctc_beam(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, int beam_width, int top_paths,
-                    int* d_labels, float* d_logp) {
+                    int* d_labels, float* d_logp, const CharMask& cm) {
   if (M <= 0) return KOCR_OK;
   const int To = T - discard, B = beam_width;
   if (To < 1 || To > 63 || B < 1 || B > 64 || top_paths < 1 || top_paths > B || C < 1)
@@ -928,8 +1011,12 @@ int launch_ctc_beam(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, i
   const int Sp = (2 * To + 1 + 63) & ~63, Ls = To | 1;
   const size_t lds = (size_t)2 * B * (4 * Ls + 32) + (size_t)8 * Sp + 1024;
   ProfScope ps(ctx, "ctc_beam", 0, 4.0 * M * T * C * (2 + top_paths));
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, B, top_paths, d_labels, d_logp, Sp,
-                     Ls);
+  if (cm.on())
+    hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(M), dim3(64), lds + cm_bytes(cm, C), ctx->stream, d_logits, T, C, discard, B, top_paths,
+                       d_labels, d_logp, Sp, Ls, cm);
+  else
+    hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, B, top_paths, d_labels, d_logp,
+                       Sp, Ls, cm);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }
@@ -972,20 +1059,30 @@ int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, 
 // Nothing is shared between crops and every order of evaluation is fixed: a crop's values are the same bits in any batch.
 constexpr int LEX_BLOCK = 128;  // words (= lanes) per workgroup of lexicon_score_kernel, all of one crop
 
+// MASKED: the table of the masked rows (a masked class: logf(CTC_EPS) - logz, finite); the wave's one row takes the crop's
+// mask words through LDS once.  lexicon_score_kernel reads only this table and needs no mask of its own.
+template <bool MASKED>
 __global__ __launch_bounds__(64) void lexicon_logq_kernel(const float* __restrict__ logits, int T, int C, int discard,
-                                                          float* __restrict__ lq) {
+                                                          float* __restrict__ lq, CharMask cm) {
   const int To = T - discard, m = blockIdx.x / To, t = blockIdx.x % To, lane = threadIdx.x;
   const float* row = logits + ((size_t)m * T + discard + t) * C;
+  const uint32_t* w = nullptr;
+  if constexpr (MASKED) {
+    extern __shared__ uint32_t cm_words[];
+    cm_load(cm.bits, cm.set_of, cm.uniform, cm.shift, cm.first, m, C, lane, cm_words);
+    __syncthreads();
+    w = cm_words;
+  }
   float mx;
   int bi;
-  ctc_row_argmax(row, C, lane, mx, bi);
-  const float es = ctc_row_expsum(row, C, lane, mx);
+  ctc_row_argmax<MASKED>(row, C, lane, mx, bi, w);
+  const float es = ctc_row_expsum<MASKED>(row, C, lane, mx, w);
   float z = 0.f;
-  for (int c = lane; c < C; c += 64) z += ctc_softmax(row[c], mx, es) + CTC_EPS;
+  for (int c = lane; c < C; c += 64) z += ctc_softmax(cm_at<MASKED>(row, w, c), mx, es) + CTC_EPS;
   for (int o = 32; o; o >>= 1) z += __shfl_xor(z, o);
   const float logz = logf(z);
   float* out = lq + ((size_t)m * To + t) * C;
-  for (int c = lane; c < C; c += 64) out[c] = logf(ctc_softmax(row[c], mx, es) + CTC_EPS) - logz;
+  for (int c = lane; c < C; c += 64) out[c] = logf(ctc_softmax(cm_at<MASKED>(row, w, c), mx, es) + CTC_EPS) - logz;
 }
 
 // lq: [Mc][To][C]; words: [V][wstride] / lens: [V] in the caller's order; order: [V] sorted position -> caller index;
@@ -1046,15 +1143,23 @@ __global__ __launch_bounds__(LEX_BLOCK) void lexicon_score_kernel(const float* _
 // higher value first, then the smaller index; -inf is never picked), then ctc_loss_wave<true> on each pick -- log_prob is,
 // bit for bit, -kocr_crnn_ctc_loss of the crop with that word -- and the rows in the order of the rescored value (same tie
 // rule); behind them index -1, log_prob -inf.  LDS: the loss's la [2][Sp], then val [64], idx [64].
+// MASKED: the rescoring reads the rows through the crop's mask words, kept behind idx.
+template <bool MASKED>
 __global__ __launch_bounds__(64) void lexicon_select_kernel(const float* __restrict__ logits, int T, int C, int discard,
                                                             const float* __restrict__ values, int V, const int* __restrict__ words,
                                                             int wstride, const int* __restrict__ lens, int K,
-                                                            int* __restrict__ index, float* __restrict__ logp, int Sp) {
+                                                            int* __restrict__ index, float* __restrict__ logp, int Sp, CharMask cm) {
   extern __shared__ float la[];
   float* val = la + 2 * Sp;
   int* idx = reinterpret_cast<int*>(val + 64);
   const int m = blockIdx.x, lane = threadIdx.x, To = T - discard;
   const float* y0 = logits + ((size_t)m * T + discard) * C;
+  const uint32_t* w = nullptr;
+  if constexpr (MASKED) {
+    uint32_t* mine = reinterpret_cast<uint32_t*>(idx + 64);
+    cm_load(cm.bits, cm.set_of, cm.uniform, cm.shift, cm.first, m, C, lane, mine);  // the __syncthreads() behind the selection rounds orders it before the first read
+    w = mine;
+  }
   const float* v = values + (size_t)m * V;
   float pv = INFINITY;
   int pi = -1, n = 0;
@@ -1085,11 +1190,11 @@ __global__ __launch_bounds__(64) void lexicon_select_kernel(const float* __restr
   float lp = -INFINITY;
   int mine = -1;
   for (int k = 0; k < n; ++k) {
-    const int w = idx[k];
-    const float loss = ctc_loss_wave<true>(y0, C, words + (size_t)w * wstride, lens[w], To, la, Sp, lane);
+    const int wd = idx[k];
+    const float loss = ctc_loss_wave<true, MASKED>(y0, C, words + (size_t)wd * wstride, lens[wd], To, la, Sp, lane, w);
     if (lane == k) {
       lp = -loss;
-      mine = w;
+      mine = wd;
     }
   }
   __syncthreads();
@@ -1111,10 +1216,14 @@ __global__ __launch_bounds__(64) void lexicon_select_kernel(const float* __restr
 }
 
 // d_lq: [M][T - discard][C] scratch
-int launch_lexicon_logq(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, float* d_lq) {
+int launch_lexicon_logq(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, float* d_lq, const CharMask& cm) {
   if (M <= 0) return KOCR_OK;
   ProfScope ps(ctx, "lexicon_logq", 0, 4.0 * M * (T - discard) * C * 2);
-  hipLaunchKernelGGL(lexicon_logq_kernel, dim3(M * (T - discard)), dim3(64), 0, ctx->stream, d_logits, T, C, discard, d_lq);
+  if (cm.on())
+    hipLaunchKernelGGL(lexicon_logq_kernel<true>, dim3(M * (T - discard)), dim3(64), cm_bytes(cm, C), ctx->stream, d_logits, T, C, discard,
+                       d_lq, cm);
+  else
+    hipLaunchKernelGGL(lexicon_logq_kernel<false>, dim3(M * (T - discard)), dim3(64), 0, ctx->stream, d_logits, T, C, discard, d_lq, cm);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }
@@ -1142,14 +1251,19 @@ int launch_lexicon_score(kocr_ctx* ctx, const float* d_lq, int M, int To, int C,
 
 // d_index / d_logp: [M][top_words]
 int launch_lexicon_select(kocr_ctx* ctx, const float* d_logits, int M, int T, int C, int discard, const float* d_values, int V,
-                          const int* d_words, int wstride, const int* d_lens, int top_words, int* d_index, float* d_logp) {
+                          const int* d_words, int wstride, const int* d_lens, int top_words, int* d_index, float* d_logp,
+                          const CharMask& cm) {
   if (M <= 0) return KOCR_OK;
   if (top_words < 1 || top_words > 64 || V < 1) KOCR_FAIL(ctx, KOCR_EINVAL, "lexicon_select: bad sizes");
   const int Sp = (2 * KOCR_LEXICON_MAX_WORD + 1 + 63) & ~63;
   const size_t lds = (size_t)2 * Sp * sizeof(float) + 64 * sizeof(float) + 64 * sizeof(int);
   ProfScope ps(ctx, "lexicon_select", 0, 4.0 * M * V * top_words);
-  hipLaunchKernelGGL(lexicon_select_kernel, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_values, V, d_words,
-                     wstride, d_lens, top_words, d_index, d_logp, Sp);
+  if (cm.on())
+    hipLaunchKernelGGL(lexicon_select_kernel<true>, dim3(M), dim3(64), lds + cm_bytes(cm, C), ctx->stream, d_logits, T, C, discard,
+                       d_values, V, d_words, wstride, d_lens, top_words, d_index, d_logp, Sp, cm);
+  else
+    hipLaunchKernelGGL(lexicon_select_kernel<false>, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_values, V, d_words,
+                       wstride, d_lens, top_words, d_index, d_logp, Sp, cm);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }

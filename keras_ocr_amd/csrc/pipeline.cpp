@@ -76,6 +76,8 @@ struct OrientRun {
   int32_t* turns2 = nullptr;  // [2M]
   float* quads2 = nullptr;    // [2M][8]
   OrientRun(kocr_ctx* ctx, long M) : rec(ctx, 2 * M, true) { won.words = M; }
+  // a per-box list of character sets (device, [M]): both candidates of box m are crops 2 m and 2 m + 1
+  void set_charsets(kocr_ctx* ctx, const int32_t* d_set_of) { rec.cm = ctx->charmask(d_set_of, 1); }
   template <class F> int each(F f) {
     const size_t m = (size_t)won.words, lw = (size_t)rec.LW, i4 = sizeof(int32_t), f4 = sizeof(float);
     KOCR_TRY(f(prm, 2 * m * sizeof(WarpParam)));
@@ -114,9 +116,8 @@ bool orient_args_ok(int mode, double tall_ratio, bool allow_off) {
 }
 
 // kocr_recognize_boxes with the switch on: the set-up on the host with the function the device runs (as prepare_box_warps)
-int recognize_boxes_oriented(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes, const int32_t* counts,
-                             int32_t* labels, int on_device) {
-  const char* fn = "kocr_recognize_boxes";
+int recognize_boxes_oriented(kocr_ctx* ctx, const char* fn, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                             const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of) {
   if (const char* why = orient_refusal(ctx, false)) KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + why);
   long M = 0;
   for (int i = 0; i < N; ++i) {
@@ -144,10 +145,15 @@ int recognize_boxes_oriented(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H
   const size_t ib = (size_t)N * H * W * 3;
   OrientRun r(ctx, M);
   Staging st{ctx, ctx->io, fn, on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {staging_bytes(r)}));
+  KOCR_TRY(st.reserve(0, {ib}, {staging_bytes(r), set_of ? (size_t)M * sizeof(int32_t) : 0}));
   const uint8_t* d_img;
   KOCR_TRY(staging_take(st, r));
   KOCR_TRY(st.in(img_rgb, ib, d_img));
+  if (set_of) {  // the caller's array outlives the copy: the call synchronises before it returns
+    const int32_t* d_set;
+    KOCR_TRY(st.upload(set_of, (size_t)M * sizeof(int32_t), d_set));
+    r.set_charsets(ctx, d_set);
+  }
   KOCR_TRY(st.put(r.prm, (const WarpParam*)prm.data(), prm.size() * sizeof(WarpParam)));
   KOCR_TRY(st.put(r.turns2, (const int32_t*)turns.data(), turns.size() * sizeof(int32_t)));
   KOCR_TRY(st.put(r.quads2, (const float*)quads.data(), quads.size() * sizeof(float)));
@@ -160,21 +166,28 @@ int recognize_boxes_oriented(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H
 }  // namespace
 
 // Recognizer.recognize_from_boxes' device half in one call: crops are warped and recognised without
-// leaving HBM.  All N images share one size; boxes/counts/labels are HOST buffers.
-extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
-                                    const int32_t* counts, int32_t* labels, int on_device) {
-  if (!ctx) return KOCR_EINVAL;
-  if (N < 0 || (N > 0 && (!img_rgb || !counts))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes: null buffer");
-  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_recognize_boxes: call kocr_load_crnn first");
-  if (ctx->orient_mode != KOCR_ORIENT_OFF) return recognize_boxes_oriented(ctx, img_rgb, N, H, W, boxes, counts, labels, on_device);
+// leaving HBM.  All N images share one size; boxes/counts/labels are HOST buffers.  set_of (HOST, nullable; `fn` =
+// kocr_recognize_boxes_charsets): one character set per box in place of the context's switch, checked before any launch.
+static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                                const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of) {
+  const std::string f(fn);
+  if (N < 0 || (N > 0 && (!img_rgb || !counts))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+  if (set_of) {
+    long n = 0;
+    for (int i = 0; i < N; ++i) n += std::max<int32_t>(counts[i], 0);
+    KOCR_TRY(charsets_validate(ctx, fn, set_of, n, "box"));
+  }
+  if (ctx->orient_mode != KOCR_ORIENT_OFF)
+    return recognize_boxes_oriented(ctx, fn, img_rgb, N, H, W, boxes, counts, labels, on_device, set_of);
   std::vector<WarpParam> prm;
-  const long M = prepare_box_warps(ctx, "kocr_recognize_boxes", N, boxes, counts, labels, CRNN_CROP_H, CRNN_CROP_W, prm);
+  const long M = prepare_box_warps(ctx, fn, N, boxes, counts, labels, CRNN_CROP_H, CRNN_CROP_W, prm);
   if (M <= 0) return (int)M;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), pb = (size_t)M * sizeof(WarpParam);
   RecStage rec(ctx, M);
-  Staging st{ctx, ctx->io, "kocr_recognize_boxes", on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, rec.bytes()}));
+  Staging st{ctx, ctx->io, fn, on_device != 0};
+  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, rec.bytes(), set_of ? (size_t)M * sizeof(int32_t) : 0}));
   WarpParam* d_prm;
   float* d_crops;
   const uint8_t* d_img;
@@ -183,12 +196,30 @@ extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N
   KOCR_TRY(rec.take(st));
   KOCR_TRY(st.in(img_rgb, ib, d_img));
   KOCR_TRY(st.put(d_prm, (const WarpParam*)prm.data(), pb));
+  if (set_of) {  // the caller's array outlives the copy: the call synchronises before it returns
+    const int32_t* d_set;
+    KOCR_TRY(st.upload(set_of, (size_t)M * sizeof(int32_t), d_set));
+    rec.cm = ctx->charmask(d_set, 0);
+  }
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   KOCR_TRY(rec.run(d_crops));
   KOCR_TRY(st.download(labels, (const int32_t*)rec.lab, (size_t)M * rec.LW * sizeof(int32_t)));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   rec.keep();
   return KOCR_OK;
+}
+
+extern "C" int kocr_recognize_boxes(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                                    const int32_t* counts, int32_t* labels, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  return recognize_boxes_call(ctx, "kocr_recognize_boxes", img_rgb, N, H, W, boxes, counts, labels, on_device, nullptr);
+}
+
+extern "C" int kocr_recognize_boxes_charsets(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                                             const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of) {
+  if (!ctx) return KOCR_EINVAL;
+  if (N > 0 && !set_of) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes_charsets: null buffer");
+  return recognize_boxes_call(ctx, "kocr_recognize_boxes_charsets", img_rgb, N, H, W, boxes, counts, labels, on_device, set_of);
 }
 
 namespace {

@@ -1,7 +1,9 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
+import contextlib
+
 import numpy as np
 
-from . import _lib, detection, evaluation as _evaluation, layout as _layout, lexicon as _lexicon, recognition, scores as _scores, tools
+from . import _lib, charsets as _charsets, detection, evaluation as _evaluation, layout as _layout, lexicon as _lexicon, recognition, scores as _scores, tools
 from .results import Results
 
 
@@ -35,6 +37,22 @@ def orientation_of(recognition_kwargs, char_boxes=None):
     _lib.refuse_orientation_with(kwargs["orientation"], beam_width=kwargs.get("beam_width"), lexicon_top=kwargs.get("lexicon_top"),
                                  char_boxes=char_boxes)
     return kwargs["orientation"], _lib.orientation_args(kwargs["orientation"], kwargs.get("tall_ratio", 1.5))[1]
+
+
+def charset_scope(recognizer, recognition_kwargs):
+    """The scope in which the recogniser's context decodes under ``recognition_kwargs["charset"]`` (a name loaded with
+    ``recognizer.set_charsets``; DESIGN.md section 4, "Character sets"); no ``charset``: a scope that does nothing.
+    ValueError listing the loaded names for an unknown one; TypeError for a recogniser without character sets."""
+    name = (recognition_kwargs or {}).get("charset")
+    if name is None:
+        return contextlib.nullcontext()
+    if not hasattr(recognizer, "_charset_names") or getattr(recognizer, "_ctx", None) is None:
+        raise TypeError(f"charset: the recognizer ({type(recognizer).__name__}) has no character sets (it is not libkocr-backed)")
+    if not isinstance(name, str):
+        raise ValueError(f"charset in recognition_kwargs is one name for every box, got {name!r} (per-box sets: "
+                         "Recognizer.recognize_from_boxes)")
+    index = _charsets.index_of(recognizer._charset_names(name), name)  # pylint: disable=protected-access
+    return recognizer._ctx._charset_scope(index)  # pylint: disable=protected-access
 
 
 def _one_text_per_word(recognition_kwargs, why):
@@ -112,7 +130,11 @@ class Pipeline:
         the winner's and each ``box`` the word's box [tl, tr, br, bl] of the text as read (the detector's rectangle, its corners
         renamed), so ``box[0] -> box[1]`` is the reading direction.  Not together with ``beam_width``, ``lexicon_top`` or
         character boxes (ValueError); uint8 images only (NotImplementedError).  ``recognize_with_scores``, ``recognize_lines``,
-        ``evaluate``, ``recognize_padded`` and ``recognize_raw`` take it in the same way."""
+        ``evaluate``, ``recognize_padded`` and ``recognize_raw`` take it in the same way.
+
+        ``recognition_kwargs={"charset": name}`` (section 4, "Character sets"; after
+        ``recognizer.set_charsets({name: characters})``): every box is decoded under that set, whatever else is asked for;
+        the boxes are the same bits.  ValueError listing the loaded names for an unknown one."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs)
 
     def recognize_with_scores(self, images, detection_kwargs=None, recognition_kwargs=None):
@@ -192,7 +214,12 @@ class Pipeline:
 
     def _recognize(self, images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores=False, char_boxes=None):
         """recognize_raw's ``Results``, over one of three routes: the fused one, and the stage-wise one for images that are
-        not uint8 or for foreign stages"""
+        not uint8 or for foreign stages.  ``recognition_kwargs={"charset": name}``: every decode of the call runs under that
+        character set of the recogniser (``charset_scope``); the boxes are the same either way."""
+        with charset_scope(self.recognizer, recognition_kwargs):
+            return self._recognize_routes(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
+
+    def _recognize_routes(self, images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes):
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
@@ -271,9 +298,13 @@ class Pipeline:
         everything behind them is recognize()'s own path.  Returns what recognize() returns, boxes in input-image pixels; with
         ``return_scores`` the tuples are ``recognize_with_scores``', with ``char_boxes`` (True or a dict of rule parameters)
         ``recognize_characters``' (not both).  ``recognition_kwargs`` takes ``beam_width`` / ``top_paths``, ``lexicon_top`` and
-        ``orientation`` / ``tall_ratio`` as recognize() does, with the same refusals.  uint8 images only (NotImplementedError);
-        detector and recogniser must share one ``Context`` (TypeError).  A halo narrower than the detector's receptive field
-        does not reproduce a whole-page pass exactly: see DESIGN.md."""
+        ``orientation`` / ``tall_ratio`` and ``charset`` as recognize() does, with the same refusals.  uint8 images only
+        (NotImplementedError); detector and recogniser must share one ``Context`` (TypeError).  A halo narrower than the
+        detector's receptive field does not reproduce a whole-page pass exactly: see DESIGN.md."""
+        with charset_scope(self.recognizer, recognition_kwargs):
+            return self._recognize_tiled(images, tile, overlap, scale, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
+
+    def _recognize_tiled(self, images, tile, overlap, scale, detection_kwargs, recognition_kwargs, return_scores, char_boxes):
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]

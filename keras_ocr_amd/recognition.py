@@ -1,11 +1,12 @@
 """Host-side mirror of ``keras_ocr.recognition.Recognizer`` (reference
 ``keras_ocr/recognition.py:353-545``).  The Keras models are replaced by libkocr."""
+import contextlib
 import string
 import typing
 
 import numpy as np
 
-from . import _lib, layout as _layout, lexicon as _lexicon, scores as _scores, tools, weights as _weights
+from . import _lib, charsets as _charsets, layout as _layout, lexicon as _lexicon, scores as _scores, tools, weights as _weights
 from .results import Results
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
@@ -281,6 +282,33 @@ class Recognizer:
         self.backbone = _Backbone(self._ctx)
         self.training_model = _TrainingModel(self._ctx)
         self.lexicon = None
+        self.charsets = None
+
+    def set_charsets(self, charsets, lowercase=False):
+        """The character sets for ``charset=`` ("Character sets"): a mapping name -> characters, e.g.
+        ``{"digits": "0123456789"}``; the table is loaded into the context once and stays there like a lexicon, and
+        ``Recognizer.charsets`` holds the names.  ``None`` unloads.  ``lowercase``: lower-case the characters first.
+        ValueError naming the set and the character for one outside the alphabet, for an empty set and for more than 256."""
+        if charsets is None:
+            self._ctx.set_charsets(None)
+            self.charsets = None
+            return
+        names, allowed = _charsets.table(charsets, self.alphabet, lowercase=lowercase)
+        self._ctx.set_charsets(allowed)
+        self.charsets = names
+
+    def _charset_names(self, charset):
+        """The loaded names for a ``charset=`` argument (None when none is asked for); ValueError without a loaded table"""
+        if charset is None:
+            return None
+        if self.charsets is None or self._ctx.charset_count() != len(self.charsets):
+            raise ValueError("charset needs loaded character sets: call Recognizer.set_charsets({name: characters}) first (the "
+                             "sets are unloaded when a recogniser of another class count is loaded on their context)")
+        return self.charsets
+
+    def _charset_scope(self, index):
+        """The context's character-set switch for one call (None: no call at all on the context)"""
+        return contextlib.nullcontext() if index is None else self._ctx._charset_scope(index)  # pylint: disable=protected-access
 
     def set_lexicon(self, words, lowercase=False):
         """The word list for ``lexicon_top=`` ("Lexicon"): an iterable of strings or a
@@ -342,7 +370,7 @@ class Recognizer:
         return [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
                 for i in range(m)]
 
-    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None):
+    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None, charset=None):
         """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string; ``return_scores=True``:
         ``(text, score)``, a ``scores.Score`` whose ``detection`` is None.
 
@@ -353,9 +381,14 @@ class Recognizer:
 
         ``lexicon_top=K`` (1..64, after ``set_lexicon``): instead of the string, a list of up to K ``(word, log_prob)``, the
         lexicon's words of the highest exact CTC log-probability given the crop, best first (DESIGN.md section 4,
-        "Lexicon").  Not together with ``beam_width`` (ValueError)."""
+        "Lexicon").  Not together with ``beam_width`` (ValueError).
+
+        ``charset=name`` (after ``set_charsets``; default None: unconstrained): the crop is decoded as if the recogniser could
+        only answer the characters of that set -- the text, its scores, the beam alternatives and the lexicon values all
+        follow ("Character sets").  ValueError listing the loaded names for an unknown one."""
         lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
+        charset = _charsets.index_of(self._charset_names(charset), charset)
         image = tools.read_and_fit(filepath_or_array=image, width=200, height=31, cval=0)
         if image.shape[-1] == 3:
             # gray conversion on the GPU: warp the full 31x200 rectangle onto itself (identity map)
@@ -363,7 +396,8 @@ class Recognizer:
             crops = self._ctx.warp_crops(image[np.newaxis], [box[np.newaxis]], 31, 200)
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
-        return self._words(self._recognize_crops(crops, return_scores, beam, lexicon_top))[0]
+        with self._charset_scope(charset):
+            return self._words(self._recognize_crops(crops, return_scores, beam, lexicon_top))[0]
 
     def _recognize_crops(self, crops, return_scores, beam, lexicon_top):
         """The ``Results`` of crops on the host: the decode [with its scores], and the alternatives or matches asked for"""
@@ -380,7 +414,8 @@ class Recognizer:
         return out
 
     def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None,
-                             orientation=None, tall_ratio=1.5, return_orientation=False, **kwargs) -> typing.List[typing.List[str]]:
+                             orientation=None, tall_ratio=1.5, return_orientation=False, charset=None,
+                             **kwargs) -> typing.List[typing.List[str]]:
         """Recognizer.recognize_from_boxes (recognition.py:491-537); ``return_scores=True``: per image a list of
         ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None.  ``beam_width`` / ``top_paths``: as
         ``recognize`` -- every text becomes its list of ``(text, log_prob)`` alternatives; ``lexicon_top``: as ``recognize`` --
@@ -391,8 +426,21 @@ class Recognizer:
         height is at least ``tall_ratio`` times its width -- and each text (and score) is that of the reading with the larger
         exact CTC log-probability, an empty reading losing to a non-empty one.  ``return_orientation=True`` (needs
         ``orientation``): every word becomes ``(text[, score], layout.Orientation(turns, box, log_words))``.  Not together
-        with ``beam_width`` or ``lexicon_top`` (ValueError naming both); uint8 images only (NotImplementedError)."""
+        with ``beam_width`` or ``lexicon_top`` (ValueError naming both); uint8 images only (NotImplementedError).
+
+        ``charset`` (after ``set_charsets``; DESIGN.md section 4, "Character sets"): a name -- every box is decoded under
+        that set -- or per image a list with one name or None (unconstrained) per box: an amount and a name on one page.
+        It combines with every other argument; with ``orientation`` both readings of a box use its set.  Per-box lists
+        need uint8 images (NotImplementedError)."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
+        uniform_set, set_of = _charsets.per_box(self._charset_names(charset), charset, box_groups)
+        with self._charset_scope(uniform_set):
+            return self._recognize_from_boxes(images, box_groups, return_scores, beam_width, top_paths, lexicon_top, orientation,
+                                              tall_ratio, return_orientation, set_of)
+
+    def _recognize_from_boxes(self, images, box_groups, return_scores, beam_width, top_paths, lexicon_top, orientation, tall_ratio,
+                              return_orientation, set_of):
+        """recognize_from_boxes under the context's character-set switch; set_of: the flat per-box set indices, or None"""
         lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         _lib.refuse_orientation_with(orientation, beam_width=beam_width, lexicon_top=lexicon_top)
@@ -411,6 +459,8 @@ class Recognizer:
             start = 0 if not start_end else start_end[-1][1]
             start_end.append((start, start + len(boxes)))
         images = [np.asarray(image) for image in images]
+        if set_of is not None and any(im.dtype != np.uint8 for im in images):
+            raise NotImplementedError("charset: per-box character sets need uint8 images (the float crop path decodes plain crops)")
         if any(im.dtype != np.uint8 for im in images):
             # float images (recognition.py:507-526 works in the image's own type): gray conversion and the crop warp in
             # float ON THE GPU (kocr_warp_crops_f32, round 5), the division by 255 of :524, the recogniser
@@ -422,11 +472,12 @@ class Recognizer:
             out = self._recognize_crops(np.concatenate(crops) / np.float32(255), return_scores, beam, lexicon_top)
         elif len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top, oriented)  # pylint: disable=protected-access
+            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top, oriented, set_of)  # pylint: disable=protected-access
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top, oriented)  # pylint: disable=protected-access
-                                       for image, boxes in zip(images, box_groups) if len(boxes)])
+            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top, oriented,  # pylint: disable=protected-access
+                                                                  None if set_of is None else set_of[start:end])
+                                       for image, boxes, (start, end) in zip(images, box_groups, start_end) if len(boxes)])
         words = self._words(out)
         if return_orientation:
             how = _layout.orientations_of(*out.orientation)
