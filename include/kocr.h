@@ -669,6 +669,50 @@ int kocr_get_charset(const kocr_ctx* ctx, int* set);
 int kocr_recognize_boxes_charsets(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
                                   const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of);
 
+/* ---- patterns: decode a crop under a regular expression ("Patterns") -----------------------------------
+ * A pattern is a trimmed deterministic automaton over the non-blank classes [0, classes - 2] of the loaded recogniser: start
+ * state 0, delta[s][c] the next state or -1, accept[s]; every state reachable from 0 and able to reach an accepting one.  A
+ * crop decoded under it gets the best single CTC alignment of its crnn_label_width() frames whose collapsed text the
+ * automaton accepts -- a Viterbi pass over (frame x state x last label) on the loss's float32 log q_t, exact, with a fixed
+ * tie rule -- as labels [LW] (-1 padded), log_path (that alignment's log-probability) and log_prob, the CTC
+ * log-probability of the text over ALL its alignments: bit for bit -kocr_crnn_ctc_loss of the row, as for the beam and the
+ * lexicon.  When the greedy text satisfies the pattern it is the greedy text.  Where no accepted text fits the frames, and
+ * for a crop without a pattern (-1), the row is all -1 and both values are -inf.  The decode itself is untouched: the
+ * pattern launches run behind it on the same logits (never masked by a character set).
+ * kocr_set_patterns: P automata, pattern p with n_states[p] states; delta = the patterns' rows one after another, each of
+ * classes - 1 int32; accept = one byte per row (HOST).  classes must equal kocr_crnn_classes() (KOCR_ENOWEIGHTS without a
+ * recogniser); 0 <= P <= KOCR_PATTERNS_MAX, 1 <= n_states <= KOCR_PATTERN_MAX_STATES, at most KOCR_PATTERN_MAX_NODES pairs
+ * (state, class entering it) per pattern, every move in [-1, n_states), trimmed (so the language is not empty): else
+ * KOCR_EINVAL naming the argument, the pattern and the count.  The tables stay resident on the context like a lexicon.  P = 0
+ * unloads and switches off; a call replaces the previous tables (and switches off); a refused one changes nothing.  Loading
+ * another recogniser with a DIFFERENT class count unloads them and switches off.  kocr_pattern_count: P (0: none).
+ * kocr_set_pattern(ctx, index): -1 (the default) is off -- the calls launch what they always launched and return the same
+ * bits; index in [0, P) makes the recogniser stage of kocr_recognize_boxes and kocr_pipeline[_tiled] also run the pattern
+ * launches on every batch's logits and leave the rows resident beside the label rows for kocr_recognition_patterns (the
+ * resident-result protocol of kocr_recognition_lexicon).  Scores, the beam and the lexicon match run as before beside it;
+ * orientation and an active character set (kocr_set_charset) are KOCR_EINVAL.
+ * kocr_crnn_pattern: the forward to the logits, then the pattern launches alone; pattern_of int32 [M] (HOST, each in
+ * [-1, P), else KOCR_EINVAL naming the crop) or NULL for the context's switch; crops and results as kocr_crnn_lexicon's.
+ * kocr_recognize_boxes_patterns: kocr_recognize_boxes with one pattern per box, pattern_of int32 [sum of counts] (HOST),
+ * each in [-1, P) else KOCR_EINVAL naming the box, before any launch; the context's switch is not consulted.
+ * kocr_crnn_decode_logits_patterns (development): the pattern launches on the caller's logits (HOST, M <= 1024), as
+ * kocr_crnn_decode_logits.  The back-pointers of a large pattern leave LDS for workspace scratch, a crop's table lies there
+ * too, and both are chunked under the byte budget of kocr_set_lexicon_scratch; no result depends on the chunking. */
+#define KOCR_PATTERNS_MAX 64
+#define KOCR_PATTERN_MAX_STATES 256
+#define KOCR_PATTERN_MAX_NODES 4096
+int kocr_set_patterns(kocr_ctx* ctx, const int32_t* delta, const uint8_t* accept, const int32_t* n_states, int P, int classes);
+int kocr_pattern_count(const kocr_ctx* ctx);
+int kocr_set_pattern(kocr_ctx* ctx, int index);
+int kocr_get_pattern(const kocr_ctx* ctx, int* index);
+int kocr_recognition_patterns(kocr_ctx* ctx, int32_t* labels, float* log_path, float* log_prob, int max_crops, int32_t* n_crops);
+int kocr_crnn_pattern(kocr_ctx* ctx, const float* crops, int M, const int32_t* pattern_of, int32_t* labels, float* log_path,
+                      float* log_prob, int on_device);
+int kocr_recognize_boxes_patterns(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                                  const int32_t* counts, int32_t* labels, int on_device, const int32_t* pattern_of);
+int kocr_crnn_decode_logits_patterns(kocr_ctx* ctx, const float* logits, int M, const int32_t* pattern_of, int32_t* labels,
+                                     float* log_path, float* log_prob);
+
 /* ---- orientation: read each box both ways and keep the better reading ("Orientation") ----------------
  * The reference's get_rotated_box always names the upper of the two leftmost corners tl, so an upside-down word is warped
  * upside down and a vertical one into a sliver.  With the switch on, every box is read in two orientations: its ordered box

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .results import Results, empty_beam, empty_lexicon, empty_orientation, empty_scores
+from .results import Results, empty_beam, empty_lexicon, empty_orientation, empty_pattern, empty_scores
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkocr.so")
@@ -91,6 +91,14 @@ def load_library():
         "kocr_get_charset": (ci, [vp, vp]),
         "kocr_recognize_boxes_charsets": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
         "kocr_crnn_decode_logits_charsets": (ci, [vp, vp, ci, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+        "kocr_set_patterns": (ci, [vp, vp, vp, vp, ci, ci]),
+        "kocr_pattern_count": (ci, [vp]),
+        "kocr_set_pattern": (ci, [vp, ci]),
+        "kocr_get_pattern": (ci, [vp, vp]),
+        "kocr_recognition_patterns": (ci, [vp, vp, vp, vp, ci, vp]),
+        "kocr_crnn_pattern": (ci, [vp, vp, ci, vp, vp, vp, vp, ci]),
+        "kocr_recognize_boxes_patterns": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, ci, vp]),
+        "kocr_crnn_decode_logits_patterns": (ci, [vp, vp, ci, vp, vp, vp, vp]),
         "kocr_set_orientation": (ci, [vp, ci, ctypes.c_double]),
         "kocr_get_orientation": (ci, [vp, vp, vp]),
         "kocr_recognition_orientation": (ci, [vp, vp, vp, vp, ci, vp]),
@@ -741,6 +749,94 @@ class Context:
             raise ValueError(f"set_of must hold one character set per {what}: {m}, got {s.shape[0]}")
         return s
 
+    # -- patterns (include/kocr.h: "Patterns") ---------------------------------------------------------------------------
+    def set_patterns(self, delta=None, accept=None, n_states=None):
+        """Load the automata (kocr_set_patterns; ``patterns.Patterns.tables()``): delta (sum S, classes - 1) int32, accept
+        (sum S,) of 0 / 1, n_states (P,); they stay resident like a lexicon.  ``set_patterns(None)`` unloads and switches off.
+        ValueError naming the pattern for a refused table."""
+        if delta is None or len(delta) == 0:
+            self._check(self._lib.kocr_set_patterns(self._h, None, None, None, 0, 0), value_error=True)
+            return
+        d = np.ascontiguousarray(delta, dtype=np.int32)
+        a = np.ascontiguousarray(np.asarray(accept) != 0, dtype=np.uint8).reshape(-1)
+        n = np.ascontiguousarray(n_states, dtype=np.int32).reshape(-1)
+        if d.ndim != 2 or len(a) != len(d) or int(n.sum()) != len(d):
+            raise ValueError(f"patterns: delta {d.shape}, accept {a.shape} and n_states (sum {int(n.sum())}) do not describe the same states")
+        self._check(self._lib.kocr_set_patterns(self._h, _ptr(d), _ptr(a), _ptr(n), len(n), d.shape[1] + 1), value_error=True)
+
+    def pattern_count(self):
+        return self._check(self._lib.kocr_pattern_count(self._h))
+
+    def set_pattern(self, index=-1):
+        """The pattern every crop of recognize_boxes / pipeline is also decoded under (kocr_set_pattern); -1 = off."""
+        self._check(self._lib.kocr_set_pattern(self._h, int(index)), value_error=True)
+
+    def get_pattern(self):
+        k = ctypes.c_int(0)
+        self._check(self._lib.kocr_get_pattern(self._h, ctypes.byref(k)))
+        return k.value
+
+    def _pattern_scope(self, index):
+        """The pattern for one call; None: the context's own setting.  Tables unloaded meanwhile took the switch with them:
+        then nothing is restored."""
+        return _option_scope(self.get_pattern, self.set_pattern, None if index is None else int(index),
+                             lambda old: old < self.pattern_count() and self.set_pattern(old))
+
+    def _pattern_of(self, pattern_of, m, what):
+        """``pattern_of`` as (m,) int32, or ValueError naming the count"""
+        p = np.ascontiguousarray(np.reshape(pattern_of, -1), dtype=np.int32)
+        if p.shape != (m,):
+            raise ValueError(f"pattern_of must hold one pattern per {what}: {m}, got {p.shape[0]}")
+        return p
+
+    def recognition_patterns(self):
+        """The resident pattern decodes (kocr_recognition_patterns): labels (M, label width) int32, log_path (M,) and log_prob
+        (M,) float32 as they were produced; ValueError when nothing is resident or the pattern was off."""
+        m = ctypes.c_int32(0)
+        rc = self._lib.kocr_recognition_patterns(self._h, None, None, None, 0, ctypes.byref(m))
+        if rc != KOCR_ECAPACITY:
+            self._check(rc, value_error=True)
+        labels = np.full((m.value, self.crnn_label_width()), -1, dtype=np.int32)
+        log_path, log_prob = np.full(m.value, -np.inf, dtype=np.float32), np.full(m.value, -np.inf, dtype=np.float32)
+        if m.value:
+            self._check(self._lib.kocr_recognition_patterns(self._h, _ptr(labels), _ptr(log_path), _ptr(log_prob), m.value, None),
+                        value_error=True)
+        return labels, log_path, log_prob
+
+    def crnn_pattern(self, crops, pattern_of=None):
+        """The crops' best readings under their patterns (kocr_crnn_pattern): labels (M, 48) int32, -1 padded; log_path (M,)
+        float32, the best accepted alignment; log_prob (M,) float32 = -crnn_ctc_loss of the row, bit for bit; -1 / -inf where
+        nothing fits or the crop has no pattern.  ``pattern_of`` (M integers in [-1, pattern_count())); None: the context's
+        ``set_pattern`` switch."""
+        x = self._crops(crops)
+        m = x.shape[0]
+        of = None if pattern_of is None else self._pattern_of(pattern_of, m, "crop")
+        labels = np.full((m, self.crnn_label_width()), -1, dtype=np.int32)
+        log_path, log_prob = np.full(m, -np.inf, dtype=np.float32), np.full(m, -np.inf, dtype=np.float32)
+        self._check(self._lib.kocr_crnn_pattern(self._h, _ptr(x), m, _ptr(of), _ptr(labels), _ptr(log_path), _ptr(log_prob), 0),
+                    value_error=True)
+        return labels, log_path, log_prob
+
+    def crnn_pattern_device(self, d_crops, m, d_labels, d_log_path, d_log_prob, pattern_of=None):
+        """``crnn_pattern`` on device buffers; ``pattern_of`` stays a host list"""
+        of = None if pattern_of is None else self._pattern_of(pattern_of, int(m), "crop")
+        self._check(self._lib.kocr_crnn_pattern(self._h, _ptr(d_crops), int(m), _ptr(of), _ptr(d_labels), _ptr(d_log_path),
+                                                _ptr(d_log_prob), 1), value_error=True)
+
+    def crnn_decode_logits_patterns(self, logits, pattern_of=None):
+        """The pattern launches on given logits (M, 50, classes) float32 (kocr_crnn_decode_logits_patterns; development):
+        ``(labels, log_path, log_prob)`` as ``crnn_pattern``."""
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        if lg.ndim != 3 or lg.shape[1:] != (50, self.crnn_classes()):
+            raise ValueError(f"logits must be (M, 50, {self.crnn_classes()}), got {lg.shape}")
+        m = lg.shape[0]
+        of = None if pattern_of is None else self._pattern_of(pattern_of, m, "crop")
+        labels = np.full((m, self.crnn_label_width()), -1, dtype=np.int32)
+        log_path, log_prob = np.full(m, -np.inf, dtype=np.float32), np.full(m, -np.inf, dtype=np.float32)
+        self._check(self._lib.kocr_crnn_decode_logits_patterns(self._h, _ptr(lg), m, _ptr(of), _ptr(labels), _ptr(log_path),
+                                                               _ptr(log_prob)), value_error=True)
+        return labels, log_path, log_prob
+
     def crnn_forward_device(self, d_crops, m, d_labels, d_probs=None):
         self._check(self._lib.kocr_crnn_forward(self._h, _ptr(d_crops), int(m), _ptr(d_labels), _ptr(d_probs), 1))
 
@@ -906,7 +1002,8 @@ class Context:
             int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0), min_area_rect, return_scores, char_boxes)
 
     # -- Recognizer.recognize_from_boxes, device-resident crops ---------------------------------------
-    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None):
+    def recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None,
+                        pattern=None, pattern_of=None):
         """images: (N,H,W,3) uint8; box_groups: list of (n_i,4,2).  Returns labels (M,48) int32 [, log_word (M,), char_scores
         (M,48) float32 as ``crnn_forward_scores``] [, beam labels (M,K,48), beam log_prob (M,K) as ``crnn_beam``, with
         ``beam=(beam_width, top_paths)``; the other results are the same bits] [, lexicon index (M,K), log_prob (M,K) as
@@ -914,16 +1011,26 @@ class Context:
         with ``orientation=(mode, tall_ratio)``: labels and scores are then those of each word's better reading; not
         together with ``beam`` or ``lexicon_top`` (ValueError)].  ``set_of`` (one integer per box, image-major, in
         [-1, charset_count())): each box's character set (kocr_recognize_boxes_charsets), -1 = unconstrained; None: the
-        context's ``set_charset`` switch."""
-        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top, orientation, set_of).render_recognition()
+        context's ``set_charset`` switch.  ``pattern`` (an index in [0, pattern_count())): every box is also decoded under
+        that pattern, or ``pattern_of`` (one integer per box in [-1, pattern_count()), -1 = none:
+        kocr_recognize_boxes_patterns); last come pattern labels (M,48), log_path (M,), log_prob (M,) as ``crnn_pattern``.
+        Not together with ``orientation`` or ``set_of`` (ValueError)."""
+        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top, orientation, set_of, pattern,
+                                     pattern_of).render_recognition()
 
-    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None):
+    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None,
+                         pattern=None, pattern_of=None):
         """recognize_boxes' ``Results`` (no boxes; the detection part of its scores is None); no library call for zero boxes
         beyond the switches"""
         beam = None if beam is None else beam_args(*beam)
-        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top)
+        patterned = pattern is not None or pattern_of is not None
+        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, pattern=True if patterned else None)
+        if patterned and set_of is not None:
+            raise ValueError("pattern and set_of cannot be combined: the pattern states the characters itself")
+        if pattern is not None and pattern_of is not None:
+            raise ValueError("pattern and pattern_of cannot be combined: one pattern for every box, or one per box")
         orientation = None if orientation is None else orientation_args(*orientation)
-        with self._lexicon_scope(lexicon_top), self._orientation_scope(orientation):
+        with self._lexicon_scope(lexicon_top), self._orientation_scope(orientation), self._pattern_scope(pattern):
             with self._beam_scope(beam):
                 x = np.ascontiguousarray(images, dtype=np.uint8)
                 n, h, w, _ = x.shape
@@ -932,8 +1039,15 @@ class Context:
                 out = Results(None, np.full((int(counts.sum()), lw), -1, dtype=np.int32))
                 m = len(out.labels)
                 sets = None if set_of is None else self._set_of(set_of, m, "box")
+                pats = None if pattern_of is None else self._pattern_of(pattern_of, m, "box")
                 with self._scores_scope(return_scores and m):
-                    if m and sets is not None:
+                    if m and pats is not None:
+                        self._check(self._lib.kocr_recognize_boxes_patterns(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
+                                                                            _ptr(out.labels), 0, _ptr(pats)), value_error=True)
+                    elif m and patterned:
+                        self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
+                                                                   _ptr(out.labels), 0), value_error=True)
+                    elif m and sets is not None:
                         self._check(self._lib.kocr_recognize_boxes_charsets(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
                                                                             _ptr(out.labels), 0, _ptr(sets)), value_error=True)
                     elif m:
@@ -947,6 +1061,8 @@ class Context:
                 out.lexicon = self.recognition_lexicon() if m else empty_lexicon(lexicon_top)
             if orientation is not None:
                 out.orientation = self.recognition_orientation() if m else empty_orientation()
+            if patterned:
+                out.pattern = self.recognition_patterns() if m else empty_pattern(lw)
         return out
 
     # -- crops --------------------------------------------------------------------------------
@@ -1026,7 +1142,7 @@ class Context:
     def pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold=0.7, text_threshold=0.4,
                  link_threshold=0.4, size_threshold=10, micro_batch=0, on_device=False, cap=256, max_crops=None,
                  min_area_rect=None, return_scores=False, beam=None, lexicon_top=None, char_boxes=None, orientation=None,
-                 tiled=False):
+                 tiled=False, pattern=None):
         """ptrs: per-image source pointers (ints) or host uint8 arrays.  Returns ``Results.render_context()``: (boxes
         list[(n_i,4,2) f32, detector-input px], labels (M,48) int32), then one element per extra asked for, as the fields of
         ``results.Results`` describe them -- ``return_scores``: its ``scores``; ``beam=(beam_width, top_paths)``: its ``beam``,
@@ -1035,12 +1151,15 @@ class Context:
         ``orientation=(mode, tall_ratio)``, mode "flip" / "any": every box is read in two orientations (include/kocr.h:
         "orientation"); labels and scores are those of each word's better reading, the boxes stay getBoxes' bits, and its
         ``orientation`` comes last (quads in detector-input px).  Not together with ``beam``, ``lexicon_top`` or ``char_boxes``
-        (ValueError).  ``tiled`` (``pipeline_tiled``): ``hmax`` / ``wmax`` are the tile and the overlap of kocr_pipeline_tiled."""
-        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, char_boxes=None if char_rule(char_boxes) is None else True)
+        (ValueError).  ``tiled`` (``pipeline_tiled``): ``hmax`` / ``wmax`` are the tile and the overlap of kocr_pipeline_tiled.
+        ``pattern`` (an index in [0, pattern_count())): every crop is also decoded under that pattern (include/kocr.h:
+        "Patterns") and its ``pattern`` comes last of all; not together with ``orientation`` (ValueError)."""
+        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, char_boxes=None if char_rule(char_boxes) is None else True,
+                                pattern=pattern)
         orientation = None if orientation is None else orientation_args(*orientation)
         with self._char_boxes_scope(char_boxes):
             with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
-                    self._lexicon_scope(lexicon_top), self._orientation_scope(orientation):
+                    self._lexicon_scope(lexicon_top), self._orientation_scope(orientation), self._pattern_scope(pattern):
                 out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
                                      size_threshold, micro_batch, on_device, cap, max_crops, return_scores, tiled)
                 if orientation is not None:
@@ -1049,6 +1168,8 @@ class Context:
                     out.lexicon = self.recognition_lexicon() if len(ptrs) else empty_lexicon(lexicon_top)
                 elif beam is not None:
                     out.beam = self.recognition_beams() if len(ptrs) else empty_beam(beam[1], self.crnn_label_width())
+                if pattern is not None:
+                    out.pattern = self.recognition_patterns() if len(ptrs) else empty_pattern(self.crnn_label_width())
             if char_rule(char_boxes) is not None:
                 # the boxes' own counts and the cap they were produced with (the largest count after a capacity overflow)
                 counts = [len(b) for b in out.boxes]

@@ -374,6 +374,8 @@ int kocr_load_crnn(kocr_ctx* ctx, int n, const char* const* names, const float* 
   if (ctx->lex.V && ctx->lex.classes != crnn_classes(ctx)) lexicon_unload(ctx, ctx->lex.classes);
   // ... and so were the character sets' class indices
   if (ctx->charsets.S && ctx->charsets.classes != crnn_classes(ctx)) charsets_unload(ctx);
+  // ... and the patterns' transition tables
+  if (ctx->patterns.P && ctx->patterns.classes != crnn_classes(ctx)) patterns_unload(ctx);
   return KOCR_OK;
 }
 
@@ -660,6 +662,220 @@ int kocr_get_charset(const kocr_ctx* ctx, int* set) {
   if (!ctx || !set) return KOCR_EINVAL;
   *set = ctx->charset;
   return KOCR_OK;
+}
+
+// ---- patterns (include/kocr.h, "Patterns") -------------------------------------------------------------------------------
+int kocr_set_patterns(kocr_ctx* ctx, const int32_t* delta, const uint8_t* accept, const int32_t* n_states, int P, int classes) {
+  if (!ctx) return KOCR_EINVAL;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  if (P == 0) {
+    patterns_unload(ctx);
+    return KOCR_OK;
+  }
+  const int C = crnn_classes(ctx);
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_set_patterns: call kocr_load_crnn first (the transitions are over its classes)");
+  if (P < 0 || P > KOCR_PATTERNS_MAX)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: P " + std::to_string(P) + " outside [0, KOCR_PATTERNS_MAX = " +
+                                    std::to_string(KOCR_PATTERNS_MAX) + "]");
+  if (classes != C)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: classes " + std::to_string(classes) + " is not the recogniser's " + std::to_string(C) +
+                                    " (class count mismatch)");
+  if (C - 1 >= 0xffff) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: more than 65535 classes");
+  if (!delta || !accept || !n_states) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: null buffer");
+  const int K = C - 1;
+  std::vector<int32_t> hdr((size_t)P * 8, 0), pred;
+  std::vector<int2> nodes, states;
+  std::vector<int> Sv(P), NTv(P);
+  size_t row0 = 0;
+  for (int p = 0; p < P; ++p) {
+    const std::string sp = "pattern " + std::to_string(p);
+    const int S = n_states[p];
+    if (S < 1 || S > KOCR_PATTERN_MAX_STATES)
+      KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: n_states: " + sp + " has " + std::to_string(S) +
+                                      " states, outside [1, KOCR_PATTERN_MAX_STATES = " + std::to_string(KOCR_PATTERN_MAX_STATES) + "]");
+    const int32_t* d = delta + row0 * K;
+    const uint8_t* a = accept + row0;
+    // the transitions in range; the label nodes: (s, c) for every c that enters s
+    std::vector<std::vector<int>> in((size_t)S * K);  // [s][c] -> the p with delta[p][c] == s, ascending
+    for (int q = 0; q < S; ++q)
+      for (int c = 0; c < K; ++c) {
+        const int to = d[(size_t)q * K + c];
+        if (to < -1 || to >= S)
+          KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: delta: " + sp + ": state " + std::to_string(q) + ", class " + std::to_string(c) +
+                                          " moves to " + std::to_string(to) + " outside [-1, " + std::to_string(S) + ")");
+        if (to >= 0) in[(size_t)to * K + c].push_back(q);
+      }
+    // trimmed: every state reachable from state 0 and able to reach an accepting state
+    std::vector<char> fwd(S, 0), bwd(S, 0);
+    std::vector<int> stack{0};
+    fwd[0] = 1;
+    while (!stack.empty()) {
+      const int q = stack.back();
+      stack.pop_back();
+      for (int c = 0; c < K; ++c) {
+        const int to = d[(size_t)q * K + c];
+        if (to >= 0 && !fwd[to]) {
+          fwd[to] = 1;
+          stack.push_back(to);
+        }
+      }
+    }
+    for (int q = 0; q < S; ++q)
+      if (a[q]) {
+        bwd[q] = 1;
+        stack.push_back(q);
+      }
+    while (!stack.empty()) {
+      const int q = stack.back();
+      stack.pop_back();
+      for (int c = 0; c < K; ++c)
+        for (int from : in[(size_t)q * K + c])
+          if (!bwd[from]) {
+            bwd[from] = 1;
+            stack.push_back(from);
+          }
+    }
+    for (int q = 0; q < S; ++q)
+      if (!fwd[q] || !bwd[q])
+        KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: " + sp + " is not trimmed: state " + std::to_string(q) +
+                                        (fwd[q] ? " reaches no accepting state" : " is not reachable from state 0"));
+    hdr[(size_t)p * 8 + 2] = (int)nodes.size();
+    hdr[(size_t)p * 8 + 3] = (int)states.size();
+    hdr[(size_t)p * 8 + 4] = (int)pred.size();
+    const int node0 = (int)nodes.size(), pred0 = (int)pred.size();
+    int n_label = 0;
+    for (int q = 0; q < S; ++q) {
+      states.push_back(make_int2((int)nodes.size() - node0, a[q] ? 1 : 0));
+      nodes.push_back(make_int2(0xffff | (q << 16), (int)pred.size() - pred0));
+      for (int c = 0; c < K; ++c) {
+        const auto& from = in[(size_t)q * K + c];
+        if (from.empty()) continue;
+        nodes.push_back(make_int2(c | (q << 16), (int)pred.size() - pred0));
+        pred.insert(pred.end(), from.begin(), from.end());
+        ++n_label;
+      }
+    }
+    if (n_label > KOCR_PATTERN_MAX_NODES)
+      KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_patterns: " + sp + " has " + std::to_string(n_label) +
+                                      " label nodes, more than KOCR_PATTERN_MAX_NODES = " + std::to_string(KOCR_PATTERN_MAX_NODES));
+    const int NT = (int)nodes.size() - node0;
+    states.push_back(make_int2(NT, 0));
+    nodes.push_back(make_int2(0xffff, (int)pred.size() - pred0));
+    hdr[(size_t)p * 8 + 0] = Sv[p] = S;
+    hdr[(size_t)p * 8 + 1] = NTv[p] = NT;
+    row0 += S;
+  }
+  if (pred.empty()) pred.push_back(0);
+  patterns_unload(ctx);
+  auto& pats = ctx->patterns;
+  auto put = [&](void** dptr, const void* h, size_t bytes) -> int {
+    KOCR_TRY(ctx->dev_alloc(dptr, bytes));
+    KOCR_HIP(ctx, hipMemcpyAsync(*dptr, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return KOCR_OK;
+  };
+  int rc = put((void**)&pats.d_hdr, hdr.data(), hdr.size() * sizeof(int32_t));
+  if (rc == KOCR_OK) rc = put((void**)&pats.d_nodes, nodes.data(), nodes.size() * sizeof(int2));
+  if (rc == KOCR_OK) rc = put((void**)&pats.d_states, states.data(), states.size() * sizeof(int2));
+  if (rc == KOCR_OK) rc = put((void**)&pats.d_pred, pred.data(), pred.size() * sizeof(int32_t));
+  hipStreamSynchronize(ctx->stream);  // the host vectors go out of scope
+  if (rc != KOCR_OK) {
+    patterns_unload(ctx);
+    return rc;
+  }
+  pats.P = P;
+  pats.classes = C;
+  pats.S = Sv;
+  pats.NT = NTv;
+  return KOCR_OK;
+}
+
+int kocr_pattern_count(const kocr_ctx* ctx) { return ctx ? ctx->patterns.P : KOCR_EINVAL; }
+
+int kocr_set_pattern(kocr_ctx* ctx, int index) {
+  if (!ctx) return KOCR_EINVAL;
+  if (index < -1 || index >= ctx->patterns.P)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_set_pattern: index " + std::to_string(index) + " outside [-1, " + std::to_string(ctx->patterns.P) +
+                                    ") (" + std::to_string(ctx->patterns.P) + " patterns are loaded: kocr_set_patterns)");
+  ctx->pattern = index;
+  return KOCR_OK;
+}
+
+int kocr_get_pattern(const kocr_ctx* ctx, int* index) {
+  if (!ctx || !index) return KOCR_EINVAL;
+  *index = ctx->pattern;
+  return KOCR_OK;
+}
+
+// What the two entry points below share: pattern_of (HOST, nullable: the context's switch, which must then be on) checked
+static int pattern_args(kocr_ctx* ctx, const char* fn, const void* in, int M, const int32_t* pattern_of, const void* labels,
+                        const void* log_path, const void* log_prob) {
+  const std::string f(fn);
+  if (M < 0 || (M > 0 && (!in || !labels || !log_path || !log_prob))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+  if (ctx->patterns.P == 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": no patterns are loaded (kocr_set_patterns first)");
+  if (pattern_of) KOCR_TRY(patterns_validate(ctx, fn, pattern_of, M, "crop"));
+  else if (ctx->pattern < 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": pattern_of is null and no pattern is switched on (kocr_set_pattern)");
+  if (ctx->charset >= 0)
+    KOCR_FAIL(ctx, KOCR_EINVAL, f + ": a pattern cannot be combined with an active character set (kocr_set_charset): the pattern states "
+                                    "the characters itself");
+  return KOCR_OK;
+}
+
+// The pattern decode of include/kocr.h ("Patterns") alone: the forward up to fc_12, then the pattern launches
+int kocr_crnn_pattern(kocr_ctx* ctx, const float* crops, int M, const int32_t* pattern_of, int32_t* labels, float* log_path,
+                      float* log_prob, int on_device) {
+  if (!ctx) return KOCR_EINVAL;
+  KOCR_TRY(pattern_args(ctx, "kocr_crnn_pattern", crops, M, pattern_of, labels, log_path, log_prob));
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int mb = crnn_batch(M), LW = crnn_label_width(ctx), C = crnn_classes(ctx);
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = (size_t)LW * sizeof(int32_t), vb = sizeof(float);
+  const CrnnPattern whole{pattern_of, nullptr, ctx->pattern, 0, nullptr, nullptr, nullptr};
+  Staging st{ctx, ctx->ws, "kocr_crnn_pattern", on_device != 0};
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C) + pattern_workspace_bytes(ctx, M, whole), {cb * mb, lb * mb, vb * mb, vb * mb},
+                      {pattern_of ? mb * sizeof(int32_t) : 0}));
+  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
+    const float* d_c;
+    CrnnPattern pt{pattern_of ? pattern_of + s : nullptr, nullptr, ctx->pattern, 0, nullptr, nullptr, nullptr};
+    if (pattern_of) KOCR_TRY(st.upload(pattern_of + s, nb * sizeof(int32_t), pt.d_of));
+    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
+    KOCR_TRY(st.out(labels + s * LW, lb * nb, pt.d_labels));
+    KOCR_TRY(st.out(log_path + s, vb * nb, pt.d_logpath));
+    KOCR_TRY(st.out(log_prob + s, vb * nb, pt.d_logp));
+    KOCR_TRY(crnn_pattern(ctx, d_c, nb, pt));
+    KOCR_TRY(st.back(labels + s * LW, pt.d_labels, lb * nb));
+    KOCR_TRY(st.back(log_path + s, pt.d_logpath, vb * nb));
+    KOCR_TRY(st.back(log_prob + s, pt.d_logp, vb * nb));
+    return st.finish();
+  });
+}
+
+// Development entry (include/kocr.h): the pattern launches on the caller's logits (HOST)
+int kocr_crnn_decode_logits_patterns(kocr_ctx* ctx, const float* logits, int M, const int32_t* pattern_of, int32_t* labels,
+                                     float* log_path, float* log_prob) {
+  if (!ctx) return KOCR_EINVAL;
+  const char* fn = "kocr_crnn_decode_logits_patterns";
+  KOCR_TRY(pattern_args(ctx, fn, logits, M, pattern_of, labels, log_path, log_prob));
+  if (M > CRNN_BATCH)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": M " + std::to_string(M) + " exceeds one recogniser batch of " + std::to_string(CRNN_BATCH));
+  if (M == 0) return KOCR_OK;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t m = (size_t)M, LW = crnn_label_width(ctx), C = crnn_classes(ctx);
+  const size_t gb = m * CRNN_STEPS * C * sizeof(float), lb = m * LW * sizeof(int32_t), vb = m * sizeof(float);
+  CrnnPattern pt{pattern_of, nullptr, ctx->pattern, 0, nullptr, nullptr, nullptr};
+  Staging st{ctx, ctx->ws, fn, false};
+  KOCR_TRY(st.reserve(pattern_workspace_bytes(ctx, M, pt), {gb, lb, vb, vb}, {pattern_of ? m * sizeof(int32_t) : 0}));
+  const float* d_lg;
+  if (pattern_of) KOCR_TRY(st.upload(pattern_of, m * sizeof(int32_t), pt.d_of));
+  KOCR_TRY(st.in(logits, gb, d_lg));
+  KOCR_TRY(st.out(labels, lb, pt.d_labels));
+  KOCR_TRY(st.out(log_path, vb, pt.d_logpath));
+  KOCR_TRY(st.out(log_prob, vb, pt.d_logp));
+  KOCR_TRY(pattern_run(ctx, d_lg, M, pt));
+  KOCR_TRY(st.back(labels, pt.d_labels, lb));
+  KOCR_TRY(st.back(log_path, pt.d_logpath, vb));
+  KOCR_TRY(st.back(log_prob, pt.d_logp, vb));
+  return st.finish();
 }
 
 // Development entry (include/kocr.h): crnn_forward's launches behind fc_12 on the caller's logits; set_of (HOST, nullable):

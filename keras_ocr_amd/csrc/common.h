@@ -158,6 +158,17 @@ struct CharMask {
   }
 };
 
+// Patterns (kocr_set_patterns; DESIGN.md section 4, "Patterns"): the device tables pattern_viterbi_kernel takes by value, all
+// patterns in one buffer each.  hdr: [P][8] = {states S, nodes NT, first node, first state, first pred, 0, 0, 0}; nodes:
+// per node (label | state << 16, first pred), label 0xffff for a blank node, one entry behind a pattern's last; states: per
+// state (its blank node, accept), one entry behind the last; pred: the predecessor states of the label nodes.
+struct PatternTables {
+  const int* hdr = nullptr;
+  const int2* nodes = nullptr;
+  const int2* states = nullptr;
+  const int* pred = nullptr;
+};
+
 struct kocr_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -303,6 +314,31 @@ struct kocr_ctx {
   CharMask charmask(const int32_t* d_set_of, int shift) const {
     return d_set_of ? CharMask{charsets.d_bits, d_set_of, -1, shift, 0} : charmask();
   }
+  // patterns (kocr_set_patterns / kocr_set_pattern; DESIGN.md section 4, "Patterns"): the caller's P automata as node tables,
+  // resident like the lexicon; S / NT: every pattern's state and node count (host); classes: the recogniser's class count
+  // they were built for.  pattern: the one every crop of kocr_recognize_boxes / kocr_pipeline is also decoded under (-1:
+  // none); only ever >= 0 while a table is loaded.  The rows stay resident beside the label rows for
+  // kocr_recognition_patterns.  Valid like last_beam.
+  struct Patterns {
+    int* d_hdr = nullptr;
+    int2* d_nodes = nullptr;
+    int2* d_states = nullptr;
+    int* d_pred = nullptr;
+    int P = 0, classes = 0;
+    std::vector<int> S, NT;
+    PatternTables tables() const { return PatternTables{d_hdr, d_nodes, d_states, d_pred}; }
+  } patterns;
+  int pattern = -1;
+  struct LastPattern {
+    const int* d_labels = nullptr;    // [M][lw]
+    const float* d_logpath = nullptr;  // [M]
+    const float* d_logp = nullptr;     // [M]
+    int M = 0, lw = 0;
+    Resident state = Resident::NONE;
+  } last_pat;
+  void keep_patterns(const int* d_labels, const float* d_logpath, const float* d_logp, int M, int lw, bool on) {
+    last_pat = {d_labels, d_logpath, d_logp, M, lw, resident(on)};
+  }
   // character boxes (kocr_set_char_boxes; DESIGN.md section 4, "Characters"): with the switch on, kocr_get_boxes /
   // kocr_detect / kocr_pipeline run the two launches of chars.hip on the heat-maps and boxes in HBM (chars_resident) and leave
   // the packed quads and scores resident for kocr_detection_char_boxes.  Workspace and results live in two arenas of their
@@ -340,7 +376,8 @@ struct kocr_ctx {
   // Whoever sizes an arena is about to overwrite what the records point at: arena_reserve calls this, and so does an entry
   // point that replaces the results without sizing one.  The one list of what there is to forget.
   void invalidate_results() {
-    last_pl.state = last_sc.det = last_sc.rec = last_beam.state = last_lex.state = last_ch.state = last_or.state = Resident::NONE;
+    last_pl.state = last_sc.det = last_sc.rec = last_beam.state = last_lex.state = last_ch.state = last_or.state = last_pat.state =
+        Resident::NONE;
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
@@ -583,12 +620,41 @@ struct CrnnLexicon {
   float* d_logp;
   float* d_all;
 };
+// pt (CRNN_DECODE only): after the decode (and the beam, the lexicon match), lexicon_logq_kernel<false> and the two pattern
+// launches on the same logits, never masked: crop m under pattern of[first + m] (HOST list; d_of its device copy), or under
+// `uniform` when `of` is null; -1: none (a -1 / -inf row).  d_labels [M][crnn_label_width()], d_logpath / d_logp [M].
+struct CrnnPattern {
+  const int32_t* of;
+  const int32_t* d_of;
+  int uniform;
+  int first;
+  int* d_labels;
+  float* d_logpath;
+  float* d_logp;
+};
 // cm: the character sets of the batch's crops (CharMask above; off by default).  Every decode launch behind fc_12 -- the greedy
 // decode or the scores, the beam, the lexicon launches -- reads its rows through it; the logits themselves, the taps, the loss
 // and the features are never masked.
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
                  float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr,
-                 const CrnnBeam* bm = nullptr, const CrnnLexicon* lx = nullptr, const CharMask& cm = CharMask{});
+                 const CrnnBeam* bm = nullptr, const CrnnLexicon* lx = nullptr, const CharMask& cm = CharMask{},
+                 const CrnnPattern* pt = nullptr);
+// crnn_forward to the logits, then the pattern launches alone (kocr_crnn_pattern)
+int crnn_pattern(kocr_ctx* ctx, const float* d_crops, int M, const CrnnPattern& pt);
+// the pattern launches on logits [M][50][n_classes] that are already on the device (kocr_crnn_decode_logits_patterns)
+int pattern_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnPattern& pt);
+// Crops per chunk of the pattern launches: as many as lex_scratch bytes (kocr_set_lexicon_scratch) hold of what a crop takes
+// -- its To x C table and, when they leave LDS, its back-pointers -- clamp(lex_scratch / per crop, 1, M), for the patterns the
+// M crops from pt.first on run under; and the workspace bytes that the launches of any recogniser batch (at most 1024 crops)
+// of a call's M crops take on top of crnn_workspace_bytes.
+int pattern_chunk(kocr_ctx* ctx, int M, const CrnnPattern& pt);
+size_t pattern_workspace_bytes(kocr_ctx* ctx, int M, const CrnnPattern& pt);
+// the tables freed, P = 0, the switch off
+void patterns_unload(kocr_ctx* ctx);
+// KOCR_EINVAL naming the entry unless each of pattern_of[0 .. M) (HOST) lies in [-1, P); `what`: what an entry belongs to
+int patterns_validate(kocr_ctx* ctx, const char* fn, const int32_t* pattern_of, long M, const char* what);
+// KOCR_EINVAL when a pattern cannot run here: an active character set (kocr_set_charset), or orientation
+int pattern_refusal(kocr_ctx* ctx, const char* fn);
 // crnn_forward to the logits, then the lexicon launches alone (kocr_crnn_lexicon)
 int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx, const CharMask& cm = CharMask{});
 // Crops per chunk of the lexicon launches: as many as lex_scratch bytes of values hold, clamp(lex_scratch / (4 V), 1, M);
@@ -624,6 +690,12 @@ int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32
                  const int32_t* label_lengths, const int32_t* input_lengths, int* Lmax);
 
 // crnn_kernels.hip
+// the bytes of 16-bit back-pointers one crop takes in the workspace under patterns of at most NTmax nodes / Smax states (0:
+// they fit the launch's LDS), and the two pattern launches on the table d_lq of launch_lexicon_logq
+size_t pattern_bp_bytes(int To, int C, int NTmax, int Smax);
+int launch_pattern(kocr_ctx* ctx, const float* d_logits, const float* d_lq, int M, int T, int C, int discard, const PatternTables& pt,
+                   const int32_t* d_pat_of, int uniform, int first, int NTmax, int Smax, void* d_bp, int* d_labels, float* d_logpath,
+                   float* d_logp);
 int launch_ctc_loss(kocr_ctx* ctx, bool logits, const float* d_y, int M, int T, int C, int t0, const int* d_lab, int lstride,
                     const int* d_len, const int* d_in_len, float* d_loss, int Lmax);
 

@@ -260,6 +260,64 @@ static int lexicon_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnLexico
   return KOCR_OK;
 }
 
+// The largest node and state counts among the patterns that crops [pt.first, pt.first + M) run under (0: none of them has one)
+static void pattern_extent(const kocr_ctx* ctx, int M, const CrnnPattern& pt, int* NTmax, int* Smax) {
+  const auto& pats = ctx->patterns;
+  *NTmax = *Smax = 0;
+  auto take = [&](int p) {
+    if (p < 0 || p >= pats.P) return;
+    *NTmax = std::max(*NTmax, pats.NT[p]);
+    *Smax = std::max(*Smax, pats.S[p]);
+  };
+  if (!pt.of) take(pt.uniform);
+  else
+    for (int m = 0; m < M; ++m) take(pt.of[pt.first + m]);
+}
+
+static size_t pattern_crop_bytes(kocr_ctx* ctx, int M, const CrnnPattern& pt) {
+  int NTmax, Smax;
+  pattern_extent(ctx, M, pt, &NTmax, &Smax);
+  const int C = std::max(crnn_classes(ctx), 2), To = std::max(crnn_label_width(ctx), 1);
+  const size_t bp = NTmax ? (pattern_bp_bytes(To, C, NTmax, Smax) + 255) & ~(size_t)255 : 0;
+  return (size_t)To * C * sizeof(float) + bp;
+}
+
+int pattern_chunk(kocr_ctx* ctx, int M, const CrnnPattern& pt) {
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(M, 1), ctx->lex_scratch / pattern_crop_bytes(ctx, M, pt)));
+}
+
+// A batch's chunk times what its crops take is at most max(one crop, min(the budget, the batch)) of the whole call's extent.
+size_t pattern_workspace_bytes(kocr_ctx* ctx, int M, const CrnnPattern& pt) {
+  const size_t cb = pattern_crop_bytes(ctx, M, pt), mb = (size_t)std::min(std::max(M, 1), 1024);
+  return std::max(cb, std::min(ctx->lex_scratch, mb * cb)) + 1024;
+}
+
+// lexicon_logq (unmasked), pattern_viterbi, pattern_rescore on the logits [M][T][C] of a batch, chunk by chunk.  The chunk and
+// the launch's extent follow the patterns of the whole batch: a crop's rows do not depend on either.
+int pattern_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnPattern& pt) {
+  if (M <= 0) return KOCR_OK;
+  const auto& pats = ctx->patterns;
+  const int C = ctx->crnn->n_classes, discard = ctx->crnn->discard, To = T - discard;
+  if (pats.P <= 0 || pats.classes != C) KOCR_FAIL(ctx, KOCR_EINVAL, "patterns: no patterns loaded for this recogniser's class count");
+  int NTmax, Smax;
+  pattern_extent(ctx, M, pt, &NTmax, &Smax);
+  NTmax = std::max(NTmax, 1);  // a batch of -1 rows
+  Smax = std::max(Smax, 1);
+  const int chunk = pattern_chunk(ctx, M, pt);
+  const size_t bpb = (pattern_bp_bytes(To, C, NTmax, Smax) + 255) & ~(size_t)255;
+  float* d_lq = (float*)ctx->ws_alloc((size_t)chunk * To * C * sizeof(float));
+  void* d_bp = bpb ? ctx->ws_alloc((size_t)chunk * bpb) : nullptr;
+  if (!d_lq || (bpb && !d_bp)) KOCR_FAIL(ctx, KOCR_ENOMEM, "patterns: workspace exhausted");
+  for (int c0 = 0; c0 < M; c0 += chunk) {
+    const int nc = std::min(chunk, M - c0);
+    const float* lg = d_lg + (size_t)c0 * T * C;
+    KOCR_TRY(launch_lexicon_logq(ctx, lg, nc, T, C, discard, d_lq, CharMask{}));
+    KOCR_TRY(launch_pattern(ctx, lg, d_lq, nc, T, C, discard, pats.tables(), pt.d_of, pt.uniform, pt.first + c0, NTmax, Smax, d_bp,
+                            pt.d_labels + (size_t)c0 * To, pt.d_logpath + c0, pt.d_logp + c0));
+  }
+  return KOCR_OK;
+}
+
 // The launches behind fc_12 on the logits [M][T][C] of a batch, shared by crnn_forward and crnn_decode_logits: the greedy decode
 // (with the scores when sc is given) ...
 static int decode_launch(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
@@ -268,19 +326,22 @@ static int decode_launch(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels,
   if (sc) return launch_ctc_scores(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars, cm);
   return launch_ctc(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, cm);
 }
-// ... then the beam search and the lexicon match, each where asked for
-static int decode_extras(kocr_ctx* ctx, const float* d_lg, int M, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm) {
+// ... then the beam search, the lexicon match and the pattern decode, each where asked for
+static int decode_extras(kocr_ctx* ctx, const float* d_lg, int M, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm,
+                         const CrnnPattern* pt = nullptr) {
   const CrnnNet* net = ctx->crnn;
   if (bm)
     KOCR_TRY(launch_ctc_beam(ctx, d_lg, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp, cm));
   if (lx) KOCR_TRY(lexicon_run(ctx, d_lg, M, *lx, cm));
+  if (pt) KOCR_TRY(pattern_run(ctx, d_lg, M, *pt));
   return KOCR_OK;
 }
 
 // d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
 // `stop` / d_feats / d_logits / sc / bm / lx: common.h
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
-                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm) {
+                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm,
+                 const CrnnPattern* pt) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -482,7 +543,7 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   probs.C = probs.cs = net->n_classes;
   probs.p = d_probs;
   KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() { return decode_launch(ctx, lg.p, M, d_labels, d_probs, sc, cm); }));
-  return decode_extras(ctx, lg.p, M, bm, lx, cm);
+  return decode_extras(ctx, lg.p, M, bm, lx, cm, pt);
 }
 
 int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
@@ -498,6 +559,42 @@ int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& 
   KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
   if (M <= 0) return KOCR_OK;
   return lexicon_run(ctx, d_lg, M, lx, cm);
+}
+
+int crnn_pattern(kocr_ctx* ctx, const float* d_crops, int M, const CrnnPattern& pt) {
+  const float* d_lg = nullptr;
+  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
+  if (M <= 0) return KOCR_OK;
+  return pattern_run(ctx, d_lg, M, pt);
+}
+
+void patterns_unload(kocr_ctx* ctx) {
+  hipStreamSynchronize(ctx->stream);  // no launch still reads the tables
+  ctx->release(ctx->patterns.d_hdr);
+  ctx->release(ctx->patterns.d_nodes);
+  ctx->release(ctx->patterns.d_states);
+  ctx->release(ctx->patterns.d_pred);
+  ctx->patterns = kocr_ctx::Patterns{};
+  ctx->pattern = -1;
+}
+
+int patterns_validate(kocr_ctx* ctx, const char* fn, const int32_t* pattern_of, long M, const char* what) {
+  const int P = ctx->patterns.P;
+  for (long m = 0; m < M; ++m)
+    if (pattern_of[m] < -1 || pattern_of[m] >= P)
+      KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": pattern_of: " + what + " " + std::to_string(m) + " has pattern " +
+                                      std::to_string(pattern_of[m]) + " outside [-1, " + std::to_string(P) + ") (" + std::to_string(P) +
+                                      " patterns are loaded: kocr_set_patterns)");
+  return KOCR_OK;
+}
+
+int pattern_refusal(kocr_ctx* ctx, const char* fn) {
+  if (ctx->charset >= 0)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": a pattern cannot be combined with an active character set (kocr_set_charset): the "
+                                                  "pattern states the characters itself");
+  if (ctx->orient_mode != KOCR_ORIENT_OFF)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": orientation cannot be combined with a pattern (kocr_set_pattern)");
+  return KOCR_OK;
 }
 
 int lexicon_validate(kocr_ctx* ctx, const char* fn, int top_words) {

@@ -1267,3 +1267,243 @@ int launch_lexicon_select(kocr_ctx* ctx, const float* d_logits, int M, int T, in
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }
+
+// ---- patterns ("Patterns"): the best CTC alignment whose collapsed text a regular expression accepts.
+// The pattern is a trimmed deterministic automaton (kocr_set_patterns); a NODE is (state, blank) or (state, label c) for a
+// label that enters the state, in the order state ascending, blank first, labels ascending.  Viterbi over (frame x node) on
+// the To x C table of lexicon_logq_kernel<false>: V_0 = 0 at node 0 = (0, blank), -inf elsewhere; per frame
+//   (s, blank)  the best of itself, then the label nodes of s
+//   (s, c)      the best of itself, then for every p with delta[p][c] == s (ascending): (p, blank), the nodes (p, c'), c' != c
+// the FIRST of the largest, then + lq_t(blank or c): one float32 add per node per frame, in frame order.
+//   pattern_viterbi_kernel  one workgroup per crop, the lanes over the nodes, the frame loop inside.  Phase A reduces the label
+//                           nodes of every state to their best and second best (two distinct labels; first of the largest, so
+//                           the smaller label); phase B then costs a label node its predecessor STATES, not their nodes: per
+//                           p the blank node, then the best label node that is not c.  That is the statement's candidate
+//                           order.  After the last frame the first of the largest among the accepting nodes, and lane 0 walks
+//                           the 16-bit back-pointers into the label row.
+//   pattern_rescore_kernel  ctc_loss_wave<true> on that row: log_prob == -kocr_crnn_ctc_loss of it, bit for bit.
+// LDS: two value rows [NTmax], the per-state reductions, the crop's table when TAB_LDS, the back-pointers [To][NT] when
+// BP_LDS (else they lie in the workspace, To x NTmax per crop).  Which of the two a launch takes changes no result.
+// Device tables per pattern p: hdr[p] = {S, NT, first node, first state, first pred, ...}; nodes[i] = (label | state << 16,
+// first pred) with label 0xffff for a blank node, one entry behind the last; states[s] = (its blank node, accept), one entry
+// behind the last; pred: the predecessor states of the label nodes.
+// Nothing is shared between crops and every order of evaluation is fixed: a crop's rows are the same bits in any batch.
+constexpr int PAT_BLOCK = 256;
+constexpr unsigned PAT_NONE = 0xffffffffu;
+
+template <bool TAB_LDS, bool BP_LDS>
+__global__ __launch_bounds__(PAT_BLOCK) void pattern_viterbi_kernel(const float* __restrict__ lq, int To, int C, PatternTables pt,
+                                                                    const int32_t* __restrict__ pat_of, int uniform, int first,
+                                                                    int NTmax, int Smax, unsigned short* __restrict__ bp_ws,
+                                                                    int* __restrict__ labels, float* __restrict__ log_path) {
+  extern __shared__ float pat_lds[];
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const int p = pat_of ? pat_of[first + m] : uniform;
+  int* lab = labels + (size_t)m * To;
+  const int* h = pt.hdr + (p < 0 ? 0 : p) * 8;
+  const int S = h[0], NT = h[1];
+  if (p < 0 || NT > NTmax || S > Smax) {  // no pattern for this crop (the launcher sizes NTmax / Smax for every pattern it is given)
+    for (int i = tid; i < To; i += PAT_BLOCK) lab[i] = -1;
+    if (tid == 0) log_path[m] = -INFINITY;
+    return;
+  }
+  const int2* nodes = pt.nodes + h[2];
+  const int2* states = pt.states + h[3];
+  const int* pred = pt.pred + h[4];
+  float* val = pat_lds;                                          // [2][NTmax]
+  float* b1v = val + 2 * NTmax;                                  // [Smax] best label node of the state: value
+  float* b2v = b1v + Smax;                                       // [Smax] second best
+  unsigned* b1i = reinterpret_cast<unsigned*>(b2v + Smax);       // [Smax] label << 16 | node
+  unsigned* b2i = b1i + Smax;                                    // [Smax]
+  float* redv = reinterpret_cast<float*>(b2i + Smax);            // [PAT_BLOCK]
+  int* redi = reinterpret_cast<int*>(redv + PAT_BLOCK);          // [PAT_BLOCK]
+  float* tab = reinterpret_cast<float*>(redi + PAT_BLOCK);       // [To * C] when TAB_LDS
+  unsigned short* bp = BP_LDS ? reinterpret_cast<unsigned short*>(tab + (TAB_LDS ? To * C : 0)) : bp_ws + (size_t)m * To * NTmax;
+  const float* lqm = lq + (size_t)m * To * C;
+  if (TAB_LDS)
+    for (int i = tid; i < To * C; i += PAT_BLOCK) tab[i] = lqm[i];
+  for (int i = tid; i < NT; i += PAT_BLOCK) val[i] = i == 0 ? 0.f : -INFINITY;
+  __syncthreads();
+  auto Q = [&](int i) { return TAB_LDS ? tab[i] : lqm[i]; };
+  const int blank = C - 1;
+  for (int t = 0; t < To; ++t) {
+    const float* cur = val + (t & 1) * NTmax;
+    float* nxt = val + ((t & 1) ^ 1) * NTmax;
+    // phase A: per state the best and the second best of its label nodes
+    for (int s = tid; s < S; s += PAT_BLOCK) {
+      const int b = states[s].x, e = states[s + 1].x;
+      float v1 = -INFINITY, v2 = -INFINITY;
+      int i1 = -1, i2 = -1;
+      for (int i = b + 1; i < e; ++i) {
+        const float v = cur[i];
+        if (v > v1) {
+          v2 = v1;
+          i2 = i1;
+          v1 = v;
+          i1 = i;
+        } else if (v > v2) {
+          v2 = v;
+          i2 = i;
+        }
+      }
+      b1v[s] = v1;
+      b2v[s] = v2;
+      b1i[s] = i1 < 0 ? PAT_NONE : ((unsigned)nodes[i1].x << 16) | (unsigned)i1;
+      b2i[s] = i2 < 0 ? PAT_NONE : ((unsigned)nodes[i2].x << 16) | (unsigned)i2;
+    }
+    __syncthreads();
+    // phase B: every node's best predecessor, the stay first
+    for (int i = tid; i < NT; i += PAT_BLOCK) {
+      const int2 nd = nodes[i];
+      const unsigned label = (unsigned)nd.x & 0xffffu;
+      float best = cur[i];
+      int from = i;
+      float q;
+      if (label == 0xffffu) {
+        const int s = nd.x >> 16;
+        const float v = b1v[s];
+        if (v > best) {
+          best = v;
+          from = (int)(b1i[s] & 0xffffu);
+        }
+        q = Q(t * C + blank);
+      } else {
+        const int ke = nodes[i + 1].y;
+        for (int k = nd.y; k < ke; ++k) {
+          const int ps = pred[k];
+          const int pb = states[ps].x;
+          float v = cur[pb];
+          if (v > best) {
+            best = v;
+            from = pb;
+          }
+          unsigned u = b1i[ps];
+          v = b1v[ps];
+          if ((u >> 16) == label) {
+            u = b2i[ps];
+            v = b2v[ps];
+          }
+          if (v > best) {
+            best = v;
+            from = (int)(u & 0xffffu);
+          }
+        }
+        q = Q(t * C + (int)label);
+      }
+      nxt[i] = best + q;
+      bp[(size_t)t * NT + i] = (unsigned short)from;
+    }
+    __syncthreads();
+  }
+  // the first of the largest among the accepting nodes
+  const float* fin = val + (To & 1) * NTmax;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = tid; i < NT; i += PAT_BLOCK) {
+    const float v = fin[i];
+    if (states[nodes[i].x >> 16].y && v > bv) {
+      bv = v;
+      bi = i;
+    }
+  }
+  redv[tid] = bv;
+  redi[tid] = bi;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int j = 1; j < PAT_BLOCK; ++j) {
+    const float v = redv[j];
+    const int i = redi[j];
+    if (v > bv || (v == bv && i < bi)) {
+      bv = v;
+      bi = i;
+    }
+  }
+  log_path[m] = bv;
+  int n = 0;
+  if (bv != -INFINITY) {
+    int node = bi;
+    for (int t = To - 1; t >= 0; --t) {  // the text backwards into redi (To <= PAT_BLOCK)
+      const int from = bp[(size_t)t * NT + node];
+      const int label = nodes[node].x & 0xffff;
+      if (label != 0xffff && from != node) redi[n++] = label;
+      node = from;
+    }
+  }
+  for (int k = 0; k < To; ++k) lab[k] = k < n ? redi[n - 1 - k] : -1;
+}
+
+// One wave (= one workgroup) per crop: the label row of pattern_viterbi_kernel rescored by ctc_loss_wave<true>.
+// LDS: the loss's la [2][Sp], then int[To]: the label.
+__global__ __launch_bounds__(64) void pattern_rescore_kernel(const float* __restrict__ logits, int T, int C, int discard,
+                                                             const int* __restrict__ labels, const float* __restrict__ log_path,
+                                                             float* __restrict__ logp, int Sp) {
+  extern __shared__ float la[];
+  int* dec = reinterpret_cast<int*>(la + 2 * Sp);
+  const int m = blockIdx.x, lane = threadIdx.x, To = T - discard;
+  if (log_path[m] == -INFINITY) {  // uniform: nothing fits (or no pattern)
+    if (lane == 0) logp[m] = -INFINITY;
+    return;
+  }
+  int L = 0;
+  for (int i = lane; i < To; i += 64) {
+    const int v = labels[(size_t)m * To + i];
+    dec[i] = v;
+    L += v >= 0 ? 1 : 0;
+  }
+  for (int o = 32; o; o >>= 1) L += __shfl_xor(L, o);
+  __syncthreads();
+  const float loss = ctc_loss_wave<true>(logits + ((size_t)m * T + discard) * C, C, dec, L, To, la, Sp, lane);
+  if (lane == 0) logp[m] = -loss;
+}
+
+// The LDS of one pattern_viterbi_kernel launch over patterns of at most NTmax nodes and Smax states: what always lies there,
+// then the table and the back-pointers while the budget holds them.
+constexpr size_t PAT_LDS_BUDGET = 64 * 1024;
+static size_t pattern_lds(int To, int C, int NTmax, int Smax, bool* tab_lds, bool* bp_lds) {
+  size_t b = ((size_t)2 * NTmax + 4 * (size_t)Smax + 2 * PAT_BLOCK) * sizeof(float);
+  const size_t tab = (size_t)To * C * sizeof(float), bp = (size_t)To * NTmax * sizeof(unsigned short);
+  *tab_lds = b + tab <= PAT_LDS_BUDGET;
+  if (*tab_lds) b += tab;
+  *bp_lds = b + bp <= PAT_LDS_BUDGET;
+  if (*bp_lds) b += bp;
+  return b;
+}
+
+size_t pattern_bp_bytes(int To, int C, int NTmax, int Smax) {
+  bool tab_lds, bp_lds;
+  pattern_lds(To, C, NTmax, Smax, &tab_lds, &bp_lds);
+  return bp_lds ? 0 : (size_t)To * NTmax * sizeof(unsigned short);
+}
+
+// d_lq: [M][To][C] of launch_lexicon_logq; d_bp: [M][To][NTmax] 16-bit workspace (pattern_bp_bytes; unused when 0);
+// d_labels [M][To], d_logpath / d_logp [M]
+int launch_pattern(kocr_ctx* ctx, const float* d_logits, const float* d_lq, int M, int T, int C, int discard, const PatternTables& pt,
+                   const int32_t* d_pat_of, int uniform, int first, int NTmax, int Smax, void* d_bp, int* d_labels, float* d_logpath,
+                   float* d_logp) {
+  if (M <= 0) return KOCR_OK;
+  const int To = T - discard;
+  if (To < 1 || To > PAT_BLOCK || C < 2 || NTmax < 1 || Smax < 1) KOCR_FAIL(ctx, KOCR_EINVAL, "pattern_viterbi: bad sizes");
+  bool tab_lds, bp_lds;
+  const size_t lds = pattern_lds(To, C, NTmax, Smax, &tab_lds, &bp_lds);
+  if (lds > PAT_LDS_BUDGET) KOCR_FAIL(ctx, KOCR_EINVAL, "pattern_viterbi: the value rows exceed the LDS budget");
+  if (!bp_lds && !d_bp) KOCR_FAIL(ctx, KOCR_EINVAL, "pattern_viterbi: no back-pointer workspace");
+  {
+    ProfScope ps(ctx, "pattern_viterbi", 8.0 * M * To * NTmax, 4.0 * M * To * C + (bp_lds ? 0.0 : 2.0 * M * To * NTmax));
+    unsigned short* bp = (unsigned short*)d_bp;
+#define KOCR_PAT_LAUNCH(TAB, BP)                                                                                                     \
+  hipLaunchKernelGGL((pattern_viterbi_kernel<TAB, BP>), dim3(M), dim3(PAT_BLOCK), lds, ctx->stream, d_lq, To, C, pt, d_pat_of, uniform, \
+                     first, NTmax, Smax, bp, d_labels, d_logpath)
+    if (tab_lds && bp_lds) KOCR_PAT_LAUNCH(true, true);
+    else if (tab_lds) KOCR_PAT_LAUNCH(true, false);
+    else if (bp_lds) KOCR_PAT_LAUNCH(false, true);
+    else KOCR_PAT_LAUNCH(false, false);
+#undef KOCR_PAT_LAUNCH
+    KOCR_HIP(ctx, hipGetLastError());
+  }
+  const int Sp = (2 * To + 1 + 63) & ~63;
+  ProfScope ps(ctx, "pattern_rescore", 0, 4.0 * M * To * C);
+  hipLaunchKernelGGL(pattern_rescore_kernel, dim3(M), dim3(64), (size_t)2 * Sp * sizeof(float) + To * sizeof(int), ctx->stream, d_logits, T,
+                     C, discard, d_labels, d_logpath, d_logp, Sp);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}

@@ -106,6 +106,7 @@ int orient_run(kocr_ctx* ctx, const uint8_t* d_img, int H, int W, OrientRun& r) 
 const char* orient_refusal(const kocr_ctx* ctx, bool with_chars) {
   if (ctx->beam_width) return ": orientation cannot be combined with a beam (kocr_set_beam)";
   if (ctx->lex_top) return ": orientation cannot be combined with a lexicon match (kocr_set_lexicon_match)";
+  if (ctx->pattern >= 0) return ": orientation cannot be combined with a pattern (kocr_set_pattern)";
   if (with_chars && ctx->chars_on) return ": orientation cannot be combined with character boxes (kocr_set_char_boxes)";
   return nullptr;
 }
@@ -168,8 +169,10 @@ int recognize_boxes_oriented(kocr_ctx* ctx, const char* fn, const uint8_t* img_r
 // Recognizer.recognize_from_boxes' device half in one call: crops are warped and recognised without
 // leaving HBM.  All N images share one size; boxes/counts/labels are HOST buffers.  set_of (HOST, nullable; `fn` =
 // kocr_recognize_boxes_charsets): one character set per box in place of the context's switch, checked before any launch.
+// pattern_of (HOST, nullable; kocr_recognize_boxes_patterns): one pattern per box likewise.
 static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
-                                const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of) {
+                                const int32_t* counts, int32_t* labels, int on_device, const int32_t* set_of,
+                                const int32_t* pattern_of = nullptr) {
   const std::string f(fn);
   if (N < 0 || (N > 0 && (!img_rgb || !counts))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
   if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
@@ -178,6 +181,12 @@ static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* im
     for (int i = 0; i < N; ++i) n += std::max<int32_t>(counts[i], 0);
     KOCR_TRY(charsets_validate(ctx, fn, set_of, n, "box"));
   }
+  if (pattern_of) {
+    long n = 0;
+    for (int i = 0; i < N; ++i) n += std::max<int32_t>(counts[i], 0);
+    KOCR_TRY(patterns_validate(ctx, fn, pattern_of, n, "box"));
+  }
+  if (pattern_of || ctx->pattern >= 0) KOCR_TRY(pattern_refusal(ctx, fn));
   if (ctx->orient_mode != KOCR_ORIENT_OFF)
     return recognize_boxes_oriented(ctx, fn, img_rgb, N, H, W, boxes, counts, labels, on_device, set_of);
   std::vector<WarpParam> prm;
@@ -186,8 +195,10 @@ static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* im
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t ib = (size_t)N * H * W * 3, crop_b = (size_t)M * CRNN_CROP_PIXELS * sizeof(float), pb = (size_t)M * sizeof(WarpParam);
   RecStage rec(ctx, M);
+  if (pattern_of) rec.set_patterns(pattern_of, nullptr);
   Staging st{ctx, ctx->io, fn, on_device != 0};
-  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, rec.bytes(), set_of ? (size_t)M * sizeof(int32_t) : 0}));
+  KOCR_TRY(st.reserve(0, {ib}, {pb, crop_b, rec.bytes(), set_of ? (size_t)M * sizeof(int32_t) : 0,
+                                pattern_of ? (size_t)M * sizeof(int32_t) : 0}));
   WarpParam* d_prm;
   float* d_crops;
   const uint8_t* d_img;
@@ -200,6 +211,11 @@ static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* im
     const int32_t* d_set;
     KOCR_TRY(st.upload(set_of, (size_t)M * sizeof(int32_t), d_set));
     rec.cm = ctx->charmask(d_set, 0);
+  }
+  if (pattern_of) {
+    const int32_t* d_of;
+    KOCR_TRY(st.upload(pattern_of, (size_t)M * sizeof(int32_t), d_of));
+    rec.set_patterns(pattern_of, d_of);
   }
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   KOCR_TRY(rec.run(d_crops));
@@ -220,6 +236,14 @@ extern "C" int kocr_recognize_boxes_charsets(kocr_ctx* ctx, const uint8_t* img_r
   if (!ctx) return KOCR_EINVAL;
   if (N > 0 && !set_of) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes_charsets: null buffer");
   return recognize_boxes_call(ctx, "kocr_recognize_boxes_charsets", img_rgb, N, H, W, boxes, counts, labels, on_device, set_of);
+}
+
+extern "C" int kocr_recognize_boxes_patterns(kocr_ctx* ctx, const uint8_t* img_rgb, int N, int H, int W, const float* boxes,
+                                             const int32_t* counts, int32_t* labels, int on_device, const int32_t* pattern_of) {
+  if (!ctx) return KOCR_EINVAL;
+  if (N > 0 && !pattern_of) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes_patterns: null buffer");
+  if (ctx->patterns.P == 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_recognize_boxes_patterns: no patterns are loaded (kocr_set_patterns first)");
+  return recognize_boxes_call(ctx, "kocr_recognize_boxes_patterns", img_rgb, N, H, W, boxes, counts, labels, on_device, nullptr, pattern_of);
 }
 
 namespace {
@@ -255,6 +279,7 @@ int pipeline_begin(kocr_ctx* ctx, const PipelineCall& c, bool sizes_ok, bool* go
   if (!sizes_ok || c.cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": bad sizes");
   if (ctx->orient_mode != KOCR_ORIENT_OFF)
     if (const char* why = orient_refusal(ctx, true)) KOCR_FAIL(ctx, KOCR_EINVAL, f + why);
+  if (ctx->pattern >= 0) KOCR_TRY(pattern_refusal(ctx, c.fn));
   *go = true;
   return KOCR_OK;
 }
@@ -531,6 +556,17 @@ extern "C" int kocr_recognition_lexicon(kocr_ctx* ctx, int32_t* index, float* lo
                         ": no lexicon matches are resident (call it right after kocr_recognize_boxes or kocr_pipeline)", smaller_than("matches", r.M),
                         {{n_crops, r.M}, {top_words, r.K}}, nullptr, r.M, max_crops,
                         {{index, r.d_index, r.K * sizeof(int32_t)}, {log_prob, r.d_logp, r.K * sizeof(float)}});
+}
+
+// The resident pattern decodes (see include/kocr.h, "Patterns")
+extern "C" int kocr_recognition_patterns(kocr_ctx* ctx, int32_t* labels, float* log_path, float* log_prob, int max_crops, int32_t* n_crops) {
+  if (!ctx) return KOCR_EINVAL;
+  const auto& r = ctx->last_pat;
+  return fetch_resident(ctx, "kocr_recognition_patterns", r.state,
+                        ": the results on this context were produced with the pattern off (kocr_set_pattern(ctx, index) before the call)",
+                        ": no pattern decodes are resident (call it right after kocr_recognize_boxes or kocr_pipeline)", smaller_than("decodes", r.M),
+                        {{n_crops, r.M}}, nullptr, r.M, max_crops,
+                        {{labels, r.d_labels, r.lw * sizeof(int32_t)}, {log_path, r.d_logpath, sizeof(float)}, {log_prob, r.d_logp, sizeof(float)}});
 }
 
 // The results of the last successful kocr_pipeline call as they lie in HBM (see include/kocr.h)

@@ -283,16 +283,25 @@ class ShardedPipeline:
                                       "getBoxes' boxes and one label row per word; use Pipeline.recognize(..., recognition_kwargs="
                                       "{'orientation': ...}) on each rank's own pages")
 
+    @staticmethod
+    def _refuse_pattern(recognition_kwargs):
+        if (recognition_kwargs or {}).get("pattern") is not None:
+            raise NotImplementedError("ShardedPipeline does not carry pattern decodes across ranks: its packed result rows hold "
+                                      "boxes and one label row per word; use Pipeline.recognize(..., recognition_kwargs="
+                                      "{'pattern': ...}) on each rank's own pages")
+
     def recognize(self, images, detection_kwargs=None, recognition_kwargs=None, timing=None, return_scores=False):
         """``timing`` (optional dict) receives ``gather_s``: the time spent in the three result all-gathers.
-        ``return_scores=True`` and a ``beam_width``, ``lexicon_top`` or ``orientation`` in ``recognition_kwargs`` are refused
-        (NotImplementedError): neither scores nor beam alternatives nor lexicon matches nor orientation cross ranks."""
+        ``return_scores=True`` and a ``beam_width``, ``lexicon_top``, ``orientation`` or ``pattern`` in ``recognition_kwargs``
+        are refused (NotImplementedError): neither scores nor beam alternatives nor lexicon matches nor orientation nor
+        pattern decodes cross ranks."""
         from . import tools
 
         self._refuse_scores(return_scores)
         self._refuse_beam(recognition_kwargs)
         self._refuse_lexicon(recognition_kwargs)
         self._refuse_orientation(recognition_kwargs)
+        self._refuse_pattern(recognition_kwargs)
 
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]

@@ -3,7 +3,7 @@ import contextlib
 
 import numpy as np
 
-from . import _lib, charsets as _charsets, detection, evaluation as _evaluation, layout as _layout, lexicon as _lexicon, recognition, scores as _scores, tools
+from . import _lib, charsets as _charsets, detection, evaluation as _evaluation, layout as _layout, lexicon as _lexicon, patterns as _patterns, recognition, scores as _scores, tools
 from .results import Results
 
 
@@ -55,11 +55,35 @@ def charset_scope(recognizer, recognition_kwargs):
     return recognizer._ctx._charset_scope(index)  # pylint: disable=protected-access
 
 
+def pattern_of(recognizer, recognition_kwargs):
+    """The index of ``recognition_kwargs["pattern"]`` (a name loaded with ``recognizer.set_patterns``; DESIGN.md section 4,
+    "Patterns"), or None without one.  ValueError listing the loaded names for an unknown one, and when it is combined with
+    ``beam_width`` / ``lexicon_top`` (one text per word), ``charset`` or ``orientation``; TypeError for a recogniser without
+    patterns."""
+    kwargs = recognition_kwargs or {}
+    name = kwargs.get("pattern")
+    if name is None:
+        return None
+    _one_text_per_word({k: v for k, v in kwargs.items() if k != "pattern"}, "a pattern gives one reading per word")
+    for key in ("charset", "orientation"):
+        if kwargs.get(key) is not None:
+            raise ValueError(f"pattern and {key} cannot be combined: " + (
+                "the pattern states the characters itself" if key == "charset" else "ask for one of the two"))
+    if not hasattr(recognizer, "_pattern_names") or getattr(recognizer, "_ctx", None) is None:
+        raise TypeError(f"pattern: the recognizer ({type(recognizer).__name__}) has no patterns (it is not libkocr-backed)")
+    if not isinstance(name, str):
+        raise ValueError(f"pattern in recognition_kwargs is one name for every box, got {name!r} (per-box patterns: "
+                         "Recognizer.recognize_from_boxes)")
+    return _patterns.index_of(recognizer._pattern_names(name), name)  # pylint: disable=protected-access
+
+
 def _one_text_per_word(recognition_kwargs, why):
-    """ValueError for ``beam_width`` / ``lexicon_top``: the caller needs every ``text`` to be one string"""
+    """ValueError for ``beam_width`` / ``lexicon_top`` / ``pattern``: the caller needs every ``text`` to be one string"""
     for key in ("beam_width", "lexicon_top"):
         if (recognition_kwargs or {}).get(key) is not None:
             raise ValueError(f"{why}: {key} in recognition_kwargs makes every text a list of alternatives")
+    if (recognition_kwargs or {}).get("pattern") is not None:
+        raise ValueError(f"{why}: pattern in recognition_kwargs makes every text a (text, log_prob) pair")
 
 
 def _wants_characters(char_boxes):
@@ -134,7 +158,13 @@ class Pipeline:
 
         ``recognition_kwargs={"charset": name}`` (section 4, "Character sets"; after
         ``recognizer.set_charsets({name: characters})``): every box is decoded under that set, whatever else is asked for;
-        the boxes are the same bits.  ValueError listing the loaded names for an unknown one."""
+        the boxes are the same bits.  ValueError listing the loaded names for an unknown one.
+
+        ``recognition_kwargs={"pattern": name}`` (section 4, "Patterns"; after ``recognizer.set_patterns({name: regex})``):
+        every ``text`` becomes ``(text, log_prob)``, the best reading of the box that the regular expression accepts and its
+        exact CTC log-probability, ``(None, -inf)`` where nothing fits; the boxes are the same bits.  Not together with
+        ``beam_width``, ``lexicon_top``, ``charset`` or ``orientation`` (ValueError); uint8 images only (NotImplementedError).
+        ``recognize_with_scores``, ``recognize_padded``, ``recognize_raw`` and ``recognize_tiled`` take it in the same way."""
         return self.recognize_padded(images, None, None, detection_kwargs, recognition_kwargs)
 
     def recognize_with_scores(self, images, detection_kwargs=None, recognition_kwargs=None):
@@ -216,6 +246,7 @@ class Pipeline:
         """recognize_raw's ``Results``, over one of three routes: the fused one, and the stage-wise one for images that are
         not uint8 or for foreign stages.  ``recognition_kwargs={"charset": name}``: every decode of the call runs under that
         character set of the recogniser (``charset_scope``); the boxes are the same either way."""
+        pattern_of(self.recognizer, recognition_kwargs)  # its refusals come first
         with charset_scope(self.recognizer, recognition_kwargs):
             return self._recognize_routes(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
 
@@ -227,10 +258,12 @@ class Pipeline:
         beam = beam_of(recognition_kwargs)  # the rest: Keras predict kwargs, no effect on results
         want_characters = _wants_characters(char_boxes)
         orientation = orientation_of(recognition_kwargs, char_boxes if want_characters else None)
+        pattern = pattern_of(self.recognizer, recognition_kwargs)
         if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
             raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         if not images:
-            return Results.empty(return_scores, beam, lexicon_top, want_characters, orientation=orientation is not None)
+            return Results.empty(return_scores, beam, lexicon_top, want_characters, orientation=orientation is not None,
+                                 pattern=pattern is not None)
         detection_kwargs = dict(detection_kwargs or {})
         if want_characters:
             detection_kwargs["char_boxes"] = char_boxes
@@ -239,6 +272,8 @@ class Pipeline:
         if floats and orientation is not None:
             raise NotImplementedError("orientation: only uint8 images are read in two orientations (the float crop path has no "
                                       "turned set-up)")
+        if floats and pattern is not None:
+            raise NotImplementedError("pattern: patterns need uint8 images (the float crop path decodes plain crops)")
         if floats or ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx:
             # float (or any non-uint8) images: the reference's cv2 calls interpolate them in float (tools.py:394, :107); the
             # stage-wise path does the same with the float kernels (kocr_resize_pad_f32 / kocr_warp_crops_f32, round 5) -- off
@@ -248,25 +283,28 @@ class Pipeline:
                 raise TypeError(f"char_boxes: the detector ({type(self.detector).__name__}.detect) cannot give character boxes "
                                 "(it takes no char_boxes argument)")
             out, scales = self._recognize_stagewise([im.astype(np.float32) for im in images] if floats else images, detection_kwargs,
-                                                    hmax, wmax, return_scores, beam, lexicon_top, orientation)
+                                                    hmax, wmax, return_scores, beam, lexicon_top, orientation,
+                                                    (recognition_kwargs or {}).get("pattern"))
         else:
             scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
             hmax = hmax_ if hmax is None else max(hmax, hmax_)
             wmax = wmax_ if wmax is None else max(wmax, wmax_)
             out = self._fused(ctx.pipeline, images, dhs, dws, (hmax, wmax), detection_kwargs, return_scores, beam, lexicon_top,
-                              want_characters, orientation)
+                              want_characters, orientation, pattern)
         return self._to_input_pixels(out, scales, orientation, want_characters)
 
     @staticmethod
-    def _fused(call, images, dhs, dws, sizes, detection_kwargs, return_scores, beam, lexicon_top, want_characters, orientation):
+    def _fused(call, images, dhs, dws, sizes, detection_kwargs, return_scores, beam, lexicon_top, want_characters, orientation,
+               pattern=None):
         """One fused call (``Context.pipeline`` with ``sizes`` = (hmax, wmax), ``Context.pipeline_tiled`` with (tile, overlap))
         on uint8 images -> its ``Results``, boxes and characters in detector-input pixels"""
         micro_batch = detection_kwargs.pop("batch_size", 0) or 0
         out = Results.parse_context(call(
             images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, *sizes,
             micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top,
-            **({} if orientation is None else {"orientation": orientation}), **detection_kwargs),
-            return_scores, beam is not None, lexicon_top is not None, want_characters, orientation is not None)
+            **({} if orientation is None else {"orientation": orientation}), **({} if pattern is None else {"pattern": pattern}),
+            **detection_kwargs),
+            return_scores, beam is not None, lexicon_top is not None, want_characters, orientation is not None, pattern is not None)
         if want_characters:
             out.characters = _layout.characters_of(out.characters)
         return out
@@ -301,6 +339,7 @@ class Pipeline:
         ``orientation`` / ``tall_ratio`` and ``charset`` as recognize() does, with the same refusals.  uint8 images only
         (NotImplementedError); detector and recogniser must share one ``Context`` (TypeError).  A halo narrower than the
         detector's receptive field does not reproduce a whole-page pass exactly: see DESIGN.md."""
+        pattern_of(self.recognizer, recognition_kwargs)  # its refusals come first
         with charset_scope(self.recognizer, recognition_kwargs):
             return self._recognize_tiled(images, tile, overlap, scale, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
 
@@ -316,6 +355,7 @@ class Pipeline:
             if return_scores:
                 raise ValueError("return_scores and char_boxes cannot be combined: ask for one of the two")
         orientation = orientation_of(recognition_kwargs, char_boxes if want_characters else None)
+        pattern = pattern_of(self.recognizer, recognition_kwargs)
         if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
             raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         ctx = getattr(self.detector, "_ctx", None)
@@ -333,7 +373,7 @@ class Pipeline:
             if want_characters:
                 kwargs["char_boxes"] = char_boxes
             out = self._fused(ctx.pipeline_tiled, [im], [int(im.shape[0] * scale)], [int(im.shape[1] * scale)], (tile, overlap), kwargs,
-                              return_scores, beam, lexicon_top, want_characters, orientation)
+                              return_scores, beam, lexicon_top, want_characters, orientation, pattern)
             out = self._to_input_pixels(out, [scale], orientation, want_characters)
             words = self._assemble(out)[0]
             pages.append([(text, box, characters) for (text, box), characters in zip(words, out.characters[0])] if want_characters
@@ -341,7 +381,7 @@ class Pipeline:
         return pages
 
     def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None,
-                             orientation=None):
+                             orientation=None, pattern=None):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size).
@@ -404,6 +444,15 @@ class Pipeline:
                 for k, (word, log_prob) in enumerate(matches):
                     out.lexicon[0][r, k] = where[word]
                     out.lexicon[1][r, k] = log_prob
+        if pattern is not None:
+            # likewise a second recogniser call (``pattern``: the name); the public method gives no log_path: NaN
+            read = [w for group in self.recognizer.recognize_from_boxes(images=padded, box_groups=out.boxes, pattern=pattern) for w in group]
+            out.pattern = (np.full(out.labels.shape, -1, np.int32), np.full(len(rows), np.nan, np.float32),
+                           np.full(len(rows), -np.inf, np.float32))
+            for r, (t, log_prob) in enumerate(read):
+                if t is not None:
+                    out.pattern[0][r, :len(t)] = [alphabet.index(ch) for ch in t]
+                    out.pattern[2][r] = log_prob
         if return_scores:
             chars = np.zeros(out.labels.shape, np.float32)
             for r, (_, score) in enumerate(pairs):
@@ -459,7 +508,10 @@ class Pipeline:
 
     def _assemble(self, results):
         # recognition.py:527-534: label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding
-        if results.lexicon is not None:
+        if results.pattern is not None:
+            texts = decode_labels(self.recognizer.alphabet, results.pattern[0])
+            predictions = [(text, float(v)) if v != -np.inf else (None, -np.inf) for text, v in zip(texts, np.asarray(results.pattern[2]))]
+        elif results.lexicon is not None:
             words = self.recognizer.lexicon.words
             predictions = [[(words[i], float(v)) for i, v in zip(row, vals) if i >= 0]
                            for row, vals in zip(np.asarray(results.lexicon[0]).tolist(), np.asarray(results.lexicon[1]))]

@@ -6,7 +6,7 @@ import typing
 
 import numpy as np
 
-from . import _lib, charsets as _charsets, layout as _layout, lexicon as _lexicon, scores as _scores, tools, weights as _weights
+from . import _lib, charsets as _charsets, layout as _layout, lexicon as _lexicon, patterns as _patterns, scores as _scores, tools, weights as _weights
 from .results import Results
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
@@ -283,6 +283,45 @@ class Recognizer:
         self.training_model = _TrainingModel(self._ctx)
         self.lexicon = None
         self.charsets = None
+        self.patterns = None
+
+    def set_patterns(self, patterns, lowercase=False):
+        """The patterns for ``pattern=`` ("Patterns"): a mapping name -> regular expression, e.g.
+        ``{"date": r"\\d{2}/\\d{2}/\\d{4}"}``, or a ``patterns.Patterns`` built with this recogniser's alphabet; compiled on
+        the host (``patterns.py`` lists the syntax), loaded into the context once, resident like a lexicon;
+        ``Recognizer.patterns`` holds them.  ``None`` unloads.  ``lowercase``: lower-case the literal characters first.
+        ValueError naming the pattern and the position for unsupported syntax, naming the character for a literal the alphabet
+        cannot spell, naming the count for more than 64 patterns, 256 states or 4096 label nodes, and for an empty language."""
+        if patterns is None:
+            self._ctx.set_patterns(None)
+            self.patterns = None
+            return
+        pats = patterns if isinstance(patterns, _patterns.Patterns) else _patterns.Patterns(self.alphabet, patterns, lowercase=lowercase)
+        if pats.classes != len(self.alphabet) + 1 or pats.alphabet != self.alphabet:
+            raise ValueError(f"the patterns were built for an alphabet of {pats.classes} classes (blank included), the recogniser "
+                             f"has {len(self.alphabet) + 1}: class count / alphabet mismatch")
+        self._ctx.set_patterns(*pats.tables())
+        self.patterns = pats
+
+    def _pattern_names(self, pattern, **others):
+        """The loaded names for a ``pattern=`` argument (None when none is asked for); ValueError without loaded patterns, and
+        naming both when it is combined with one of ``others`` (name=value; None counts as not asked for)"""
+        if pattern is None:
+            return None
+        for name, value in others.items():
+            if value is not None:
+                raise ValueError(f"pattern and {name} cannot be combined: " + (
+                    "the pattern states the characters itself" if name == "charset" else "ask for one of the two"))
+        if self.patterns is None or self._ctx.pattern_count() != len(self.patterns):
+            raise ValueError("pattern needs loaded patterns: call Recognizer.set_patterns({name: regex}) first (the patterns are "
+                             "unloaded when a recogniser of another class count is loaded on their context)")
+        return self.patterns.names
+
+    def _readings(self, labels, log_path, log_prob):
+        """Pattern rows -> per word ``(text, log_prob)``, ``(None, -inf)`` where nothing fits (or the box has no pattern)"""
+        del log_path
+        texts = self._decode(labels)
+        return [(text, float(v)) if v != -np.inf else (None, -np.inf) for text, v in zip(texts, np.asarray(log_prob))]
 
     def set_charsets(self, charsets, lowercase=False):
         """The character sets for ``charset=`` ("Character sets"): a mapping name -> characters, e.g.
@@ -370,7 +409,7 @@ class Recognizer:
         return [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
                 for i in range(m)]
 
-    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None, charset=None):
+    def recognize(self, image, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None, charset=None, pattern=None):
         """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string; ``return_scores=True``:
         ``(text, score)``, a ``scores.Score`` whose ``detection`` is None.
 
@@ -385,7 +424,13 @@ class Recognizer:
 
         ``charset=name`` (after ``set_charsets``; default None: unconstrained): the crop is decoded as if the recogniser could
         only answer the characters of that set -- the text, its scores, the beam alternatives and the lexicon values all
-        follow ("Character sets").  ValueError listing the loaded names for an unknown one."""
+        follow ("Character sets").  ValueError listing the loaded names for an unknown one.
+
+        ``pattern=name`` (after ``set_patterns``; default None): instead of the string, ``(text, log_prob)`` -- the best
+        reading of the crop that the regular expression accepts and its exact CTC log-probability (DESIGN.md section 4,
+        "Patterns"); ``(None, -inf)`` when no accepted text fits the crop's frames.  Not together with ``beam_width``,
+        ``lexicon_top`` or ``charset`` (ValueError)."""
+        pattern = _patterns.index_of(self._pattern_names(pattern, beam_width=beam_width, lexicon_top=lexicon_top, charset=charset), pattern)
         lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         charset = _charsets.index_of(self._charset_names(charset), charset)
@@ -397,11 +442,15 @@ class Recognizer:
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
         with self._charset_scope(charset):
-            return self._words(self._recognize_crops(crops, return_scores, beam, lexicon_top))[0]
+            return self._words(self._recognize_crops(crops, return_scores, beam, lexicon_top, pattern))[0]
 
-    def _recognize_crops(self, crops, return_scores, beam, lexicon_top):
-        """The ``Results`` of crops on the host: the decode [with its scores], and the alternatives or matches asked for"""
+    def _recognize_crops(self, crops, return_scores, beam, lexicon_top, pattern=None):
+        """The ``Results`` of crops on the host: the decode [with its scores], and the alternatives or matches asked for;
+        ``pattern``: the index every crop is decoded under"""
         out = Results(None, None)
+        if pattern is not None:
+            out.pattern = self._ctx.crnn_pattern(crops, np.full(len(crops), pattern, np.int32))
+            out.labels = out.pattern[0]
         if return_scores:
             out.labels, *scores = self._ctx.crnn_forward_scores(crops)
             out.scores = (None, *scores)
@@ -409,12 +458,12 @@ class Recognizer:
             out.beam = self._ctx.crnn_beam(crops, *beam)
         elif lexicon_top is not None:
             out.lexicon = self._ctx.crnn_lexicon(crops, lexicon_top)
-        elif not return_scores:
+        elif not return_scores and pattern is None:
             out.labels = self._ctx.crnn_forward(crops)
         return out
 
     def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None,
-                             orientation=None, tall_ratio=1.5, return_orientation=False, charset=None,
+                             orientation=None, tall_ratio=1.5, return_orientation=False, charset=None, pattern=None,
                              **kwargs) -> typing.List[typing.List[str]]:
         """Recognizer.recognize_from_boxes (recognition.py:491-537); ``return_scores=True``: per image a list of
         ``(text, score)``, ``score`` a ``scores.Score`` whose ``detection`` is None.  ``beam_width`` / ``top_paths``: as
@@ -431,16 +480,27 @@ class Recognizer:
         ``charset`` (after ``set_charsets``; DESIGN.md section 4, "Character sets"): a name -- every box is decoded under
         that set -- or per image a list with one name or None (unconstrained) per box: an amount and a name on one page.
         It combines with every other argument; with ``orientation`` both readings of a box use its set.  Per-box lists
-        need uint8 images (NotImplementedError)."""
+        need uint8 images (NotImplementedError).
+
+        ``pattern`` (after ``set_patterns``; DESIGN.md section 4, "Patterns"): a name -- every box is decoded under that
+        regular expression -- or per image a list with one name or None per box: a date and an amount on one page.  Every
+        text becomes ``(text, log_prob)``, the best accepted reading and its exact CTC log-probability, ``(None, -inf)``
+        where nothing fits or the box has no pattern.  Not together with ``beam_width``, ``lexicon_top``, ``charset`` or
+        ``orientation`` (ValueError); uint8 images only (NotImplementedError)."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
+        names = self._pattern_names(pattern, beam_width=beam_width, lexicon_top=lexicon_top, charset=charset, orientation=orientation)
+        pattern = _patterns.per_box(names, pattern, box_groups)
         uniform_set, set_of = _charsets.per_box(self._charset_names(charset), charset, box_groups)
         with self._charset_scope(uniform_set):
             return self._recognize_from_boxes(images, box_groups, return_scores, beam_width, top_paths, lexicon_top, orientation,
-                                              tall_ratio, return_orientation, set_of)
+                                              tall_ratio, return_orientation, set_of, pattern)
 
     def _recognize_from_boxes(self, images, box_groups, return_scores, beam_width, top_paths, lexicon_top, orientation, tall_ratio,
-                              return_orientation, set_of):
-        """recognize_from_boxes under the context's character-set switch; set_of: the flat per-box set indices, or None"""
+                              return_orientation, set_of, pattern=(None, None)):
+        """recognize_from_boxes under the context's character-set switch; set_of: the flat per-box set indices, or None;
+        pattern: (the index for every box or None, the flat per-box pattern indices or None)"""
+        pattern, pattern_of = pattern
+        patterned = pattern is not None or pattern_of is not None
         lexicon_top = self._lexicon_top(lexicon_top, beam_width)
         beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
         _lib.refuse_orientation_with(orientation, beam_width=beam_width, lexicon_top=lexicon_top)
@@ -453,7 +513,7 @@ class Recognizer:
             raise NotImplementedError("orientation: only uint8 images are read in two orientations (the float crop path has no "
                                       "turned set-up)")
         if not sum(len(b) for b in box_groups):
-            return [[] for _ in images] if return_scores or beam or lexicon_top or return_orientation else [[]] * len(images)
+            return [[] for _ in images] if return_scores or beam or lexicon_top or return_orientation or patterned else [[]] * len(images)
         start_end: typing.List[typing.Tuple[int, int]] = []
         for boxes in box_groups:
             start = 0 if not start_end else start_end[-1][1]
@@ -461,6 +521,8 @@ class Recognizer:
         images = [np.asarray(image) for image in images]
         if set_of is not None and any(im.dtype != np.uint8 for im in images):
             raise NotImplementedError("charset: per-box character sets need uint8 images (the float crop path decodes plain crops)")
+        if patterned and any(im.dtype != np.uint8 for im in images):
+            raise NotImplementedError("pattern: patterns need uint8 images (the float crop path decodes plain crops)")
         if any(im.dtype != np.uint8 for im in images):
             # float images (recognition.py:507-526 works in the image's own type): gray conversion and the crop warp in
             # float ON THE GPU (kocr_warp_crops_f32, round 5), the division by 255 of :524, the recogniser
@@ -472,11 +534,13 @@ class Recognizer:
             out = self._recognize_crops(np.concatenate(crops) / np.float32(255), return_scores, beam, lexicon_top)
         elif len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top, oriented, set_of)  # pylint: disable=protected-access
+            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top, oriented, set_of,  # pylint: disable=protected-access
+                                             pattern, pattern_of)
         else:
             # the reference loops per image, so sizes may differ: one call per image
             out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top, oriented,  # pylint: disable=protected-access
-                                                                  None if set_of is None else set_of[start:end])
+                                                                  None if set_of is None else set_of[start:end], pattern,
+                                                                  None if pattern_of is None else pattern_of[start:end])
                                        for image, boxes, (start, end) in zip(images, box_groups, start_end) if len(boxes)])
         words = self._words(out)
         if return_orientation:
@@ -487,7 +551,9 @@ class Recognizer:
     def _words(self, out):
         """A ``Results``' crops as what recognize_from_boxes returns for each: the text, or its alternatives (``beam``), or
         its matches (``lexicon``) [paired with the ``Score`` of the greedy decode]"""
-        if out.beam is not None:
+        if out.pattern is not None:
+            words = self._readings(*out.pattern)
+        elif out.beam is not None:
             words = self._alternatives(*out.beam)
         else:
             words = self._decode(out.labels) if out.lexicon is None else self._matches(*out.lexicon)

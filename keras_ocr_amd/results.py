@@ -18,6 +18,10 @@ def empty_lexicon(top_words):
     return np.zeros((0, top_words), np.int32), np.zeros((0, top_words), np.float32)
 
 
+def empty_pattern(label_width=48):
+    return np.zeros((0, label_width), np.int32), np.zeros(0, np.float32), np.zeros(0, np.float32)
+
+
 def empty_orientation():
     return np.zeros(0, np.int32), np.zeros((0, 4, 2), np.float32), np.zeros((0, 2), np.float32)
 
@@ -41,7 +45,10 @@ class Results:
     orientation: ``(turns (M,) int32, quads (M, 4, 2) float32, log_words (M, 2) float32)`` as
         ``Context.recognition_orientation``: with it, labels and the recogniser's scores are those of each word's better
         reading, ``quads[m]`` is [tl, tr, br, bl] of the text as read and ``log_words[m]`` the two candidates' values.  While it
-        is None every layout below is what it was; where present it comes last.
+        is None every layout below is what it was; where present it comes last (before ``pattern``).
+    pattern: ``(labels (M, label width) int32, log_path (M,) float32, log_prob (M,) float32)`` as ``Context.crnn_pattern``: each
+        crop's best reading that its pattern accepts ("Patterns"), -1 / -inf where nothing fits or the crop
+        has no pattern.  While it is None every layout below is what it was; where present it comes last of all.
 
     For zero images (``empty``) or zero crops the extras are zero-row arrays of these shapes and dtypes."""
     boxes: typing.Any
@@ -51,38 +58,41 @@ class Results:
     lexicon: typing.Any = None
     characters: typing.Any = None
     orientation: typing.Any = None
+    pattern: typing.Any = None
 
     @classmethod
-    def empty(cls, scores=False, beam=None, lexicon=None, characters=False, label_width=48, orientation=False):
+    def empty(cls, scores=False, beam=None, lexicon=None, characters=False, label_width=48, orientation=False, pattern=False):
         """The results of zero images; ``beam`` = (beam_width, top_paths), ``lexicon`` = top_words"""
         return cls([], np.zeros((0, label_width), np.int32), empty_scores(label_width, []) if scores else None,
                    empty_beam(beam[1], label_width) if beam else None, empty_lexicon(lexicon) if lexicon else None,
-                   [] if characters else None, empty_orientation() if orientation else None)
+                   [] if characters else None, empty_orientation() if orientation else None,
+                   empty_pattern(label_width) if pattern else None)
 
     def render_context(self):
-        """``Context.pipeline``'s layout: ``(boxes, labels[, scores][, beam | lexicon][, characters][, orientation])``, nothing
-        padded"""
+        """``Context.pipeline``'s layout: ``(boxes, labels[, scores][, beam | lexicon][, characters][, orientation][, pattern])``,
+        nothing padded"""
         alternatives = self.beam if self.lexicon is None else self.lexicon
-        return tuple([self.boxes, self.labels] + [v for v in (self.scores, alternatives, self.characters, self.orientation) if v is not None])
+        return tuple([self.boxes, self.labels] +
+                     [v for v in (self.scores, alternatives, self.characters, self.orientation, self.pattern) if v is not None])
 
     @classmethod
-    def parse_context(cls, out, scores=False, beam=False, lexicon=False, characters=False, orientation=False):
+    def parse_context(cls, out, scores=False, beam=False, lexicon=False, characters=False, orientation=False, pattern=False):
         """``render_context``'s inverse, given which extras were asked for (with both ``beam`` and ``lexicon``: the lexicon)"""
-        wanted = (True, True, scores, beam and not lexicon, lexicon, characters, orientation)
+        wanted = (True, True, scores, beam and not lexicon, lexicon, characters, orientation, pattern)
         if len(out) != sum(map(bool, wanted)):
             raise ValueError(f"{len(out)} results do not fit scores={scores}, beam={beam}, lexicon={lexicon}, characters={characters}"
-                             + (f", orientation={orientation}" if orientation else ""))
+                             + (f", orientation={orientation}" if orientation else "") + (f", pattern={pattern}" if pattern else ""))
         values = iter(out)
         return cls(*[next(values) if w else None for w in wanted])
 
     def render_raw(self):
         """``Pipeline.recognize_raw``'s layout: ``(boxes, labels[, scores_or_None[, beam_or_None[, lexicon]]][, characters]
-        [, orientation])`` -- as short as the extras allow, None in the place of an earlier extra that was not asked for"""
+        [, orientation][, pattern])`` -- as short as the extras allow, None in the place of an earlier extra that was not asked for"""
         extras = [self.scores, self.beam, self.lexicon]
         while extras and extras[-1] is None:
             extras.pop()
         return (self.boxes, self.labels, *extras) + (() if self.characters is None else (self.characters,)) + \
-            (() if self.orientation is None else (self.orientation,))
+            (() if self.orientation is None else (self.orientation,)) + (() if self.pattern is None else (self.pattern,))
 
     def render_detection(self):
         """``Context.get_boxes`` / ``detect``: the boxes, or ``(boxes[, detection scores][, characters])`` with an extra"""
@@ -92,10 +102,11 @@ class Results:
 
     def render_recognition(self):
         """``Context.recognize_boxes``: the labels, or ``(labels[, log_word, char_scores][, beam pair][, lexicon pair][, turns,
-        quads, log_words])``, flat"""
-        if self.scores is None and self.beam is None and self.lexicon is None and self.orientation is None:
+        quads, log_words][, pattern labels, log_path, log_prob])``, flat"""
+        if self.scores is None and self.beam is None and self.lexicon is None and self.orientation is None and self.pattern is None:
             return self.labels
-        return (self.labels, *(self.scores or (None,))[1:], *(self.beam or ()), *(self.lexicon or ()), *(self.orientation or ()))
+        return (self.labels, *(self.scores or (None,))[1:], *(self.beam or ()), *(self.lexicon or ()), *(self.orientation or ()),
+                *(self.pattern or ()))
 
     @classmethod
     def concatenate(cls, parts):
@@ -104,4 +115,4 @@ class Results:
             values = [getattr(part, field) for part in parts]
             return None if values[0] is None else tuple(None if v[0] is None else np.concatenate(v) for v in zip(*values))
         return cls(None, np.concatenate([part.labels for part in parts]), join("scores"), join("beam"), join("lexicon"),
-                   orientation=join("orientation"))
+                   orientation=join("orientation"), pattern=join("pattern"))
