@@ -775,6 +775,29 @@ int kocr_profile_report(kocr_ctx* ctx, int cap, char* names /* cap x 64 */, int6
 int kocr_range_stats_enable(kocr_ctx* ctx, int on);
 int kocr_range_stats_report(kocr_ctx* ctx, int cap, char* names /* cap x 64 */, double* values /* cap x 7 */);
 
+/* ---- workspace arenas (FOR TESTS ONLY: not for callers, and no part of the stable surface) ------------ */
+/* Every entry point sizes the context's bump arenas from a plan -- the bytes it hands the reservation -- and then allocates
+ * from them.  These calls let the suite see whether the plans hold ("Arena book-keeping").
+ * For tests: kocr_debug_arena_count() arenas, kocr_debug_arena_name(i) the name of arena i (NULL outside the range). */
+int kocr_debug_arena_count(void);
+const char* kocr_debug_arena_name(int i);
+/* For tests: arena i's capacity, the bytes its last reservation asked for, the largest offset an allocation reached (or, when
+ * refused for want of room, would have reached) since then, and the largest peak - requested over the arena's life (0 when
+ * every plan held).  Any pointer may be NULL.  KOCR_EINVAL outside the range. */
+int kocr_debug_arena_stats(kocr_ctx* ctx, int i, uint64_t* cap, uint64_t* requested, uint64_t* peak, uint64_t* excess);
+/* For tests: synchronises, frees every arena and zeroes its statistics, forgets every resident result and the latched guard
+ * damage -- the context is as cold as a new one, but keeps its networks, lexicon, patterns, character sets and switches. */
+int kocr_debug_release_arenas(kocr_ctx* ctx);
+/* For tests: guard mode (off by default; off costs nothing and changes no launch).  On, every arena allocation is followed by
+ * a guard -- from the first byte behind the buffer to the next 256-byte boundary plus 256 bytes -- filled with 0xA5 on the
+ * context's stream when the buffer is allocated, and compared whenever the arena is emptied (so for every batch of a call) and
+ * by kocr_debug_check_arena_guards.  A reservation takes 256 KiB more for the guards; they do not count in the statistics. */
+int kocr_debug_set_arena_guards(kocr_ctx* ctx, int on);
+/* For tests: compares the guards still recorded and returns the number of damaged guards since the last check or release
+ * (negative: a KOCR_* code); *arena, *offset, *byte (nullable) name the first: its arena, the offset of the buffer it follows,
+ * and the offset of its first damaged byte.  The count starts again at 0. */
+int kocr_debug_check_arena_guards(kocr_ctx* ctx, int* arena, uint64_t* offset, uint64_t* byte);
+
 #ifdef __cplusplus
 }
 #endif

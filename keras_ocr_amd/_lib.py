@@ -160,6 +160,12 @@ def load_library():
         "kocr_profile_report": (ci, [vp, ci, ctypes.c_char_p, _c_i64_p, _c_dbl_p, _c_dbl_p, _c_dbl_p]),
         "kocr_range_stats_enable": (ci, [vp, ci]),
         "kocr_range_stats_report": (ci, [vp, ci, ctypes.c_char_p, _c_dbl_p]),
+        "kocr_debug_arena_count": (ci, []),
+        "kocr_debug_arena_name": (ctypes.c_char_p, [ci]),
+        "kocr_debug_arena_stats": (ci, [vp, ci, vp, vp, vp, vp]),
+        "kocr_debug_release_arenas": (ci, [vp]),
+        "kocr_debug_set_arena_guards": (ci, [vp, ci]),
+        "kocr_debug_check_arena_guards": (ci, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if not hasattr(lib, name):
@@ -1507,6 +1513,33 @@ class Context:
                         "frac_below_2^-4": b4 / nz if nz else 0.0, "frac_below_2^-14": b14 / nz if nz else 0.0,
                         "share_of_sum_abs_below_2^-4": sb / sa if sa else 0.0}
         return rows
+
+    # -- workspace arenas (include/kocr.h: for tests, not for callers) ----------------------------------
+    def arena_names(self):
+        return [self._lib.kocr_debug_arena_name(i).decode() for i in range(self._lib.kocr_debug_arena_count())]
+
+    def arena_stats(self):
+        """{arena: {cap, requested, peak, excess}} in bytes (kocr_debug_arena_stats)"""
+        out = {}
+        for i, name in enumerate(self.arena_names()):
+            v = [ctypes.c_uint64(0) for _ in range(4)]
+            self._check(self._lib.kocr_debug_arena_stats(self._h, i, *[ctypes.byref(x) for x in v]))
+            out[name] = dict(zip(("cap", "requested", "peak", "excess"), (int(x.value) for x in v)))
+        return out
+
+    def release_arenas(self):
+        """Frees every arena and forgets every resident result: the context is cold again, its networks stay loaded."""
+        self._check(self._lib.kocr_debug_release_arenas(self._h))
+
+    def set_arena_guards(self, on=True):
+        self._check(self._lib.kocr_debug_set_arena_guards(self._h, int(bool(on))))
+
+    def check_arena_guards(self):
+        """(damaged guards since the last check, first one's arena name or None, its buffer's offset, its first damaged byte)"""
+        arena, off, byte = ctypes.c_int(-1), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        n = self._check(self._lib.kocr_debug_check_arena_guards(self._h, ctypes.byref(arena), ctypes.byref(off), ctypes.byref(byte)))
+        names = self.arena_names()
+        return n, (names[arena.value] if 0 <= arena.value < len(names) else None), int(off.value), int(byte.value)
 
 
 def _detector_input(images):

@@ -24,7 +24,7 @@ struct Staging {
       for (size_t b : staged) need += b + 256;
     for (size_t b : always) need += b + 256;
     if (need) KOCR_TRY(arena_reserve(ctx, arena, need + 8192));
-    arena.off = 0;
+    arena.reset();
     return KOCR_OK;
   }
   template <class T> int scratch(size_t bytes, T*& d) {

@@ -12,14 +12,18 @@
 // ---------------------------------------------------------------------------------------
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   ctx->invalidate_results();  // whoever sizes an arena is about to overwrite it (the entry points re-validate at their end)
-  if (bytes <= a.cap) return KOCR_OK;
+  a.requested = bytes;
+  a.peak = 0;
+  const size_t guard = a.gctx ? ARENA_GUARD_RESERVE : 0;  // guard mode: room for the guards, outside the plan
+  if (bytes + guard <= a.cap) return KOCR_OK;
   if (a.base) {
+    if (!a.guards.empty()) arena_guard_check(a);  // before the memory they lie in goes
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     KOCR_HIP(ctx, hipFree(a.base));
     a.base = nullptr;
     a.cap = 0;
   }
-  const size_t want = bytes + (bytes >> 3) + 4096;
+  const size_t want = bytes + (bytes >> 3) + 4096 + guard;
   void* p = nullptr;
   hipError_t e = hipMalloc(&p, want);
   if (e != hipSuccess) {
@@ -28,8 +32,36 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   }
   a.base = (char*)p;
   a.cap = want;
-  a.off = 0;
+  a.reset();
   return KOCR_OK;
+}
+
+void arena_guard_fill(Arena& a, size_t at, size_t len) {
+  kocr_ctx* ctx = a.gctx;
+  if (hipMemsetAsync(a.base + at, ARENA_GUARD_FILL, len, ctx->stream) != hipSuccess) ctx->set_err("arena guard: hipMemsetAsync failed");
+}
+
+void arena_guard_check(Arena& a) {
+  kocr_ctx* ctx = a.gctx;
+  std::vector<ArenaGuard> list;
+  list.swap(a.guards);
+  if (!ctx || list.empty()) return;
+  int index = -1;
+  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i)
+    if (ctx->arena_at(i) == &a) index = i;
+  std::vector<unsigned char> copy;
+  bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
+  for (const ArenaGuard& g : list) {
+    copy.assign(g.len, 0);
+    ok = ok && hipMemcpy(copy.data(), a.base + g.at, g.len, hipMemcpyDeviceToHost) == hipSuccess;
+    const long bad = ok ? arena_guard_damage(copy.data(), g.len) : 0;  // a guard that cannot be read counts as damaged
+    if (bad < 0) continue;
+    if (ctx->guard_damage.count++ == 0) {
+      ctx->guard_damage.arena = index;
+      ctx->guard_damage.offset = g.buf;
+      ctx->guard_damage.byte = g.at + (size_t)bad;
+    }
+  }
 }
 
 int kocr_ctx::ws_reserve(size_t bytes) { return arena_reserve(this, ws, bytes); }
@@ -1501,6 +1533,60 @@ int kocr_range_stats_report(kocr_ctx* ctx, int cap, char* names, double* values)
     ++i;
   }
   return i;
+}
+
+// ---- workspace arenas: for tests (include/kocr.h) ----
+int kocr_debug_arena_count(void) { return kocr_ctx::N_ARENAS; }
+
+const char* kocr_debug_arena_name(int i) { return kocr_ctx::arena_name(i); }
+
+int kocr_debug_arena_stats(kocr_ctx* ctx, int i, uint64_t* cap, uint64_t* requested, uint64_t* peak, uint64_t* excess) {
+  if (!ctx) return KOCR_EINVAL;
+  const Arena* a = ctx->arena_at(i);
+  if (!a) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_debug_arena_stats: no arena " + std::to_string(i));
+  if (cap) *cap = a->cap;
+  if (requested) *requested = a->requested;
+  if (peak) *peak = a->peak;
+  if (excess) *excess = a->excess;
+  return KOCR_OK;
+}
+
+int kocr_debug_release_arenas(kocr_ctx* ctx) {
+  if (!ctx) return KOCR_EINVAL;
+  KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) {
+    Arena& a = *ctx->arena_at(i);
+    if (a.base) KOCR_HIP(ctx, hipFree(a.base));
+    kocr_ctx* const gctx = a.gctx;
+    a = Arena{};
+    a.gctx = gctx;
+  }
+  ctx->invalidate_results();
+  ctx->guard_damage = kocr_ctx::GuardDamage{};
+  return KOCR_OK;
+}
+
+int kocr_debug_set_arena_guards(kocr_ctx* ctx, int on) {
+  if (!ctx) return KOCR_EINVAL;
+  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) {
+    Arena& a = *ctx->arena_at(i);
+    if (!a.guards.empty()) arena_guard_check(a);
+    // the next allocation of an arena comes behind a reset of it; until then its offsets stay what they are
+    a.gctx = on ? ctx : nullptr;
+  }
+  return KOCR_OK;
+}
+
+int kocr_debug_check_arena_guards(kocr_ctx* ctx, int* arena, uint64_t* offset, uint64_t* byte) {
+  if (!ctx) return KOCR_EINVAL;
+  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) arena_guard_check(*ctx->arena_at(i));
+  const kocr_ctx::GuardDamage d = ctx->guard_damage;
+  ctx->guard_damage = kocr_ctx::GuardDamage{};
+  if (arena) *arena = d.arena;
+  if (offset) *offset = d.offset;
+  if (byte) *byte = d.byte;
+  return d.count;
 }
 
 }  // extern "C"

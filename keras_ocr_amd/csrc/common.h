@@ -119,10 +119,38 @@ struct RangeRow {
   double launches = 0, elements = 0, nonzero = 0, below_m4 = 0, below_m14 = 0, sum_abs = 0, sum_abs_below_m4 = 0;
 };
 
+// A bump arena.  requested / peak / excess state how well the entry point's plan (the bytes it gave arena_reserve) covers what
+// it then took: peak is the largest offset an allocation reached (or, refused for want of room, would have reached) since the
+// last arena_reserve, excess the largest peak - requested over the arena's life -- the part of a plan's shortfall that the
+// slack of arena_reserve hides (kocr_debug_arena_stats).  Guard mode (kocr_debug_set_arena_guards; gctx
+// set): every allocation is followed by ARENA_GUARD_BYTES more, and the bytes from its end to the end of those are filled with
+// ARENA_GUARD_FILL on the stream at allocation time and compared by reset() and kocr_debug_check_arena_guards.  off stays the
+// offset the allocations would have reached without guards (gextra: what the guards have added), so the stats are the same.
+constexpr size_t ARENA_GUARD_BYTES = 256, ARENA_GUARD_RESERVE = (size_t)256 << 10;
+constexpr unsigned char ARENA_GUARD_FILL = 0xA5;
+struct ArenaGuard {
+  size_t buf, at, len;  // the buffer's offset in the arena; the guard's first byte behind it and its length
+};
+struct kocr_ctx;
 struct Arena {
   char* base = nullptr;
   size_t cap = 0, off = 0;
+  size_t requested = 0, peak = 0, excess = 0;
+  kocr_ctx* gctx = nullptr;  // guard mode: the context whose stream fills and whose record latches the damage
+  size_t gextra = 0;
+  std::vector<ArenaGuard> guards;  // of the allocations since the last check
+  inline void reset();
+  void note(size_t end) {  // an allocation that reaches (or would reach) `end`
+    if (end > peak) peak = end;
+    if (peak > requested && peak - requested > excess) excess = peak - requested;
+  }
 };
+// the first byte of a copied-back guard that is not ARENA_GUARD_FILL, or -1
+inline long arena_guard_damage(const unsigned char* copy, size_t len) {
+  for (size_t i = 0; i < len; ++i)
+    if (copy[i] != ARENA_GUARD_FILL) return (long)i;
+  return -1;
+}
 
 struct CraftNet;
 struct CrnnNet;
@@ -219,8 +247,20 @@ struct kocr_ctx {
   // pl = buffers that live for a whole kocr_pipeline call (padded batch, heat-maps, boxes)
   Arena ws, pp, pp2, io, pl;
   Arena bx;  // kocr_pipeline: the box buffer of a page with more boxes than the caller's cap (the pl arena holds the heat-maps)
+  // every arena by index, with its name (kocr_debug_arena_*; chw / chr are declared with the character boxes below)
+  static constexpr int N_ARENAS = 8;
+  inline Arena* arena_at(int i);
+  static const char* arena_name(int i) {
+    static const char* const names[N_ARENAS] = {"ws", "pp", "pp2", "io", "pl", "bx", "chw", "chr"};
+    return i >= 0 && i < N_ARENAS ? names[i] : nullptr;
+  }
+  // guard mode (tests): the damaged guards since the last kocr_debug_check_arena_guards, and the first of them
+  struct GuardDamage {
+    int count = 0, arena = -1;
+    size_t offset = 0, byte = 0;  // the buffer the guard follows; the first damaged byte (both offsets in the arena)
+  } guard_damage;
   int ws_reserve(size_t bytes);
-  void ws_reset() { ws.off = 0; }
+  void ws_reset() { ws.reset(); }
   void* ws_alloc(size_t bytes);
 
   // persistent allocations (weights)
@@ -419,13 +459,35 @@ struct kocr_ctx {
 };
 
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes);
+// guard mode only (api.cpp): the fill of one guard on the stream; the comparison of the recorded guards, which latches the
+// first damaged one in ctx->guard_damage and forgets the list
+void arena_guard_fill(Arena& a, size_t at, size_t len);
+void arena_guard_check(Arena& a);
+inline void Arena::reset() {
+  if (!guards.empty()) arena_guard_check(*this);
+  off = gextra = 0;
+}
 inline void* arena_alloc(Arena& a, size_t bytes) {
   const size_t o = (a.off + 255) & ~(size_t)255;
-  if (o + bytes > a.cap) return nullptr;
+  a.note(o + bytes);
+  if (!a.gctx) {
+    if (o + bytes > a.cap) return nullptr;
+    a.off = o + bytes;
+    return a.base + o;
+  }
+  const size_t at = o + a.gextra, end = at + bytes, glen = ((end + 255) & ~(size_t)255) + ARENA_GUARD_BYTES - end;
+  if (end + glen > a.cap) return nullptr;
   a.off = o + bytes;
-  return a.base + o;
+  a.gextra += ARENA_GUARD_BYTES;
+  a.guards.push_back(ArenaGuard{at, end, glen});
+  arena_guard_fill(a, end, glen);
+  return a.base + at;
 }
 inline void* kocr_ctx::ws_alloc(size_t bytes) { return arena_alloc(ws, bytes); }
+inline Arena* kocr_ctx::arena_at(int i) {
+  Arena* const all[N_ARENAS] = {&ws, &pp, &pp2, &io, &pl, &bx, &chw, &chr};
+  return i >= 0 && i < N_ARENAS ? all[i] : nullptr;
+}
 
 // RAII-less helper used around launches
 struct ProfScope {

@@ -309,6 +309,11 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
     const size_t o = (ctx->ws.off + 255) & ~(size_t)255;
     base = ctx->ws.base + o;
     room = ctx->ws.cap > o ? ctx->ws.cap - o : 0;
+    if (ctx->ws.gctx) {  // guard mode: the pool is one guarded allocation of its planned size
+      const size_t plan = craft_workspace_bytes(N, H, W) - 4096;
+      base = (char*)arena_alloc(ctx->ws, plan);
+      room = base ? plan : 0;
+    }
     KOCR_TRY(ctx->amax_begin());
   }
   // track = true: the tensor feeds a 3x3 convolution that may run in fp16 arithmetic (conv_w43h.hip); it carries one
@@ -525,6 +530,9 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
   done(k2);
 #undef RUN
   if (peak_out) *peak_out = pool.peak;
+  // the pool lives behind the arena's offset without moving it: what it reached, for the arena's book-keeping
+  if constexpr (!DRY)
+    if (!ctx->ws.gctx) ctx->ws.note(((ctx->ws.off + 255) & ~(size_t)255) + pool.peak);
   return KOCR_OK;
 }
 

@@ -278,7 +278,9 @@ static size_t pattern_crop_bytes(kocr_ctx* ctx, int M, const CrnnPattern& pt) {
   int NTmax, Smax;
   pattern_extent(ctx, M, pt, &NTmax, &Smax);
   const int C = std::max(crnn_classes(ctx), 2), To = std::max(crnn_label_width(ctx), 1);
-  const size_t bp = NTmax ? (pattern_bp_bytes(To, C, NTmax, Smax) + 255) & ~(size_t)255 : 0;
+  // as pattern_run launches: a batch of -1 rows runs with one node and one state, and its table may take the LDS that their
+  // back-pointers would have had
+  const size_t bp = (pattern_bp_bytes(To, C, std::max(NTmax, 1), std::max(Smax, 1)) + 255) & ~(size_t)255;
   return (size_t)To * C * sizeof(float) + bp;
 }
 
@@ -502,10 +504,11 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   {
     // Dense(64) over 11 200 features: split-K (crnn_kernels.hip); the weight rows must be in plain k order
     const ConvLayer& Ld = net->L["stn_dense_1"];
-    const bool no_sk = !ctx->sw.dense_splitk;
-    float* part = no_sk ? nullptr : (float*)ctx->ws_alloc(dense_splitk_workspace(M, 11200));
+    const bool sk = ctx->sw.dense_splitk && Ld.Cout == 64 && Ld.Cin == 11200;
+    float* part = sk ? (float*)ctx->ws_alloc(dense_splitk_workspace(M, 11200)) : nullptr;
+    if (sk && !part) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_crnn_forward: workspace exhausted");
     const Tensor flat = view(s2, M, 1, 1, 11200);
-    if (part && Ld.Cout == 64 && Ld.Cin == 11200)
+    if (sk)
       KOCR_TRY(tapped(ctx, "stn_dense_1", &flat, &d1, nullptr, [&]() { return launch_dense_splitk(ctx, Ld, s2.p, d1.p, part, M); }));
     else
       KOCR_TRY(conv("stn_dense_1", view(s2, M, 1, 1, 11200), d1));

@@ -994,8 +994,13 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   const size_t need = NP * (1 + 7 * 4) + (size_t)N * p.bpi * 8 + (size_t)N * 4 + (size_t)N * cap * 8 +
                       (size_t)N * cap * sizeof(CompInfo) + (size_t)(N + 1) * 4 + 64 + 20 * 256;
   KOCR_TRY(arena_reserve(ctx, ctx->pp, need));
-  ctx->pp.off = 0;
-  auto A = [&](size_t bytes) { return arena_alloc(ctx->pp, bytes); };
+  ctx->pp.reset();
+  bool got = true;  // every pointer of the run below, not only the last: a small one may fit where a large one did not
+  auto A = [&](size_t bytes) {
+    void* q = arena_alloc(ctx->pp, bytes);
+    got = got && q;
+    return q;
+  };
   p.flags = (unsigned char*)A(NP);
   p.label = (int*)A(NP * 4);
   p.area = (int*)A(NP * 4);
@@ -1012,7 +1017,7 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   p.info = (CompInfo*)A((size_t)N * cap * sizeof(CompInfo));
   p.img_base = (int*)A((size_t)(N + 1) * 4);
   p.totals = (int*)A(64);
-  if (!p.totals) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_get_boxes: scratch exhausted");
+  if (!got) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_get_boxes: scratch exhausted");
   if (dev) {
     dev->d_counts = p.counts;
     dev->d_totals = p.totals;
@@ -1062,8 +1067,12 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   const size_t cneed = (size_t)a.total * (1 + 1 + 4) + (size_t)ncomp * 4 + (size_t)a.total_rows * 8 +
                        ((size_t)a.total_rows * 4 + (size_t)ncomp * 8 + 16) * sizeof(int2) + 16 * 256;
   KOCR_TRY(arena_reserve(ctx, ctx->pp2, cneed));
-  ctx->pp2.off = 0;
-  auto B = [&](size_t bytes) { return arena_alloc(ctx->pp2, bytes); };
+  ctx->pp2.reset();
+  auto B = [&](size_t bytes) {
+    void* q = arena_alloc(ctx->pp2, bytes);
+    got = got && q;
+    return q;
+  };
   a.seg0 = (unsigned char*)B(a.total);
   a.seg1 = (unsigned char*)B(a.total);
   a.clabel = (int*)B((size_t)a.total * 4);
@@ -1071,7 +1080,7 @@ int postproc_get_boxes(kocr_ctx* ctx, const float* d_heat, int N, int h, int w, 
   a.rowmin = (int*)B((size_t)a.total_rows * 4);
   a.rowmax = (int*)B((size_t)a.total_rows * 4);
   a.hullbuf = (int2*)B(((size_t)a.total_rows * 4 + (size_t)ncomp * 8 + 16) * sizeof(int2));
-  if (!a.hullbuf) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_get_boxes: canvas scratch exhausted");
+  if (!got) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_get_boxes: canvas scratch exhausted");
   {
     ProfScope ps(ctx, "pp_canvas_boxes", 0, 0);
     hipLaunchKernelGGL(k_fill_int, grid_for(ncomp), dim3(256), 0, s, a.sel, ncomp, -1);

@@ -29,15 +29,18 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   return KOCR_OK;
 }
 int kocr_ctx::ws_reserve(size_t bytes) { return arena_reserve(this, ws, bytes); }
+void arena_guard_fill(Arena&, size_t, size_t) {}  // guard mode stays off here (scripts/host_arena_check.cpp drives it)
+void arena_guard_check(Arena&) {}
 int crnn_label_width(kocr_ctx*) { return LW; }
 int crnn_classes(kocr_ctx*) { return 37; }
 size_t crnn_workspace_bytes(int M, int) { return (size_t)M * 64; }
 size_t lexicon_workspace_bytes(kocr_ctx*, int M, bool) { return (size_t)M * 16; }
+size_t pattern_workspace_bytes(kocr_ctx*, int M, const CrnnPattern&) { return (size_t)M * 8; }
 int craft_micro_batch(int micro_batch, int N, int, int) { return std::min(micro_batch > 0 ? micro_batch : 32, N); }
 
 static long crops_seen;
 int crnn_forward(kocr_ctx*, const float* d_crops, int M, int* d_labels, float*, CrnnStop, float*, const float**, const CrnnScores* sc,
-                 const CrnnBeam* bm, const CrnnLexicon* lx) {
+                 const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask&, const CrnnPattern*) {
   const size_t m = (size_t)M;
   for (size_t i = 0; i < m * CRNN_CROP_PIXELS; ++i) CHECK(d_crops[i] == 0.f);
   memset(d_labels, 1, m * LW * 4);
