@@ -120,76 +120,52 @@ struct OrientWinners {
   float* pair = nullptr;    // [words][2]
 };
 
-// The recogniser stage of kocr_recognize_boxes / kocr_pipeline: its outputs for M crops on a context -- the label rows, and
-// what the context's switches add: score rows (scores), beam rows (BW > 0), lexicon rows (LK > 0), pattern rows (PT).  An
-// oriented run is the same stage over its 2 M candidate crops with scores forced on (no beam, no lexicon, no pattern:
-// orient_refusal).  each() is the one
-// list of the buffers: every pointer with its size.  cm: the character sets the crops are decoded under -- the context's
-// uniform switch unless the caller puts a per-crop list in its place (kocr_recognize_boxes_charsets).  pt: the pattern the
-// crops are also decoded under -- the context's switch, or a per-crop list (set_patterns: kocr_recognize_boxes_patterns).
+// The recogniser stage of kocr_recognize_boxes / kocr_pipeline: the request (CrnnDecode, common.h) that the context's switches
+// make for M crops -- the label rows always, score rows (scores), beam rows (beam width > 0), lexicon rows (top words > 0),
+// pattern rows (pattern switched on) -- and its buffers.  An oriented run is the same stage over its 2 M candidate crops with
+// scores forced on (no beam, no lexicon, no pattern: orient_refusal).  req.cm: the character sets the crops are decoded under
+// -- the context's uniform switch unless the caller puts a per-crop list in its place (kocr_recognize_boxes_charsets).  req.pt:
+// the pattern the crops are also decoded under -- the context's switch, or a per-crop list (set_patterns:
+// kocr_recognize_boxes_patterns).
 struct RecStage {
   kocr_ctx* ctx;
   long M;
-  int LW, BW, BK, LK;
-  bool scores, PT;
-  int32_t* lab = nullptr;
-  CrnnScores sc{nullptr, nullptr};
-  CrnnBeam bm;
-  CrnnLexicon lx;
-  CharMask cm;
-  CrnnPattern pt;
-  RecStage(kocr_ctx* c, long m, bool force_scores = false)
-      : ctx(c), M(m), LW(crnn_label_width(c)), BW(c->beam_width), BK(c->beam_top_paths), LK(c->lex_top),
-        scores(c->scores_on || force_scores), PT(c->pattern >= 0), bm{BW, BK, nullptr, nullptr}, lx{LK, nullptr, nullptr, nullptr},
-        cm(c->charmask()), pt{nullptr, nullptr, c->pattern, 0, nullptr, nullptr, nullptr} {}
+  int LW;
+  CrnnDecode req;
+  RecStage(kocr_ctx* c, long m, bool force_scores = false) : ctx(c), M(m), LW(crnn_label_width(c)) {
+    req.greedy = true;
+    req.sc.on = c->scores_on || force_scores;
+    req.bm.beam_width = c->beam_width;
+    req.bm.top_paths = c->beam_top_paths;
+    req.lx.top_words = c->lex_top;
+    req.pt.on = c->pattern >= 0;
+    req.pt.uniform = c->pattern;
+    req.cm = c->charmask();
+  }
   // one pattern per crop (HOST list and its device copy, [M]) in place of the context's switch; before bytes() / take()
   void set_patterns(const int32_t* of, const int32_t* d_of) {
-    PT = true;
-    pt.of = of;
-    pt.d_of = d_of;
-    pt.uniform = -1;
+    req.pt.on = true;
+    req.pt.of = of;
+    req.pt.d_of = d_of;
+    req.pt.uniform = -1;
   }
 
+  // the request's outputs, each for all M crops (no probabilities, no lexicon values: V plays no part)
   template <class F> int each(F f) {
-    const size_t m = (size_t)M, i4 = sizeof(int32_t), f4 = sizeof(float);
-    KOCR_TRY(f(lab, m * LW * i4));
-    if (scores) {
-      KOCR_TRY(f(sc.d_logw, m * f4));
-      KOCR_TRY(f(sc.d_chars, m * LW * f4));
-    }
-    if (BW) {
-      KOCR_TRY(f(bm.d_labels, m * BK * LW * i4));
-      KOCR_TRY(f(bm.d_logp, m * BK * f4));
-    }
-    if (LK) {
-      KOCR_TRY(f(lx.d_index, m * LK * i4));
-      KOCR_TRY(f(lx.d_logp, m * LK * f4));
-    }
-    if (PT) {
-      KOCR_TRY(f(pt.d_labels, m * LW * i4));
-      KOCR_TRY(f(pt.d_logpath, m * f4));
-      KOCR_TRY(f(pt.d_logp, m * f4));
-    }
-    return KOCR_OK;
+    return req.each(LW, crnn_classes(ctx), 0, [&](auto*& p, size_t b) { return f(p, (size_t)M * b); });
   }
   // (a) what take() needs of an arena, counted as Staging::reserve counts its buffers
   size_t bytes() { return staging_bytes(*this); }
   // (b) the buffers from `st`
   int take(Staging& st) { return staging_take(st, *this); }
-  // (c) the recogniser over d_crops [M][31][200]: ctx->ws sized for one batch (with the lexicon's share), every batch given
-  // its rows of the buffers
+  // (c) the recogniser over d_crops [M][31][200]: ctx->ws sized for one batch (with the lexicon's and the patterns' share),
+  // every batch given its rows of the buffers
   int run(const float* d_crops) {
-    const int mb = crnn_batch(M);
-    KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, crnn_classes(ctx)) + (LK ? lexicon_workspace_bytes(ctx, mb, true) : 0) +
-                             (PT ? pattern_workspace_bytes(ctx, (int)M, pt) : 0)));
+    const int mb = crnn_batch(M), C = crnn_classes(ctx);
+    KOCR_TRY(ctx->ws_reserve(crnn_workspace_bytes(mb, C) + (req.lx.top_words ? lexicon_workspace_bytes(ctx, mb, true) : 0) +
+                             (req.pt.on ? pattern_workspace_bytes(ctx, (int)M, req.pt) : 0)));
     return crnn_batches(ctx, M, [&](long s, int nb) {
-      const CrnnScores part{scores ? sc.d_logw + s : nullptr, scores ? sc.d_chars + s * LW : nullptr};
-      const CrnnBeam bpart{BW, BK, BW ? bm.d_labels + s * BK * LW : nullptr, BW ? bm.d_logp + s * BK : nullptr};
-      const CrnnLexicon lpart{LK, LK ? lx.d_index + s * LK : nullptr, LK ? lx.d_logp + s * LK : nullptr, nullptr};
-      const CrnnPattern ppart{pt.of, pt.d_of, pt.uniform, (int)s, PT ? pt.d_labels + s * LW : nullptr, PT ? pt.d_logpath + s : nullptr,
-                              PT ? pt.d_logp + s : nullptr};
-      return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, lab + s * LW, nullptr, CRNN_DECODE, nullptr, nullptr,
-                          scores ? &part : nullptr, BW ? &bpart : nullptr, LK ? &lpart : nullptr, cm.from((int)s), PT ? &ppart : nullptr);
+      return crnn_forward(ctx, d_crops + s * CRNN_CROP_PIXELS, nb, req.from(s, LW, C, 0));
     });
   }
   // (d) what the stage leaves resident for the getters, each record with the state of its switch.  An oriented run keeps its
@@ -197,10 +173,10 @@ struct RecStage {
   void keep(const OrientWinners* won = nullptr) const {
     const OrientWinners w = won ? *won : OrientWinners{};
     const int m = (int)(won ? w.words : M);
-    ctx->keep_rec_scores(won ? w.logw : sc.d_logw, won ? w.chars : sc.d_chars, m, LW);
-    ctx->keep_beams(bm.d_labels, bm.d_logp, m, LW);
-    ctx->keep_lexicon(lx.d_index, lx.d_logp, m);
-    ctx->keep_patterns(pt.d_labels, pt.d_logpath, pt.d_logp, m, LW, PT);
+    ctx->keep_rec_scores(won ? w.logw : req.sc.d_logw, won ? w.chars : req.sc.d_chars, m, LW);
+    ctx->keep_beams(req.bm.d_labels, req.bm.d_logp, m, LW);
+    ctx->keep_lexicon(req.lx.d_index, req.lx.d_logp, m);
+    ctx->keep_patterns(req.pt.d_labels, req.pt.d_logpath, req.pt.d_logp, m, LW, req.pt.on);
     ctx->keep_orientation(w.turn, w.quad, w.pair, (int)w.words);
   }
 };

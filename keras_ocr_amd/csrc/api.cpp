@@ -207,47 +207,111 @@ long prepare_box_warps(kocr_ctx* ctx, const char* fn, int N, const float* boxes,
   return M;
 }
 
-// kocr_crnn_forward, and with log_word / char_scores kocr_crnn_forward_scores (`fn`: the one that was called): the same
-// batches, with the score buffers ctc_scores_kernel as the last launch
-static int crnn_forward_call(kocr_ctx* ctx, const char* fn, const float* crops, int M, int32_t* labels, float* probs, float* log_word,
-                             float* char_scores, int on_device) {
-  const std::string f(fn);
-  if (M < 0 || (M > 0 && (!crops || !labels))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
-  const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+// The targets of a CTC loss as the caller gives them (HOST; validated by ctc_validate, which gives Lmax) and where the losses
+// [M] go
+struct CtcTargets {
+  const int32_t* labels;
+  int stride;
+  const int32_t* lengths;
+  const int32_t* input_lengths;
+  float* loss;
+  int Lmax = 0;
+  int row() const { return std::max(Lmax, 1); }                                   // columns of a staged label row
+  size_t staged_bytes() const { return (size_t)(row() + 2) * sizeof(int32_t); }  // per sample
+};
+// Rows [s, s + nb) of the targets in the workspace as [nb][row()] | len[nb] | in_len[nb]: `dev`.  `host` is the staging
+// vector: it has to outlive the asynchronous copy (the callers synchronise before it is reused or goes out of scope).
+struct CtcStaged {
+  std::vector<int32_t> host;
+  CtcLabels dev;
+};
+static int ctc_stage_labels(Staging& st, const CtcTargets& tg, long s, int nb, CtcStaged& out) {
+  const int ls = tg.row();
+  out.host.assign((size_t)nb * (ls + 2), -1);
+  for (int i = 0; i < nb; ++i) {
+    const long m = s + i;
+    for (int k = 0; k < tg.lengths[m]; ++k) out.host[(size_t)i * ls + k] = tg.labels[(size_t)m * tg.stride + k];
+    out.host[(size_t)nb * ls + i] = tg.lengths[m];
+    out.host[(size_t)nb * (ls + 1) + i] = tg.input_lengths[m];
+  }
+  const int32_t* d;
+  KOCR_TRY(st.upload(out.host.data(), out.host.size() * sizeof(int32_t), d));
+  out.dev = {d, ls, d + (size_t)nb * ls, d + (size_t)nb * (ls + 1), tg.Lmax};
+  return KOCR_OK;
+}
+
+// The staged call behind every recogniser entry point that decodes: kocr_crnn_forward / _forward_scores / _beam / _lexicon /
+// _pattern from crops, kocr_crnn_decode_logits / _charsets / _patterns from logits.  The entry validates its arguments, states
+// them as a request on the caller's buffers (CrnnDecode; cm is the driver's) and names what else its family has:
+struct CrnnSource {
+  const float* p;  // the caller's crops [M][31][200] (any M, batch by batch; device with on_device) ...
+  bool logits;     // ... or fc_12's logits [M][50][C] (HOST, at most one batch; with them the decode alone runs)
+};
+struct CrnnExtras {
+  // The output and host-list arguments of the entry.  The plan counts 256 bytes for each, given or null, as Staging::reserve does
+  // for an empty buffer.
+  int slots = 0, lists = 0;
+  size_t workspace = 0;              // lexicon_workspace_bytes / pattern_workspace_bytes of the call, where it has them
+  bool taps = false;                 // the call records the taps of kocr_crnn_set_taps
+  const int32_t* set_of = nullptr;   // HOST [M]: the crops' character sets in place of the context's switch
+  const CtcTargets* loss = nullptr;  // logits only: the loss launch on the same logits, behind the decode
+};
+// Workspace for crnn_batch(M) crops; per batch: the lists (set_of, the request's pt.of) and the source in, a buffer per output
+// of the request -- CrnnDecode::each is the one list of them and of their sizes --, the launches, every output back.
+static int crnn_call(kocr_ctx* ctx, const char* fn, CrnnSource src, int M, const CrnnDecode& host, bool on_device, const CrnnExtras& x) {
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const bool scores = log_word != nullptr;
-  const int mb = crnn_batch(M);
-  const int LW = crnn_label_width(ctx);
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = LW * sizeof(int32_t), pb = (size_t)LW * C * sizeof(float);
-  const size_t wb = sizeof(float), hb = LW * sizeof(float);
-  Staging st{ctx, ctx->ws, fn, on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, probs ? pb * mb : 0, scores ? wb * mb : 0, scores ? hb * mb : 0}));
+  const int mb = crnn_batch(M), LW = crnn_label_width(ctx), C = crnn_classes(ctx), V = ctx->lex.V;
+  const size_t i4 = sizeof(int32_t), f4 = sizeof(float), src_n = src.logits ? (size_t)CRNN_STEPS * C : CRNN_CROP_PIXELS;
+  size_t staged = src_n * f4 * mb + 256 + 256 * (size_t)x.slots, always = 256 * (size_t)x.lists;
+  CrnnDecode(host).each(LW, C, V, [&](auto*&, size_t b) {
+    staged += b * mb;
+    return KOCR_OK;
+  });
+  if (x.loss) staged += f4 * mb, always += x.loss->staged_bytes() * mb;
+  always += ((x.set_of ? i4 : 0) + (host.pt.of ? i4 : 0)) * mb;
+  Staging st{ctx, ctx->ws, fn, on_device};
+  KOCR_TRY(st.reserve((src.logits ? 0 : crnn_workspace_bytes(mb, C)) + x.workspace + (on_device ? 0 : staged) + always, {}));
+  CtcStaged tg;
+  auto batch = [&](long s, int nb) -> int {
+    if (x.taps) taps_batch(ctx, TAPS_CRNN, (int)s, nb);
+    const CrnnDecode h = host.from(s, LW, C, V);  // the caller's rows of this batch
+    CrnnDecode d = h;                             // ... and the device's; its lists are the batch's own, entry 0 its crop 0
+    const int32_t* d_set = nullptr;
+    if (x.set_of) KOCR_TRY(st.upload(x.set_of + s, i4 * nb, d_set));
+    d.cm = ctx->charmask(d_set, 0);
+    d.pt.first = 0;
+    if (h.pt.of) {
+      d.pt.of = h.pt.of + s;
+      KOCR_TRY(st.upload(d.pt.of, i4 * nb, d.pt.d_of));
+    }
+    const float* d_src;
+    KOCR_TRY(st.in(src.p + s * src_n, src_n * f4 * nb, d_src));
+    void* dev[CrnnDecode::MAX_OUTPUTS];
+    int n = 0;
+    KOCR_TRY(d.each(LW, C, V, [&](auto*& p, size_t b) -> int {
+      KOCR_TRY(st.out(p, b * nb, p));
+      dev[n++] = p;
+      return KOCR_OK;
+    }));
+    KOCR_TRY(src.logits ? crnn_decode_logits(ctx, d_src, nb, d) : crnn_forward(ctx, d_src, nb, d));
+    n = 0;
+    KOCR_TRY(CrnnDecode(h).each(LW, C, V, [&](auto*& p, size_t b) {
+      return st.back(p, (std::remove_reference_t<decltype(p)>)dev[n++], b * nb);
+    }));
+    if (x.loss) {
+      float* d_loss;
+      KOCR_TRY(ctc_stage_labels(st, *x.loss, s, nb, tg));
+      KOCR_TRY(st.out(x.loss->loss + s, f4 * nb, d_loss));
+      KOCR_TRY(crnn_logits_loss(ctx, d_src, nb, tg.dev, d_loss));
+      KOCR_TRY(st.back(x.loss->loss + s, d_loss, f4 * nb));
+    }
+    return st.finish();  // also: `tg` is reused or gone only after its copy
+  };
+  if (!x.taps) return crnn_batches(ctx, M, batch);
   KOCR_TRY(taps_begin(ctx, TAPS_CRNN, M));
   TapsEnd taps_end{ctx, TAPS_CRNN};
-  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    taps_batch(ctx, TAPS_CRNN, (int)s, nb);
-    const float* d_c;
-    int32_t* d_l;
-    float* d_p = nullptr;
-    CrnnScores sc{nullptr, nullptr};
-    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
-    KOCR_TRY(st.out(labels + s * LW, lb * nb, d_l));
-    if (probs) KOCR_TRY(st.out(probs + (size_t)s * LW * C, pb * nb, d_p));
-    if (scores) {
-      KOCR_TRY(st.out(log_word + s, wb * nb, sc.d_logw));
-      KOCR_TRY(st.out(char_scores + s * LW, hb * nb, sc.d_chars));
-    }
-    KOCR_TRY(crnn_forward(ctx, d_c, nb, d_l, d_p, CRNN_DECODE, nullptr, nullptr, scores ? &sc : nullptr, nullptr, nullptr, ctx->charmask()));
-    KOCR_TRY(st.back(labels + s * LW, d_l, lb * nb));
-    if (probs) KOCR_TRY(st.back(probs + (size_t)s * LW * C, d_p, pb * nb));
-    if (scores) {
-      KOCR_TRY(st.back(log_word + s, sc.d_logw, wb * nb));
-      KOCR_TRY(st.back(char_scores + s * LW, sc.d_chars, hb * nb));
-    }
-    return st.finish();
-  });
+  return crnn_batches(ctx, M, batch);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -415,8 +479,25 @@ int kocr_crnn_classes(kocr_ctx* ctx) { return ctx ? crnn_classes(ctx) : KOCR_EIN
 int kocr_crnn_label_width(kocr_ctx* ctx) { return ctx ? crnn_label_width(ctx) : KOCR_EINVAL; }
 int kocr_crnn_set_rnn_steps_to_discard(kocr_ctx* ctx, int steps) { return ctx ? crnn_set_discard(ctx, steps) : KOCR_EINVAL; }
 
+// kocr_crnn_forward, and with log_word / char_scores kocr_crnn_forward_scores (`fn`: the one that was called): the same
+// batches, with the score buffers ctc_scores_kernel as the last launch
+static int crnn_forward_call(kocr_ctx* ctx, const char* fn, const float* crops, int M, const CrnnDecode& rq, int on_device) {
+  const std::string f(fn);
+  if (M < 0 || (M > 0 && (!crops || !rq.d_labels))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+  CrnnExtras x;
+  x.slots = 4;
+  x.taps = true;
+  return crnn_call(ctx, fn, {crops, false}, M, rq, on_device != 0, x);
+}
+
 int kocr_crnn_forward(kocr_ctx* ctx, const float* crops, int M, int32_t* labels, float* probs, int on_device) {
-  return ctx ? crnn_forward_call(ctx, "kocr_crnn_forward", crops, M, labels, probs, nullptr, nullptr, on_device) : KOCR_EINVAL;
+  if (!ctx) return KOCR_EINVAL;
+  CrnnDecode rq;
+  rq.greedy = true;
+  rq.d_labels = labels;
+  rq.d_probs = probs;
+  return crnn_forward_call(ctx, "kocr_crnn_forward", crops, M, rq, on_device);
 }
 
 // kocr_crnn_forward with the scores of include/kocr.h ("Scores")
@@ -424,7 +505,12 @@ int kocr_crnn_forward_scores(kocr_ctx* ctx, const float* crops, int M, int32_t* 
                              float* char_scores, int on_device) {
   if (!ctx) return KOCR_EINVAL;
   if (M > 0 && (!log_word || !char_scores)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_forward_scores: null buffer");
-  return crnn_forward_call(ctx, "kocr_crnn_forward_scores", crops, M, labels, probs, log_word, char_scores, on_device);
+  CrnnDecode rq;
+  rq.greedy = true;
+  rq.d_labels = labels;
+  rq.d_probs = probs;
+  rq.sc = {log_word != nullptr, log_word, char_scores};
+  return crnn_forward_call(ctx, "kocr_crnn_forward_scores", crops, M, rq, on_device);
 }
 
 // The beam search of include/kocr.h ("Beam search") alone: the forward up to fc_12, then ctc_beam_kernel
@@ -433,26 +519,12 @@ int kocr_crnn_beam(kocr_ctx* ctx, const float* crops, int M, int beam_width, int
   if (!ctx) return KOCR_EINVAL;
   KOCR_TRY(beam_validate(ctx, "kocr_crnn_beam", beam_width, top_paths));
   if (M < 0 || (M > 0 && (!crops || !labels || !log_prob))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_beam: null buffer");
-  const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_beam: call kocr_load_crnn first");
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = crnn_batch(M);
-  const int LW = crnn_label_width(ctx);
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = (size_t)top_paths * LW * sizeof(int32_t), vb = top_paths * sizeof(float);
-  Staging st{ctx, ctx->ws, "kocr_crnn_beam", on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, lb * mb, vb * mb}));
-  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    const float* d_c;
-    CrnnBeam bm{beam_width, top_paths, nullptr, nullptr};
-    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
-    KOCR_TRY(st.out(labels + s * top_paths * LW, lb * nb, bm.d_labels));
-    KOCR_TRY(st.out(log_prob + s * top_paths, vb * nb, bm.d_logp));
-    KOCR_TRY(crnn_beam(ctx, d_c, nb, bm, ctx->charmask()));
-    KOCR_TRY(st.back(labels + s * top_paths * LW, bm.d_labels, lb * nb));
-    KOCR_TRY(st.back(log_prob + s * top_paths, bm.d_logp, vb * nb));
-    return st.finish();
-  });
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_beam: call kocr_load_crnn first");
+  CrnnDecode rq;
+  rq.bm = {beam_width, top_paths, labels, log_prob};
+  CrnnExtras x;
+  x.slots = 2;
+  return crnn_call(ctx, "kocr_crnn_beam", {crops, false}, M, rq, on_device != 0, x);
 }
 
 // ---- lexicon (include/kocr.h, "Lexicon") --------------------------------------------------------------------------------
@@ -525,50 +597,14 @@ int kocr_crnn_lexicon(kocr_ctx* ctx, const float* crops, int M, int top_words, i
   if (!ctx) return KOCR_EINVAL;
   if (top_words < 1 || top_words > 64) KOCR_TRY(lexicon_validate(ctx, "kocr_crnn_lexicon", top_words));
   if (M < 0 || (M > 0 && (!crops || !index || !log_prob))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_lexicon: null buffer");
-  const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_lexicon: call kocr_load_crnn first");
+  if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_lexicon: call kocr_load_crnn first");
   KOCR_TRY(lexicon_validate(ctx, "kocr_crnn_lexicon", top_words));
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = crnn_batch(M), V = ctx->lex.V;
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), ib = top_words * sizeof(int32_t), vb = top_words * sizeof(float);
-  const size_t ab = all_values ? (size_t)V * sizeof(float) : 0;
-  Staging st{ctx, ctx->ws, "kocr_crnn_lexicon", on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C) + lexicon_workspace_bytes(ctx, mb, !all_values), {cb * mb, ib * mb, vb * mb, ab * mb}));
-  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    const float* d_c;
-    CrnnLexicon lx{top_words, nullptr, nullptr, nullptr};
-    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
-    KOCR_TRY(st.out(index + s * top_words, ib * nb, lx.d_index));
-    KOCR_TRY(st.out(log_prob + s * top_words, vb * nb, lx.d_logp));
-    if (all_values) KOCR_TRY(st.out(all_values + (size_t)s * V, ab * nb, lx.d_all));
-    KOCR_TRY(crnn_lexicon(ctx, d_c, nb, lx, ctx->charmask()));
-    KOCR_TRY(st.back(index + s * top_words, lx.d_index, ib * nb));
-    KOCR_TRY(st.back(log_prob + s * top_words, lx.d_logp, vb * nb));
-    if (all_values) KOCR_TRY(st.back(all_values + (size_t)s * V, lx.d_all, ab * nb));
-    return st.finish();
-  });
-}
-
-// labels rows [s, s + nb) of a validated batch (ctc_validate) into the workspace as [nb][Lmax] | len[nb] | in_len[nb]; the
-// host staging vector is returned so that it outlives the asynchronous copy (the callers synchronise before returning)
-static int ctc_stage_labels(Staging& st, const int32_t* labels, int label_stride, const int32_t* label_lengths,
-                            const int32_t* input_lengths, long s, int nb, int Lmax, std::vector<int32_t>& host, const int** d_lab,
-                            const int** d_len, const int** d_in) {
-  const int ls = std::max(Lmax, 1);
-  host.assign((size_t)nb * (ls + 2), -1);
-  for (int i = 0; i < nb; ++i) {
-    const long m = s + i;
-    for (int k = 0; k < label_lengths[m]; ++k) host[(size_t)i * ls + k] = labels[(size_t)m * label_stride + k];
-    host[(size_t)nb * ls + i] = label_lengths[m];
-    host[(size_t)nb * (ls + 1) + i] = input_lengths[m];
-  }
-  const int32_t* d;
-  KOCR_TRY(st.upload(host.data(), host.size() * sizeof(int32_t), d));
-  *d_lab = d;
-  *d_len = d + (size_t)nb * ls;
-  *d_in = d + (size_t)nb * (ls + 1);
-  return KOCR_OK;
+  CrnnDecode rq;
+  rq.lx = {top_words, index, log_prob, all_values};
+  CrnnExtras x;
+  x.slots = 3;
+  x.workspace = lexicon_workspace_bytes(ctx, crnn_batch(M), !all_values);
+  return crnn_call(ctx, "kocr_crnn_lexicon", {crops, false}, M, rq, on_device != 0, x);
 }
 
 int kocr_ctc_batch_cost(kocr_ctx* ctx, const float* y_pred, int M, int T, int C, const int32_t* labels, int label_stride,
@@ -578,22 +614,21 @@ int kocr_ctc_batch_cost(kocr_ctx* ctx, const float* y_pred, int M, int T, int C,
   if (M < 0 || T < 1 || C < 1 || label_stride < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_ctc_batch_cost: bad sizes");
   if (M > 0 && (!y_pred || !labels || !label_lengths || !input_lengths || !loss))
     KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_ctc_batch_cost: null buffer");
-  int Lmax = 0;
-  KOCR_TRY(ctc_validate(ctx, fn, M, T, C, labels, label_stride, label_lengths, input_lengths, &Lmax));
+  CtcTargets tg{labels, label_stride, label_lengths, input_lengths, loss};
+  KOCR_TRY(ctc_validate(ctx, fn, M, T, C, labels, label_stride, label_lengths, input_lengths, &tg.Lmax));
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t yb = (size_t)M * T * C * sizeof(float), lb = (size_t)M * sizeof(float);
-  const size_t ib = (size_t)M * (std::max(Lmax, 1) + 2) * sizeof(int32_t);
   Staging st{ctx, ctx->ws, fn, on_device != 0};
-  KOCR_TRY(st.reserve(0, {yb, lb}, {ib}));
-  std::vector<int32_t> staged;
-  const int *d_lab, *d_len, *d_in;
-  KOCR_TRY(ctc_stage_labels(st, labels, label_stride, label_lengths, input_lengths, 0, M, Lmax, staged, &d_lab, &d_len, &d_in));
+  KOCR_TRY(st.reserve(0, {yb, lb}, {tg.staged_bytes() * M}));
+  CtcStaged staged;
+  KOCR_TRY(ctc_stage_labels(st, tg, 0, M, staged));
   const float* d_y;
   float* d_loss;
   KOCR_TRY(st.in(y_pred, yb, d_y));
   KOCR_TRY(st.out(loss, lb, d_loss));
-  KOCR_TRY(launch_ctc_loss(ctx, /*logits=*/false, d_y, M, T, C, 0, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
+  const CtcLabels& lab = staged.dev;
+  KOCR_TRY(launch_ctc_loss(ctx, /*logits=*/false, d_y, M, T, C, 0, lab.d_lab, lab.lstride, lab.d_len, lab.d_in_len, d_loss, lab.Lmax));
   KOCR_TRY(st.back(loss, d_loss, lb));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `staged` goes out of scope
   return KOCR_OK;
@@ -609,23 +644,22 @@ int kocr_crnn_ctc_loss(kocr_ctx* ctx, const float* crops, int M, const int32_t* 
   const int C = crnn_classes(ctx);
   if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_ctc_loss: call kocr_load_crnn first");
   const int LW = crnn_label_width(ctx);
-  int Lmax = 0;
-  KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, labels, label_stride, label_lengths, input_lengths, &Lmax));
+  CtcTargets tg{labels, label_stride, label_lengths, input_lengths, loss};
+  KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, labels, label_stride, label_lengths, input_lengths, &tg.Lmax));
   if (M == 0) return KOCR_OK;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int mb = crnn_batch(M);
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), ib = (std::max(Lmax, 1) + 2) * sizeof(int32_t);
+  const size_t cb = CRNN_CROP_PIXELS * sizeof(float);
   Staging st{ctx, ctx->ws, fn, on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, sizeof(float) * mb}, {ib * mb}));
-  std::vector<int32_t> staged;
+  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C), {cb * mb, sizeof(float) * mb}, {tg.staged_bytes() * mb}));
+  CtcStaged staged;
   return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    const int *d_lab, *d_len, *d_in;
-    KOCR_TRY(ctc_stage_labels(st, labels, label_stride, label_lengths, input_lengths, s, nb, Lmax, staged, &d_lab, &d_len, &d_in));
+    KOCR_TRY(ctc_stage_labels(st, tg, s, nb, staged));
     const float* d_c;
     float* d_loss;
     KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
     KOCR_TRY(st.out(loss + s, sizeof(float) * nb, d_loss));
-    KOCR_TRY(crnn_ctc_loss(ctx, d_c, nb, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
+    KOCR_TRY(crnn_ctc_loss(ctx, d_c, nb, staged.dev, d_loss));
     KOCR_TRY(st.back(loss + s, d_loss, sizeof(float) * nb));
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `staged` is reused by the next batch
     return KOCR_OK;
@@ -858,28 +892,20 @@ int kocr_crnn_pattern(kocr_ctx* ctx, const float* crops, int M, const int32_t* p
                       float* log_prob, int on_device) {
   if (!ctx) return KOCR_EINVAL;
   KOCR_TRY(pattern_args(ctx, "kocr_crnn_pattern", crops, M, pattern_of, labels, log_path, log_prob));
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const int mb = crnn_batch(M), LW = crnn_label_width(ctx), C = crnn_classes(ctx);
-  const size_t cb = CRNN_CROP_PIXELS * sizeof(float), lb = (size_t)LW * sizeof(int32_t), vb = sizeof(float);
-  const CrnnPattern whole{pattern_of, nullptr, ctx->pattern, 0, nullptr, nullptr, nullptr};
-  Staging st{ctx, ctx->ws, "kocr_crnn_pattern", on_device != 0};
-  KOCR_TRY(st.reserve(crnn_workspace_bytes(mb, C) + pattern_workspace_bytes(ctx, M, whole), {cb * mb, lb * mb, vb * mb, vb * mb},
-                      {pattern_of ? mb * sizeof(int32_t) : 0}));
-  return crnn_batches(ctx, M, [&](long s, int nb) -> int {
-    const float* d_c;
-    CrnnPattern pt{pattern_of ? pattern_of + s : nullptr, nullptr, ctx->pattern, 0, nullptr, nullptr, nullptr};
-    if (pattern_of) KOCR_TRY(st.upload(pattern_of + s, nb * sizeof(int32_t), pt.d_of));
-    KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
-    KOCR_TRY(st.out(labels + s * LW, lb * nb, pt.d_labels));
-    KOCR_TRY(st.out(log_path + s, vb * nb, pt.d_logpath));
-    KOCR_TRY(st.out(log_prob + s, vb * nb, pt.d_logp));
-    KOCR_TRY(crnn_pattern(ctx, d_c, nb, pt));
-    KOCR_TRY(st.back(labels + s * LW, pt.d_labels, lb * nb));
-    KOCR_TRY(st.back(log_path + s, pt.d_logpath, vb * nb));
-    KOCR_TRY(st.back(log_prob + s, pt.d_logp, vb * nb));
-    return st.finish();
-  });
+  CrnnDecode rq;
+  rq.pt = {true, pattern_of, nullptr, ctx->pattern, 0, labels, log_path, log_prob};
+  CrnnExtras x;
+  x.slots = 3;
+  x.lists = 1;
+  x.workspace = pattern_workspace_bytes(ctx, M, rq.pt);
+  return crnn_call(ctx, "kocr_crnn_pattern", {crops, false}, M, rq, on_device != 0, x);
+}
+
+// KOCR_EINVAL unless the logits of a development entry fit one recogniser batch
+static int one_batch(kocr_ctx* ctx, const char* fn, int M) {
+  if (M > CRNN_BATCH)
+    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": M " + std::to_string(M) + " exceeds one recogniser batch of " + std::to_string(CRNN_BATCH));
+  return KOCR_OK;
 }
 
 // Development entry (include/kocr.h): the pattern launches on the caller's logits (HOST)
@@ -888,121 +914,48 @@ int kocr_crnn_decode_logits_patterns(kocr_ctx* ctx, const float* logits, int M, 
   if (!ctx) return KOCR_EINVAL;
   const char* fn = "kocr_crnn_decode_logits_patterns";
   KOCR_TRY(pattern_args(ctx, fn, logits, M, pattern_of, labels, log_path, log_prob));
-  if (M > CRNN_BATCH)
-    KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": M " + std::to_string(M) + " exceeds one recogniser batch of " + std::to_string(CRNN_BATCH));
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t m = (size_t)M, LW = crnn_label_width(ctx), C = crnn_classes(ctx);
-  const size_t gb = m * CRNN_STEPS * C * sizeof(float), lb = m * LW * sizeof(int32_t), vb = m * sizeof(float);
-  CrnnPattern pt{pattern_of, nullptr, ctx->pattern, 0, nullptr, nullptr, nullptr};
-  Staging st{ctx, ctx->ws, fn, false};
-  KOCR_TRY(st.reserve(pattern_workspace_bytes(ctx, M, pt), {gb, lb, vb, vb}, {pattern_of ? m * sizeof(int32_t) : 0}));
-  const float* d_lg;
-  if (pattern_of) KOCR_TRY(st.upload(pattern_of, m * sizeof(int32_t), pt.d_of));
-  KOCR_TRY(st.in(logits, gb, d_lg));
-  KOCR_TRY(st.out(labels, lb, pt.d_labels));
-  KOCR_TRY(st.out(log_path, vb, pt.d_logpath));
-  KOCR_TRY(st.out(log_prob, vb, pt.d_logp));
-  KOCR_TRY(pattern_run(ctx, d_lg, M, pt));
-  KOCR_TRY(st.back(labels, pt.d_labels, lb));
-  KOCR_TRY(st.back(log_path, pt.d_logpath, vb));
-  KOCR_TRY(st.back(log_prob, pt.d_logp, vb));
-  return st.finish();
+  KOCR_TRY(one_batch(ctx, fn, M));
+  CrnnDecode rq;
+  rq.pt = {true, pattern_of, nullptr, ctx->pattern, 0, labels, log_path, log_prob};
+  CrnnExtras x;
+  x.slots = 3;
+  x.lists = 1;
+  x.workspace = pattern_workspace_bytes(ctx, M, rq.pt);
+  return crnn_call(ctx, fn, {logits, true}, M, rq, false, x);
 }
 
-// Development entry (include/kocr.h): crnn_forward's launches behind fc_12 on the caller's logits; set_of (HOST, nullable):
-// the crops' character sets in place of the context's switch
-static int decode_logits_call(kocr_ctx* ctx, const char* fn, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
-                              float* char_scores, int beam_width, int top_paths, int32_t* beam_labels, float* beam_log_prob,
-                              int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
-                              int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss,
+// What kocr_crnn_decode_logits and kocr_crnn_decode_logits_charsets (`fn`: the one that was called) share: crnn_forward's
+// launches behind fc_12 on the caller's logits, as `rq` on the caller's buffers states them, then the loss where tg.labels is
+// given; set_of (HOST, nullable): the crops' character sets in place of the context's switch
+static int decode_logits_call(kocr_ctx* ctx, const char* fn, const float* logits, int M, const CrnnDecode& rq, CtcTargets tg,
                               const int32_t* set_of) {
-  if (M < 0 || (M > 0 && (!logits || !labels))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null buffer");
-  if (!log_word != !char_scores) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: log_word and char_scores go together");
+  const std::string f(fn);
+  if (M < 0 || (M > 0 && (!logits || !rq.d_labels))) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
+  if (!rq.sc.d_logw != !rq.sc.d_chars) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": log_word and char_scores go together");
   const int C = crnn_classes(ctx);
-  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_decode_logits: call kocr_load_crnn first");
-  if (M > CRNN_BATCH)
-    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: M " + std::to_string(M) + " exceeds one recogniser batch of " +
-                                    std::to_string(CRNN_BATCH));
-  if (beam_width) {
-    KOCR_TRY(beam_validate(ctx, fn, beam_width, top_paths));
-    if (M > 0 && (!beam_labels || !beam_log_prob)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null beam buffer");
+  if (C == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
+  KOCR_TRY(one_batch(ctx, fn, M));
+  if (rq.bm.beam_width) {
+    KOCR_TRY(beam_validate(ctx, fn, rq.bm.beam_width, rq.bm.top_paths));
+    if (M > 0 && (!rq.bm.d_labels || !rq.bm.d_logp)) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null beam buffer");
   }
-  if (top_words) {
-    KOCR_TRY(lexicon_validate(ctx, fn, top_words));
-    if (M > 0 && (!lex_index || !lex_log_prob)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null lexicon buffer");
+  if (rq.lx.top_words) {
+    KOCR_TRY(lexicon_validate(ctx, fn, rq.lx.top_words));
+    if (M > 0 && (!rq.lx.d_index || !rq.lx.d_logp)) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null lexicon buffer");
   }
-  const int LW = crnn_label_width(ctx);
-  int Lmax = 0;
-  if (loss_labels) {
-    if (label_stride < 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: bad sizes");
-    if (M > 0 && (!label_lengths || !input_lengths || !loss)) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_decode_logits: null loss buffer");
-    KOCR_TRY(ctc_validate(ctx, fn, M, LW, C, loss_labels, label_stride, label_lengths, input_lengths, &Lmax));
+  if (tg.labels) {
+    if (tg.stride < 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": bad sizes");
+    if (M > 0 && (!tg.lengths || !tg.input_lengths || !tg.loss)) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null loss buffer");
+    KOCR_TRY(ctc_validate(ctx, fn, M, crnn_label_width(ctx), C, tg.labels, tg.stride, tg.lengths, tg.input_lengths, &tg.Lmax));
   }
   if (set_of) KOCR_TRY(charsets_validate(ctx, fn, set_of, M, "crop"));
-  if (M == 0) return KOCR_OK;
-  KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t m = (size_t)M, f = sizeof(float), V = top_words ? (size_t)ctx->lex.V : 0;
-  const size_t gb = m * CRNN_STEPS * C * f, lb = m * LW * sizeof(int32_t), pb = probs ? m * LW * C * f : 0;
-  const size_t wb = log_word ? m * f : 0, hb = log_word ? m * LW * f : 0;
-  const size_t bl = beam_width ? m * top_paths * LW * sizeof(int32_t) : 0, bv = beam_width ? m * top_paths * f : 0;
-  const size_t xi = top_words ? m * top_words * sizeof(int32_t) : 0, xv = top_words ? m * top_words * f : 0;
-  const size_t xa = lex_values ? m * V * f : 0, sb = loss_labels ? m * f : 0;
-  const size_t ib = loss_labels ? m * (std::max(Lmax, 1) + 2) * sizeof(int32_t) : 0;
-  Staging st{ctx, ctx->ws, fn, false};
-  KOCR_TRY(st.reserve(top_words ? lexicon_workspace_bytes(ctx, M, !lex_values) : 0,
-                      {gb, lb, pb, wb, hb, bl, bv, xi, xv, xa, sb}, {ib, set_of ? m * sizeof(int32_t) : 0}));
-  const float* d_lg;
-  const int32_t* d_set = nullptr;  // the caller's array outlives the copy: finish() synchronises
-  if (set_of) KOCR_TRY(st.upload(set_of, m * sizeof(int32_t), d_set));
-  int32_t* d_l;
-  float* d_p = nullptr;
-  CrnnScores sc{nullptr, nullptr};
-  CrnnBeam bm{beam_width, top_paths, nullptr, nullptr};
-  CrnnLexicon lx{top_words, nullptr, nullptr, nullptr};
-  KOCR_TRY(st.in(logits, gb, d_lg));
-  KOCR_TRY(st.out(labels, lb, d_l));
-  if (probs) KOCR_TRY(st.out(probs, pb, d_p));
-  if (log_word) {
-    KOCR_TRY(st.out(log_word, wb, sc.d_logw));
-    KOCR_TRY(st.out(char_scores, hb, sc.d_chars));
-  }
-  if (beam_width) {
-    KOCR_TRY(st.out(beam_labels, bl, bm.d_labels));
-    KOCR_TRY(st.out(beam_log_prob, bv, bm.d_logp));
-  }
-  if (top_words) {
-    KOCR_TRY(st.out(lex_index, xi, lx.d_index));
-    KOCR_TRY(st.out(lex_log_prob, xv, lx.d_logp));
-    if (lex_values) KOCR_TRY(st.out(lex_values, xa, lx.d_all));
-  }
-  KOCR_TRY(crnn_decode_logits(ctx, d_lg, M, d_l, d_p, log_word ? &sc : nullptr, beam_width ? &bm : nullptr, top_words ? &lx : nullptr,
-                              ctx->charmask(d_set, 0)));
-  KOCR_TRY(st.back(labels, d_l, lb));
-  if (probs) KOCR_TRY(st.back(probs, d_p, pb));
-  if (log_word) {
-    KOCR_TRY(st.back(log_word, sc.d_logw, wb));
-    KOCR_TRY(st.back(char_scores, sc.d_chars, hb));
-  }
-  if (beam_width) {
-    KOCR_TRY(st.back(beam_labels, bm.d_labels, bl));
-    KOCR_TRY(st.back(beam_log_prob, bm.d_logp, bv));
-  }
-  if (top_words) {
-    KOCR_TRY(st.back(lex_index, lx.d_index, xi));
-    KOCR_TRY(st.back(lex_log_prob, lx.d_logp, xv));
-    if (lex_values) KOCR_TRY(st.back(lex_values, lx.d_all, xa));
-  }
-  std::vector<int32_t> staged;
-  if (loss_labels) {
-    const int *d_lab, *d_len, *d_in;
-    float* d_loss;
-    KOCR_TRY(ctc_stage_labels(st, loss_labels, label_stride, label_lengths, input_lengths, 0, M, Lmax, staged, &d_lab, &d_len, &d_in));
-    KOCR_TRY(st.out(loss, sb, d_loss));
-    KOCR_TRY(crnn_logits_loss(ctx, d_lg, M, d_lab, std::max(Lmax, 1), d_len, d_in, d_loss, Lmax));
-    KOCR_TRY(st.back(loss, d_loss, sb));
-  }
-  return st.finish();  // also keeps `staged` alive until its copy is done
+  CrnnExtras x;
+  x.slots = 10;
+  x.lists = 2;
+  x.workspace = rq.lx.top_words ? lexicon_workspace_bytes(ctx, M, !rq.lx.d_all) : 0;
+  x.set_of = set_of;
+  x.loss = tg.labels ? &tg : nullptr;
+  return crnn_call(ctx, fn, {logits, true}, M, rq, false, x);
 }
 
 int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
@@ -1010,9 +963,15 @@ int kocr_crnn_decode_logits(kocr_ctx* ctx, const float* logits, int M, int32_t* 
                             int top_words, int32_t* lex_index, float* lex_log_prob, float* lex_values, const int32_t* loss_labels,
                             int label_stride, const int32_t* label_lengths, const int32_t* input_lengths, float* loss) {
   if (!ctx) return KOCR_EINVAL;
-  return decode_logits_call(ctx, "kocr_crnn_decode_logits", logits, M, labels, probs, log_word, char_scores, beam_width, top_paths,
-                            beam_labels, beam_log_prob, top_words, lex_index, lex_log_prob, lex_values, loss_labels, label_stride,
-                            label_lengths, input_lengths, loss, nullptr);
+  CrnnDecode rq;
+  rq.greedy = true;
+  rq.d_labels = labels;
+  rq.d_probs = probs;
+  rq.sc = {log_word != nullptr, log_word, char_scores};
+  rq.bm = {beam_width, top_paths, beam_labels, beam_log_prob};
+  rq.lx = {top_words, lex_index, lex_log_prob, lex_values};
+  const CtcTargets tg{loss_labels, label_stride, label_lengths, input_lengths, loss};
+  return decode_logits_call(ctx, "kocr_crnn_decode_logits", logits, M, rq, tg, nullptr);
 }
 
 int kocr_crnn_decode_logits_charsets(kocr_ctx* ctx, const float* logits, int M, int32_t* labels, float* probs, float* log_word,
@@ -1021,9 +980,15 @@ int kocr_crnn_decode_logits_charsets(kocr_ctx* ctx, const float* logits, int M, 
                                      const int32_t* loss_labels, int label_stride, const int32_t* label_lengths,
                                      const int32_t* input_lengths, float* loss, const int32_t* set_of) {
   if (!ctx) return KOCR_EINVAL;
-  return decode_logits_call(ctx, "kocr_crnn_decode_logits_charsets", logits, M, labels, probs, log_word, char_scores, beam_width,
-                            top_paths, beam_labels, beam_log_prob, top_words, lex_index, lex_log_prob, lex_values, loss_labels,
-                            label_stride, label_lengths, input_lengths, loss, set_of);
+  CrnnDecode rq;
+  rq.greedy = true;
+  rq.d_labels = labels;
+  rq.d_probs = probs;
+  rq.sc = {log_word != nullptr, log_word, char_scores};
+  rq.bm = {beam_width, top_paths, beam_labels, beam_log_prob};
+  rq.lx = {top_words, lex_index, lex_log_prob, lex_values};
+  const CtcTargets tg{loss_labels, label_stride, label_lengths, input_lengths, loss};
+  return decode_logits_call(ctx, "kocr_crnn_decode_logits_charsets", logits, M, rq, tg, set_of);
 }
 
 int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, int on_device) {
@@ -1043,7 +1008,7 @@ int kocr_crnn_features(kocr_ctx* ctx, const float* crops, int M, float* feats, i
     float* d_f;
     KOCR_TRY(st.in(crops + s * CRNN_CROP_PIXELS, cb * nb, d_c));
     KOCR_TRY(st.out(feats + s * fpc, fb * nb, d_f));
-    KOCR_TRY(crnn_forward(ctx, d_c, nb, nullptr, nullptr, CRNN_FEATURES, d_f));
+    KOCR_TRY(crnn_features(ctx, d_c, nb, d_f));
     KOCR_TRY(st.back(feats + s * fpc, d_f, fb * nb));
     return st.finish();
   });

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include "../../include/kocr.h"
 
 // ---------------------------------------------------------------------------------------
@@ -657,54 +658,106 @@ int crnn_classes(kocr_ctx* ctx);
 int crnn_label_width(kocr_ctx* ctx);  // 50 - rnn_steps_to_discard (48)
 int crnn_set_discard(kocr_ctx* ctx, int d);
 size_t crnn_workspace_bytes(int M, int n_classes);
-// How far crnn_forward runs: the whole recogniser with the greedy decode (kocr_crnn_forward), up to fc_12's logits
-// (kocr_crnn_ctc_loss: *d_logits = [M][50][n_classes] in the workspace), or up to the Concatenate output (kocr_crnn_features:
-// written to d_feats [M][50][256] instead of the workspace).  The launches before the stop are the same in all three.
-enum CrnnStop { CRNN_DECODE, CRNN_LOGITS, CRNN_FEATURES };
-// sc (CRNN_DECODE only): the decode's launch also writes the word log-probabilities [M] and the character scores
-// [M][crnn_label_width()] (ctc_scores_kernel instead of ctc_kernel; the label rows and probabilities are the same bits).
+// What runs behind fc_12 on a batch's logits, and where its results go: one request for crnn_forward, crnn_decode_logits,
+// the recogniser stage (abi.h) and the staged calls of api.cpp.  Each member carries its own "off".
+// sc: the greedy decode's launch also writes the word log-probabilities [M] and the character scores [M][crnn_label_width()]
+// (ctc_scores_kernel instead of ctc_kernel; the label rows and probabilities are the same bits).
 struct CrnnScores {
-  float* d_logw;
-  float* d_chars;
+  bool on = false;
+  float* d_logw = nullptr;
+  float* d_chars = nullptr;
 };
-// bm (CRNN_DECODE only): after the decode, ctc_beam_kernel on the same logits: d_labels [M][top_paths][crnn_label_width()],
-// d_logp [M][top_paths].  The decode's own launch and results are untouched.
+// bm (beam_width > 0): ctc_beam_kernel on the same logits: d_labels [M][top_paths][crnn_label_width()], d_logp [M][top_paths].
 struct CrnnBeam {
-  int beam_width, top_paths;
-  int* d_labels;
-  float* d_logp;
+  int beam_width = 0, top_paths = 0;
+  int* d_labels = nullptr;
+  float* d_logp = nullptr;
 };
-// lx (CRNN_DECODE only): after the decode (and the beam), the three lexicon launches on the same logits: d_index / d_logp
-// [M][top_words]; d_all (nullable) [M][V]: lexicon_score_kernel's own values, else they live in workspace scratch.
+// lx (top_words > 0): after the beam, the three lexicon launches on the same logits: d_index / d_logp [M][top_words]; d_all
+// (nullable) [M][V]: lexicon_score_kernel's own values, else they live in workspace scratch.
 struct CrnnLexicon {
-  int top_words;
-  int* d_index;
-  float* d_logp;
-  float* d_all;
+  int top_words = 0;
+  int* d_index = nullptr;
+  float* d_logp = nullptr;
+  float* d_all = nullptr;
 };
-// pt (CRNN_DECODE only): after the decode (and the beam, the lexicon match), lexicon_logq_kernel<false> and the two pattern
-// launches on the same logits, never masked: crop m under pattern of[first + m] (HOST list; d_of its device copy), or under
-// `uniform` when `of` is null; -1: none (a -1 / -inf row).  d_labels [M][crnn_label_width()], d_logpath / d_logp [M].
+// pt (on): after the lexicon match, lexicon_logq_kernel<false> and the two pattern launches on the same logits, never masked:
+// crop m under pattern of[first + m] (HOST list; d_of its device copy), or under `uniform` when `of` is null; -1: none (a -1 /
+// -inf row: a run like any other, so "off" is a flag of its own).  d_labels [M][crnn_label_width()], d_logpath / d_logp [M].
 struct CrnnPattern {
-  const int32_t* of;
-  const int32_t* d_of;
-  int uniform;
-  int first;
-  int* d_labels;
-  float* d_logpath;
-  float* d_logp;
+  bool on = false;
+  const int32_t* of = nullptr;
+  const int32_t* d_of = nullptr;
+  int uniform = -1;
+  int first = 0;
+  int* d_labels = nullptr;
+  float* d_logpath = nullptr;
+  float* d_logp = nullptr;
 };
-// cm: the character sets of the batch's crops (CharMask above; off by default).  Every decode launch behind fc_12 -- the greedy
-// decode or the scores, the beam, the lexicon launches -- reads its rows through it; the logits themselves, the taps, the loss
-// and the features are never masked.
-int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop = CRNN_DECODE,
-                 float* d_feats = nullptr, const float** d_logits = nullptr, const CrnnScores* sc = nullptr,
-                 const CrnnBeam* bm = nullptr, const CrnnLexicon* lx = nullptr, const CharMask& cm = CharMask{},
-                 const CrnnPattern* pt = nullptr);
-// crnn_forward to the logits, then the pattern launches alone (kocr_crnn_pattern)
-int crnn_pattern(kocr_ctx* ctx, const float* d_crops, int M, const CrnnPattern& pt);
-// the pattern launches on logits [M][50][n_classes] that are already on the device (kocr_crnn_decode_logits_patterns)
-int pattern_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnPattern& pt);
+// greedy: the decode launch itself, d_labels [M][crnn_label_width()] and (nullable) d_probs [M][crnn_label_width()][C]; off,
+// nothing is launched for it (kocr_crnn_beam / _lexicon / _pattern).  The switches are flags rather than null pointers because
+// the recogniser stage lists its buffers before they have addresses.
+// cm: the character sets of the batch's crops (CharMask above; off by default).  Every decode launch behind fc_12 but the
+// patterns' reads its rows through it; the logits themselves, the taps, the loss and the features are never masked.
+struct CrnnDecode {
+  bool greedy = false;
+  int* d_labels = nullptr;
+  float* d_probs = nullptr;
+  CrnnScores sc;
+  CrnnBeam bm;
+  CrnnLexicon lx;
+  CrnnPattern pt;
+  CharMask cm;
+  static constexpr int MAX_OUTPUTS = 12;
+  // THE list of the outputs: f(pointer&, bytes per crop) for every one the request produces, for label rows of LW columns, C
+  // classes and a lexicon of V words; stops at the first failure
+  template <class F> int each(int LW, int C, int V, F f) {
+    const size_t lw = (size_t)LW, i4 = sizeof(int32_t), f4 = sizeof(float);
+    if (greedy) {
+      KOCR_TRY(f(d_labels, lw * i4));
+      if (d_probs) KOCR_TRY(f(d_probs, lw * C * f4));
+    }
+    if (sc.on) {
+      KOCR_TRY(f(sc.d_logw, f4));
+      KOCR_TRY(f(sc.d_chars, lw * f4));
+    }
+    if (bm.beam_width) {
+      KOCR_TRY(f(bm.d_labels, bm.top_paths * lw * i4));
+      KOCR_TRY(f(bm.d_logp, bm.top_paths * f4));
+    }
+    if (lx.top_words) {
+      KOCR_TRY(f(lx.d_index, lx.top_words * i4));
+      KOCR_TRY(f(lx.d_logp, lx.top_words * f4));
+      if (lx.d_all) KOCR_TRY(f(lx.d_all, (size_t)V * f4));
+    }
+    if (pt.on) {
+      KOCR_TRY(f(pt.d_labels, lw * i4));
+      KOCR_TRY(f(pt.d_logpath, f4));
+      KOCR_TRY(f(pt.d_logp, f4));
+    }
+    return KOCR_OK;
+  }
+  // the same request for the crops from `s` on: every output at its row s, the per-crop lists read from entry s
+  CrnnDecode from(long s, int LW, int C, int V) const {
+    CrnnDecode r = *this;
+    r.each(LW, C, V, [s](auto*& p, size_t b) {
+      p = (std::remove_reference_t<decltype(p)>)((char*)p + (size_t)s * b);
+      return KOCR_OK;
+    });
+    r.cm = cm.from((int)s);
+    r.pt.first += (int)s;
+    return r;
+  }
+};
+// The recogniser on d_crops [M][31][200] (device), three ways over one body -- the launches up to the stop are the same in all
+// three: up to the Concatenate output, written to d_feats [M][50][256] (kocr_crnn_features); up to fc_12's logits, *d_logits =
+// [M][50][n_classes] in the workspace (crnn_ctc_loss); the whole recogniser with what `rq` asks for behind fc_12.
+int crnn_features(kocr_ctx* ctx, const float* d_crops, int M, float* d_feats);
+int crnn_logits(kocr_ctx* ctx, const float* d_crops, int M, const float** d_logits);
+int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, const CrnnDecode& rq);
+// crnn_forward's launches behind fc_12 alone, on the caller's logits [M][50][n_classes] (device): the same launch functions with
+// the same arguments.  No taps, nothing resident changes.
+int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, const CrnnDecode& rq);
 // Crops per chunk of the pattern launches: as many as lex_scratch bytes (kocr_set_lexicon_scratch) hold of what a crop takes
 // -- its To x C table and, when they leave LDS, its back-pointers -- clamp(lex_scratch / per crop, 1, M), for the patterns the
 // M crops from pt.first on run under; and the workspace bytes that the launches of any recogniser batch (at most 1024 crops)
@@ -717,8 +770,6 @@ void patterns_unload(kocr_ctx* ctx);
 int patterns_validate(kocr_ctx* ctx, const char* fn, const int32_t* pattern_of, long M, const char* what);
 // KOCR_EINVAL when a pattern cannot run here: an active character set (kocr_set_charset), or orientation
 int pattern_refusal(kocr_ctx* ctx, const char* fn);
-// crnn_forward to the logits, then the lexicon launches alone (kocr_crnn_lexicon)
-int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx, const CharMask& cm = CharMask{});
 // Crops per chunk of the lexicon launches: as many as lex_scratch bytes of values hold, clamp(lex_scratch / (4 V), 1, M);
 // and the workspace bytes the launches take on top of crnn_workspace_bytes(M) (own_values: no d_all buffer is given)
 int lexicon_chunk(const kocr_ctx* ctx, int M);
@@ -731,21 +782,20 @@ void lexicon_unload(kocr_ctx* ctx, int dropped_classes);
 void charsets_unload(kocr_ctx* ctx);
 // KOCR_EINVAL naming the entry unless each of set_of[0 .. M) (HOST) lies in [-1, S); `what`: what an entry belongs to ("box")
 int charsets_validate(kocr_ctx* ctx, const char* fn, const int32_t* set_of, long M, const char* what);
-// crnn_forward to the logits, then ctc_beam_kernel alone (kocr_crnn_beam)
-int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm, const CharMask& cm = CharMask{});
 // KOCR_EINVAL naming the argument unless 1 <= beam_width <= 64 and 1 <= top_paths <= beam_width
 int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths);
-// training_model (recognition.py:334-349): crnn_forward to the logits, then ctc_loss_kernel on fc_12's softmax of frames
+// training_model (recognition.py:334-349): crnn_logits, then ctc_loss_kernel on fc_12's softmax of frames
 // rnn_steps_to_discard .. + input_length - 1; labels / lengths already validated (ctc_validate) and on the device
-int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
-                  float* d_loss, int Lmax);
+struct CtcLabels {  // device: label rows [M][lstride], their lengths [M] (at most Lmax), the input lengths [M]
+  const int* d_lab = nullptr;
+  int lstride = 0;
+  const int* d_len = nullptr;
+  const int* d_in_len = nullptr;
+  int Lmax = 0;
+};
+int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const CtcLabels& lab, float* d_loss);
 // the same loss launch on logits [M][50][n_classes] that are already on the device (crnn_ctc_loss's tail; kocr_crnn_decode_logits)
-int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
-                     float* d_loss, int Lmax);
-// crnn_forward's launches behind fc_12 on the caller's logits [M][50][n_classes] (device): the decode (with sc: the scores), then
-// the beam, then the lexicon match -- the same launch functions with the same arguments.  No taps, nothing resident changes.
-int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
-                       const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm = CharMask{});
+int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const CtcLabels& lab, float* d_loss);
 // keras.backend.ctc_batch_cost's refusals on host arrays, before anything is launched: T_m in [1, T],
 // L_m in [0, min(T_m, label_stride)], labels[m][0 .. L_m) in [0, C - 2]; KOCR_EINVAL naming the sample.  *Lmax = max L_m.
 int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32_t* labels, int label_stride,

@@ -296,7 +296,7 @@ size_t pattern_workspace_bytes(kocr_ctx* ctx, int M, const CrnnPattern& pt) {
 
 // lexicon_logq (unmasked), pattern_viterbi, pattern_rescore on the logits [M][T][C] of a batch, chunk by chunk.  The chunk and
 // the launch's extent follow the patterns of the whole batch: a crop's rows do not depend on either.
-int pattern_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnPattern& pt) {
+static int pattern_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnPattern& pt) {
   if (M <= 0) return KOCR_OK;
   const auto& pats = ctx->patterns;
   const int C = ctx->crnn->n_classes, discard = ctx->crnn->discard, To = T - discard;
@@ -320,30 +320,39 @@ int pattern_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnPattern& pt) 
   return KOCR_OK;
 }
 
-// The launches behind fc_12 on the logits [M][T][C] of a batch, shared by crnn_forward and crnn_decode_logits: the greedy decode
-// (with the scores when sc is given) ...
-static int decode_launch(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
-                         const CharMask& cm) {
+// The launches behind fc_12 on the logits [M][T][C] of a batch, for crnn_forward (`lg`: the logits as the "ctc" tap's input) and
+// crnn_decode_logits (no taps): the greedy decode (with the scores when asked for), then the beam search, the lexicon match
+// and the pattern decode, each where `rq` asks for it
+static int decode_run(kocr_ctx* ctx, const float* d_lg, int M, const CrnnDecode& rq, const Tensor* lg = nullptr) {
   const CrnnNet* net = ctx->crnn;
-  if (sc) return launch_ctc_scores(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, sc->d_logw, sc->d_chars, cm);
-  return launch_ctc(ctx, d_lg, M, T, net->n_classes, net->discard, d_labels, d_probs, cm);
-}
-// ... then the beam search, the lexicon match and the pattern decode, each where asked for
-static int decode_extras(kocr_ctx* ctx, const float* d_lg, int M, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm,
-                         const CrnnPattern* pt = nullptr) {
-  const CrnnNet* net = ctx->crnn;
-  if (bm)
-    KOCR_TRY(launch_ctc_beam(ctx, d_lg, M, T, net->n_classes, net->discard, bm->beam_width, bm->top_paths, bm->d_labels, bm->d_logp, cm));
-  if (lx) KOCR_TRY(lexicon_run(ctx, d_lg, M, *lx, cm));
-  if (pt) KOCR_TRY(pattern_run(ctx, d_lg, M, *pt));
+  const int C = net->n_classes, discard = net->discard;
+  if (rq.greedy) {
+    auto greedy = [&]() {
+      if (rq.sc.on) return launch_ctc_scores(ctx, d_lg, M, T, C, discard, rq.d_labels, rq.d_probs, rq.sc.d_logw, rq.sc.d_chars, rq.cm);
+      return launch_ctc(ctx, d_lg, M, T, C, discard, rq.d_labels, rq.d_probs, rq.cm);
+    };
+    if (lg) {
+      Tensor probs;  // tap view [M][1][LW][C] (not recorded without d_probs)
+      probs.N = M;
+      probs.H = 1;
+      probs.W = T - discard;
+      probs.C = probs.cs = C;
+      probs.p = rq.d_probs;
+      KOCR_TRY(tapped(ctx, "ctc", lg, &probs, nullptr, greedy));
+    } else {
+      KOCR_TRY(greedy());
+    }
+  }
+  if (rq.bm.beam_width)
+    KOCR_TRY(launch_ctc_beam(ctx, d_lg, M, T, C, discard, rq.bm.beam_width, rq.bm.top_paths, rq.bm.d_labels, rq.bm.d_logp, rq.cm));
+  if (rq.lx.top_words) KOCR_TRY(lexicon_run(ctx, d_lg, M, rq.lx, rq.cm));
+  if (rq.pt.on) KOCR_TRY(pattern_run(ctx, d_lg, M, rq.pt));
   return KOCR_OK;
 }
 
-// d_crops: device [M][31][200]; d_labels: device [M][LW]; d_probs: device [M][LW][C] or null, LW = crnn_label_width (48);
-// `stop` / d_feats / d_logits / sc / bm / lx: common.h
-int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, float* d_probs, CrnnStop stop, float* d_feats,
-                 const float** d_logits, const CrnnScores* sc, const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm,
-                 const CrnnPattern* pt) {
+// The one body of crnn_features / crnn_logits / crnn_forward (common.h): exactly one of d_feats, d_logits and rq is given.
+// d_crops: device [M][31][200]
+static int crnn_run(kocr_ctx* ctx, const float* d_crops, int M, float* d_feats, const float** d_logits, const CrnnDecode* rq) {
   CrnnNet* net = ctx->crnn;
   if (!net || !net->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_forward: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
@@ -526,49 +535,36 @@ int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, int* d_labels, floa
   KOCR_TRY(mk(M, T, 1, 8 * UNITS, &xp));
   KOCR_TRY(mk(M, T, 1, 2 * UNITS, &r1));
   KOCR_TRY(mk(M, T, 1, 2 * UNITS, &r2));
-  if (stop == CRNN_FEATURES) r2.p = d_feats;  // the backbone's output (recognition.py:319-320) goes straight to the caller
+  if (d_feats) r2.p = d_feats;  // the backbone's output (recognition.py:319-320) goes straight to the caller
   KOCR_TRY(conv("lstm_10_xproj", f9, xp));
   KOCR_TRY(tapped(ctx, "lstm_10", &xp, &r1, nullptr, [&]() { return launch_lstm(ctx, xp.p, net->U[0], net->U[1], r1.p, M, T); }));
   KOCR_TRY(conv("lstm_11_xproj", r1, xp));
   KOCR_TRY(tapped(ctx, "lstm_11", &xp, &r2, nullptr, [&]() { return launch_lstm(ctx, xp.p, net->U[2], net->U[3], r2.p, M, T); }));
-  if (stop == CRNN_FEATURES) return KOCR_OK;
+  if (d_feats) return KOCR_OK;
   // fc_12 + softmax + decode (recognition.py:321-328, 169-184)
   KOCR_TRY(mk(M, T, 1, net->n_classes, &lg));
   KOCR_TRY(conv("fc_12", r2, lg));
-  if (stop == CRNN_LOGITS) {
+  if (d_logits) {
     *d_logits = lg.p;
     return KOCR_OK;
   }
-  Tensor probs;  // tap view [M][1][LW][C] (not recorded without d_probs)
-  probs.N = M;
-  probs.H = 1;
-  probs.W = T - net->discard;
-  probs.C = probs.cs = net->n_classes;
-  probs.p = d_probs;
-  KOCR_TRY(tapped(ctx, "ctc", &lg, &probs, nullptr, [&]() { return decode_launch(ctx, lg.p, M, d_labels, d_probs, sc, cm); }));
-  return decode_extras(ctx, lg.p, M, bm, lx, cm, pt);
+  return decode_run(ctx, lg.p, M, *rq, &lg);
 }
 
-int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, int* d_labels, float* d_probs, const CrnnScores* sc,
-                       const CrnnBeam* bm, const CrnnLexicon* lx, const CharMask& cm) {
+int crnn_features(kocr_ctx* ctx, const float* d_crops, int M, float* d_feats) {
+  return crnn_run(ctx, d_crops, M, d_feats, nullptr, nullptr);
+}
+int crnn_logits(kocr_ctx* ctx, const float* d_crops, int M, const float** d_logits) {
+  return crnn_run(ctx, d_crops, M, nullptr, d_logits, nullptr);
+}
+int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, const CrnnDecode& rq) {
+  return crnn_run(ctx, d_crops, M, nullptr, nullptr, &rq);
+}
+
+int crnn_decode_logits(kocr_ctx* ctx, const float* d_lg, int M, const CrnnDecode& rq) {
   if (!ctx->crnn || !ctx->crnn->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_crnn_decode_logits: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
-  KOCR_TRY(decode_launch(ctx, d_lg, M, d_labels, d_probs, sc, cm));
-  return decode_extras(ctx, d_lg, M, bm, lx, cm);
-}
-
-int crnn_lexicon(kocr_ctx* ctx, const float* d_crops, int M, const CrnnLexicon& lx, const CharMask& cm) {
-  const float* d_lg = nullptr;
-  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
-  if (M <= 0) return KOCR_OK;
-  return lexicon_run(ctx, d_lg, M, lx, cm);
-}
-
-int crnn_pattern(kocr_ctx* ctx, const float* d_crops, int M, const CrnnPattern& pt) {
-  const float* d_lg = nullptr;
-  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
-  if (M <= 0) return KOCR_OK;
-  return pattern_run(ctx, d_lg, M, pt);
+  return decode_run(ctx, d_lg, M, rq);
 }
 
 void patterns_unload(kocr_ctx* ctx) {
@@ -639,13 +635,6 @@ void lexicon_unload(kocr_ctx* ctx, int dropped_classes) {
   ctx->lex_top = 0;
 }
 
-int crnn_beam(kocr_ctx* ctx, const float* d_crops, int M, const CrnnBeam& bm, const CharMask& cm) {
-  const float* d_lg = nullptr;
-  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
-  if (M <= 0) return KOCR_OK;
-  return launch_ctc_beam(ctx, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, bm.beam_width, bm.top_paths, bm.d_labels, bm.d_logp, cm);
-}
-
 int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths) {
   if (beam_width < 1 || beam_width > 64)
     KOCR_FAIL(ctx, KOCR_EINVAL, std::string(fn) + ": beam_width " + std::to_string(beam_width) + " outside [1, 64]");
@@ -655,19 +644,17 @@ int beam_validate(kocr_ctx* ctx, const char* fn, int beam_width, int top_paths) 
   return KOCR_OK;
 }
 
-int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
-                  float* d_loss, int Lmax) {
+int crnn_ctc_loss(kocr_ctx* ctx, const float* d_crops, int M, const CtcLabels& lab, float* d_loss) {
   const float* d_lg = nullptr;
-  KOCR_TRY(crnn_forward(ctx, d_crops, M, nullptr, nullptr, CRNN_LOGITS, nullptr, &d_lg));
-  return crnn_logits_loss(ctx, d_lg, M, d_lab, lstride, d_len, d_in_len, d_loss, Lmax);
+  KOCR_TRY(crnn_logits(ctx, d_crops, M, &d_lg));
+  return crnn_logits_loss(ctx, d_lg, M, lab, d_loss);
 }
 
-int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const int* d_lab, int lstride, const int* d_len, const int* d_in_len,
-                     float* d_loss, int Lmax) {
+int crnn_logits_loss(kocr_ctx* ctx, const float* d_lg, int M, const CtcLabels& lab, float* d_loss) {
   if (!ctx->crnn || !ctx->crnn->loaded) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "ctc loss: call kocr_load_crnn first");
   if (M <= 0) return KOCR_OK;
-  return launch_ctc_loss(ctx, /*logits=*/true, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, d_lab, lstride, d_len, d_in_len,
-                         d_loss, Lmax);
+  return launch_ctc_loss(ctx, /*logits=*/true, d_lg, M, T, ctx->crnn->n_classes, ctx->crnn->discard, lab.d_lab, lab.lstride, lab.d_len,
+                         lab.d_in_len, d_loss, lab.Lmax);
 }
 
 int ctc_validate(kocr_ctx* ctx, const char* fn, int M, int T, int C, const int32_t* labels, int label_stride,

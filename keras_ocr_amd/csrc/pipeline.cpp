@@ -77,7 +77,7 @@ struct OrientRun {
   float* quads2 = nullptr;    // [2M][8]
   OrientRun(kocr_ctx* ctx, long M) : rec(ctx, 2 * M, true) { won.words = M; }
   // a per-box list of character sets (device, [M]): both candidates of box m are crops 2 m and 2 m + 1
-  void set_charsets(kocr_ctx* ctx, const int32_t* d_set_of) { rec.cm = ctx->charmask(d_set_of, 1); }
+  void set_charsets(kocr_ctx* ctx, const int32_t* d_set_of) { rec.req.cm = ctx->charmask(d_set_of, 1); }
   template <class F> int each(F f) {
     const size_t m = (size_t)won.words, lw = (size_t)rec.LW, i4 = sizeof(int32_t), f4 = sizeof(float);
     KOCR_TRY(f(prm, 2 * m * sizeof(WarpParam)));
@@ -99,7 +99,8 @@ int orient_run(kocr_ctx* ctx, const uint8_t* d_img, int H, int W, OrientRun& r) 
   const long M = r.won.words;
   KOCR_TRY(launch_warp(ctx, d_img, H, W, r.prm, (int)(2 * M), CRNN_CROP_H, CRNN_CROP_W, r.crops));
   KOCR_TRY(r.rec.run(r.crops));
-  return launch_orient_select(ctx, r.rec.lab, r.rec.sc.d_logw, r.rec.sc.d_chars, r.turns2, r.quads2, M, r.rec.LW, r.won.lab, r.won.logw,
+  const CrnnDecode& rq = r.rec.req;
+  return launch_orient_select(ctx, rq.d_labels, rq.sc.d_logw, rq.sc.d_chars, r.turns2, r.quads2, M, r.rec.LW, r.won.lab, r.won.logw,
                               r.won.chars, r.won.turn, r.won.quad, r.won.pair);
 }
 
@@ -210,7 +211,7 @@ static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* im
   if (set_of) {  // the caller's array outlives the copy: the call synchronises before it returns
     const int32_t* d_set;
     KOCR_TRY(st.upload(set_of, (size_t)M * sizeof(int32_t), d_set));
-    rec.cm = ctx->charmask(d_set, 0);
+    rec.req.cm = ctx->charmask(d_set, 0);
   }
   if (pattern_of) {
     const int32_t* d_of;
@@ -219,7 +220,7 @@ static int recognize_boxes_call(kocr_ctx* ctx, const char* fn, const uint8_t* im
   }
   KOCR_TRY(launch_warp(ctx, d_img, H, W, d_prm, (int)M, CRNN_CROP_H, CRNN_CROP_W, d_crops));
   KOCR_TRY(rec.run(d_crops));
-  KOCR_TRY(st.download(labels, (const int32_t*)rec.lab, (size_t)M * rec.LW * sizeof(int32_t)));
+  KOCR_TRY(st.download(labels, (const int32_t*)rec.req.d_labels, (size_t)M * rec.LW * sizeof(int32_t)));
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   rec.keep();
   return KOCR_OK;
@@ -411,7 +412,7 @@ int pipeline_tail(kocr_ctx* ctx, const PipelineCall& c, const uint8_t* d_bat, in
   // status words to the host, what stays resident ----
   int* d_status;
   auto finish_crops = [&](const RecStage& rec, const OrientWinners* won) -> int {
-    const int32_t* d_lab = won ? won->lab : rec.lab;
+    const int32_t* d_lab = won ? won->lab : rec.req.d_labels;
     if (host_fits)
       KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, (size_t)M * rec.LW * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
