@@ -384,7 +384,7 @@ int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, const int32_
                   int32_t* labels, int max_crops, int32_t* n_crops, int on_device);
 
 /* The same results where kocr_pipeline left them in HBM (round 5): d_boxes [N][cap][4][2] float32 (rows >= counts[i] of an
- * image undefined), d_counts [N] int32, d_labels [M][48] int32 (M = sum of the counts; NULL when M == 0).  Valid only until
+ * image undefined), d_counts [N] int32, d_labels [M][label width] int32 (M = sum of the counts; NULL when M == 0; the width: see below).  Valid only until
  * the next libkocr call on this context that processes images (the buffers live in the context's arenas); KOCR_EINVAL when
  * no result is resident.  For callers that hand the results to another device-side consumer -- keras_ocr_amd.dist packs
  * them on the device and all-gathers them over RCCL without a host round trip. */
@@ -392,12 +392,19 @@ int kocr_pipeline(kocr_ctx* ctx, int N, const uint8_t* const* imgs, const int32_
  * cap, or there are more crops than max_crops, kocr_pipeline still runs the whole chain once (a larger device box buffer, the
  * post-processing alone repeated on the resident heat-maps), leaves the results in HBM and returns KOCR_ECAPACITY with the
  * true counts / n_crops.  This call copies them into buffers sized from those numbers: boxes N x cap x 4 x 2 (cap >= the
- * largest count), labels n_crops x kocr_crnn_label_width().  Valid until the next libkocr call on this context that
- * processes images. */
+ * largest count), labels n_crops x label width.  Valid until the next libkocr call on this context that processes images.
+ *
+ * The width contract: resident label rows keep the width they were PRODUCED with.  kocr_crnn_set_rnn_steps_to_discard between
+ * kocr_pipeline and a fetch changes kocr_crnn_label_width() but neither the rows nor their pitch: kocr_pipeline_results copies
+ * n_crops rows of the produced width, densely, and writes nothing behind them; d_labels of kocr_pipeline_device_results is
+ * [M][produced width].  kocr_pipeline_results_shape reports that width (and M) -- *n_crops / *label_width, either may be NULL;
+ * KOCR_EINVAL when no result is resident -- as kocr_recognition_scores / _beams report the width of their rows.  Size the label
+ * buffer from it, not from kocr_crnn_label_width(), whenever the build parameter may have changed since the call. */
 int kocr_pipeline_results(kocr_ctx* ctx, float* boxes, int cap, int32_t* labels, int max_crops);
 
 int kocr_pipeline_device_results(kocr_ctx* ctx, const float** d_boxes, const int32_t** d_counts, const int32_t** d_labels,
                                  int32_t* N, int32_t* cap, int32_t* M);
+int kocr_pipeline_results_shape(kocr_ctx* ctx, int32_t* n_crops, int32_t* label_width);
 
 /* ---- tiled pages: a page larger than the detector takes in one image, read in overlapping tiles (DESIGN.md section 4,
  * "Tiled pages"; statement: tests/tiling_statement.py) ------------------------------------------------------------------------

@@ -145,6 +145,7 @@ def load_library():
         "kocr_pipeline_tiled": (ci, [vp, ci, ctypes.POINTER(vp), _c_int_p, _c_int_p, _c_int_p, _c_int_p, ci, ci,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_float, ci, ci, vp, vp, ci, vp, ci, vp, ci]),
         "kocr_pipeline_results": (ci, [vp, vp, ci, vp, ci]),
+        "kocr_pipeline_results_shape": (ci, [vp, vp, vp]),
         "kocr_resize_pad_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]),
         "kocr_warp_crops_f32": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
         "kocr_conv2d_nhwc": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp]),
@@ -1206,6 +1207,7 @@ class Context:
             cap = max(cap, int(counts.max()))
             max_crops = max(max_crops, int(n_crops[0]))
             boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
+            lw = self.pipeline_results_shape()[1]  # the width the resident rows were produced with
             labels = np.full((max_crops, lw), -1, dtype=np.int32)
             rc = self._lib.kocr_pipeline_results(self._h, _ptr(boxes), cap, _ptr(labels), max_crops)
         self._check(rc)
@@ -1287,15 +1289,23 @@ class Context:
             float(link_threshold), int(size_threshold), int(micro_batch), _ptr(boxes), _ptr(counts), cap, 0),
             min_area_rect, return_scores, char_boxes)
 
+    def pipeline_results_shape(self):
+        """``(m, lw)`` of the label rows the last `pipeline()` call left resident (kocr_pipeline_results_shape): ``lw`` is the
+        label width they were PRODUCED with, whatever ``crnn_label_width()`` says by now."""
+        m, lw = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.kocr_pipeline_results_shape(self._h, ctypes.byref(m), ctypes.byref(lw)))
+        return m.value, lw.value
+
     def pipeline_device_results(self):
         """Device pointers of the last `pipeline()` call's results (include/kocr.h: kocr_pipeline_device_results):
-        {"boxes": ptr of [n][cap][4][2] f32, "counts": ptr of [n] i32, "labels": ptr of [m][48] i32 or 0, "n", "cap", "m"};
-        valid until the next call on this context."""
+        {"boxes": ptr of [n][cap][4][2] f32, "counts": ptr of [n] i32, "labels": ptr of [m][lw] i32 or 0, "n", "cap", "m",
+        "lw": the label width the rows were produced with (48 by default)}; valid until the next call on this context."""
         pb, pc, pl = ctypes.c_void_p(0), ctypes.c_void_p(0), ctypes.c_void_p(0)
         n, cap, m = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
         self._check(self._lib.kocr_pipeline_device_results(self._h, ctypes.byref(pb), ctypes.byref(pc), ctypes.byref(pl),
                                                            ctypes.byref(n), ctypes.byref(cap), ctypes.byref(m)))
-        return {"boxes": pb.value or 0, "counts": pc.value or 0, "labels": pl.value or 0, "n": n.value, "cap": cap.value, "m": m.value}
+        return {"boxes": pb.value or 0, "counts": pc.value or 0, "labels": pl.value or 0, "n": n.value, "cap": cap.value, "m": m.value,
+                "lw": self.pipeline_results_shape()[1]}
 
     def conv2d_nhwc(self, x, w_hwio, dilation=1, pre_a=None, pre_b=None, relu=False, post_a=None, post_b=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -281,12 +281,13 @@ struct kocr_ctx {
 
   // the device-resident results of the last successful kocr_pipeline call (kocr_pipeline_device_results): boxes in the pl
   // arena, counts in the post-processing scratch, label rows in the io arena -- all valid until the next call that uses
-  // those arenas, which resets `state` first (arena_reserve)
+  // those arenas, which resets `state` first (arena_reserve).  lw: the label width the rows were produced with, which is
+  // their pitch whatever kocr_crnn_set_rnn_steps_to_discard says afterwards (kocr_pipeline_results_shape reports it)
   struct LastPipeline {
     const float* d_boxes = nullptr;
     const int32_t* d_counts = nullptr;
-    const int32_t* d_labels = nullptr;
-    int N = 0, cap = 0, M = 0;
+    const int32_t* d_labels = nullptr;  // [M][lw]
+    int N = 0, cap = 0, M = 0, lw = 0;
     Resident state = Resident::NONE;  // never OFF: the call has no switch
   } last_pl;
 

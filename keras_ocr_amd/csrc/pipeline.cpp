@@ -399,7 +399,7 @@ int pipeline_tail(kocr_ctx* ctx, const PipelineCall& c, const uint8_t* d_bat, in
   };
   if (M == 0) {
     KOCR_TRY(finish());
-    ctx->last_pl = {d_boxes, dv.d_counts, nullptr, N, cap, 0, Resident::VALID};
+    ctx->last_pl = {d_boxes, dv.d_counts, nullptr, N, cap, 0, crnn_label_width(ctx), Resident::VALID};
     ctx->keep_det_scores(dv.d_scores, N, d_cap);
     RecStage(ctx, 0).keep();
     return KOCR_OK;
@@ -417,7 +417,7 @@ int pipeline_tail(kocr_ctx* ctx, const PipelineCall& c, const uint8_t* d_bat, in
       KOCR_HIP(ctx, hipMemcpyAsync(labels, d_lab, (size_t)M * rec.LW * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     KOCR_HIP(ctx, hipMemcpyAsync(&host_flags[4], d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     KOCR_TRY(finish());
-    ctx->last_pl = {d_boxes, dv.d_counts, d_lab, N, d_cap, (int)M, Resident::VALID};
+    ctx->last_pl = {d_boxes, dv.d_counts, d_lab, N, d_cap, (int)M, rec.LW, Resident::VALID};
     ctx->keep_det_scores(dv.d_scores, N, d_cap);
     rec.keep(won);
     if (!host_fits)
@@ -512,7 +512,7 @@ extern "C" int kocr_pipeline_results(kocr_ctx* ctx, float* boxes, int cap, int32
   return fetch_resident(ctx, "kocr_pipeline_results", r.state, "", ": no kocr_pipeline result is resident (call it right after kocr_pipeline)",
                         ": buffers smaller than the resident results (cap >= " + std::to_string(r.cap) + ", max_crops >= " +
                             std::to_string(r.M) + ")",
-                        {}, &rows, r.M, max_crops, {{labels, r.d_labels, crnn_label_width(ctx) * sizeof(int32_t)}});
+                        {}, &rows, r.M, max_crops, {{labels, r.d_labels, r.lw * sizeof(int32_t)}});
 }
 
 // The resident scores (see include/kocr.h, "Scores")
@@ -582,6 +582,16 @@ extern "C" int kocr_pipeline_device_results(kocr_ctx* ctx, const float** d_boxes
   if (N) *N = ctx->last_pl.N;
   if (cap) *cap = ctx->last_pl.cap;
   if (M) *M = ctx->last_pl.M;
+  return KOCR_OK;
+}
+
+// How many label rows of which width are resident (see include/kocr.h): the width they were PRODUCED with
+extern "C" int kocr_pipeline_results_shape(kocr_ctx* ctx, int32_t* n_crops, int32_t* label_width) {
+  if (!ctx) return KOCR_EINVAL;
+  if (ctx->last_pl.state != Resident::VALID)
+    KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_pipeline_results_shape: no kocr_pipeline result is resident (call it right after kocr_pipeline)");
+  if (n_crops) *n_crops = ctx->last_pl.M;
+  if (label_width) *label_width = ctx->last_pl.lw;
   return KOCR_OK;
 }
 

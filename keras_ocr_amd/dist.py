@@ -13,7 +13,10 @@ import os
 import numpy as np
 
 
-LABEL_WIDTH = 48  # CTC rows: 50 time-steps minus the 2 discarded (recognition.py:175-182, 328)
+# The width of a label row is the recogniser's: 50 time-steps minus its rnn_steps_to_discard (recognition.py:175-182, 328; 48
+# for the default build).  Nothing here assumes a value: a rank reads the width off its own label rows, or asks its recogniser
+# when it has none, and the ranks compare what they read in the counts exchange (the status slot's upper bits).
+_STATUS_BITS = 8  # the status slot: the exception code in the low byte, the rank's label width (0 = no opinion) above it
 
 
 def init_from_env(backend=None, force=False):
@@ -68,11 +71,12 @@ def ranks_seen(group=None):
     return int(one.item())
 
 
-def packed_payload_bytes(per_rank_images, cap):
-    """Bytes ONE rank contributes to the three all-gathers of `gather_packed` (counts, boxes, label rows)."""
-    cap = max(int(cap), 1)
-    return {"counts": 4 * (per_rank_images + 2), "boxes": cap * 8 * 4, "labels": cap * LABEL_WIDTH * 4,
-            "total": 4 * (per_rank_images + 2) + cap * 8 * 4 + cap * LABEL_WIDTH * 4}
+def packed_payload_bytes(per_rank_images, cap, label_width=48):
+    """Bytes ONE rank contributes to the three all-gathers of `gather_packed` (counts, boxes, label rows of ``label_width``
+    columns: 48 for the default recogniser build).  The width itself travels in the status slot of the counts: no bytes."""
+    cap, label_width = max(int(cap), 1), int(label_width)
+    return {"counts": 4 * (per_rank_images + 2), "boxes": cap * 8 * 4, "labels": cap * label_width * 4,
+            "total": 4 * (per_rank_images + 2) + cap * 8 * 4 + cap * label_width * 4}
 
 
 class ShardError(RuntimeError):
@@ -107,16 +111,22 @@ class _DeviceArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
-def _pack_tensors(counts, boxes, labels, cap, dev):
-    """(cap, 8) box tensor and (cap, 48) label tensor from the per-image form kocr_pipeline produces -- counts [n], boxes
-    [n][cap_local][8] (rows >= counts[i] of image i undefined), label rows [m][48] -- on whatever device the inputs live:
-    a boolean-mask gather by the counts, image-major, which is the order of the label rows."""
+def _pack_tensors(counts, boxes, labels, cap, dev, label_width=None):
+    """(cap, 8) box tensor and (cap, label width) label tensor from the per-image form kocr_pipeline produces -- counts [n],
+    boxes [n][cap_local][8] (rows >= counts[i] of image i undefined), label rows [m][label width] -- on whatever device the
+    inputs live: a boolean-mask gather by the counts, image-major, which is the order of the label rows.  The width is the
+    rows' own; ``label_width`` says it for a rank without rows (``labels`` None; 48, the default build's, when it is None too)
+    and must agree with rows that are there."""
     import torch
 
     n, cl = boxes.shape[0], boxes.shape[1]
     m = int(labels.shape[0]) if labels is not None else 0
+    if labels is not None and label_width is not None and int(labels.shape[1]) != int(label_width):
+        raise ValueError(f"_pack_tensors: label rows of width {int(labels.shape[1])} packed as width {int(label_width)}")
+    # no rows and nobody to say the width: the default build's, as gather_packed does when no rank has an opinion
+    lw = int(labels.shape[1]) if labels is not None else 48 if label_width is None else int(label_width)
     b = torch.zeros((cap, 8), dtype=torch.float32, device=dev)
-    l = torch.full((cap, LABEL_WIDTH), -1, dtype=torch.int32, device=dev)
+    l = torch.full((cap, lw), -1, dtype=torch.int32, device=dev)
     if m:
         mask = torch.arange(cl, device=dev)[None, :] < counts[:, None]
         b[:m] = boxes.reshape(n, cl, 8)[mask]
@@ -124,26 +134,49 @@ def _pack_tensors(counts, boxes, labels, cap, dev):
     return b, l
 
 
-def _pack_on_device(dev_res, cap, dev):
+def _pack_on_device(dev_res, cap, dev, label_width):
     """The packed tensors of gather_packed built IN HBM from what kocr_pipeline left there: the payload RCCL moves never
-    visits the host."""
+    visits the host.  The device rows are viewed at the width they were produced with (``dev_res["lw"]``), which must be the
+    width the ranks agreed on (``label_width``)."""
     import torch
 
-    n, cl, m = dev_res["n"], dev_res["cap"], dev_res["m"]
+    n, cl, m, lw = dev_res["n"], dev_res["cap"], dev_res["m"], dev_res["lw"]
+    if m and lw != label_width:
+        raise ValueError(f"_pack_on_device: resident label rows of width {lw}, the gather runs at {label_width}")
     counts = torch.as_tensor(_DeviceArray(dev_res["counts"], (n,), "<i4"), device=dev)
     boxes = torch.as_tensor(_DeviceArray(dev_res["boxes"], (n, cl, 8), "<f4"), device=dev)
-    labels = torch.as_tensor(_DeviceArray(dev_res["labels"], (m, LABEL_WIDTH), "<i4"), device=dev) if m else None
-    return _pack_tensors(counts, boxes, labels, cap, dev)
+    labels = torch.as_tensor(_DeviceArray(dev_res["labels"], (m, lw), "<i4"), device=dev) if m else None
+    return _pack_tensors(counts, boxes, labels, cap, dev, label_width)
+
+
+def _label_rows(labels, m):
+    """``labels`` as an (m, width) int32 array; ValueError for anything that is not m rows of one width"""
+    labels = np.asarray(labels, np.int32)
+    if not m and not labels.size:
+        return np.zeros((0, labels.shape[1] if labels.ndim == 2 else 0), np.int32)
+    if labels.ndim != 2 and m and labels.size and labels.size % m == 0:
+        labels = labels.reshape(m, -1)
+    if labels.ndim != 2 or labels.shape[0] != m or (m and not labels.shape[1]):
+        raise ValueError(f"label rows of shape {labels.shape} for {m} boxes")
+    return labels
 
 
 def gather_packed(box_groups, labels, per_rank_images, group=None, error=None, timing=None, device_results=None,
-                  device_scale=None):
+                  device_scale=None, label_width=None):
     """all-gather of the per-image box counts, then of fixed-capacity packed results.
 
     Every rank contributes ``per_rank_images`` count slots (its shard, zero padded), a (cap, 8) float32
-    box tensor and a (cap, 48) int32 label tensor, where cap = the largest crop count of any rank (known
+    box tensor and a (cap, label width) int32 label tensor, where cap = the largest crop count of any rank (known
     after the counts exchange).  Three collectives, no pickling; on the nccl backend the tensors stay in
     HBM and travel over xGMI.  Returns (box_groups, labels) of the whole batch in image order.
+
+    The label width (48 by default: 50 - the recogniser's rnn_steps_to_discard) is never assumed.  A rank with rows takes
+    the width of its rows; a rank without rows says ``label_width`` (its recogniser's: ``ShardedPipeline`` passes it), else
+    the width of its zero-row array, and has no opinion (0) when that is 0 too.  The widths travel in the upper bits of the
+    status slot of the counts exchange, so no collective and no byte is added: ranks without an opinion adopt the others'
+    width and enter the label gather with a (cap, width) tensor of -1; two different widths raise ``ShardError`` naming the
+    ranks on EVERY rank, after the first collective like any failure; when no rank has an opinion there are no rows
+    either, and the result is (0, 48).
 
     ``device_scale`` (nccl backend, the SAME value on every rank or None on every rank) switches the box / label gathers to
     device-originated payloads: a rank that had work passes ``device_results`` (``Pipeline.recognize_device_raw``: where its
@@ -161,11 +194,13 @@ def gather_packed(box_groups, labels, per_rank_images, group=None, error=None, t
     import torch
     import torch.distributed as dist
 
+    opinion = int(label_width or 0)
     if error is not None:
-        box_groups, labels = [], np.zeros((0, LABEL_WIDTH), np.int32)
+        box_groups, labels = [], np.zeros((0, opinion), np.int32)
     counts_local = [len(b) for b in box_groups]
     m_local = int(sum(counts_local))
-    labels = np.asarray(labels, np.int32).reshape(m_local, LABEL_WIDTH)
+    labels = _label_rows(labels, m_local)
+    lw_local = int(labels.shape[1]) if m_local else (opinion or int(labels.shape[1]))
     boxes_local = (np.concatenate([np.asarray(b, np.float32).reshape(-1, 8) for b in box_groups if len(b)])
                    if m_local else np.zeros((0, 8), np.float32))
     if not (dist.is_available() and dist.is_initialized()):
@@ -180,56 +215,74 @@ def gather_packed(box_groups, labels, per_rank_images, group=None, error=None, t
         # found BEFORE the first collective and sent through the status slot: raised locally after the counts exchange it would
         # leave the other ranks blocked in the box / label gathers
         error = RuntimeError("gather_packed: device-originated gather without this rank's device results")
-        box_groups, labels = [], np.zeros((0, LABEL_WIDTH), np.int32)
+        box_groups, labels = [], np.zeros((0, lw_local), np.int32)
         counts_local, m_local, boxes_local = [], 0, np.zeros((0, 8), np.float32)
-    # 1. counts: per_rank_images + 2 ints per rank (slot -2 = number of images this rank really had, slot -1 = status)
+    if error is None and device_scale is not None and dev.type == "cuda" and m_local and device_results.get("lw") != lw_local:
+        # likewise: rows that lie in HBM at another pitch than the host rows say are not viewed at all
+        error = RuntimeError(f"gather_packed: the resident label rows have width {device_results.get('lw')}, the host rows {lw_local}")
+        box_groups, labels = [], np.zeros((0, lw_local), np.int32)
+        counts_local, m_local, boxes_local = [], 0, np.zeros((0, 8), np.float32)
+    # 1. counts: per_rank_images + 2 ints per rank (slot -2 = number of images this rank really had, slot -1 = status in the
+    # low byte, this rank's label width above it)
     c = torch.zeros(per_rank_images + 2, dtype=torch.int32)
     c[:len(counts_local)] = torch.tensor(counts_local, dtype=torch.int32)
     c[-2] = len(counts_local)
-    c[-1] = _status_of(error)
+    c[-1] = _status_of(error) | (lw_local << _STATUS_BITS)
     c = c.to(dev)
     all_c = torch.empty(world * (per_rank_images + 2), dtype=torch.int32, device=dev)
     dist.all_gather_into_tensor(all_c, c, group=group)
     all_c = all_c.cpu().numpy().reshape(world, per_rank_images + 2)
-    failed = [r for r in range(world) if all_c[r, -1] != 0]
+    status = all_c[:, -1] & ((1 << _STATUS_BITS) - 1)
+    widths = all_c[:, -1] >> _STATUS_BITS
+    failed = [r for r in range(world) if status[r] != 0]
     if failed:
-        kinds = sorted({_STATUS_NAMES.get(int(all_c[r, -1]), "Exception") for r in failed})
+        kinds = sorted({_STATUS_NAMES.get(int(status[r]), "Exception") for r in failed})
         msg = f"sharded recognize failed on rank(s) {failed} ({', '.join(kinds)})"
         exc = ShardError(f"{msg}: {type(error).__name__}: {error}" if error is not None else msg)
         exc.failed_ranks = failed
-        exc.kinds = {r: _STATUS_NAMES.get(int(all_c[r, -1]), "Exception") for r in failed}
+        exc.kinds = {r: _STATUS_NAMES.get(int(status[r]), "Exception") for r in failed}
         if error is not None:
             raise exc from error
         raise exc
+    said = {r: int(widths[r]) for r in range(world) if widths[r] != 0}
+    if len(set(said.values())) > 1:
+        # every rank sees the same widths and raises here, before the box / label gathers: nobody is left in a collective
+        exc = ShardError(f"sharded recognize failed on rank(s) {sorted(said)} (LabelWidth): the ranks disagree on the label width "
+                         f"{said} ({{rank: width}}; every recogniser must be built with the same rnn_steps_to_discard)")
+        exc.failed_ranks = sorted(said)
+        exc.kinds = {r: "LabelWidth" for r in said}
+        raise exc
+    lw = next(iter(said.values())) if said else 48  # nobody has rows or a recogniser to ask: the default build's empty result
     cap = max(int(all_c[:, :-2].sum(axis=1).max()), 1)
     # 2. + 3. packed boxes and label rows, capacity = the busiest rank's crop count
     # every rank must take the same branch below: the scale travels with the decision (all ranks of a device-resident batch
     # have it or none has: recognize_device / recognize_scattered pass it on every rank that had work)
     on_device = device_scale is not None and dev.type == "cuda"
     if on_device and m_local:
-        b, l = _pack_on_device(device_results, cap, dev)
+        b, l = _pack_on_device(device_results, cap, dev, lw)
     elif on_device:
         b = torch.zeros((cap, 8), dtype=torch.float32, device=dev)
-        l = torch.full((cap, LABEL_WIDTH), -1, dtype=torch.int32, device=dev)
+        l = torch.full((cap, lw), -1, dtype=torch.int32, device=dev)
     else:
         b = torch.zeros((cap, 8), dtype=torch.float32)
         b[:m_local] = torch.from_numpy(boxes_local)
-        l = torch.full((cap, LABEL_WIDTH), -1, dtype=torch.int32)
-        l[:m_local] = torch.from_numpy(labels)
+        l = torch.full((cap, lw), -1, dtype=torch.int32)
+        if m_local:
+            l[:m_local] = torch.from_numpy(labels)
         b, l = b.to(dev), l.to(dev)
     all_b = torch.empty((world * cap, 8), dtype=torch.float32, device=dev)
-    all_l = torch.empty((world * cap, LABEL_WIDTH), dtype=torch.int32, device=dev)
+    all_l = torch.empty((world * cap, lw), dtype=torch.int32, device=dev)
     dist.all_gather_into_tensor(all_b, b, group=group)
     dist.all_gather_into_tensor(all_l, l, group=group)
     all_b = all_b.cpu().numpy().reshape(world, cap, 4, 2)
-    all_l = all_l.cpu().numpy().reshape(world, cap, LABEL_WIDTH)
+    all_l = all_l.cpu().numpy().reshape(world, cap, lw)
     if on_device and device_scale != 1:
         all_b = all_b * (1 / device_scale)  # tools.adjust_boxes (pipeline.py:66-71), as Pipeline._adjust does on the host path
     if timing is not None:
         timing["gather_packed_on_device"] = on_device
     if timing is not None:
         timing["gather_s"] = timing.get("gather_s", 0.0) + (time.perf_counter() - t0)
-        timing["gather_payload_bytes_per_rank"] = packed_payload_bytes(per_rank_images, cap)["total"]
+        timing["gather_payload_bytes_per_rank"] = packed_payload_bytes(per_rank_images, cap, lw)["total"]
     out_boxes, out_labels = [], []
     for r in range(world):
         pos = 0
@@ -239,7 +292,7 @@ def gather_packed(box_groups, labels, per_rank_images, group=None, error=None, t
             out_boxes.append(all_b[r, pos:pos + n].copy() if n else np.zeros((0,), np.float32))
             pos += n
         out_labels.append(all_l[r, :pos])
-    return out_boxes, np.concatenate(out_labels) if out_labels else np.zeros((0, LABEL_WIDTH), np.int32)
+    return out_boxes, np.concatenate(out_labels) if out_labels else np.zeros((0, lw), np.int32)
 
 
 class ShardedPipeline:
@@ -408,19 +461,28 @@ class ShardedPipeline:
             return self._run_shard(run, rank == src_rank, per, timing, dev_res, scale)
         return self._run_shard(run, n_mine > 0, per, timing, dev_res, scale)
 
+    def _label_width(self):
+        """The width of the recogniser's label rows -- its libkocr context's ``crnn_label_width()``, else its ``label_width``
+        attribute -- for a rank that has no rows to read it off; 0 (no opinion) for a recogniser that says neither."""
+        from .pipeline import label_width_of
+
+        return label_width_of(getattr(self.pipeline, "recognizer", self.pipeline)) or 0
+
     def _run_shard(self, run, has_work, per, timing, device_results=None, device_scale=None):
-        box_groups, labels, err = [], np.zeros((0, LABEL_WIDTH), np.int32), None
+        box_groups, labels, err, lw = [], None, None, 0
         try:
+            lw = self._label_width()
+            labels = np.zeros((0, lw), np.int32)
             if has_work:
                 box_groups, labels = run()
                 # the packing of gather_packed's preamble, done here so that a malformed local result is exchanged as a
                 # status too instead of raising on one rank before the first collective (ADVICE r03)
-                np.asarray(labels, np.int32).reshape(sum(len(b) for b in box_groups), LABEL_WIDTH)
+                labels = _label_rows(labels, sum(len(b) for b in box_groups))
                 for b in box_groups:
                     if len(b):
                         np.asarray(b, np.float32).reshape(-1, 8)
         except Exception as e:  # noqa: BLE001 -- exchanged as a status flag so that no rank is left in a collective
-            box_groups, labels, err = [], np.zeros((0, LABEL_WIDTH), np.int32), e
+            box_groups, labels, err = [], np.zeros((0, lw), np.int32), e
         box_groups, labels = gather_packed(box_groups, labels, per, self.group, error=err, timing=timing,
-                                           device_results=device_results, device_scale=device_scale)
+                                           device_results=device_results, device_scale=device_scale, label_width=lw)
         return self.pipeline.assemble(box_groups, labels)

@@ -90,6 +90,16 @@ def _wants_characters(char_boxes):
     return char_boxes is not None and char_boxes is not False
 
 
+def label_width_of(recognizer):
+    """The width of ``recognizer``'s label rows: its libkocr context's ``crnn_label_width()`` (50 - rnn_steps_to_discard; 48 by
+    default), else its ``label_width`` attribute (a duck-typed recogniser may define one), else None: it reports no width."""
+    ctx = getattr(recognizer, "_ctx", None)
+    if ctx is not None and hasattr(ctx, "crnn_label_width"):
+        return int(ctx.crnn_label_width())
+    width = getattr(recognizer, "label_width", None)
+    return None if width is None else int(width)
+
+
 def decode_labels(alphabet, labels):
     """Label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding (recognition.py:527-534).
 
@@ -235,7 +245,7 @@ class Pipeline:
                       char_boxes=None):
         """The fused device path up to (but not including) string assembly: ``Results.render_raw()`` -- ``(box_groups,
         label_rows)``, per image an (n_i,4,2) float32 array in INPUT-image pixels (adjust_boxes already applied,
-        pipeline.py:66-71) and one (sum n_i, 48) int32 array of decoded label rows (-1 padded, recognition.py:177-182) in image
+        pipeline.py:66-71) and one (sum n_i, label width (48 by default)) int32 array of decoded label rows (-1 padded, recognition.py:177-182) in image
         order: the fixed-width form that crosses ranks in ``dist.ShardedPipeline``.  The extras follow as the fields of
         ``results.Results`` describe them: ``return_scores=True``, a ``beam_width`` or a ``lexicon_top`` in
         ``recognition_kwargs``, and ``char_boxes`` (True or a dict of rule parameters; ``layout.Characters`` in input-image
@@ -263,7 +273,7 @@ class Pipeline:
             raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         if not images:
             return Results.empty(return_scores, beam, lexicon_top, want_characters, orientation=orientation is not None,
-                                 pattern=pattern is not None)
+                                 pattern=pattern is not None, label_width=label_width_of(self.recognizer))
         detection_kwargs = dict(detection_kwargs or {})
         if want_characters:
             detection_kwargs["char_boxes"] = char_boxes
@@ -386,7 +396,10 @@ class Pipeline:
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size).
         With ``char_boxes`` in ``detection_kwargs``, ``detect`` also returns its character groups.  Returns the ``Results``,
-        boxes and characters still in detector-input pixels, and the scale of every page."""
+        boxes and characters still in detector-input pixels, and the scale of every page.
+        The label rows, and the character-score, beam and pattern rows beside them, have the recogniser's label width
+        (``label_width_of``), as the fused route's; a text longer than that is a ValueError.  A duck-typed recogniser that
+        reports no width keeps ``max(48, longest text)`` columns."""
         own = getattr(self.detector, "_ctx", None)  # a libkocr-backed detector: its context also resizes (else the default one)
         resized = [tools.resize_image(image, max_scale=self.scale, max_size=self.max_size, **({"ctx": own} if own is not None else {}))
                    for image in images]
@@ -421,7 +434,12 @@ class Pipeline:
                 how = [o for _, o in rows]
                 rows = [t for t, _ in rows]
         alphabet = self.recognizer.alphabet
-        out = Results(detected[0], np.full((len(rows), max([48] + [len(t) for t in rows])), -1, np.int32),
+        width = label_width_of(self.recognizer)
+        if width is None:
+            width = max([48] + [len(t) for t in rows])
+        elif any(len(t) > width for t in rows):
+            raise ValueError(f"the recognizer reports a label width of {width} but returned a text of {max(len(t) for t in rows)} characters")
+        out = Results(detected[0], np.full((len(rows), width), -1, np.int32),
                       characters=detected[-1] if with_characters else None)
         for r, t in enumerate(rows):
             out.labels[r, :len(t)] = [alphabet.index(ch) for ch in t]

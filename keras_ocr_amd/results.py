@@ -32,7 +32,8 @@ class Results:
     leaves its field (or its part of ``scores``) None; an extra that was not asked for is None.
 
     boxes: per image an (n_i, 4, 2) float32 array [tl, tr, br, bl] (``np.array([])`` for an image without boxes).
-    labels: (M, label width = 48) int32 decoded label rows, -1 padded.
+    labels: (M, label width) int32 decoded label rows, -1 padded; the label width is the recogniser's (50 - its
+        rnn_steps_to_discard: 48 by default) on every route, the empty one included.
     scores: ``(detection, log_word, char_scores)`` -- per image an (n_i,) float32 array, the maximum of the text map over each
         box's component; (M,) float32, the log-probability of every alignment of the crop's own (greedy) decode; (M, label
         width) float32, per decoded label the peak probability of its run, 0 behind the decode.
@@ -62,7 +63,9 @@ class Results:
 
     @classmethod
     def empty(cls, scores=False, beam=None, lexicon=None, characters=False, label_width=48, orientation=False, pattern=False):
-        """The results of zero images; ``beam`` = (beam_width, top_paths), ``lexicon`` = top_words"""
+        """The results of zero images; ``beam`` = (beam_width, top_paths), ``lexicon`` = top_words; ``label_width``: the
+        recogniser's (None: it reports none, the default build's 48)"""
+        label_width = 48 if label_width is None else int(label_width)
         return cls([], np.zeros((0, label_width), np.int32), empty_scores(label_width, []) if scores else None,
                    empty_beam(beam[1], label_width) if beam else None, empty_lexicon(lexicon) if lexicon else None,
                    [] if characters else None, empty_orientation() if orientation else None,

@@ -33,17 +33,39 @@ def nccl_group():
 
 
 @pytest.fixture(scope="module")
-def pipe(ctx, craft_weights, crnn_weights):
+def calibrated(craft_weights):
     import keras_ocr_amd
     from oracle import craft as ocraft, tools as otools
 
     page = synth.text_page(96, 128, 5, seed=21)[None]
     big = np.stack([otools.resize_image(p, 2, 2048)[0] for p in page])
     heat = ocraft.detector_predict(craft_weights, big)
-    w = keras_ocr_amd.weights.calibrate_craft_head(craft_weights, heat, text_frac=0.10, link_frac=0.04)
-    det = keras_ocr_amd.detection.Detector(weights=w, ctx=ctx)
+    return keras_ocr_amd.weights.calibrate_craft_head(craft_weights, heat, text_frac=0.10, link_frac=0.04)
+
+
+@pytest.fixture(scope="module")
+def pipe(ctx, calibrated, crnn_weights):
+    import keras_ocr_amd
+
+    det = keras_ocr_amd.detection.Detector(weights=calibrated, ctx=ctx)
     rec = keras_ocr_amd.recognition.Recognizer(weights=crnn_weights, ctx=ctx)
     return keras_ocr_amd.pipeline.Pipeline(detector=det, recognizer=rec)
+
+
+@pytest.fixture(scope="module", params=[0, 5], ids=["discard_0", "discard_5"])
+def pipe_at(request, calibrated, crnn_weights):
+    """(pipeline, label width) of a recogniser built with another rnn_steps_to_discard, on a context of its own: the
+    session's context keeps the discard the other modules rely on"""
+    import keras_ocr_amd
+    from keras_ocr_amd.recognition import DEFAULT_BUILD_PARAMS
+
+    c = keras_ocr_amd.Context(0)
+    det = keras_ocr_amd.detection.Detector(weights=calibrated, ctx=c)
+    rec = keras_ocr_amd.recognition.Recognizer(weights=crnn_weights, ctx=c,
+                                               build_params=dict(DEFAULT_BUILD_PARAMS, rnn_steps_to_discard=request.param))
+    assert c.crnn_label_width() == 50 - request.param
+    yield keras_ocr_amd.pipeline.Pipeline(detector=det, recognizer=rec), 50 - request.param
+    c.close()
 
 
 def _same(a, b):
@@ -95,7 +117,8 @@ def test_device_results_of_the_last_pipeline_call(nccl_group, pipe, ctx):
     assert res["n"] == 3 and res["m"] == labels.shape[0] == sum(len(b) for b in boxes) > 0 and res["scale"] == 2
     counts = torch.as_tensor(_DeviceArray(res["counts"], (3,), "<i4"), device="cuda").cpu().numpy()
     assert list(counts) == [len(b) for b in boxes]
-    lab = torch.as_tensor(_DeviceArray(res["labels"], (res["m"], 48), "<i4"), device="cuda").cpu().numpy()
+    assert res["lw"] == ctx.crnn_label_width()
+    lab = torch.as_tensor(_DeviceArray(res["labels"], (res["m"], ctx.crnn_label_width()), "<i4"), device="cuda").cpu().numpy()
     assert np.array_equal(lab, labels)
     bx = torch.as_tensor(_DeviceArray(res["boxes"], (3, res["cap"], 4, 2), "<f4"), device="cuda").cpu().numpy()
     for i, b in enumerate(boxes):
@@ -107,12 +130,13 @@ def test_device_results_of_the_last_pipeline_call(nccl_group, pipe, ctx):
         ctx.pipeline_device_results()
 
 
-def test_gather_packed_on_hbm_tensors_empty_rank(nccl_group):
+def test_gather_packed_on_hbm_tensors_empty_rank(nccl_group, ctx):
     """a rank without any box still takes part in all three collectives (cap = 1)"""
     from keras_ocr_amd import dist as kd
 
-    boxes, labels = kd.gather_packed([np.array([]), np.array([])], np.zeros((0, 48), np.int32), 2)
-    assert len(boxes) == 2 and all(len(b) == 0 for b in boxes) and labels.shape == (0, 48)
+    lw = ctx.crnn_label_width()
+    boxes, labels = kd.gather_packed([np.array([]), np.array([])], np.zeros((0, lw), np.int32), 2)
+    assert len(boxes) == 2 and all(len(b) == 0 for b in boxes) and labels.shape == (0, lw)
 
 
 def test_scattered_batch_over_rccl(nccl_group, pipe):
@@ -133,3 +157,56 @@ def test_scattered_batch_over_rccl(nccl_group, pipe):
     with pytest.raises(keras_ocr_amd.dist.ShardError, match="ValueError") as ei:
         keras_ocr_amd.dist.ShardedPipeline(pipe).recognize_scattered(None, 3, 96, 128, src_rank=0)
     assert isinstance(ei.value.__cause__, ValueError) and "source rank needs" in str(ei.value.__cause__)
+
+
+# ---- other label widths: rnn_steps_to_discard 0 and 5 (rows of 50 and 45 columns) ----------------------------------------------
+def _raw_width(pipe, pages):
+    """The width of the label rows the pages give (and that there are some)"""
+    labels = pipe.recognize_raw(list(pages))[1]
+    assert labels.shape[0] > 0
+    return labels.shape[1]
+
+
+def test_sharded_host_pages_at_other_label_widths(nccl_group, pipe_at):
+    import keras_ocr_amd
+
+    pipe, lw = pipe_at
+    pages = [synth.text_page(96, 128, 5, seed=s) for s in (21, 22)] + [np.full((64, 80, 3), 255, np.uint8),
+                                                                       synth.text_page(80, 112, 4, seed=23)]
+    want = pipe.recognize(pages)
+    assert sum(len(p) for p in want) > 0 and _raw_width(pipe, pages) == lw
+    timing = {}
+    got = keras_ocr_amd.dist.ShardedPipeline(pipe).recognize(pages, timing=timing)
+    _same(got, want)
+    m = sum(len(p) for p in want)
+    assert timing["gather_payload_bytes_per_rank"] == keras_ocr_amd.dist.packed_payload_bytes(4, m, lw)["total"]
+
+
+def test_sharded_device_resident_batch_at_other_label_widths(nccl_group, pipe_at):
+    import torch
+    import keras_ocr_amd
+
+    pipe, lw = pipe_at
+    pages = np.stack([synth.text_page(96, 128, 5, seed=s) for s in (31, 32, 33)])
+    want = pipe.recognize(pages)
+    assert sum(len(p) for p in want) > 0 and _raw_width(pipe, pages) == lw
+    d = torch.from_numpy(pages).cuda()
+    timing = {}
+    got = keras_ocr_amd.dist.ShardedPipeline(pipe).recognize_device(d.data_ptr(), 3, 96, 128, timing=timing)
+    _same(got, want)
+    assert timing["gather_packed_on_device"] is True
+
+
+def test_scattered_batch_at_other_label_widths(nccl_group, pipe_at):
+    import torch
+    import keras_ocr_amd
+
+    pipe, lw = pipe_at
+    pages = np.stack([synth.text_page(96, 128, 5, seed=s) for s in (41, 42, 43)])
+    want = pipe.recognize(pages)
+    assert sum(len(p) for p in want) > 0 and _raw_width(pipe, pages) == lw
+    timing = {}
+    got = keras_ocr_amd.dist.ShardedPipeline(pipe).recognize_scattered(torch.from_numpy(pages).cuda(), 3, 96, 128, src_rank=0,
+                                                                       timing=timing)
+    _same(got, want)
+    assert timing["gather_packed_on_device"] is True

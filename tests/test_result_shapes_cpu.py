@@ -11,6 +11,8 @@ import pytest
 
 import keras_ocr_amd as k
 from keras_ocr_amd import layout, lexicon as lexicon_module, scores as scores_module
+from keras_ocr_amd.results import Results
+from keras_ocr_amd.scores import Score
 
 ALPHABET = k.recognition.DEFAULT_ALPHABET
 WORDS = ["ab", "c", "cab"]
@@ -303,3 +305,156 @@ def test_lexicon_top_refusals(monkeypatch, route):
         assert str(err.value) == "lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first"
         with pytest.raises(ValueError):
             call([], recognition_kwargs={"lexicon_top": 2})
+
+
+# ---- one label width on every route ------------------------------------------------------------------------------------------
+# The label rows -- and the character-score, beam and pattern rows beside them -- have ONE width on every route of
+# ``Pipeline._recognize``: the recogniser's (50 - rnn_steps_to_discard; 48 for the default build).  It is read with
+# ``pipeline.label_width_of``: the recogniser's ``_ctx.crnn_label_width()`` where its context has one, else its ``label_width``
+# attribute.  A duck-typed recogniser that reports NEITHER (``_Recognizer`` above) keeps the stage-wise route's
+# ``max(48, longest text)`` columns, and (0, 48) for no images: nothing else is known about it.
+WIDTHS = (1, 45, 48, 50)
+LW_PAGES = [np.zeros((10, 12, 3), np.uint8), np.zeros((8, 12, 3), np.uint8)]
+LW_BOXES = [np.arange(16, dtype=np.float32).reshape(2, 4, 2), np.arange(8, dtype=np.float32).reshape(1, 4, 2)]
+
+
+class _Ctx:
+    """What ``label_width_of`` asks of a libkocr context"""
+
+    def __init__(self, width):
+        self.width = width
+
+    def crnn_label_width(self):
+        return self.width
+
+
+class _Det:
+    def detect(self, images, return_scores=False, **kw):
+        boxes = [b.copy() for b in LW_BOXES[:len(images)]]
+        return (boxes, [np.full(len(b), 0.9, np.float32) for b in boxes]) if return_scores else boxes
+
+
+class _Rec:
+    """A duck-typed recogniser: every word reads ``text``; alternatives, pattern readings and scores as the public
+    ``Recognizer.recognize_from_boxes`` returns them.  ``how``: "ctx" (the width from ``_ctx.crnn_label_width()``), "attribute"
+    (``label_width``) or None (it reports none)."""
+    alphabet = ALPHABET
+
+    def __init__(self, width, how, text):
+        self.text = text
+        self._ctx = _Ctx(width) if how == "ctx" else object()  # patterns need some context; this one reports no width
+        if how == "attribute":
+            self.label_width = width
+
+    def _pattern_names(self, _name):
+        return ["serial"]
+
+    def recognize_from_boxes(self, images, box_groups, return_scores=False, beam_width=None, top_paths=1, pattern=None, **kw):
+        t = self.text
+        if beam_width is not None:
+            word = [(t, -0.5)] + [(t[:-1], -1.5)] * (top_paths - 1)
+        elif pattern is not None:
+            word = (t, -0.25)
+        elif return_scores:
+            word = (t, Score(None, 0.5, np.log(0.5), np.full(len(t), 0.75, np.float32)))
+        else:
+            word = t
+        return [[word] * len(boxes) for boxes in box_groups]
+
+
+@pytest.fixture
+def no_gpu_resize(monkeypatch):
+    monkeypatch.setattr(k.tools, "resize_image", lambda image, max_scale, max_size, **kw: (
+        np.zeros((image.shape[0] * max_scale, image.shape[1] * max_scale, 3), np.uint8), max_scale))
+
+
+def _widths(pipe, pages):
+    """label, char-score, beam-label and pattern-label widths (and the row count) over three calls of ``pipe._recognize``"""
+    plain = pipe._recognize(pages, None, None, None, None, return_scores=True)  # pylint: disable=protected-access
+    beam = pipe._recognize(pages, None, None, None, {"beam_width": 4, "top_paths": 2})  # pylint: disable=protected-access
+    pattern = pipe._recognize(pages, None, None, None, {"pattern": "serial"})  # pylint: disable=protected-access
+    m = len(plain.labels)
+    assert plain.labels.dtype == np.int32 and plain.labels.ndim == 2
+    assert plain.scores[2].shape[0] == m == len(plain.scores[1])
+    assert beam.beam[0].shape[:2] == (m, 2) == beam.beam[1].shape and beam.labels.shape == plain.labels.shape
+    assert pattern.pattern[0].shape[0] == m == len(pattern.pattern[1]) == len(pattern.pattern[2])
+    assert pattern.labels.shape == plain.labels.shape
+    return m, (plain.labels.shape[1], plain.scores[2].shape[1], beam.beam[0].shape[2], pattern.pattern[0].shape[1])
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+def test_results_empty_has_the_width_it_is_given(width):
+    out = Results.empty(scores=True, beam=(4, 2), pattern=True, label_width=width)
+    assert out.labels.shape == (0, width) and out.scores[2].shape == (0, width)
+    assert out.beam[0].shape == (0, 2, width) and out.pattern[0].shape == (0, width)
+
+
+@pytest.mark.parametrize("how", ["ctx", "attribute"])
+@pytest.mark.parametrize("width", WIDTHS)
+def test_no_images_route(width, how):
+    pipe = k.pipeline.Pipeline(detector=_Det(), recognizer=_Rec(width, how, "a"))
+    assert _widths(pipe, []) == (0, (width,) * 4)
+
+
+@pytest.mark.parametrize("how", ["ctx", "attribute"])
+@pytest.mark.parametrize("width", WIDTHS)
+def test_stagewise_route_has_the_width(no_gpu_resize, width, how):
+    """Duck-typed stages; the texts are as long as a row of that width can be (and no longer than 3)"""
+    text = "abc"[:width]
+    pipe = k.pipeline.Pipeline(detector=_Det(), recognizer=_Rec(width, how, text))
+    assert _widths(pipe, LW_PAGES) == (3, (width,) * 4)
+    raw = pipe.recognize_raw(LW_PAGES)
+    assert raw[1].shape == (3, width) and (raw[1][:, :len(text)] == [ALPHABET.index(c) for c in text]).all()
+    assert (raw[1][:, len(text):] == -1).all()
+    assert [[t for t, _ in page] for page in pipe.recognize(LW_PAGES)] == [[text, text], [text]]
+
+
+def test_stagewise_route_refuses_a_text_longer_than_the_reported_width(no_gpu_resize):
+    pipe = k.pipeline.Pipeline(detector=_Det(), recognizer=_Rec(1, "attribute", "ab"))
+    with pytest.raises(ValueError, match="label width of 1"):
+        pipe.recognize_raw(LW_PAGES)
+
+
+@pytest.mark.parametrize("text, want", [("abc", 48), ("a" * 53, 53)])
+def test_a_recogniser_that_reports_no_width_keeps_max_48_longest(no_gpu_resize, text, want):
+    """A duck-typed recogniser with neither a context that has ``crnn_label_width()`` nor a ``label_width`` attribute keeps
+    what the stage-wise route always built: ``max(48, longest text)`` columns, and (0, 48) for no images"""
+    pipe = k.pipeline.Pipeline(detector=_Det(), recognizer=_Rec(None, None, text))
+    assert k.pipeline.label_width_of(pipe.recognizer) is None
+    assert _widths(pipe, LW_PAGES) == (3, (want,) * 4)
+    assert _widths(pipe, []) == (0, (48,) * 4)
+
+
+class _FusedCtx(_Ctx):
+    """``Context.pipeline`` at the C-ABI seam: rows of the context's width, the extras that were asked for"""
+
+    def pipeline(self, images, hs, ws, dhs, dws, hmax, wmax, micro_batch=0, return_scores=False, beam=None, lexicon_top=None,
+                 pattern=None, **kw):
+        boxes = [b.copy() for b in LW_BOXES[:len(images)]]
+        m, w = sum(len(b) for b in boxes), self.width
+        out = Results(boxes, np.full((m, w), -1, np.int32))
+        out.labels[:, 0] = 3
+        if return_scores:
+            out.scores = ([np.full(len(b), 0.9, np.float32) for b in boxes], np.zeros(m, np.float32), np.zeros((m, w), np.float32))
+        if beam is not None:
+            out.beam = (np.full((m, beam[1], w), -1, np.int32), np.zeros((m, beam[1]), np.float32))
+        if pattern is not None:
+            out.pattern = (np.full((m, w), -1, np.int32), np.zeros(m, np.float32), np.zeros(m, np.float32))
+        return out.render_context()
+
+
+@pytest.mark.parametrize("width", WIDTHS)
+def test_parsed_context_route(width):
+    """The real Pipeline / Detector / Recognizer classes over one mocked context: the fused route hands the context's rows
+    on as they are, and the call without images gives zero rows of the same width"""
+    ctx = _FusedCtx(width)
+    det = object.__new__(k.detection.Detector)
+    rec = object.__new__(k.recognition.Recognizer)
+    det._ctx = rec._ctx = ctx  # pylint: disable=protected-access
+    rec.alphabet = ALPHABET
+    rec._pattern_names = lambda _name: ["serial"]  # pylint: disable=protected-access
+    pipe = k.pipeline.Pipeline(detector=det, recognizer=rec)
+    assert k.pipeline.label_width_of(rec) == width
+    assert _widths(pipe, LW_PAGES) == (3, (width,) * 4)
+    assert _widths(pipe, []) == (0, (width,) * 4)
+    assert [[t for t, _ in page] for page in pipe.recognize(LW_PAGES)] == [["3", "3"], ["3"]]

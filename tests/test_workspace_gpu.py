@@ -239,6 +239,7 @@ def _getters(c):
     return {
         "kocr_pipeline_device_results": lambda: lib.kocr_pipeline_device_results(h, n, n, n, n, n, n),
         "kocr_pipeline_results": lambda: lib.kocr_pipeline_results(h, n, 0, n, 0),
+        "kocr_pipeline_results_shape": lambda: lib.kocr_pipeline_results_shape(h, n, n),
         "kocr_detection_scores": lambda: lib.kocr_detection_scores(h, n, 0),
         "kocr_recognition_scores": lambda: lib.kocr_recognition_scores(h, n, n, 0, n, n),
         "kocr_recognition_beams": lambda: lib.kocr_recognition_beams(h, n, n, 0, n, n, n),
