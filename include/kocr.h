@@ -292,11 +292,30 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
  * line_counts are complete then too (total is always enough).  line_boxes == NULL with cap_lines == 0 skips the boxes.
  * KOCR_EINVAL with a message, before anything is launched: offsets that do not start at 0 or decrease, a page above
  * KOCR_LINES_MAX_WORDS (naming the page and its count), a non-finite coordinate (naming page and word), a rule parameter out of
- * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is reserved and must be 0.  Two
- * launches on the ctx stream (profiler rows lines_group, lines_pack), one workgroup per page; a page's results do not
- * depend on what else is in the batch.  The results are complete on return.  Workspace comes from the staging arena: like
- * every other call that processes images it ends the validity of resident pipeline results. */
+ * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is 0 or KOCR_LINES_BLOCKS (below),
+ * anything else KOCR_EINVAL with a message that names flags.  Two launches on the ctx stream (profiler rows lines_group,
+ * lines_pack), one workgroup per page; a page's results do not depend on what else is in the batch.  The results are
+ * complete on return.  Workspace comes from the staging arena: like every other call that processes images it ends the
+ * validity of resident pipeline results.
+ *
+ * flags == KOCR_LINES_BLOCKS: the quads of a page -- any quads, in practice the line boxes of a call with flags == 0 -- are cut
+ * into BLOCKS (columns, paragraphs) by a recursive XY-cut and returned in reading order.  The rule is tests/blocks_statement.py
+ * ("Blocks"): a quad counts as its axis-aligned box; H is the mean height of the boxes that have one;
+ * along an axis the gap in front of a box is its start minus the largest end of the boxes of its set that start before it,
+ * and it is valid when it is > 0 and >= min_gap H.  A set with valid gaps along x is cut at ALL of them (columns, gutters,
+ * sidebars), the parts taken left to right; otherwise, with valid gaps along y, at ONE, the widest (the topmost of equal
+ * ones), the upper part first; otherwise it is a block.  Inside a block the quads are ordered by (top, left, index); a block's
+ * box is the axis-aligned box of its members.  The cut is axis-aligned -- a rotated page must be deskewed by the caller --
+ * and whitespace is its only cue: a paragraph gap wider than the heading's and the footer's is cut first.
+ * How the arguments are read: max_offset is min_gap_x and max_gap is min_gap_y, both finite and >= 0 (the same check and
+ * message); cos_max and min_height_ratio are validated as ever and not read.  What the outputs hold: line_of[j] is the block
+ * of quad j among its page's blocks; order holds, per page, the page-local indices block after block; line_counts the
+ * blocks per page; line_boxes / cap_lines / true_lines the block boxes [tl, tr, br, bl], with the same KOCR_ECAPACITY
+ * contract.  Every other check and its message is the one above; a page has at most as many blocks as quads, so the
+ * workspace is the same.  Profiler rows blocks_cut, lines_pack.  A call with flags == 0 launches and returns exactly what
+ * it did before this flag existed. */
 #define KOCR_LINES_MAX_WORDS 2048
+#define KOCR_LINES_BLOCKS 1
 int kocr_group_lines(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, double cos_max, double min_height_ratio,
                      double max_offset, double max_gap, int32_t* line_of, int32_t* order, int32_t* line_counts, float* line_boxes,
                      int64_t cap_lines, int64_t* true_lines, int flags);

@@ -19,6 +19,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libkocr.so")
 KOCR_U8, KOCR_F32 = 0, 1
 # return codes (include/kocr.h)
 KOCR_OK, KOCR_EINVAL, KOCR_EHIP, KOCR_ENOWEIGHTS, KOCR_ECAPACITY, KOCR_ENOMEM, KOCR_EEMPTYCONTOUR, KOCR_EZERODIV = range(0, -8, -1)
+KOCR_LINES_BLOCKS = 1  # kocr_group_lines' flags: blocks instead of lines (include/kocr.h)
 # minAreaRect rule of getBoxes (include/kocr.h: KOCR_RECT_EXACT / KOCR_RECT_OPENCV)
 MIN_AREA_RECT_RULES = {"exact": 0, "opencv": 1}
 
@@ -1463,7 +1464,8 @@ class Context:
         (N,), line_boxes float32 (lines, 4, 2) or None)``: the index of each word's line among its page's lines; per page
         the page-local word indices in reading order, line after line; the lines per page; the box of every line of every
         page in that order.  ValueError for ``max_angle`` outside [0, 90), another rule parameter out of range, offsets that
-        do not start at 0 or decrease, a page of more than 2048 words and a non-finite coordinate (naming page and word)."""
+        do not start at 0 or decrease, a page of more than 2048 words and a non-finite coordinate (naming page and word).
+        Columns are not detected: ``group_blocks`` on the line boxes cuts a page into columns and paragraphs."""
         max_angle = float(max_angle)
         if not 0 <= max_angle < 90:
             raise ValueError(f"group_lines: max_angle {max_angle} outside [0, 90)")
@@ -1479,6 +1481,38 @@ class Context:
                                                float(max_offset), float(max_gap), _ptr(line_of), _ptr(order), _ptr(counts), _ptr(boxes),
                                                total if return_boxes else 0, ctypes.byref(lines), 0), value_error=True)
         return line_of, order, counts, (boxes[:lines.value].copy() if return_boxes else None)
+
+    def group_blocks(self, quads, offsets, min_gap_x=1.0, min_gap_y=0.75, return_boxes=True):
+        """The quads of N pages -- any quads, in practice ``group_lines``' line boxes -- cut into blocks (columns,
+        paragraphs) by a recursive XY-cut and put into reading order, in one call (kocr_group_lines with
+        KOCR_LINES_BLOCKS; DESIGN.md section 4, "Blocks"): ``quads`` float32 (total, 4, 2), ``offsets`` (N + 1,), at most
+        2048 quads on a page.  A quad counts as its axis-aligned box.  A set of boxes is cut at every gap along x of at
+        least ``min_gap_x`` mean line heights (columns, left to right), otherwise at the widest gap along y of at least
+        ``min_gap_y`` mean line heights (paragraphs, headings, footers; top first), otherwise it is a block.  The defaults
+        are judgement, not fitted to real pages.  Returns ``(block_of int32 (total,), order int32 (total,), block_counts
+        int32 (N,), block_boxes float32 (blocks, 4, 2) or None)``: the index of each quad's block among its page's blocks;
+        per page the page-local quad indices in reading order, block after block, top to bottom inside a block; the
+        blocks per page; the box [tl, tr, br, bl] of every block of every page in that order.  The cut is axis-aligned (a
+        rotated page must be deskewed first) and whitespace is its only cue.  ValueError for a gap that is negative or
+        not finite, offsets that do not start at 0 or decrease, a page of more than 2048 quads and a non-finite
+        coordinate (naming page and quad)."""
+        gaps = {"min_gap_x": float(min_gap_x), "min_gap_y": float(min_gap_y)}
+        for name, value in gaps.items():
+            if not (value >= 0 and math.isfinite(value)):
+                raise ValueError(f"group_blocks: {name} {value} is not a finite number >= 0")
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 4, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        if len(off) < 1 or off[-1] != len(q):
+            raise ValueError(f"group_blocks: offsets must hold N + 1 entries and end at the number of boxes, {len(q)}")
+        n, total = len(off) - 1, len(q)
+        block_of, order, counts = np.zeros(total, np.int32), np.zeros(total, np.int32), np.zeros(n, np.int32)
+        boxes = np.zeros((total, 4, 2), np.float32) if return_boxes else None  # a page has at most as many blocks as quads
+        blocks = ctypes.c_int64(0)
+        # cos_max and min_height_ratio are checked and not read; the two gaps travel as max_offset and max_gap
+        self._check(self._lib.kocr_group_lines(self._h, n, _ptr(q), _ptr(off), 1.0, 0.0, gaps["min_gap_x"], gaps["min_gap_y"], _ptr(block_of),
+                                               _ptr(order), _ptr(counts), _ptr(boxes), total if return_boxes else 0, ctypes.byref(blocks),
+                                               KOCR_LINES_BLOCKS), value_error=True)
+        return block_of, order, counts, (boxes[:blocks.value].copy() if return_boxes else None)
 
     def profile_enable(self, on=True):
         self._check(self._lib.kocr_profile_enable(self._h, int(bool(on))))

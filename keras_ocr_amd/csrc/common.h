@@ -914,6 +914,13 @@ int launch_lines_group(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off
                        int32_t* d_line_of, int32_t* d_order, int32_t* d_line_counts, float* d_boxes);
 int launch_lines_pack(kocr_ctx* ctx, const float* d_scratch, const int32_t* d_off, const long long* d_line_off, int N, float* d_boxes);
 
+// blocks.hip: the quads of a page cut into blocks in reading order (kocr_group_lines with KOCR_LINES_BLOCKS; DESIGN.md section
+// 4, "Blocks").  The buffers are launch_lines_group's: d_block_of [total] the block of every quad, d_order [total] per page the
+// page-local indices block after block, d_block_counts [N], d_boxes (nullable) [total][4][2] the blocks of page i at its QUAD
+// offset d_off[i], which launch_lines_pack packs.  min_gap_x / min_gap_y: the smallest cut in mean line heights.
+int launch_blocks_cut(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_quads, double min_gap_x, double min_gap_y,
+                      int32_t* d_block_of, int32_t* d_order, int32_t* d_block_counts, float* d_boxes);
+
 // chars.hip: the characters of word boxes from the region map (kocr_char_boxes; DESIGN.md section 4, "Characters").  d_heat
 // [N][h][w][2]; M words in packed word order with d_off [N + 1]; word j of page i is quad d_off[i] + j of d_quads with
 // stride == 0, quad i * stride + j otherwise.  launch_chars_split fills the workspace rows of every word, launch_chars_pack

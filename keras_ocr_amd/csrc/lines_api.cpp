@@ -1,4 +1,5 @@
-// lines_api.cpp — kocr_group_lines (include/kocr.h, "lines"): argument checks, staging, the two launches of lines.hip.
+// lines_api.cpp — kocr_group_lines (include/kocr.h, "lines"): argument checks, staging, the two launches of lines.hip; with
+// flags == KOCR_LINES_BLOCKS the first launch is blocks.hip's instead (the same checks, buffers and staging plan).
 #include "abi.h"
 #include <cmath>
 
@@ -8,7 +9,9 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
               int32_t* line_counts, float* line_boxes, int64_t cap_lines, int64_t* true_lines, int flags) {
   const std::string fn("kocr_group_lines");
   if (N < 0 || cap_lines < 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": bad sizes");
-  if (flags != 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": flags must be 0");
+  if (flags != 0 && flags != KOCR_LINES_BLOCKS)
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": flags " + std::to_string(flags) + " is neither 0 nor KOCR_LINES_BLOCKS");
+  const bool blocks = flags == KOCR_LINES_BLOCKS;  // max_offset is then read as min_gap_x, max_gap as min_gap_y
   if (!line_boxes && cap_lines != 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": null line_boxes with cap_lines " + std::to_string((long long)cap_lines));
   // !(a <= x) also refuses a NaN
   if (!(rule.cos_max > 0 && rule.cos_max <= 1))
@@ -53,7 +56,7 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
   } drain{ctx->stream};
   const size_t quads_b = total * 8 * sizeof(float), off_b = ((size_t)N + 1) * sizeof(int32_t), words_b = total * sizeof(int32_t);
   const size_t counts_b = (size_t)N * sizeof(int32_t), line_off_b = ((size_t)N + 1) * sizeof(long long);
-  const size_t boxes_b = line_boxes ? quads_b : 0;  // a page has at most as many lines as words
+  const size_t boxes_b = line_boxes ? quads_b : 0;  // a page has at most as many lines (or blocks) as words
   Staging st{ctx, ctx->io, "kocr_group_lines", false};
   KOCR_TRY(st.reserve(0, {quads_b, off_b, words_b, words_b, counts_b}, {boxes_b, boxes_b, line_off_b}));
   const float* d_quads;
@@ -66,7 +69,10 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
   KOCR_TRY(st.out(order, words_b, d_order));
   KOCR_TRY(st.out(line_counts, counts_b, d_counts));
   if (line_boxes) KOCR_TRY(st.scratch(boxes_b, d_scratch));
-  KOCR_TRY(launch_lines_group(ctx, d_quads, d_off, N, max_words, rule, d_line_of, d_order, d_counts, d_scratch));
+  if (blocks)
+    KOCR_TRY(launch_blocks_cut(ctx, d_quads, d_off, N, max_words, rule.max_offset, rule.max_gap, d_line_of, d_order, d_counts, d_scratch));
+  else
+    KOCR_TRY(launch_lines_group(ctx, d_quads, d_off, N, max_words, rule, d_line_of, d_order, d_counts, d_scratch));
   KOCR_TRY(st.back(line_of, d_line_of, words_b));
   KOCR_TRY(st.back(order, d_order, words_b));
   KOCR_TRY(st.back(line_counts, d_counts, counts_b));
@@ -76,7 +82,7 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
   if (true_lines) *true_lines = lines;
   if (!line_boxes) return KOCR_OK;
   if (lines > cap_lines)
-    KOCR_FAIL(ctx, KOCR_ECAPACITY, fn + ": " + std::to_string(lines) + " lines, line_boxes holds " + std::to_string((long long)cap_lines));
+    KOCR_FAIL(ctx, KOCR_ECAPACITY, fn + ": " + std::to_string(lines) + (blocks ? " blocks" : " lines") + ", line_boxes holds " + std::to_string((long long)cap_lines));
   const size_t packed_b = (size_t)lines * 8 * sizeof(float);
   const long long* d_line_off;
   KOCR_TRY(st.upload((const long long*)line_off.data(), line_off_b, d_line_off));

@@ -1,5 +1,6 @@
 """What follows detection and recognition: the words of a page grouped into text lines, in reading order, on the GPU
-(kocr_group_lines; DESIGN.md section 4, "Lines"), and the type of a word's character boxes (kocr_char_boxes; "Characters").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
+(kocr_group_lines; DESIGN.md section 4, "Lines"), the lines cut into blocks -- columns and paragraphs -- in reading order
+(the same call with KOCR_LINES_BLOCKS; "Blocks"), and the type of a word's character boxes (kocr_char_boxes; "Characters").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
 labels that are already grouped -- and there is no host path."""
 import typing
 
@@ -13,6 +14,13 @@ class Line(typing.NamedTuple):
     ``words``: the indices of its words in the page's list of boxes, in reading order."""
     box: np.ndarray
     words: typing.List[int]
+
+
+class Block(typing.NamedTuple):
+    """One block of a page (a column, a paragraph, a heading): ``box`` (4, 2) float32, the axis-aligned box [tl, tr, br, bl]
+    around its members; ``lines``: the indices of its members in the page's list of boxes, top to bottom."""
+    box: np.ndarray
+    lines: typing.List[int]
 
 
 class Characters(typing.NamedTuple):
@@ -49,29 +57,48 @@ def _context(ctx):
     return _lib.default_context() if ctx is None or ctx is True else ctx
 
 
+def _groups(record, offsets, group_of, order, group_counts, boxes):
+    """kocr_group_lines' arrays as, per page, a list of ``record(box, members)``: ``order`` lists a page's members group
+    after group, ``group_of`` says how many each group has"""
+    pages, group = [], 0
+    for i, groups in enumerate(group_counts.tolist()):
+        members = order[offsets[i]:offsets[i + 1]].tolist()
+        page, at = [], 0
+        lengths = np.bincount(group_of[offsets[i]:offsets[i + 1]], minlength=groups).tolist() if groups else []
+        for k in range(groups):
+            page.append(record(boxes[group + k], members[at:at + lengths[k]]))
+            at += lengths[k]
+        pages.append(page)
+        group += groups
+    return pages
+
+
 def group_lines(box_groups, ctx=None, **rule):
     """Per image the text lines of its word boxes: ``box_groups`` is a list (one entry per image) of (n_i, 4, 2) boxes
     [tl, tr, br, bl], e.g. ``Detector.detect``'s result or the boxes of ``Pipeline.recognize``.  Returns, per image, a list
     of ``Line(box, words)`` from the top of the page to its bottom.  One GPU call for the whole batch; ``ctx`` is a
     ``Context`` (None or True: the default one).  ``rule``: ``max_angle`` (degrees, default 15), ``min_height_ratio`` (0.5),
     ``max_offset`` (0.5), ``max_gap`` (1.5) -- when two words belong to one line, see ``Context.group_lines``.  The defaults
-    are judgement, not fitted to real pages.  Columns are not detected: two columns side by side interleave.  At most 2048
-    words per image (ValueError)."""
+    are judgement, not fitted to real pages.  Columns are not detected: two columns side by side interleave -- hand the
+    line boxes to ``group_blocks`` for a column-aware reading order.  At most 2048 words per image (ValueError)."""
     unknown = set(rule) - {"max_angle", "min_height_ratio", "max_offset", "max_gap"}
     if unknown:
         raise TypeError(f"group_lines: unknown rule parameter(s) {sorted(unknown)}")
     counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
     offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
-    line_of, order, line_counts, boxes = _context(ctx).group_lines(quads, offsets, **rule)
-    pages, line = [], 0
-    for i, lines in enumerate(line_counts.tolist()):
-        words = order[offsets[i]:offsets[i + 1]].tolist()
-        # `order` lists the words line after line; line_of says how many each line has
-        page, at = [], 0
-        lengths = np.bincount(line_of[offsets[i]:offsets[i + 1]], minlength=lines).tolist() if lines else []
-        for k in range(lines):
-            page.append(Line(boxes[line + k], words[at:at + lengths[k]]))
-            at += lengths[k]
-        pages.append(page)
-        line += lines
-    return pages
+    return _groups(Line, offsets, *_context(ctx).group_lines(quads, offsets, **rule))
+
+
+def group_blocks(box_groups, ctx=None, min_gap_x=1.0, min_gap_y=0.75):
+    """Per image its boxes cut into blocks -- columns, paragraphs, headings -- in reading order, by a recursive XY-cut on the
+    GPU (kocr_group_lines with KOCR_LINES_BLOCKS; DESIGN.md section 4, "Blocks").  ``box_groups`` is a list (one entry per
+    image) of (n_i, 4, 2) boxes, in practice the line boxes of ``group_lines``.  Returns, per image, a list of
+    ``Block(box, lines)`` in reading order, ``lines`` the indices into that image's boxes from the top of the block to its
+    bottom.  One GPU call for the whole batch; ``ctx`` as in ``group_lines``.  ``min_gap_x`` / ``min_gap_y``: the narrowest
+    gutter and the smallest paragraph gap that are cut, in mean line heights -- see ``Context.group_blocks``; the defaults
+    are judgement, not fitted to real pages.  The cut is axis-aligned (deskew a rotated page first) and whitespace is its
+    only cue: a paragraph gap wider than the heading's and the footer's is cut before them.  At most 2048 boxes per image
+    (ValueError)."""
+    counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
+    offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
+    return _groups(Block, offsets, *_context(ctx).group_blocks(quads, offsets, min_gap_x=min_gap_x, min_gap_y=min_gap_y))

@@ -209,13 +209,28 @@ class Pipeline:
         of the page to its bottom: ``words`` are recognize()'s own ``(text, box)`` tuples of the line in reading order,
         ``text`` their texts joined by single spaces, ``box`` the (4, 2) float32 rectangle around the line along its axis.
         ``rule``: ``max_angle``, ``min_height_ratio``, ``max_offset``, ``max_gap`` as ``layout.group_lines``.
-        ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list."""
+        ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list.  Columns are not detected:
+        ``recognize_blocks`` reads a page column after column."""
         _one_text_per_word(recognition_kwargs, "recognize_lines joins one text per word")
         predictions = self.recognize(images, detection_kwargs, recognition_kwargs)
         ctx = getattr(self.detector, "_ctx", None)
         pages = _layout.group_lines([[box for _, box in group] for group in predictions], ctx=ctx, **rule)
         return [[(" ".join(group[j][0] for j in line.words), line.box, [group[j] for j in line.words]) for line in lines]
                 for group, lines in zip(predictions, pages)]
+
+    def recognize_blocks(self, images, detection_kwargs=None, recognition_kwargs=None, min_gap_x=1.0, min_gap_y=0.75, **line_rule):
+        """recognize_lines() with the lines of every image cut into blocks -- columns, paragraphs, headings -- in reading
+        order on the GPU (layout.group_blocks on the line boxes, with the detector's context; DESIGN.md section 4,
+        "Blocks"): two columns side by side are read one after the other.  Returns, per image, a list of ``(text, box,
+        lines)`` in reading order: ``lines`` are recognize_lines()' own ``(text, box, words)`` tuples of the block from
+        its top to its bottom, ``text`` their texts joined by ``"\\n"``, ``box`` the (4, 2) float32 axis-aligned box around
+        them.  ``min_gap_x`` / ``min_gap_y`` as ``layout.group_blocks`` (judgement, not fitted to real pages);
+        ``line_rule`` as ``recognize_lines``.  It refuses what recognize_lines() refuses."""
+        pages = self.recognize_lines(images, detection_kwargs, recognition_kwargs, **line_rule)
+        ctx = getattr(self.detector, "_ctx", None)
+        cut = _layout.group_blocks([[box for _, box, _ in lines] for lines in pages], ctx=ctx, min_gap_x=min_gap_x, min_gap_y=min_gap_y)
+        return [[("\n".join(lines[j][0] for j in block.lines), block.box, [lines[j] for j in block.lines]) for block in blocks]
+                for lines, blocks in zip(pages, cut)]
 
     def recognize_characters(self, images, detection_kwargs=None, recognition_kwargs=None, **rule):
         """recognize() with the character boxes of every word, read off the detector's region map on the GPU in the same
