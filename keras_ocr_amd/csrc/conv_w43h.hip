@@ -35,9 +35,31 @@ namespace {
 #define W4H_SCALED_CONSTANTS(sc)                                                                       \
   const float k_s = (sc), k_sA = (sc) * W4_A, k_sB = (sc) * W4_B, k_sA2 = (sc) * W4_A2, k_sB2 = (sc) * W4_B2, \
               k_sA2B2 = (sc) * W4_A2B2, k_sA2PB2 = (sc) * W4_A2PB2
+// The transform is written per COMPONENT with plain scalar fp32 instructions.  As vector expressions (T = v4f / v2f) the
+// compiler selected v_pk_fma_f32 / v_pk_mul_f32 for it, and a packed fp32 instruction that issues beside the K loop's MFMAs
+// stalls a lone wave far longer than the two scalar instructions it replaces (profiles/pk32_ab_notes.txt).  The roundings are
+// pinned to the ones the contracted vector form performed -- which products are fused is spelled out, contraction is off
+// inside -- so the bits are those of every earlier build (tests/test_w43h_bits_gpu.py); the empty asm on every second
+// component's result keeps the SLP vectoriser from pairing the components again.
+//   xi 0, 5:  fma(s, d4, fma(s A2B2, d0, -(s A2PB2 * d2)))
+//   xi 1..4:  fma(+-s a, fma(-b2, d1, d3), fma(-s b2, d2, s * d4))
+__device__ __forceinline__ float w4h_transform1(float d0, float d1, float d2, float d3, float d4, float d5, int xi, float k_s,
+                                                float k_sA, float k_sB, float k_sA2, float k_sB2, float k_sA2B2, float k_sA2PB2) {
+#pragma clang fp contract(off)
+  switch (xi) {
+    case 0: return __builtin_fmaf(k_s, d4, __builtin_fmaf(k_sA2B2, d0, -(k_sA2PB2 * d2)));
+    case 1: return __builtin_fmaf(k_sA, __builtin_fmaf(-W4_B2, d1, d3), __builtin_fmaf(-k_sB2, d2, k_s * d4));
+    case 2: return __builtin_fmaf(-k_sA, __builtin_fmaf(-W4_B2, d1, d3), __builtin_fmaf(-k_sB2, d2, k_s * d4));
+    case 3: return __builtin_fmaf(k_sB, __builtin_fmaf(-W4_A2, d1, d3), __builtin_fmaf(-k_sA2, d2, k_s * d4));
+    case 4: return __builtin_fmaf(-k_sB, __builtin_fmaf(-W4_A2, d1, d3), __builtin_fmaf(-k_sA2, d2, k_s * d4));
+    default: return __builtin_fmaf(k_s, d5, __builtin_fmaf(k_sA2B2, d1, -(k_sA2PB2 * d3)));
+  }
+}
+// The same values from vector expressions (the compiler contracts them to exactly the roundings above and selects packed
+// instructions): kept for conv_w43rh_kernel, which did not gain from the scalar form (profiles/pk32_ab_notes.txt item 4).
 template <class T>
-__device__ __forceinline__ T w4h_transform(const T (&d)[6], int xi, float k_s, float k_sA, float k_sB, float k_sA2, float k_sB2,
-                                           float k_sA2B2, float k_sA2PB2) {
+__device__ __forceinline__ T w4h_transform_packed(const T (&d)[6], int xi, float k_s, float k_sA, float k_sB, float k_sA2, float k_sB2,
+                                                  float k_sA2B2, float k_sA2PB2) {
   switch (xi) {
     case 0: return (k_sA2B2 * d[0] - k_sA2PB2 * d[2]) + k_s * d[4];
     case 1: return (k_s * d[4] - k_sB2 * d[2]) + k_sA * (d[3] - W4_B2 * d[1]);
@@ -46,6 +68,44 @@ __device__ __forceinline__ T w4h_transform(const T (&d)[6], int xi, float k_s, f
     case 4: return (k_s * d[4] - k_sA2 * d[2]) - k_sB * (d[3] - W4_A2 * d[1]);
     default: return (k_sA2B2 * d[1] - k_sA2PB2 * d[3]) + k_s * d[5];
   }
+}
+template <class T>
+__device__ __forceinline__ T w4h_transform(const T (&d)[6], int xi, float k_s, float k_sA, float k_sB, float k_sA2, float k_sB2,
+                                           float k_sA2B2, float k_sA2PB2) {
+  T V;
+#pragma unroll
+  for (int c = 0; c < (int)(sizeof(T) / sizeof(float)); ++c) {
+    float x = w4h_transform1(d[0][c], d[1][c], d[2][c], d[3][c], d[4][c], d[5][c], xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
+    if (c & 1) asm("" : "+v"(x));  // one of each pair is enough
+    V[c] = x;
+  }
+  return V;
+}
+
+// MODE 2 (cells): w4_transform(d, xi) * s with a per-thread s, per component in the same way:
+//   xi 0, 5:  s * (fma(A2B2, d0, -(A2PB2 * d2)) + d4)
+//   xi 1..4:  s * fma(+-a, fma(-b2, d1, d3), fma(-b2, d2, d4))
+__device__ __forceinline__ float w4h_cell_transform1(float d0, float d1, float d2, float d3, float d4, float d5, int xi, float s) {
+#pragma clang fp contract(off)
+  switch (xi) {
+    case 0: return s * (__builtin_fmaf(W4_A2B2, d0, -(W4_A2PB2 * d2)) + d4);
+    case 1: return s * __builtin_fmaf(W4_A, __builtin_fmaf(-W4_B2, d1, d3), __builtin_fmaf(-W4_B2, d2, d4));
+    case 2: return s * __builtin_fmaf(-W4_A, __builtin_fmaf(-W4_B2, d1, d3), __builtin_fmaf(-W4_B2, d2, d4));
+    case 3: return s * __builtin_fmaf(W4_B, __builtin_fmaf(-W4_A2, d1, d3), __builtin_fmaf(-W4_A2, d2, d4));
+    case 4: return s * __builtin_fmaf(-W4_B, __builtin_fmaf(-W4_A2, d1, d3), __builtin_fmaf(-W4_A2, d2, d4));
+    default: return s * (__builtin_fmaf(W4_A2B2, d1, -(W4_A2PB2 * d3)) + d5);
+  }
+}
+template <class T>
+__device__ __forceinline__ T w4h_cell_transform(const T (&d)[6], int xi, float s) {
+  T V;
+#pragma unroll
+  for (int c = 0; c < (int)(sizeof(T) / sizeof(float)); ++c) {
+    float x = w4h_cell_transform1(d[0][c], d[1][c], d[2][c], d[3][c], d[4][c], d[5][c], xi, s);
+    if (c & 1) asm("" : "+v"(x));  // one of each pair is enough
+    V[c] = x;
+  }
+  return V;
 }
 
 constexpr int W4H_TOP = 12;  // scaled inputs lie below 2^13: 5.28 x 2^13 < 65 504
@@ -259,7 +319,7 @@ __global__ __launch_bounds__(256) void conv_w43vh_kernel(W4Params p) {
     if constexpr (MODE == 2) {
       // a per-THREAD scale: folded into the constants it would hold seven more registers across the step (they spill);
       // scaling the transformed value costs one multiply per component and gives the same bits (a power of two)
-      V = w4_transform(d, xi) * sk;
+      V = w4h_cell_transform(d, xi, sk);
     } else {
       W4H_SCALED_CONSTANTS(sk);
       V = w4h_transform(d, xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
@@ -285,7 +345,7 @@ __global__ __launch_bounds__(256) void conv_w43vh_kernel(W4Params p) {
     }
     v2f V;
     if constexpr (MODE == 2) {
-      V = w4_transform(d, xi) * sk;
+      V = w4h_cell_transform(d, xi, sk);
     } else {
       W4H_SCALED_CONSTANTS(sk);
       V = w4h_transform(d, xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
@@ -371,7 +431,10 @@ __global__ __launch_bounds__(256) void conv_w43vh_kernel(W4Params p) {
     auto interleave = [&]() __attribute__((always_inline)) {
       __builtin_amdgcn_sched_group_barrier(0x100, 2 * NP, 0);  // the LDS fetches of the next point first
       if constexpr (KY < 2) {
-        constexpr int VPG = (KY == 0 ? 30 : 16) / (2 * PR - 1) + 1;  // VALU per MFMA gap
+        // VALU per MFMA gap.  The scalar transform and split of one point are about 24 (item 0) / 12 (half item) plain
+        // instructions: five resp. three per gap spread them over all five gaps of a point (one gap hides about five
+        // single-issue instructions; seven per gap left three of the five gaps empty)
+        constexpr int VPG = PR == 3 ? (KY == 0 ? 5 : 3) : (KY == 0 ? 30 : 16) / (2 * PR - 1) + 1;
 #pragma unroll
         for (int i = 0; i < 2 * PR - 1; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
@@ -836,7 +899,7 @@ __global__ __launch_bounds__(256, OCC) void conv_w43rh_kernel(W4Params p) {
   };
   auto produce4 = [&](const v4f (&d)[6], unsigned short* bufp, int xi, float sk) __attribute__((always_inline)) {
     W4H_SCALED_CONSTANTS(sk);
-    const v4f V = w4h_transform(d, xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
+    const v4f V = w4h_transform_packed(d, xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
     unsigned short* dst = bufp + xi * NP * PLANE_R + ldst[0];
     if constexpr (NP == 2) {
       u2v h, l;
@@ -850,7 +913,7 @@ __global__ __launch_bounds__(256, OCC) void conv_w43rh_kernel(W4Params p) {
   };
   auto produce2 = [&](const v2f (&d)[6], unsigned short* bufp, int xi, float sk) __attribute__((always_inline)) {
     W4H_SCALED_CONSTANTS(sk);
-    const v2f V = w4h_transform(d, xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
+    const v2f V = w4h_transform_packed(d, xi, k_s, k_sA, k_sB, k_sA2, k_sB2, k_sA2B2, k_sA2PB2);
     unsigned short* dst = bufp + xi * NP * PLANE_R + ldst[1];
     if constexpr (NP == 2) {
       unsigned h, l;
@@ -1355,7 +1418,7 @@ __global__ __launch_bounds__(256) void conv_w43fh_kernel(W4Params p) {
     };
     auto interleave = [&]() __attribute__((always_inline)) {
       __builtin_amdgcn_sched_group_barrier(0x100, 2 * NP, 0);
-      constexpr int VPG = 30 / (2 * PR - 1) + 1;
+      constexpr int VPG = PR == 3 ? 5 : 30 / (2 * PR - 1) + 1;  // see conv_w43vh_kernel
 #pragma unroll
       for (int i = 0; i < 2 * PR - 1; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);

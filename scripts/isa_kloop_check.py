@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Developer check: per kernel of a device assembly listing (hipcc --cuda-device-only -S), where its scratch instructions sit
 relative to the MFMA stream -- a scratch access between the first and the last MFMA of the K loop is a spill that costs a
-full memory round trip per iteration at one wave per SIMD.  usage: isa_kloop_check.py <file.s> [kernel-substring]"""
+full memory round trip per iteration at one wave per SIMD -- and how many packed fp32 instructions (v_pk_fma_f32,
+v_pk_mul_f32, v_pk_add_f32) stand in that span: beside MFMAs one of them stalls the wave far longer than the two scalar
+instructions it replaces (profiles/pk32_ab_notes.txt).  usage: isa_kloop_check.py <file.s> [kernel-substring]"""
 import re
 import sys
 
@@ -27,5 +29,6 @@ for k, (i, name) in enumerate(starts):
     clusters.append(cur)
     inside = sum(1 for j in sc for c in clusters if len(c) > 30 and c[0] < j < c[-1])
     valu = sum(1 for l in body[mf[0]:mf[-1]] if re.match(r"\s+v_(?!mfma)", l))
+    pk = sum(1 for l in body[mf[0]:mf[-1]] if re.match(r"\s+v_pk_(fma|mul|add)_f32", l))
     print(f"{name[:60]:60s} mfma {len(mf):4d} in {len(clusters)} cluster(s) {[len(c) for c in clusters]}, scratch ops {len(sc):3d}, "
-          f"inside an MFMA cluster {inside}, non-MFMA VALU between first and last MFMA {valu}")
+          f"inside an MFMA cluster {inside}, non-MFMA VALU between first and last MFMA {valu}, of them packed fp32 {pk}")
