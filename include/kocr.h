@@ -292,8 +292,8 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
  * line_counts are complete then too (total is always enough).  line_boxes == NULL with cap_lines == 0 skips the boxes.
  * KOCR_EINVAL with a message, before anything is launched: offsets that do not start at 0 or decrease, a page above
  * KOCR_LINES_MAX_WORDS (naming the page and its count), a non-finite coordinate (naming page and word), a rule parameter out of
- * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is 0 or KOCR_LINES_BLOCKS (below),
- * anything else KOCR_EINVAL with a message that names flags.  Two launches on the ctx stream (profiler rows lines_group,
+ * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is 0, KOCR_LINES_BLOCKS or
+ * KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW (both below), anything else KOCR_EINVAL with a message that names flags.  Two launches on the ctx stream (profiler rows lines_group,
  * lines_pack), one workgroup per page; a page's results do not depend on what else is in the batch.  The results are
  * complete on return.  Workspace comes from the staging arena: like every other call that processes images it ends the
  * validity of resident pipeline results.
@@ -305,7 +305,7 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
  * and it is valid when it is > 0 and >= min_gap H.  A set with valid gaps along x is cut at ALL of them (columns, gutters,
  * sidebars), the parts taken left to right; otherwise, with valid gaps along y, at ONE, the widest (the topmost of equal
  * ones), the upper part first; otherwise it is a block.  Inside a block the quads are ordered by (top, left, index); a block's
- * box is the axis-aligned box of its members.  The cut is axis-aligned -- a rotated page must be deskewed by the caller --
+ * box is the axis-aligned box of its members.  The cut is axis-aligned -- a rotated page needs KOCR_LINES_DESKEW (below) --
  * and whitespace is its only cue: a paragraph gap wider than the heading's and the footer's is cut first.
  * How the arguments are read: max_offset is min_gap_x and max_gap is min_gap_y, both finite and >= 0 (the same check and
  * message); cos_max and min_height_ratio are validated as ever and not read.  What the outputs hold: line_of[j] is the block
@@ -313,9 +313,30 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
  * blocks per page; line_boxes / cap_lines / true_lines the block boxes [tl, tr, br, bl], with the same KOCR_ECAPACITY
  * contract.  Every other check and its message is the one above; a page has at most as many blocks as quads, so the
  * workspace is the same.  Profiler rows blocks_cut, lines_pack.  A call with flags == 0 launches and returns exactly what
- * it did before this flag existed. */
+ * it did before this flag existed.
+ *
+ * flags == KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW (5): block mode for ROTATED pages -- a skewed scan, a photo, a page fed in
+ * sideways or upside down.  The rule is tests/deskew_statement.py ("Rotated pages"), float64 in the
+ * statement's operation order.  Every quad has a direction u = a / |a| with a = (tr + br) / 2 - (tl + bl) / 2 and the weight
+ * w = |a| (the per-word arithmetic of line mode); a quad with w == 0 has none.  The page's axis A is the weighted medoid of
+ * the directions: the u_k with the smallest sum over j of w_j |u_k - u_j|, the smallest k among equal ones; (1, 0) on a page
+ * without any direction.  The chord |u_k - u_j| grows with the angle up to 180 degrees, so an upside-down page has its own
+ * axis, and a medoid is a median: a minority of short quads turned by 90 degrees does not pull it.  Every corner is
+ * expressed in the frame (A, V), V = (-A.y, A.x), and rounded to float32; the cut above runs on those quads unchanged; the
+ * block boxes come back as ROTATED rectangles in page coordinates, tl = X0 A + Y0 V, tr = X1 A + Y0 V, br = X1 A + Y1 V,
+ * bl = X0 A + Y1 V of the cut's frame box, so tl -> tr is the page's text direction, as for line boxes.  On a page whose
+ * directions are all exactly (1, 0) the results equal plain block mode's as numbers.  Inputs, outputs, the capacity
+ * protocol, every check and its message are block mode's.  The workspace grows by the frame quads (total x 8 floats) and
+ * the axes (N x 2 doubles), planned in the same single request and in this mode only.  Profiler rows blocks_axis (one
+ * workgroup per page, n^2 chords), blocks_frame, blocks_cut, blocks_unframe (only with line_boxes), lines_pack; nothing waits
+ * on the host between them.  KOCR_LINES_DESKEW without KOCR_LINES_BLOCKS (4) is KOCR_EINVAL naming flags: lines do not depend
+ * on the page's rotation, and re-ordering them by a page axis is not built.  Not covered: a page whose text runs in several
+ * directions, and a page turned by 90 or 180 degrees whose quads do not run tl -> tr along the text (read such words with
+ * an orientation mode first).  Calls with flags == 0 and flags == KOCR_LINES_BLOCKS launch, reserve and return exactly what
+ * they did before this flag existed. */
 #define KOCR_LINES_MAX_WORDS 2048
 #define KOCR_LINES_BLOCKS 1
+#define KOCR_LINES_DESKEW 4
 int kocr_group_lines(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, double cos_max, double min_height_ratio,
                      double max_offset, double max_gap, int32_t* line_of, int32_t* order, int32_t* line_counts, float* line_boxes,
                      int64_t cap_lines, int64_t* true_lines, int flags);

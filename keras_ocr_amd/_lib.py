@@ -20,6 +20,7 @@ KOCR_U8, KOCR_F32 = 0, 1
 # return codes (include/kocr.h)
 KOCR_OK, KOCR_EINVAL, KOCR_EHIP, KOCR_ENOWEIGHTS, KOCR_ECAPACITY, KOCR_ENOMEM, KOCR_EEMPTYCONTOUR, KOCR_EZERODIV = range(0, -8, -1)
 KOCR_LINES_BLOCKS = 1  # kocr_group_lines' flags: blocks instead of lines (include/kocr.h)
+KOCR_LINES_DESKEW = 4  # beside KOCR_LINES_BLOCKS: the cut runs in the page's own frame
 # minAreaRect rule of getBoxes (include/kocr.h: KOCR_RECT_EXACT / KOCR_RECT_OPENCV)
 MIN_AREA_RECT_RULES = {"exact": 0, "opencv": 1}
 
@@ -1493,9 +1494,23 @@ class Context:
         int32 (N,), block_boxes float32 (blocks, 4, 2) or None)``: the index of each quad's block among its page's blocks;
         per page the page-local quad indices in reading order, block after block, top to bottom inside a block; the
         blocks per page; the box [tl, tr, br, bl] of every block of every page in that order.  The cut is axis-aligned (a
-        rotated page must be deskewed first) and whitespace is its only cue.  ValueError for a gap that is negative or
-        not finite, offsets that do not start at 0 or decrease, a page of more than 2048 quads and a non-finite
-        coordinate (naming page and quad)."""
+        rotated page goes to ``group_blocks_deskewed``) and whitespace is its only cue.  ValueError for a gap that is
+        negative or not finite, offsets that do not start at 0 or decrease, a page of more than 2048 quads and a
+        non-finite coordinate (naming page and quad)."""
+        return Context._group_blocks(self, quads, offsets, min_gap_x, min_gap_y, return_boxes, KOCR_LINES_BLOCKS)
+
+    def group_blocks_deskewed(self, quads, offsets, min_gap_x=1.0, min_gap_y=0.75, return_boxes=True):
+        """``group_blocks`` for rotated pages -- a skewed scan, a photo, a page fed in sideways or upside down
+        (kocr_group_lines with KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW; DESIGN.md section 4, "Rotated pages").  Every page's
+        text direction is estimated on the GPU from its own quads (the weighted medoid of their tl -> tr directions), the
+        cut runs in that frame, and ``block_boxes`` are rotated rectangles in page coordinates, tl -> tr along the text
+        (``layout.box_angle`` reads the skew off any of them).  Arguments, the rest of the return value and the
+        ValueErrors are ``group_blocks``'; so are the numbers on a page that is not rotated.  Not covered: a page whose
+        text runs in several directions, and quads whose tl -> tr is not the reading direction."""
+        return Context._group_blocks(self, quads, offsets, min_gap_x, min_gap_y, return_boxes, KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW)
+
+    def _group_blocks(self, quads, offsets, min_gap_x, min_gap_y, return_boxes, flags):
+        """both block modes; called through the class, so that the arguments are refused by name on any object"""
         gaps = {"min_gap_x": float(min_gap_x), "min_gap_y": float(min_gap_y)}
         for name, value in gaps.items():
             if not (value >= 0 and math.isfinite(value)):
@@ -1511,7 +1526,7 @@ class Context:
         # cos_max and min_height_ratio are checked and not read; the two gaps travel as max_offset and max_gap
         self._check(self._lib.kocr_group_lines(self._h, n, _ptr(q), _ptr(off), 1.0, 0.0, gaps["min_gap_x"], gaps["min_gap_y"], _ptr(block_of),
                                                _ptr(order), _ptr(counts), _ptr(boxes), total if return_boxes else 0, ctypes.byref(blocks),
-                                               KOCR_LINES_BLOCKS), value_error=True)
+                                               flags), value_error=True)
         return block_of, order, counts, (boxes[:blocks.value].copy() if return_boxes else None)
 
     def profile_enable(self, on=True):

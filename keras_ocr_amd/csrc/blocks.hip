@@ -2,6 +2,8 @@
 // (kocr_group_lines with flags == KOCR_LINES_BLOCKS; the reference has no counterpart).  The rule is tests/blocks_statement.py
 // ("Blocks"): a gap is one float64 subtraction of two float32 values, a threshold one float64 product,
 // the mean height one sum in ascending index; this file is compiled with -ffp-contract=off like lines.hip.
+// With KOCR_LINES_DESKEW the cut runs in the page's own frame (tests/deskew_statement.py, "Rotated pages" in the same section):
+// blocks_axis_kernel, blocks_frame_kernel and blocks_unframe_kernel at the end of this file, around an unchanged cut.
 #include "common.h"
 #include <algorithm>
 
@@ -331,6 +333,157 @@ int launch_blocks_cut(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off,
   ProfScope ps(ctx, "blocks_cut", 0, 0);
   hipLaunchKernelGGL(blocks_cut_kernel, dim3(N), dim3(cap / 2), blocks_lds_bytes(max_quads), ctx->stream, d_quads, d_off, cap, min_gap_x,
                      min_gap_y, d_block_of, d_order, d_block_counts, d_boxes);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// ---- KOCR_LINES_DESKEW: the page's own frame (tests/deskew_statement.py) -------------------------------------------------
+
+namespace {
+
+struct BkCost {
+  double c;  // the summed weighted chords of a candidate; +inf where there is none
+  int k;     // the candidate
+};
+// the cheaper candidate, of two equal ones the smaller index: a total order, so the reduction is exact in any order
+__device__ inline BkCost bk_cheaper(BkCost a, BkCost b) { return (b.c < a.c || (b.c == a.c && b.k < a.k)) ? b : a; }
+
+constexpr int BK_NONE = 0x7fffffff;
+
+}  // namespace
+
+// One workgroup per page of at most `cap` quads, blockDim.x = cap / 2: lane t owns the candidates t and t + blockDim.x.
+//   records   "Lines" per-word arithmetic: u = a / w and w of every quad into LDS as float64 (u = (1, 0), w = 0 for a quad
+//             without direction)
+//   costs     every lane walks j = 0 .. n - 1 in that order; the read of quad j is the same address in every lane (an LDS
+//             broadcast), and c_k = c_k + w_j * sqrt(dx * dx + dy * dy) is the statement's sum, operation for operation
+//   arg-min   over (c_k, k), by shuffles inside a wave and through LDS between them
+//   output    axes[2 page], axes[2 page + 1] = the axis; (1, 0) for a page without any direction
+__global__ __launch_bounds__(BK_MAX_THREADS) void blocks_axis_kernel(const float* __restrict__ quads, const int32_t* __restrict__ off, int cap,
+                                                                      double* __restrict__ axes) {
+  extern __shared__ double bk_axis_lds[];
+  __shared__ double best_c[BK_WAVES];
+  __shared__ int best_k[BK_WAVES];
+  const int page = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  const int o = off[page];
+  const int n = min(min(off[page + 1] - o, cap), 2 * T);
+  if (n <= 0) {
+    if (tid == 0) {
+      axes[2 * (size_t)page] = 1.0;
+      axes[2 * (size_t)page + 1] = 0.0;
+    }
+    return;
+  }
+  double *ux = bk_axis_lds, *uy = ux + cap, *wt = uy + cap;
+  const float4* q4 = (const float4*)quads + (size_t)o * 2;
+
+  // records
+  for (int x = tid; x < n; x += T) {
+    const float4 q01 = q4[2 * x], q23 = q4[2 * x + 1];
+    const double p0x = q01.x, p0y = q01.y, p1x = q01.z, p1y = q01.w, p2x = q23.x, p2y = q23.y, p3x = q23.z, p3y = q23.w;
+    const double lx = (p0x + p3x) * 0.5, ly = (p0y + p3y) * 0.5;
+    const double rx = (p1x + p2x) * 0.5, ry = (p1y + p2y) * 0.5;
+    const double ax = rx - lx, ay = ry - ly;
+    const double w = __dsqrt_rn(ax * ax + ay * ay);
+    ux[x] = w == 0 ? 1.0 : ax / w;
+    uy[x] = w == 0 ? 0.0 : ay / w;
+    wt[x] = w;
+  }
+  __syncthreads();
+
+  // costs
+  const int k0 = tid, k1 = tid + T;
+  const bool has0 = k0 < n && wt[k0] > 0, has1 = k1 < n && wt[k1] > 0;
+  const double u0x = has0 ? ux[k0] : 1.0, u0y = has0 ? uy[k0] : 0.0, u1x = has1 ? ux[k1] : 1.0, u1y = has1 ? uy[k1] : 0.0;
+  double c0 = 0.0, c1 = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const double wj = wt[j];
+    if (!(wj > 0)) continue;  // the same j in every lane
+    const double jx = ux[j], jy = uy[j];
+    const double d0x = u0x - jx, d0y = u0y - jy, d1x = u1x - jx, d1y = u1y - jy;
+    c0 = c0 + wj * __dsqrt_rn(d0x * d0x + d0y * d0y);
+    c1 = c1 + wj * __dsqrt_rn(d1x * d1x + d1y * d1y);
+  }
+
+  // arg-min
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  BkCost best = bk_cheaper(BkCost{has0 ? c0 : inf, has0 ? k0 : BK_NONE}, BkCost{has1 ? c1 : inf, has1 ? k1 : BK_NONE});
+  for (int d = 32; d > 0; d >>= 1) best = bk_cheaper(best, BkCost{__shfl_xor(best.c, d), __shfl_xor(best.k, d)});
+  const int wave = tid >> 6, waves = (T + 63) >> 6;
+  if ((tid & 63) == 0) {
+    best_c[wave] = best.c;
+    best_k[wave] = best.k;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int v = 1; v < waves; ++v) best = bk_cheaper(best, BkCost{best_c[v], best_k[v]});
+    const bool any = best.k != BK_NONE;
+    axes[2 * (size_t)page] = any ? ux[best.k] : 1.0;
+    axes[2 * (size_t)page + 1] = any ? uy[best.k] : 0.0;
+  }
+}
+
+// Every corner p of every quad into its page's frame: x' = p.x A.x + p.y A.y, y' = p.x V.x + p.y V.y with V = (-A.y, A.x),
+// float64 of float32, each rounded to float32.  blockIdx.x is the page, one quad per lane.
+__global__ __launch_bounds__(256) void blocks_frame_kernel(const float* __restrict__ quads, const int32_t* __restrict__ off,
+                                                            const double* __restrict__ axes, float* __restrict__ frame) {
+  const int page = blockIdx.x;
+  const int o = off[page], n = off[page + 1] - o;
+  const int x = blockIdx.y * blockDim.x + threadIdx.x;
+  if (x >= n) return;
+  const double ax = axes[2 * (size_t)page], ay = axes[2 * (size_t)page + 1];
+  const double vx = -ay, vy = ax;
+  const float4* src = (const float4*)quads + (size_t)(o + x) * 2;
+  float4* dst = (float4*)frame + (size_t)(o + x) * 2;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float4 q = src[h];
+    const double p0x = q.x, p0y = q.y, p1x = q.z, p1y = q.w;
+    dst[h] = make_float4((float)(p0x * ax + p0y * ay), (float)(p0x * vx + p0y * vy), (float)(p1x * ax + p1y * ay), (float)(p1x * vx + p1y * vy));
+  }
+}
+
+// The first counts[page] boxes of every page, which blocks_cut_kernel wrote at the page's quad offset as (X0, Y0), (X1, Y0),
+// (X1, Y1), (X0, Y1) in the frame, back onto the page in place: tl = X0 A + Y0 V, tr = X1 A + Y0 V, br = X1 A + Y1 V,
+// bl = X0 A + Y1 V, every coordinate a * b + c * d in that order in float64, rounded to float32.
+__global__ __launch_bounds__(256) void blocks_unframe_kernel(float* __restrict__ boxes, const int32_t* __restrict__ off,
+                                                              const int32_t* __restrict__ counts, const double* __restrict__ axes) {
+  const int page = blockIdx.x;
+  const int o = off[page], blocks = min(counts[page], off[page + 1] - o);  // a page has at most as many blocks as quads
+  const double ax = axes[2 * (size_t)page], ay = axes[2 * (size_t)page + 1];
+  const double vx = -ay, vy = ax;
+  for (int k = threadIdx.x; k < blocks; k += blockDim.x) {
+    float4* box = (float4*)boxes + (size_t)(o + k) * 2;
+    const float4 b0 = box[0], b1 = box[1];
+    const double X0 = b0.x, Y0 = b0.y, X1 = b0.z, Y1 = b1.y;
+    box[0] = make_float4((float)(X0 * ax + Y0 * vx), (float)(X0 * ay + Y0 * vy), (float)(X1 * ax + Y0 * vx), (float)(X1 * ay + Y0 * vy));
+    box[1] = make_float4((float)(X1 * ax + Y1 * vx), (float)(X1 * ay + Y1 * vy), (float)(X0 * ax + Y1 * vx), (float)(X0 * ay + Y1 * vy));
+  }
+}
+
+int launch_blocks_axis(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_quads, double* d_axes) {
+  if (N == 0) return KOCR_OK;
+  if (max_quads > KOCR_LINES_MAX_WORDS) KOCR_FAIL(ctx, KOCR_EINVAL, "launch_blocks_axis: a page above KOCR_LINES_MAX_WORDS");
+  const int cap = blocks_cap(max_quads);  // 24 bytes a quad: 48 KB at KOCR_LINES_MAX_WORDS, below the limit that needs no attribute
+  static_assert((size_t)KOCR_LINES_MAX_WORDS * 3 * sizeof(double) + 256 <= 64 * 1024, "the axis kernel's page must fit the default LDS limit");
+  ProfScope ps(ctx, "blocks_axis", 0, 0);
+  hipLaunchKernelGGL(blocks_axis_kernel, dim3(N), dim3(cap / 2), (size_t)cap * 3 * sizeof(double), ctx->stream, d_quads, d_off, cap, d_axes);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+int launch_blocks_frame(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, const double* d_axes, int N, int max_quads, float* d_frame) {
+  if (N == 0 || max_quads == 0) return KOCR_OK;
+  ProfScope ps(ctx, "blocks_frame", 0, 0);
+  hipLaunchKernelGGL(blocks_frame_kernel, dim3(N, (max_quads + 255) / 256), dim3(256), 0, ctx->stream, d_quads, d_off, d_axes, d_frame);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+int launch_blocks_unframe(kocr_ctx* ctx, float* d_boxes, const int32_t* d_off, const int32_t* d_counts, const double* d_axes, int N) {
+  if (N == 0) return KOCR_OK;
+  ProfScope ps(ctx, "blocks_unframe", 0, 0);
+  hipLaunchKernelGGL(blocks_unframe_kernel, dim3(N), dim3(256), 0, ctx->stream, d_boxes, d_off, d_counts, d_axes);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }

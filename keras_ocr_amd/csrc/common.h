@@ -920,6 +920,13 @@ int launch_lines_pack(kocr_ctx* ctx, const float* d_scratch, const int32_t* d_of
 // offset d_off[i], which launch_lines_pack packs.  min_gap_x / min_gap_y: the smallest cut in mean line heights.
 int launch_blocks_cut(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_quads, double min_gap_x, double min_gap_y,
                       int32_t* d_block_of, int32_t* d_order, int32_t* d_block_counts, float* d_boxes);
+// KOCR_LINES_DESKEW ("Rotated pages"; the rule is tests/deskew_statement.py): d_axes [N][2] float64, every page's text direction,
+// the weighted medoid of its quads' directions; d_frame [total][4][2] the quads in their page's frame, which launch_blocks_cut
+// then reads; launch_blocks_unframe maps the first d_block_counts[i] boxes at page i's quad offset back onto the page in
+// place, before launch_lines_pack.
+int launch_blocks_axis(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_quads, double* d_axes);
+int launch_blocks_frame(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, const double* d_axes, int N, int max_quads, float* d_frame);
+int launch_blocks_unframe(kocr_ctx* ctx, float* d_boxes, const int32_t* d_off, const int32_t* d_counts, const double* d_axes, int N);
 
 // chars.hip: the characters of word boxes from the region map (kocr_char_boxes; DESIGN.md section 4, "Characters").  d_heat
 // [N][h][w][2]; M words in packed word order with d_off [N + 1]; word j of page i is quad d_off[i] + j of d_quads with

@@ -1,5 +1,6 @@
 // lines_api.cpp — kocr_group_lines (include/kocr.h, "lines"): argument checks, staging, the two launches of lines.hip; with
-// flags == KOCR_LINES_BLOCKS the first launch is blocks.hip's instead (the same checks, buffers and staging plan).
+// flags == KOCR_LINES_BLOCKS the first launch is blocks.hip's instead (the same checks, buffers and staging plan); with
+// KOCR_LINES_DESKEW beside it the cut runs on the quads in their page's own frame and the boxes are mapped back before the pack.
 #include "abi.h"
 #include <cmath>
 
@@ -9,9 +10,12 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
               int32_t* line_counts, float* line_boxes, int64_t cap_lines, int64_t* true_lines, int flags) {
   const std::string fn("kocr_group_lines");
   if (N < 0 || cap_lines < 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": bad sizes");
-  if (flags != 0 && flags != KOCR_LINES_BLOCKS)
-    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": flags " + std::to_string(flags) + " is neither 0 nor KOCR_LINES_BLOCKS");
-  const bool blocks = flags == KOCR_LINES_BLOCKS;  // max_offset is then read as min_gap_x, max_gap as min_gap_y
+  if (flags == KOCR_LINES_DESKEW)
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": flags " + std::to_string(flags) + ": KOCR_LINES_DESKEW needs KOCR_LINES_BLOCKS (lines do not depend on the page's rotation)");
+  if (flags != 0 && flags != KOCR_LINES_BLOCKS && flags != (KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW))
+    KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": flags " + std::to_string(flags) + " is neither 0 nor KOCR_LINES_BLOCKS, with or without KOCR_LINES_DESKEW");
+  const bool blocks = (flags & KOCR_LINES_BLOCKS) != 0;  // max_offset is then read as min_gap_x, max_gap as min_gap_y
+  const bool deskew = (flags & KOCR_LINES_DESKEW) != 0;  // the cut runs in the page's own frame
   if (!line_boxes && cap_lines != 0) KOCR_FAIL(ctx, KOCR_EINVAL, fn + ": null line_boxes with cap_lines " + std::to_string((long long)cap_lines));
   // !(a <= x) also refuses a NaN
   if (!(rule.cos_max > 0 && rule.cos_max <= 1))
@@ -57,8 +61,10 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
   const size_t quads_b = total * 8 * sizeof(float), off_b = ((size_t)N + 1) * sizeof(int32_t), words_b = total * sizeof(int32_t);
   const size_t counts_b = (size_t)N * sizeof(int32_t), line_off_b = ((size_t)N + 1) * sizeof(long long);
   const size_t boxes_b = line_boxes ? quads_b : 0;  // a page has at most as many lines (or blocks) as words
+  // deskew only: the quads in their page's frame and the axes, counted as arena_alloc places them; nothing in the other modes
+  const size_t axes_b = (size_t)N * 2 * sizeof(double), frame_b = deskew ? quads_b + 256 + axes_b + 256 : 0;
   Staging st{ctx, ctx->io, "kocr_group_lines", false};
-  KOCR_TRY(st.reserve(0, {quads_b, off_b, words_b, words_b, counts_b}, {boxes_b, boxes_b, line_off_b}));
+  KOCR_TRY(st.reserve(frame_b, {quads_b, off_b, words_b, words_b, counts_b}, {boxes_b, boxes_b, line_off_b}));
   const float* d_quads;
   const int32_t* d_off;
   int32_t *d_line_of, *d_order, *d_counts;
@@ -69,7 +75,16 @@ int lines_run(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, 
   KOCR_TRY(st.out(order, words_b, d_order));
   KOCR_TRY(st.out(line_counts, counts_b, d_counts));
   if (line_boxes) KOCR_TRY(st.scratch(boxes_b, d_scratch));
-  if (blocks)
+  if (deskew) {
+    float* d_frame;
+    double* d_axes;
+    KOCR_TRY(st.scratch(quads_b, d_frame));
+    KOCR_TRY(st.scratch(axes_b, d_axes));
+    KOCR_TRY(launch_blocks_axis(ctx, d_quads, d_off, N, max_words, d_axes));
+    KOCR_TRY(launch_blocks_frame(ctx, d_quads, d_off, d_axes, N, max_words, d_frame));
+    KOCR_TRY(launch_blocks_cut(ctx, d_frame, d_off, N, max_words, rule.max_offset, rule.max_gap, d_line_of, d_order, d_counts, d_scratch));
+    if (d_scratch) KOCR_TRY(launch_blocks_unframe(ctx, d_scratch, d_off, d_counts, d_axes, N));
+  } else if (blocks)
     KOCR_TRY(launch_blocks_cut(ctx, d_quads, d_off, N, max_words, rule.max_offset, rule.max_gap, d_line_of, d_order, d_counts, d_scratch));
   else
     KOCR_TRY(launch_lines_group(ctx, d_quads, d_off, N, max_words, rule, d_line_of, d_order, d_counts, d_scratch));

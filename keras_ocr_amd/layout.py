@@ -2,6 +2,7 @@
 (kocr_group_lines; DESIGN.md section 4, "Lines"), the lines cut into blocks -- columns and paragraphs -- in reading order
 (the same call with KOCR_LINES_BLOCKS; "Blocks"), and the type of a word's character boxes (kocr_char_boxes; "Characters").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
 labels that are already grouped -- and there is no host path."""
+import math
 import typing
 
 import numpy as np
@@ -17,8 +18,9 @@ class Line(typing.NamedTuple):
 
 
 class Block(typing.NamedTuple):
-    """One block of a page (a column, a paragraph, a heading): ``box`` (4, 2) float32, the axis-aligned box [tl, tr, br, bl]
-    around its members; ``lines``: the indices of its members in the page's list of boxes, top to bottom."""
+    """One block of a page (a column, a paragraph, a heading): ``box`` (4, 2) float32, the box [tl, tr, br, bl] around its
+    members -- axis-aligned from ``group_blocks``, a rectangle along the page's text direction from
+    ``group_blocks_deskewed``; ``lines``: the indices of its members in the page's list of boxes, top to bottom."""
     box: np.ndarray
     lines: typing.List[int]
 
@@ -96,9 +98,34 @@ def group_blocks(box_groups, ctx=None, min_gap_x=1.0, min_gap_y=0.75):
     ``Block(box, lines)`` in reading order, ``lines`` the indices into that image's boxes from the top of the block to its
     bottom.  One GPU call for the whole batch; ``ctx`` as in ``group_lines``.  ``min_gap_x`` / ``min_gap_y``: the narrowest
     gutter and the smallest paragraph gap that are cut, in mean line heights -- see ``Context.group_blocks``; the defaults
-    are judgement, not fitted to real pages.  The cut is axis-aligned (deskew a rotated page first) and whitespace is its
+    are judgement, not fitted to real pages.  The cut is axis-aligned (``group_blocks_deskewed`` takes a rotated page) and whitespace is its
     only cue: a paragraph gap wider than the heading's and the footer's is cut before them.  At most 2048 boxes per image
     (ValueError)."""
     counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
     offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
     return _groups(Block, offsets, *_context(ctx).group_blocks(quads, offsets, min_gap_x=min_gap_x, min_gap_y=min_gap_y))
+
+
+def group_blocks_deskewed(box_groups, ctx=None, min_gap_x=1.0, min_gap_y=0.75):
+    """``group_blocks`` for rotated pages -- a skewed scan, a photo, a page fed in sideways or upside down (kocr_group_lines
+    with KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW; DESIGN.md section 4, "Rotated pages").  Every image's text direction is
+    estimated on the GPU from its own boxes (the weighted medoid of their tl -> tr directions), the XY-cut runs in that
+    frame, and ``Block.box`` is a rotated rectangle in page coordinates whose tl -> tr runs along the text: ``box_angle``
+    reads the page's skew off any of them.  Arguments, return value and limits are ``group_blocks``', and on a page that is
+    not rotated so are the numbers.  Not covered: a page whose text runs in several directions, and a page turned by 90 or
+    180 degrees whose boxes were not read with ``orientation`` (tl -> tr is then not the reading direction)."""
+    counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
+    offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
+    return _groups(Block, offsets, *_context(ctx).group_blocks_deskewed(quads, offsets, min_gap_x=min_gap_x, min_gap_y=min_gap_y))
+
+
+def box_angle(box):
+    """The direction of ``box``'s tl -> tr in degrees, in (-180, 180], by atan2 (y grows down the page: a positive angle is a
+    clockwise turn on screen); 0.0 for a box without width.  How a caller reads a page's skew off any block box of
+    ``group_blocks_deskewed``.  For display only: nothing on the device uses an angle."""
+    b = np.asarray(box, dtype=np.float64).reshape(4, 2)
+    dx, dy = float(b[1, 0] - b[0, 0]), float(b[1, 1] - b[0, 1])
+    if dx == 0 and dy == 0:
+        return 0.0
+    angle = math.degrees(math.atan2(dy, dx))
+    return 180.0 if angle == -180.0 else angle

@@ -225,10 +225,20 @@ class Pipeline:
         lines)`` in reading order: ``lines`` are recognize_lines()' own ``(text, box, words)`` tuples of the block from
         its top to its bottom, ``text`` their texts joined by ``"\\n"``, ``box`` the (4, 2) float32 axis-aligned box around
         them.  ``min_gap_x`` / ``min_gap_y`` as ``layout.group_blocks`` (judgement, not fitted to real pages);
-        ``line_rule`` as ``recognize_lines``.  It refuses what recognize_lines() refuses."""
+        ``line_rule`` as ``recognize_lines``.  It refuses what recognize_lines() refuses.
+
+        ``deskew=True`` (a keyword beside the line rule's, default False) is for rotated pages -- a skewed scan, a photo, a
+        page fed in sideways or upside down: the page's text direction is estimated on the GPU from the line boxes
+        handed to the cut, the cut runs in that frame (``layout.group_blocks_deskewed``; DESIGN.md section 4, "Rotated
+        pages"), and ``box`` becomes a rotated rectangle whose tl -> tr runs along the text (``layout.box_angle``).  The
+        rest of the return value keeps its shape."""
+        deskew = line_rule.pop("deskew", False)
+        if not isinstance(deskew, (bool, np.bool_)):
+            raise TypeError(f"recognize_blocks: deskew must be True or False, not {deskew!r}")
         pages = self.recognize_lines(images, detection_kwargs, recognition_kwargs, **line_rule)
         ctx = getattr(self.detector, "_ctx", None)
-        cut = _layout.group_blocks([[box for _, box, _ in lines] for lines in pages], ctx=ctx, min_gap_x=min_gap_x, min_gap_y=min_gap_y)
+        group = _layout.group_blocks_deskewed if deskew else _layout.group_blocks
+        cut = group([[box for _, box, _ in lines] for lines in pages], ctx=ctx, min_gap_x=min_gap_x, min_gap_y=min_gap_y)
         return [[("\n".join(lines[j][0] for j in block.lines), block.box, [lines[j] for j in block.lines]) for block in blocks]
                 for lines, blocks in zip(pages, cut)]
 
