@@ -292,8 +292,8 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
  * line_counts are complete then too (total is always enough).  line_boxes == NULL with cap_lines == 0 skips the boxes.
  * KOCR_EINVAL with a message, before anything is launched: offsets that do not start at 0 or decrease, a page above
  * KOCR_LINES_MAX_WORDS (naming the page and its count), a non-finite coordinate (naming page and word), a rule parameter out of
- * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is 0, KOCR_LINES_BLOCKS or
- * KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW (both below), anything else KOCR_EINVAL with a message that names flags.  Two launches on the ctx stream (profiler rows lines_group,
+ * range.  N == 0 and pages without words are valid.  All buffers are HOST arrays; flags is 0, KOCR_LINES_BLOCKS,
+ * KOCR_LINES_BLOCKS | KOCR_LINES_DESKEW or KOCR_LINES_TABLE (all below), anything else KOCR_EINVAL with a message that names flags.  Two launches on the ctx stream (profiler rows lines_group,
  * lines_pack), one workgroup per page; a page's results do not depend on what else is in the batch.  The results are
  * complete on return.  Workspace comes from the staging arena: like every other call that processes images it ends the
  * validity of resident pipeline results.
@@ -333,10 +333,36 @@ int kocr_score(kocr_ctx* ctx, int N, const int32_t* truth_quads, const int32_t* 
  * on the page's rotation, and re-ordering them by a page axis is not built.  Not covered: a page whose text runs in several
  * directions, and a page turned by 90 or 180 degrees whose quads do not run tl -> tr along the text (read such words with
  * an orientation mode first).  Calls with flags == 0 and flags == KOCR_LINES_BLOCKS launch, reserve and return exactly what
- * they did before this flag existed. */
+ * they did before this flag existed.
+ *
+ * flags == KOCR_LINES_TABLE (16): the quads of a page -- any quads, in practice the word boxes of ONE table: a whole page, or the
+ * words of one block -- are put into ROWS, COLUMNS and spanning cells by the white space between them.  The rule is
+ * tests/table_statement.py ("Tables"): a quad counts as its axis-aligned box; H is the mean height as in
+ * block mode, tx = min_gap_x H, ty = min_gap_y H.  Rows: the page by (top, index) is cut at ALL gaps along y that are > 0 and
+ * >= ty (a gap is a box's top minus the largest bottom before it); nothing recurses.  A row's white intervals are its gaps
+ * along x that are > 0 and >= tx, and its two margins up to the page's extent, whatever their width: a short row does not
+ * vote against the columns it does not reach.  Where at least K = max(1, ceil(min_support R)) of the R rows are white, over
+ * a maximal stretch (a, b) with b - a >= tx that ends before the page's right edge, stands a separator; S separators make
+ * S + 1 columns.  Quad j lies in the columns col0 = #{b_s <= its left} to col1 = max(col0, #{b_s < its right}); col1 > col0
+ * is a spanning cell (a title row, a merged header).
+ * How the arguments are read: max_offset is min_gap_x and max_gap is min_gap_y, both finite and >= 0 (block mode's check and
+ * message); min_height_ratio is min_support, under its [0, 1] check; cos_max is validated as ever and not read.  What the
+ * outputs hold: line_of[j] is the row of quad j; order[j] is col0 | col1 << 16; line_counts[i] = R_i + S_i + 1, the page's
+ * bands (0 for a page without quads; R_i = 1 + the largest line_of of the page, every row has a member); line_boxes holds,
+ * per page, its R_i row bands (the page's width, the row's members' height) and then its S_i + 1 column bands (from the page's
+ * left edge or b_{k-1} to a_k or the right edge, the page's height), [tl, tr, br, bl], under the same cap_lines / true_lines /
+ * KOCR_ECAPACITY contract.  A page of n quads has at most 2 n bands (S <= n - 1: every b_s is the left edge of a box other
+ * than the leftmost), so the box workspace is planned for 2 total quads, in the same single request and in this mode only.
+ * Every other check and its message is the one above.  Profiler rows table_grid (one workgroup per page), lines_pack.
+ * KOCR_LINES_TABLE stands alone: every other value that contains it (17, 20, 21, 48, ...) is KOCR_EINVAL naming flags, before
+ * anything is launched -- the rule is axis-aligned, so there is no deskewed table.  Not covered: several tables in one call
+ * (pass each table's words as a page of its own), ruling lines (whitespace is the only cue), a cell whose text wraps (two
+ * rows unless min_gap_y is raised).  Calls with flags 0, 1 and 5 launch, reserve and return exactly what they did before this
+ * flag existed. */
 #define KOCR_LINES_MAX_WORDS 2048
 #define KOCR_LINES_BLOCKS 1
 #define KOCR_LINES_DESKEW 4
+#define KOCR_LINES_TABLE 16
 int kocr_group_lines(kocr_ctx* ctx, int N, const float* quads, const int32_t* offsets, double cos_max, double min_height_ratio,
                      double max_offset, double max_gap, int32_t* line_of, int32_t* order, int32_t* line_counts, float* line_boxes,
                      int64_t cap_lines, int64_t* true_lines, int flags);

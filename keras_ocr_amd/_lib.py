@@ -21,6 +21,7 @@ KOCR_U8, KOCR_F32 = 0, 1
 KOCR_OK, KOCR_EINVAL, KOCR_EHIP, KOCR_ENOWEIGHTS, KOCR_ECAPACITY, KOCR_ENOMEM, KOCR_EEMPTYCONTOUR, KOCR_EZERODIV = range(0, -8, -1)
 KOCR_LINES_BLOCKS = 1  # kocr_group_lines' flags: blocks instead of lines (include/kocr.h)
 KOCR_LINES_DESKEW = 4  # beside KOCR_LINES_BLOCKS: the cut runs in the page's own frame
+KOCR_LINES_TABLE = 16  # alone: rows, columns and spanning cells of a table's word boxes
 # minAreaRect rule of getBoxes (include/kocr.h: KOCR_RECT_EXACT / KOCR_RECT_OPENCV)
 MIN_AREA_RECT_RULES = {"exact": 0, "opencv": 1}
 
@@ -1528,6 +1529,53 @@ class Context:
                                                _ptr(order), _ptr(counts), _ptr(boxes), total if return_boxes else 0, ctypes.byref(blocks),
                                                flags), value_error=True)
         return block_of, order, counts, (boxes[:blocks.value].copy() if return_boxes else None)
+
+    def group_table(self, quads, offsets, min_gap_x=1.0, min_gap_y=0.25, min_support=0.5, return_boxes=True):
+        """The quads of N pages -- any quads, in practice the word boxes of ONE table each: a whole page, or the words of one
+        ``Block`` -- put into rows, columns and spanning cells by the white space between them, in one call
+        (kocr_group_lines with KOCR_LINES_TABLE; DESIGN.md section 4, "Tables"): ``quads`` float32 (total, 4, 2),
+        ``offsets`` (N + 1,), at most 2048 quads on a page.  A quad counts as its axis-aligned box.  Rows: the page is cut at
+        every gap along y of at least ``min_gap_y`` mean heights.  Columns: a separator stands where at least
+        ``min_support`` of the rows (rounded up, at least one) are white over a stretch of at least ``min_gap_x`` mean
+        heights that ends before the page's right edge; a row's margins up to the page's extent count as white.  The
+        defaults are judgement, not fitted to real pages.  Returns ``(row_of int32 (total,), col_first int32 (total,),
+        col_last int32 (total,), row_counts int32 (N,), col_counts int32 (N,), row_boxes, col_boxes)``: the row of every
+        quad and the first and last column it touches (``col_last > col_first``: a spanning cell); rows and columns per
+        page (0 and 0 for a page without quads); the bands [tl, tr, br, bl] of all rows of all pages in page order, float32
+        (rows, 4, 2), and likewise of all columns -- both None without ``return_boxes``.  The rule is axis-aligned and
+        whitespace is its only cue; one table per page.  ValueError for a gap that is negative or not finite,
+        ``min_support`` outside [0, 1], offsets that do not start at 0 or decrease, a page of more than 2048 quads and a
+        non-finite coordinate (naming page and quad)."""
+        rule = {"min_gap_x": float(min_gap_x), "min_gap_y": float(min_gap_y)}
+        for name, value in rule.items():
+            if not (value >= 0 and math.isfinite(value)):
+                raise ValueError(f"group_table: {name} {value} is not a finite number >= 0")
+        min_support = float(min_support)
+        if not 0 <= min_support <= 1:
+            raise ValueError(f"group_table: min_support {min_support} outside [0, 1]")
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 4, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        if len(off) < 1 or off[-1] != len(q):
+            raise ValueError(f"group_table: offsets must hold N + 1 entries and end at the number of boxes, {len(q)}")
+        n, total = len(off) - 1, len(q)
+        row_of, cols, counts = np.zeros(total, np.int32), np.zeros(total, np.int32), np.zeros(n, np.int32)
+        boxes = np.zeros((2 * total, 4, 2), np.float32) if return_boxes else None  # a page of n quads has at most 2 n bands
+        bands = ctypes.c_int64(0)
+        # cos_max is checked and not read; the gaps travel as max_offset and max_gap, min_support as min_height_ratio
+        self._check(self._lib.kocr_group_lines(self._h, n, _ptr(q), _ptr(off), 1.0, min_support, rule["min_gap_x"], rule["min_gap_y"],
+                                               _ptr(row_of), _ptr(cols), _ptr(counts), _ptr(boxes), 2 * total if return_boxes else 0,
+                                               ctypes.byref(bands), KOCR_LINES_TABLE), value_error=True)
+        # a page's rows: 1 + its largest row (every row has a member); its columns: the other bands
+        row_counts = np.array([int(row_of[a:b].max()) + 1 if b > a else 0 for a, b in zip(off[:-1], off[1:])], np.int32).reshape(n)
+        col_counts = counts - row_counts
+        row_boxes = col_boxes = None
+        if return_boxes:
+            first = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+            is_row = np.zeros(int(bands.value), bool)
+            for i in range(n):
+                is_row[first[i]:first[i] + row_counts[i]] = True
+            row_boxes, col_boxes = boxes[:bands.value][is_row], boxes[:bands.value][~is_row]
+        return row_of, cols & 0xFFFF, cols >> 16, row_counts, col_counts, row_boxes, col_boxes
 
     def profile_enable(self, on=True):
         self._check(self._lib.kocr_profile_enable(self._h, int(bool(on))))

@@ -928,6 +928,13 @@ int launch_blocks_axis(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off
 int launch_blocks_frame(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, const double* d_axes, int N, int max_quads, float* d_frame);
 int launch_blocks_unframe(kocr_ctx* ctx, float* d_boxes, const int32_t* d_off, const int32_t* d_counts, const double* d_axes, int N);
 
+// table.hip: the word boxes of a table put into rows, columns and spanning cells (kocr_group_lines with KOCR_LINES_TABLE;
+// DESIGN.md section 4, "Tables").  d_row_of [total] the row of every quad, d_cols [total] col0 | col1 << 16, d_band_counts [N]
+// rows + columns, d_boxes (nullable) [2 total][4][2] the row bands, then the column bands of page i at TWICE its quad offset
+// (a page of n quads has at most 2 n bands): launch_lines_pack packs them when it is given the doubled offsets.
+int launch_table_grid(kocr_ctx* ctx, const float* d_quads, const int32_t* d_off, int N, int max_quads, double min_gap_x, double min_gap_y,
+                      double min_support, int32_t* d_row_of, int32_t* d_cols, int32_t* d_band_counts, float* d_boxes);
+
 // chars.hip: the characters of word boxes from the region map (kocr_char_boxes; DESIGN.md section 4, "Characters").  d_heat
 // [N][h][w][2]; M words in packed word order with d_off [N + 1]; word j of page i is quad d_off[i] + j of d_quads with
 // stride == 0, quad i * stride + j otherwise.  launch_chars_split fills the workspace rows of every word, launch_chars_pack

@@ -1,6 +1,7 @@
 """What follows detection and recognition: the words of a page grouped into text lines, in reading order, on the GPU
 (kocr_group_lines; DESIGN.md section 4, "Lines"), the lines cut into blocks -- columns and paragraphs -- in reading order
-(the same call with KOCR_LINES_BLOCKS; "Blocks"), and the type of a word's character boxes (kocr_char_boxes; "Characters").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
+(the same call with KOCR_LINES_BLOCKS; "Blocks"), the words of a table put into rows, columns and spanning cells (the same call
+with KOCR_LINES_TABLE; "Tables"), and the type of a word's character boxes (kocr_char_boxes; "Characters").  The reference has no counterpart -- its ``tools.combine_line`` / ``fix_line`` serve training
 labels that are already grouped -- and there is no host path."""
 import math
 import typing
@@ -23,6 +24,39 @@ class Block(typing.NamedTuple):
     ``group_blocks_deskewed``; ``lines``: the indices of its members in the page's list of boxes, top to bottom."""
     box: np.ndarray
     lines: typing.List[int]
+
+
+class Cell(typing.NamedTuple):
+    """One cell of a table: the words of one ``row`` that start in column ``col``; it reaches over ``colspan`` columns
+    (more than 1: a spanning cell, such as a title row or a merged header).  ``words``: from ``group_table`` the indices
+    of its words in the page's list of boxes, from ``Pipeline.recognize_table`` recognize()'s own ``(text, box)`` tuples,
+    either way from left to right; ``text``: their texts joined by single spaces (None from ``group_table``, which sees
+    no text)."""
+    row: int
+    col: int
+    colspan: int
+    words: list
+    text: typing.Optional[str] = None
+
+
+class Table(typing.NamedTuple):
+    """The words of one table as a grid ("Tables"): ``rows`` and ``cols``, its size; ``row_boxes``
+    (rows, 4, 2) and ``col_boxes`` (cols, 4, 2) float32, the bands [tl, tr, br, bl] of every row (the table's width, the
+    row's height) and every column (between two separators, the table's height); ``cells``: the ``Cell``s that hold words,
+    in reading order -- row after row, left to right inside a row.  A page without words is a table of 0 x 0."""
+    rows: int
+    cols: int
+    row_boxes: np.ndarray
+    col_boxes: np.ndarray
+    cells: typing.List[Cell]
+
+    def grid(self):
+        """``rows`` lists of ``cols`` strings: every cell's ``text`` at (row, col) -- a spanning cell's at its first column
+        --, ``""`` where no word starts.  Cells without text (``group_table``) show their word indices joined by spaces."""
+        out = [[""] * self.cols for _ in range(self.rows)]
+        for cell in self.cells:
+            out[cell.row][cell.col] = cell.text if cell.text is not None else " ".join(str(w) for w in cell.words)
+        return out
 
 
 class Characters(typing.NamedTuple):
@@ -117,6 +151,38 @@ def group_blocks_deskewed(box_groups, ctx=None, min_gap_x=1.0, min_gap_y=0.75):
     counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
     offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
     return _groups(Block, offsets, *_context(ctx).group_blocks_deskewed(quads, offsets, min_gap_x=min_gap_x, min_gap_y=min_gap_y))
+
+
+def group_table(box_groups, ctx=None, **rule):
+    """Per image its word boxes as a table: rows, columns and spanning cells, by the white space between the boxes, on the
+    GPU (kocr_group_lines with KOCR_LINES_TABLE; DESIGN.md section 4, "Tables").  ``box_groups`` is a list (one entry per
+    image) of (n_i, 4, 2) boxes: the words of ONE table each -- a whole page, or the words of one ``Block``.  Returns, per
+    image, a ``Table``.  One GPU call for the whole batch; ``ctx`` as in ``group_lines``.  ``rule``: ``min_gap_x`` (1.0:
+    the narrowest column gutter, in mean word heights), ``min_gap_y`` (0.25: the smallest leading that separates two
+    rows), ``min_support`` (0.5: the share of the rows that must show a gutter) -- see ``Context.group_table``; the
+    defaults are judgement, not fitted to real pages.  The rule is axis-aligned, whitespace is its only cue (no ruling
+    lines), and a cell whose text wraps becomes two rows unless ``min_gap_y`` is raised.  At most 2048 boxes per image
+    (ValueError)."""
+    unknown = set(rule) - {"min_gap_x", "min_gap_y", "min_support"}
+    if unknown:
+        raise TypeError(f"group_table: unknown rule parameter(s) {sorted(unknown)}")
+    counts, quads = _lib._flatten_boxes(box_groups)  # pylint: disable=protected-access
+    offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int32)
+    row_of, col_first, col_last, row_counts, col_counts, row_boxes, col_boxes = _context(ctx).group_table(quads, offsets, **rule)
+    left = np.asarray(quads, dtype=np.float32).reshape(-1, 4, 2)[:, :, 0].min(axis=1)
+    tables, row_at, col_at = [], 0, 0
+    for i, (rows, cols) in enumerate(zip(np.asarray(row_counts).tolist(), np.asarray(col_counts).tolist())):
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        keys = zip(row_of[a:b].tolist(), col_first[a:b].tolist(), left[a:b].tolist(), range(b - a), col_last[a:b].tolist())
+        cells = {}  # (row, col) -> [last column, words]; filled in reading order, which a dict keeps
+        for row, col, _, j, last in sorted(keys):
+            cell = cells.setdefault((row, col), [last, []])
+            cell[0] = max(cell[0], last)
+            cell[1].append(j)
+        tables.append(Table(rows, cols, row_boxes[row_at:row_at + rows], col_boxes[col_at:col_at + cols],
+                            [Cell(row, col, last - col + 1, words) for (row, col), (last, words) in cells.items()]))
+        row_at, col_at = row_at + rows, col_at + cols
+    return tables
 
 
 def box_angle(box):

@@ -242,6 +242,27 @@ class Pipeline:
         return [[("\n".join(lines[j][0] for j in block.lines), block.box, [lines[j] for j in block.lines]) for block in blocks]
                 for lines, blocks in zip(pages, cut)]
 
+    def recognize_table(self, images, detection_kwargs=None, recognition_kwargs=None, **rule):
+        """recognize() with the words of every image put into the rows, columns and spanning cells of a table on the GPU
+        (layout.group_table with the detector's context; DESIGN.md section 4, "Tables").  Every image is ONE table: a
+        price list, an invoice's item lines -- crop the table, or group the words of one block yourself.  Returns, per image,
+        a ``layout.Table`` whose ``cells`` are in reading order; a cell's ``words`` are recognize()'s own ``(text, box)``
+        tuples from left to right, its ``text`` their texts joined by single spaces; ``table.grid()`` is the rows x cols
+        matrix of texts (``""`` where no word starts, a spanning cell's text at its first column).  ``rule``: ``min_gap_x``,
+        ``min_gap_y``, ``min_support`` as ``layout.group_table`` (judgement, not fitted to real pages).  It refuses what
+        recognize_blocks() refuses: ``beam_width`` / ``lexicon_top`` / ``pattern`` (ValueError), their ``text`` is no
+        string."""
+        _one_text_per_word(recognition_kwargs, "recognize_table joins one text per word")
+        unknown = set(rule) - {"min_gap_x", "min_gap_y", "min_support"}
+        if unknown:
+            raise TypeError(f"recognize_table: unknown rule parameter(s) {sorted(unknown)}")
+        predictions = self.recognize(images, detection_kwargs, recognition_kwargs)
+        ctx = getattr(self.detector, "_ctx", None)
+        tables = _layout.group_table([[box for _, box in group] for group in predictions], ctx=ctx, **rule)
+        return [table._replace(cells=[cell._replace(words=[group[j] for j in cell.words], text=" ".join(group[j][0] for j in cell.words))
+                                      for cell in table.cells])
+                for group, table in zip(predictions, tables)]
+
     def recognize_characters(self, images, detection_kwargs=None, recognition_kwargs=None, **rule):
         """recognize() with the character boxes of every word, read off the detector's region map on the GPU in the same
         pass ("Characters").  Returns, per image, a list of ``(text, box, characters)``: ``characters``
