@@ -826,6 +826,59 @@ int kocr_orient_select(kocr_ctx* ctx, int M, int L, const int32_t* labels, const
                        const int32_t* turns, const float* quads, int32_t* out_labels, float* out_log_word, float* out_char_scores,
                        int32_t* out_turns, float* out_quads, float* out_log_words);
 
+/* ---- long words ---------------------------------------------------------------------- */
+/* The opt-in calls that read a box wider than 200 : 31 in overlapping windows -- the whole route, its results and its
+ * unit-test seams -- are declared in kocr_windows.h beside this file; they are part of this ABI and of libkocr.so.  The rule:
+ *
+ * Every other recognition route fits a box into ONE 31 x 200 crop with scale = min(200 / w, 31 / h), so a box wider than
+ * 200 : 31 is shrunk in both directions and at 20 : 1 its text reaches the recogniser 10 pixels high.  Those calls cut such
+ * a box into K windows along its long side, read every window as an ordinary crop, stitch the windows' fc_12 logit rows
+ * into ONE frame sequence per word and decode that sequence.  Opt-in: no other call launches or returns anything else.
+ *
+ * Constants: the crop is 31 x 200, T = 50 frames of 4 pixels, d = the recogniser's rnn_steps_to_discard.
+ * Parameters: aspect A (float64, finite, >= 200 / 31; 10.0 is a good default), overlap O (a multiple of 8 in [16, 96]; 40),
+ * S = 200 - O, f = O / 8.  KOCR_EINVAL when they are out of range or when d >= 50 - f.
+ *
+ * Per box: ob = get_rotated_box(box) = [tl, tr, br, bl], (w, h) the integers of get_rotated_width_height(ob); a zero w or h
+ * stays KOCR_EZERODIV.
+ *   1. The box is LONG iff (double)w > A * (double)h.  Not long: K = 1 and q_0 = ob, the ordinary crop operation for operation.
+ *   2. Long: K = ceil((31 w - 200 h) / (S h)) + 1 in exact 64-bit integers (the numerator is positive since A >= 200 / 31).
+ *   3. Window k spans the fractions [a_k, b_k] of the top edge tl -> tr and of the bottom edge bl -> br:
+ *      a_k = (double)(k S h) / (double)(31 w), b_k = min(1, (double)((k S + 200) h) / (double)(31 w)), products in int64.
+ *   4. The point at fraction a of an edge p -> q is (float)((double)p + ((double)q - (double)p) * a) per component, in this
+ *      order, never fused; a == 0 takes p's own float32 numbers and a == 1 takes q's.
+ *   5. q_k = [top(a_k), top(b_k), bottom(b_k), bottom(a_k)]; everything behind it is the ordinary set-up of an ordered quad for
+ *      a 31 x 200 crop and the unchanged warp.  The last window is shorter: its crop is narrower and zero-padded on the right.
+ *   6. Frames kept of window k: [lo_k, hi_k) with lo_k = d for k = 0, else f; hi_k = 50 for k = K - 1, else 50 - f.  The seam
+ *      is the middle of the overlap: frame 50 - f of window k and frame f of window k + 1 lie at the same nominal crop x.
+ *   7. The word's sequence has T' = (K - 1) S / 4 + 50 - d frames (K = 1: frames d .. 49, the ordinary ones).
+ *   8. A call is refused with KOCR_EINVAL before any launch when some T' exceeds KOCR_WINDOW_FRAMES_MAX, naming the image and
+ *      the box.
+ * A window's own quad goes through the ordinary set-up, so a window whose integer width or height comes out zero (only boxes a
+ * pixel or two high have such windows) is KOCR_EZERODIV as well.
+ * Window k of box m (image-major box order) is crop offset(m) + k, offset = the exclusive prefix sum of K.  The recogniser
+ * runs on all sum K crops in its usual batches of at most 1024; a word's windows may straddle two batches.  One difference:
+ * a last batch of fewer than 82 crops behind a full one takes crops from it (1040 crops run as 958 + 82).  Below 82 crops the
+ * recogniser's per-frame 1x1 layers run on another GEMM kernel, whose sums round differently in the last bits; this way the
+ * last windows of a call do not depend on how many windows came before them.
+ *
+ * Stitch and decode: row j of word m's sequence is the fc_12 logit row of (window k, frame t), k upwards and t from lo_k to
+ * hi_k - 1 -- copied, never recomputed.  On that sequence: the greedy labels (first maximum on ties, repeats merged ACROSS
+ * seams too, blank dropped), per emitted label the largest arg-max probability of its run, and log_word = minus the exact CTC
+ * loss of the decode over all T' frames -- the rules and the device functions of "Scores" above.  One wave per word, every
+ * reduction in a fixed order, nothing shared between words: on the same logits a K = 1 word comes out bit for bit as
+ * kocr_recognize_boxes with scores gives it, and a word's bits do not depend on the other words of the call.  The logits are
+ * the recogniser's, and the recogniser picks its GEMM kernels by the size of the batch (the 1x1 layers at 82 crops, stn_conv_2
+ * at 12): the two statements hold for whole calls whenever both calls' batches lie on the same side of
+ * those sizes -- always from 82 crops on --, as they do between any two calls of kocr_recognize_boxes itself.
+ *
+ * Not combinable: a beam, a lexicon match, a character set, a pattern, orientation and character boxes switched on on the
+ * context are refused with KOCR_EINVAL naming both sides, by every one of those calls.  uint8 images only.
+ *
+ * Limits.  With the spatial transformer on, the frame <-> x correspondence the seam relies on is nominal, not exact.  The edges
+ * of a trapezoid are cut by linear fractions, not perspective-correct ones.  What windowing does for the reading of real long
+ * words has not been measured (it needs pretrained weights): these calls establish the statement, not an accuracy figure. */
+
 /* ---- measurement -------------------------------------------------------------------- */
 /* When enabled, every kernel launch on the ctx is bracketed by hipEvents on the ctx
  * stream; kocr_profile_report fills parallel arrays (up to cap rows) with per-kernel-name

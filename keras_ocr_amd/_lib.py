@@ -107,6 +107,12 @@ def load_library():
         "kocr_recognition_orientation": (ci, [vp, vp, vp, vp, ci, vp]),
         "kocr_warp_crops_turned": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ctypes.c_double, ci, ci, vp, vp, vp]),
         "kocr_orient_select": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "kocr_recognize_boxes_windowed": (ci, [vp, vp, ci, ci, ci, vp, vp, ctypes.c_double, ci, ci]),
+        "kocr_windowed_results_shape": (ci, [vp, vp, vp]),
+        "kocr_windowed_results": (ci, [vp, vp, vp, vp, vp, vp, ci, ci]),
+        "kocr_window_plan": (ci, [vp, ci, vp, ctypes.c_double, ci, vp, vp, vp, ci, vp]),
+        "kocr_warp_crops_windowed": (ci, [vp, vp, ci, ci, ci, vp, vp, ctypes.c_double, ci, vp, vp, vp, vp, ci, vp]),
+        "kocr_ctc_stitch_decode": (ci, [vp, vp, ci, vp, ci, vp, vp, vp, vp, ci]),
         "kocr_set_scores": (ci, [vp, ci]),
         "kocr_get_scores": (ci, [vp]),
         "kocr_detection_scores": (ci, [vp, vp, ci]),
@@ -529,6 +535,99 @@ class Context:
         self._check(self._lib.kocr_orient_select(self._h, m, width, _ptr(lab), _ptr(logw), _ptr(chars), _ptr(turns), _ptr(quads),
                                                  *[_ptr(a) for a in out]), value_error=True)
         return out
+
+    # -- long words (include/kocr_windows.h) --------------------------------------------------------------------------------
+    def window_plan(self, boxes, aspect=10.0, overlap=40):
+        """The window plan of word boxes, computed on the device (kocr_window_plan): boxes (M,4,2) float32.  Returns windows
+        (M,) int32 = K per box, quads (sum K,4,2) float32 = every window's ordered source quad and ranges (sum K,2) int32 =
+        the frames [lo, hi) kept of every window's crop, for the context's rnn_steps_to_discard.  ValueError for parameters
+        out of range, a box beyond the frame cap or a conflicting switch; ZeroDivisionError for a box without width or height."""
+        flat = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4, 2)
+        m = len(flat)
+        windows, total = np.ones(m, np.int32), ctypes.c_int32(0)
+        rc = self._lib.kocr_window_plan(self._h, m, _ptr(flat), float(aspect), int(overlap), _ptr(windows), None, None, 0,
+                                        ctypes.byref(total))
+        if rc != KOCR_ECAPACITY:
+            self._check(rc, value_error=True)
+        quads, ranges = np.zeros((total.value, 4, 2), np.float32), np.zeros((total.value, 2), np.int32)
+        if total.value:
+            self._check(self._lib.kocr_window_plan(self._h, m, _ptr(flat), float(aspect), int(overlap), _ptr(windows), _ptr(quads),
+                                                   _ptr(ranges), total.value, None), value_error=True)
+        return windows, quads, ranges
+
+    def warp_crops_windowed(self, images, box_groups, aspect=10.0, overlap=40):
+        """The crop stage of the windowed route (kocr_warp_crops_windowed): images (N,H,W,3) uint8, box_groups a list of
+        (n_i,4,2).  Returns crops (sum K,31,200) float32 and the plan as ``window_plan`` (image-major box order): window k of
+        box m is crop offset(m) + k, offset the exclusive prefix sum of windows."""
+        x = np.ascontiguousarray(images, dtype=np.uint8)
+        n, h, w, c = x.shape
+        if c != 3:
+            raise ValueError("images must be RGB")
+        counts, flat = _flatten_boxes(box_groups)
+        m = int(counts.sum())
+        windows, total = np.ones(m, np.int32), ctypes.c_int32(0)
+
+        def call(crops, quads, ranges, cap):
+            return self._lib.kocr_warp_crops_windowed(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), float(aspect), int(overlap),
+                                                      _ptr(crops), _ptr(windows), _ptr(quads), _ptr(ranges), cap, ctypes.byref(total))
+
+        rc = call(None, None, None, 0)
+        if rc != KOCR_ECAPACITY:
+            self._check(rc, value_error=True)
+        t = total.value
+        crops, quads, ranges = np.zeros((t, 31, 200), np.float32), np.zeros((t, 4, 2), np.float32), np.zeros((t, 2), np.int32)
+        if t:
+            self._check(call(crops, quads, ranges, t), value_error=True)
+        return crops, windows, quads, ranges
+
+    def ctc_stitch_decode(self, logits, windows, overlap=40):
+        """Stitch and decode on the caller's logits (kocr_ctc_stitch_decode): logits (sum K,50,C) float32, windows (M,) = K per
+        word.  Returns labels (M,L) int32 (-1 padded), log_word (M,), char_scores (M,L) float32 and frames (M,) int32 = T',
+        L the longest T' (the recogniser's label width for no words)."""
+        from . import tools  # pylint: disable=import-outside-toplevel
+
+        k = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+        m = len(k)
+        discard = 50 - self.crnn_label_width()
+        _, overlap, _ = tools.window_args(200 / 31, overlap, discard)
+        if m and int(k.min()) < 1:
+            raise ValueError("every word has at least one window")
+        lg = np.ascontiguousarray(logits, dtype=np.float32)
+        if lg.ndim != 3 or lg.shape[0] != int(k.sum()) or lg.shape[1] != 50 or lg.shape[2] != self.crnn_classes():
+            raise ValueError(f"logits must have shape (sum of windows = {int(k.sum())}, 50, {self.crnn_classes()}), got {lg.shape}")
+        width = int((k.max() - 1) * ((200 - overlap) // 4) + 50 - discard) if m else self.crnn_label_width()
+        labels, logw = np.full((m, width), -1, np.int32), np.zeros(m, np.float32)
+        chars, frames = np.zeros((m, width), np.float32), np.zeros(m, np.int32)
+        self._check(self._lib.kocr_ctc_stitch_decode(self._h, _ptr(lg), m, _ptr(k), overlap, _ptr(labels), _ptr(logw), _ptr(chars),
+                                                     _ptr(frames), width), value_error=True)
+        return labels, logw, chars, frames
+
+    def windowed_results(self):
+        """The resident rows of the last ``recognize_boxes_windowed`` (kocr_windowed_results_shape / kocr_windowed_results):
+        labels (M,L) int32, log_word (M,), char_scores (M,L) float32, frames (M,) and windows (M,) int32; ValueError when
+        nothing is resident."""
+        m, width = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.kocr_windowed_results_shape(self._h, ctypes.byref(m), ctypes.byref(width)), value_error=True)
+        m, width = m.value, width.value
+        labels, logw = np.full((m, width), -1, np.int32), np.zeros(m, np.float32)
+        chars, frames, windows = np.zeros((m, width), np.float32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        self._check(self._lib.kocr_windowed_results(self._h, _ptr(labels), _ptr(logw), _ptr(chars), _ptr(frames), _ptr(windows), m, width),
+                    value_error=True)
+        return labels, logw, chars, frames, windows
+
+    def recognize_boxes_windowed(self, images, box_groups, aspect=10.0, overlap=40):
+        """Recognizer.recognize_from_boxes with long boxes read in overlapping windows (kocr_recognize_boxes_windowed): images
+        (N,H,W,3) uint8, box_groups a list of (n_i,4,2).  Returns ``windowed_results()``: ragged rows of width L = the longest
+        sequence of the call (the label width for no boxes).  ValueError for parameters out of range, a box beyond the frame
+        cap (naming it) or a switch that cannot be combined with it; ZeroDivisionError for a box without width or height."""
+        x = np.ascontiguousarray(images, dtype=np.uint8)
+        if x.ndim != 4 or x.shape[3] != 3:
+            raise ValueError("images must be (N,H,W,3) RGB")
+        n, h, w, _ = x.shape
+        counts, flat = _flatten_boxes(box_groups)
+        self._check(self._lib.kocr_recognize_boxes_windowed(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), float(aspect),
+                                                            int(overlap), 0), value_error=True)
+        return self.windowed_results()
 
     # -- character boxes (include/kocr.h: "characters") ----------------------------------------------------------------
     def set_char_boxes(self, on=True, peak_threshold=0.4, valley_ratio=0.7, extent_threshold=0.2):

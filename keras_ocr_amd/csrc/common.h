@@ -10,6 +10,7 @@
 #include <cstring>
 #include <type_traits>
 #include "../../include/kocr.h"
+#include "../../include/kocr_windows.h"
 
 // ---------------------------------------------------------------------------------------
 // error plumbing
@@ -415,11 +416,23 @@ struct kocr_ctx {
   void keep_orientation(const int* d_turns, const float* d_quads, const float* d_pairs, int M) {
     last_or = {d_turns, d_quads, d_pairs, M, resident(orient_mode != KOCR_ORIENT_OFF)};
   }
+  // long words (include/kocr_windows.h; DESIGN.md section 4, "Long words"): kocr_recognize_boxes_windowed leaves its ragged rows
+  // in the io arena for kocr_windowed_results_shape / kocr_windowed_results.  lw: the row width, the longest T' of the call.
+  // Valid like last_pl; never OFF: the call has no switch.
+  struct LastWindowed {
+    const int32_t* d_labels = nullptr;   // [M][lw]
+    const float* d_logw = nullptr;       // [M]
+    const float* d_chars = nullptr;      // [M][lw]
+    const int32_t* d_frames = nullptr;   // [M]
+    const int32_t* d_windows = nullptr;  // [M]
+    int M = 0, lw = 0;
+    Resident state = Resident::NONE;
+  } last_win;
   // Whoever sizes an arena is about to overwrite what the records point at: arena_reserve calls this, and so does an entry
   // point that replaces the results without sizing one.  The one list of what there is to forget.
   void invalidate_results() {
     last_pl.state = last_sc.det = last_sc.rec = last_beam.state = last_lex.state = last_ch.state = last_or.state = last_pat.state =
-        Resident::NONE;
+        last_win.state = Resident::NONE;
   }
   // what an entry point leaves resident at its end (with the switch off: only the fact that it was off)
   void keep_det_scores(const float* d, int N, int cap) {
@@ -613,6 +626,9 @@ int launch_conv_w43(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in, const T
 int prepare_dsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw);
 bool dsplit_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);
 bool dsplit_usable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);
+// launch_conv prefers conv_ds from this many pixels on; below it a layer stays on the fp32 MFMA kernel, whose sums round
+// differently.  The recogniser's per-frame 1x1 layers (50 pixels a crop) cross it at 82 crops.
+constexpr size_t DSPLIT_MIN_PIXELS = 4096;
 // conv_hsplit.hip
 int prepare_hsplit(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw);
 bool hsplit_applicable(kocr_ctx* ctx, const ConvLayer& L, const Tensor& in);
@@ -753,6 +769,8 @@ struct CrnnDecode {
 // The recogniser on d_crops [M][31][200] (device), three ways over one body -- the launches up to the stop are the same in all
 // three: up to the Concatenate output, written to d_feats [M][50][256] (kocr_crnn_features); up to fc_12's logits, *d_logits =
 // [M][50][n_classes] in the workspace (crnn_ctc_loss); the whole recogniser with what `rq` asks for behind fc_12.
+// crops of the smallest batch that takes the large-batch kernels for the per-frame 1x1 layers (crnn.cpp); 0: no such size
+int crnn_small_batch(const kocr_ctx* ctx);
 int crnn_features(kocr_ctx* ctx, const float* d_crops, int M, float* d_feats);
 int crnn_logits(kocr_ctx* ctx, const float* d_crops, int M, const float** d_logits);
 int crnn_forward(kocr_ctx* ctx, const float* d_crops, int M, const CrnnDecode& rq);
@@ -853,6 +871,26 @@ int launch_warp_prepare_turned(kocr_ctx* ctx, const float* d_boxes, const int* d
 int launch_orient_select(kocr_ctx* ctx, const int* d_lab, const float* d_logw, const float* d_chars, const int* d_turns,
                          const float* d_quads, long M, int LW, int* o_lab, float* o_logw, float* o_chars, int* o_turn, float* o_quad,
                          float* o_pair);
+
+// windows.hip: long words (include/kocr_windows.h).  A window of the call: its word, the frames [lo, hi) kept of its crop and the
+// row of the call's ragged sequence buffer [sum T'][C] that frame lo goes to.
+struct WindowRec {
+  int word, lo, hi, pad;
+  long long row;
+};
+// The plan on the device for M boxes d_boxes [M][4][2] of images d_img_of [M]: d_K [M] windows and d_T [M] frames per word, their
+// ordered boxes d_ob [M][4][2], the
+// exclusive prefix sums d_woff / d_roff [M + 1], and per window (total = sum K of them, known to the host from the same
+// function) its source quad, warp parameters and record.  *d_status: max return code as warp_prepare (the caller zeroes it).
+int launch_window_plan(kocr_ctx* ctx, const float* d_boxes, const int* d_img_of, int M, double aspect, int overlap, int discard,
+                       long total, int* d_K, int* d_T, float* d_ob, long long* d_woff, long long* d_roff, WarpParam* d_prm,
+                       float* d_quads, WindowRec* d_rec, int* d_status);
+// The kept logit rows of windows [0, n) of d_rec, whose logits are d_logits [n][50][C], into the ragged buffer d_seq
+int launch_window_stitch(kocr_ctx* ctx, const float* d_logits, const WindowRec* d_rec, int n, int C, float* d_seq);
+// crnn_kernels.hip: ctc_scores_kernel's two passes on word m's frames d_seq[d_roff[m] .. + d_T[m]) of C classes: labels / chars
+// [M][LW] (-1 / 0 behind the decode), logw [M]; LW >= every d_T[m] (the host knows: it sizes the LDS)
+int launch_ctc_scores_ragged(kocr_ctx* ctx, const float* d_seq, const long long* d_roff, const int* d_T, int M, int C, int LW,
+                             int* d_labels, float* d_logw, float* d_chars);
 
 // warp.hip: detection.compute_maps for a batch of pages (kocr_compute_maps).  A slot is one quad drawn into one plane (0 text,
 // 1 link) of one page: the inverse homography and the pixel box [x0, x1] x [y0, y1] it may touch (x1 < x0: nothing).

@@ -606,7 +606,7 @@ bool dsplit_usable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
 // ... and launch_conv's dispatch prefers it: small GEMMs (the CRNN's dense layers) stay on the fp32 kernel, nothing to
 // gain below a few tiles
 bool dsplit_applicable(const kocr_ctx* ctx, const ConvLayer& L, const Tensor& in) {
-  return dsplit_usable(ctx, L, in) && in.pixels() >= 4096;
+  return dsplit_usable(ctx, L, in) && (size_t)in.pixels() >= DSPLIT_MIN_PIXELS;
 }
 
 template <int WM, int WN, int HALF, int UP = 0, int PAIR = 0>

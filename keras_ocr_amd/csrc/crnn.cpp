@@ -73,6 +73,10 @@ struct Blob {
 
 int crnn_classes(kocr_ctx* ctx) { return ctx->crnn && ctx->crnn->loaded ? ctx->crnn->n_classes : 0; }
 int crnn_label_width(kocr_ctx* ctx) { return T - (ctx->crnn ? ctx->crnn->discard : DISCARD); }
+// The smallest batch whose per-frame 1x1 layers (fc_9, the LSTM projections, fc_12: T pixels a crop) launch_conv sends to
+// conv_ds; a smaller batch runs them on the fp32 MFMA kernel, whose sums round differently.  0: conv_ds is switched off on this
+// context (KOCR_DSPLIT=0), every batch takes the same kernel.
+int crnn_small_batch(const kocr_ctx* ctx) { return ctx->sw.dsplit ? (int)((DSPLIT_MIN_PIXELS + T - 1) / T) : 0; }
 int crnn_set_discard(kocr_ctx* ctx, int d) {
   if (d < 0 || d >= T) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_crnn_set_rnn_steps_to_discard: 0 <= steps < 50 (recognition.py:328)");
   if (!ctx->crnn) ctx->crnn = new CrnnNet();

@@ -541,6 +541,54 @@ __global__ __launch_bounds__(64) void ctc_scores_kernel(const float* __restrict_
   if (lane == 0) logw[m] = -loss;
 }
 
+// ---- long words ("Long words"): ctc_scores_kernel on a RAGGED batch.  Word m's frames are rows
+// roff[m] .. roff[m] + Tn[m] - 1 of seq [sum T'][C] (the stitched windows; nothing is discarded any more), its label and score
+// rows are LW wide, LW >= every Tn (the launcher sizes the LDS from it: [2][Sp] alpha rows, then int[LW + 1]).  The two passes
+// are ctc_scores_kernel's, expression for expression, through the same device functions: a word of one window comes out bit
+// for bit as ctc_scores_kernel gives its crop, and since one wave owns a word and nothing is shared between words, a word's
+// bits do not depend on the batch.  No character sets (the windowed calls refuse them): the unmasked instantiations.
+__global__ __launch_bounds__(64) void ctc_scores_ragged_kernel(const float* __restrict__ seq, const long long* __restrict__ roff,
+                                                               const int* __restrict__ Tn, int C, int LW, int* __restrict__ labels,
+                                                               float* __restrict__ logw, float* __restrict__ chars, int Sp) {
+  extern __shared__ float la[];
+  int* dec = reinterpret_cast<int*>(la + 2 * Sp);
+  const int m = blockIdx.x, lane = threadIdx.x;
+  const int To = min(max(Tn[m], 0), LW), blank = C - 1;  // clamped: whatever the buffers hold, the rows are LW wide
+  const float* y0 = seq + (size_t)roff[m] * C;
+  int prev = -1, k = 0;
+  float run = 0.f;
+  for (int t = 0; t < To; ++t) {
+    const float* row = y0 + (size_t)t * C;
+    float bv;
+    int bi;
+    ctc_row_argmax<false>(row, C, lane, bv, bi);
+    const float s = ctc_row_expsum<false>(row, C, lane, bv);
+    if (lane == 0) {
+      const float p = ctc_softmax(bv, bv, s);
+      if (bi != prev && bi != blank) {
+        if (k) chars[(size_t)m * LW + k - 1] = run;
+        dec[k] = bi;
+        labels[(size_t)m * LW + k++] = bi;
+        run = p;
+      } else if (bi == prev && bi != blank) {
+        run = fmaxf(run, p);
+      }
+      prev = bi;
+    }
+  }
+  if (lane == 0) {
+    if (k) chars[(size_t)m * LW + k - 1] = run;
+    dec[LW] = k;
+    for (; k < LW; ++k) {
+      labels[(size_t)m * LW + k] = -1;
+      chars[(size_t)m * LW + k] = 0.f;
+    }
+  }
+  __syncthreads();
+  const float loss = ctc_loss_wave<true, false>(y0, C, dec, dec[LW], To, la, Sp, lane);
+  if (lane == 0) logw[m] = -loss;
+}
+
 // ---- beam search ("Beam search"): CTC prefix beam search without a language model (Graves 2012,
 // Hannun 2014; keras.backend.ctc_decode(greedy=False)), one wave (= one workgroup) per crop, lane i owning beam entry i.
 // Frame probabilities are the loss's q_t (ctc_loss_wave<true>: fc_12's softmax + eps, renormalised), float32 log domain.
@@ -997,6 +1045,23 @@ int launch_ctc_scores(kocr_ctx* ctx, const float* d_logits, int M, int T, int C,
   else
     hipLaunchKernelGGL(ctc_scores_kernel<false>, dim3(M), dim3(64), lds, ctx->stream, d_logits, T, C, discard, d_labels, d_probs, d_logw,
                        d_chars, Sp, cm);
+  KOCR_HIP(ctx, hipGetLastError());
+  return KOCR_OK;
+}
+
+// ctc_scores_ragged_kernel: one wave per word; labels / chars [M][LW], logw [M]
+int launch_ctc_scores_ragged(kocr_ctx* ctx, const float* d_seq, const long long* d_roff, const int* d_T, int M, int C, int LW,
+                             int* d_labels, float* d_logw, float* d_chars) {
+  if (M <= 0) return KOCR_OK;
+  if (LW < 1 || LW > KOCR_WINDOW_FRAMES_MAX || C < 1) KOCR_FAIL(ctx, KOCR_EINVAL, "ctc_scores_ragged: bad sizes");
+  // LDS: two alpha rows of Sp floats, Sp = 2 LW + 1 rounded up to 64, then the label row and its length, LW + 1 ints; no
+  // mask words (no character sets here).  At LW = KOCR_WINDOW_FRAMES_MAX = 2048: Sp = 4160, 2 * 4160 * 4 + 2049 * 4 =
+  // 33 280 + 8 196 = 41 476 bytes, under the 64 KB a workgroup gets without raising the kernel's limit.
+  const int Sp = (2 * LW + 1 + 63) & ~63;
+  const size_t lds = (size_t)2 * Sp * sizeof(float) + (size_t)(LW + 1) * sizeof(int);
+  ProfScope ps(ctx, "ctc_scores_ragged", 0, 4.0 * M * LW * C * 4);
+  hipLaunchKernelGGL(ctc_scores_ragged_kernel, dim3(M), dim3(64), lds, ctx->stream, d_seq, d_roff, d_T, C, LW, d_labels, d_logw, d_chars,
+                     Sp);
   KOCR_HIP(ctx, hipGetLastError());
   return KOCR_OK;
 }

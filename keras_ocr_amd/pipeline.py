@@ -527,6 +527,41 @@ class Pipeline:
                                np.array([o.log_words for o in how], np.float32).reshape(-1, 2))
         return out, [scale for _, scale in resized]
 
+    def recognize_windowed(self, images, aspect=10.0, overlap=40, detection_kwargs=None, return_scores=False):
+        """recognize() with long words read in overlapping windows ("Long words"): the detector runs as
+        in recognize(), then ``Recognizer.recognize_from_boxes_windowed`` reads its boxes -- a box wider than ``aspect`` times
+        its height in windows stitched on the GPU, every other box as ever.  The stage-wise route (resize, detect, windowed
+        recogniser), not the fused call.  Returns what recognize() returns, (text, box) tuples per image with the boxes in
+        input-image pixels -- recognize()'s boxes, and its texts for every box that is not long --, or, with
+        ``return_scores=True``, recognize_with_scores()' (text, box, score) tuples.  uint8 images only (NotImplementedError)."""
+        read = getattr(self.recognizer, "recognize_from_boxes_windowed", None)
+        if read is None:
+            raise TypeError(f"the recognizer ({type(self.recognizer).__name__}) cannot read boxes in windows (it has no "
+                            "recognize_from_boxes_windowed method)")
+        if not isinstance(images, np.ndarray):
+            images = [tools.read(image) for image in images]
+        images = [np.ascontiguousarray(im) for im in images]
+        if any(im.dtype != np.uint8 for im in images):
+            raise NotImplementedError("windowed reading: only uint8 images are read in windows (the float crop path has no window plan)")
+        if not images:
+            return []
+        own = getattr(self.detector, "_ctx", None)
+        resized = [tools.resize_image(image, max_scale=self.scale, max_size=self.max_size, **({"ctx": own} if own is not None else {}))
+                   for image in images]
+        max_height, max_width = np.array([image.shape[:2] for image, _ in resized]).max(axis=0)
+        padded = np.array([tools.pad(image, width=int(max_width), height=int(max_height)) for image, _ in resized])
+        detection_kwargs = dict(detection_kwargs or {})
+        if return_scores:
+            box_groups, detection = _scores.need("detector", self.detector, "detect")(images=padded, return_scores=True, **detection_kwargs)
+        else:
+            box_groups, detection = self.detector.detect(images=padded, **detection_kwargs), None
+        words = read(padded, box_groups, aspect=aspect, overlap=overlap, return_scores=return_scores)
+        adjusted = self._adjust(box_groups, [scale for _, scale in resized])
+        if not return_scores:
+            return [list(zip(texts, boxes)) for texts, boxes in zip(words, adjusted)]
+        return [[(text, box, score._replace(detection=float(d))) for (text, score), box, d in zip(group, boxes, np.asarray(det).reshape(-1))]
+                for group, boxes, det in zip(words, adjusted, detection)]
+
     def recognize_device(self, d_ptr, n, h, w, detection_kwargs=None, return_scores=False):
         """Same as recognize() for a batch already resident in HBM: ``d_ptr`` = device pointer of an
         (n,h,w,3) uint8 tensor (e.g. ``torch.Tensor.data_ptr()``)."""

@@ -548,6 +548,38 @@ class Recognizer:
             words = [(*word, o) if return_scores else (word, o) for word, o in zip(words, how)]
         return [words[start:end] for start, end in start_end]
 
+    def recognize_from_boxes_windowed(self, images, box_groups, aspect=10.0, overlap=40, return_scores=False, return_windows=False):
+        """``recognize_from_boxes`` with long words read in overlapping windows (DESIGN.md section 4, "Long words";
+        include/kocr_windows.h): a box whose width exceeds ``aspect`` times its height is cut along its long side into 31 x 200
+        windows that overlap by ``overlap`` crop pixels, the windows' frames are stitched into one sequence on the GPU and
+        that sequence is decoded; every other box is read as ever, bit for bit.  Per image a list of texts, or of
+        ``(text, score)`` with ``return_scores`` (``score`` a ``scores.Score`` whose ``detection`` is None, ``log_word`` the exact
+        CTC log-probability over the whole sequence); ``return_windows=True`` appends every word's window count.  ValueError
+        for ``aspect`` < 200 / 31, an ``overlap`` that is no multiple of 8 in [16, 96], a box of more than 2048 frames, or a
+        switch of the context that cannot be combined with it; uint8 images only (NotImplementedError)."""
+        assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
+        tools.window_args(aspect, overlap, 50 - self._ctx.crnn_label_width())
+        images = [np.asarray(tools.read(image)) for image in images]
+        if any(im.dtype != np.uint8 for im in images):
+            raise NotImplementedError("windowed reading: only uint8 images are read in windows (the float crop path has no window plan)")
+        runs = []  # one call for images of one size, else one per image (as recognize_from_boxes)
+        if len({im.shape for im in images}) == 1:
+            runs.append(self._ctx.recognize_boxes_windowed(np.stack(images), box_groups, aspect, overlap))
+        else:
+            runs.extend(self._ctx.recognize_boxes_windowed(im[np.newaxis], [boxes], aspect, overlap) for im, boxes in zip(images, box_groups))
+        words = []
+        for labels, log_word, chars, _, windows in runs:
+            texts = self._decode(labels) if len(labels) else []
+            row = list(zip(texts, _scores.assemble(labels, log_word, chars))) if return_scores else texts
+            if return_windows:
+                row = [(*w, int(k)) if return_scores else (w, int(k)) for w, k in zip(row, windows)]
+            words.extend(row)
+        out, start = [], 0
+        for boxes in box_groups:
+            out.append(words[start:start + len(boxes)])
+            start += len(boxes)
+        return out
+
     def _words(self, out):
         """A ``Results``' crops as what recognize_from_boxes returns for each: the text, or its alternatives (``beam``), or
         its matches (``lexicon``) [paired with the ``Score`` of the greedy decode]"""

@@ -132,6 +132,59 @@ def tile_plan(height, width, tile, overlap):
                     [(y0, y1, x0, x1) for y0, y1 in ys for x0, x1 in xs])
 
 
+class WindowPlan(typing.NamedTuple):
+    """``window_plan``'s result.  ``windows`` K; ``fractions`` per window (a, b) of the box's long edges; ``ranges`` per
+    window the frames (lo, hi), half-open, kept of its crop; ``frames`` T', the length of the word's sequence."""
+    windows: int
+    fractions: typing.List[typing.Tuple[float, float]]
+    ranges: typing.List[typing.Tuple[int, int]]
+    frames: int
+
+
+WINDOW_FRAMES_MAX = 2048  # include/kocr_windows.h: KOCR_WINDOW_FRAMES_MAX
+
+
+def window_args(aspect=10.0, overlap=40, discard=2):
+    """(aspect, overlap, discard) as float, int, int, or ValueError naming the argument: ``aspect`` finite and at least
+    200 / 31, ``overlap`` a multiple of 8 in [16, 96], 0 <= ``discard`` < 50 - overlap / 8 (include/kocr_windows.h; the library
+    checks the same)."""
+    aspect = float(aspect)
+    if int(overlap) != overlap or int(discard) != discard:
+        raise ValueError(f"overlap {overlap!r} and discard {discard!r} must be integers")
+    overlap, discard = int(overlap), int(discard)
+    if not (np.isfinite(aspect) and aspect >= 200 / 31):
+        raise ValueError(f"aspect {aspect} must be finite and at least 200 / 31")
+    if overlap % 8 or not 16 <= overlap <= 96:
+        raise ValueError(f"overlap {overlap} must be a multiple of 8 in [16, 96]")
+    if not 0 <= discard < 50 - overlap // 8:
+        raise ValueError(f"discard {discard} must lie in [0, 50 - overlap / 8 = {50 - overlap // 8})")
+    return aspect, overlap, discard
+
+
+def window_plan(w, h, aspect=10.0, overlap=40, discard=2):
+    """How a word box of ``w`` x ``h`` pixels (the integers of ``get_rotated_width_height``) is read in overlapping windows
+    (include/kocr_windows.h; DESIGN.md section 4, "Long words"): the integer part of the rule.  One window unless
+    float(w) > aspect * float(h); else K = ceil((31 w - 200 h) / (S h)) + 1 with S = 200 - overlap; window k spans
+    [k S h / (31 w), min(1, (k S + 200) h / (31 w))] of the long edges and keeps the frames [discard if k == 0 else
+    overlap / 8, 50 if k == K - 1 else 50 - overlap / 8); T' = (K - 1) S / 4 + 50 - discard.  ValueError for parameters out of
+    range, ZeroDivisionError for a zero ``w`` or ``h``.  Needs no GPU."""
+    aspect, overlap, discard = window_args(aspect, overlap, discard)
+    w, h = int(w), int(h)
+    if w < 0 or h < 0:
+        raise ValueError(f"window_plan: a {w} x {h} box")
+    if w == 0 or h == 0:
+        raise ZeroDivisionError("division by zero")
+    stride, f = 200 - overlap, overlap // 8
+    num = 31 * w - 200 * h
+    k_n = -(-num // (stride * h)) + 1 if float(w) > aspect * float(h) and num > 0 else 1
+    if k_n == 1:
+        fractions = [(0.0, 1.0)]
+    else:
+        fractions = [(k * stride * h / (31 * w), min(1.0, (k * stride + 200) * h / (31 * w))) for k in range(k_n)]
+    ranges = [(discard if k == 0 else f, 50 if k == k_n - 1 else 50 - f) for k in range(k_n)]
+    return WindowPlan(k_n, fractions, ranges, (k_n - 1) * (stride // 4) + 50 - discard)
+
+
 def pad(image, width: int, height: int, cval: int = 255):
     """tools.pad (tools.py:356-375)."""
     if len(image.shape) == 3:
