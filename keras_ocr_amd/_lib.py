@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from .extras import Extras  # pylint: disable=cyclic-import  (it reads this module's validators when called)
 from .results import Results, empty_beam, empty_lexicon, empty_orientation, empty_pattern, empty_scores
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -224,21 +225,6 @@ def _char_lists(counts, quads, scores):
     return pages
 
 
-@contextlib.contextmanager
-def _option_scope(get, set_, value, restore=None):
-    """One of a context's switches for one call: read the old setting, set ``value``, and afterwards hand the old setting to
-    ``restore`` (default: ``set_``).  ``value`` None: the context's own setting, and no call at all."""
-    if value is None:
-        yield
-        return
-    old = get()
-    set_(value)
-    try:
-        yield
-    finally:
-        (restore or set_)(old)
-
-
 def beam_args(beam_width, top_paths=1):
     """(beam_width, top_paths) as ints, or ValueError naming the argument: 1 <= beam_width <= 64, 1 <= top_paths <=
     beam_width (include/kocr.h: "Beam search"; the library checks the same)."""
@@ -263,16 +249,6 @@ def orientation_args(orientation, tall_ratio=1.5):
     if not (math.isfinite(ratio) and ratio > 0):
         raise ValueError(f"tall_ratio {tall_ratio!r} must be finite and positive")
     return ORIENTATION_MODES[orientation], ratio
-
-
-def refuse_orientation_with(orientation, **others):
-    """ValueError naming both arguments when ``orientation`` is asked for together with one of ``others`` (name=value; None
-    and False count as not asked for): beam alternatives, lexicon matches and character boxes describe ONE reading."""
-    if orientation is None:
-        return
-    for name, value in others.items():
-        if value is not None and value is not False:
-            raise ValueError(f"orientation and {name} cannot be combined: ask for one of the two")
 
 
 class Context:
@@ -459,10 +435,6 @@ class Context:
     def get_scores(self):
         return bool(self._check(self._lib.kocr_get_scores(self._h)))
 
-    def _scores_scope(self, on):
-        """The switch for one call (``return_scores=True``); falsy: the context's own setting."""
-        return _option_scope(self.get_scores, self.set_scores, True if on else None)
-
     # -- orientation (include/kocr.h: "orientation") --------------------------------------------------------------------
     def set_orientation(self, mode=0, tall_ratio=1.5):
         """Whether recognize_boxes / pipeline read every box in two orientations and keep the better reading
@@ -479,11 +451,6 @@ class Context:
         mode, ratio = ctypes.c_int(0), ctypes.c_double(0)
         self._check(self._lib.kocr_get_orientation(self._h, ctypes.byref(mode), ctypes.byref(ratio)))
         return mode.value, ratio.value
-
-    def _orientation_scope(self, orientation):
-        """The switch for one call (``orientation=(mode, tall_ratio)``, mode "flip" / "any" or its code); None: the context's
-        own setting."""
-        return _option_scope(self.get_orientation, lambda new: self.set_orientation(*new), orientation)
 
     def recognition_orientation(self):
         """The resident orientation of the last recognize_boxes / pipeline (kocr_recognition_orientation): turns (M,) int32,
@@ -643,15 +610,6 @@ class Context:
         self._check(self._lib.kocr_get_char_boxes(self._h, ctypes.byref(on), ctypes.byref(p), ctypes.byref(r), ctypes.byref(e)))
         return bool(on.value), {"peak_threshold": p.value, "valley_ratio": r.value, "extent_threshold": e.value}
 
-    def _char_boxes_scope(self, char_boxes):
-        """The switch for one call (``char_boxes=True`` or a dict of rule parameters); falsy: the context's own setting."""
-        rule = char_rule(char_boxes)
-
-        def restore(old):
-            self.set_char_boxes(True, **old[1])  # the parameters, then the switch
-            self.set_char_boxes(old[0], **old[1])
-        return _option_scope(self.get_char_boxes, lambda new: self.set_char_boxes(new[0], **new[1]), rule and (True, rule), restore)
-
     def detection_char_boxes(self, counts, cap):
         """The resident character boxes (kocr_detection_char_boxes): per image a list of one ``(quads (K, 4, 2) float32,
         scores (K,) float32)`` pair per word box; ValueError when nothing is resident or the results were produced with
@@ -749,10 +707,6 @@ class Context:
         self._check(self._lib.kocr_get_beam(self._h, ctypes.byref(bw), ctypes.byref(k)))
         return bw.value, k.value
 
-    def _beam_scope(self, beam):
-        """The beam for one call (``beam=(beam_width, top_paths)``); None: the context's own setting."""
-        return _option_scope(self.get_beam, lambda new: self.set_beam(*new), None if beam is None else beam_args(*beam))
-
     def recognition_beams(self):
         """The resident beam alternatives (kocr_recognition_beams): labels (M, top_paths, label width) int32 and log_prob
         (M, top_paths) float32 as they were produced; ValueError when nothing is resident or the beam was off."""
@@ -808,12 +762,6 @@ class Context:
         self._check(self._lib.kocr_get_lexicon_match(self._h, ctypes.byref(k)))
         return k.value
 
-    def _lexicon_scope(self, top_words):
-        """The lexicon match for one call; None: the context's own setting.  A lexicon unloaded meanwhile took the switch
-        with it: then nothing is restored."""
-        return _option_scope(self.get_lexicon_match, self.set_lexicon_match, top_words,
-                             lambda old: self.lexicon_size() and self.set_lexicon_match(old))
-
     def recognition_lexicon(self):
         """The resident lexicon matches (kocr_recognition_lexicon): index (M, top_words) int32 and log_prob (M, top_words)
         float32 as they were produced; ValueError when nothing is resident or the match was off."""
@@ -844,12 +792,6 @@ class Context:
         k = ctypes.c_int(0)
         self._check(self._lib.kocr_get_charset(self._h, ctypes.byref(k)))
         return k.value
-
-    def _charset_scope(self, index):
-        """The character set for one call; None: the context's own setting.  A table unloaded meanwhile took the switch with
-        it: then nothing is restored."""
-        return _option_scope(self.get_charset, self.set_charset, None if index is None else int(index),
-                             lambda old: old < self.charset_count() and self.set_charset(old))
 
     def _set_of(self, set_of, m, what):
         """``set_of`` as (m,) int32, or ValueError naming the count"""
@@ -884,12 +826,6 @@ class Context:
         k = ctypes.c_int(0)
         self._check(self._lib.kocr_get_pattern(self._h, ctypes.byref(k)))
         return k.value
-
-    def _pattern_scope(self, index):
-        """The pattern for one call; None: the context's own setting.  Tables unloaded meanwhile took the switch with them:
-        then nothing is restored."""
-        return _option_scope(self.get_pattern, self.set_pattern, None if index is None else int(index),
-                             lambda old: old < self.pattern_count() and self.set_pattern(old))
 
     def _pattern_of(self, pattern_of, m, what):
         """``pattern_of`` as (m,) int32, or ValueError naming the count"""
@@ -1077,7 +1013,8 @@ class Context:
         on KOCR_ECAPACITY (the counts hold it): a ``Results`` of the boxes [, the resident detection scores of the call that
         succeeded] [, its resident character boxes]"""
         cap = int(cap) if cap else 1024
-        with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._char_boxes_scope(char_boxes):
+        extras = Extras(min_area_rect=min_area_rect, scores=return_scores, char_boxes=char_rule(char_boxes))
+        with self._extras_scope(extras):
             while True:
                 boxes = np.zeros((n, cap, 4, 2), dtype=np.float32)
                 counts = np.zeros(n, dtype=np.int32)
@@ -1086,12 +1023,42 @@ class Context:
                     cap = int(counts.max())
                     continue
                 self._check(rc)
-                out = Results(_box_lists(boxes, counts), None)
-                if return_scores:
-                    out.scores = (self.detection_scores(counts, cap) if n else [], None, None)
-                if char_rule(char_boxes) is not None:
-                    out.characters = self.detection_char_boxes(counts, cap) if n else []
-                return out
+                return self._fetch_extras(Results(_box_lists(boxes, counts), None), extras, n, counts, cap)
+
+    # -- the per-call extras: one scope over the switches, one fetch of what they left resident ----------------------------
+    @contextlib.contextmanager
+    def _extras_scope(self, extras):
+        """The context's switches for one call: every field of ``extras`` (an ``extras.Extras``) that asks for something sets
+        its switch, in the order of ``_SWITCHES``, and the old settings come back in reverse -- also when a later setter
+        raises.  A field that asks for nothing makes no call at all: the context's own setting holds."""
+        with contextlib.ExitStack() as stack:
+            for field, value_of, get, set_, restore in _SWITCHES:
+                value = value_of(getattr(extras, field))
+                if value is not None:
+                    old = get(self)
+                    set_(self, value)
+                    stack.callback(restore or set_, self, old)
+            yield
+
+    def _fetch_extras(self, out, extras, n, counts=None, cap=None):
+        """``out`` with what the call left resident for ``extras``, or the empty values when nothing ran (``n`` == 0: no
+        images, or no crops for a call on boxes).  ``counts`` / ``cap`` (of a call that ran the detector): the boxes per image
+        and the capacity they were produced with; scores have a recogniser part where ``out`` has labels."""
+        if extras.scores:
+            detection = None if counts is None else self.detection_scores(counts, cap) if n else []
+            recognition = (None, None) if out.labels is None else self.recognition_scores() if n else empty_scores(self.crnn_label_width())[1:]
+            out.scores = (detection, *recognition)
+        if extras.beam is not None:
+            out.beam = self.recognition_beams() if n else empty_beam(extras.beam[1], self.crnn_label_width())
+        if extras.lexicon_top is not None:
+            out.lexicon = self.recognition_lexicon() if n else empty_lexicon(extras.lexicon_top)
+        if extras.orientation is not None:
+            out.orientation = self.recognition_orientation() if n else empty_orientation()
+        if extras.patterned:
+            out.pattern = self.recognition_patterns() if n else empty_pattern(self.crnn_label_width())
+        if extras.characters:
+            out.characters = self.detection_char_boxes(counts, cap) if n else []
+        return out
 
     # -- Detector.detect, device-resident heat-maps -----------------------------------------------
     def detect(self, images, detection_threshold=0.7, text_threshold=0.4, link_threshold=0.4, size_threshold=10,
@@ -1124,55 +1091,29 @@ class Context:
         that pattern, or ``pattern_of`` (one integer per box in [-1, pattern_count()), -1 = none:
         kocr_recognize_boxes_patterns); last come pattern labels (M,48), log_path (M,), log_prob (M,) as ``crnn_pattern``.
         Not together with ``orientation`` or ``set_of`` (ValueError)."""
-        return self._recognize_boxes(images, box_groups, return_scores, beam, lexicon_top, orientation, set_of, pattern,
-                                     pattern_of).render_recognition()
+        return self._recognize_boxes(images, box_groups, Extras(
+            scores=return_scores, beam=beam, lexicon_top=lexicon_top, orientation=orientation, set_of=set_of, pattern=pattern,
+            pattern_of=pattern_of).validate()).render_recognition()
 
-    def _recognize_boxes(self, images, box_groups, return_scores=False, beam=None, lexicon_top=None, orientation=None, set_of=None,
-                         pattern=None, pattern_of=None):
-        """recognize_boxes' ``Results`` (no boxes; the detection part of its scores is None); no library call for zero boxes
-        beyond the switches"""
-        beam = None if beam is None else beam_args(*beam)
-        patterned = pattern is not None or pattern_of is not None
-        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, pattern=True if patterned else None)
-        if patterned and set_of is not None:
-            raise ValueError("pattern and set_of cannot be combined: the pattern states the characters itself")
-        if pattern is not None and pattern_of is not None:
-            raise ValueError("pattern and pattern_of cannot be combined: one pattern for every box, or one per box")
-        orientation = None if orientation is None else orientation_args(*orientation)
-        with self._lexicon_scope(lexicon_top), self._orientation_scope(orientation), self._pattern_scope(pattern):
-            with self._beam_scope(beam):
-                x = np.ascontiguousarray(images, dtype=np.uint8)
-                n, h, w, _ = x.shape
-                counts, flat = _flatten_boxes(box_groups)
-                lw = self.crnn_label_width()
-                out = Results(None, np.full((int(counts.sum()), lw), -1, dtype=np.int32))
-                m = len(out.labels)
-                sets = None if set_of is None else self._set_of(set_of, m, "box")
-                pats = None if pattern_of is None else self._pattern_of(pattern_of, m, "box")
-                with self._scores_scope(return_scores and m):
-                    if m and pats is not None:
-                        self._check(self._lib.kocr_recognize_boxes_patterns(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
-                                                                            _ptr(out.labels), 0, _ptr(pats)), value_error=True)
-                    elif m and patterned:
-                        self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
-                                                                   _ptr(out.labels), 0), value_error=True)
-                    elif m and sets is not None:
-                        self._check(self._lib.kocr_recognize_boxes_charsets(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
-                                                                            _ptr(out.labels), 0, _ptr(sets)), value_error=True)
-                    elif m:
-                        self._check(self._lib.kocr_recognize_boxes(self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts),
-                                                                   _ptr(out.labels), 0))
-                    if return_scores:
-                        out.scores = (None,) + self.recognition_scores() if m else empty_scores(lw)
-                if beam is not None:
-                    out.beam = self.recognition_beams() if m else empty_beam(beam[1], lw)
-            if lexicon_top is not None:
-                out.lexicon = self.recognition_lexicon() if m else empty_lexicon(lexicon_top)
-            if orientation is not None:
-                out.orientation = self.recognition_orientation() if m else empty_orientation()
-            if patterned:
-                out.pattern = self.recognition_patterns() if m else empty_pattern(lw)
-        return out
+    def _recognize_boxes(self, images, box_groups, extras):
+        """recognize_boxes' ``Results`` (no boxes; the detection part of its scores is None) for a validated ``extras.Extras``;
+        no library call for zero boxes beyond the switches"""
+        x = np.ascontiguousarray(images, dtype=np.uint8)
+        n, h, w, _ = x.shape
+        counts, flat = _flatten_boxes(box_groups)
+        m = int(counts.sum())
+        sets = None if extras.set_of is None else self._set_of(extras.set_of, m, "box")
+        pats = None if extras.pattern_of is None else self._pattern_of(extras.pattern_of, m, "box")
+        with self._extras_scope(extras):
+            out = Results(None, np.full((m, self.crnn_label_width()), -1, dtype=np.int32))
+            args = (self._h, _ptr(x), n, h, w, _ptr(flat), _ptr(counts), _ptr(out.labels), 0)
+            if m and pats is not None:
+                self._check(self._lib.kocr_recognize_boxes_patterns(*args, _ptr(pats)), value_error=True)
+            elif m and sets is not None and not extras.patterned:
+                self._check(self._lib.kocr_recognize_boxes_charsets(*args, _ptr(sets)), value_error=True)
+            elif m:
+                self._check(self._lib.kocr_recognize_boxes(*args), value_error=extras.patterned)
+            return self._fetch_extras(out, extras, m)
 
     # -- crops --------------------------------------------------------------------------------
     def warp_crops(self, images, box_groups, target_height=31, target_width=200):
@@ -1263,27 +1204,14 @@ class Context:
         (ValueError).  ``tiled`` (``pipeline_tiled``): ``hmax`` / ``wmax`` are the tile and the overlap of kocr_pipeline_tiled.
         ``pattern`` (an index in [0, pattern_count())): every crop is also decoded under that pattern (include/kocr.h:
         "Patterns") and its ``pattern`` comes last of all; not together with ``orientation`` (ValueError)."""
-        refuse_orientation_with(orientation, beam=beam, lexicon_top=lexicon_top, char_boxes=None if char_rule(char_boxes) is None else True,
-                                pattern=pattern)
-        orientation = None if orientation is None else orientation_args(*orientation)
-        with self._char_boxes_scope(char_boxes):
-            with self._min_area_rect_scope(min_area_rect), self._scores_scope(return_scores), self._beam_scope(beam), \
-                    self._lexicon_scope(lexicon_top), self._orientation_scope(orientation), self._pattern_scope(pattern):
-                out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
-                                     size_threshold, micro_batch, on_device, cap, max_crops, return_scores, tiled)
-                if orientation is not None:
-                    out.orientation = self.recognition_orientation() if len(ptrs) else empty_orientation()
-                if lexicon_top is not None:
-                    out.lexicon = self.recognition_lexicon() if len(ptrs) else empty_lexicon(lexicon_top)
-                elif beam is not None:
-                    out.beam = self.recognition_beams() if len(ptrs) else empty_beam(beam[1], self.crnn_label_width())
-                if pattern is not None:
-                    out.pattern = self.recognition_patterns() if len(ptrs) else empty_pattern(self.crnn_label_width())
-            if char_rule(char_boxes) is not None:
-                # the boxes' own counts and the cap they were produced with (the largest count after a capacity overflow)
-                counts = [len(b) for b in out.boxes]
-                out.characters = self.detection_char_boxes(counts, max([int(cap)] + counts)) if len(ptrs) else []
-        return out.render_context()
+        extras = Extras(char_boxes=char_rule(char_boxes), min_area_rect=min_area_rect, scores=return_scores, beam=beam,
+                        lexicon_top=lexicon_top, orientation=orientation, pattern=pattern).validate()
+        with self._extras_scope(extras):
+            out = self._pipeline(ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
+                                 size_threshold, micro_batch, on_device, cap, max_crops, tiled=tiled)
+            # the boxes' own counts and the cap they were produced with (the largest count after a capacity overflow)
+            counts = [len(b) for b in out.boxes]
+            return self._fetch_extras(out, extras, len(ptrs), counts, max([int(cap)] + counts)).render_context()
 
     def _pipeline(self, ptrs, hs, ws, dhs, dws, hmax, wmax, detection_threshold, text_threshold, link_threshold,
                   size_threshold, micro_batch, on_device, cap, max_crops, return_scores=False, tiled=False):
@@ -1314,9 +1242,7 @@ class Context:
             rc = self._lib.kocr_pipeline_results(self._h, _ptr(boxes), cap, _ptr(labels), max_crops)
         self._check(rc)
         out = Results(_box_lists(boxes, counts), labels[:int(n_crops[0])].copy())
-        if return_scores:
-            out.scores = (self.detection_scores(counts, cap),) + self.recognition_scores() if n else empty_scores(lw, [])
-        return out
+        return self._fetch_extras(out, Extras(scores=True), n, counts, cap) if return_scores else out
 
     # -- tiled pages (include/kocr.h: "tiled pages") ------------------------------------------------
     def pipeline_tiled(self, ptrs, hs, ws, dhs, dws, tile, overlap, **kwargs):
@@ -1470,10 +1396,6 @@ class Context:
     def get_min_area_rect(self):
         code = self._check(self._lib.kocr_get_min_area_rect(self._h))
         return {v: k for k, v in MIN_AREA_RECT_RULES.items()}[code]
-
-    def _min_area_rect_scope(self, rule):
-        """A per-call rule: set for the block, the context's own restored afterwards (None: the context's rule)."""
-        return _option_scope(self.get_min_area_rect, self.set_min_area_rect, rule)
 
     # -- measurement -------------------------------------------------------------------
     # -- the detector's training data and validation loss (detection.py:106-198, :696) ----------------------------------
@@ -1746,6 +1668,24 @@ class Context:
         n = self._check(self._lib.kocr_debug_check_arena_guards(self._h, ctypes.byref(arena), ctypes.byref(off), ctypes.byref(byte)))
         names = self.arena_names()
         return n, (names[arena.value] if 0 <= arena.value < len(names) else None), int(off.value), int(byte.value)
+
+
+# Context._extras_scope's switches in the order they are set: (field of extras.Extras, the field -> what the setter takes
+# (None: it asks for nothing), getter, setter, how the old setting is restored (None: the setter)).  A lexicon, character sets
+# or patterns unloaded meanwhile took their switch with them: then nothing is restored.
+_SWITCHES = (
+    ("char_boxes", lambda v: char_rule(v) and (True, char_rule(v)), Context.get_char_boxes,
+     lambda ctx, new: ctx.set_char_boxes(new[0], **new[1]),
+     lambda ctx, old: (ctx.set_char_boxes(True, **old[1]), ctx.set_char_boxes(old[0], **old[1]))),  # the parameters, then the switch
+    ("min_area_rect", lambda v: v, Context.get_min_area_rect, Context.set_min_area_rect, None),
+    ("scores", lambda v: True if v else None, Context.get_scores, Context.set_scores, None),
+    ("beam", lambda v: None if v is None else beam_args(*v), Context.get_beam, lambda ctx, new: ctx.set_beam(*new), None),
+    ("lexicon_top", lambda v: v, Context.get_lexicon_match, Context.set_lexicon_match,
+     lambda ctx, old: ctx.lexicon_size() and ctx.set_lexicon_match(old)),
+    ("orientation", lambda v: v, Context.get_orientation, lambda ctx, new: ctx.set_orientation(*new), None),
+    ("charset", lambda v: v if v is None else int(v), Context.get_charset, Context.set_charset, lambda ctx, old: old < ctx.charset_count() and ctx.set_charset(old)),
+    ("pattern", lambda v: v if v is None else int(v), Context.get_pattern, Context.set_pattern, lambda ctx, old: old < ctx.pattern_count() and ctx.set_pattern(old)),
+)
 
 
 def _detector_input(images):

@@ -1,93 +1,25 @@
 """Host-side mirror of ``keras_ocr.pipeline.Pipeline`` (reference ``keras_ocr/pipeline.py:7-75``)."""
-import contextlib
-
 import numpy as np
 
-from . import _lib, charsets as _charsets, detection, evaluation as _evaluation, layout as _layout, lexicon as _lexicon, patterns as _patterns, recognition, scores as _scores, tools
-from .results import Results
+from . import _lib, detection, evaluation as _evaluation, layout as _layout, recognition, scores as _scores, tools
+from .extras import Extras, only_uint8
+from .results import Results, decode_labels  # noqa: F401  (decode_labels: imported from here by callers)
 
 
 def beam_of(recognition_kwargs):
-    """``(beam_width, top_paths)`` from recognize()'s ``recognition_kwargs`` (validated: ValueError naming the argument), or
-    None without a ``beam_width``.  Every other key is a Keras predict argument and has no effect on results."""
-    kwargs = recognition_kwargs or {}
-    if kwargs.get("beam_width") is None:
-        return None
-    return _lib.beam_args(kwargs["beam_width"], kwargs.get("top_paths", 1))
+    """``(beam_width, top_paths)`` from recognize()'s ``recognition_kwargs``, validated (ValueError naming the argument), or None"""
+    return Extras.asked(recognition_kwargs).checked_beam()
 
 
 def lexicon_of(recognition_kwargs):
-    """``lexicon_top`` from recognize()'s ``recognition_kwargs`` (validated: ValueError naming the argument, or saying that
-    it cannot be combined with ``beam_width``), or None without one."""
-    kwargs = recognition_kwargs or {}
-    if kwargs.get("lexicon_top") is None:
-        return None
-    if kwargs.get("beam_width") is not None:
-        raise ValueError("lexicon_top and beam_width cannot be combined: ask for one of the two")
-    return _lexicon.top_arg(kwargs["lexicon_top"])
+    """``lexicon_top`` from ``recognition_kwargs``, validated (ValueError also together with ``beam_width``), or None"""
+    return Extras.asked(recognition_kwargs).checked_lexicon_top()
 
 
 def orientation_of(recognition_kwargs, char_boxes=None):
-    """``(orientation, tall_ratio)`` from recognize()'s ``recognition_kwargs`` (validated: ValueError naming the argument, or
-    naming both when it is combined with ``beam_width``, ``lexicon_top`` or character boxes), or None without an
-    ``orientation``."""
-    kwargs = recognition_kwargs or {}
-    if kwargs.get("orientation") is None:
-        return None
-    _lib.refuse_orientation_with(kwargs["orientation"], beam_width=kwargs.get("beam_width"), lexicon_top=kwargs.get("lexicon_top"),
-                                 char_boxes=char_boxes)
-    return kwargs["orientation"], _lib.orientation_args(kwargs["orientation"], kwargs.get("tall_ratio", 1.5))[1]
-
-
-def charset_scope(recognizer, recognition_kwargs):
-    """The scope in which the recogniser's context decodes under ``recognition_kwargs["charset"]`` (a name loaded with
-    ``recognizer.set_charsets``; DESIGN.md section 4, "Character sets"); no ``charset``: a scope that does nothing.
-    ValueError listing the loaded names for an unknown one; TypeError for a recogniser without character sets."""
-    name = (recognition_kwargs or {}).get("charset")
-    if name is None:
-        return contextlib.nullcontext()
-    if not hasattr(recognizer, "_charset_names") or getattr(recognizer, "_ctx", None) is None:
-        raise TypeError(f"charset: the recognizer ({type(recognizer).__name__}) has no character sets (it is not libkocr-backed)")
-    if not isinstance(name, str):
-        raise ValueError(f"charset in recognition_kwargs is one name for every box, got {name!r} (per-box sets: "
-                         "Recognizer.recognize_from_boxes)")
-    index = _charsets.index_of(recognizer._charset_names(name), name)  # pylint: disable=protected-access
-    return recognizer._ctx._charset_scope(index)  # pylint: disable=protected-access
-
-
-def pattern_of(recognizer, recognition_kwargs):
-    """The index of ``recognition_kwargs["pattern"]`` (a name loaded with ``recognizer.set_patterns``; DESIGN.md section 4,
-    "Patterns"), or None without one.  ValueError listing the loaded names for an unknown one, and when it is combined with
-    ``beam_width`` / ``lexicon_top`` (one text per word), ``charset`` or ``orientation``; TypeError for a recogniser without
-    patterns."""
-    kwargs = recognition_kwargs or {}
-    name = kwargs.get("pattern")
-    if name is None:
-        return None
-    _one_text_per_word({k: v for k, v in kwargs.items() if k != "pattern"}, "a pattern gives one reading per word")
-    for key in ("charset", "orientation"):
-        if kwargs.get(key) is not None:
-            raise ValueError(f"pattern and {key} cannot be combined: " + (
-                "the pattern states the characters itself" if key == "charset" else "ask for one of the two"))
-    if not hasattr(recognizer, "_pattern_names") or getattr(recognizer, "_ctx", None) is None:
-        raise TypeError(f"pattern: the recognizer ({type(recognizer).__name__}) has no patterns (it is not libkocr-backed)")
-    if not isinstance(name, str):
-        raise ValueError(f"pattern in recognition_kwargs is one name for every box, got {name!r} (per-box patterns: "
-                         "Recognizer.recognize_from_boxes)")
-    return _patterns.index_of(recognizer._pattern_names(name), name)  # pylint: disable=protected-access
-
-
-def _one_text_per_word(recognition_kwargs, why):
-    """ValueError for ``beam_width`` / ``lexicon_top`` / ``pattern``: the caller needs every ``text`` to be one string"""
-    for key in ("beam_width", "lexicon_top"):
-        if (recognition_kwargs or {}).get(key) is not None:
-            raise ValueError(f"{why}: {key} in recognition_kwargs makes every text a list of alternatives")
-    if (recognition_kwargs or {}).get("pattern") is not None:
-        raise ValueError(f"{why}: pattern in recognition_kwargs makes every text a (text, log_prob) pair")
-
-
-def _wants_characters(char_boxes):
-    return char_boxes is not None and char_boxes is not False
+    """``(orientation, tall_ratio)`` from ``recognition_kwargs``, validated (ValueError naming the argument, or naming both
+    when it is combined with ``beam_width``, ``lexicon_top`` or character boxes), or None"""
+    return Extras.asked(recognition_kwargs, char_boxes=char_boxes).checked_orientation()
 
 
 def label_width_of(recognizer):
@@ -98,28 +30,6 @@ def label_width_of(recognizer):
         return int(ctx.crnn_label_width())
     width = getattr(recognizer, "label_width", None)
     return None if width is None else int(width)
-
-
-def decode_labels(alphabet, labels):
-    """Label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding (recognition.py:527-534).
-
-    One table lookup and one UTF-32 decode for the whole batch: iterating 600 x 48 numpy scalars costs 4 ms
-    per call, during which the GPU sits idle."""
-    labels = np.asarray(labels)
-    if labels.size == 0:
-        return [""] * len(labels)
-    n = len(alphabet)
-    if (labels.ndim != 2 or any(len(c) != 1 or c == "\0" or 0xD800 <= ord(c) <= 0xDFFF for c in alphabet)
-            or labels.min() < -1 or labels.max() > n):
-        # multi-character entries, lone surrogates (no UTF-32 encoding), a single row, or indices the reference's own
-        # expression would wrap / reject: evaluate that expression
-        skip = (n, -1)
-        rows = labels.tolist() if labels.ndim == 2 else [labels.tolist()] if labels.ndim == 1 else labels.reshape(-1, labels.shape[-1]).tolist()
-        return ["".join([alphabet[i] for i in row if i not in skip]) for row in rows]
-    table = np.array([ord(c) for c in alphabet] + [0], "<u4")
-    text = table[np.where(labels < 0, n, labels)].tobytes().decode("utf-32-le")
-    w = labels.shape[1]
-    return [text[i * w:(i + 1) * w].replace("\0", "") for i in range(labels.shape[0])]
 
 
 class Pipeline:
@@ -193,7 +103,7 @@ class Pipeline:
         ``(predictions, results, (precision, recall))``: ``predictions`` is what recognize() returns, ``results`` and the two
         numbers what ``evaluation.score({i: true[i]}, {i: [{"text", "vertices"} per word]})`` returns, the image ids being
         the positions in ``images``.  ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list."""
-        _one_text_per_word(recognition_kwargs, "evaluate scores one text per word")
+        Extras.asked(recognition_kwargs).one_text_per_word("evaluate scores one text per word")
         true = list(true)
         predictions = self.recognize(images, detection_kwargs, recognition_kwargs)
         if len(true) != len(predictions):
@@ -211,7 +121,7 @@ class Pipeline:
         ``rule``: ``max_angle``, ``min_height_ratio``, ``max_offset``, ``max_gap`` as ``layout.group_lines``.
         ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list.  Columns are not detected:
         ``recognize_blocks`` reads a page column after column."""
-        _one_text_per_word(recognition_kwargs, "recognize_lines joins one text per word")
+        Extras.asked(recognition_kwargs).one_text_per_word("recognize_lines joins one text per word")
         predictions = self.recognize(images, detection_kwargs, recognition_kwargs)
         ctx = getattr(self.detector, "_ctx", None)
         pages = _layout.group_lines([[box for _, box in group] for group in predictions], ctx=ctx, **rule)
@@ -252,7 +162,7 @@ class Pipeline:
         ``min_gap_y``, ``min_support`` as ``layout.group_table`` (judgement, not fitted to real pages).  It refuses what
         recognize_blocks() refuses: ``beam_width`` / ``lexicon_top`` / ``pattern`` (ValueError), their ``text`` is no
         string."""
-        _one_text_per_word(recognition_kwargs, "recognize_table joins one text per word")
+        Extras.asked(recognition_kwargs).one_text_per_word("recognize_table joins one text per word")
         unknown = set(rule) - {"min_gap_x", "min_gap_y", "min_support"}
         if unknown:
             raise TypeError(f"recognize_table: unknown rule parameter(s) {sorted(unknown)}")
@@ -273,7 +183,7 @@ class Pipeline:
         the caller checks that.  ``rule``: ``peak_threshold``, ``valley_ratio``, ``extent_threshold`` as
         ``detection.get_char_boxes``.  ``beam_width`` / ``lexicon_top`` are refused (ValueError): their ``text`` is a list.
         A method of its own because recognize() keeps the reference's exact signature."""
-        _one_text_per_word(recognition_kwargs, "recognize_characters pairs one text per word with its characters")
+        Extras.asked(recognition_kwargs).one_text_per_word("recognize_characters pairs one text per word with its characters")
         orientation_of(recognition_kwargs, char_boxes=True)  # ValueError naming both
         unknown = set(rule) - set(_lib.CHAR_RULE_DEFAULTS)
         if unknown:
@@ -301,83 +211,69 @@ class Pipeline:
     def _recognize(self, images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores=False, char_boxes=None):
         """recognize_raw's ``Results``, over one of three routes: the fused one, and the stage-wise one for images that are
         not uint8 or for foreign stages.  ``recognition_kwargs={"charset": name}``: every decode of the call runs under that
-        character set of the recogniser (``charset_scope``); the boxes are the same either way."""
-        pattern_of(self.recognizer, recognition_kwargs)  # its refusals come first
-        with charset_scope(self.recognizer, recognition_kwargs):
-            return self._recognize_routes(images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
+        character set of the recogniser (``Extras.charset_scope``); the boxes are the same either way."""
+        extras = Extras.from_recognition_kwargs(self.recognizer, recognition_kwargs, return_scores, char_boxes)
+        with extras.charset_scope(getattr(self.recognizer, "_ctx", None)):
+            return self._recognize_routes(images, hmax, wmax, detection_kwargs, extras, (recognition_kwargs or {}).get("pattern"))
 
-    def _recognize_routes(self, images, hmax, wmax, detection_kwargs, recognition_kwargs, return_scores, char_boxes):
+    def _recognize_routes(self, images, hmax, wmax, detection_kwargs, extras, pattern_name):
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
-        lexicon_top = lexicon_of(recognition_kwargs)
-        beam = beam_of(recognition_kwargs)  # the rest: Keras predict kwargs, no effect on results
-        want_characters = _wants_characters(char_boxes)
-        orientation = orientation_of(recognition_kwargs, char_boxes if want_characters else None)
-        pattern = pattern_of(self.recognizer, recognition_kwargs)
-        if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
-            raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         if not images:
-            return Results.empty(return_scores, beam, lexicon_top, want_characters, orientation=orientation is not None,
-                                 pattern=pattern is not None, label_width=label_width_of(self.recognizer))
+            return extras.empty_results(label_width_of(self.recognizer))
         detection_kwargs = dict(detection_kwargs or {})
-        if want_characters:
-            detection_kwargs["char_boxes"] = char_boxes
+        if extras.characters:
+            detection_kwargs["char_boxes"] = extras.char_boxes
         ctx = getattr(self.detector, "_ctx", None)
         floats = any(im.dtype != np.uint8 for im in images)
-        if floats and orientation is not None:
-            raise NotImplementedError("orientation: only uint8 images are read in two orientations (the float crop path has no "
-                                      "turned set-up)")
-        if floats and pattern is not None:
-            raise NotImplementedError("pattern: patterns need uint8 images (the float crop path decodes plain crops)")
+        for feature in ("orientation", "pattern"):
+            if getattr(extras, feature) is not None:
+                only_uint8(images, feature)
         if floats or ctx is None or getattr(self.recognizer, "_ctx", None) is not ctx:
             # float (or any non-uint8) images: the reference's cv2 calls interpolate them in float (tools.py:394, :107); the
             # stage-wise path does the same with the float kernels (kocr_resize_pad_f32 / kocr_warp_crops_f32, round 5) -- off
             # the fused fixed-point path, which is defined for uint8 pixels only.  Duck-typed / separately-placed stages: the
             # reference's stage-wise path (pipeline.py:44-75)
-            if want_characters and "char_boxes" not in _scores.parameters(self.detector.detect):
+            if extras.characters and "char_boxes" not in _scores.parameters(self.detector.detect):
                 raise TypeError(f"char_boxes: the detector ({type(self.detector).__name__}.detect) cannot give character boxes "
                                 "(it takes no char_boxes argument)")
             out, scales = self._recognize_stagewise([im.astype(np.float32) for im in images] if floats else images, detection_kwargs,
-                                                    hmax, wmax, return_scores, beam, lexicon_top, orientation,
-                                                    (recognition_kwargs or {}).get("pattern"))
+                                                    hmax, wmax, extras, pattern_name)
         else:
             scales, dhs, dws, hmax_, wmax_ = self._plan([im.shape for im in images])
             hmax = hmax_ if hmax is None else max(hmax, hmax_)
             wmax = wmax_ if wmax is None else max(wmax, wmax_)
-            out = self._fused(ctx.pipeline, images, dhs, dws, (hmax, wmax), detection_kwargs, return_scores, beam, lexicon_top,
-                              want_characters, orientation, pattern)
-        return self._to_input_pixels(out, scales, orientation, want_characters)
+            out = self._fused(ctx.pipeline, images, dhs, dws, (hmax, wmax), detection_kwargs, extras)
+        return self._to_input_pixels(out, scales, extras)
 
     @staticmethod
-    def _fused(call, images, dhs, dws, sizes, detection_kwargs, return_scores, beam, lexicon_top, want_characters, orientation,
-               pattern=None):
+    def _fused(call, images, dhs, dws, sizes, detection_kwargs, extras):
         """One fused call (``Context.pipeline`` with ``sizes`` = (hmax, wmax), ``Context.pipeline_tiled`` with (tile, overlap))
         on uint8 images -> its ``Results``, boxes and characters in detector-input pixels"""
         micro_batch = detection_kwargs.pop("batch_size", 0) or 0
         out = Results.parse_context(call(
             images, [im.shape[0] for im in images], [im.shape[1] for im in images], dhs, dws, *sizes,
-            micro_batch=micro_batch, return_scores=return_scores, beam=beam, lexicon_top=lexicon_top,
-            **({} if orientation is None else {"orientation": orientation}), **({} if pattern is None else {"pattern": pattern}),
-            **detection_kwargs),
-            return_scores, beam is not None, lexicon_top is not None, want_characters, orientation is not None, pattern is not None)
-        if want_characters:
+            micro_batch=micro_batch, return_scores=extras.scores, beam=extras.beam, lexicon_top=extras.lexicon_top,
+            **({} if extras.orientation is None else {"orientation": extras.orientation}),
+            **({} if extras.pattern is None else {"pattern": extras.pattern}), **detection_kwargs), *extras.flags())
+        if extras.characters:
             out.characters = _layout.characters_of(out.characters)
         return out
 
-    def _to_input_pixels(self, out, scales, orientation, want_characters):
+    def _to_input_pixels(self, out, scales, extras):
         """``Results`` in detector-input pixels -> the same in input-image pixels (pipeline.py:66-71), an oriented run's boxes
         replaced by its quads"""
-        if orientation is not None:
+        if extras.orientation is not None:
             # every word's box becomes its oriented quad: the same corners, renamed
             turns, quads, log_words = out.orientation
             ends = np.cumsum([len(b) for b in out.boxes])
             out.boxes = [quads[end - len(b):end] if len(b) else b for b, end in zip(out.boxes, ends)]
         out.boxes = self._adjust(out.boxes, scales)
-        if orientation is not None:
+        if extras.orientation is not None:
             filled = [b for b in out.boxes if len(b)]
             out.orientation = (turns, np.concatenate(filled) if filled else quads, log_words)
-        if want_characters:
+        if extras.characters:
             out.characters = [[_layout.Characters(self._adjust([c.boxes], [scale])[0], c.scores) for c in page]
                               for page, scale in zip(out.characters, scales)]
         return out
@@ -395,49 +291,36 @@ class Pipeline:
         ``orientation`` / ``tall_ratio`` and ``charset`` as recognize() does, with the same refusals.  uint8 images only
         (NotImplementedError); detector and recogniser must share one ``Context`` (TypeError).  A halo narrower than the
         detector's receptive field does not reproduce a whole-page pass exactly: see DESIGN.md."""
-        pattern_of(self.recognizer, recognition_kwargs)  # its refusals come first
-        with charset_scope(self.recognizer, recognition_kwargs):
-            return self._recognize_tiled(images, tile, overlap, scale, detection_kwargs, recognition_kwargs, return_scores, char_boxes)
+        extras = Extras.from_recognition_kwargs(self.recognizer, recognition_kwargs, return_scores, char_boxes, tiled=True)
+        with extras.charset_scope(getattr(self.recognizer, "_ctx", None)):
+            return self._recognize_tiled(images, tile, overlap, scale, detection_kwargs, extras)
 
-    def _recognize_tiled(self, images, tile, overlap, scale, detection_kwargs, recognition_kwargs, return_scores, char_boxes):
+    def _recognize_tiled(self, images, tile, overlap, scale, detection_kwargs, extras):
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
-        lexicon_top = lexicon_of(recognition_kwargs)
-        beam = beam_of(recognition_kwargs)
-        want_characters = _wants_characters(char_boxes)
-        if want_characters:
-            _one_text_per_word(recognition_kwargs, "character boxes pair one text per word with its characters")
-            if return_scores:
-                raise ValueError("return_scores and char_boxes cannot be combined: ask for one of the two")
-        orientation = orientation_of(recognition_kwargs, char_boxes if want_characters else None)
-        pattern = pattern_of(self.recognizer, recognition_kwargs)
-        if lexicon_top is not None and getattr(self.recognizer, "lexicon", None) is None:
-            raise ValueError("lexicon_top needs a loaded lexicon: call recognizer.set_lexicon(words) first")
         ctx = getattr(self.detector, "_ctx", None)
         if ctx is None or not hasattr(ctx, "pipeline_tiled"):
             raise TypeError(f"recognize_tiled: the detector ({type(self.detector).__name__}) has no libkocr context to run tiles on")
         if getattr(self.recognizer, "_ctx", None) is not ctx:
             raise TypeError(f"recognize_tiled: the recognizer ({type(self.recognizer).__name__}) is not on the detector's context")
-        if any(im.dtype != np.uint8 for im in images):
-            raise NotImplementedError("recognize_tiled: only uint8 images are read in tiles (the tile copy moves RGB bytes)")
+        only_uint8(images, "recognize_tiled")
         tools.tile_plan(1, 1, tile, overlap)  # ValueError for a refused tile or overlap, pages or not
         scale = self.scale if scale is None else scale
         pages = []
         for im in images:
             kwargs = dict(detection_kwargs or {})
-            if want_characters:
-                kwargs["char_boxes"] = char_boxes
+            if extras.characters:
+                kwargs["char_boxes"] = extras.char_boxes
             out = self._fused(ctx.pipeline_tiled, [im], [int(im.shape[0] * scale)], [int(im.shape[1] * scale)], (tile, overlap), kwargs,
-                              return_scores, beam, lexicon_top, want_characters, orientation, pattern)
-            out = self._to_input_pixels(out, [scale], orientation, want_characters)
+                              extras)
+            out = self._to_input_pixels(out, [scale], extras)
             words = self._assemble(out)[0]
-            pages.append([(text, box, characters) for (text, box), characters in zip(words, out.characters[0])] if want_characters
+            pages.append([(text, box, characters) for (text, box), characters in zip(words, out.characters[0])] if extras.characters
                          else words)
         return pages
 
-    def _recognize_stagewise(self, images, detection_kwargs, hmax=None, wmax=None, return_scores=False, beam=None, lexicon_top=None,
-                             orientation=None, pattern=None):
+    def _recognize_stagewise(self, images, detection_kwargs, hmax, wmax, extras, pattern=None):
         """pipeline.py:44-75 with the public stage APIs only (any object with ``detect`` /
         ``recognize_from_boxes``); strings are mapped back to label rows through the recognizer's alphabet.
         ``hmax`` / ``wmax``: padded size imposed by the caller (a sharded batch pads to the WHOLE batch's size).
@@ -445,7 +328,8 @@ class Pipeline:
         boxes and characters still in detector-input pixels, and the scale of every page.
         The label rows, and the character-score, beam and pattern rows beside them, have the recogniser's label width
         (``label_width_of``), as the fused route's; a text longer than that is a ValueError.  A duck-typed recogniser that
-        reports no width keeps ``max(48, longest text)`` columns."""
+        reports no width keeps ``max(48, longest text)`` columns.  ``pattern``: the name ``extras.pattern`` was resolved from."""
+        return_scores, beam, lexicon_top, orientation = extras.scores, extras.beam, extras.lexicon_top, extras.orientation
         own = getattr(self.detector, "_ctx", None)  # a libkocr-backed detector: its context also resizes (else the default one)
         resized = [tools.resize_image(image, max_scale=self.scale, max_size=self.max_size, **({"ctx": own} if own is not None else {}))
                    for image in images]
@@ -453,7 +337,7 @@ class Pipeline:
         max_height = max(int(max_height), int(hmax or 0))
         max_width = max(int(max_width), int(wmax or 0))
         padded = np.array([tools.pad(image, width=max_width, height=max_height) for image, _ in resized])
-        with_characters = _wants_characters(detection_kwargs.get("char_boxes"))
+        with_characters = extras.characters
         turned = {}
         if orientation is not None:
             # passed on only to a recogniser that takes the two arguments
@@ -541,8 +425,7 @@ class Pipeline:
         if not isinstance(images, np.ndarray):
             images = [tools.read(image) for image in images]
         images = [np.ascontiguousarray(im) for im in images]
-        if any(im.dtype != np.uint8 for im in images):
-            raise NotImplementedError("windowed reading: only uint8 images are read in windows (the float crop path has no window plan)")
+        only_uint8(images, "windowed")
         if not images:
             return []
         own = getattr(self.detector, "_ctx", None)
@@ -607,26 +490,8 @@ class Pipeline:
 
     def _assemble(self, results):
         # recognition.py:527-534: label rows -> strings, skipping the blank (= len(alphabet)) and the -1 padding
-        if results.pattern is not None:
-            texts = decode_labels(self.recognizer.alphabet, results.pattern[0])
-            predictions = [(text, float(v)) if v != -np.inf else (None, -np.inf) for text, v in zip(texts, np.asarray(results.pattern[2]))]
-        elif results.lexicon is not None:
-            words = self.recognizer.lexicon.words
-            predictions = [[(words[i], float(v)) for i, v in zip(row, vals) if i >= 0]
-                           for row, vals in zip(np.asarray(results.lexicon[0]).tolist(), np.asarray(results.lexicon[1]))]
-        elif results.beam is not None:
-            beam_labels, beam_log_prob = np.asarray(results.beam[0]), np.asarray(results.beam[1])
-            m, k = beam_log_prob.shape
-            texts = decode_labels(self.recognizer.alphabet, beam_labels.reshape(m * k, -1)) if m * k else []
-            predictions = [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
-                           for i in range(m)]
-        else:
-            predictions = decode_labels(self.recognizer.alphabet, results.labels)
-        columns = []
-        if results.scores is not None:
-            det, log_word, chars = results.scores
-            flat = np.concatenate([np.asarray(d, np.float32).reshape(-1) for d in det]) if len(det) else np.zeros(0, np.float32)
-            columns.append(_scores.assemble(results.labels, log_word, chars, flat))
+        predictions, scores = results.words(self.recognizer.alphabet, getattr(self.recognizer, "lexicon", None))
+        columns = [] if scores is None else [scores]
         out, start = [], 0
         for boxes in results.boxes:
             out.append(list(zip(predictions[start:start + len(boxes)], boxes, *[c[start:start + len(boxes)] for c in columns])))

@@ -1,13 +1,14 @@
 """Host-side mirror of ``keras_ocr.recognition.Recognizer`` (reference
 ``keras_ocr/recognition.py:353-545``).  The Keras models are replaced by libkocr."""
-import contextlib
+import dataclasses
 import string
 import typing
 
 import numpy as np
 
 from . import _lib, charsets as _charsets, layout as _layout, lexicon as _lexicon, patterns as _patterns, scores as _scores, tools, weights as _weights
-from .results import Results
+from .extras import Extras, only_uint8
+from .results import Results, decode_labels
 
 DEFAULT_BUILD_PARAMS = {  # recognition.py:13-23
     "height": 31,
@@ -303,25 +304,14 @@ class Recognizer:
         self._ctx.set_patterns(*pats.tables())
         self.patterns = pats
 
-    def _pattern_names(self, pattern, **others):
-        """The loaded names for a ``pattern=`` argument (None when none is asked for); ValueError without loaded patterns, and
-        naming both when it is combined with one of ``others`` (name=value; None counts as not asked for)"""
+    def _pattern_names(self, pattern):
+        """The loaded names for a ``pattern=`` argument (None when none is asked for); ValueError without loaded patterns"""
         if pattern is None:
             return None
-        for name, value in others.items():
-            if value is not None:
-                raise ValueError(f"pattern and {name} cannot be combined: " + (
-                    "the pattern states the characters itself" if name == "charset" else "ask for one of the two"))
         if self.patterns is None or self._ctx.pattern_count() != len(self.patterns):
             raise ValueError("pattern needs loaded patterns: call Recognizer.set_patterns({name: regex}) first (the patterns are "
                              "unloaded when a recogniser of another class count is loaded on their context)")
         return self.patterns.names
-
-    def _readings(self, labels, log_path, log_prob):
-        """Pattern rows -> per word ``(text, log_prob)``, ``(None, -inf)`` where nothing fits (or the box has no pattern)"""
-        del log_path
-        texts = self._decode(labels)
-        return [(text, float(v)) if v != -np.inf else (None, -np.inf) for text, v in zip(texts, np.asarray(log_prob))]
 
     def set_charsets(self, charsets, lowercase=False):
         """The character sets for ``charset=`` ("Character sets"): a mapping name -> characters, e.g.
@@ -345,10 +335,6 @@ class Recognizer:
                              "sets are unloaded when a recogniser of another class count is loaded on their context)")
         return self.charsets
 
-    def _charset_scope(self, index):
-        """The context's character-set switch for one call (None: no call at all on the context)"""
-        return contextlib.nullcontext() if index is None else self._ctx._charset_scope(index)  # pylint: disable=protected-access
-
     def set_lexicon(self, words, lowercase=False):
         """The word list for ``lexicon_top=`` ("Lexicon"): an iterable of strings or a
         ``lexicon.Lexicon`` built with this recogniser's alphabet; it is loaded into the context once and stays there like
@@ -367,25 +353,6 @@ class Recognizer:
         self._ctx.set_lexicon(lex.labels, lex.lengths)
         self.lexicon = lex
 
-    def _lexicon_top(self, lexicon_top, beam_width):
-        """``lexicon_top`` validated (None stays None): ValueError naming the argument, without a loaded lexicon, or together
-        with ``beam_width``."""
-        if lexicon_top is None:
-            return None
-        if beam_width is not None:
-            raise ValueError("lexicon_top and beam_width cannot be combined: ask for one of the two")
-        k = _lexicon.top_arg(lexicon_top)
-        if self.lexicon is None or self._ctx.lexicon_size() != len(self.lexicon):
-            raise ValueError("lexicon_top needs a loaded lexicon: call Recognizer.set_lexicon(words) first (a lexicon is "
-                             "unloaded when a recogniser of another class count is loaded on its context)")
-        return k
-
-    def _matches(self, index, log_prob):
-        """Lexicon rows (M, K) / (M, K) -> per word a list of up to K ``(word, log_prob)``, best first; the entries that do
-        not exist (-1, -inf) are dropped.  The words come from ``self.lexicon.words``, not through the label rows."""
-        words = self.lexicon.words
-        return [[(words[i], float(v)) for i, v in zip(row, vals) if i >= 0] for row, vals in zip(np.asarray(index).tolist(), np.asarray(log_prob))]
-
     def get_batch_generator(self, image_generator, batch_size=8, lowercase=False):
         """Recognizer.get_batch_generator (recognition.py:406-465): batches for training_model.predict; see
         batch_generator."""
@@ -397,17 +364,7 @@ class Recognizer:
         raise NotImplementedError(_INFERENCE_ONLY)
 
     def _decode(self, rows):
-        from .pipeline import decode_labels
         return decode_labels(self.alphabet, rows)
-
-    def _alternatives(self, beam_labels, beam_log_prob):
-        """Beam rows (M, K, width) / (M, K) -> per word a list of up to K ``(text, log_prob)``, best first; the rows that do
-        not exist (all -1, -inf) are dropped."""
-        beam_labels, beam_log_prob = np.asarray(beam_labels), np.asarray(beam_log_prob)
-        m, k = beam_log_prob.shape
-        texts = self._decode(beam_labels.reshape(m * k, -1)) if m * k else []
-        return [[(texts[i * k + j], float(beam_log_prob[i, j])) for j in range(k) if beam_log_prob[i, j] != -np.inf]
-                for i in range(m)]
 
     def recognize(self, image, return_scores=False, beam_width=None, top_paths=1, lexicon_top=None, charset=None, pattern=None):
         """Recognizer.recognize (recognition.py:467-489): one pre-cropped RGB image -> string; ``return_scores=True``:
@@ -430,10 +387,7 @@ class Recognizer:
         reading of the crop that the regular expression accepts and its exact CTC log-probability (DESIGN.md section 4,
         "Patterns"); ``(None, -inf)`` when no accepted text fits the crop's frames.  Not together with ``beam_width``,
         ``lexicon_top`` or ``charset`` (ValueError)."""
-        pattern = _patterns.index_of(self._pattern_names(pattern, beam_width=beam_width, lexicon_top=lexicon_top, charset=charset), pattern)
-        lexicon_top = self._lexicon_top(lexicon_top, beam_width)
-        beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
-        charset = _charsets.index_of(self._charset_names(charset), charset)
+        extras = Extras.from_arguments(self, return_scores, beam_width, top_paths, lexicon_top, charset=charset, pattern=pattern)
         image = tools.read_and_fit(filepath_or_array=image, width=200, height=31, cval=0)
         if image.shape[-1] == 3:
             # gray conversion on the GPU: warp the full 31x200 rectangle onto itself (identity map)
@@ -441,24 +395,24 @@ class Recognizer:
             crops = self._ctx.warp_crops(image[np.newaxis], [box[np.newaxis]], 31, 200)
         else:
             crops = image[np.newaxis, ..., 0].astype("float32") / 255
-        with self._charset_scope(charset):
-            return self._words(self._recognize_crops(crops, return_scores, beam, lexicon_top, pattern))[0]
+        with extras.charset_scope(self._ctx):
+            return self._words(self._recognize_crops(crops, extras))[0]
 
-    def _recognize_crops(self, crops, return_scores, beam, lexicon_top, pattern=None):
+    def _recognize_crops(self, crops, extras):
         """The ``Results`` of crops on the host: the decode [with its scores], and the alternatives or matches asked for;
-        ``pattern``: the index every crop is decoded under"""
+        ``extras.pattern``: the index every crop is decoded under"""
         out = Results(None, None)
-        if pattern is not None:
-            out.pattern = self._ctx.crnn_pattern(crops, np.full(len(crops), pattern, np.int32))
+        if extras.pattern is not None:
+            out.pattern = self._ctx.crnn_pattern(crops, np.full(len(crops), extras.pattern, np.int32))
             out.labels = out.pattern[0]
-        if return_scores:
+        if extras.scores:
             out.labels, *scores = self._ctx.crnn_forward_scores(crops)
             out.scores = (None, *scores)
-        if beam is not None:
-            out.beam = self._ctx.crnn_beam(crops, *beam)
-        elif lexicon_top is not None:
-            out.lexicon = self._ctx.crnn_lexicon(crops, lexicon_top)
-        elif not return_scores and pattern is None:
+        if extras.beam is not None:
+            out.beam = self._ctx.crnn_beam(crops, *extras.beam)
+        elif extras.lexicon_top is not None:
+            out.lexicon = self._ctx.crnn_lexicon(crops, extras.lexicon_top)
+        elif not extras.scores and extras.pattern is None:
             out.labels = self._ctx.crnn_forward(crops)
         return out
 
@@ -488,41 +442,29 @@ class Recognizer:
         where nothing fits or the box has no pattern.  Not together with ``beam_width``, ``lexicon_top``, ``charset`` or
         ``orientation`` (ValueError); uint8 images only (NotImplementedError)."""
         del kwargs  # Keras predict kwargs (batch_size, verbose, ...) have no effect on results
-        names = self._pattern_names(pattern, beam_width=beam_width, lexicon_top=lexicon_top, charset=charset, orientation=orientation)
-        pattern = _patterns.per_box(names, pattern, box_groups)
-        uniform_set, set_of = _charsets.per_box(self._charset_names(charset), charset, box_groups)
-        with self._charset_scope(uniform_set):
-            return self._recognize_from_boxes(images, box_groups, return_scores, beam_width, top_paths, lexicon_top, orientation,
-                                              tall_ratio, return_orientation, set_of, pattern)
+        extras = Extras.from_arguments(self, return_scores, beam_width, top_paths, lexicon_top, orientation, tall_ratio, return_orientation,
+                                       charset, pattern, box_groups)
+        with extras.charset_scope(self._ctx):
+            return self._recognize_from_boxes(images, box_groups, dataclasses.replace(extras, charset=None))
 
-    def _recognize_from_boxes(self, images, box_groups, return_scores, beam_width, top_paths, lexicon_top, orientation, tall_ratio,
-                              return_orientation, set_of, pattern=(None, None)):
-        """recognize_from_boxes under the context's character-set switch; set_of: the flat per-box set indices, or None;
-        pattern: (the index for every box or None, the flat per-box pattern indices or None)"""
-        pattern, pattern_of = pattern
-        patterned = pattern is not None or pattern_of is not None
-        lexicon_top = self._lexicon_top(lexicon_top, beam_width)
-        beam = None if beam_width is None else _lib.beam_args(beam_width, top_paths)
-        _lib.refuse_orientation_with(orientation, beam_width=beam_width, lexicon_top=lexicon_top)
-        if return_orientation and orientation is None:
-            raise ValueError("return_orientation=True needs orientation='flip' or 'any'")
-        oriented = None if orientation is None else (orientation, _lib.orientation_args(orientation, tall_ratio)[1])
+    def _recognize_from_boxes(self, images, box_groups, extras):
+        """recognize_from_boxes under the context's character-set switch"""
         assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
         images = [tools.read(image) for image in images]
-        if oriented and any(np.asarray(image).dtype != np.uint8 for image in images):
-            raise NotImplementedError("orientation: only uint8 images are read in two orientations (the float crop path has no "
-                                      "turned set-up)")
+        if extras.orientation is not None:
+            only_uint8(images, "orientation")
         if not sum(len(b) for b in box_groups):
-            return [[] for _ in images] if return_scores or beam or lexicon_top or return_orientation or patterned else [[]] * len(images)
+            asked = extras.scores or extras.beam or extras.lexicon_top or extras.return_orientation or extras.patterned
+            return [[] for _ in images] if asked else [[]] * len(images)
         start_end: typing.List[typing.Tuple[int, int]] = []
         for boxes in box_groups:
             start = 0 if not start_end else start_end[-1][1]
             start_end.append((start, start + len(boxes)))
         images = [np.asarray(image) for image in images]
-        if set_of is not None and any(im.dtype != np.uint8 for im in images):
-            raise NotImplementedError("charset: per-box character sets need uint8 images (the float crop path decodes plain crops)")
-        if patterned and any(im.dtype != np.uint8 for im in images):
-            raise NotImplementedError("pattern: patterns need uint8 images (the float crop path decodes plain crops)")
+        if extras.set_of is not None:
+            only_uint8(images, "charset")
+        if extras.patterned:
+            only_uint8(images, "pattern")
         if any(im.dtype != np.uint8 for im in images):
             # float images (recognition.py:507-526 works in the image's own type): gray conversion and the crop warp in
             # float ON THE GPU (kocr_warp_crops_f32, round 5), the division by 255 of :524, the recogniser
@@ -531,21 +473,20 @@ class Recognizer:
                 if len(boxes):
                     im = np.asarray(image, np.float32)
                     crops.append(self._ctx.warp_crops_f32((im if im.ndim == 3 else im[..., np.newaxis])[np.newaxis], [boxes], 31, 200))
-            out = self._recognize_crops(np.concatenate(crops) / np.float32(255), return_scores, beam, lexicon_top)
+            out = self._recognize_crops(np.concatenate(crops) / np.float32(255), extras)
         elif len({im.shape for im in images}) == 1:
             # one size (what Pipeline / Detector hand over): crops never leave HBM
-            out = self._ctx._recognize_boxes(np.stack(images), box_groups, return_scores, beam, lexicon_top, oriented, set_of,  # pylint: disable=protected-access
-                                             pattern, pattern_of)
+            out = self._ctx._recognize_boxes(np.stack(images), box_groups, extras)  # pylint: disable=protected-access
         else:
             # the reference loops per image, so sizes may differ: one call per image
-            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], return_scores, beam, lexicon_top, oriented,  # pylint: disable=protected-access
-                                                                  None if set_of is None else set_of[start:end], pattern,
-                                                                  None if pattern_of is None else pattern_of[start:end])
-                                       for image, boxes, (start, end) in zip(images, box_groups, start_end) if len(boxes)])
+            out = Results.concatenate([self._ctx._recognize_boxes(image[np.newaxis], [boxes], dataclasses.replace(  # pylint: disable=protected-access
+                extras, set_of=None if extras.set_of is None else extras.set_of[start:end],
+                pattern_of=None if extras.pattern_of is None else extras.pattern_of[start:end]))
+                for image, boxes, (start, end) in zip(images, box_groups, start_end) if len(boxes)])
         words = self._words(out)
-        if return_orientation:
+        if extras.return_orientation:
             how = _layout.orientations_of(*out.orientation)
-            words = [(*word, o) if return_scores else (word, o) for word, o in zip(words, how)]
+            words = [(*word, o) if extras.scores else (word, o) for word, o in zip(words, how)]
         return [words[start:end] for start, end in start_end]
 
     def recognize_from_boxes_windowed(self, images, box_groups, aspect=10.0, overlap=40, return_scores=False, return_windows=False):
@@ -560,8 +501,7 @@ class Recognizer:
         assert len(box_groups) == len(images), "You must provide the same number of box groups as images."
         tools.window_args(aspect, overlap, 50 - self._ctx.crnn_label_width())
         images = [np.asarray(tools.read(image)) for image in images]
-        if any(im.dtype != np.uint8 for im in images):
-            raise NotImplementedError("windowed reading: only uint8 images are read in windows (the float crop path has no window plan)")
+        only_uint8(images, "windowed")
         runs = []  # one call for images of one size, else one per image (as recognize_from_boxes)
         if len({im.shape for im in images}) == 1:
             runs.append(self._ctx.recognize_boxes_windowed(np.stack(images), box_groups, aspect, overlap))
@@ -583,10 +523,5 @@ class Recognizer:
     def _words(self, out):
         """A ``Results``' crops as what recognize_from_boxes returns for each: the text, or its alternatives (``beam``), or
         its matches (``lexicon``) [paired with the ``Score`` of the greedy decode]"""
-        if out.pattern is not None:
-            words = self._readings(*out.pattern)
-        elif out.beam is not None:
-            words = self._alternatives(*out.beam)
-        else:
-            words = self._decode(out.labels) if out.lexicon is None else self._matches(*out.lexicon)
-        return words if out.scores is None else list(zip(words, _scores.assemble(out.labels, *out.scores[1:])))
+        words, scores = out.words(self.alphabet, self.lexicon)
+        return words if scores is None else list(zip(words, scores))

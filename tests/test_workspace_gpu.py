@@ -15,7 +15,6 @@ tests/workspace_cases.py runs here on contexts of this module's own:
 Integers and floats are compared as bit patterns; there is no tolerance in this file.  ``pytest -s`` prints, per row and
 arena, peak / requested, and the last test prints the largest of each arena over the table."""
 import collections
-import contextlib
 import ctypes
 import functools
 import os
@@ -260,16 +259,15 @@ def _nothing_resident(c):
 
 
 def test_release_forgets_every_resident_result(contexts):
+    from keras_ocr_amd.extras import Extras
+
     state = contexts.get({})
     c = _prepare(state, wc.row("pipeline-widest"))
     c.release_arenas()
     _nothing_resident(c)
     args, kwargs = wc.call_of(wc.row("pipeline-widest"))
-    with contextlib.ExitStack() as stack:  # the call's switches stay on for the getters
-        stack.enter_context(c._scores_scope(True))  # pylint: disable=protected-access
-        stack.enter_context(c._lexicon_scope(wc.TOP_WORDS))  # pylint: disable=protected-access
-        stack.enter_context(c._pattern_scope(kwargs["pattern"]))  # pylint: disable=protected-access
-        stack.enter_context(c._char_boxes_scope(True))  # pylint: disable=protected-access
+    # the call's switches stay on for the getters
+    with c._extras_scope(Extras(scores=True, lexicon_top=wc.TOP_WORDS, pattern=kwargs["pattern"], char_boxes=True)):  # pylint: disable=protected-access
         out = c._pipeline(*args, 0.7, 0.4, 0.4, 10, 0, False, 256, None)  # pylint: disable=protected-access
         counts = [len(b) for b in out.boxes]
         assert sum(counts) == len(out.labels) > 0
@@ -283,7 +281,7 @@ def test_release_forgets_every_resident_result(contexts):
         _nothing_resident(c)
     c = _prepare(state, wc.row("pipeline-orientation"))
     args, kwargs = wc.call_of(wc.row("pipeline-orientation"))
-    with c._orientation_scope((2, 1.5)):  # pylint: disable=protected-access
+    with c._extras_scope(Extras(orientation=(2, 1.5))):  # pylint: disable=protected-access
         out = c._pipeline(*args, 0.7, 0.4, 0.4, 10, 0, False, 256, None)  # pylint: disable=protected-access
         turns, quads, pairs = c.recognition_orientation()
         assert len(turns) == len(quads) == len(pairs) == len(out.labels) > 0
