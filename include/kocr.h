@@ -923,6 +923,14 @@ int kocr_debug_set_arena_guards(kocr_ctx* ctx, int on);
  * (negative: a KOCR_* code); *arena, *offset, *byte (nullable) name the first: its arena, the offset of the buffer it follows,
  * and the offset of its first damaged byte.  The count starts again at 0. */
 int kocr_debug_check_arena_guards(kocr_ctx* ctx, int* arena, uint64_t* offset, uint64_t* byte);
+/* For tests: poison mode (byte = -1: off, the default; off costs one test per allocation and changes no launch).  With byte in
+ * [0, 255], every allocation from an arena -- and every tensor the detector's lifetime pool hands out inside the ws arena --
+ * is filled with that byte over exactly its bytes, on the context's stream when it is allocated: behind the previous user of
+ * those bytes, before its own first writer.  A kernel that reads what this call has not written then reads the byte instead of
+ * whatever the memory last held, so a call whose results differ between byte 0x00 and byte 0xFF (NaN as a float, -1 as an
+ * integer) depends on stale workspace.  Results that stay resident are not touched by their getters.  Works together with
+ * guard mode.  KOCR_EINVAL for another byte.  ("Poison mode".) */
+int kocr_debug_set_arena_poison(kocr_ctx* ctx, int byte);
 
 #ifdef __cplusplus
 }

@@ -177,6 +177,7 @@ def load_library():
         "kocr_debug_release_arenas": (ci, [vp]),
         "kocr_debug_set_arena_guards": (ci, [vp, ci]),
         "kocr_debug_check_arena_guards": (ci, [vp, vp, vp, vp]),
+        "kocr_debug_set_arena_poison": (ci, [vp, ci]),
     }
     for name, (res, args) in sigs.items():
         if not hasattr(lib, name):
@@ -1661,6 +1662,11 @@ class Context:
 
     def set_arena_guards(self, on=True):
         self._check(self._lib.kocr_debug_set_arena_guards(self._h, int(bool(on))))
+
+    def set_arena_poison(self, byte=None):
+        """Poison mode (kocr_debug_set_arena_poison): every workspace allocation is filled with ``byte`` (0..255) on the stream
+        when it is made; None switches the mode off."""
+        self._check(self._lib.kocr_debug_set_arena_poison(self._h, -1 if byte is None else int(byte)))
 
     def check_arena_guards(self):
         """(damaged guards since the last check, first one's arena name or None, its buffer's offset, its first damaged byte)"""

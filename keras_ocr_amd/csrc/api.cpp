@@ -41,6 +41,11 @@ void arena_guard_fill(Arena& a, size_t at, size_t len) {
   if (hipMemsetAsync(a.base + at, ARENA_GUARD_FILL, len, ctx->stream) != hipSuccess) ctx->set_err("arena guard: hipMemsetAsync failed");
 }
 
+void arena_poison_fill(Arena& a, void* p, size_t bytes) {
+  kocr_ctx* ctx = a.pctx;
+  if (bytes && hipMemsetAsync(p, a.pbyte, bytes, ctx->stream) != hipSuccess) ctx->set_err("arena poison: hipMemsetAsync failed");
+}
+
 void arena_guard_check(Arena& a) {
   kocr_ctx* ctx = a.gctx;
   std::vector<ArenaGuard> list;
@@ -1523,9 +1528,12 @@ int kocr_debug_release_arenas(kocr_ctx* ctx) {
   for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) {
     Arena& a = *ctx->arena_at(i);
     if (a.base) KOCR_HIP(ctx, hipFree(a.base));
-    kocr_ctx* const gctx = a.gctx;
+    kocr_ctx *const gctx = a.gctx, *const pctx = a.pctx;
+    const unsigned char pbyte = a.pbyte;
     a = Arena{};
     a.gctx = gctx;
+    a.pctx = pctx;
+    a.pbyte = pbyte;
   }
   ctx->invalidate_results();
   ctx->guard_damage = kocr_ctx::GuardDamage{};
@@ -1539,6 +1547,17 @@ int kocr_debug_set_arena_guards(kocr_ctx* ctx, int on) {
     if (!a.guards.empty()) arena_guard_check(a);
     // the next allocation of an arena comes behind a reset of it; until then its offsets stay what they are
     a.gctx = on ? ctx : nullptr;
+  }
+  return KOCR_OK;
+}
+
+int kocr_debug_set_arena_poison(kocr_ctx* ctx, int byte) {
+  if (!ctx) return KOCR_EINVAL;
+  if (byte < -1 || byte > 255) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_debug_set_arena_poison: byte must be -1 (off) or in [0, 255]");
+  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) {
+    Arena& a = *ctx->arena_at(i);
+    a.pctx = byte >= 0 ? ctx : nullptr;
+    a.pbyte = (unsigned char)(byte >= 0 ? byte : 0);
   }
   return KOCR_OK;
 }

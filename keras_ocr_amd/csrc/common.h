@@ -128,6 +128,9 @@ struct RangeRow {
 // set): every allocation is followed by ARENA_GUARD_BYTES more, and the bytes from its end to the end of those are filled with
 // ARENA_GUARD_FILL on the stream at allocation time and compared by reset() and kocr_debug_check_arena_guards.  off stays the
 // offset the allocations would have reached without guards (gextra: what the guards have added), so the stats are the same.
+// Poison mode (kocr_debug_set_arena_poison; pctx set): every allocation is filled with `pbyte` over exactly its bytes on the
+// stream at allocation time -- behind the previous user of those bytes, like a guard's fill -- so that a kernel which reads
+// what this call has not written reads the same loud value wherever the bytes came from ("Poison mode").
 constexpr size_t ARENA_GUARD_BYTES = 256, ARENA_GUARD_RESERVE = (size_t)256 << 10;
 constexpr unsigned char ARENA_GUARD_FILL = 0xA5;
 struct ArenaGuard {
@@ -141,6 +144,8 @@ struct Arena {
   kocr_ctx* gctx = nullptr;  // guard mode: the context whose stream fills and whose record latches the damage
   size_t gextra = 0;
   std::vector<ArenaGuard> guards;  // of the allocations since the last check
+  kocr_ctx* pctx = nullptr;  // poison mode: the context whose stream fills
+  unsigned char pbyte = 0;
   inline void reset();
   void note(size_t end) {  // an allocation that reaches (or would reach) `end`
     if (end > peak) peak = end;
@@ -478,6 +483,9 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes);
 // first damaged one in ctx->guard_damage and forgets the list
 void arena_guard_fill(Arena& a, size_t at, size_t len);
 void arena_guard_check(Arena& a);
+// poison mode only (api.cpp): the fill of one allocation on the stream.  The sub-allocators that carve a reserved block
+// themselves (craft.cpp: LivePool) call it for every hand-out.
+void arena_poison_fill(Arena& a, void* p, size_t bytes);
 inline void Arena::reset() {
   if (!guards.empty()) arena_guard_check(*this);
   off = gextra = 0;
@@ -488,6 +496,7 @@ inline void* arena_alloc(Arena& a, size_t bytes) {
   if (!a.gctx) {
     if (o + bytes > a.cap) return nullptr;
     a.off = o + bytes;
+    if (a.pctx) arena_poison_fill(a, a.base + o, bytes);
     return a.base + o;
   }
   const size_t at = o + a.gextra, end = at + bytes, glen = ((end + 255) & ~(size_t)255) + ARENA_GUARD_BYTES - end;
@@ -496,6 +505,7 @@ inline void* arena_alloc(Arena& a, size_t bytes) {
   a.gextra += ARENA_GUARD_BYTES;
   a.guards.push_back(ArenaGuard{at, end, glen});
   arena_guard_fill(a, end, glen);
+  if (a.pctx) arena_poison_fill(a, a.base + at, bytes);
   return a.base + at;
 }
 inline void* kocr_ctx::ws_alloc(size_t bytes) { return arena_alloc(ws, bytes); }

@@ -336,6 +336,7 @@ int craft_run(kocr_ctx* ctx, CraftNet* net, const void* d_img, int dtype, int N,
       t->amax = track ? ctx->amax_slots(N) : nullptr;
       if (off + al(bytes) > room) KOCR_FAIL(ctx, KOCR_ENOMEM, "kocr_craft_forward: workspace exhausted");
       t->p = reinterpret_cast<float*>(base + off);
+      if (ctx->ws.pctx) arena_poison_fill(ctx->ws, t->p, bytes);  // poison mode: a hand-out is an allocation like any other
     }
     live[t->p] = {off, bytes};
     return KOCR_OK;

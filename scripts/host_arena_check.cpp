@@ -1,6 +1,6 @@
 // Developer check on the host alone (no GPU, nothing of the library linked): the book-keeping of Arena (common.h) --
-// requested / peak / excess, reset(), guard placement and the guard comparison -- over a block of HOST memory.  The two guard
-// hooks that api.cpp implements on the stream are restated here with memset / memcpy; everything else is the library's own
+// requested / peak / excess, reset(), guard placement, the guard comparison and the poison fill -- over a block of HOST memory.
+// The three hooks that api.cpp implements on the stream are restated here with memset / memcpy; everything else is the library's own
 // inline code.  Under the address and undefined-behaviour sanitizers a guard placed outside the block is reported.
 //   hipcc -std=c++17 -x hip --cuda-host-only -Xarch_host -fsanitize=address,undefined -Wno-unused-value -I keras_ocr_amd/csrc \
 //         scripts/host_arena_check.cpp -o host_arena_check && ./host_arena_check
@@ -19,6 +19,7 @@
 
 // ---- the hooks of api.cpp, restated on host memory ----
 void arena_guard_fill(Arena& a, size_t at, size_t len) { memset(a.base + at, ARENA_GUARD_FILL, len); }
+void arena_poison_fill(Arena& a, void* p, size_t bytes) { memset(p, a.pbyte, bytes); }
 void arena_guard_check(Arena& a) {
   kocr_ctx* ctx = a.gctx;
   std::vector<ArenaGuard> list;
@@ -123,6 +124,34 @@ int main() {
   // guards off: the plain layout again
   a.gctx = nullptr;
   CHECK(arena_alloc(a, 100) == a.base && arena_alloc(a, 1) == a.base + 256 && a.guards.empty());
+
+  // (7) poison mode: exactly the buffer's bytes are filled -- not the alignment gap behind it, not a guard -- with and
+  // without guards, and the layout and the statistics are those of the mode off
+  reserve(a, 1000, 1000 + 125 + 4096 + 2 * (256 + 255));
+  memset(a.base, 0x11, a.cap);
+  a.pctx = &ctx;
+  a.pbyte = 0xFF;
+  p0 = (char*)arena_alloc(a, 100);
+  p1 = (char*)arena_alloc(a, 300);
+  CHECK(p0 == a.base && p1 == a.base + 256 && a.off == 556 && a.peak == 556 && a.guards.empty());
+  for (size_t i = 0; i < 556; ++i) CHECK((unsigned char)a.base[i] == ((i < 100 || i >= 256) ? 0xFF : 0x11));
+  CHECK((unsigned char)a.base[556] == 0x11);
+  a.reset();
+  a.gctx = &ctx;
+  a.pbyte = 0x00;
+  memset(a.base, 0x11, a.cap);
+  g0 = (char*)arena_alloc(a, 100);
+  g1 = (char*)arena_alloc(a, 300);
+  CHECK(g0 == a.base && g1 == a.base + 512 && a.off == 556 && a.guards.size() == 2);
+  for (size_t i = 0; i < 100; ++i) CHECK(g0[i] == 0);
+  for (size_t i = 100; i < 512; ++i) CHECK((unsigned char)a.base[i] == ARENA_GUARD_FILL);
+  for (size_t i = 0; i < 300; ++i) CHECK(g1[i] == 0);
+  CHECK((unsigned char)g1[300] == ARENA_GUARD_FILL);
+  const int before = ctx.guard_damage.count;
+  a.reset();
+  CHECK(ctx.guard_damage.count == before);  // the fill damaged no guard
+  a.gctx = a.pctx = nullptr;
+  CHECK(arena_alloc(a, 100) == a.base && (unsigned char)a.base[0] == 0);  // off: nothing is filled
   free(a.base);
   a.base = nullptr;
   printf("host_arena_check ok\n");

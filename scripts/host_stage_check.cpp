@@ -33,6 +33,7 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
 int kocr_ctx::ws_reserve(size_t bytes) { return arena_reserve(this, ws, bytes); }
 void arena_guard_fill(Arena&, size_t, size_t) {}  // guard mode stays off here (scripts/host_arena_check.cpp drives it)
 void arena_guard_check(Arena&) {}
+void arena_poison_fill(Arena&, void*, size_t) {}  // ... and so does poison mode
 int crnn_label_width(kocr_ctx*) { return LW; }
 int crnn_classes(kocr_ctx*) { return C; }
 size_t crnn_workspace_bytes(int M, int) { return (size_t)M * 64; }
