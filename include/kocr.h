@@ -69,6 +69,22 @@ int kocr_memcpy_h2d(kocr_ctx* ctx, void* dst, const void* src, uint64_t bytes);
 int kocr_memcpy_d2h(kocr_ctx* ctx, void* dst, const void* src, uint64_t bytes);
 
 /* ---- weights ------------------------------------------------------------------------ */
+/* Both loaders may be called again on a context that already holds weights, and both keep one contract:
+ *  - Validate first, change afterwards.  Every required tensor is looked up by name and checked for its size before the
+ *    context is touched.  A refused set returns KOCR_EINVAL, kocr_last_error naming the first tensor that is missing
+ *    ("missing tensor <name>") or of another size ("tensor <name> has wrong size"), and leaves everything as it was: the
+ *    weights and whether they are loaded, the class count, the label width, the lexicon, character sets and patterns, and
+ *    the device memory the context holds.  On a context without weights every forward then still returns KOCR_ENOWEIGHTS.
+ *  - A reload replaces.  After a successful load the context computes what a new context with that set computes, bit for
+ *    bit, and holds the same persistent device memory: every device copy derived from the previous set has been freed (the
+ *    stream is drained first).  A recogniser set without the stn_* tensors replaces one with them by a network without the
+ *    transformer, whose four layers are freed too.  The stn_* tensors come all eight or not at all: a set with some of them
+ *    is refused naming the first that is missing.
+ *  - A recogniser of another class count (the length of "fc_12/bias") unloads the lexicon, the character sets and the
+ *    patterns, which were validated against the previous count, and gives back the workspace arenas, which were sized for it.
+ *    The label width (kocr_crnn_set_rnn_steps_to_discard) is no part of a weight set and stays.
+ *  - Should a load fail after its validation (a device allocation or a copy), the network is left NOT loaded
+ *    (KOCR_ENOWEIGHTS until a load succeeds), never a mixture of two sets. */
 /* CRAFT detector weights.  Replaces detection.build_keras_model(weights_path) +
  * load_torch_weights (detection.py:353-424, 428-468).  `names[i]` are the PyTorch
  * state-dict keys minus the "module." prefix (the naming load_torch_weights uses,
@@ -931,6 +947,15 @@ int kocr_debug_check_arena_guards(kocr_ctx* ctx, int* arena, uint64_t* offset, u
  * integer) depends on stale workspace.  Results that stay resident are not touched by their getters.  Works together with
  * guard mode.  KOCR_EINVAL for another byte.  ("Poison mode".) */
 int kocr_debug_set_arena_poison(kocr_ctx* ctx, int byte);
+/* For tests: the device memory the library holds ("What a context owns and when it lets go").
+ * *persistent_count / *persistent_bytes: the context's persistent allocations -- weights with their derived copies, lexicon,
+ * character sets, patterns, the lazily allocated buffers -- and their sizes as asked for; *arena_bytes: the sum of its arenas'
+ * capacities.  *process_count / *process_bytes: every allocation the library has made and not yet freed in this process, all
+ * contexts' and kocr_device_alloc's included (counted where the memory is taken and given back, never read from the device,
+ * whose free memory moves with other processes' work).  ctx may be NULL: the context's three figures are then 0.  Any pointer
+ * may be NULL. */
+int kocr_debug_memory_stats(kocr_ctx* ctx, uint64_t* persistent_count, uint64_t* persistent_bytes, uint64_t* arena_bytes,
+                            uint64_t* process_count, uint64_t* process_bytes);
 
 #ifdef __cplusplus
 }

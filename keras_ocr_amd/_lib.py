@@ -174,6 +174,7 @@ def load_library():
         "kocr_debug_arena_count": (ci, []),
         "kocr_debug_arena_name": (ctypes.c_char_p, [ci]),
         "kocr_debug_arena_stats": (ci, [vp, ci, vp, vp, vp, vp]),
+        "kocr_debug_memory_stats": (ci, [vp, vp, vp, vp, vp, vp]),
         "kocr_debug_release_arenas": (ci, [vp]),
         "kocr_debug_set_arena_guards": (ci, [vp, ci]),
         "kocr_debug_check_arena_guards": (ci, [vp, vp, vp, vp]),
@@ -250,6 +251,14 @@ def orientation_args(orientation, tall_ratio=1.5):
     if not (math.isfinite(ratio) and ratio > 0):
         raise ValueError(f"tall_ratio {tall_ratio!r} must be finite and positive")
     return ORIENTATION_MODES[orientation], ratio
+
+
+def debug_process_memory():
+    """{process_count, process_bytes}: the device allocations the library holds in this process, over all contexts
+    (kocr_debug_memory_stats without a context; for tests).  Touches no device."""
+    v = [ctypes.c_uint64(0) for _ in range(2)]
+    load_library().kocr_debug_memory_stats(None, None, None, None, ctypes.byref(v[0]), ctypes.byref(v[1]))
+    return {"process_count": int(v[0].value), "process_bytes": int(v[1].value)}
 
 
 class Context:
@@ -1655,6 +1664,14 @@ class Context:
             self._check(self._lib.kocr_debug_arena_stats(self._h, i, *[ctypes.byref(x) for x in v]))
             out[name] = dict(zip(("cap", "requested", "peak", "excess"), (int(x.value) for x in v)))
         return out
+
+    def debug_memory(self):
+        """{persistent_count, persistent_bytes, arena_bytes, process_count, process_bytes} (kocr_debug_memory_stats): the device
+        memory this context owns, and what the library holds in the whole process -- counted, never read from the device."""
+        v = [ctypes.c_uint64(0) for _ in range(5)]
+        self._check(self._lib.kocr_debug_memory_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("persistent_count", "persistent_bytes", "arena_bytes", "process_count", "process_bytes"),
+                        (int(x.value) for x in v)))
 
     def release_arenas(self):
         """Frees every arena and forgets every resident result: the context is cold again, its networks stay loaded."""

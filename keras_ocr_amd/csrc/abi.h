@@ -193,16 +193,15 @@ long prepare_box_warps(kocr_ctx* ctx, const char* fn, int N, const float* boxes,
                        int tw, std::vector<WarpParam>& prm);
 
 // The temporary layer of a kocr_conv2d_* call: the device buffers its preparation adds to ctx->owned after construction are
-// freed, once the stream has drained, on every return path.
+// freed, once the stream has drained, on every return path.  A buffer that is to outlive the call must therefore be allocated
+// BEFORE the mark is taken (the max-|x| slot pool: amax_begin ahead of the layer; the range-statistics block:
+// kocr_range_stats_enable) -- tests/test_lifecycle_gpu.py checks what a first call leaves behind.
 struct TempLayer {
   kocr_ctx* ctx;
   size_t mark;
   explicit TempLayer(kocr_ctx* c) : ctx(c), mark(c->owned.size()) {}
   ~TempLayer() {
     hipStreamSynchronize(ctx->stream);
-    while (ctx->owned.size() > mark) {
-      hipFree(ctx->owned.back());
-      ctx->owned.pop_back();
-    }
+    ctx->release_since(mark);
   }
 };

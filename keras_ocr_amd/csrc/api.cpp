@@ -4,12 +4,64 @@
 #include "taps.h"
 #include <cmath>
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <set>
+#include <unordered_map>
 
 // ---------------------------------------------------------------------------------------
 // ctx internals
 // ---------------------------------------------------------------------------------------
+// Device memory: every allocation of the library, for all contexts of the process, goes through this pair.  The sizes are kept
+// by address, so that a free needs none (kocr_device_free has only the pointer).
+namespace {
+std::mutex g_mem_mu;
+std::unordered_map<void*, size_t> g_mem_size;
+std::atomic<uint64_t> g_mem_count{0}, g_mem_bytes{0};
+}  // namespace
+
+hipError_t kocr_counted_malloc(void** p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> g(g_mem_mu);
+  g_mem_size[*p] = bytes;
+  g_mem_count += 1;
+  g_mem_bytes += bytes;
+  return e;
+}
+
+hipError_t kocr_counted_free(void* p) {
+  if (!p) return hipSuccess;
+  {  // forgotten before it is freed: the address may be handed out again at once
+    std::lock_guard<std::mutex> g(g_mem_mu);
+    auto it = g_mem_size.find(p);
+    if (it != g_mem_size.end()) {
+      g_mem_count -= 1;
+      g_mem_bytes -= it->second;
+      g_mem_size.erase(it);
+    }
+  }
+  return hipFree(p);
+}
+
+// every arena given back (kocr_debug_release_arenas; kocr_load_crnn with another class count); the debug modes stay as set
+static int release_arenas(kocr_ctx* ctx) {
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) {
+    Arena& a = *ctx->arena_at(i);
+    if (!a.guards.empty()) arena_guard_check(a);  // before the memory they lie in goes
+    if (a.base) KOCR_HIP(ctx, kocr_counted_free(a.base));
+    kocr_ctx *const gctx = a.gctx, *const pctx = a.pctx;
+    const unsigned char pbyte = a.pbyte;
+    a = Arena{};
+    a.gctx = gctx;
+    a.pctx = pctx;
+    a.pbyte = pbyte;
+  }
+  ctx->invalidate_results();
+  return KOCR_OK;
+}
+
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   ctx->invalidate_results();  // whoever sizes an arena is about to overwrite it (the entry points re-validate at their end)
   a.requested = bytes;
@@ -19,15 +71,15 @@ int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes) {
   if (a.base) {
     if (!a.guards.empty()) arena_guard_check(a);  // before the memory they lie in goes
     KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    KOCR_HIP(ctx, hipFree(a.base));
+    KOCR_HIP(ctx, kocr_counted_free(a.base));
     a.base = nullptr;
     a.cap = 0;
   }
   const size_t want = bytes + (bytes >> 3) + 4096 + guard;
   void* p = nullptr;
-  hipError_t e = hipMalloc(&p, want);
+  hipError_t e = kocr_counted_malloc(&p, want);
   if (e != hipSuccess) {
-    ctx->set_err("workspace hipMalloc(" + std::to_string(want) + " B) failed: " + hipGetErrorString(e));
+    ctx->set_err("workspace allocation of " + std::to_string(want) + " B failed: " + hipGetErrorString(e));
     return KOCR_ENOMEM;
   }
   a.base = (char*)p;
@@ -91,18 +143,6 @@ unsigned* kocr_ctx::amax_slots(int n) {
   return s;
 }
 
-int kocr_ctx::dev_alloc(void** out, size_t bytes) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, bytes ? bytes : 4);
-  if (e != hipSuccess) {
-    set_err(std::string("hipMalloc failed: ") + hipGetErrorString(e));
-    return KOCR_ENOMEM;
-  }
-  owned.push_back(p);
-  *out = p;
-  return KOCR_OK;
-}
-
 void kocr_note_dispatch(const char* family, const ConvLayer& L, const Tensor& in) {
   static const char* path = getenv("KOCR_DISPATCH_LOG");
   if (!path) return;
@@ -117,16 +157,6 @@ void kocr_note_dispatch(const char* family, const ConvLayer& L, const Tensor& in
     fprintf(f, "%s\n", line);
     fclose(f);
   }
-}
-
-void kocr_ctx::release(void* p) {
-  if (!p) return;
-  for (size_t i = owned.size(); i-- > 0;)
-    if (owned[i] == p) {
-      owned.erase(owned.begin() + (long)i);
-      hipFree(p);
-      return;
-    }
 }
 
 int kocr_ctx::upload(float** out, const std::vector<float>& host) {
@@ -377,9 +407,8 @@ void kocr_destroy(kocr_ctx* ctx) {
   hipStreamSynchronize(ctx->stream);
   craft_free(ctx);
   crnn_free(ctx);
-  for (void* p : ctx->owned) hipFree(p);
-  for (Arena* a : {&ctx->ws, &ctx->pp, &ctx->pp2, &ctx->io, &ctx->pl, &ctx->bx, &ctx->chw, &ctx->chr})
-    if (a->base) hipFree(a->base);
+  ctx->release_since(0);
+  for (Arena* a : {&ctx->ws, &ctx->pp, &ctx->pp2, &ctx->io, &ctx->pl, &ctx->bx, &ctx->chw, &ctx->chr}) kocr_counted_free(a->base);
   for (auto& pd : ctx->pending) {
     hipEventDestroy(pd.a);
     hipEventDestroy(pd.b);
@@ -407,14 +436,14 @@ int kocr_synchronize(kocr_ctx* ctx) {
 int kocr_device_alloc(kocr_ctx* ctx, void** out, uint64_t bytes) {
   if (!ctx || !out) return KOCR_EINVAL;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  KOCR_HIP(ctx, hipMalloc(out, bytes ? bytes : 4));
+  KOCR_HIP(ctx, kocr_counted_malloc(out, bytes ? bytes : 4));
   return KOCR_OK;
 }
 
 int kocr_device_free(kocr_ctx* ctx, void* p) {
   if (!ctx) return KOCR_EINVAL;
   KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  KOCR_HIP(ctx, hipFree(p));
+  KOCR_HIP(ctx, kocr_counted_free(p));
   return KOCR_OK;
 }
 
@@ -445,6 +474,7 @@ int kocr_craft_forward(kocr_ctx* ctx, const void* img, int dtype, int N, int H, 
   if (N < 0 || (N > 0 && (!img || !heat))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_forward: null buffer");
   if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_forward: bad dtype");
   if (N == 0) return KOCR_OK;
+  if (!craft_loaded(ctx)) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_craft_forward: call kocr_load_craft first");
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int mb = craft_micro_batch(micro_batch, N, H, W);
   const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
@@ -470,7 +500,11 @@ int kocr_load_crnn(kocr_ctx* ctx, int n, const char* const* names, const float* 
                    const int64_t* shapes, const int* ranks) {
   if (!ctx || n <= 0 || !names || !data || !shapes || !ranks) return KOCR_EINVAL;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
+  const int before = crnn_classes(ctx);
   KOCR_TRY(crnn_load(ctx, n, names, data, shapes, ranks));
+  // the arenas were sized for the previous class count (logits, probabilities): a recogniser of fewer classes would keep them
+  // for ever.  Given back here, they grow again to what this one asks for -- the state of a fresh context.
+  if (before && before != crnn_classes(ctx)) KOCR_TRY(release_arenas(ctx));
   // a lexicon's labels were validated against the class count of the recogniser it was loaded under
   if (ctx->lex.V && ctx->lex.classes != crnn_classes(ctx)) lexicon_unload(ctx, ctx->lex.classes);
   // ... and so were the character sets' class indices
@@ -1103,6 +1137,7 @@ int kocr_craft_mse(kocr_ctx* ctx, const void* img, int dtype, int N, int H, int 
   if (N < 0 || (N > 0 && (!img || !y_true || !sums))) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_mse: null buffer");
   if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_craft_mse: bad dtype");
   if (N == 0) return KOCR_OK;
+  if (!craft_loaded(ctx)) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_craft_mse: call kocr_load_craft first");
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int mb = craft_micro_batch(micro_batch, N, H, W);
   const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
@@ -1524,19 +1559,24 @@ int kocr_debug_arena_stats(kocr_ctx* ctx, int i, uint64_t* cap, uint64_t* reques
 int kocr_debug_release_arenas(kocr_ctx* ctx) {
   if (!ctx) return KOCR_EINVAL;
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
-  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) {
-    Arena& a = *ctx->arena_at(i);
-    if (a.base) KOCR_HIP(ctx, hipFree(a.base));
-    kocr_ctx *const gctx = a.gctx, *const pctx = a.pctx;
-    const unsigned char pbyte = a.pbyte;
-    a = Arena{};
-    a.gctx = gctx;
-    a.pctx = pctx;
-    a.pbyte = pbyte;
-  }
-  ctx->invalidate_results();
+  KOCR_TRY(release_arenas(ctx));
   ctx->guard_damage = kocr_ctx::GuardDamage{};
+  return KOCR_OK;
+}
+
+int kocr_debug_memory_stats(kocr_ctx* ctx, uint64_t* persistent_count, uint64_t* persistent_bytes, uint64_t* arena_bytes,
+                            uint64_t* process_count, uint64_t* process_bytes) {
+  uint64_t pc = 0, pb = 0, ab = 0;
+  if (ctx) {
+    pc = ctx->owned.size();
+    for (const kocr_ctx::Owned& o : ctx->owned) pb += o.bytes;
+    for (int i = 0; i < kocr_ctx::N_ARENAS; ++i) ab += ctx->arena_at(i)->cap;
+  }
+  if (persistent_count) *persistent_count = pc;
+  if (persistent_bytes) *persistent_bytes = pb;
+  if (arena_bytes) *arena_bytes = ab;
+  if (process_count) *process_count = g_mem_count.load();
+  if (process_bytes) *process_bytes = g_mem_bytes.load();
   return KOCR_OK;
 }
 

@@ -270,11 +270,17 @@ struct kocr_ctx {
   void ws_reset() { ws.reset(); }
   void* ws_alloc(size_t bytes);
 
-  // persistent allocations (weights)
-  std::vector<void*> owned;
-  int dev_alloc(void** out, size_t bytes);
+  // persistent allocations (weights, tables, the lazy buffers of DESIGN.md section 2), each with its size
+  // (kocr_debug_memory_stats)
+  struct Owned {
+    void* p;
+    size_t bytes;
+  };
+  std::vector<Owned> owned;
+  inline int dev_alloc(void** out, size_t bytes);
   int upload(float** out, const std::vector<float>& host);
-  void release(void* p);  // hipFree one persistent allocation (a re-prepared layer's previous weights); nullptr is ignored
+  inline void release(void* p);            // frees one persistent allocation (a re-prepared layer's previous weights); nullptr is ignored
+  inline void release_since(size_t mark);  // frees every allocation behind the first `mark` (TempLayer, abi.h)
   float* d_div255 = nullptr;  // [256] float32 v / 255 of kocr_compute_maps, uploaded by its first call on the context
 
   CraftNet* craft = nullptr;
@@ -478,6 +484,39 @@ struct kocr_ctx {
   int prof_flush();
 };
 
+// The one pair of calls through which the library takes device memory and gives it back (api.cpp): they keep the process-wide
+// figures of kocr_debug_memory_stats.  tests/test_lifecycle_cpu.py asserts that the runtime's allocator is called nowhere else.
+hipError_t kocr_counted_malloc(void** p, size_t bytes);
+hipError_t kocr_counted_free(void* p);  // nullptr is ignored
+
+inline int kocr_ctx::dev_alloc(void** out, size_t bytes) {
+  void* p = nullptr;
+  const size_t want = bytes ? bytes : 4;
+  hipError_t e = kocr_counted_malloc(&p, want);
+  if (e != hipSuccess) {
+    set_err(std::string("device allocation failed: ") + hipGetErrorString(e));
+    return KOCR_ENOMEM;
+  }
+  owned.push_back(Owned{p, want});
+  *out = p;
+  return KOCR_OK;
+}
+inline void kocr_ctx::release(void* p) {
+  if (!p) return;
+  for (size_t i = owned.size(); i-- > 0;)
+    if (owned[i].p == p) {
+      owned.erase(owned.begin() + (long)i);
+      kocr_counted_free(p);
+      return;
+    }
+}
+inline void kocr_ctx::release_since(size_t mark) {
+  while (owned.size() > mark) {
+    kocr_counted_free(owned.back().p);
+    owned.pop_back();
+  }
+}
+
 int arena_reserve(kocr_ctx* ctx, Arena& a, size_t bytes);
 // guard mode only (api.cpp): the fill of one guard on the stream; the comparison of the recorded guards, which latches the
 // first damaged one in ctx->guard_damage and forgets the list
@@ -600,6 +639,7 @@ __device__ __forceinline__ void kocr_amax_update(unsigned* slot, float m) { kocr
 int prepare_conv(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw, int Cin, int Cout,
                  int KH, int KW, int dil, const float* pre_a, const float* pre_b, int relu,
                  const float* post_a, const float* post_b);
+int release_layer(kocr_ctx* ctx, ConvLayer& L);  // every device copy of L given back; L is then not ready()
 // in_u8 != nullptr: first-layer mode, raw RGB bytes + LUT normalisation.
 // developer instrumentation (KOCR_DISPATCH_LOG=<file>): one line per distinct (kernel family, layer, input shape) the dispatcher
 // of launch_conv_pool chose in this process -- the table of DESIGN.md section 3 "which shapes reach which family" comes from it
@@ -669,6 +709,9 @@ int launch_head_tail(kocr_ctx* ctx, const ConvLayer& L6, const ConvLayer& L8, co
 int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* const* data,
                const int64_t* shapes, const int* ranks);
 int craft_forward(kocr_ctx* ctx, const void* d_img, int dtype, int N, int H, int W, float* d_heat);
+// a complete detector is loaded (not: none yet, a refused first load, a load that failed on its way).  The entry points ask
+// this ahead of any work; craft_forward asks again.
+bool craft_loaded(const kocr_ctx* ctx);
 size_t craft_workspace_bytes(int N, int H, int W);
 void craft_free(kocr_ctx* ctx);
 void taps_free(kocr_ctx* ctx);  // taps.cpp

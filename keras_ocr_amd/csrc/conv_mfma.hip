@@ -465,6 +465,25 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 8) ? 2 : 2) void conv_mfm
 // ---------------------------------------------------------------------------------------
 static int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
+// Every device copy of a layer given back, once the stream has drained; the layer is then not ready().  The one list of what a
+// layer owns: prepare_conv (a layer prepared again) and crnn_load (the stn_* layers of a recogniser replaced by one without
+// them) both come here.
+int release_layer(kocr_ctx* ctx, ConvLayer& L) {
+  void* old[] = {L.d_w, L.d_pre_a, L.d_pre_b, L.d_post_a, L.d_post_b, L.d_w_rgb4, L.d_pre_a_h, L.d_ws, L.d_w4,
+                 L.d_w4h, L.d_ds, L.d_first, L.d_hs, L.d_hs16, L.d_hsh, L.d_k5};
+  bool any = false;
+  for (void* q : old) any = any || q != nullptr;
+  if (any) {
+    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (void* q : old) ctx->release(q);
+  }
+  L.d_w = L.d_pre_a = L.d_pre_b = L.d_post_a = L.d_post_b = L.d_w_rgb4 = L.d_pre_a_h = nullptr;
+  L.d_ws = L.d_w4 = L.d_w4h = L.d_ds = L.d_first = L.d_hs = L.d_hs16 = L.d_hsh = L.d_k5 = nullptr;
+  L.hs_wexp.clear();
+  L.first_bound = 0.f;
+  return KOCR_OK;
+}
+
 int prepare_conv(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw, int Cin, int Cout,
                  int KH, int KW, int dil, const float* pre_a, const float* pre_b, int relu,
                  const float* post_a, const float* post_b) {
@@ -474,20 +493,7 @@ int prepare_conv(kocr_ctx* ctx, ConvLayer& L, const float* w, bool w_is_oihw, in
   // tests/test_range_gpu.py's re-loaded detector: conv_cls.0 / .2 a factor 2^k off per channel).  The old device buffers
   // are released here, after the stream has drained (kept until the context died, every kocr_load_* on a live
   // context leaked the whole previous weight set -- fp32 plus every split / transformed copy).
-  {
-    void* old[] = {L.d_w, L.d_pre_a, L.d_pre_b, L.d_post_a, L.d_post_b, L.d_w_rgb4, L.d_pre_a_h, L.d_ws, L.d_w4,
-                   L.d_w4h, L.d_ds, L.d_first, L.d_hs, L.d_hs16, L.d_hsh, L.d_k5};
-    bool any = false;
-    for (void* q : old) any = any || q != nullptr;
-    if (any) {
-      KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      for (void* q : old) ctx->release(q);
-    }
-  }
-  L.d_w = L.d_pre_a = L.d_pre_b = L.d_post_a = L.d_post_b = L.d_w_rgb4 = L.d_pre_a_h = nullptr;
-  L.d_ws = L.d_w4 = L.d_w4h = L.d_ds = L.d_first = L.d_hs = L.d_hs16 = L.d_hsh = L.d_k5 = nullptr;
-  L.hs_wexp.clear();
-  L.first_bound = 0.f;
+  KOCR_TRY(release_layer(ctx, L));
   L.Cin = Cin;
   L.Cout = Cout;
   L.KH = KH;

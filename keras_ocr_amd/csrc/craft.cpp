@@ -14,6 +14,7 @@
 // resize(conv1x1_y(y)) + conv1x1_skip(skip) (up_conv, kocr_set_schedule / KOCR_UPFOLD); the up-sampled halves of cat2..4 and s5 are then
 // never written.
 #include "common.h"
+#include "load_check.h"
 #include "taps.h"
 #include <algorithm>
 #include <cmath>
@@ -27,42 +28,8 @@ struct CraftNet {
 
 namespace {
 
-struct Spec {
-  const char* conv;
-  const char* bn;  // nullptr: no BN
-  int cin, cout, k, dil, relu;
-};
-
-const Spec kSpecs[] = {
-    {"basenet.slice1.0", "basenet.slice1.1", 3, 64, 3, 1, 1},
-    {"basenet.slice1.3", "basenet.slice1.4", 64, 64, 3, 1, 1},
-    {"basenet.slice1.7", "basenet.slice1.8", 64, 128, 3, 1, 1},
-    {"basenet.slice1.10", "basenet.slice1.11", 128, 128, 3, 1, 1},
-    {"basenet.slice2.14", "basenet.slice2.15", 128, 256, 3, 1, 1},
-    {"basenet.slice2.17", "basenet.slice2.18", 256, 256, 3, 1, 1},
-    {"basenet.slice3.20", "basenet.slice3.21", 256, 256, 3, 1, 1},
-    {"basenet.slice3.24", "basenet.slice3.25", 256, 512, 3, 1, 1},
-    {"basenet.slice3.27", "basenet.slice3.28", 512, 512, 3, 1, 1},
-    {"basenet.slice4.30", "basenet.slice4.31", 512, 512, 3, 1, 1},
-    {"basenet.slice4.34", "basenet.slice4.35", 512, 512, 3, 1, 1},
-    // s4 is the BN output, NOT its ReLU (detection.py:333)
-    {"basenet.slice4.37", "basenet.slice4.38", 512, 512, 3, 1, 0},
-    {"basenet.slice5.1", nullptr, 512, 1024, 3, 6, 0},
-    {"basenet.slice5.2", nullptr, 1024, 1024, 1, 1, 0},
-    {"upconv1.conv.0", "upconv1.conv.1", 1536, 512, 1, 1, 1},
-    {"upconv1.conv.3", "upconv1.conv.4", 512, 256, 3, 1, 1},
-    {"upconv2.conv.0", "upconv2.conv.1", 768, 256, 1, 1, 1},
-    {"upconv2.conv.3", "upconv2.conv.4", 256, 128, 3, 1, 1},
-    {"upconv3.conv.0", "upconv3.conv.1", 384, 128, 1, 1, 1},
-    {"upconv3.conv.3", "upconv3.conv.4", 128, 64, 3, 1, 1},
-    {"upconv4.conv.0", "upconv4.conv.1", 192, 64, 1, 1, 1},
-    {"upconv4.conv.3", "upconv4.conv.4", 64, 32, 3, 1, 1},
-    {"conv_cls.0", nullptr, 32, 32, 3, 1, 1},
-    {"conv_cls.2", nullptr, 32, 32, 3, 1, 1},
-    {"conv_cls.4", nullptr, 32, 16, 3, 1, 1},
-    {"conv_cls.6", nullptr, 16, 16, 1, 1, 1},
-    {"conv_cls.8", nullptr, 16, 2, 1, 1, 0},
-};
+using Spec = CraftSpec;
+constexpr auto& kSpecs = kCraftSpecs;  // load_check.h
 
 // channels of the up-sampled decoder tensor y at the head of the concat a 1x1 layer reads (detection.py:380-389)
 int fold_channels(const char* conv) {
@@ -114,6 +81,13 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
     if (nm.rfind("module.", 0) == 0) nm = nm.substr(7);
     blobs[nm] = b;
   }
+  // Validate first, change afterwards (include/kocr.h): a refused set leaves the context as it was.
+  {
+    BlobSizes sizes;
+    for (const auto& kv : blobs) sizes[kv.first] = kv.second.numel();
+    const std::string bad = craft_check_blobs(sizes);
+    if (!bad.empty()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_load_craft: " + bad);
+  }
   auto need = [&](const std::string& k, size_t numel, const Blob** out) -> int {
     auto it = blobs.find(k);
     if (it == blobs.end()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_load_craft: missing tensor " + k);
@@ -124,6 +98,9 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
   };
   if (!ctx->craft) ctx->craft = new CraftNet();
   CraftNet* net = ctx->craft;
+  // The changing phase: the network counts as not loaded until its end, so that a failure on the way (an allocation or a copy)
+  // leaves KOCR_ENOWEIGHTS behind and never a network of two weight sets.
+  net->loaded = false;
   for (const Spec& s : kSpecs) {
     const Blob *w, *b;
     KOCR_TRY(need(std::string(s.conv) + ".weight", (size_t)s.cout * s.cin * s.k * s.k, &w));
@@ -223,10 +200,17 @@ int craft_load(kocr_ctx* ctx, int n, const char* const* names, const float* cons
       const float t = (float)((double)(float)v - mean[c] * 255);
       lut[c * 256 + v] = (float)((double)t / (var[c] * 255));
     }
+  if (net->d_lut) {  // a reload: the previous table goes once no launch reads it
+    KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->release(net->d_lut);
+    net->d_lut = nullptr;
+  }
   KOCR_TRY(ctx->upload(&net->d_lut, lut));
   net->loaded = true;
   return KOCR_OK;
 }
+
+bool craft_loaded(const kocr_ctx* ctx) { return ctx->craft && ctx->craft->loaded; }
 
 void craft_free(kocr_ctx* ctx) {
   delete ctx->craft;

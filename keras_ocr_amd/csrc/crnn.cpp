@@ -18,6 +18,7 @@
 //     Add (recognition.py:305) is folded into the next projection by stacking its kernel over
 //     the [forward | backward] channel halves; Concatenate (:319) is the same buffer.
 #include "common.h"
+#include "load_check.h"
 #include "taps.h"
 #include <algorithm>
 #include <cmath>
@@ -87,11 +88,19 @@ int crnn_set_discard(kocr_ctx* ctx, int d) {
 int crnn_load(kocr_ctx* ctx, int n, const char* const* names, const float* const* data, const int64_t* shapes,
               const int* ranks) {
   std::map<std::string, Blob> blobs;
+  BlobSizes sizes;
   for (int i = 0; i < n; ++i) {
     size_t ne = 1;
     for (int d = 0; d < ranks[i]; ++d) ne *= (size_t)shapes[i * 4 + d];
     blobs[names[i]] = Blob{data[i], ne};
+    sizes[names[i]] = ne;
   }
+  // Validate first, change afterwards (include/kocr.h): a refused set leaves the context as it was -- weights, loaded, class
+  // count, label width, tables and device memory.  Nothing below this check can fail for a reason the caller's set gives.
+  int n_classes = 0;
+  bool stn = false;
+  const std::string bad = crnn_check_blobs(sizes, &n_classes, &stn);
+  if (!bad.empty()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_load_crnn: " + bad);
   auto need = [&](const std::string& k, size_t numel, const float** out) -> int {
     auto it = blobs.find(k);
     if (it == blobs.end()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_load_crnn: missing tensor " + k);
@@ -101,6 +110,23 @@ int crnn_load(kocr_ctx* ctx, int n, const char* const* names, const float* const
   };
   if (!ctx->crnn) ctx->crnn = new CrnnNet();
   CrnnNet* net = ctx->crnn;
+  // The changing phase: from here to its end the network counts as not loaded, so that a failure on the way (an allocation or a
+  // copy -- nothing else is left) leaves KOCR_ENOWEIGHTS behind and never a network of two weight sets.
+  net->loaded = false;
+  KOCR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // no launch still reads what is released below
+  for (float*& u : net->U) {
+    ctx->release(u);
+    u = nullptr;
+  }
+  if (!stn)  // a recogniser without the transformer replaces one with it: its four layers and their device copies go
+    for (auto it = net->L.begin(); it != net->L.end();) {
+      if (it->first.rfind("stn_", 0) == 0) {
+        KOCR_TRY(release_layer(ctx, it->second));
+        it = net->L.erase(it);
+      } else {
+        ++it;
+      }
+    }
   auto add = [&](const std::string& name, const float* w, int cin, int cout, int k, const float* bias, int relu,
                  const float* post_a, const float* post_b) -> int {
     ConvLayer& L = net->L[name];
@@ -140,7 +166,7 @@ int crnn_load(kocr_ctx* ctx, int n, const char* const* names, const float* const
     cin = cout;
   }
   // build_params["stn"] = False (recognition.py:243): a weight set without the localisation network -> no transformer
-  net->stn = blobs.count("stn_conv_1/kernel") != 0;
+  net->stn = stn;
   if (net->stn) {
     const float *w, *b;
     KOCR_TRY(need("stn_conv_1/kernel", (size_t)25 * 512 * 16, &w));
@@ -190,9 +216,7 @@ int crnn_load(kocr_ctx* ctx, int n, const char* const* names, const float* const
     }
   }
   {
-    auto it = blobs.find("fc_12/bias");
-    if (it == blobs.end()) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_load_crnn: missing tensor fc_12/bias");
-    net->n_classes = (int)it->second.numel;
+    net->n_classes = n_classes;
     const float *w, *b;
     KOCR_TRY(need("fc_12/kernel", (size_t)2 * UNITS * net->n_classes, &w));
     KOCR_TRY(need("fc_12/bias", net->n_classes, &b));

@@ -34,6 +34,7 @@ extern "C" int kocr_detect(kocr_ctx* ctx, const void* img, int dtype, int N, int
   if (dtype != KOCR_U8 && dtype != KOCR_F32) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detect: bad dtype");
   if (N == 0) return KOCR_OK;
   if (cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, "kocr_detect: cap must be positive");
+  if (!craft_loaded(ctx)) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, "kocr_detect: call kocr_load_craft first");
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int h2 = H / 2, w2 = W / 2;
   const size_t in_img = (size_t)H * W * 3 * (dtype == KOCR_U8 ? 1 : 4);
@@ -275,7 +276,7 @@ int pipeline_begin(kocr_ctx* ctx, const PipelineCall& c, bool sizes_ok, bool* go
     KOCR_FAIL(ctx, KOCR_EINVAL, f + ": null buffer");
   ctx->invalidate_results();  // also for the returns before the first arena is sized: N == 0 replaces the results by none
   if (c.N == 0) return KOCR_OK;
-  if (!ctx->craft) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_craft first");
+  if (!craft_loaded(ctx)) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_craft first");
   if (crnn_classes(ctx) == 0) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, f + ": call kocr_load_crnn first");
   if (!sizes_ok || c.cap <= 0) KOCR_FAIL(ctx, KOCR_EINVAL, f + ": bad sizes");
   if (ctx->orient_mode != KOCR_ORIENT_OFF)
@@ -840,6 +841,7 @@ extern "C" int kocr_craft_forward_tiled(kocr_ctx* ctx, const uint8_t* canvas, in
   TilePlan p;
   KOCR_TRY(canvas_plan(ctx, fn, N, Hc, Wc, tile, overlap, p));
   KOCR_TRY(tiled_limit(ctx, fn, p));
+  if (!craft_loaded(ctx)) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, std::string(fn) + ": call kocr_load_craft first");  // ahead of the tile gather
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const size_t cb = (size_t)N * Hc * Wc * 3, hb = page_heat_bytes(N, p), tb = tiles_bytes(N, p), thb = tile_heat_bytes(N, p);
   Staging st{ctx, ctx->pl, fn, on_device != 0};
@@ -868,6 +870,7 @@ extern "C" int kocr_detect_tiled(kocr_ctx* ctx, const uint8_t* canvas, int N, in
   TilePlan p;
   KOCR_TRY(canvas_plan(ctx, fn, N, Hc, Wc, tile, overlap, p));
   KOCR_TRY(tiled_limit(ctx, fn, p));
+  if (!craft_loaded(ctx)) KOCR_FAIL(ctx, KOCR_ENOWEIGHTS, std::string(fn) + ": call kocr_load_craft first");  // ahead of the tile gather
   KOCR_HIP(ctx, hipSetDevice(ctx->device));
   const int h2 = Hc / 2, w2 = Wc / 2;
   const size_t cb = (size_t)N * Hc * Wc * 3, hb = page_heat_bytes(N, p), tb = tiles_bytes(N, p), thb = tile_heat_bytes(N, p);

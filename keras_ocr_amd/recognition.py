@@ -275,8 +275,9 @@ class Recognizer:
             state = {k: v for k, v in state.items() if not k.startswith("stn_")}
         elif "stn_conv_1/kernel" not in state:
             raise ValueError("build_params['stn'] is True but the weights carry no stn_* tensors")
-        self._ctx.crnn_set_rnn_steps_to_discard(discard)
+        # the load first: a refused weight set must leave a shared context's label width as the recogniser serving there set it
         self._ctx.load_crnn(state)
+        self._ctx.crnn_set_rnn_steps_to_discard(discard)
         self.build_params = dict(DEFAULT_BUILD_PARAMS, **dict(build_params))
         self.model = _Model(self._ctx, probs=True)
         self.prediction_model = _Model(self._ctx, probs=False)

@@ -43,7 +43,7 @@ kocr_set_charsets kocr_charset_count kocr_set_charset kocr_get_charset kocr_set_
 kocr_get_pattern kocr_recognition_patterns kocr_set_orientation kocr_get_orientation kocr_recognition_orientation
 kocr_profile_enable kocr_profile_reset kocr_profile_report kocr_range_stats_enable kocr_range_stats_report
 kocr_debug_arena_count kocr_debug_arena_name kocr_debug_arena_stats kocr_debug_release_arenas kocr_debug_set_arena_guards
-kocr_debug_check_arena_guards kocr_debug_set_arena_poison kocr_pipeline_results_shape
+kocr_debug_check_arena_guards kocr_debug_set_arena_poison kocr_debug_memory_stats kocr_pipeline_results_shape
 """.split()
 
 DEFAULT_CRNN = (37, 2, True)
